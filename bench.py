@@ -4,6 +4,8 @@ sigmas) over B x 4 x 128 x 128 bf16 latents, north-star shape B = 256 per GPU.  
 
     python bench.py --gpus 1 --steps 200 --warmup 20
     python bench.py --config cfg3c          # headline | cfg2 | cfg3 | cfg3c | cfg4 | cfg5
+    python bench.py --full                  # + roofline, live PMC traffic, wrapper / graph-loop rates, CPU baseline
+    python bench.py --dump-outputs DIR      # + DIR/<name>.npy: what the last timed step computed
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--config cfg4]
 
@@ -15,7 +17,9 @@ schedule with launch tracing on, and the launches it emitted for the steady-stat
 shards with no collective (weak scaling: the per-GPU batch is fixed; configs 4 and 5 are DEFINED as 8-GPU shards -- B = 2048 / 8
 and 512 / 8 per GPU -- so a run at N = 8 is the BASELINE configuration itself); noise seeds are indexed by global sample id.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline keys (metric, value, unit,
+ms_per_step, ...); `--full` adds everything else the benchmark measures -- `roofline` (step-kernel time from HIP events, live
+rocprofv3 counter passes, a D2D copy reference, per-rank clocks), the eager-wrapper and graph-loop rates and `cpu_baseline`.
 """
 
 from __future__ import annotations
@@ -37,6 +41,8 @@ import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (guides/MI355X_MICROARCH.md:36)
 HBM_ACHIEVABLE_GBS = 6300.0  # what that guide measures as achievable on this part (float4 copy, "8 TB/s peak (spec); ~6.3 TB/s achievable")
+DUMP_MAX_ELEMS = 1 << 23  # --dump-outputs: at most this many values in all (32 MiB as float32)
+DUMP_SAMPLE_SEED = 0  # --dump-outputs: seed of the fixed sample of an output that does not fit
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -152,12 +158,16 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (default: the config's own)")
     ap.add_argument("--sets", type=int, default=6, help="rotating buffer sets (>= 4; raised until the footprint passes 1 GB)")
     ap.add_argument("--precondition", type=int, default=None, help="untimed conditioning steps before the warm-up (default ~80 ms worth; see the comment at its use)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline (second step-kernel region for generator configs, "
+                    "live counter passes, D2D copy), per-rank clocks, wrapper / graph-loop rates and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy "
+                    "(float32; a fixed seeded sample of each when all of them together exceed %d elements)" % DUMP_MAX_ELEMS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-traffic", action="store_true", help="skip the live rocprofv3 FETCH_SIZE / WRITE_SIZE passes (roofline.traffic falls back to the committed summary)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the live rocprofv3 FETCH_SIZE / WRITE_SIZE passes (roofline.traffic falls back to the committed summary)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="diagnostic: kernel-selection switches (skr_set_tuning) applied before anything is launched")
     ap.add_argument("--drift", type=int, default=0, help="diagnostic: run this many steps back to back and print the average step time of every block of 50 (then exit)")
-    ap.add_argument("--no-extras", action="store_true", help="no wrapper-rate, graph-loop and memcpy keys (used by the counter passes)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no wrapper-rate, graph-loop and memcpy keys (used by the counter passes)")
     return ap.parse_args()
 
 
@@ -299,6 +309,27 @@ class _HipEvent:
         if self._hip.hipEventElapsedTime(ctypes.byref(ms), self.handle, other.handle) != 0:
             raise RuntimeError("hipEventElapsedTime failed")
         return ms.value
+
+
+def dump_outputs(outputs: dict[str, torch.Tensor], out_dir: str) -> None:
+    """--dump-outputs: every output of the last timed step as out_dir/<name>.npy, float32 (float64 stays float64).  When all of them
+    together hold more than DUMP_MAX_ELEMS values, each is represented by the same number of values at fixed, distinct, sorted
+    positions -- one drawn by a seeded CPU generator in each of that many equal bands of the output -- the same positions for the
+    same arguments, so two builds can be compared value for value."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in outputs.values())
+    per = DUMP_MAX_ELEMS // max(len(outputs), 1)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        if total > DUMP_MAX_ELEMS and flat.numel() > per:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            bounds = torch.arange(per + 1, dtype=torch.float64).mul_(flat.numel() / per).floor_().long()  # band k = [bounds[k], bounds[k + 1])
+            idx = bounds[:-1] + (torch.rand(per, generator=g, dtype=torch.float64) * (bounds[1:] - bounds[:-1])).long()
+            flat = flat[idx.to(flat.device)]
+        host = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), host)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -544,7 +575,7 @@ def measure_traffic(wl: Workload, batch: int, steps: int = 40) -> tuple[float | 
             out_dir = os.path.join(tmp, name)
             cmd = [exe, "--pmc", name, "--kernel-trace", "-d", out_dir, "-o", "prof", "--output-format", "csv", "--",
                    sys.executable, os.path.abspath(__file__), "--config", wl.name, "--steps", str(steps), "--warmup", "2", "--precondition", "0",
-                   "--batch", str(batch), "--no-cpu-baseline", "--no-traffic", "--no-extras"]  # fmt: skip
+                   "--batch", str(batch), "--full", "--no-cpu-baseline", "--no-traffic", "--no-extras"]  # fmt: skip
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "TORCHELASTIC_RUN_ID", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "LOCAL_WORLD_SIZE")}
             env["TMPDIR"] = "/tmp"
             proc = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=180)
@@ -633,6 +664,7 @@ def main() -> None:
     g = torch.Generator(device=dev).manual_seed(99 + rank)
     order = [s for s in wl.steady]
     plan_calls = []  # one entry per (steady step, buffer set) in cycling order
+    plan_outs = []  # per entry of plan_calls: the tensors its launches write, by name (--dump-outputs)
     held = []
     bufsets: list[dict[tuple[int, int], torch.Tensor]] = []
     for k in range(nsets):
@@ -648,6 +680,8 @@ def main() -> None:
                     t = empty_output((n,), dt, dev)
                     if sid not in written:
                         t.copy_(torch.randn(n, device=dev, generator=g))
+                    else:  # (a step may read a slot another step writes before that step has run: never uninitialised memory)
+                        t.zero_()
                 else:
                     t = torch.randn(n, device=dev, generator=g).to(dt)
                 bufs[key] = t
@@ -665,6 +699,12 @@ def main() -> None:
             calls.append((ctypes.byref(l.plan), ptrs, buf(l.out0).data_ptr() if l.out0 is not None else None, buf(l.out1).data_ptr() if l.out1 is not None else None,
                           l.seeds.data_ptr() if l.seeds is not None else None, patch))  # fmt: skip
         plan_calls.append((calls, rec.noise_step if rec.drawn is not None else None))
+        outs = {}
+        for j, l in enumerate(rec.launches):
+            for o, sid in enumerate((l.out0, l.out1)):
+                if sid is not None:
+                    outs[f"out{o}" if len(rec.launches) == 1 else f"stage{j}_out{o}"] = buf(sid)
+        plan_outs.append(outs)
 
     stream = torch.cuda.current_stream(dev).cuda_stream
     launches_per_step = wl.calls
@@ -780,10 +820,12 @@ def main() -> None:
     # rocprofv3's per-kernel average agrees with; K = 1 has no such window.
     span_ms = e0.elapsed_time(e1) / args.steps
     steady_ms = e_first.elapsed_time(e1) / (args.steps - marked[0]) if args.steps > marked[0] > 0 else span_ms
+    if args.dump_outputs and rank == 0:  # before anything else is launched on the rotating buffer sets
+        dump_outputs(plan_outs[(args.warmup + args.steps - 1) % len(plan_calls)], args.dump_outputs)
     # configs with a noise generator: a second region with the step launches alone (noise tensors already resident), after the
     # contract's region -- the 8(d) roofline of those configs is stated for the step kernel, "generator reported separately"
     kernels_ms = None
-    if generator is not None:
+    if generator is not None and args.full:
         run(max(args.warmup, 2), draw=False)
         f0.record()
         run(args.steps, offset=args.warmup, draw=False)
@@ -792,11 +834,11 @@ def main() -> None:
         kernels_ms = f0.elapsed_time(f1) / args.steps
 
     coll_dev = dev if backend == "nccl" else None
-    ranks = rank_spread({"wall_us_per_step": wall * 1e6 / args.steps, "span_us_per_step": span_ms * 1e3, "steady_us_per_step": steady_ms * 1e3}, dist, coll_dev)
+    ranks = rank_spread({"wall_us_per_step": wall * 1e6 / args.steps, "span_us_per_step": span_ms * 1e3, "steady_us_per_step": steady_ms * 1e3}, dist, coll_dev) if args.full else None
     vals = max_over_ranks([wall, span_ms, steady_ms, kernels_ms or 0.0], dist, coll_dev)  # the slowest rank defines the step time
-    wall, span_ms, steady_ms, kernels_ms = vals[0], vals[1], vals[2], (vals[3] if generator is not None else None)
+    wall, span_ms, steady_ms, kernels_ms = vals[0], vals[1], vals[2], (vals[3] if kernels_ms is not None else None)
 
-    extras = rank == 0 and not args.no_extras
+    extras = rank == 0 and args.full and not args.no_extras
     wrapper = wrapper_rate(wl, batch, dev, shard) if extras else None
 
     # streaming reference point of this box: runtime device-to-device copy of 512 MiB (read + write
@@ -818,66 +860,6 @@ def main() -> None:
 
     if rank == 0:
         steps_per_s = aggregate_rate(args.steps, world, wall)
-        algo_bytes = numel * wl.bytes_per_elem
-        roof_ms = kernels_ms if kernels_ms is not None else span_ms  # the step kernels' own time
-        achieved = algo_bytes / (roof_ms * 1e-3) / 1e9
-        steady = algo_bytes / (steady_ms * 1e-3) / 1e9
-        if args.no_traffic:
-            traffic, traffic_source, breakdown = None, "skipped (--no-traffic)", {}
-        else:
-            traffic, traffic_source, breakdown = measure_traffic(wl, batch, steps=40 if not heavy else 12)
-        if traffic is None:
-            committed, where = load_traffic(wl)
-            traffic, traffic_source = committed, f"{where}; live: {traffic_source}"
-        step_needle = wl.pmc_kernels[0][0]
-        roofline = {
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "clock": ("HIP events around all K solver steps on the launch stream (cold-queue start of the region included)" if kernels_ms is None else
-                      "HIP events around K solver steps' STEP launches alone (noise tensors resident), a second region behind the contract's; SURVEY 8(d) states this config's bytes for the step kernel, generator separately (see whole_step)"),
-            "us_per_step": roof_ms * 1e3,
-            "us_per_launch": roof_ms * 1e3 / launches_per_step,
-            "launches_per_step": launches_per_step,
-            "achievable_peak": HBM_ACHIEVABLE_GBS,  # guides/MI355X_MICROARCH.md: ~6.3 TB/s achievable of the 8 TB/s spec
-            "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
-            "steady_state": {  # steps 2..K only (what rocprofv3's per-kernel average of the same command shows)
-                "us_per_step": steady_ms * 1e3,
-                **({"achieved": steady, "frac": steady / HBM_PEAK_GBS} if kernels_ms is None else {}),
-            },
-            "wall_clock": {  # the host clock `value` is computed from: region start/stop cost spread over K steps
-                "us_per_step": wall * 1e6 / args.steps,
-                "frac": algo_bytes * args.steps / wall / 1e9 / HBM_PEAK_GBS,
-            },
-            "traffic": breakdown.get(step_needle, traffic) if breakdown else traffic,
-            "traffic_source": traffic_source,
-            # the same time priced on the bytes the step kernels actually moved (PMC): differs from `frac` where the implementation moves
-            # fewer bytes than SURVEY 8(d) counts (cfg5: stored derivatives are read as 2 B, 8(d) counts verbatim (x, out) pairs at 4 B)
-            "frac_on_measured_traffic": None,
-            "algorithmic_bytes_per_step": algo_bytes,
-            "algorithmic_bytes_per_element": wl.bytes_per_elem,
-            "kernel": wl.kernel,
-            "measured_d2d_memcpy": copy_gbs,  # hipMemcpy D2D of 512 MiB on this box, read+write GB/s
-            # every rank's own clocks (min / max / per rank): each wall is read after that rank's own synchronise, before the closing barrier
-            "ranks": ranks,
-        }
-        if roofline["traffic"]:
-            roofline["frac_on_measured_traffic"] = roofline["traffic"] / (roof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        if launches_per_step == 1:
-            roofline["algorithmic_bytes_per_launch"] = algo_bytes
-        if wl.mix_ceiling:
-            roofline["mix_ceiling"] = wl.mix_ceiling  # a no-arithmetic kernel with this launch's traffic mix, same buffers
-        if kernels_ms is not None:
-            roofline["whole_step"] = {  # generator launches + step launches: what `value` counts
-                "us_per_step": span_ms * 1e3,
-                "generator_us_per_step": (span_ms - kernels_ms) * 1e3,
-                "frac_of_step_bytes": algo_bytes / (span_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "traffic_all_kernels": traffic,
-                "traffic_by_kernel": breakdown or None,
-                "generator_note": wl.generator_bytes_note,
-            }
         out = {
             "metric": wl.metric,
             "value": steps_per_s,
@@ -906,14 +888,75 @@ def main() -> None:
                 "precondition_steps": precondition,
                 "parallelism": f"batch-shard x{world}, no collective",
             },
-            "roofline": roofline,
-            "wrapper_steps_per_s": wrapper,
         }
-        if wl.name == "headline":
-            out["graph_loop_cfg2"] = None if args.no_extras else graph_loop_rate(dev)
-        if not args.no_cpu_baseline:
-            # host-only work: at N > 1 rank 0 times it (shorter) while the other ranks wait at the closing barrier
-            out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds if world == 1 else min(args.cpu_seconds, 8.0), world)
+        if args.full:  # everything beyond the headline figure
+            algo_bytes = numel * wl.bytes_per_elem
+            roof_ms = kernels_ms if kernels_ms is not None else span_ms  # the step kernels' own time
+            achieved = algo_bytes / (roof_ms * 1e-3) / 1e9
+            steady = algo_bytes / (steady_ms * 1e-3) / 1e9
+            if args.no_traffic:
+                traffic, traffic_source, breakdown = None, "skipped (--no-traffic)", {}
+            else:
+                traffic, traffic_source, breakdown = measure_traffic(wl, batch, steps=40 if not heavy else 12)
+            if traffic is None:
+                committed, where = load_traffic(wl)
+                traffic, traffic_source = committed, f"{where}; live: {traffic_source}"
+            step_needle = wl.pmc_kernels[0][0]
+            roofline = {
+                "bound": "hbm",
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "clock": ("HIP events around all K solver steps on the launch stream (cold-queue start of the region included)" if kernels_ms is None else
+                          "HIP events around K solver steps' STEP launches alone (noise tensors resident), a second region behind the contract's; SURVEY 8(d) states this config's bytes for the step kernel, generator separately (see whole_step)"),
+                "us_per_step": roof_ms * 1e3,
+                "us_per_launch": roof_ms * 1e3 / launches_per_step,
+                "launches_per_step": launches_per_step,
+                "achievable_peak": HBM_ACHIEVABLE_GBS,  # ~6.3 TB/s achievable (float4 copy) of the 8 TB/s spec
+                "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
+                "steady_state": {  # steps 2..K only (what rocprofv3's per-kernel average of the same command shows)
+                    "us_per_step": steady_ms * 1e3,
+                    **({"achieved": steady, "frac": steady / HBM_PEAK_GBS} if kernels_ms is None else {}),
+                },
+                "wall_clock": {  # the host clock `value` is computed from: region start/stop cost spread over K steps
+                    "us_per_step": wall * 1e6 / args.steps,
+                    "frac": algo_bytes * args.steps / wall / 1e9 / HBM_PEAK_GBS,
+                },
+                "traffic": breakdown.get(step_needle, traffic) if breakdown else traffic,
+                "traffic_source": traffic_source,
+                # the same time priced on the bytes the step kernels actually moved (PMC): differs from `frac` where the implementation moves
+                # fewer bytes than SURVEY 8(d) counts (cfg5: stored derivatives are read as 2 B, 8(d) counts verbatim (x, out) pairs at 4 B)
+                "frac_on_measured_traffic": None,
+                "algorithmic_bytes_per_step": algo_bytes,
+                "algorithmic_bytes_per_element": wl.bytes_per_elem,
+                "kernel": wl.kernel,
+                "measured_d2d_memcpy": copy_gbs,  # hipMemcpy D2D of 512 MiB on this box, read+write GB/s
+                # every rank's own clocks (min / max / per rank): each wall is read after that rank's own synchronise, before the closing barrier
+                "ranks": ranks,
+            }
+            if roofline["traffic"]:
+                roofline["frac_on_measured_traffic"] = roofline["traffic"] / (roof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+            if launches_per_step == 1:
+                roofline["algorithmic_bytes_per_launch"] = algo_bytes
+            if wl.mix_ceiling:
+                roofline["mix_ceiling"] = wl.mix_ceiling  # a no-arithmetic kernel with this launch's traffic mix, same buffers
+            if kernels_ms is not None:
+                roofline["whole_step"] = {  # generator launches + step launches: what `value` counts
+                    "us_per_step": span_ms * 1e3,
+                    "generator_us_per_step": (span_ms - kernels_ms) * 1e3,
+                    "frac_of_step_bytes": algo_bytes / (span_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "traffic_all_kernels": traffic,
+                    "traffic_by_kernel": breakdown or None,
+                    "generator_note": wl.generator_bytes_note,
+                }
+            out["roofline"] = roofline
+            out["wrapper_steps_per_s"] = wrapper
+            if wl.name == "headline":
+                out["graph_loop_cfg2"] = None if args.no_extras else graph_loop_rate(dev)
+            if not args.no_cpu_baseline:
+                # host-only work: at N > 1 rank 0 times it (shorter) while the other ranks wait at the closing barrier
+                out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds if world == 1 else min(args.cpu_seconds, 8.0), world)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()  # rank 0's informational extras (wrapper rate, graph loop, counters, CPU baseline) are done: every rank leaves together

@@ -78,9 +78,49 @@ def tables():
     return json.load(open(os.path.join(GOLDEN, "tables.json")))
 
 
+# ---- host numerics: MKL's code branch -------------------------------------------------------------------------------------
+# torch's CPU FFT and vector math run on MKL, whose last bits differ between its AVX-512 branch (Intel CPUs, where the fixtures were
+# recorded) and the generic branch it takes on other CPUs.  mkl_generic.npz holds the reference's own results recorded on the generic
+# branch (tools/make_mkl_overlay.py) for the cases a non-Intel host reproduces from that recording -- the FFT-based noise -- and a
+# canary transform recorded on both branches.  load_npz hands those values over, bit for bit, on a host whose canary matches the
+# generic branch; every other host gets the fixtures as recorded.
+MKL_GENERIC = "mkl_generic.npz"
+_mkl_overlay: list = []
+
+
+def host_fft_canary() -> np.ndarray:
+    "a real 3-D FFT of fixed, RNG-free input on this host's torch CPU path"
+    import torch
+
+    x = (torch.arange(4 * 16 * 16, dtype=torch.float64) * 0.6180339887498949).remainder(1.0).to(torch.float32).reshape(4, 16, 16)
+    return torch.view_as_real(torch.fft.rfftn(x)).numpy()
+
+
+def host_mkl_generic() -> bool:
+    "this host's MKL takes the generic branch: its canary transform matches that branch's recording (and not the fixtures' own)"
+    if not _mkl_overlay:
+        with np.load(os.path.join(GOLDEN, MKL_GENERIC)) as z:
+            blob = {k: z[k] for k in z.files}
+        generic = np.array_equal(host_fft_canary(), blob["canary/generic"]) and not np.array_equal(blob["canary/generic"], blob["canary/recorded"])
+        _mkl_overlay.append((generic, {k: v for k, v in blob.items() if "::" in k} if generic else {}))
+    return _mkl_overlay[0][0]
+
+
+def mkl_overlay() -> dict:
+    "{'<fixture file>::<key>': generic-branch value} when this host's MKL takes the generic branch, else {}"
+    host_mkl_generic()
+    return _mkl_overlay[0][1]
+
+
 def load_npz(name: str) -> dict:
     with np.load(os.path.join(GOLDEN, name)) as z:
-        return {k: z[k] for k in z.files}
+        blob = {k: z[k] for k in z.files}
+    for key, value in mkl_overlay().items():
+        fname, _, k = key.partition("::")
+        if fname == name:
+            assert k in blob, key
+            blob[k] = value
+    return blob
 
 
 def eq_nan(a, b) -> bool:

@@ -94,5 +94,5 @@ def test_round5_lines_of_every_config_follow_the_contract():
 def test_bench_cli_parses_without_a_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--full", "--dump-outputs"):
         assert flag in out.stdout

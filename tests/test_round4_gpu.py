@@ -280,7 +280,7 @@ def test_bench_line_of_a_config_on_the_device(config):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", config, "--steps", "12", "--warmup", "3", "--precondition", "12", "--sets", "4",
-                          "--no-cpu-baseline", "--no-traffic", "--no-extras"], capture_output=True, text=True, timeout=600)  # fmt: skip
+                          "--full", "--no-cpu-baseline", "--no-traffic", "--no-extras"], capture_output=True, text=True, timeout=600)  # fmt: skip
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-500:]  # ONE line on stdout
@@ -295,6 +295,51 @@ def test_bench_line_of_a_config_on_the_device(config):
     assert ("whole_step" in r) == (config != "headline")
     if config != "headline":
         assert r["whole_step"]["us_per_step"] > r["us_per_step"] and r["whole_step"]["generator_us_per_step"] > 0
+
+
+@pytest.mark.parametrize("config", ["headline", "cfg3c"])
+def test_plain_bench_line_and_its_dumped_outputs(config, tmp_path):
+    """`python bench.py --config <c> --dump-outputs DIR` without --full: one JSON line with the headline keys and none of the --full
+    ones, and the outputs of the last timed step in DIR as finite float32 arrays, within the dump's size limit.  The same arguments
+    dump the same bits; so does a split of the same launches into one more warm-up and one fewer timed step (the last timed step
+    is the same launch), while one more timed step dumps a different step."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    def run(tag, steps, warmup):
+        out_dir = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", config, "--steps", str(steps), "--warmup", str(warmup), "--precondition", "12",
+                              "--sets", "4", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)  # fmt: skip
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout[-500:]
+        files = sorted(os.listdir(out_dir))
+        assert files == (["out0.npy"] if config == "headline" else ["out0.npy", "out1.npy"]), files
+        return json.loads(lines[0]), [np.load(out_dir / f) for f in files]
+
+    d, arrays = run("a", 7, 2)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in d, key
+    assert not {"roofline", "cpu_baseline", "wrapper_steps_per_s", "graph_loop_cfg2"} & set(d)
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["config"]["name"] == config and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    numel = d["config"]["per_gpu_batch"] * (4 * 128 * 128 if config == "headline" else 16 * 128 * 128)
+    assert sum(a.size for a in arrays) <= bench.DUMP_MAX_ELEMS
+    for a in arrays:
+        assert a.dtype == np.float32 and a.size == min(numel, bench.DUMP_MAX_ELEMS // len(arrays)) and np.isfinite(a).all() and a.std() > 0
+    again = run("again", 7, 2)[1]
+    shifted = run("shifted", 6, 3)[1]
+    longer = run("longer", 8, 2)[1]
+    for k, a in enumerate(arrays):
+        assert np.array_equal(a, again[k]) and np.array_equal(a, shifted[k]), k
+        assert not np.array_equal(a, longer[k]), k
 
 
 def test_two_threads_on_two_streams_do_not_disturb_each_other(dev):

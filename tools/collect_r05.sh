@@ -18,7 +18,7 @@ has() { case " $PARTS " in *" $1 "*) return 0;; *) return 1;; esac; }
 T="timeout -k 10"
 CONFIGS="${R5_CONFIGS:-headline cfg2 cfg3 cfg3c cfg4 cfg5}"   # R5_CONFIGS="cfg5" refreshes one configuration
 stats_csv() { ls $1/*kernel_stats.csv $1/*/*kernel_stats.csv 2>/dev/null | head -1; }
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 if has bench; then
   case " $CONFIGS " in *" headline "*)
     $T 400 $B > $O/profiles/r05_bench_line.json 2> $O/bench.err
@@ -104,14 +104,14 @@ if has rehearsal; then
     echo "# (SKR_BENCH_DEVICE=0 SKR_BENCH_BACKEND=gloo).  A rehearsal of the N > 1 code path -- shards through BatchShard.from_env, opening barrier, every rank's wall read after ITS OWN"
     echo "# synchronise and before the closing barrier (sharding.TimedRegion), MAX over ranks, per-rank clocks in roofline.ranks -- NOT a scaling number: the two ranks share one GPU."
     for c in headline cfg4; do
-      (cd $R && SKR_BENCH_DEVICE=0 SKR_BENCH_BACKEND=gloo $T 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --config $c --no-traffic 2>/dev/null | python3 -c "
+      (cd $R && SKR_BENCH_DEVICE=0 SKR_BENCH_BACKEND=gloo $T 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --config $c --full --no-traffic 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']
 print(json.dumps({k: d[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'scaling')} | {'config': {k: d['config'][k] for k in ('name', 'global_batch', 'per_gpu_batch', 'parallelism')}, 'roofline.us_per_step': r['us_per_step'], 'roofline.ranks': r['ranks'], 'cpu_baseline': d.get('cpu_baseline')}))")
     done
     echo "# the RCCL code path itself (backend nccl: communicator, barriers, the per-rank all_gather) with ONE rank under torch.distributed.run:"
-    (cd $R && $T 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --steps 20 --warmup 5 --no-traffic 2>/dev/null | python3 -c "
+    (cd $R && $T 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-traffic 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

@@ -2,8 +2,8 @@
 """Generate the measured-number tables of DESIGN.md / README.md from the COMMITTED evidence files, so that no quoted figure can
 drift from the file it cites ("DESIGN quotes numbers the committed profile does not contain").
 
-  inputs : profiles/r05_bench_line[_k20|_<config>].json   (one JSON line per `python bench.py [--config <c>]`)
-           profiles/r05_kernel_stats_<config>.csv          (tools/kernel_stats.py over `rocprofv3 --kernel-trace --stats -- python3 bench.py --config <c> ...`)
+  inputs : profiles/r05_bench_line[_k20|_<config>].json   (one JSON line per `python bench.py --full [--config <c>]`)
+           profiles/r05_kernel_stats_<config>.csv          (tools/kernel_stats.py over `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config <c> ...`)
   output : the text between  <!-- GENERATED:<name> BEGIN ... -->  and  <!-- GENERATED:<name> END -->  in DESIGN.md and README.md
 
 usage:  python tools/design_tables.py            rewrite the blocks in place
@@ -141,7 +141,7 @@ def table_readme() -> str:
         return "(no committed bench line yet)"
     r = d["roofline"]
     out = [
-        f"* headline (`python bench.py`, {d['steps']} steps): **{fmt(d['value'])} steps/s**, {fmt(r['us_per_step'], 2)} µs per launch = {fmt(r['achieved'] / 1e3, 2)} TB/s algorithmic = "
+        f"* headline (`python bench.py --full`, {d['steps']} steps): **{fmt(d['value'])} steps/s**, {fmt(r['us_per_step'], 2)} µs per launch = {fmt(r['achieved'] / 1e3, 2)} TB/s algorithmic = "
         f"**{fmt(100 * r['frac'], 1)} %** of the 8 TB/s spec ({fmt(100 * r['wall_clock']['frac'], 1)} % by the wall clock `value` is computed from); PMC traffic ÷ algorithmic bytes = {fmt(r['traffic'] / r['algorithmic_bytes_per_step'], 4)}"
     ]
     if k is not None:

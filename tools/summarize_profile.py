@@ -56,7 +56,7 @@ out = {
     "hbm_bytes_per_launch": 2 * statistics.mean(fetch) * 1024 + statistics.mean(write) * 1024,
     "algorithmic_bytes_per_launch": 256 * 4 * 128 * 128 * 10,
     "correction": "FETCH_SIZE x2 (gfx950 counts 128-B requests as 64 B on wide coalesced streams), WRITE_SIZE x1, KiB -> bytes",
-    "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline (one counter per pass; B=256 launches only)",
+    "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline (one counter per pass; B=256 launches only)",
 }
 json.dump(out, open(f"{OUT}/{round_tag}_pmc_traffic.json", "w"), indent=1)
 print(json.dumps(out, indent=1))

@@ -298,7 +298,9 @@ int skr_power_blend(void* out, int32_t out_dtype, const void* a, int32_t a_dtype
 
 /* Diagnostics counters of this process (tests assert that a shape did NOT go to the vendor FFT): "hipfft_plans" = hipFFT plan pairs
  * created so far, "hipfft_execs" = forward hipFFT transforms run so far, "own_fft_execs" = forward N-D transforms run by the library's
- * own any-length kernels so far; -1 for an unknown key. */
+ * own any-length kernels so far, "colored_inv128_launches" = launches of the persistent 128 x 128 inverse kernel of Colored noise so far,
+ * "colored_inv128_ticketed" = those of its launches in which at least one plane was claimed from the device ticket (more than two planes
+ * per block, ticket not disabled); -1 for an unknown key. */
 int64_t skr_stat(const char* key);
 
 int skr_abi_version(void);

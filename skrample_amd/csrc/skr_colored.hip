@@ -18,6 +18,7 @@
 // Reductions are per block into fixed slots and summed in a fixed order (bit-reproducible, no atomics).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <stdlib.h>
 
 #include "skr_device.h"
@@ -1635,10 +1636,16 @@ static int64_t inverse128_blocks(int32_t d2, int32_t d3, int32_t out_dtype, int6
   return blocks > n_planes ? n_planes : blocks;
 }
 
+// skr_stat("colored_inv128_launches" / "colored_inv128_ticketed"): launches of colored_inverse128, and those of them in which at least one
+// plane was dealt from the device ticket (every block's first two planes are fixed)
+std::atomic<int64_t> g_inv128_launches{0}, g_inv128_ticketed{0};
+
 static int launch_inverse128(ColoredArgs a, int32_t out_dtype, int64_t n_planes, float* factors /* [batch] workspace, unused when a.raw */, hipStream_t s) {
   if (a.d2 != 128 || a.d3 != 128 || n_planes < 1 || (!a.raw && factors == nullptr) || (out_dtype != SKR_BF16 && out_dtype != SKR_F16 && out_dtype != SKR_F32)) return -1;
   const int64_t blocks = inverse128_blocks(a.d2, a.d3, out_dtype, n_planes);
   if (blocks < 1) return -1;
+  ++g_inv128_launches;
+  if (a.ticket != nullptr && n_planes > 2 * blocks) ++g_inv128_ticketed;
   const size_t lds = sizeof(float2) * (64 * 129 + 128);
   a.factors = factors;
 #ifdef SKR_COLORED_TRACE

@@ -446,6 +446,7 @@ __global__ __launch_bounds__(256) void selftest_check_inverse(const SelfTest t) 
 
 // (skr_colored.hip) rfft2 / irfft2 of independent planes on the LDS plane kernels
 namespace skr {
+extern std::atomic<int64_t> g_inv128_launches, g_inv128_ticketed;
 int colored_planes(int mode, float2* spec, double* plane_partials, float* real_out, const uint64_t* seeds, uint64_t stream_id,
                    int64_t batch, int64_t planes, int32_t d2, int32_t d3, hipStream_t s);
 }
@@ -724,5 +725,7 @@ extern "C" int64_t skr_stat(const char* key) {
   if (!strcmp(key, "hipfft_plans")) return g_hipfft_plans;
   if (!strcmp(key, "hipfft_execs")) return g_hipfft_execs;
   if (!strcmp(key, "own_fft_execs")) return g_own_execs;
+  if (!strcmp(key, "colored_inv128_launches")) return skr::g_inv128_launches;
+  if (!strcmp(key, "colored_inv128_ticketed")) return skr::g_inv128_ticketed;
   return -1;
 }

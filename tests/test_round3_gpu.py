@@ -26,6 +26,7 @@ import skrample_amd.scheduling as PS
 from skr_oracle import rk as OK
 from skr_oracle import samplers as OA
 from skr_oracle import schedules as OS
+from skr_oracle import noise as ON
 from skr_oracle import wrapper as OW
 from skrample_amd import _hip
 from skrample_amd.common import Step
@@ -79,8 +80,8 @@ def test_cfg5_rkultra6_pyramid_vs_oracle_small(dev):
 
 FULL = {
     # name: (wrapper, oracle, noise kind, props, per-GPU shape, calls)
-    "cfg5_rkultra6_sde_pyramid": (cfg5_wrapper, lambda: OW.RKDriver(OK.pick_tableau(6), OS.scaled(), "eps", "data", 1.0), PN.Pyramid, PN.PyramidProps(), (64, 4, 256, 256), 12),
-    "cfg3_unipc3_sde_flow_colored": (cfg3_wrapper, lambda: OW.StepDriver(OA.make("unipc", 3, eta=1), OS.linear(), "flow"), PN.Colored, PN.ColoredProps(), (256, 16, 128, 128), 5),
+    "cfg5_rkultra6_sde_pyramid": (cfg5_wrapper, lambda compute=torch.float32: OW.RKDriver(OK.pick_tableau(6), OS.scaled(), "eps", "data", 1.0, compute=compute), PN.Pyramid, PN.PyramidProps(), (64, 4, 256, 256), 12),
+    "cfg3_unipc3_sde_flow_colored": (cfg3_wrapper, lambda compute=torch.float32: OW.StepDriver(OA.make("unipc", 3, eta=1), OS.linear(), "flow", compute=compute), PN.Colored, PN.ColoredProps(), (256, 16, 128, 128), 5),
 }
 
 
@@ -88,7 +89,13 @@ FULL = {
 def test_full_size_configs_with_their_noise(name, dev):
     """The BASELINE configs that name a noise generator, at their full per-GPU size and WITH that generator: determinism, and the
     oracle (teacher-forced) on three samples, fed the tensors a three-sample generator with the same seeds realises -- a sample's
-    noise depends on nothing but its own seed (tests/test_noise_gpu.py::test_generators_full_size_properties)."""
+    noise depends on nothing but its own seed (tests/test_noise_gpu.py::test_generators_full_size_properties); then the oracle in float64
+    on the device over the WHOLE batch, teacher-forced with the same inputs and fed the noise the full-batch generator draws -- the noise
+    the step consumed, 16-bit as the wrapper draws it.  Colored: that draw is first held, every sample, to the float64 colorize of
+    PN.Random's white noise (tests/test_colored_whole_batch_gpu.py) at that module's bar.  (Feeding the step reference the float64
+    colorize itself, rounded to 16 bits, would not do: where the kernel's fp32 value and the float64 one straddle a bf16 rounding
+    boundary the two draws differ in the last place, and the step's noise coefficient carries that difference past one last-place
+    unit of a result that is a cancellation residue.)  Pyramid parity stays in tests/test_noise_gpu.py: here the step is checked."""
     mk_w, mk_o, kind, props, shape, calls = FULL[name]
     B, steps = shape[0], 20
     gd = torch.Generator(device=dev).manual_seed(977)
@@ -97,20 +104,24 @@ def test_full_size_configs_with_their_noise(name, dev):
     seeds = [4200 + i for i in range(B)]
     idx = [0, B // 2, B - 1]
 
-    def run():
+    def run(keep=False):
         w = mk_w()
         w.set_timesteps(steps)
-        cur, ins, res = x, [], []
+        cur, ins, res, whole = x, [], [], []
         for i in range(calls):
             o_ = (outs[i % 2] * 0.25 + cur * 0.5).bfloat16()
             ins.append((cur[idx].cpu(), o_[idx].cpu()))
+            if keep:
+                whole.append((cur, o_))
             cur = w.step(o_, w.timesteps[i], cur, generator=seeds, return_dict=False)[0]
             res.append(cur[idx].cpu())
+            if keep:
+                whole[-1] += (cur,)
             del o_
-        return ins, res, w
+        return ins, res, w, whole
 
-    ins, full, w = run()
-    _, again, _ = run()
+    ins, full, w, whole = run(keep=True)
+    _, again, _, _ = run()
     for f, a in zip(full, again):
         assert torch.equal(f, a) and torch.isfinite(f.float()).all()
     torch.cuda.empty_cache()
@@ -126,6 +137,34 @@ def test_full_size_configs_with_their_noise(name, dev):
         else:
             ref = o.step(oin, o.timesteps[i], xin, noise=shadow.generate(Step.from_int(i, steps)).cpu())[0]
         assert_close(full[i], ref, torch.bfloat16, f"{name} call {i}", flips=0.10)
+    del shadow
+    torch.cuda.empty_cache()
+
+    o64 = mk_o(compute=torch.float64)
+    o64.set_timesteps(steps)
+    gen = PN.BatchTensorNoise.from_batch_inputs(kind, shape[1:], seeds, props=props, dtype=torch.bfloat16)
+    white = PN.BatchTensorNoise.from_batch_inputs(PN.Random, shape[1:], seeds, dtype=torch.float32) if kind is PN.Colored else None
+
+    def noise_all(step):
+        got = gen.generate(step)
+        if white is not None:
+            from test_colored_whole_batch_gpu import assert_every_sample, colorize64
+
+            kw = dict(color_start=props.color_start, color_end=props.color_end, color_curve=props.color_curve)
+            assert_every_sample(got, colorize64(white.generate(None), ON.colored_exponent(step, **kw), props.energy, dev), f"{name}: the draw at {step}")
+        return got.double()
+
+    for i in range(calls):
+        xin, oin, res = whole[i]
+        if isinstance(o64, OW.RKDriver):
+            ref = o64.step(oin, o64.timesteps[i], xin, noise_fn=lambda step=None: noise_all(step))
+        else:
+            ref = o64.step(oin, o64.timesteps[i], xin, noise=noise_all(Step.from_int(i, steps)))[0]
+        assert ref.dtype == torch.bfloat16 and ref.device == res.device
+        assert_close(res, ref, torch.bfloat16, f"{name} call {i}, whole batch vs float64", flips=0.10)
+        del ref
+    del o64, gen, whole
+    torch.cuda.empty_cache()
 
 
 DEVICE_TIMESTEP_LOOPS = {

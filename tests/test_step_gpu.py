@@ -24,6 +24,7 @@ from skr_oracle import samplers as OA
 from skr_oracle import schedules as OS
 from skr_oracle import wrapper as OW
 from skrample_amd import _hip
+from skrample_amd.pytorch import noise as PN
 from skrample_amd.sampling import lazy
 from skrample_amd.sampling import models as PM
 from skrample_amd.sampling import structured as PT
@@ -1367,31 +1368,31 @@ FULL_SIZE = {
     # name: (wrapper factory, oracle factory, shape per GPU, calls)
     "cfg2_dpm2_sde_karras": (  # BASELINE config 2 as written: B = 64 on one GPU
         lambda: PD.SkrampleWrapperScheduler(PT.DPM(order=2, stochasticity=1), PS.Karras(PS.Scaled())),
-        lambda n: OW.StepDriver(OA.make("dpm", 2, eta=1), OS.karras(OS.scaled(), steps=n), "eps"),
+        lambda n, compute=torch.float32: OW.StepDriver(OA.make("dpm", 2, eta=1), OS.karras(OS.scaled(), steps=n), "eps", compute=compute),
         (64, 4, 128, 128),
         6,
     ),
     "headline_dpm2_sde_karras_b256": (  # the north-star shape of the same config
         lambda: PD.SkrampleWrapperScheduler(PT.DPM(order=2, stochasticity=1), PS.Karras(PS.Scaled())),
-        lambda n: OW.StepDriver(OA.make("dpm", 2, eta=1), OS.karras(OS.scaled(), steps=n), "eps"),
+        lambda n, compute=torch.float32: OW.StepDriver(OA.make("dpm", 2, eta=1), OS.karras(OS.scaled(), steps=n), "eps", compute=compute),
         (256, 4, 128, 128),
         5,
     ),
     "cfg3_unipc3_sde_flow": (
         lambda: PD.SkrampleWrapperScheduler(PT.UniPC(order=3, stochasticity=1), PS.Linear(), PM.FlowModel()),
-        lambda n: OW.StepDriver(OA.make("unipc", 3, eta=1), OS.linear(), "flow"),
+        lambda n, compute=torch.float32: OW.StepDriver(OA.make("unipc", 3, eta=1), OS.linear(), "flow", compute=compute),
         (256, 16, 128, 128),
         5,
     ),
     "cfg4_adams4_v_zsnr": (
         lambda: PD.SkrampleWrapperScheduler(PT.Adams(order=4), PS.ZSNR(), PM.VelocityModel()),
-        lambda n: OW.StepDriver(OA.make("adams", 4), OS.zsnr(), "v"),
+        lambda n, compute=torch.float32: OW.StepDriver(OA.make("adams", 4), OS.zsnr(), "v", compute=compute),
         (256, 4, 128, 128),
         6,
     ),
     "cfg5_rkultra6_sde": (
         lambda: PD.RKUltraWrapperScheduler(PS.Scaled(), sampler_order=6, stochasticity=1),
-        lambda n: OW.RKDriver(OK.pick_tableau(6), OS.scaled(), "eps", "data", 1.0),
+        lambda n, compute=torch.float32: OW.RKDriver(OK.pick_tableau(6), OS.scaled(), "eps", "data", 1.0, compute=compute),
         (64, 4, 256, 256),
         12,
     ),
@@ -1401,7 +1402,9 @@ FULL_SIZE = {
 @pytest.mark.parametrize("name", sorted(FULL_SIZE))
 def test_full_size_baseline_configs(name, dev):
     """BASELINE configs 3-5 at their full per-GPU size: determinism, bitwise shard invariance (two half batches
-    reproduce the whole), and the oracle on a few samples of the full-size run (teacher-forced)."""
+    reproduce the whole), the oracle on a few samples of the full-size run (teacher-forced), and the oracle in float64 on the device
+    over the whole batch (teacher-forced with the same inputs; its noise is PN.Random's, the Philox stream d * 256 the step kernels
+    draw in-kernel, spot-checked against the specification on the three samples)."""
     mk_w, mk_o, shape, calls = FULL_SIZE[name]
     B, steps = shape[0], 20
     gd = torch.Generator(device=dev).manual_seed(4321)
@@ -1435,17 +1438,40 @@ def test_full_size_baseline_configs(name, dev):
     n = int(np.prod(shape[1:]))
     draws = iter(range(10**6))
 
+    drawn3 = []
+
     def philox_noise(_step=None):
         d = next(draws)
-        return torch.from_numpy(np.stack([ON.philox_normal(seeds[j], d * 256, n) for j in idx])).reshape(len(idx), *shape[1:])
+        drawn3.append(torch.from_numpy(np.stack([ON.philox_normal(seeds[j], d * 256, n) for j in idx])).reshape(len(idx), *shape[1:]))
+        return drawn3[-1]
+
+    o64 = mk_o(steps, compute=torch.float64)
+    o64.set_timesteps(steps)
+    white = PN.BatchTensorNoise.from_batch_inputs(PN.Random, shape[1:], seeds, dtype=torch.float32)
+    drawn = []
+
+    def philox_noise_all(_step=None):
+        "the whole batch's draw d (PN.Random: stream d * 256), its three samples checked against the specification's"
+        got = white.generate(None)
+        assert (got[idx].cpu().double() - drawn3[len(drawn)].double()).abs().max().item() < 4e-6, len(drawn)
+        drawn.append(1)
+        return got
 
     for i in range(calls):
         xin, oin = ins[i][0][idx].cpu(), ins[i][1][idx].cpu()
         if isinstance(o, OW.RKDriver):
             ref = o.step(oin, o.timesteps[i], xin, noise_fn=philox_noise)
+            ref_all = o64.step(ins[i][1], o64.timesteps[i], ins[i][0], noise_fn=philox_noise_all)
         else:
             ref = o.step(oin, o.timesteps[i], xin, noise=philox_noise() if OA.require_noise(o.cfg) else None)[0]
+            ref_all = o64.step(ins[i][1], o64.timesteps[i], ins[i][0], noise=philox_noise_all() if OA.require_noise(o64.cfg) else None)[0]
         assert_close(full[i][idx], ref, torch.bfloat16, f"{name} call {i}", flips=0.10)
+        assert ref_all.dtype == torch.bfloat16 and ref_all.device == full[i].device
+        assert_close(full[i], ref_all, torch.bfloat16, f"{name} call {i}, whole batch vs float64", flips=0.10)
+        del ref_all
+    assert len(drawn) == len(drawn3)
+    del o64, ins, full, again, lo_half, hi_half
+    torch.cuda.empty_cache()
 
 
 def test_step_programs_replay_bitwise(dev):

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 13
+#define SKR_ABI_VERSION 14
 #define SKR_MAX_TERMS 80 /* 2 x 35-stage tableau pairs + base + noise, see skr_step_plan */
 
 /* Devices and streams: every entry point launches on the device that owns its output buffer (queried from the pointer when
@@ -94,6 +94,36 @@ typedef struct skr_step_plan {
 int skr_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
                     const uint64_t* seeds_dev /* [batch] device, may be NULL if noise_mode==0 */,
                     int64_t numel, void* stream);
+
+/*
+ * The transposed step (autograd of skr_step_launch).  A step is linear in its tensor operands and its coefficients are host
+ * numbers, so the gradient of every operand is a fixed combination of the incoming gradients of out0 / out1 -- no saved tensors:
+ *
+ *     grad_k[e] = a[k] * g0[e] + b[k] * g1[e]        (forward: a[k] = coef0[k], b[k] = chain * coef0[k] + coef1[k])
+ *
+ * evaluated in fp32 (fp64 if acc_f64) registers and rounded to the gradient's dtype as the step's outputs are (store8): once from
+ * fp32; from fp64 to a 16-bit gradient through fp32, i.e. twice.  One pass over HBM: g0 (and g1) read once, one gradient written per
+ * operand.  Launches of whole 2048-element chunks with one 16/32-bit dtype throughout, fp32 arithmetic and <= 16 gradients take the
+ * one-trip kernel; anything else (mixed dtypes, ragged sizes, fp64, more gradients) a grid-stride kernel of per-element accesses.  g1 may be NULL (g1_dtype = SKR_NONE); g0 is required (a caller with only an out1
+ * gradient passes it as g0 with b as a).  Gradients are grouped by dtype as the operands of skr_step_plan: [0, n_group_a) have
+ * dtype_a, the rest dtype_b.  The noise terms have no gradient; the derivative of a rounded pair conversion (convert_*) is affine
+ * in (s, o) and folded into a[0..1] by the caller, so there is no conversion mode here.  Every buffer 16-byte aligned.
+ */
+typedef struct skr_step_grad_plan {
+  int32_t n_grads;   /* 1..SKR_MAX_TERMS */
+  int32_t n_group_a; /* grads [0,n_group_a) are dtype_a, [n_group_a,n_grads) dtype_b */
+  int32_t dtype_a;   /* skr_dtype */
+  int32_t dtype_b;   /* skr_dtype; ignored when n_group_a == n_grads */
+  int32_t g0_dtype;  /* skr_dtype of the incoming gradient of out0 */
+  int32_t g1_dtype;  /* skr_dtype of the second incoming gradient, SKR_NONE if absent */
+  int32_t acc_f64;   /* 1 = evaluate in double */
+  int32_t reserved;  /* 0 */
+  double a[SKR_MAX_TERMS];
+  double b[SKR_MAX_TERMS];
+} skr_step_grad_plan;
+
+int skr_step_backward_launch(const skr_step_grad_plan* plan, const void* g0, const void* g1, void* const* grads, int64_t numel,
+                             void* stream);
 
 /*
  * Device-resident step scalars -- SURVEY.md 8(f) rank 1; replaces the per-step host work of
@@ -295,6 +325,15 @@ int skr_colorize(void* out, int32_t out_dtype, void* spec_c64, float* white_f32,
  * fp64 (the wrappers' compute_scale; fp64 uses double-precision pow); a and b may be any of the four dtypes.  P != 0. */
 int skr_power_blend(void* out, int32_t out_dtype, const void* a, int32_t a_dtype, const void* b, int32_t b_dtype, double p,
                     double c, double power, int64_t numel, void* stream);
+
+/* Backward of skr_power_blend: with u = p * spowf(a, P) + c * spowf(b, P) and g the incoming gradient (out_dtype of the forward,
+ * fp32 or fp64, which is also the arithmetic),
+ *     grad_a = g * p * |u|^(1/P - 1) * |a|^(P - 1),   grad_b likewise with c and b
+ * evaluated as torch autograd evaluates the host expression spowf(x, f) = |x|^f * sign(x) -- the chain
+ * ((g * sgn u) * (1/P) |u|^(1/P-1)) * sgn u, then (p * that * sgn a) * P |a|^(P-1) * sgn a, sgn(0) = 0 -- so that exact zeros give
+ * what it gives (0, or NaN where a zero meets a negative exponent).  grad_a has a's dtype, grad_b b's; either may be NULL. */
+int skr_power_blend_backward(void* grad_a, void* grad_b, const void* g, int32_t g_dtype, const void* a, int32_t a_dtype, const void* b,
+                             int32_t b_dtype, double p, double c, double power, int64_t numel, void* stream);
 
 /* Diagnostics counters of this process (tests assert that a shape did NOT go to the vendor FFT): "hipfft_plans" = hipFFT plan pairs
  * created so far, "hipfft_execs" = forward hipFFT transforms run so far, "own_fft_execs" = forward N-D transforms run by the library's

@@ -14,7 +14,7 @@ import threading
 import torch
 
 MAX_TERMS = 80
-ABI_VERSION = 13
+ABI_VERSION = 14
 SKR_ERR_UNSUPPORTED = 7  # include/skrample_hip.h: valid request outside what the fast kernels cover
 
 BF16, F16, F32, F64, NONE = 0, 1, 2, 3, -1
@@ -28,6 +28,7 @@ LIB_PATH = os.environ.get("SKR_HIP_LIB") or os.path.join(os.path.dirname(os.path
 EXPORTS = (
     "skr_step_launch",
     "skr_step_launch_indexed",
+    "skr_step_backward_launch",
     "skr_program_create",
     "skr_program_launch",
     "skr_program_destroy",
@@ -43,6 +44,7 @@ EXPORTS = (
     "skr_colorize",
     "skr_error_mean",
     "skr_power_blend",
+    "skr_power_blend_backward",
     "skr_philox_u32",
     "skr_abi_version",
     "skr_strerror",
@@ -80,6 +82,23 @@ class StepPlanC(ctypes.Structure):
         ("convert_to", ctypes.c_int32),
         ("convert_from", ctypes.c_int32),
         ("convert_k", ctypes.c_double * 4),
+    ]
+
+
+class StepGradPlanC(ctypes.Structure):
+    "mirror of `skr_step_grad_plan`"
+
+    _fields_ = [
+        ("n_grads", ctypes.c_int32),
+        ("n_group_a", ctypes.c_int32),
+        ("dtype_a", ctypes.c_int32),
+        ("dtype_b", ctypes.c_int32),
+        ("g0_dtype", ctypes.c_int32),
+        ("g1_dtype", ctypes.c_int32),
+        ("acc_f64", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("a", ctypes.c_double * MAX_TERMS),
+        ("b", ctypes.c_double * MAX_TERMS),
     ]
 
 
@@ -262,6 +281,8 @@ def load() -> ctypes.CDLL:
         lib.skr_step_launch.restype = ctypes.c_int
         lib.skr_step_launch_indexed.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
         lib.skr_step_launch_indexed.restype = ctypes.c_int
+        lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
+        lib.skr_step_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]
         lib.skr_program_create.restype = ctypes.c_int
         lib.skr_program_launch.argtypes = [vp, ctypes.POINTER(vp), vp, vp, vp, u64, u64, vp]
@@ -294,6 +315,8 @@ def load() -> ctypes.CDLL:
         lib.skr_philox_u32.restype = ctypes.c_int
         lib.skr_power_blend.argtypes = [vp, i32, vp, i32, vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i64, vp]
         lib.skr_power_blend.restype = ctypes.c_int
+        lib.skr_power_blend_backward.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i64, vp]
+        lib.skr_power_blend_backward.restype = ctypes.c_int
         lib.skr_abi_version.restype = ctypes.c_int
         lib.skr_strerror.argtypes = [ctypes.c_int]
         lib.skr_strerror.restype = ctypes.c_char_p

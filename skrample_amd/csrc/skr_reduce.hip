@@ -124,3 +124,89 @@ extern "C" int skr_power_blend(void* out, int32_t out_dtype, const void* a, int3
   if (out_dtype == SKR_F64) return skr::power_blend_a<double>((double*)out, a, a_dtype, b, b_dtype, p, c, power, numel, s);
   return SKR_ERR_DTYPE;
 }
+
+// ---- backward of the signed-power blend (include/skrample_hip.h, skr_power_blend_backward) ---------------------------------------
+// torch autograd of the host expression spowf(x, f) = |x|^f * sign(x) gives, per spowf, d/dx = sgn(x) * f |x|^(f-1) * sgn(x) with
+// sgn(0) = 0: the products below are that chain in that order, so exact zeros give what autograd gives (0, or 0 * inf = NaN where
+// a zero meets a negative exponent).  |x|^f: pow in fp64; in fp32 the raw log2 / exp2 units, as the forward, with x^0 = 1.
+namespace skr {
+template <typename M> __device__ __forceinline__ M sgn_dev(M x) { return x > (M)0 ? (M)1 : (x < (M)0 ? (M)-1 : (M)0); }
+__device__ __forceinline__ float apow_dev(float x, float f) {
+  return f == 0.f ? 1.f : __builtin_amdgcn_exp2f(f * __builtin_amdgcn_logf(__builtin_fabsf(x)));
+}
+__device__ __forceinline__ double apow_dev(double x, double f) { return pow(fabs(x), f); }
+
+template <typename T> __device__ __forceinline__ void blend_store(void* p, int64_t i, double v) {
+  if constexpr (__is_same(T, __bf16)) {
+    float f = (float)v;
+    asm("" : "+v"(f));
+    reinterpret_cast<__bf16*>(p)[i] = (__bf16)f;  // RNE
+  } else if constexpr (__is_same(T, _Float16)) {
+    float f = (float)v;
+    asm("" : "+v"(f));
+    reinterpret_cast<_Float16*>(p)[i] = (_Float16)f;
+  } else {
+    reinterpret_cast<T*>(p)[i] = (T)v;
+  }
+}
+
+template <typename TA, typename TB, typename M>
+__global__ __launch_bounds__(256) void power_blend_bwd_kernel(void* ga, void* gb, const M* g, const void* a, const void* b, M p, M c, M power, M inv_power,
+                                                              int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const M av = blend_load<TA, M>(a, i), bv = blend_load<TB, M>(b, i);
+    const M u = spow_dev(av, power) * p + spow_dev(bv, power) * c;
+    const M su = sgn_dev(u);
+    const M gu = ((g[i] * su) * (inv_power * apow_dev(u, inv_power - (M)1))) * su;
+    if (ga) {
+      const M sa = sgn_dev(av);
+      blend_store<TA>(ga, i, (double)((((gu * p) * sa) * (power * apow_dev(av, power - (M)1))) * sa));
+    }
+    if (gb) {
+      const M sb = sgn_dev(bv);
+      blend_store<TB>(gb, i, (double)((((gu * c) * sb) * (power * apow_dev(bv, power - (M)1))) * sb));
+    }
+  }
+}
+
+template <typename TA, typename M>
+static int power_blend_bwd_b(void* ga, void* gb, const M* g, const void* a, const void* b, int32_t b_dtype, double p, double c, double power, int64_t n,
+                             hipStream_t s) {
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  const M mp = (M)p, mc = (M)c, mw = (M)power, ip = (M)(1.0 / power);
+  switch (b_dtype) {
+    case SKR_BF16: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, __bf16, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
+    case SKR_F16: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, _Float16, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
+    case SKR_F32: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, float, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
+    case SKR_F64: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, double, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
+    default: return SKR_ERR_DTYPE;
+  }
+  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+}
+
+template <typename M>
+static int power_blend_bwd_a(void* ga, void* gb, const M* g, const void* a, int32_t a_dtype, const void* b, int32_t b_dtype, double p, double c, double power,
+                             int64_t n, hipStream_t s) {
+  switch (a_dtype) {
+    case SKR_BF16: return power_blend_bwd_b<__bf16, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
+    case SKR_F16: return power_blend_bwd_b<_Float16, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
+    case SKR_F32: return power_blend_bwd_b<float, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
+    case SKR_F64: return power_blend_bwd_b<double, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
+    default: return SKR_ERR_DTYPE;
+  }
+}
+}  // namespace skr
+
+extern "C" int skr_power_blend_backward(void* grad_a, void* grad_b, const void* g, int32_t g_dtype, const void* a, int32_t a_dtype, const void* b,
+                                        int32_t b_dtype, double p, double c, double power, int64_t numel, void* stream) {
+  skr::DeviceGuard device_guard(g);
+  if (numel < 0) return SKR_ERR_SHAPE;
+  if (numel == 0 || (!grad_a && !grad_b)) return SKR_OK;
+  if (!g || !a || !b) return SKR_ERR_NULL;
+  if (power == 0.0) return SKR_ERR_UNSUPPORTED;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (g_dtype == SKR_F32) return skr::power_blend_bwd_a<float>(grad_a, grad_b, (const float*)g, a, a_dtype, b, b_dtype, p, c, power, numel, s);
+  if (g_dtype == SKR_F64) return skr::power_blend_bwd_a<double>(grad_a, grad_b, (const double*)g, a, a_dtype, b, b_dtype, p, c, power, numel, s);
+  return SKR_ERR_DTYPE;
+}

@@ -1,0 +1,183 @@
+// The transposed solver step (include/skrample_hip.h, skr_step_backward_launch): grad_k = a_k * g0 + b_k * g1 for every operand
+// that needs a gradient, in one pass over HBM.  No saved tensors: the forward is linear in its operands and its coefficients are
+// host numbers.
+//   * one-trip kernel: whole 2048-element chunks, every gradient and incoming gradient of one 16- or 32-bit dtype, fp32 arithmetic,
+//     <= 16 gradients (kernarg slots of 4 / 8 / 16).  Lane ownership, XCD chunk map, loads and stores are those of step_kernel_k1
+//     (skr_step_fast.hip), so a DPM-2 backward moves the same kind of traffic as a forward step: one or two reads, K writes.
+//   * general kernel: grid-stride, any size, any dtype combination, up to SKR_MAX_TERMS gradients, fp32 or fp64 arithmetic.
+// Both evaluate  o = a*g0  (one gradient)  or  o = fma(b, g1, a*g0)  and round o once, so they agree bit for bit where both apply.
+#include "skr_step_common.h"
+#include "skr_device.h"
+
+namespace skr {
+
+template <int KMAX>
+struct BwdOneTripArgs {
+  void* grad[KMAX];
+  const void* g0;
+  const void* g1;
+  int32_t xmap_lr;
+  int32_t n;  // gradients written (<= KMAX)
+  float a[KMAX];
+  float b[KMAX];
+};
+
+template <typename T, int KMAX, bool HAS1>
+__global__ __launch_bounds__(BLOCK) void step_bwd_k1(const BwdOneTripArgs<KMAX> p) {
+  constexpr bool TILE = sizeof(T) == 4;  // whole chunks are whole tiles: 32-bit tensors take the whole-line layout, as in launch_k1
+  const uint32_t c = chunk_of(blockIdx.x, p.xmap_lr);
+  const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
+  Raw<T> r0 = load_raw<T, TILE>(p.g0, v), r1;
+  if constexpr (HAS1) r1 = load_raw<T, TILE>(p.g1, v);
+  float x0[VEC], x1[VEC];
+  widen<T, float>(r0, x0);
+  if constexpr (HAS1) widen<T, float>(r1, x1);
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) {
+    if (j < p.n) {  // (uniform: the count is a kernarg scalar)
+      const float aj = p.a[j];
+      float o[VEC];
+      if constexpr (HAS1) {
+        const float bj = p.b[j];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) o[i] = fma_(bj, x1[i], mul_(aj, x0[i]));
+      } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) o[i] = mul_(aj, x0[i]);
+      }
+      store8<T, float, TILE>(p.grad[j], v, o);
+    }
+  }
+}
+
+struct BwdArgs {
+  void* grad[MAXK];
+  double a[MAXK];
+  double b[MAXK];
+  const void* g0;
+  const void* g1;
+  int64_t numel;
+  int32_t n, n_a, dt_a, dt_b, dt_g0, dt_g1;
+};
+
+template <typename Acc> __device__ __forceinline__ Acc load_any(const void* base, int64_t i, int dt) {
+  switch (dt) {
+    case SKR_BF16: return (Acc)load_scalar<bf16_t>(base, i);
+    case SKR_F16: return (Acc)load_scalar<f16_t>(base, i);
+    case SKR_F32: return (Acc)load_scalar<float>(base, i);
+    default: return (Acc)reinterpret_cast<const double*>(base)[i];
+  }
+}
+
+// one rounding from Acc; the same conversions as store8 (fp32 -> 16-bit: RNE of the fp32 value, pinned so that no fused
+// multiply-add-and-convert rounds the exact sum instead)
+template <typename Acc> __device__ __forceinline__ void store_any(void* base, int64_t i, int dt, Acc v) {
+  switch (dt) {
+    case SKR_BF16: {
+      float f = (float)v;
+      asm("" : "+v"(f));
+      reinterpret_cast<uint16_t*>(base)[i] = (uint16_t)(pack_bf16(f, 0.f) & 0xFFFFu);
+      break;
+    }
+    case SKR_F16: {
+      float f = (float)v;
+      asm("" : "+v"(f));
+      reinterpret_cast<_Float16*>(base)[i] = (_Float16)f;
+      break;
+    }
+    case SKR_F32: reinterpret_cast<float*>(base)[i] = (float)v; break;
+    default: reinterpret_cast<double*>(base)[i] = (double)v; break;
+  }
+}
+
+template <typename Acc, bool HAS1>
+__global__ __launch_bounds__(BLOCK) void step_bwd_general(const BwdArgs p) {
+  for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < p.numel; e += (int64_t)gridDim.x * BLOCK) {
+    const Acc x0 = load_any<Acc>(p.g0, e, p.dt_g0);
+    Acc x1 = 0;
+    if constexpr (HAS1) x1 = load_any<Acc>(p.g1, e, p.dt_g1);
+    for (int j = 0; j < p.n; ++j) {
+      const Acc aj = (Acc)p.a[j];
+      const Acc o = HAS1 ? fma_((Acc)p.b[j], x1, mul_(aj, x0)) : mul_(aj, x0);
+      store_any<Acc>(p.grad[j], e, j < p.n_a ? p.dt_a : p.dt_b, o);
+    }
+  }
+}
+
+template <typename T, int KMAX, bool HAS1>
+static void launch_bwd_k1(const skr_step_grad_plan& pl, const void* g0, const void* g1, void* const* grads, int64_t chunks, hipStream_t s) {
+  BwdOneTripArgs<KMAX> p;
+  for (int k = 0; k < KMAX; ++k) {
+    const bool live = k < pl.n_grads;
+    p.grad[k] = live ? grads[k] : nullptr;
+    p.a[k] = live ? (float)pl.a[k] : 0.f;
+    p.b[k] = live ? (float)pl.b[k] : 0.f;
+  }
+  p.g0 = g0; p.g1 = g1; p.n = pl.n_grads; p.xmap_lr = xmap_lr_for(chunks);
+  hipLaunchKernelGGL((step_bwd_k1<T, KMAX, HAS1>), dim3((unsigned)chunks), dim3(BLOCK), 0, s, p);
+}
+
+template <typename T>
+static void launch_bwd_k1_t(const skr_step_grad_plan& pl, const void* g0, const void* g1, void* const* grads, int64_t chunks, hipStream_t s) {
+  const bool has1 = g1 != nullptr;
+  if (pl.n_grads <= 4) has1 ? launch_bwd_k1<T, 4, true>(pl, g0, g1, grads, chunks, s) : launch_bwd_k1<T, 4, false>(pl, g0, g1, grads, chunks, s);
+  else if (pl.n_grads <= 8) has1 ? launch_bwd_k1<T, 8, true>(pl, g0, g1, grads, chunks, s) : launch_bwd_k1<T, 8, false>(pl, g0, g1, grads, chunks, s);
+  else has1 ? launch_bwd_k1<T, 16, true>(pl, g0, g1, grads, chunks, s) : launch_bwd_k1<T, 16, false>(pl, g0, g1, grads, chunks, s);
+}
+
+static bool valid_dtype(int32_t d) { return d == SKR_BF16 || d == SKR_F16 || d == SKR_F32 || d == SKR_F64; }
+
+}  // namespace skr
+
+extern "C" int skr_step_backward_launch(const skr_step_grad_plan* plan, const void* g0, const void* g1, void* const* grads, int64_t numel,
+                                        void* stream) {
+  using namespace skr;
+  if (!plan) return SKR_ERR_NULL;
+  const skr_step_grad_plan& p = *plan;
+  if (p.n_grads < 1 || p.n_grads > SKR_MAX_TERMS || p.n_group_a < 0 || p.n_group_a > p.n_grads) return SKR_ERR_TERMS;
+  if (numel < 0) return SKR_ERR_SHAPE;
+  if (!grads) return SKR_ERR_NULL;
+  DeviceGuard device_guard(grads[0]);
+  const bool has1 = p.g1_dtype != SKR_NONE;
+  if (!valid_dtype(p.g0_dtype) || (has1 && !valid_dtype(p.g1_dtype)) || !valid_dtype(p.dtype_a) || (p.n_group_a < p.n_grads && !valid_dtype(p.dtype_b)))
+    return SKR_ERR_DTYPE;
+  if (numel == 0) return SKR_OK;
+  if (!g0 || (has1 != (g1 != nullptr))) return SKR_ERR_NULL;
+  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
+  if (!aligned(g0) || (has1 && !aligned(g1))) return SKR_ERR_ALIGN;
+  for (int k = 0; k < p.n_grads; ++k) {
+    if (!grads[k]) return SKR_ERR_NULL;
+    if (!aligned(grads[k])) return SKR_ERR_ALIGN;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
+  const int32_t t = p.dtype_a;
+  const bool one_dtype = (p.n_group_a == p.n_grads || p.dtype_b == t) && p.g0_dtype == t && (!has1 || p.g1_dtype == t);
+  if (g_tune.one_trip && !p.acc_f64 && one_dtype && t != SKR_F64 && p.n_grads <= 16 && numel % CHUNK == 0 && numel / CHUNK <= 0x7fffffffll) {
+    const int64_t chunks = numel / CHUNK;
+    if (t == SKR_BF16) launch_bwd_k1_t<bf16_t>(p, g0, g1, grads, chunks, s);
+    else if (t == SKR_F16) launch_bwd_k1_t<f16_t>(p, g0, g1, grads, chunks, s);
+    else launch_bwd_k1_t<float>(p, g0, g1, grads, chunks, s);
+    return finish_launch();
+  }
+  BwdArgs a;
+  for (int k = 0; k < MAXK; ++k) {
+    const bool live = k < p.n_grads;
+    a.grad[k] = live ? grads[k] : nullptr;
+    // fp32 arithmetic uses the coefficients rounded to fp32, as the one-trip kernel does
+    a.a[k] = live ? (p.acc_f64 ? p.a[k] : (double)(float)p.a[k]) : 0.0;
+    a.b[k] = live ? (p.acc_f64 ? p.b[k] : (double)(float)p.b[k]) : 0.0;
+  }
+  a.g0 = g0; a.g1 = g1; a.numel = numel; a.n = p.n_grads; a.n_a = p.n_group_a;
+  a.dt_a = p.dtype_a; a.dt_b = p.dtype_b; a.dt_g0 = p.g0_dtype; a.dt_g1 = p.g1_dtype;
+  int64_t blocks = (numel + BLOCK - 1) / BLOCK;
+  if (blocks > 256 * 64) blocks = 256 * 64;
+  if (p.acc_f64) {
+    if (has1) hipLaunchKernelGGL((step_bwd_general<double, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((step_bwd_general<double, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+  } else {
+    if (has1) hipLaunchKernelGGL((step_bwd_general<float, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((step_bwd_general<float, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+  }
+  return finish_launch();
+}

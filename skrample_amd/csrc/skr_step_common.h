@@ -346,6 +346,21 @@ struct RkArgs {
   uint64_t stream1;
 };
 
+// XCD-aware chunk map of the one-trip kernels (skr_step_fast.hip, skr_step_backward.hip)
+__device__ __forceinline__ uint32_t chunk_of(uint32_t b, int lr) {  // lr = log2(run length); 0 = identity
+  const uint32_t g = 3 + lr;
+  return ((b >> g) << g) + ((b & 7u) << lr) + ((b >> 3) & ((1u << lr) - 1u));
+}
+
+// run length of the XCD chunk map: the largest power of two <= the tuned one whose group of 8 runs divides the grid
+static inline int xmap_lr_for(int64_t chunks) {
+  int lr = g_tune.xmap;
+  if (lr < 0) lr = 0;
+  if (lr > 20) lr = 20;
+  while (lr > 0 && chunks % (8ll << lr) != 0) --lr;
+  return lr;
+}
+
 extern thread_local int g_last_hip_error;
 int finish_launch();
 

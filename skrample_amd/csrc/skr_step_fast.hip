@@ -38,10 +38,6 @@ __device__ __forceinline__ void sample_of(uint32_t c, int32_t bps_shift, uint32_
   else { const uint32_t bps = (uint32_t)(-bps_shift); smp = c / bps; within = c - smp * bps; }
 }
 
-__device__ __forceinline__ uint32_t chunk_of(uint32_t b, int lr) {  // lr = log2(run length); 0 = identity
-  const uint32_t g = 3 + lr;
-  return ((b >> g) << g) + ((b & 7u) << lr) + ((b >> 3) & ((1u << lr) - 1u));
-}
 
 // kernarg sizes: 4 / 8 / 12 / 16 / 20 operand slots (Adams-Bashforth 5-9 and UniP >= 5 give 10-18 operands: round 3)
 constexpr int one_trip_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 16 ? 16 : 20))); }
@@ -241,14 +237,6 @@ static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, int* bp
   return true;
 }
 
-// run length of the XCD chunk map: the largest power of two <= the tuned one whose group of 8 runs divides the grid
-static int xmap_lr_for(int64_t chunks) {
-  int lr = g_tune.xmap;
-  if (lr < 0) lr = 0;
-  if (lr > 20) lr = 20;
-  while (lr > 0 && chunks % (8ll << lr) != 0) --lr;
-  return lr;
-}
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 template <typename T, bool NOISE, int KMAX>

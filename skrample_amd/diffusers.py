@@ -798,7 +798,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         return self.sampler.scale_input(sample, Point(*self.schedule_np[idx]))
 
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
-        if type(timestep) is float and self._fast_ids is not None:
+        # a step autograd records takes the general path: the replayed steps and step programs bind raw pointers (no autograd node)
+        recorded = lazy.grad_recorded(model_output, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
+        if type(timestep) is float and self._fast_ids is not None and not recorded:
             done = self._fast_step(model_output, timestep, sample, generator, return_dict)
             if done is not None:
                 return done
@@ -847,7 +849,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             tuple((rec.sample is raw, getattr(rec.sample, "dtype", None)) for rec, raw in zip(self._previous, self._raw_samples)),
         )  # fmt: skip
         record = None
-        prog = self._programs.get(key)
+        prog = self._programs.get(key) if not recorded else False
         if prog is not None and prog is not False:
             record = prog.run(roles, step, prediction, sample.device)
             if record is not None and self._run_seq and (self._index, idx) not in self._fast:
@@ -1309,7 +1311,8 @@ class RKWrapperCore(SkrampleWrapperCore):
             self._rk_programs, self._rk_programs_for = {}, owner
         held = len(self._derivatives)
         key = (self._index, held, sample.dtype, model_output.dtype, tuple(sample.shape))
-        prog = self._rk_programs.get(key)
+        recorded = lazy.grad_recorded(model_output, sample, self._sample, *(leaf for form in self._derivatives if isinstance(form, Lin) for leaf, _ in form.terms.values()))
+        prog = self._rk_programs.get(key) if not recorded else False  # (a step autograd records is not replayed by pointer binding)
         if prog:
             done = self._replay_stage(prog, model_output, sample, generator)
             if done is not None:

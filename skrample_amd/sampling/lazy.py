@@ -18,6 +18,7 @@ Operand residency decides where a form is evaluated, never availability of the l
 from __future__ import annotations
 
 import contextvars
+import ctypes
 import math
 import os
 from typing import Any, Sequence
@@ -474,10 +475,116 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
             plan.zeta0, plan.stream0 = fused0[1], fused0[0].stream
         if fused1 is not None:
             plan.zeta1, plan.stream1 = fused1[1], fused1[0].stream
+    operands = [prepared[i] for i in order]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
+        if conv is not None:
+            plan_a = conversion_gradient(conv.to_kind, conv.from_kind, conv.k)
+        else:
+            plan_a = None
+        outs = _StepFunction.apply(plan, plan_a, seeds, shape, numel, device, *operands)
+        return list(outs) if f1 is not None else [outs]
     out0 = empty_output(shape, out_dtypes[0], device)
     out1 = empty_output(shape, out_dtypes[1], device) if f1 is not None else None
-    _hip.launch_step(plan, [prepared[i] for i in order], out0, out1, seeds, numel, device)
+    _hip.launch_step(plan, operands, out0, out1, seeds, numel, device)
     return [out0] if out1 is None else [out0, out1]
+
+
+# ---- autograd ------------------------------------------------------------------------------------------------------------------------
+# A step is linear in its tensor operands with host fp64 coefficients, so its backward is the transposed step (skr_step_backward_launch):
+#     grad_k = a_k * g0 + b_k * g1,   a_k = coef0_k,  b_k = chain * coef0_k + coef1_k
+# one launch, no saved tensors.  The Functions below are used only while autograd records and an operand requires grad: every other
+# call takes the launches above unchanged.
+def grad_recorded(*tensors) -> bool:
+    "autograd is recording and some tensor among `tensors` requires grad"
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+def conversion_gradient(to_kind: int, from_kind: int, k: Sequence[float]) -> tuple[float, float]:
+    """(d out0 / d s, d out0 / d o) of the rounded pair conversion out0 = from_x(s, to_x(s, o)) (include/skrample_hip.h, convert_*):
+    affine in (s, o), so its derivative is two numbers, folded into the operands' coef0"""
+    # to_x: x = xs * s + xo * o
+    # (only the kind's own constants are read: the others may be 0)
+    xs, xo = {0: lambda: (0.0, 1.0), 1: lambda: (1.0 / k[1], -k[0] / k[1]), 2: lambda: (k[1], -k[0]), 3: lambda: (0.0, k[0])}[to_kind]()
+    # from_x: v = vs * s + vx * x
+    vs, vx = {0: lambda: (0.0, 1.0), 1: lambda: (1.0 / k[3], -k[2] / k[3]), 2: lambda: (k[2] / k[3], -1.0 / k[3]), 3: lambda: (0.0, 1.0 / k[2])}[from_kind]()
+    return vs + vx * xs, vx * xo
+
+
+def transposed(plan, conv_grad, n: int) -> tuple[list[float], list[float]]:
+    "(a_k, b_k) of every operand of a forward plan: the gradient of operand k is a_k * grad(out0) + b_k * grad(out1)"
+    a = [plan.coef0[k] for k in range(n)]
+    if conv_grad is not None:
+        a[0], a[1] = conv_grad
+    b = [plan.chain * a[k] + plan.coef1[k] for k in range(n)] if plan.out1_dtype != _hip.NONE else [0.0] * n
+    return a, b
+
+
+def launch_backward(g0, g1, a: Sequence[float], b: Sequence[float], like: Sequence[torch.Tensor], acc_f64: bool) -> list[torch.Tensor]:
+    """grads[k] = a[k] * g0 + b[k] * g1 (g0 or g1 may be None) in one skr_step_backward_launch; grads[k] has like[k]'s dtype and shape.
+    `like` must be grouped by dtype (at most two groups)."""
+    if g0 is None:
+        g0, g1, a, b = g1, None, b, a
+    device = g0.device
+    g0 = _prepare_tensor(g0)
+    g1 = _prepare_tensor(g1) if g1 is not None else None
+    grads = [torch.empty(t.shape, dtype=t.dtype, device=device) for t in like]
+    plan = _hip.StepGradPlanC()
+    plan.n_grads = len(grads)
+    plan.dtype_a = _hip.DTYPE_CODE[grads[0].dtype]
+    plan.n_group_a = sum(1 for t in grads if t.dtype == grads[0].dtype)
+    plan.dtype_b = _hip.DTYPE_CODE[grads[-1].dtype]
+    if any(t.dtype != grads[0].dtype for t in grads[: plan.n_group_a]) or len({t.dtype for t in grads}) > 2:
+        raise SkrampleHipError("gradients must come in at most two dtype groups")
+    plan.g0_dtype = _hip.DTYPE_CODE[g0.dtype]
+    plan.g1_dtype = _hip.DTYPE_CODE[g1.dtype] if g1 is not None else _hip.NONE
+    plan.acc_f64 = 1 if acc_f64 else 0
+    for k in range(len(grads)):
+        plan.a[k] = a[k]
+        plan.b[k] = b[k] if g1 is not None else 0.0
+    arr = (ctypes.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
+    status = _hip.load().skr_step_backward_launch(ctypes.byref(plan), g0.data_ptr(), g1.data_ptr() if g1 is not None else None, arr, g0.numel(), _hip.current_stream_ptr(device))
+    _hip.check(status, "skr_step_backward_launch")
+    return grads
+
+
+class _StepFunction(torch.autograd.Function):
+    "one fused step launch (forward) and its transposed step (backward)"
+
+    @staticmethod
+    def forward(ctx, plan, conv_grad, seeds, shape, numel, device, *operands):
+        ctx.set_materialize_grads(False)
+        ctx.plan, ctx.conv_grad = plan, conv_grad
+        # plain tensors: a view made here (empty_output's staggered placement) would make a later in-place op on the result raise
+        out0 = torch.empty(shape, dtype=_hip.CODE_DTYPE[plan.out0_dtype], device=device)
+        out1 = torch.empty(shape, dtype=_hip.CODE_DTYPE[plan.out1_dtype], device=device) if plan.out1_dtype != _hip.NONE else None
+        _hip.launch_step(plan, list(operands), out0, out1, seeds, numel, device)
+        ctx.like = [(t.shape, t.dtype) for t in operands]
+        return out0 if out1 is None else (out0, out1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g0, g1=None):
+        n = len(ctx.like)
+        skip = 6
+        want = [k for k in range(n) if ctx.needs_input_grad[skip + k]]
+        result: list = [None] * (skip + n)
+        if not want or (g0 is None and g1 is None):
+            return tuple(result)
+        a, b = transposed(ctx.plan, ctx.conv_grad, n)
+        like = [_Like(*ctx.like[k]) for k in want]
+        grads = launch_backward(g0, g1, [a[k] for k in want], [b[k] for k in want], like, bool(ctx.plan.acc_f64))
+        for k, g in zip(want, grads):
+            result[skip + k] = g
+        return tuple(result)
+
+
+class _Like:
+    "shape and dtype of a tensor a gradient is made for"
+
+    __slots__ = ("shape", "dtype")
+
+    def __init__(self, shape, dtype):
+        self.shape, self.dtype = shape, dtype
 
 
 
@@ -574,10 +681,41 @@ def power_blend(a: torch.Tensor, b: torch.Tensor, wa: float, wb: float, power: f
         blended = spow(wa * spow(a.to(dtype), power) + wb * spow(b.to(dtype), power), 1 / power)
         return blended.numpy() if as_numpy else blended
     a, b = _prepare_tensor(a), _prepare_tensor(b)
+    if grad_recorded(a, b):
+        return _PowerBlendFunction.apply(float(wa), float(wb), float(power), dtype, a, b)
     out = empty_output(a.shape, dtype, a.device)
     status = _hip.load().skr_power_blend(out.data_ptr(), _hip.DTYPE_CODE[dtype], a.data_ptr(), _hip.DTYPE_CODE[a.dtype], b.data_ptr(), _hip.DTYPE_CODE[b.dtype], float(wa), float(wb), float(power), a.numel(), _hip.current_stream_ptr(a.device))
     _hip.check(status, "skr_power_blend")
     return out
+
+
+class _PowerBlendFunction(torch.autograd.Function):
+    "skr_power_blend (forward) and skr_power_blend_backward: the one non-linear step operation, so the one that saves its operands"
+
+    @staticmethod
+    def forward(ctx, wa, wb, power, dtype, a, b):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a, b)
+        ctx.wa, ctx.wb, ctx.power = wa, wb, power
+        out = torch.empty(a.shape, dtype=dtype, device=a.device)
+        status = _hip.load().skr_power_blend(out.data_ptr(), _hip.DTYPE_CODE[dtype], a.data_ptr(), _hip.DTYPE_CODE[a.dtype], b.data_ptr(), _hip.DTYPE_CODE[b.dtype], wa, wb, power, a.numel(), _hip.current_stream_ptr(a.device))
+        _hip.check(status, "skr_power_blend")
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        if g is None:
+            return None, None, None, None, None, None
+        g = _prepare_tensor(g)
+        ga = torch.empty_like(a, memory_format=torch.contiguous_format) if ctx.needs_input_grad[4] else None
+        gb = torch.empty_like(b, memory_format=torch.contiguous_format) if ctx.needs_input_grad[5] else None
+        status = _hip.load().skr_power_blend_backward(
+            ga.data_ptr() if ga is not None else None, gb.data_ptr() if gb is not None else None, g.data_ptr(), _hip.DTYPE_CODE[g.dtype],
+            a.data_ptr(), _hip.DTYPE_CODE[a.dtype], b.data_ptr(), _hip.DTYPE_CODE[b.dtype], ctx.wa, ctx.wb, ctx.power, a.numel(), _hip.current_stream_ptr(a.device))
+        _hip.check(status, "skr_power_blend_backward")
+        return None, None, None, None, ga, gb
 
 
 def settle(value, like=None, dtype: torch.dtype | None = None):

@@ -410,9 +410,10 @@ def _compile(tape: Tape, results: list):
     return c, used_leaves, stores
 
 
-def _launch(c, leaves: list[torch.Tensor], n_outputs: int) -> list[torch.Tensor]:
+def _launch(c, leaves: list[torch.Tensor], n_outputs: int, plain: bool = False) -> list[torch.Tensor]:
     first = leaves[0]
-    outs = [lazy.empty_output(first.shape, first.dtype, first.device) for _ in range(n_outputs)]
+    make = torch.empty if plain else lazy.empty_output
+    outs = [make(first.shape, dtype=first.dtype, device=first.device) for _ in range(n_outputs)]
     ins = (ctypes.c_void_p * len(leaves))(*[t.data_ptr() for t in leaves])
     ous = (ctypes.c_void_p * n_outputs)(*[t.data_ptr() for t in outs])
     _hip.check(_hip.load().skr_tape_launch(ctypes.byref(c), ins, ous, first.numel(), _hip.current_stream_ptr(first.device)), "skr_tape_launch")
@@ -425,8 +426,95 @@ def _run(tape: Tape, results: list) -> list[torch.Tensor]:
     """Fill a skr_tape and launch it.  `results` are the values to return: a leaf comes back as the caller's own tensor, anything else
     is stored by the launch right behind its definition."""
     c, used_leaves, stores = _compile(tape, results)
+    if lazy.grad_recorded(*tape.leaves):
+        outs = _run_recorded(tape, c, used_leaves, stores)
+        return [tape.leaves[tape.ops[v.n][1]] if tape.ops[v.n][0] == _hip.TAPE_LOAD else outs[stores[v.n]] for v in results]
     outs = _launch(c, [tape.leaves[i] for i in used_leaves], len(stores))
     return [tape.leaves[tape.ops[v.n][1]] if tape.ops[v.n][0] == _hip.TAPE_LOAD else outs[stores[v.n]] for v in results]
+
+
+# ---- autograd ---------------------------------------------------------------------------------------------------------------------------
+# The forward keeps the tape's (the reference's) bits.  Every op a sampler records is affine in the tensors -- a scalar product or quotient,
+# a sum or difference, a negation, an added scalar -- so each stored value is  sum_leaf c_leaf * leaf + const  up to rounding: the tape is
+# folded into those coefficients by reverse accumulation in fp64 on the host, and the backward is the transposed step kernel
+# (skr_step_backward_launch), no saved tensors.  A product or quotient of two tensors would need its operands: such a tape is refused.
+_NONLINEAR = {_hip.TAPE_MUL: "MUL (tensor * tensor)", _hip.TAPE_DIV: "DIV (tensor / tensor)", _hip.TAPE_RDIV_S: "RDIV_S (number / tensor)"}
+
+
+def fold(tape: Tape, n: int) -> dict[int, float]:
+    "d value(n) / d leaf, for every leaf it depends on (index into tape.leaves -> fp64 coefficient)"
+    adj: dict[int, float] = {n: 1.0}
+    coef: dict[int, float] = {}
+    for i in range(n, -1, -1):
+        if i not in adj:
+            continue
+        w = adj.pop(i)
+        code, a, b, k = tape.ops[i]
+        if code in _NONLINEAR:
+            raise _hip.SkrampleHipError(f"the recorded step holds {_NONLINEAR[code]}, which has no gradient without saved operands; record grad on a fused step (compute_scale) instead")
+        if code == _hip.TAPE_LOAD:
+            coef[a] = coef.get(a, 0.0) + w
+            continue
+        if code == _hip.TAPE_MUL_S:
+            da = w * k
+        elif code == _hip.TAPE_DIV_S:
+            da = w / k
+        elif code == _hip.TAPE_ADD_S:
+            da = w
+        elif code in (_hip.TAPE_RSUB_S, _hip.TAPE_NEG):
+            da = -w
+        elif code in (_hip.TAPE_ADD, _hip.TAPE_SUB):
+            da = w
+            adj[b] = adj.get(b, 0.0) + (w if code == _hip.TAPE_ADD else -w)
+        else:
+            raise _hip.SkrampleHipError(f"tape op code {code} has no gradient")
+        adj[a] = adj.get(a, 0.0) + da
+    return coef
+
+
+class _TapeFunction(torch.autograd.Function):
+    "one skr_tape_launch (forward, the reference's bits) and the transposed step of its folded coefficients (backward)"
+
+    @staticmethod
+    def forward(ctx, c, n_outputs, coefs, *leaves):
+        ctx.set_materialize_grads(False)
+        ctx.coefs = coefs  # [output][leaf position] fp64
+        ctx.like = [(t.shape, t.dtype) for t in leaves]
+        return tuple(_launch(c, list(leaves), n_outputs, plain=True))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        skip = 3
+        want = [k for k in range(len(ctx.like)) if ctx.needs_input_grad[skip + k]]
+        result: list = [None] * (skip + len(ctx.like))
+        live = [r for r, g in enumerate(gs) if g is not None]
+        if not want or not live:
+            return tuple(result)
+        like = [lazy._Like(*ctx.like[k]) for k in want]
+        acc_f64 = ctx.like[0][1] == torch.float64
+        partial = None
+        for p in range(0, len(live), 2):  # the kernel takes two incoming gradients; more outputs (rare) are summed pairwise by the fused step
+            pair = live[p : p + 2]
+            g0, g1 = gs[pair[0]], gs[pair[1]] if len(pair) == 2 else None
+            a = [ctx.coefs[pair[0]][k] for k in want]
+            b = [ctx.coefs[pair[1]][k] for k in want] if len(pair) == 2 else [0.0] * len(want)
+            grads = lazy.launch_backward(g0, g1, a, b, like, acc_f64)
+            partial = grads if partial is None else [lazy.evaluate([lazy.Lin.leaf(x) + lazy.Lin.leaf(y)], [x.dtype])[0] for x, y in zip(partial, grads)]
+        for k, g in zip(want, partial):
+            result[skip + k] = g
+        return tuple(result)
+
+
+def _run_recorded(tape: Tape, c, used_leaves: list[int], stores: dict[int, int]) -> list[torch.Tensor]:
+    "the tape's launch as an autograd node (autograd is recording and a leaf requires grad)"
+    position = {leaf: p for p, leaf in enumerate(used_leaves)}
+    coefs = [[0.0] * len(used_leaves) for _ in stores]
+    for n, slot in stores.items():
+        for leaf, w in fold(tape, n).items():
+            if leaf in position:
+                coefs[slot][position[leaf]] += w
+    return list(_TapeFunction.apply(c, len(stores), coefs, *[tape.leaves[i] for i in used_leaves]))
 
 
 # ---- remembered steps ---------------------------------------------------------------------------------------------------------------
@@ -467,6 +555,9 @@ def _remembered_step(kind: str, recorder, sampler, packed, model, schedule, prev
     key = entry = None
     if like.is_cuda:
         settled = [None if t is None else _settled(t, like.dtype) for t in arguments]  # (what the recorder's leaves would be: sameness is judged on these)
+        if lazy.grad_recorded(*settled):  # recorded afresh: the backward folds the tape itself
+            tape, results = recorder(sampler, packed, model, schedule, previous, require_device=False)
+            return _run(tape, results)
         key = _step_key(kind, sampler, model, schedule, packed, previous, settled)
         entry = _remembered.get(key) if key is not None else None
     if entry is not None:

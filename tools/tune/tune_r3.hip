@@ -8,6 +8,7 @@
 // scenario must produce the same bytes as the scenario's first one (word sums of the outputs are compared).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tune_r3 tune_r3.hip
 //   ./tune_r3 [only=substring] [reps=3] [iters=200]
+//   ./tune_r3 only=bwd   the backward launch (skr_step_backward_launch) against its ceilings kmix<R1,W4> / kmix<R2,W5>
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +45,7 @@ struct Args {
   uint64_t stream0, stream1;
   int lr;          // log2 run length of the XCD chunk map
   int bps_shift;   // log2(chunks per sample)
+  void* outx[3];   // third to fifth output streams (the backward ceilings kmix<R, W > 2>)
 };
 
 // store policies: 0 plain write-back, 1 nt, 2 sc0 sc1, 3 sc1
@@ -357,6 +359,8 @@ __global__ __launch_bounds__(BLK) void kmix(const Args a) {
   }
   if constexpr (W >= 1) st16<SP>(reinterpret_cast<u32x4_t*>(a.out0) + v, acc);
   if constexpr (W >= 2) st16<SP>(reinterpret_cast<u32x4_t*>(a.out1) + v, acc + 1u);
+#pragma unroll
+  for (int j = 0; j + 2 < W; ++j) st16<SP>(reinterpret_cast<u32x4_t*>(a.outx[j]) + v, acc + (uint32_t)(j + 2));
 }
 
 // ---- helpers -----------------------------------------------------------------------------------------------------------
@@ -394,7 +398,9 @@ struct Scenario {
   std::vector<void*> o0, o1;
   uint64_t* seeds = nullptr;
   bool out0_unwritten = false;   // (read-only ceilings: the buffer exists, nothing is stored)
-  double bytes_per_launch() const { return (double)numel * (2.0 * n16 + 4.0 * n32 + (out0_unwritten ? 0 : out0_bytes) + out1_bytes); }
+  int n_extra = 0;               // further bf16 outputs (outx)
+  std::vector<std::vector<void*>> ox;
+  double bytes_per_launch() const { return (double)numel * (2.0 * n16 + 4.0 * n32 + (out0_unwritten ? 0 : out0_bytes) + out1_bytes + 2.0 * n_extra); }
   void alloc() {
     for (int s = 0; s < nsets; ++s) {
       std::vector<void*> v;
@@ -405,6 +411,9 @@ struct Scenario {
       if (out0_bytes) CK(hipMalloc(&a, numel * out0_bytes + (4 << 20)));
       if (out1_bytes) CK(hipMalloc(&b, numel * out1_bytes + (4 << 20)));
       o0.push_back(a); o1.push_back(b);
+      std::vector<void*> x;
+      for (int j = 0; j < n_extra; ++j) { void* p; CK(hipMalloc(&p, numel * 2 + (4 << 20))); x.push_back(p); }
+      ox.push_back(x);
     }
     const int64_t batch = numel / sample;
     std::vector<uint64_t> h(batch);
@@ -417,8 +426,9 @@ struct Scenario {
     for (auto& v : in) for (void* p : v) CK(hipFree(p));
     for (void* p : o0) if (p) CK(hipFree(p));
     for (void* p : o1) if (p) CK(hipFree(p));
+    for (auto& v : ox) for (void* p : v) CK(hipFree(p));
     CK(hipFree(seeds));
-    in.clear(); o0.clear(); o1.clear();
+    in.clear(); o0.clear(); o1.clear(); ox.clear();
   }
 };
 
@@ -460,6 +470,7 @@ static void run_scenario(Scenario& sc, std::vector<Variant>& vars, int want_lr =
     auto go = [&](int s) {
       for (size_t j = 0; j < sc.in[s].size(); ++j) a.in[j] = sc.in[s][j];
       a.out0 = sc.o0[s] ? (char*)sc.o0[s] + g_off0 : nullptr; a.out1 = sc.o1[s] ? (char*)sc.o1[s] + g_off1 : nullptr;
+      for (int j = 0; j < 3; ++j) a.outx[j] = j < sc.n_extra ? sc.ox[s][j] : nullptr;
       v.launch(a, (unsigned)chunks);
     };
     // correctness: set 0
@@ -528,6 +539,26 @@ static Variant lib_variant(const std::string& name, int kind, int n16, int n32, 
   }};
 }
 
+// the shipped transposed step (skr_step_backward_launch) on the same buffers: in[0] (and in[1]) are the incoming bf16 gradients,
+// out0, out1, outx[] the operand gradients (bf16, one-trip kernel)
+typedef int (*bwd_fn)(const skr_step_grad_plan*, const void*, const void*, void* const*, int64_t, void*);
+static Variant lib_backward_variant(const std::string& name, int reads, int writes, int64_t numel) {
+  load_lib();
+  const char* path = getenv("SKR_LIB") ? getenv("SKR_LIB") : "skrample_amd/csrc/libskrample_hip.so";
+  bwd_fn fn = (bwd_fn)dlsym(dlopen(path, RTLD_NOW), "skr_step_backward_launch");
+  if (!fn) { printf("no skr_step_backward_launch in %s\n", path); exit(1); }
+  auto plan = std::make_shared<skr_step_grad_plan>();
+  memset(plan.get(), 0, sizeof(skr_step_grad_plan));
+  plan->n_grads = writes; plan->n_group_a = writes; plan->dtype_a = SKR_BF16; plan->dtype_b = SKR_BF16;
+  plan->g0_dtype = SKR_BF16; plan->g1_dtype = reads == 2 ? SKR_BF16 : SKR_NONE;
+  for (int k = 0; k < writes; ++k) { plan->a[k] = 0.5 + 0.1 * k; plan->b[k] = -0.3 + 0.05 * k; }
+  return Variant{name, 2048, [plan, fn, numel, reads, writes](const Args& a, unsigned) {
+    void* grads[5] = {a.out0, a.out1, a.outx[0], a.outx[1], a.outx[2]};
+    const int st = fn(plan.get(), a.in[0], reads == 2 ? a.in[1] : nullptr, grads, numel, nullptr);
+    if (st) { printf("skr_step_backward_launch failed: %d\n", st); exit(1); }
+  }};
+}
+
 #define KU(K, NO, BLK, UV, SP0, SP1, PACE, NOISE, ORDER) \
   Variant{"ku<K" #K ",NO" #NO ",B" #BLK ",UV" #UV ",sp" #SP0 #SP1 ",pace" #PACE ",n" #NOISE ",ord" #ORDER ">", BLK * UV * 8, \
           [](const Args& a, unsigned chunks) { hipLaunchKernelGGL((ku<K, NO, BLK, UV, SP0, SP1, PACE, NOISE, ORDER>), dim3(chunks), dim3(BLK), 0, 0, a); }}
@@ -583,6 +614,12 @@ int main(int argc, char** argv) {
     { Scenario sc{"bigk18", 256 * S4, S4, 18, 0, 2, 0, 2}; std::vector<Variant> v = {KU(18, 1, 256, 1, 2, 2, 0, 0, 0), lib_variant("LIB K=18", 0, 18, 0, false, sc.numel, sc.sample)}; run_scenario(sc, v); }
     { Scenario sc{"k1", 256 * S4, S4, 1, 0, 2, 0, 8}; std::vector<Variant> v = {KU(1, 1, 256, 1, 2, 2, 0, 0, 0), lib_variant("LIB K=1", 0, 1, 0, false, sc.numel, sc.sample), KMIX(1, 1, 256, 2), KU(1, 1, 128, 1, 2, 2, 0, 0, 0), KU(1, 1, 512, 1, 2, 2, 0, 0, 0)}; run_scenario(sc, v); }
     { Scenario sc{"k2", 256 * S4, S4, 2, 0, 2, 0, 8}; std::vector<Variant> v = {KU(2, 1, 256, 1, 2, 2, 0, 0, 0), lib_variant("LIB K=2", 0, 2, 0, false, sc.numel, sc.sample), KMIX(2, 1, 256, 2), KU(2, 1, 128, 1, 2, 2, 0, 0, 0), KU(2, 1, 512, 1, 2, 2, 0, 0, 0)}; run_scenario(sc, v); }
+    return 0;
+  }
+  if (g_only.rfind("bwd", 0) == 0) {  // the transposed step's traffic mixes at the headline size, > 1 GB of rotating buffers per scenario
+    g_only = "";
+    { Scenario sc{"bwd_r1w4", 256 * S4, S4, 1, 0, 2, 2, 8}; sc.n_extra = 2; std::vector<Variant> v = {lib_backward_variant("LIB backward 1 in 4 out", 1, 4, sc.numel), KMIX(1, 4, 256, 2), KMIX(1, 4, 256, 0)}; run_scenario(sc, v); }
+    { Scenario sc{"bwd_r2w5", 256 * S4, S4, 2, 0, 2, 2, 6}; sc.n_extra = 3; std::vector<Variant> v = {lib_backward_variant("LIB backward 2 in 5 out", 2, 5, sc.numel), KMIX(2, 5, 256, 2), KMIX(2, 5, 256, 0)}; run_scenario(sc, v); }
     return 0;
   }
   if (g_only.rfind("phase", 0) == 0) {

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 14
+#define SKR_ABI_VERSION 15
 #define SKR_MAX_TERMS 80 /* 2 x 35-stage tableau pairs + base + noise, see skr_step_plan */
 
 /* Devices and streams: every entry point launches on the device that owns its output buffer (queried from the pointer when
@@ -153,6 +153,26 @@ typedef struct skr_step_row {
 int skr_step_launch_indexed(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
                             const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
                             const int32_t* index_dev /* device int32, may be NULL */, int32_t row_offset, void* stream);
+
+/*
+ * Per-sample rows: the same launch with one index PER SAMPLE.  The batch is numel / plan->sample_numel samples, sample_index_dev
+ * holds that many device int32, and the workgroups of sample s read
+ *     row = rows_dev[sample_index_dev[s] + row_offset]
+ * so every sample of one launch follows its own resident schedule (another shift, sigma family, stochasticity or begin index per
+ * request of a batch).  A sample whose row has zeta = 0 skips its draw while its batch neighbours draw; Philox stays keyed by the
+ * sample's seed and the element's position within the sample, so a sample's result is bit-identical to what
+ * skr_step_launch_indexed gives it with that row for the whole batch.
+ * Covered: what skr_step_launch_indexed covers, and a workgroup must lie inside one sample: plan->sample_numel must be a positive
+ * multiple of 2048 that divides numel, with or without noise (SKR_ERR_SHAPE / SKR_ERR_UNSUPPORTED otherwise).  A NULL
+ * sample_index_dev is SKR_ERR_NULL.
+ * Index validity is the caller's business, as with index_dev: every sample_index_dev[s] + row_offset must name a row of the
+ * table.  The kernel neither checks nor clamps an index -- an entry outside the table reads whatever lies there (or faults) --
+ * so validate on the host before uploading (skrample_amd.graphs.CapturedLoop does).
+ */
+int skr_step_launch_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
+                                       const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                       const int32_t* sample_index_dev /* device int32[numel / sample_numel] */, int32_t row_offset,
+                                       void* stream);
 
 /*
  * Step programs -- a plan the library keeps, launched by handle.  Replaces the per-step host work of a REPLAYED step

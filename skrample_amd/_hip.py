@@ -14,7 +14,7 @@ import threading
 import torch
 
 MAX_TERMS = 80
-ABI_VERSION = 14
+ABI_VERSION = 15
 SKR_ERR_UNSUPPORTED = 7  # include/skrample_hip.h: valid request outside what the fast kernels cover
 
 BF16, F16, F32, F64, NONE = 0, 1, 2, 3, -1
@@ -28,6 +28,7 @@ LIB_PATH = os.environ.get("SKR_HIP_LIB") or os.path.join(os.path.dirname(os.path
 EXPORTS = (
     "skr_step_launch",
     "skr_step_launch_indexed",
+    "skr_step_launch_indexed_per_sample",
     "skr_step_backward_launch",
     "skr_program_create",
     "skr_program_launch",
@@ -120,6 +121,7 @@ class TapeC(ctypes.Structure):
 
 
 ROW_TERMS = 16  # include/skrample_hip.h SKR_ROW_TERMS
+PER_SAMPLE_CHUNK = 2048  # elements per workgroup of the one-trip kernels: a sample of a per-sample launch is made of whole ones
 
 
 class StepRowC(ctypes.Structure):
@@ -146,18 +148,23 @@ def plan_structure(plan: StepPlanC) -> tuple:
 class IndexedRows:
     """Device-resident step scalars of a captured sampling loop (skr_step_launch_indexed).
 
+    `batch` (a per-sample capture): the emitted launches are skr_step_launch_indexed_per_sample launches, and `sample_index_dev`
+    -- int32[batch], beside `index_dev` -- holds every sample's `slot * length`; sample b of the captured batch reads row
+    `sample_index_dev[b] + k`.
+
     mode "record": launches run normally and append one row each (their structure is remembered);
     mode "emit"  : launches become indexed launches reading row `base + k` (k = position in the loop) -- used under graph capture;
     mode "refill": launches run normally (on whatever tensors the dry run uses) and overwrite row `slot*length + k` after checking
                    that the structure is the captured one -- how a captured loop is re-targeted to another schedule."""
 
-    def __init__(self, device: torch.device, slots: int = 4):
-        self.device, self.slots = device, slots
+    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None):
+        self.device, self.slots, self.batch = device, slots, batch
         self.mode, self.cursor, self.length = "record", 0, 0
         self.structures: list[tuple] = []
         self.host: list[StepRowC] = []
         self.rows_dev: torch.Tensor | None = None
         self.index_dev = torch.zeros(1, dtype=torch.int32, device=device)
+        self.sample_index_dev = torch.zeros(batch, dtype=torch.int32, device=device) if batch is not None else None
         self.slot = 0
 
     @staticmethod
@@ -185,6 +192,14 @@ class IndexedRows:
         staging = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
         self.rows_dev[slot * self.length * size : (slot + 1) * self.length * size].copy_(staging, non_blocking=False)
 
+    def sample_indices(self, sample_slots) -> torch.Tensor:
+        "host int32[batch] of `slot * length`: what `sample_index_dev` must hold for the samples to follow these slots"
+        return torch.as_tensor(list(sample_slots), dtype=torch.int64).mul(self.length).to(torch.int32)
+
+    def select(self, sample_slots) -> None:
+        "publish the slot of every sample (validated by the caller): one small stream-ordered host-to-device copy"
+        self.sample_index_dev.copy_(self.sample_indices(sample_slots))
+
     def begin(self, mode: str, slot: int = 0) -> None:
         self.mode, self.cursor, self.slot = mode, 0, slot
         if mode == "refill":
@@ -196,6 +211,10 @@ class IndexedRows:
         k = self.cursor
         self.cursor += 1
         if self.mode == "record":
+            if self.batch is not None and (numel % self.batch != 0 or (numel // self.batch) % PER_SAMPLE_CHUNK != 0):
+                # (what skr_step_launch_indexed_per_sample would answer during the capture: said here, before a stream is capturing)
+                raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, "
+                                       f"not {numel} elements for {self.batch} samples")
             self.structures.append(plan_structure(plan))
             self.host.append(self.row_from(plan))
             return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
@@ -208,6 +227,13 @@ class IndexedRows:
             return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
         if plan_structure(plan) != self.structures[k]:
             raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
+        if self.sample_index_dev is not None:
+            if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
+                plan = StepPlanC.from_buffer_copy(plan)
+                plan.sample_numel = numel // self.batch
+            if numel != self.batch * plan.sample_numel:
+                raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {self.batch} samples of {plan.sample_numel} the per-sample index holds")
+            return lib.skr_step_launch_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
         return lib.skr_step_launch_indexed(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
 
 
@@ -281,6 +307,8 @@ def load() -> ctypes.CDLL:
         lib.skr_step_launch.restype = ctypes.c_int
         lib.skr_step_launch_indexed.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
         lib.skr_step_launch_indexed.restype = ctypes.c_int
+        lib.skr_step_launch_indexed_per_sample.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
+        lib.skr_step_launch_indexed_per_sample.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
         lib.skr_step_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]

@@ -60,10 +60,12 @@ struct StepArgs {
   int32_t grid_mode;    // 0 flat grid, 1 per-sample grid (noise kernels, sample_numel % 8 == 0)
   int32_t conv_to, conv_from;  // rounded pair conversion (CONV kernels): see convert_rounded()
   double ck[4];
-  // skr_step_launch_indexed: the scalars above are read from rows[index[0] + row_offset] by the kernel (one-trip kernels only)
+  // skr_step_launch_indexed: the scalars above are read from rows[index[0] + row_offset] by the kernel (one-trip kernels only);
+  // per_sample (skr_step_launch_indexed_per_sample): from rows[index[sample] + row_offset], index holding one entry per sample
   const skr_step_row* rows;
   const int32_t* index;
   int32_t row_offset;
+  int32_t per_sample;
 };
 
 // device-resident scalars of a launch (skr_step_launch_indexed); rows == nullptr: use the kernarg values

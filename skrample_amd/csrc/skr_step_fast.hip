@@ -38,13 +38,41 @@ __device__ __forceinline__ void sample_of(uint32_t c, int32_t bps_shift, uint32_
   else { const uint32_t bps = (uint32_t)(-bps_shift); smp = c / bps; within = c - smp * bps; }
 }
 
+// Per-sample rows (skr_step_launch_indexed_per_sample) are a compile-time form of the TAB instantiations, selected by wrapping the
+// element type: step_kernel_k1<PerSample<bf16_t>, ...> is step_kernel_k1<bf16_t, ...> with the row chosen by the workgroup's sample.
+// (A tag on an existing parameter, not a new one: the kernels that existed before keep their symbols and their instruction streams,
+// which tests/test_per_sample_isa.py and the headline number rely on.)
+template <typename T> struct PerSample {};
+template <typename T> struct RowsBy { using elem = T; static constexpr bool per_sample = false; };
+template <typename T> struct RowsBy<PerSample<T>> { using elem = T; static constexpr bool per_sample = true; };
+
+// The device-resident row of chunk c (TAB instantiations).  PER_SAMPLE: index holds one entry per sample and a workgroup reads its
+// own sample's -- launches of whole chunks per sample only, so the sample, and with it the row, zeta and the draw / no-draw branch,
+// is uniform over the workgroup.  The sample id goes through readfirstlane (the dividing form of sample_of runs on the vector ALU):
+// the index fetch and the row fetch stay scalar loads, two dependent ones as in the whole-batch form.  No bounds check, no clamp.
+template <bool PER_SAMPLE>
+__device__ __forceinline__ const skr_step_row* row_at(const RowRef& r, uint32_t c, int32_t bps_shift) {
+  if constexpr (PER_SAMPLE) {
+    // sample_of without its branch: ahead of the row fetch a branch made the compiler hoist the division above the operand loads
+    // and issue them once per arm.  Shift and divide instead (one of the two is by 0 / by 1): ~25 scalar-path instructions behind the loads.
+    const uint32_t smp = (c >> (bps_shift < 0 ? 0 : bps_shift)) / (bps_shift < 0 ? (uint32_t)(-bps_shift) : 1u);
+    // (the NULL test of row_of is kept although the entry point refuses a NULL index: the branch ends the basic block where the
+    //  whole-batch form ends it, and instruction selection, which works block by block, then gives both forms the same registers --
+    //  as one block, ten instantiations of 11+ operands took up to 25 more VGPRs and lost one to three waves per SIMD)
+    return r.rows + ((r.index != nullptr ? r.index[__builtin_amdgcn_readfirstlane(smp)] : 0) + r.row_offset);
+  } else {
+    return row_of(r);
+  }
+}
+
 
 // kernarg sizes: 4 / 8 / 12 / 16 / 20 operand slots (Adams-Bashforth 5-9 and UniP >= 5 give 10-18 operands: round 3)
 constexpr int one_trip_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 16 ? 16 : 20))); }
 constexpr int ONE_TRIP_MAX_K = 20;
 
-template <typename T, int K, bool NOISE, bool TILE, bool PACE, bool TAB>
+template <typename TR, int K, bool NOISE, bool TILE, bool PACE, bool TAB>  // TR: the element type, or PerSample<element type> (TAB only)
 __global__ __launch_bounds__(BLOCK) void step_kernel_k1(const OneTripArgs<one_trip_kmax(K)> a) {
+  using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
   Raw<T> raw[K];
@@ -60,7 +88,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k1(const OneTripArgs<one_tr
   zeta0 = a.zeta0; stream0 = a.stream0;                                      \
   _Pragma("unroll") for (int j = 0; j < K; ++j) cf[j] = a.c0[j];             \
   if constexpr (TAB) {                                                       \
-    const skr_step_row* row = row_of(a.tab);                                 \
+    const skr_step_row* row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift); \
     _Pragma("unroll") for (int j = 0; j < K; ++j) cf[j] = (float)row->coef0[j]; \
     zeta0 = (float)row->zeta0;                                               \
     stream0 = row->stream0;                                                  \
@@ -165,8 +193,9 @@ struct RkOneTripArgs {
 
 // NOISE: the step's last stage of a stochastic tableau step adds zeta1 * N(stream1) to out1 (the derivative out0 is never noisy)
 // BLK: threads per workgroup (256, or 128 = 1024-element chunks: tools/tune/tune_r3.hip measured the 5-operand stage 1-4 % faster so)
-template <typename T, int K, bool TILE, bool NOISE, bool TAB, int BLK>
+template <typename TR, int K, bool TILE, bool NOISE, bool TAB, int BLK>  // TR: as for step_kernel_k1
 __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <= 4 ? 4 : 8)> a) {
+  using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLK + threadIdx.x;
   Raw<T> raw[K];
@@ -178,7 +207,7 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
 #pragma unroll
   for (int j = 0; j < K; ++j) cf[j] = a.c1[j];
   if constexpr (TAB) {
-    const skr_step_row* row = row_of(a.tab);
+    const skr_step_row* row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift);
 #pragma unroll
     for (int j = 0; j < K; ++j) cf[j] = (float)row->coef1[j];
 #pragma unroll
@@ -224,11 +253,12 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
 }
 
 // one-trip launches: whole chunks, and with in-kernel noise samples made of whole chunks (any number of them)
-static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, int* bps_shift, bool forced = false) {
+// (per-sample rows: a workgroup must belong to one sample with or without noise)
+static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, int* bps_shift, bool forced = false, bool per_sample = false) {
   constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
   if ((!g_tune.one_trip && !forced) || numel % CHUNK != 0 || numel / CHUNK > 0x7fffffffll) return false;
   *bps_shift = 0;
-  if (!noise) return true;
+  if (!noise && !per_sample) return true;
   if (sample_numel % CHUNK != 0) return false;
   const int64_t bps = sample_numel / CHUNK;
   if (bps > 0x3fffffffll) return false;
@@ -248,11 +278,15 @@ static int launch_k1(const StepArgs<float>& args, int bps_shift, hipStream_t str
   fa.out0 = args.out0; fa.seeds = args.seeds; fa.zeta0 = args.zeta0; fa.stream0 = args.stream0;
   fa.bps_shift = bps_shift; fa.xmap_lr = xmap_lr_for(chunks);
   fa.tab = RowRef{args.rows, args.index, args.row_offset};
-#define SKR_K(N) case N: if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+#define SKR_K(N) case N: if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+                        else if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                         else if (g_tune.pace) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                         else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); break
   // more than 8 operands: one unpaced instantiation each (plus the table form while the operands fit a device-resident row)
-#define SKR_KB(N) case N: if (args.rows != nullptr) { if constexpr (N <= SKR_ROW_TERMS) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); else return SKR_ERR_UNSUPPORTED; } \
+#define SKR_KB(N) case N: if (args.rows != nullptr) { if constexpr (N <= SKR_ROW_TERMS) { \
+                           if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+                           else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+                         } else return SKR_ERR_UNSUPPORTED; } \
                          else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); break
   if constexpr (KMAX == 4) { switch (args.n_terms) { SKR_K(1); SKR_K(2); SKR_K(3); SKR_K(4); } }
   else if constexpr (KMAX == 8) { switch (args.n_terms) { SKR_K(5); SKR_K(6); SKR_K(7); SKR_K(8); } }
@@ -269,7 +303,7 @@ template <typename T>
 int launch_one_trip_k(const StepArgs<float>& args, bool noise, hipStream_t stream, bool& taken) {
   taken = false;
   int bps_shift = 0;
-  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr) || (sizeof(T) == 4 && !g_tune.tile && args.rows == nullptr)) return SKR_OK;
+  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr, args.per_sample != 0) || (sizeof(T) == 4 && !g_tune.tile && args.rows == nullptr)) return SKR_OK;
   if (args.n_terms > ONE_TRIP_MAX_K) return SKR_OK;
   taken = true;
 #define SKR_GO(NOISE)                                                              \
@@ -301,7 +335,8 @@ static int launch_rk1(const StepArgs<float>& args, unsigned chunks, int bps_shif
   ra.out0 = args.out0; ra.out1 = args.out1; ra.chain = args.chain;
   for (int i = 0; i < 4; ++i) ra.ck[i] = (float)args.ck[i];
   ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.xmap_lr = xmap_lr_for(chunks); ra.tab = RowRef{args.rows, args.index, args.row_offset};
-#define SKR_K(N) case N: if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
+#define SKR_K(N) case N: if (args.per_sample) hipLaunchKernelGGL((step_kernel_rk1<PerSample<T>, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
+                        else if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
                         else hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, false, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); break
   if constexpr (KMAX == 4) { switch (args.n_terms) { SKR_K(2); SKR_K(3); SKR_K(4); } }
   else { switch (args.n_terms) { SKR_K(5); SKR_K(6); SKR_K(7); SKR_K(8); } }
@@ -314,7 +349,7 @@ template <typename T>
 int launch_one_trip_rk(const StepArgs<float>& args, bool noise, hipStream_t stream, bool& taken) {
   taken = false;
   int bps_shift = 0;
-  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr) || (sizeof(T) == 4 && !g_tune.tile && args.rows == nullptr)) return SKR_OK;
+  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr, args.per_sample != 0) || (sizeof(T) == 4 && !g_tune.tile && args.rows == nullptr)) return SKR_OK;
   if (noise && args.rows == nullptr && args.zeta0 != 0.f) return SKR_OK;  // (a noisy derivative does not occur; left to the general kernel)
   taken = true;
   const unsigned chunks = (unsigned)(args.numel / ((int64_t)BLOCK * VEC));
@@ -358,8 +393,9 @@ struct TwoOutArgs {
 constexpr int NT_FROM_OPERANDS = 9;
 constexpr int two_out_nmax(int n) { return n <= 4 ? 4 : (n <= 8 ? 8 : (n <= 12 ? 12 : (n <= 16 ? 16 : (n <= 20 ? 20 : 24)))); }
 
-template <typename TA, int NA, int NB, bool NOISE, bool PACE, bool TAB, bool NT = false>
+template <typename TR, int NA, int NB, bool NOISE, bool PACE, bool TAB, bool NT = false>  // TR: as for step_kernel_k1
 __global__ __launch_bounds__(BLOCK) void step_kernel_k2(const TwoOutArgs<two_out_nmax(NA + NB)> a) {
+  using TA = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
   Raw<TA> ra[NA];
@@ -373,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k2(const TwoOutArgs<two_out
   chain = a.chain; zeta0 = a.zeta0; zeta1 = a.zeta1; stream0 = a.stream0; stream1 = a.stream1; \
   _Pragma("unroll") for (int j = 0; j < NA + NB; ++j) { cf0[j] = a.c0[j]; cf1[j] = a.c1[j]; } \
   if constexpr (TAB) {                                                                     \
-    const skr_step_row* row = row_of(a.tab);                                               \
+    const skr_step_row* row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift);       \
     _Pragma("unroll") for (int j = 0; j < NA + NB; ++j) { cf0[j] = (float)row->coef0[j]; cf1[j] = (float)row->coef1[j]; } \
     chain = (float)row->chain; zeta0 = (float)row->zeta0; zeta1 = (float)row->zeta1;       \
     stream0 = row->stream0; stream1 = row->stream1;                                        \
@@ -480,6 +516,12 @@ static int launch_k2(const StepArgs<float>& args, int bps_shift, hipStream_t str
   ta.stream0 = args.stream0; ta.stream1 = args.stream1;
   ta.chain = args.chain; ta.zeta0 = args.zeta0; ta.zeta1 = args.zeta1;
   ta.tab = RowRef{args.rows, args.index, args.row_offset};
+  if constexpr (TAB && !NT) {
+    if (args.per_sample) {
+      hipLaunchKernelGGL((step_kernel_k2<PerSample<TA>, NA, NB, NOISE, PACE, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
+      return finish_launch();
+    }
+  }
   hipLaunchKernelGGL((step_kernel_k2<TA, NA, NB, NOISE, PACE, TAB, NT>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
   return finish_launch();
 }
@@ -498,7 +540,7 @@ int launch_one_trip_two(const StepArgs<float>& args, bool noise, bool group_b_f3
   // (193 vs 197 us at 4+1, 239 vs 241 us at 6+1); from 8+1 on, and without noise, this kernel wins (344 vs 365 us at 10+1)
   if (noise && na + nb <= 7 && g_tune.two_out != 2 && args.rows == nullptr) return SKR_OK;
   int bps_shift = 0;
-  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr)) return SKR_OK;
+  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr, args.per_sample != 0)) return SKR_OK;
 #define SKR_GO(A, B)                                                                             \
   if (na == A && nb == B) {                                                                      \
     taken = true;                                                                                \

@@ -16,6 +16,12 @@ device-resident index (`loop(latents, slot=k)`).  The network's timestep argumen
 `for t in scheduler.timesteps` does, and re-targeting / switching slots rewrites that tensor -- a host float would be frozen into
 the captured network.  The reference redoes this work on the host every step, with a device sync
 (skrample/diffusers.py:565-567, skrample/scheduling.py:51-62, skrample/sampling/interface.py:34-59).
+
+`per_sample=True` (with `indexed=True`) makes the schedule per SAMPLE: the index becomes an int32 vector with one entry per sample
+(`skr_step_launch_indexed_per_sample`), and `loop(latents, slot=[2, 0, 1, ...])` lets every sample of one replay follow its own
+resident schedule -- a batch of requests with different shifts, sigma families, stochasticities or begin indices in one launch per
+step.  With `device_timesteps` the network's `t` is then a 1-D tensor of shape `[batch]` (row i of one `[steps, batch]` device
+tensor), the per-sample form diffusers models accept.  A sample's result is bit-identical to the one the whole-batch `slot=k` gives it.
 """
 
 from __future__ import annotations
@@ -30,7 +36,7 @@ class CapturedLoop:
     "replayable sampling loop: `out = loop(initial_latents, seeds=None)`"
 
     def __init__(self, graph: torch.cuda.CUDAGraph, static_in: torch.Tensor, static_out: torch.Tensor, seeds_dev: torch.Tensor | None, rows=None, runner=None,
-                 static_times: torch.Tensor | None = None):
+                 static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None):
         self.graph, self.static_in, self.static_out, self.seeds_dev = graph, static_in, static_out, seeds_dev
         self.rows, self._runner = rows, runner  # _hip.IndexedRows of an indexed capture; runner(wrapper, x) = the captured loop body
         self._filled = {0}  # table slots that hold a schedule (the capture itself fills slot 0; the others start as zero rows)
@@ -38,10 +44,46 @@ class CapturedLoop:
         self.static_times = static_times
         self._times = {0: static_times.detach().cpu().clone()} if static_times is not None else {}
         self._times_slot = 0
+        # per-sample capture: the [steps, batch] tensor whose rows the network reads as `t`, and the slot every sample follows now
+        self.sample_times = sample_times
+        self._sample_slots = [0] * self.batch if self.per_sample else None
 
     @property
     def slots(self) -> int:
         return self.rows.slots if self.rows is not None else 1
+
+    @property
+    def per_sample(self) -> bool:
+        "captured with per_sample=True: `slot` may name a schedule slot for every sample"
+        return self.rows is not None and getattr(self.rows, "sample_index_dev", None) is not None
+
+    @property
+    def batch(self) -> int:
+        return int(self.static_in.shape[0])
+
+    def _check_slots(self, slot) -> list[int]:
+        "a per-sample slot argument as a validated list (host only: nothing is enqueued before every entry is known to be good)"
+        if isinstance(slot, torch.Tensor):
+            if slot.device.type != "cpu" or slot.dtype.is_floating_point or slot.dtype in (torch.bool, torch.complex64, torch.complex128) or slot.dim() != 1:
+                raise ValueError("per-sample slots are a host sequence or a 1-D CPU integer tensor (a device tensor could not be validated without a sync)")
+            slot = slot.tolist()
+        chosen = [int(k) for k in slot]
+        if len(chosen) != self.batch:
+            raise ValueError(f"{len(chosen)} slots for a captured batch of {self.batch}")
+        for k in chosen:
+            if not 0 <= k < self.rows.slots:
+                raise ValueError(f"slot {k} outside 0..{self.rows.slots - 1}")
+            if k not in self._filled:
+                raise ValueError(f"schedule slot {k} has never been loaded: call retarget(wrapper, slot={k}) first (its rows are all zero)")
+        return chosen
+
+    def _assemble_times(self, chosen: Sequence[int]) -> torch.Tensor:
+        "host [steps, batch]: column b holds the timesteps of the slot sample b follows (from the per-slot copies in `_times`)"
+        return torch.stack([self._times[k] for k in chosen], dim=1)
+
+    def _publish_sample_times(self) -> None:
+        if self.sample_times is not None:
+            self.sample_times.copy_(self._assemble_times(self._sample_slots))  # one copy, stream-ordered ahead of the replay
 
     def retarget(self, wrapper, slot: int = 0) -> None:
         """Load the step scalars of `wrapper` (same sampler structure and number of steps as the captured one, any schedule /
@@ -70,15 +112,36 @@ class CapturedLoop:
             self._times[slot] = times.clone()
             if slot == self._times_slot:
                 self.static_times.copy_(self._times[slot])
+            if self.sample_times is not None and slot in self._sample_slots:
+                self._publish_sample_times()  # the columns of the samples that follow this slot
 
-    def __call__(self, latents: torch.Tensor, seeds: Sequence[int] | None = None, slot: int | None = None) -> torch.Tensor:
+    def __call__(self, latents: torch.Tensor, seeds: Sequence[int] | None = None, slot: int | Sequence[int] | torch.Tensor | None = None) -> torch.Tensor:
+        """Replay on `latents`.  `slot`: the resident schedule to follow -- an int for the whole batch; on a loop captured with
+        `per_sample=True` also a host sequence or 1-D CPU integer tensor with one slot per sample."""
+        chosen = None
+        if slot is not None and not isinstance(slot, int):
+            if not self.per_sample:
+                raise ValueError("one slot per sample needs a loop captured with capture_sampling_loop(..., indexed=True, per_sample=True)")
+            chosen = self._check_slots(slot)
         self.static_in.copy_(latents)
-        if slot is not None:
+        if chosen is not None:
+            self.rows.select(chosen)  # sample b reads row slot[b] * length + position in the loop
+            if self.sample_times is not None and chosen != self._sample_slots:
+                self._sample_slots = chosen
+                self._publish_sample_times()
+            self._sample_slots = chosen
+        elif slot is not None:
             if self.rows is None or not 0 <= slot < self.rows.slots:
                 raise ValueError("no such schedule slot")
             if slot not in self._filled:
                 raise ValueError(f"schedule slot {slot} has never been loaded: call retarget(wrapper, slot={slot}) first (its rows are all zero)")
             self.rows.index_dev.fill_(slot * self.rows.length)  # the device-resident step index: row = index + position in the loop
+            if self.per_sample:
+                self.rows.sample_index_dev.fill_(slot * self.rows.length)
+                if self.sample_times is not None and self._sample_slots != [slot] * self.batch:
+                    self._sample_slots = [slot] * self.batch
+                    self._publish_sample_times()
+                self._sample_slots = [slot] * self.batch
             if self.static_times is not None and slot != self._times_slot:
                 self.static_times.copy_(self._times[slot])  # what the network reads as `t` (stream-ordered ahead of the replay)
                 self._times_slot = slot
@@ -131,12 +194,12 @@ class CapturedLoops:
         "run lengths whose graphs are resident, least recently used first"
         return tuple(self._loops)
 
-    def __call__(self, latents: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, slot: int | None = None) -> torch.Tensor:
+    def __call__(self, latents: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, slot: int | Sequence[int] | torch.Tensor | None = None) -> torch.Tensor:
         return self.loop(steps)(latents, seeds, slot)
 
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
-                          indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None) -> CapturedLoop:
+                          indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False) -> CapturedLoop:
     """Capture `for t in wrapper.timesteps: x = wrapper.step(model(x, t), t, x)` for `steps` steps.
 
     `wrapper` is any scheduler wrapper of skrample_amd.diffusers; `model(x, t)` must be capturable (pure device
@@ -146,17 +209,24 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     `device_timesteps` (default: the value of `indexed`): `t` is a 0-d element of the scheduler's device-resident `timesteps`
     tensor -- located by the wrapper through its storage offset, no read-back -- instead of a host float; the network then
     follows a re-targeted schedule, because the tensor's contents are replaced with the rows.
+
+    `per_sample` (needs `indexed=True`; off by default, and then nothing changes): every sample of a replay may follow its own slot,
+    `loop(latents, slot=[...])`; with `device_timesteps` the network receives a 1-D `t` of shape `[batch]`.  Needs latents of whole
+    2048-element chunks per sample.  `slots` may be as large as the batch (one schedule per request): the table is
+    `slots * launches per loop * 328 bytes` of device memory -- 256 slots of a 30-launch loop are 2.5 MB.
     """
+    if per_sample and not indexed:
+        raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
     from .pytorch import noise as _noise
 
     _noise._private_vectors[0] += 1  # the loop's seed vector is overwritten in place by replays with new seeds: it is this loop's alone
     try:
-        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps)
+        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample)
     finally:
         _noise._private_vectors[0] -= 1
 
 
-def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps) -> CapturedLoop:
+def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False) -> CapturedLoop:
     dev = example.device
     static_in = example.clone()
     gen = list(seeds) if seeds is not None else None
@@ -172,11 +242,14 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         times = [static_times[i] for i in range(static_times.numel())]
     else:
         times = wrapper.timesteps.tolist()
+    # per-sample: the network's `t` is row i of one [steps, batch] device tensor; the wrapper keeps its own 0-d timesteps[i]
+    sample_times = static_times.detach().clone().unsqueeze(1).repeat(1, example.shape[0]).contiguous() if per_sample and device_timesteps else None
+    model_times = [sample_times[i] for i in range(sample_times.shape[0])] if sample_times is not None else times
 
     def run(x):
         wrapper.reset_run()  # same schedule, same device seed vector; history and draw counter rewound
-        for t in times:
-            x = wrapper.step(model(x, t), t, x, generator=gen, return_dict=False)[0]
+        for t, tm in zip(times, model_times):
+            x = wrapper.step(model(x, tm), t, x, generator=gen, return_dict=False)[0]
         return x
 
     def run_other(other, x):  # the same loop body on another scheduler instance (re-targeting dry run, one sample)
@@ -184,7 +257,8 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         sub = gen[: x.shape[0]] if gen is not None else None
         ts = other.timesteps
         for t in ([ts[i] for i in range(ts.numel())] if device_timesteps else ts.tolist()):
-            x = other.step(model(x, t), t, x, generator=sub, return_dict=False)[0]
+            tm = t.reshape(1).expand(x.shape[0]) if sample_times is not None else t  # (the dry run's samples: `t` of shape [1])
+            x = other.step(model(x, tm), t, x, generator=sub, return_dict=False)[0]
         return x
 
     side = torch.cuda.Stream(device=dev)
@@ -201,7 +275,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     if indexed:
         from . import _hip
 
-        rows = _hip.IndexedRows(dev, slots=slots)
+        rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None)
         _hip.indexed = rows
         try:
             rows.begin("record")
@@ -224,4 +298,4 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     from .pytorch.noise import forget_seed_vector
 
     forget_seed_vector(seeds_dev)  # the graph reads this very buffer and replays may overwrite it: no other run may share it from now on
-    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times)
+    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times)

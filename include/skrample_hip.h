@@ -175,6 +175,27 @@ int skr_step_launch_indexed_per_sample(const skr_step_plan* plan, const void* co
                                        void* stream);
 
 /*
+ * Rolling batches (continuous batching): skr_step_launch_indexed_per_sample with samples that may sit at different positions of
+ * their loops, or be absent.  Contract, coverage and error codes are those of skr_step_launch_indexed_per_sample; on top of them
+ *   inactive sample  sample_index_dev[s] < 0 (tested before row_offset is added): the workgroups of sample s return before their
+ *                    first vector-memory instruction.  Nothing of that sample is read; out0 / out1 keep their bytes there.
+ *   absent operand   an operand k whose coef0[k] and coef1[k] are both exactly zero (+0 or -0) in the sample's row is not loaded and
+ *                    adds nothing to either output: its bytes may be anything, NaN and inf included (the slot's previous occupant).
+ *                    The pair of a rounded conversion (operands 0 and 1 when plan->convert_to / convert_from is set) is always
+ *                    loaded.  A row whose zeta is zero skips the draw.
+ *   operand order    the operands that are present are accumulated in slot order, so a sample's result has the bits of the narrower
+ *                    launch (skr_step_launch) that holds exactly those operands in that order.
+ * `plan` is therefore the WIDEST step of the sampler (its steady state); a sample still in its multistep ramp-up has a row with
+ * zeros in the slots of the history it does not have yet.  Index validity stays the caller's business: every non-negative
+ * sample_index_dev[s] + row_offset must name a row of the table; the kernel neither checks nor clamps
+ * (skrample_amd.rolling.RollingBatch validates on the host).
+ */
+int skr_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
+                            const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                            const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */, int32_t row_offset,
+                            void* stream);
+
+/*
  * Step programs -- a plan the library keeps, launched by handle.  Replaces the per-step host work of a REPLAYED step
  * (skrample/diffusers.py:565-599 redoes the whole step algebra every call; skrample_amd lowers each distinct step once,
  * sampling/program.py): the plan -- coefficients, dtypes, conversion kinds, sample size -- is handed over and validated once,

@@ -29,6 +29,7 @@ EXPORTS = (
     "skr_step_launch",
     "skr_step_launch_indexed",
     "skr_step_launch_indexed_per_sample",
+    "skr_step_launch_rolling",
     "skr_step_backward_launch",
     "skr_program_create",
     "skr_program_launch",
@@ -309,6 +310,8 @@ def load() -> ctypes.CDLL:
         lib.skr_step_launch_indexed.restype = ctypes.c_int
         lib.skr_step_launch_indexed_per_sample.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
         lib.skr_step_launch_indexed_per_sample.restype = ctypes.c_int
+        lib.skr_step_launch_rolling.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
+        lib.skr_step_launch_rolling.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
         lib.skr_step_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]

@@ -514,9 +514,9 @@ static int pick_in(StepArgs<Acc>& a, const skr_step_plan& p, hipStream_t s) {
 
 template <typename Acc>
 static int run(const skr_step_plan& p, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds, int64_t numel, hipStream_t s,
-               const skr_step_row* rows = nullptr, const int32_t* index = nullptr, int32_t row_offset = 0, bool per_sample = false) {
+               const skr_step_row* rows = nullptr, const int32_t* index = nullptr, int32_t row_offset = 0, int per_sample = 0) {
   StepArgs<Acc> a;
-  a.rows = rows; a.index = index; a.row_offset = row_offset; a.per_sample = per_sample ? 1 : 0;
+  a.rows = rows; a.index = index; a.row_offset = row_offset; a.per_sample = per_sample;
   for (int k = 0; k < p.n_terms; ++k) {
     a.in[k] = inputs[k];
     a.c0[k] = (Acc)p.coef0[k];
@@ -543,7 +543,7 @@ static int run(const skr_step_plan& p, const void* const* inputs, void* out0, vo
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
-                            void* stream, const skr_step_row* rows, const int32_t* index, int32_t row_offset, bool per_sample = false) {
+                            void* stream, const skr_step_row* rows, const int32_t* index, int32_t row_offset, int per_sample = 0) {  // per_sample: 0 no, 1 yes, 2 rolling
   skr::DeviceGuard device_guard(out0 ? out0 : out1);
   if (!plan) return SKR_ERR_NULL;
   const skr_step_plan& p = *plan;
@@ -598,7 +598,14 @@ extern "C" int skr_step_launch_indexed_per_sample(const skr_step_plan* plan, con
                                                   const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
                                                   const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
   if (!rows_dev || !sample_index_dev) return SKR_ERR_NULL;
-  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, rows_dev, sample_index_dev, row_offset, true);
+  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, rows_dev, sample_index_dev, row_offset, 1);
+}
+
+extern "C" int skr_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
+                                       const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                       const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
+  if (!rows_dev || !sample_index_dev) return SKR_ERR_NULL;
+  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, rows_dev, sample_index_dev, row_offset, 2);
 }
 
 // ---- step programs: a plan kept by the library, launched by handle ------------------------------------------------------------------

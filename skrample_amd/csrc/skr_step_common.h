@@ -61,7 +61,8 @@ struct StepArgs {
   int32_t conv_to, conv_from;  // rounded pair conversion (CONV kernels): see convert_rounded()
   double ck[4];
   // skr_step_launch_indexed: the scalars above are read from rows[index[0] + row_offset] by the kernel (one-trip kernels only);
-  // per_sample (skr_step_launch_indexed_per_sample): from rows[index[sample] + row_offset], index holding one entry per sample
+  // per_sample (skr_step_launch_indexed_per_sample): from rows[index[sample] + row_offset], index holding one entry per sample;
+  // per_sample == 2 (skr_step_launch_rolling): the same, with inactive samples (entry < 0) and absent operands (zero coefficients) skipped
   const skr_step_row* rows;
   const int32_t* index;
   int32_t row_offset;

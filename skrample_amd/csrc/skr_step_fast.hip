@@ -43,8 +43,18 @@ __device__ __forceinline__ void sample_of(uint32_t c, int32_t bps_shift, uint32_
 // (A tag on an existing parameter, not a new one: the kernels that existed before keep their symbols and their instruction streams,
 // which tests/test_per_sample_isa.py and the headline number rely on.)
 template <typename T> struct PerSample {};
-template <typename T> struct RowsBy { using elem = T; static constexpr bool per_sample = false; };
-template <typename T> struct RowsBy<PerSample<T>> { using elem = T; static constexpr bool per_sample = true; };
+template <typename T> struct RowsBy { using elem = T; static constexpr bool per_sample = false, rolling = false; };
+template <typename T> struct RowsBy<PerSample<T>> { using elem = T; static constexpr bool per_sample = true, rolling = false; };
+// Rolling batches (skr_step_launch_rolling): a third form, Rolling<T>.  Per-sample rows in which a workgroup first asks its own sample's
+// index entry and row what to touch: a negative entry ends the workgroup before its first vector-memory instruction, and an operand
+// whose two coefficients are zero in the row is neither loaded nor accumulated (the history a sample in its multistep ramp-up does not
+// have yet -- its bytes are the slot's previous occupant's, possibly NaN, and fma(0, NaN, s) is NaN).  The row is uniform over the
+// workgroup, so every such decision is a scalar branch.  The row fetch therefore stands IN FRONT of the loads here, the order the
+// other forms avoid (see step_kernel_k1): two dependent scalar round trips per wave, measured in tools/bench_rolling.py.
+// (These instantiations carry TAB = false in their symbols -- a row is not optional for them, the tag alone selects it -- which keeps
+// the one-to-one census of TAB symbols and per-sample forms in tests/test_per_sample_isa.py what it was.)
+template <typename T> struct Rolling {};
+template <typename T> struct RowsBy<Rolling<T>> { using elem = T; static constexpr bool per_sample = true, rolling = true; };
 
 // The device-resident row of chunk c (TAB instantiations).  PER_SAMPLE: index holds one entry per sample and a workgroup reads its
 // own sample's -- launches of whole chunks per sample only, so the sample, and with it the row, zeta and the draw / no-draw branch,
@@ -65,16 +75,122 @@ __device__ __forceinline__ const skr_step_row* row_at(const RowRef& r, uint32_t 
   }
 }
 
+// Rolling form: the row of chunk c's sample, or nullptr for an inactive sample (index entry < 0, tested before row_offset is added).
+// sample_of keeps its branch here (nothing stands in front of it that the division could be hoisted over, and power-of-two samples
+// then never divide); the sample id goes through readfirstlane so that the index entry and the row are scalar loads.
+__device__ __forceinline__ const skr_step_row* rolling_row(const RowRef& r, uint32_t c, int32_t bps_shift, uint32_t& smp, uint32_t& within) {
+  sample_of(c, bps_shift, smp, within);
+  smp = __builtin_amdgcn_readfirstlane(smp);
+  const int32_t at = r.index[smp];
+  return at < 0 ? nullptr : r.rows + (at + r.row_offset);
+}
+// an operand is present unless both of its coefficients are exactly zero (either sign): decided on the row's doubles, in SGPRs
+__device__ __forceinline__ bool row_has(const skr_step_row* row, int j) {
+  return ((__builtin_bit_cast(uint64_t, row->coef0[j]) | __builtin_bit_cast(uint64_t, row->coef1[j])) << 1) != 0;
+}
+
+// Rolling form: one operand's terms, added in two halves of four elements.  In this form every operand is summed in a block of its
+// own, with the sums AND every operand still to come live across it; widened eight elements at a time, the eight temporaries on top of
+// that cost the fp16 instantiations of 10+ operands one wave per SIMD against their per-sample forms (fp16 only: its conversions are the ones the compiler batches).  The empty asm statement ties the
+// second half's conversions behind the first half's sums (it "rewrites" the raw registers and those sums), so four temporaries are live
+// at a time.  Element by element the arithmetic is what it was.
+template <typename T>
+__device__ __forceinline__ void tie_halves(Raw<T>& r, float* a, float* b) {
+  if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(r.q), "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+  else asm volatile("" : "+v"(r.q[0]), "+v"(r.q[1]), "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+}
+template <typename T>
+__device__ __forceinline__ void add_operand(Raw<T>& r, float c, float s[VEC]) {
+  float lo[VEC], hi[VEC];
+  widen<T, float>(r, lo);
+  if constexpr (!std::is_same<T, f16_t>::value) {  // (bf16 widens with a shift or a mask per element and fp32 not at all: tying them only costs registers)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s[i] = fma_(c, lo[i], s[i]);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < VEC / 2; ++i) s[i] = fma_(c, lo[i], s[i]);
+  if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(r.q), "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]));
+  else asm volatile("" : "+v"(r.q[0]), "+v"(r.q[1]), "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]));
+  widen<T, float>(r, hi);
+#pragma unroll
+  for (int i = VEC / 2; i < VEC; ++i) s[i] = fma_(c, hi[i], s[i]);
+}
+template <typename T>
+__device__ __forceinline__ void add_operand2(Raw<T>& r, float c0, float c1, float s0[VEC], float s1[VEC]) {
+  float lo[VEC], hi[VEC];
+  widen<T, float>(r, lo);
+  if constexpr (!std::is_same<T, f16_t>::value) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s0[i] = fma_(c0, lo[i], s0[i]);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s1[i] = fma_(c1, lo[i], s1[i]);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < VEC / 2; ++i) s0[i] = fma_(c0, lo[i], s0[i]);
+#pragma unroll
+  for (int i = 0; i < VEC / 2; ++i) s1[i] = fma_(c1, lo[i], s1[i]);
+  tie_halves<T>(r, s0, s1);
+  widen<T, float>(r, hi);
+#pragma unroll
+  for (int i = VEC / 2; i < VEC; ++i) s0[i] = fma_(c0, hi[i], s0[i]);
+#pragma unroll
+  for (int i = VEC / 2; i < VEC; ++i) s1[i] = fma_(c1, hi[i], s1[i]);
+}
 
 // kernarg sizes: 4 / 8 / 12 / 16 / 20 operand slots (Adams-Bashforth 5-9 and UniP >= 5 give 10-18 operands: round 3)
 constexpr int one_trip_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 16 ? 16 : 20))); }
 constexpr int ONE_TRIP_MAX_K = 20;
 
-template <typename TR, int K, bool NOISE, bool TILE, bool PACE, bool TAB>  // TR: the element type, or PerSample<element type> (TAB only)
+template <typename TR, int K, bool NOISE, bool TILE, bool PACE, bool TAB>  // TR: the element type, PerSample<element type> (TAB only) or Rolling<element type>
 __global__ __launch_bounds__(BLOCK) void step_kernel_k1(const OneTripArgs<one_trip_kmax(K)> a) {
   using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
+  if constexpr (RowsBy<TR>::rolling) {
+    uint32_t smp, within;
+    const skr_step_row* row = rolling_row(a.tab, c, a.bps_shift, smp, within);
+    if (row == nullptr) return;  // inactive sample: nothing read, nothing written
+    bool on[K];
+    double cd[K];  // (converted to float where they are used: the doubles sit in SGPRs, the floats would be K VGPRs live across the loads)
+#pragma unroll
+    for (int j = 0; j < K; ++j) { on[j] = row_has(row, j); cd[j] = row->coef0[j]; }
+    const float zeta0 = (float)row->zeta0;
+    const uint64_t stream0 = row->stream0;
+    // (each operand's pointer is fetched from the kernarg inside its branch -- one scalar round trip in front of its load.  Pinning the
+    //  pointers in SGPRs ahead of the branches with an asm statement made them generic pointers and the loads flat_load: left as it is)
+    // (16-bit launches of more than 12 operands keep 12 loads in flight: operand j + 12 is loaded where operand j has been summed, into
+    //  the registers that frees -- with all of them in flight the 13-16-operand fp16 forms are a wave per SIMD below their per-sample forms)
+    constexpr int AHEAD = (sizeof(T) == 2 && K > 12) ? 12 : K;
+    Raw<T> raw[K];
+#pragma unroll
+    for (int j = 0; j < AHEAD; ++j) if (on[j]) raw[j] = load_raw<T, TILE>(a.in[j], v);
+    float z[VEC];
+    bool n0 = false;
+    if constexpr (NOISE) {
+      n0 = zeta0 != 0.f;
+      if (n0) {
+        const uint64_t seed = a.seeds[smp];
+        const uint32_t vs = within * BLOCK + threadIdx.x;
+        normal4(seed, stream0, (uint64_t)group0<TILE>((int64_t)vs), z);
+        normal4(seed, stream0, (uint64_t)group1<TILE>((int64_t)vs), z + 4);
+      }
+    }
+    float s[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      if (on[j]) add_operand<T>(raw[j], (float)cd[j], s);  // present operands in slot order: the bits of the narrower launch that holds exactly these
+      if constexpr (AHEAD < K) {
+        if (j + AHEAD < K) { if (on[j + AHEAD]) raw[j + AHEAD] = load_raw<T, TILE>(a.in[j + AHEAD], v); }
+      }
+    }
+    if constexpr (NOISE) { if (n0) fma_noise8<float>(zeta0, z, s); }
+    store8<T, float, TILE>(a.out0, v, s);
+    return;
+  }
   Raw<T> raw[K];
   float z[VEC];
   // The step's scalars come from the kernarg or, in the TAB instantiation (indexed launches), from the device-resident row
@@ -198,6 +314,12 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
   using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLK + threadIdx.x;
+  [[maybe_unused]] const skr_step_row* rolling = nullptr;  // Rolling form: the inactive exit only (a Runge-Kutta step has no ramp-up)
+  if constexpr (RowsBy<TR>::rolling) {
+    uint32_t smp, within;
+    rolling = rolling_row(a.tab, c, a.bps_shift, smp, within);
+    if (rolling == nullptr) return;
+  }
   Raw<T> raw[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) raw[j] = load_raw<T, TILE>(a.in[j], v);
@@ -206,8 +328,9 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
   uint64_t stream1 = a.stream1;
 #pragma unroll
   for (int j = 0; j < K; ++j) cf[j] = a.c1[j];
-  if constexpr (TAB) {
-    const skr_step_row* row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift);
+  if constexpr (TAB || RowsBy<TR>::rolling) {
+    const skr_step_row* row;
+    if constexpr (RowsBy<TR>::rolling) row = rolling; else row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift);
 #pragma unroll
     for (int j = 0; j < K; ++j) cf[j] = (float)row->coef1[j];
 #pragma unroll
@@ -278,13 +401,15 @@ static int launch_k1(const StepArgs<float>& args, int bps_shift, hipStream_t str
   fa.out0 = args.out0; fa.seeds = args.seeds; fa.zeta0 = args.zeta0; fa.stream0 = args.stream0;
   fa.bps_shift = bps_shift; fa.xmap_lr = xmap_lr_for(chunks);
   fa.tab = RowRef{args.rows, args.index, args.row_offset};
-#define SKR_K(N) case N: if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+#define SKR_K(N) case N: if (args.per_sample == 2) hipLaunchKernelGGL((step_kernel_k1<Rolling<T>, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+                        else if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                         else if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                         else if (g_tune.pace) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                         else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); break
   // more than 8 operands: one unpaced instantiation each (plus the table form while the operands fit a device-resident row)
 #define SKR_KB(N) case N: if (args.rows != nullptr) { if constexpr (N <= SKR_ROW_TERMS) { \
-                           if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+                           if (args.per_sample == 2) hipLaunchKernelGGL((step_kernel_k1<Rolling<T>, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
+                           else if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                            else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
                          } else return SKR_ERR_UNSUPPORTED; } \
                          else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); break
@@ -335,7 +460,8 @@ static int launch_rk1(const StepArgs<float>& args, unsigned chunks, int bps_shif
   ra.out0 = args.out0; ra.out1 = args.out1; ra.chain = args.chain;
   for (int i = 0; i < 4; ++i) ra.ck[i] = (float)args.ck[i];
   ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.xmap_lr = xmap_lr_for(chunks); ra.tab = RowRef{args.rows, args.index, args.row_offset};
-#define SKR_K(N) case N: if (args.per_sample) hipLaunchKernelGGL((step_kernel_rk1<PerSample<T>, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
+#define SKR_K(N) case N: if (args.per_sample == 2) hipLaunchKernelGGL((step_kernel_rk1<Rolling<T>, N, TILE, NOISE, false, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
+                        else if (args.per_sample) hipLaunchKernelGGL((step_kernel_rk1<PerSample<T>, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
                         else if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
                         else hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, false, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); break
   if constexpr (KMAX == 4) { switch (args.n_terms) { SKR_K(2); SKR_K(3); SKR_K(4); } }
@@ -398,6 +524,53 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k2(const TwoOutArgs<two_out
   using TA = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
+  if constexpr (RowsBy<TR>::rolling) {  // see step_kernel_k1: inactive exit, absent operands skipped, present ones in slot order
+    uint32_t smp, within;
+    const skr_step_row* row = rolling_row(a.tab, c, a.bps_shift, smp, within);
+    if (row == nullptr) return;
+    bool on[NA + NB];
+    double cd0[NA + NB], cd1[NA + NB];  // (converted where they are used, see step_kernel_k1)
+#pragma unroll
+    for (int j = 0; j < NA + NB; ++j) { on[j] = row_has(row, j); cd0[j] = row->coef0[j]; cd1[j] = row->coef1[j]; }
+    const float chain = (float)row->chain, zeta0 = (float)row->zeta0, zeta1 = (float)row->zeta1;
+    const uint64_t stream0 = row->stream0, stream1 = row->stream1;
+    Raw<TA> ra[NA];
+    Raw<float> rb[NB > 0 ? NB : 1];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) if (on[j]) ra[j] = load_raw<TA, true>(a.in[j], v);
+#pragma unroll
+    for (int j = 0; j < NB; ++j) if (on[NA + j]) rb[j] = load_raw<float, true>(a.in[NA + j], v);
+    float z0[VEC], z1[VEC];
+    bool n0 = false, n1 = false;
+    if constexpr (NOISE) {
+      n0 = zeta0 != 0.f;
+      n1 = zeta1 != 0.f;
+      if (n0 || n1) {
+        const uint64_t seed = a.seeds[smp];
+        const uint32_t vs = within * BLOCK + threadIdx.x;
+        if (n0) { normal4(seed, stream0, (uint64_t)group0<true>((int64_t)vs), z0); normal4(seed, stream0, (uint64_t)group1<true>((int64_t)vs), z0 + 4); }
+        if (n1) { normal4(seed, stream1, (uint64_t)group0<true>((int64_t)vs), z1); normal4(seed, stream1, (uint64_t)group1<true>((int64_t)vs), z1 + 4); }
+      }
+    }
+    float s0[VEC], s1[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { s0[i] = 0.f; s1[i] = 0.f; }
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+      if (on[j]) add_operand2<TA>(ra[j], (float)cd0[j], (float)cd1[j], s0, s1);
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      if (on[NA + j]) add_operand2<float>(rb[j], (float)cd0[NA + j], (float)cd1[NA + j], s0, s1);
+    }
+    if constexpr (NOISE) { if (n0) fma_noise8<float>(zeta0, z0, s0); }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s1[i] = fma_(chain, s0[i], s1[i]);
+    if constexpr (NOISE) { if (n1) fma_noise8<float>(zeta1, z1, s1); }
+    store8<TA, float, true, NT>(a.out1, v, s1);
+    store8<float, float, true, NT>(a.out0, v, s0);
+    return;
+  }
   Raw<TA> ra[NA];
   Raw<float> rb[NB > 0 ? NB : 1];
   float z0[VEC], z1[VEC];
@@ -517,6 +690,10 @@ static int launch_k2(const StepArgs<float>& args, int bps_shift, hipStream_t str
   ta.chain = args.chain; ta.zeta0 = args.zeta0; ta.zeta1 = args.zeta1;
   ta.tab = RowRef{args.rows, args.index, args.row_offset};
   if constexpr (TAB && !NT) {
+    if (args.per_sample == 2) {
+      hipLaunchKernelGGL((step_kernel_k2<Rolling<TA>, NA, NB, NOISE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
+      return finish_launch();
+    }
     if (args.per_sample) {
       hipLaunchKernelGGL((step_kernel_k2<PerSample<TA>, NA, NB, NOISE, PACE, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
       return finish_launch();

@@ -1,0 +1,376 @@
+"""Rolling batches (continuous batching): every sample of a batch at its own position of its own sampling loop, one launch per tick.
+
+`capture_sampling_loop(..., per_sample=True)` gives every sample of a batch its own schedule, but all samples start together, run
+the same number of steps and finish together.  A server's requests do not: they arrive one by one, and 20-step requests sit
+beside 50-step ones.  `RollingBatch` keeps `capacity` slots; a request is admitted into a free slot at any tick, steps with
+whatever else is resident, and leaves when its own run is over -- the slot is free for the next request at once:
+
+    batch = RollingBatch(make_wrapper, example, capacity=B)
+    batch.admit(slot, latents, wrapper, steps, seed=None)
+    t = batch.timesteps                              # device tensor [B]
+    done = batch.step(model(batch.latents, t))       # ONE skr_step_launch_rolling; the slots that just finished
+    x = batch.take(slot)
+
+How it works.  The launch structure is the sampler's steady-state (widest) step, found by a dry run of `make_wrapper()` on one
+sample.  Every operand of it has a ROLE (sampling/program.py: this tick's sample / model output, or the k-th last sample, model
+output or state): the batch binds the roles to whole-batch tensors it rotates itself -- a ring of its own latents, a ring of the
+caller's last model outputs, a ring of fp32 states (UniPC / SPC).  An admitted request's rows come from a dry run of ITS wrapper on
+one sample (the mechanism of `CapturedLoop.retarget`); each row is placed into the wide structure by role, zeros elsewhere, and
+uploaded into the slot's region of one device table.  Per tick the host publishes `index[b] = base[b] + position[b]`, or -1 for a
+free or finished slot, with one small stream-ordered copy.  The kernels (csrc/skr_step_fast.hip, `Rolling<T>`) skip inactive samples
+before their first vector-memory instruction, and neither load nor accumulate an operand whose coefficients are zero in the
+sample's row: a sample in its multistep ramp-up has the bits of the narrower launch its lone run makes, whatever the slot's previous
+occupant left in the history rings.
+
+Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
+`Random` noise (drawn in the kernel) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
+`skr_step_launch_indexed` covers (UniPC on fp32 latents is refused, as by the captured loops).  Not covered: the Runge-Kutta wrapper
+classes (the kernel form exists, the stage bookkeeping does not), structured noise, graph capture of ticks, autograd, a
+device-resident position vector.
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Callable, Sequence
+
+import torch
+
+from . import _hip
+from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepPlanC, StepRowC
+
+Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py
+
+ALIAS_HELP = (
+    "a model output passed to an earlier step() is still a history operand of this batch and {what}; RollingBatch aliases the caller's "
+    "model outputs instead of copying them -- construct it with alias_history=False (one snapshot per tick) when the network reuses its output buffer"
+)
+
+
+def sampler_structure(wrapper) -> tuple:
+    "what two requests must share to step in one launch (host only: read from the wrapper's configuration)"
+    sampler = wrapper.sampler
+    nested = tuple((type(s).__name__, getattr(s, "order", None)) for s in (getattr(sampler, "predictor", None), getattr(sampler, "corrector", None)) if s is not None)
+    return (type(wrapper).__name__, type(sampler).__name__, getattr(sampler, "order", None), nested, type(wrapper.model).__name__,
+            wrapper.compute_scale, getattr(wrapper.noise_type, "__name__", None), bool(wrapper.invert_prediction))  # fmt: skip
+
+
+def place_row(wide_roles: Sequence[Role], plan: StepPlanC, roles: Sequence[Role], two_outputs: bool) -> StepRowC:
+    """The row of a (possibly narrower) launch inside the wide structure: operand j goes to the slot of its role, the other slots
+    stay zero -- absent operands for the kernel.  The operands present must keep their relative order (the kernels accumulate in
+    slot order; any other order would not be the lone run's bits).  A single-output launch inside a two-output structure (the
+    first step of a UniPC / SPC run) goes to the second output, the one that is the step's result: the state it leaves is zero
+    and is never read, because the next step's row has a zero there."""
+    row = StepRowC()
+    last = -1
+    single = two_outputs and plan.out1_dtype == _hip.NONE
+    for j, role in enumerate(roles):
+        if role not in wide_roles:
+            raise SkrampleHipError(f"operand {role} of this step has no place in the batch's launch structure {list(wide_roles)}")
+        behind = [at for at, wide in enumerate(wide_roles) if wide == role and at > last]  # (a role may have several slots: see RollingBatch._widest)
+        if not behind:
+            raise SkrampleHipError(f"operand {role} precedes its neighbours in this step but follows them in the batch's launch structure: the sums would differ in order")
+        last = at = behind[0]
+        if single:
+            row.coef1[at] = plan.coef0[j]
+        else:
+            row.coef0[at], row.coef1[at] = plan.coef0[j], plan.coef1[j]
+    if single:
+        row.zeta1, row.stream1 = plan.zeta0, plan.stream0
+    else:
+        row.chain, row.zeta0, row.zeta1, row.stream0, row.stream1 = plan.chain, plan.zeta0, plan.zeta1, plan.stream0, plan.stream1
+    return row
+
+
+class _Request:
+    __slots__ = ("rows", "times", "position")
+
+    def __init__(self, rows: list, times: list):
+        self.rows, self.times, self.position = rows, times, 0
+
+
+class RollingBatch:
+    """`capacity` slots of samples shaped like `example[0]`, stepped together by one `skr_step_launch_rolling` per tick.
+
+    `make_wrapper()` returns a fresh `SkrampleWrapperScheduler`: its sampler fixes the launch structure every admitted request must
+    share.  `max_steps` bounds a request's run length (the device table holds `capacity * max_steps` rows of 328 bytes).
+    `alias_history`: True keeps the caller's model outputs as history operands (0 bytes written; overwriting one that is still
+    held raises), False snapshots each one."""
+
+    def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True):
+        if capacity < 1:
+            raise ValueError("a rolling batch has at least one slot")
+        self.capacity, self.max_steps, self.alias_history = int(capacity), int(max_steps), bool(alias_history)
+        self.unit_shape = tuple(example.shape[1:])
+        self.dtype, self.device = example.dtype, example.device
+        self.sample_numel = 1
+        for n in self.unit_shape:
+            self.sample_numel *= int(n)
+        if self.sample_numel <= 0 or self.sample_numel % PER_SAMPLE_CHUNK != 0:
+            raise ValueError(f"per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {self.sample_numel} elements per sample")
+        self.numel = self.capacity * self.sample_numel
+        first = make_wrapper()
+        self.structure = sampler_structure(first)
+        self.keep = int(first.sampler.require_previous)
+        self.draws_noise = bool(first.sampler.require_noise)
+        self.plan, self.roles = self._widest(self._trace(first, self.keep + 4, seed=0 if self.draws_noise else None))
+        self.two_outputs = self.plan.out0_dtype != _hip.NONE and self.plan.out1_dtype != _hip.NONE
+        if self.plan.n_terms > ROW_TERMS:
+            raise SkrampleHipError(f"a launch with {self.plan.n_terms} operands does not fit a device-resident row ({ROW_TERMS})")
+        shape = (self.capacity, *self.unit_shape)
+        depth = self.keep + 1
+        # rings, oldest first: [-1] is this tick's latents / the latest state; the model outputs are the caller's (or snapshots)
+        self._x = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1)]
+        state_dtype = _hip.CODE_DTYPE[self.plan.out0_dtype] if self.two_outputs else None
+        self._state = [torch.zeros(shape, dtype=state_dtype, device=self.device) for _ in range(depth + 1)] if self.two_outputs else []
+        self._blank = torch.zeros(shape, dtype=self.dtype, device=self.device)  # stands for a model output no tick has produced yet
+        self._outputs: list[torch.Tensor] = []
+        self._stamps: list[tuple[torch.Tensor, int, int]] = []
+        self._results: dict[int, torch.Tensor] = {}
+        self._requests: list[_Request | None] = [None] * self.capacity
+        self._finished: set[int] = set()
+        self.row_bytes = ctypes.sizeof(StepRowC)
+        self.rows_dev = torch.zeros(self.capacity * self.max_steps * self.row_bytes, dtype=torch.uint8, device=self.device)
+        self.index_dev = torch.full((self.capacity,), -1, dtype=torch.int32, device=self.device)
+        self.seeds_dev = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+        self._times_host = torch.zeros(self.capacity, dtype=torch.float32)
+        self.timesteps = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        self.ticks = 0
+
+    # ---- what a test replaces to run the bookkeeping without a device ---------------------------------------------------
+    def _trace(self, wrapper, steps: int, seed: int | None) -> list[tuple[StepPlanC, list[Role], float]]:
+        """Dry run of `wrapper` for `steps` steps on one sample: (plan, operand roles, timestep) of every step's single launch.
+        Coefficients depend on the schedule and the step alone, never on tensor contents, so the model outputs are zeros."""
+        wrapper.set_timesteps(steps)
+        x = torch.zeros((1, *self.unit_shape), dtype=self.dtype, device=self.device)
+        found = []
+        for t in wrapper.timesteps.tolist():
+            out = torch.zeros_like(x)
+            known: dict[int, Role] = {}
+            for k in range(-len(wrapper._previous), 0):
+                state = wrapper._previous[k].sample
+                if isinstance(state, torch.Tensor):
+                    known[state.data_ptr()] = ("px", k)
+                known[wrapper._raw_outputs[k].data_ptr()] = ("po", k)
+                known[wrapper._raw_samples[k].data_ptr()] = ("pi", k)
+            held = _hip.trace
+            _hip.trace = []
+            try:
+                new = wrapper.step(out, t, x, generator=[seed] if seed is not None else None, return_dict=False)[0]
+                launches = _hip.trace
+            finally:
+                _hip.trace = held
+            if len(launches) != 1:
+                raise SkrampleHipError(f"a step of this wrapper is {len(launches)} launches, not one fused launch: it cannot join a rolling batch")
+            plan, inputs = StepPlanC.from_buffer_copy(launches[0][0]), launches[0][1]
+            known[x.data_ptr()], known[out.data_ptr()] = ("x",), ("o",)
+            if wrapper._raw_samples:  # (a wrapper that snapshots its history stepped on its own copies of this call's tensors)
+                known[wrapper._raw_samples[-1].data_ptr()], known[wrapper._raw_outputs[-1].data_ptr()] = ("x",), ("o",)
+            roles = [known.get(tensor.data_ptr()) for tensor in inputs]
+            if any(r is None for r in roles):
+                raise SkrampleHipError("a step of this wrapper reads a temporary tensor (a cast, a copy, realised noise): it cannot join a rolling batch")
+            found.append((plan, roles, float(t)))
+            x = new
+        torch.cuda.synchronize(self.device)
+        return found
+
+    def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None) -> None:
+        lib = _hip.load()
+        status = lib.skr_step_launch_rolling(ctypes.byref(self.plan), arr, out0.data_ptr() if out0 is not None else None, out1.data_ptr() if out1 is not None else None,
+                                             self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0,
+                                             _hip.current_stream_ptr(self.device))  # fmt: skip
+        _hip.check(status, "skr_step_launch_rolling")
+
+    # ---- structure ---------------------------------------------------------------------------------------------------------
+    def _widest(self, traced) -> tuple[StepPlanC, list[Role]]:
+        """The launch structure: the widest step of the dry run.  The kernels accumulate in slot order, so every narrower step's
+        operands must appear in it in THEIR order.  Where a ramp-up step orders two roles the other way round (SPC's second step
+        reads sample, previous sample, model output; its steady state sample, model output, previous sample, ...) the role gets a
+        second slot at the place that step needs it: a slot whose coefficients are zero costs a kernel argument and no bytes.  Two-output
+        launches are then padded with never-present slots up to an operand count the table kernels are instantiated for."""
+        plan, roles, _ = max(traced, key=lambda entry: entry[0].n_terms)
+        wide = StepPlanC.from_buffer_copy(plan)
+        roles = list(roles)
+        two = wide.out0_dtype != _hip.NONE and wide.out1_dtype != _hip.NONE
+        for _, narrow, _ in traced:
+            at = 0
+            for role in narrow:
+                if role[0] == "px":
+                    continue  # (the fp32 group stays last)
+                found = [i for i in range(at, wide.n_group_a) if roles[i] == role]
+                if found:
+                    at = found[0] + 1
+                else:
+                    roles.insert(at, role)
+                    wide.n_group_a += 1
+                    wide.n_terms += 1
+                    at += 1
+        if two and wide.n_terms > wide.n_group_a:
+            while wide.n_group_a not in (4, 6, 7, 8, 10, 12, 14) and wide.n_group_a < 14:
+                roles.insert(wide.n_group_a, ("none",))
+                wide.n_group_a += 1
+                wide.n_terms += 1
+        wide.sample_numel = self.sample_numel
+        if self.draws_noise:
+            wide.noise_mode = 1
+        if self.dtype == torch.float32 and wide.out0_dtype != _hip.NONE and wide.out1_dtype != _hip.NONE:
+            raise SkrampleHipError("skr_step_launch_rolling: request outside kernel coverage (the two-output table kernels take 16-bit operands)")
+        return wide, list(roles)
+
+    def _rows_of(self, traced) -> list[StepRowC]:
+        rows = []
+        for plan, roles, _ in traced:
+            if (plan.dtype_a, plan.acc_f64, plan.convert_to, plan.convert_from) != (self.plan.dtype_a, self.plan.acc_f64, self.plan.convert_to, self.plan.convert_from):
+                raise SkrampleHipError("a step of this request differs in dtype or conversion from the batch's launch structure")
+            rows.append(place_row(self.roles, plan, roles, self.two_outputs))
+        return rows
+
+    # ---- slots ---------------------------------------------------------------------------------------------------------------
+    def _check_slot(self, slot: int) -> int:
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.capacity:
+            raise ValueError(f"slot {slot} outside 0..{self.capacity - 1}")
+        return slot
+
+    @property
+    def latents(self) -> torch.Tensor:
+        "this tick's samples, [capacity, ...]: what the network reads (free slots hold finite leftovers)"
+        return self._x[-1]
+
+    @property
+    def active(self) -> list[int]:
+        return [b for b, r in enumerate(self._requests) if r is not None and b not in self._finished]
+
+    def free(self, slot: int) -> bool:
+        return self._requests[self._check_slot(slot)] is None
+
+    def ring_tensors(self) -> list[torch.Tensor]:
+        "every whole-batch tensor a history operand may be bound to: the batch's own latents and states, snapshots of model outputs"
+        owned = self._x[:-1] + list(self._state) + [self._blank]
+        return owned + ([] if self.alias_history else list(self._outputs))
+
+    def index_vector(self) -> list[int]:
+        "host: the row every slot reads this tick, -1 for a free or finished slot (validated: nothing outside a slot's own run)"
+        out = []
+        for b, req in enumerate(self._requests):
+            if req is None or b in self._finished:
+                out.append(-1)
+                continue
+            if not 0 <= req.position < len(req.rows) <= self.max_steps:
+                raise ValueError(f"slot {b} is at position {req.position} of a run of {len(req.rows)} steps")
+            out.append(b * self.max_steps + req.position)
+        return out
+
+    def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None) -> None:
+        """Start a request in a free slot: `latents` of one sample, `wrapper` with this request's schedule / stochasticity (same
+        sampler structure as the batch; it is consumed by the dry run that produces the rows), `steps` its run length."""
+        self._check_slot(slot)
+        if self._requests[slot] is not None:
+            raise ValueError(f"slot {slot} is busy: take() its result first" if slot in self._finished else f"slot {slot} is busy")
+        steps = int(steps)
+        if not 1 <= steps <= self.max_steps:
+            raise ValueError(f"a request runs 1..{self.max_steps} steps (max_steps), not {steps}")
+        if sampler_structure(wrapper) != self.structure:
+            raise ValueError(f"this wrapper's sampler structure {sampler_structure(wrapper)} is not the batch's {self.structure}")
+        noisy = bool(wrapper.sampler.require_noise)
+        if noisy and not self.draws_noise:
+            raise ValueError("this wrapper draws noise and the batch's sampler structure does not")
+        if noisy and seed is None:
+            raise ValueError("a request that draws noise needs a seed")
+        if tuple(latents.shape) not in (self.unit_shape, (1, *self.unit_shape)) or latents.dtype != self.dtype:
+            raise ValueError(f"latents of shape {tuple(latents.shape)} / {latents.dtype} in a batch of samples {self.unit_shape} / {self.dtype}")
+        traced = self._trace(wrapper, steps, seed if noisy else None)
+        if len(traced) != steps:
+            raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
+        request = _Request(self._rows_of(traced), [t for _, _, t in traced])
+        blob = b"".join(bytes(r) for r in request.rows)
+        at = slot * self.max_steps * self.row_bytes
+        self.rows_dev[at : at + len(blob)].copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
+        self._x[-1][slot].copy_(latents.reshape(self.unit_shape))
+        if noisy:
+            value = int(seed) & 0xFFFFFFFFFFFFFFFF
+            self.seeds_dev[slot : slot + 1].copy_(torch.tensor([value - (1 << 64) if value >= (1 << 63) else value], dtype=torch.int64))
+        self._requests[slot] = request
+        self._times_host[slot] = request.times[0]
+        self.timesteps.copy_(self._times_host)
+
+    def take(self, slot: int) -> torch.Tensor:
+        "the result of a finished slot; the slot is free again"
+        self._check_slot(slot)
+        if slot not in self._finished:
+            raise ValueError(f"slot {slot} holds no request" if self._requests[slot] is None else f"slot {slot} has not finished: {self._requests[slot].position} of {len(self._requests[slot].rows)} steps done")
+        self._finished.discard(slot)
+        self._requests[slot] = None
+        return self._results.pop(slot)
+
+    # ---- one tick --------------------------------------------------------------------------------------------------------------
+    def _guard(self, model_output: torch.Tensor) -> None:
+        for held, ptr, version in self._stamps:
+            if held._version != version or held.data_ptr() != ptr:
+                raise SkrampleHipError(ALIAS_HELP.format(what="was modified in place since"))
+            if ptr == model_output.data_ptr():
+                raise SkrampleHipError(ALIAS_HELP.format(what="its buffer now holds this tick's model output"))
+
+    def _bind(self, role: Role, model_output: torch.Tensor) -> torch.Tensor:
+        kind = role[0]
+        if kind == "x":
+            return self._x[-1]
+        if kind == "o":
+            return model_output
+        if kind == "none":
+            return self._blank
+        k = role[1]
+        if kind == "pi":
+            return self._x[k - 1]
+        if kind == "px":
+            return self._state[k]
+        if kind == "po":
+            return self._outputs[k] if -k <= len(self._outputs) else self._blank
+        raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (structured noise tensors are not covered)")
+
+    def step(self, model_output: torch.Tensor) -> list[int]:
+        "advance every active slot by one step of its own run with ONE launch; returns the slots that finished with this tick"
+        index = self.index_vector()
+        if all(i < 0 for i in index):
+            raise ValueError("no active slot: admit() a request before step()")
+        if tuple(model_output.shape) != tuple(self._x[-1].shape) or model_output.dtype != self.dtype or model_output.device != self.device or not model_output.is_contiguous():
+            raise ValueError(f"the model output of a tick is a contiguous {tuple(self._x[-1].shape)} {self.dtype} tensor on {self.device}")
+        if self.alias_history:
+            self._guard(model_output)
+        elif self.keep:
+            model_output = model_output.clone()
+        operands = [self._bind(role, model_output) for role in self.roles]
+        self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
+        arr = (ctypes.c_void_p * max(len(operands), 1))(*[t.data_ptr() for t in operands])
+        # the oldest ring entries take this tick's results: no operand of the structure reaches that far back
+        new_x = self._x.pop(0)
+        new_state = self._state.pop(0) if self.two_outputs else None
+        if self.two_outputs:
+            self._launch(arr, new_state, new_x)
+            self._state.append(new_state)
+        elif self.plan.out0_dtype != _hip.NONE:
+            self._launch(arr, new_x, None)
+        else:
+            self._launch(arr, None, new_x)
+        self._x.append(new_x)
+        if self.keep:
+            self._outputs.append(model_output)
+            del self._outputs[: max(len(self._outputs) - self.keep, 0)]
+            if self.alias_history:
+                self._stamps.append((model_output, model_output.data_ptr(), model_output._version))
+                del self._stamps[: max(len(self._stamps) - self.keep, 0)]
+        self.ticks += 1
+        done = []
+        for b, i in enumerate(index):
+            if i < 0:
+                continue
+            req = self._requests[b]
+            req.position += 1
+            if req.position == len(req.rows):
+                done.append(b)
+                self._finished.add(b)
+                self._results[b] = new_x[b].clone()
+            else:
+                self._times_host[b] = req.times[req.position]
+        # (the slices of free slots are not touched, by the kernel or here: they hold what an older tick left there)
+        self.timesteps.copy_(self._times_host)
+        return done

@@ -140,10 +140,17 @@ class StepRowC(ctypes.Structure):
     ]
 
 
-def plan_structure(plan: StepPlanC) -> tuple:
-    "what a captured launch freezes: everything of a plan except the scalars a row carries"
+def plan_structure(plan: StepPlanC, sample_numel: bool = True) -> tuple:
+    "what a captured launch freezes: everything of a plan except the scalars a row carries (`sample_numel` = False: and the sample size)"
     return (plan.n_terms, plan.n_group_a, plan.dtype_a, plan.dtype_b, plan.out0_dtype, plan.out1_dtype, plan.acc_f64, plan.noise_mode,
-            plan.sample_numel, plan.convert_to, plan.convert_from)  # fmt: skip
+            plan.sample_numel if sample_numel else None, plan.convert_to, plan.convert_from)  # fmt: skip
+
+
+def upload_rows(rows_dev: torch.Tensor, first_row: int, rows) -> None:
+    "copy `rows` (StepRowC) into the device table `rows_dev` (uint8) from row `first_row` on (stream-ordered)"
+    blob = b"".join(bytes(r) for r in rows)
+    at = first_row * ctypes.sizeof(StepRowC)
+    rows_dev[at : at + len(blob)].copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8), non_blocking=False)
 
 
 class IndexedRows:
@@ -161,7 +168,8 @@ class IndexedRows:
     def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None):
         self.device, self.slots, self.batch = device, slots, batch
         self.mode, self.cursor, self.length = "record", 0, 0
-        self.structures: list[tuple] = []
+        self.structures: list[tuple] = []  # plan_structure of every recorded launch,
+        self.shapeless: list[tuple] = []  # and without its sample size (what a refill must match)
         self.host: list[StepRowC] = []
         self.rows_dev: torch.Tensor | None = None
         self.index_dev = torch.zeros(1, dtype=torch.int32, device=device)
@@ -188,10 +196,7 @@ class IndexedRows:
 
     def upload(self, slot: int) -> None:
         "copy the host rows of `slot` to the device (stream-ordered)"
-        size = ctypes.sizeof(StepRowC)
-        blob = b"".join(bytes(r) for r in self.host[slot * self.length : (slot + 1) * self.length])
-        staging = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-        self.rows_dev[slot * self.length * size : (slot + 1) * self.length * size].copy_(staging, non_blocking=False)
+        upload_rows(self.rows_dev, slot * self.length, self.host[slot * self.length : (slot + 1) * self.length])
 
     def sample_indices(self, sample_slots) -> torch.Tensor:
         "host int32[batch] of `slot * length`: what `sample_index_dev` must hold for the samples to follow these slots"
@@ -217,12 +222,13 @@ class IndexedRows:
                 raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, "
                                        f"not {numel} elements for {self.batch} samples")
             self.structures.append(plan_structure(plan))
+            self.shapeless.append(plan_structure(plan, sample_numel=False))
             self.host.append(self.row_from(plan))
             return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
         if k >= self.length:
             raise SkrampleHipError("more launches than the captured loop has")
         if self.mode == "refill":
-            if plan_structure(plan)[:8] + plan_structure(plan)[9:] != self.structures[k][:8] + self.structures[k][9:]:
+            if plan_structure(plan, sample_numel=False) != self.shapeless[k]:
                 raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
             self.host[self.slot * self.length + k] = self.row_from(plan)
             return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
@@ -306,12 +312,9 @@ def load() -> ctypes.CDLL:
         vp, i64, u64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32
         lib.skr_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp]
         lib.skr_step_launch.restype = ctypes.c_int
-        lib.skr_step_launch_indexed.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
-        lib.skr_step_launch_indexed.restype = ctypes.c_int
-        lib.skr_step_launch_indexed_per_sample.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
-        lib.skr_step_launch_indexed_per_sample.restype = ctypes.c_int
-        lib.skr_step_launch_rolling.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
-        lib.skr_step_launch_rolling.restype = ctypes.c_int
+        for table_launch in (lib.skr_step_launch_indexed, lib.skr_step_launch_indexed_per_sample, lib.skr_step_launch_rolling):
+            table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
+            table_launch.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
         lib.skr_step_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]

@@ -329,6 +329,13 @@ static bool tile_ok(int64_t numel, int64_t sample_numel, bool noise, int grid_mo
   return g_tune.tile && numel % 512 == 0 && (!noise || (grid_mode == 1 && sample_numel % 512 == 0));
 }
 
+// f(bool_c<TILE>{}): the whole-line tile layout when a 32-bit tensor takes part (WIDE) and the launch is made of whole tiles
+template <bool WIDE, typename F>
+static int with_tile(int64_t numel, int64_t sample_numel, bool noise, int grid_mode, F&& f) {
+  if constexpr (WIDE) { if (tile_ok(numel, sample_numel, noise, grid_mode)) return f(bool_c<true>{}); }
+  return f(bool_c<false>{});
+}
+
 int finish_launch() {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { g_last_hip_error = (int)e; return SKR_ERR_LAUNCH; }
@@ -340,20 +347,16 @@ static int launch_k_uv(StepArgs<float>& args, hipStream_t stream, bool& taken) {
   Geometry g = geometry<UV, NOISE>(args.numel, args.sample_numel);
   if (NOISE && g.mode != 1) return SKR_OK;  // flat-grid noise (tiny samples): generic kernel
   FastArgs fa;
-  for (int k = 0; k < 8; ++k) { fa.in[k] = k < args.n_terms ? args.in[k] : nullptr; fa.c0[k] = k < args.n_terms ? args.c0[k] : 0.f; }
+  fill_operands(args.in, args.c0, args.n_terms, fa.in, fa.c0);
   fa.out0 = args.out0; fa.seeds = args.seeds; fa.zeta0 = args.zeta0; fa.stream0 = args.stream0;
   fa.numel = args.numel; fa.vps = args.sample_numel / VEC;
   taken = true;
-#define SKR_K(N, TILE) case N: hipLaunchKernelGGL((step_kernel_k<T, N, NOISE, UV, TILE>), g.grid, dim3(BLOCK), 0, stream, fa); break
-  if constexpr (sizeof(T) == 4) {  // 32-bit tensors: whole-line tile layout when the launch is made of whole tiles
-    if (tile_ok(args.numel, args.sample_numel, NOISE, g.mode)) {
-      switch (args.n_terms) { SKR_K(1, true); SKR_K(2, true); SKR_K(3, true); SKR_K(4, true); SKR_K(5, true); SKR_K(6, true); SKR_K(7, true); SKR_K(8, true); }
-      return finish_launch();
-    }
-  }
-  switch (args.n_terms) { SKR_K(1, false); SKR_K(2, false); SKR_K(3, false); SKR_K(4, false); SKR_K(5, false); SKR_K(6, false); SKR_K(7, false); SKR_K(8, false); }
-#undef SKR_K
-  return finish_launch();
+  return with_tile<sizeof(T) == 4>(args.numel, args.sample_numel, NOISE, g.mode, [&](auto tile) {
+    with_count<1, 8>(args.n_terms, [&](auto n) {
+      hipLaunchKernelGGL((step_kernel_k<T, decltype(n)::value, NOISE, UV, decltype(tile)::value>), g.grid, dim3(BLOCK), 0, stream, fa);
+    });
+    return finish_launch();
+  });
 }
 
 template <typename T, bool NOISE>
@@ -364,7 +367,7 @@ static int launch_k(StepArgs<float>& args, hipStream_t stream, bool& taken) {
     const int rc = launch_one_trip_k<T>(args, NOISE, stream, taken);  // whole chunks: one-trip kernel (skr_step_fast.hip), <= 20 operands
     if (taken) return rc;
   }
-  if (args.rows != nullptr) { taken = true; return SKR_ERR_UNSUPPORTED; }  // indexed launches: one-trip kernels only
+  if (has_table(args.form)) { taken = true; return SKR_ERR_UNSUPPORTED; }  // table launches: one-trip kernels only
   if (args.n_terms > 8) return SKR_OK;  // (the grid-stride compile-time kernels stop at 8: ragged launches of more operands take the general kernel)
   if constexpr (NOISE) {
     return launch_k_uv<T, true, 1>(args, stream, taken);
@@ -379,20 +382,16 @@ template <typename T, int UV>
 static int launch_rk_uv(const StepArgs<float>& args, hipStream_t stream) {
   Geometry g = geometry<UV, false>(args.numel, args.sample_numel);
   RkArgs ra;
-  for (int k = 0; k < 8; ++k) { ra.in[k] = k < args.n_terms ? args.in[k] : nullptr; ra.c1[k] = k < args.n_terms ? args.c1[k] : 0.f; }
+  fill_operands(args.in, args.c1, args.n_terms, ra.in, ra.c1);
   ra.out0 = args.out0; ra.out1 = args.out1; ra.chain = args.chain;
   for (int i = 0; i < 4; ++i) ra.ck[i] = (float)args.ck[i];
-  ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.numel = args.numel; ra.xmap_lr = 0;
-#define SKR_K(N, TILE) case N: hipLaunchKernelGGL((step_kernel_rk<T, N, UV, TILE>), g.grid, dim3(BLOCK), 0, stream, ra); break
-  if constexpr (sizeof(T) == 4) {
-    if (tile_ok(args.numel, args.sample_numel, false, g.mode)) {
-      switch (args.n_terms) { SKR_K(2, true); SKR_K(3, true); SKR_K(4, true); SKR_K(5, true); SKR_K(6, true); SKR_K(7, true); SKR_K(8, true); }
-      return finish_launch();
-    }
-  }
-  switch (args.n_terms) { SKR_K(2, false); SKR_K(3, false); SKR_K(4, false); SKR_K(5, false); SKR_K(6, false); SKR_K(7, false); SKR_K(8, false); }
-#undef SKR_K
-  return finish_launch();
+  ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.numel = args.numel;
+  return with_tile<sizeof(T) == 4>(args.numel, args.sample_numel, false, g.mode, [&](auto tile) {
+    with_count<2, 8>(args.n_terms, [&](auto n) {
+      hipLaunchKernelGGL((step_kernel_rk<T, decltype(n)::value, UV, decltype(tile)::value>), g.grid, dim3(BLOCK), 0, stream, ra);
+    });
+    return finish_launch();
+  });
 }
 
 template <typename T>
@@ -402,7 +401,7 @@ static int launch_rk(const StepArgs<float>& args, hipStream_t stream) {
     const int rc = launch_one_trip_rk<T>(args, false, stream, taken);
     if (taken) return rc;
   }
-  if (args.rows != nullptr) return SKR_ERR_UNSUPPORTED;
+  if (has_table(args.form)) return SKR_ERR_UNSUPPORTED;
   const int uv = g_tune.rk_uv ? g_tune.rk_uv : 1;  // measured on the cfg5 shard: 1, 2 and 4 vectors per lane are within 2 %
   if (uv == 4) return launch_rk_uv<T, 4>(args, stream);
   if (uv == 2) return launch_rk_uv<T, 2>(args, stream);
@@ -413,7 +412,7 @@ template <typename TA, typename TB, typename TO0, typename TO1, typename Acc, bo
 static int launch(StepArgs<Acc>& args, hipStream_t stream) {
   // fast path: uniform 16/32-bit dtype, single output of the same dtype, fp32 accumulate
   if constexpr (std::is_same<Acc, float>::value && std::is_same<TA, TB>::value && std::is_same<TO0, TA>::value && ST0 && !HAS1 && !CONV) {
-    if (args.n_a == args.n_terms && (!NOISE || args.zeta0 != 0.f || args.rows != nullptr)) {
+    if (args.n_a == args.n_terms && (!NOISE || args.zeta0 != 0.f || has_table(args.form))) {
       bool taken = false;
       const int rc = launch_k<TA, NOISE>(args, stream, taken);
       if (taken) return rc;
@@ -438,21 +437,17 @@ static int launch(StepArgs<Acc>& args, hipStream_t stream) {
     const int rc = launch_one_trip_two<TA>(args, NOISE, std::is_same<TB, float>::value, stream, taken);
     if (taken) return rc;
   }
-  if (args.rows != nullptr) return SKR_ERR_UNSUPPORTED;  // device-resident rows are read by the one-trip kernels only
+  if (has_table(args.form)) return SKR_ERR_UNSUPPORTED;  // device-resident rows are read by the one-trip kernels only
   constexpr int UV = uv_for(NOISE, HAS1);
   Geometry g = geometry<UV, NOISE>(args.numel, args.sample_numel);
   args.grid_mode = g.mode;
   args.vps = args.sample_numel / VEC;
   constexpr bool HAS32 = std::is_same<Acc, float>::value && (std::is_same<TA, float>::value || std::is_same<TB, float>::value ||
                                                                (ST0 && std::is_same<TO0, float>::value) || (HAS1 && std::is_same<TO1, float>::value));
-  if constexpr (HAS32) {  // a 32-bit tensor takes part: whole-line tile layout when the launch is made of whole tiles
-    if (tile_ok(args.numel, args.sample_numel, NOISE, g.mode)) {
-      hipLaunchKernelGGL((step_kernel<TA, TB, TO0, TO1, Acc, ST0, HAS1, NOISE, CONV, true>), g.grid, dim3(BLOCK), 0, stream, args);
-      return finish_launch();
-    }
-  }
-  hipLaunchKernelGGL((step_kernel<TA, TB, TO0, TO1, Acc, ST0, HAS1, NOISE, CONV, false>), g.grid, dim3(BLOCK), 0, stream, args);
-  return finish_launch();
+  return with_tile<HAS32>(args.numel, args.sample_numel, NOISE, g.mode, [&](auto tile) {
+    hipLaunchKernelGGL((step_kernel<TA, TB, TO0, TO1, Acc, ST0, HAS1, NOISE, CONV, decltype(tile)::value>), g.grid, dim3(BLOCK), 0, stream, args);
+    return finish_launch();
+  });
 }
 
 template <typename TA, typename TB, typename TO0, typename TO1, typename Acc>
@@ -488,10 +483,13 @@ static int pick_out(StepArgs<Acc>& a, int dt_a, int o0, int o1, bool noise, bool
   return pick_flags<TA, TB, Wide, Wide, Acc>(a, st0, has1, noise, conv, s);
 }
 
+// a launch of this plan draws noise by the plan's own scalars (table launches: whether a draw happens is the row's business -- a zero
+// zeta skips it at run time -- so every noise_mode 1 launch of theirs counts as drawing)
+static bool plan_draws(const skr_step_plan& p) { return p.noise_mode == 1 && (p.zeta0 != 0.0 || (p.out1_dtype != SKR_NONE && p.zeta1 != 0.0)); }
+
 template <typename Acc>
 static int pick_in(StepArgs<Acc>& a, const skr_step_plan& p, hipStream_t s) {
-  // (indexed launches: whether a draw happens is the row's business -- a zero zeta skips it at run time)
-  const bool noise = p.noise_mode == 1 && (a.rows != nullptr || p.zeta0 != 0.0 || (p.out1_dtype != SKR_NONE && p.zeta1 != 0.0));
+  const bool noise = p.noise_mode == 1 && (has_table(a.form) || plan_draws(p));
   const int da = p.dtype_a, db = (p.n_group_a == p.n_terms) ? p.dtype_a : p.dtype_b;
   const bool conv = p.convert_to != 0 || p.convert_from != 0;
   if constexpr (std::is_same<Acc, double>::value) {
@@ -514,9 +512,9 @@ static int pick_in(StepArgs<Acc>& a, const skr_step_plan& p, hipStream_t s) {
 
 template <typename Acc>
 static int run(const skr_step_plan& p, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds, int64_t numel, hipStream_t s,
-               const skr_step_row* rows = nullptr, const int32_t* index = nullptr, int32_t row_offset = 0, int per_sample = 0) {
+               RowForm form = RowForm::Kernarg, const skr_step_row* rows = nullptr, const int32_t* index = nullptr, int32_t row_offset = 0) {
   StepArgs<Acc> a;
-  a.rows = rows; a.index = index; a.row_offset = row_offset; a.per_sample = per_sample;
+  a.form = form; a.rows = rows; a.index = index; a.row_offset = row_offset;
   for (int k = 0; k < p.n_terms; ++k) {
     a.in[k] = inputs[k];
     a.c0[k] = (Acc)p.coef0[k];
@@ -542,41 +540,50 @@ static int run(const skr_step_plan& p, const void* const* inputs, void* out0, vo
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
-                            void* stream, const skr_step_row* rows, const int32_t* index, int32_t row_offset, int per_sample = 0) {  // per_sample: 0 no, 1 yes, 2 rolling
-  skr::DeviceGuard device_guard(out0 ? out0 : out1);
-  if (!plan) return SKR_ERR_NULL;
-  const skr_step_plan& p = *plan;
+// a sample size that divides the launch into samples made of whole `multiple`s of elements
+static int samples_ok(const skr_step_plan& p, int64_t numel, int64_t multiple) {
+  if (p.sample_numel <= 0 || numel % p.sample_numel != 0) return SKR_ERR_SHAPE;
+  return p.sample_numel % multiple == 0 ? SKR_OK : SKR_ERR_UNSUPPORTED;
+}
+
+// every check that depends on the plan and the element count alone (skr_program_create makes them once, a launch every time)
+static int validate_plan(const skr_step_plan& p, int64_t numel) {
   if (p.n_terms < 0 || p.n_terms > SKR_MAX_TERMS || p.n_group_a < 0 || p.n_group_a > p.n_terms) return SKR_ERR_TERMS;
-  if (p.n_terms > 0 && !inputs) return SKR_ERR_NULL;
   if (numel < 0) return SKR_ERR_SHAPE;
+  if (p.out0_dtype == SKR_NONE && p.out1_dtype == SKR_NONE) return SKR_ERR_NULL;
+  if (p.noise_mode != 0 && p.noise_mode != 1) return SKR_ERR_UNSUPPORTED;
+  if (p.convert_to < 0 || p.convert_to > 3 || p.convert_from < 0 || p.convert_from > 3) return SKR_ERR_UNSUPPORTED;
+  if ((p.convert_to || p.convert_from) && (p.n_group_a < 2 || p.out1_dtype == SKR_NONE)) return SKR_ERR_TERMS;
+  // fused Philox needs every 8-element lane group inside one sample; other shapes draw the noise
+  // with skr_noise_random (any shape) and pass it as an ordinary input term.
+  if (skr::plan_draws(p) && numel > 0) return samples_ok(p, numel, 8);
+  return SKR_OK;
+}
+
+static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
+                            void* stream, skr::RowForm form, const skr_step_row* rows, const int32_t* index, int32_t row_offset) {
+  skr::DeviceGuard device_guard(out0 ? out0 : out1);
+  if (!plan || (has_table(form) && (!rows || (per_sample_rows(form) && !index)))) return SKR_ERR_NULL;  // (from here on: rows != nullptr exactly when has_table(form))
+  const skr_step_plan& p = *plan;
+  // (ahead of the plan's own checks: a launch that draws without seeds is told so whatever else is wrong with its sample size)
+  if (p.noise_mode == 1 && (has_table(form) || skr::plan_draws(p)) && numel > 0 && !seeds_dev) return SKR_ERR_NULL;
+  if (const int rc = validate_plan(p, numel)) return rc;
   if (numel == 0) return SKR_OK;  // empty batch: nothing to do (the reference returns empty tensors)
   const bool st0 = p.out0_dtype != SKR_NONE, has1 = p.out1_dtype != SKR_NONE;
-  if ((st0 && !out0) || (has1 && !out1) || (!st0 && !has1)) return SKR_ERR_NULL;
+  if ((p.n_terms > 0 && !inputs) || (st0 && !out0) || (has1 && !out1)) return SKR_ERR_NULL;
   for (int k = 0; k < p.n_terms; ++k) {
     if (!inputs[k]) return SKR_ERR_NULL;
     if (!aligned16(inputs[k])) return SKR_ERR_ALIGN;
   }
   if ((st0 && !aligned16(out0)) || (has1 && !aligned16(out1))) return SKR_ERR_ALIGN;
-  const bool wants_noise = p.noise_mode == 1 && (rows != nullptr || p.zeta0 != 0.0 || (has1 && p.zeta1 != 0.0));
-  if (p.noise_mode != 0 && p.noise_mode != 1) return SKR_ERR_UNSUPPORTED;
-  if (p.convert_to < 0 || p.convert_to > 3 || p.convert_from < 0 || p.convert_from > 3) return SKR_ERR_UNSUPPORTED;
-  if ((p.convert_to || p.convert_from) && (p.n_group_a < 2 || !has1)) return SKR_ERR_TERMS;
-  if (wants_noise) {
-    if (!seeds_dev) return SKR_ERR_NULL;
-    if (p.sample_numel <= 0 || numel % p.sample_numel != 0) return SKR_ERR_SHAPE;
-    // fused Philox needs every 8-element lane group inside one sample; other shapes draw the noise
-    // with skr_noise_random (any shape) and pass it as an ordinary input term.
-    if (p.sample_numel % 8 != 0) return SKR_ERR_UNSUPPORTED;
-  }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (rows != nullptr) {
-    if (p.acc_f64 || p.n_terms > SKR_ROW_TERMS || row_offset < 0) return SKR_ERR_UNSUPPORTED;
-    if (per_sample) {  // one row per sample: the batch is numel / sample_numel, and a workgroup (2048 elements) must lie inside one sample
-      if (p.sample_numel <= 0 || numel % p.sample_numel != 0) return SKR_ERR_SHAPE;
-      if (p.sample_numel % 2048 != 0) return SKR_ERR_UNSUPPORTED;
+  if (has_table(form)) {
+    // one row per sample: the batch is numel / sample_numel, and a workgroup (2048 elements) must lie inside one sample
+    if (per_sample_rows(form) || p.noise_mode == 1) {
+      if (const int rc = samples_ok(p, numel, per_sample_rows(form) ? 2048 : 8)) return rc;
     }
-    return skr::run<float>(p, inputs, out0, out1, seeds_dev, numel, s, rows, index, row_offset, per_sample);
+    if (p.acc_f64 || p.n_terms > SKR_ROW_TERMS || row_offset < 0) return SKR_ERR_UNSUPPORTED;
+    return skr::run<float>(p, inputs, out0, out1, seeds_dev, numel, s, form, rows, index, row_offset);
   }
   return p.acc_f64 ? skr::run<double>(p, inputs, out0, out1, seeds_dev, numel, s)
                    : skr::run<float>(p, inputs, out0, out1, seeds_dev, numel, s);
@@ -584,28 +591,25 @@ static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs
 
 extern "C" int skr_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
                                const uint64_t* seeds_dev, int64_t numel, void* stream) {
-  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, nullptr, nullptr, 0);
+  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, skr::RowForm::Kernarg, nullptr, nullptr, 0);
 }
 
 extern "C" int skr_step_launch_indexed(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
                                        const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
                                        const int32_t* index_dev, int32_t row_offset, void* stream) {
-  if (!rows_dev) return SKR_ERR_NULL;
-  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, rows_dev, index_dev, row_offset);
+  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, skr::RowForm::WholeBatch, rows_dev, index_dev, row_offset);
 }
 
 extern "C" int skr_step_launch_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
                                                   const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
                                                   const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
-  if (!rows_dev || !sample_index_dev) return SKR_ERR_NULL;
-  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, rows_dev, sample_index_dev, row_offset, 1);
+  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, skr::RowForm::PerSample, rows_dev, sample_index_dev, row_offset);
 }
 
 extern "C" int skr_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1,
                                        const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
                                        const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
-  if (!rows_dev || !sample_index_dev) return SKR_ERR_NULL;
-  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, rows_dev, sample_index_dev, row_offset, 2);
+  return step_launch_impl(plan, inputs, out0, out1, seeds_dev, numel, stream, skr::RowForm::Rolling, rows_dev, sample_index_dev, row_offset);
 }
 
 // ---- step programs: a plan kept by the library, launched by handle ------------------------------------------------------------------
@@ -619,18 +623,8 @@ struct skr_program {
 extern "C" int skr_program_create(const skr_step_plan* plan, int64_t numel, skr_program** out) {
   if (!plan || !out) return SKR_ERR_NULL;
   *out = nullptr;
-  const skr_step_plan& p = *plan;
-  if (p.n_terms < 0 || p.n_terms > SKR_MAX_TERMS || p.n_group_a < 0 || p.n_group_a > p.n_terms) return SKR_ERR_TERMS;
-  if (numel < 0) return SKR_ERR_SHAPE;
-  if (p.out0_dtype == SKR_NONE && p.out1_dtype == SKR_NONE) return SKR_ERR_NULL;
-  if (p.noise_mode != 0 && p.noise_mode != 1) return SKR_ERR_UNSUPPORTED;
-  if (p.convert_to < 0 || p.convert_to > 3 || p.convert_from < 0 || p.convert_from > 3) return SKR_ERR_UNSUPPORTED;
-  if ((p.convert_to || p.convert_from) && (p.n_group_a < 2 || p.out1_dtype == SKR_NONE)) return SKR_ERR_TERMS;
-  if (p.noise_mode == 1 && numel > 0) {
-    if (p.sample_numel <= 0 || numel % p.sample_numel != 0) return SKR_ERR_SHAPE;
-    if (p.sample_numel % 8 != 0) return SKR_ERR_UNSUPPORTED;
-  }
-  *out = new (std::nothrow) skr_program{p, numel};
+  if (const int rc = validate_plan(*plan, numel)) return rc;
+  *out = new (std::nothrow) skr_program{*plan, numel};
   return *out ? SKR_OK : SKR_ERR_LAUNCH;
 }
 
@@ -640,7 +634,7 @@ extern "C" int skr_program_launch(const skr_program* prog, const void* const* in
   skr_step_plan p = prog->plan;  // (a private copy: one program may be launched from several threads at once)
   p.stream0 = stream0;
   p.stream1 = stream1;
-  return step_launch_impl(&p, inputs, out0, out1, seeds_dev, prog->numel, stream, nullptr, nullptr, 0);
+  return step_launch_impl(&p, inputs, out0, out1, seeds_dev, prog->numel, stream, skr::RowForm::Kernarg, nullptr, nullptr, 0);
 }
 
 extern "C" void skr_program_destroy(skr_program* prog) { delete prog; }

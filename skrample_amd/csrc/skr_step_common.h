@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <stdint.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/skrample_hip.h"
 #include "skr_philox.h"
 #include "skr_pack.h"
@@ -42,6 +43,15 @@ constexpr int MAXK = SKR_MAX_TERMS;
 struct bf16_t { uint16_t v; };
 struct f16_t { _Float16 v; };
 
+// Where a launch gets its scalars (coefficients, zetas, Philox streams, conversion constants) from:
+//   Kernarg     the plan's values, packed into the kernarg                                      skr_step_launch
+//   WholeBatch  rows[index[0] + row_offset], read by the kernel (one-trip kernels only)         skr_step_launch_indexed
+//   PerSample   rows[index[sample] + row_offset], index holding one entry per sample            skr_step_launch_indexed_per_sample
+//   Rolling     the same, with inactive samples (entry < 0) and absent operands (both coefficients zero) skipped   skr_step_launch_rolling
+enum class RowForm : int32_t { Kernarg, WholeBatch, PerSample, Rolling };
+constexpr bool has_table(RowForm f) { return f != RowForm::Kernarg; }
+constexpr bool per_sample_rows(RowForm f) { return f == RowForm::PerSample || f == RowForm::Rolling; }
+
 template <typename Acc>
 struct StepArgs {
   const void* in[MAXK];
@@ -60,13 +70,11 @@ struct StepArgs {
   int32_t grid_mode;    // 0 flat grid, 1 per-sample grid (noise kernels, sample_numel % 8 == 0)
   int32_t conv_to, conv_from;  // rounded pair conversion (CONV kernels): see convert_rounded()
   double ck[4];
-  // skr_step_launch_indexed: the scalars above are read from rows[index[0] + row_offset] by the kernel (one-trip kernels only);
-  // per_sample (skr_step_launch_indexed_per_sample): from rows[index[sample] + row_offset], index holding one entry per sample;
-  // per_sample == 2 (skr_step_launch_rolling): the same, with inactive samples (entry < 0) and absent operands (zero coefficients) skipped
+  // the table forms' data (host side only: no kernel reads these four from a StepArgs); rows != nullptr exactly when has_table(form)
   const skr_step_row* rows;
   const int32_t* index;
   int32_t row_offset;
-  int32_t per_sample;
+  RowForm form;
 };
 
 // device-resident scalars of a launch (skr_step_launch_indexed); rows == nullptr: use the kernarg values
@@ -330,7 +338,7 @@ __device__ __forceinline__ void fma_noise8(Acc zeta, const float z[VEC], Acc s[V
   for (int i = 0; i < VEC; ++i) s[i] = fma_(zeta, (Acc)z[i], s[i]);
 }
 
-// kernarg of the Runge-Kutta stage kernels (grid-stride and one-trip)
+// kernarg of the grid-stride Runge-Kutta stage kernel step_kernel_rk (the one-trip kernel has its own, RkOneTripArgs)
 struct RkArgs {
   const void* in[8];
   float c1[8];
@@ -339,14 +347,7 @@ struct RkArgs {
   float chain;
   float ck[4];
   int32_t conv_to, conv_from;
-  int32_t xmap_lr;
   int64_t numel;
-  RowRef tab;
-  // stochastic final stage (one-trip kernel only): out1 += zeta1 * N(stream1)
-  const uint64_t* seeds;
-  float zeta1;
-  int32_t bps_shift;
-  uint64_t stream1;
 };
 
 // XCD-aware chunk map of the one-trip kernels (skr_step_fast.hip, skr_step_backward.hip)
@@ -366,6 +367,25 @@ static inline int xmap_lr_for(int64_t chunks) {
 
 extern thread_local int g_last_hip_error;
 int finish_launch();
+
+// ---- host side: run-time values to template arguments, kernarg packing -------------------------------------------------------------
+template <typename T> struct type_tag { using type = T; };
+template <bool B> using bool_c = std::integral_constant<bool, B>;
+
+// calls f(std::integral_constant<int, N>{}) for the N of LO..HI that equals n, and nothing for an n outside
+template <int LO, int HI, typename F>
+static inline void with_count(int n, F&& f) {
+  if constexpr (LO <= HI) {
+    if (n == LO) f(std::integral_constant<int, LO>{});
+    else with_count<LO + 1, HI>(n, f);
+  }
+}
+
+// the first n operand pointers and their coefficients into a kernarg's KMAX slots; the slots beyond hold nullptr / 0
+template <int KMAX>
+static inline void fill_operands(const void* const* src_in, const float* src_c, int n, const void* (&in)[KMAX], float (&c)[KMAX]) {
+  for (int k = 0; k < KMAX; ++k) { in[k] = k < n ? src_in[k] : nullptr; c[k] = k < n ? src_c[k] : 0.f; }
+}
 
 // one-trip launches (skr_step_fast.hip); `taken` = false when the plan is outside what they cover
 template <typename T> int launch_one_trip_k(const StepArgs<float>& args, bool noise, hipStream_t stream, bool& taken);

@@ -376,12 +376,13 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
 }
 
 // one-trip launches: whole chunks, and with in-kernel noise samples made of whole chunks (any number of them)
-// (per-sample rows: a workgroup must belong to one sample with or without noise)
-static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, int* bps_shift, bool forced = false, bool per_sample = false) {
+// (per-sample rows: a workgroup must belong to one sample with or without noise; table launches have no other kernel, so the
+//  one_trip switch does not apply to them)
+static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, RowForm form, int* bps_shift) {
   constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
-  if ((!g_tune.one_trip && !forced) || numel % CHUNK != 0 || numel / CHUNK > 0x7fffffffll) return false;
+  if ((!g_tune.one_trip && !has_table(form)) || numel % CHUNK != 0 || numel / CHUNK > 0x7fffffffll) return false;
   *bps_shift = 0;
-  if (!noise && !per_sample) return true;
+  if (!noise && !per_sample_rows(form)) return true;
   if (sample_numel % CHUNK != 0) return false;
   const int64_t bps = sample_numel / CHUNK;
   if (bps > 0x3fffffffll) return false;
@@ -389,106 +390,104 @@ static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, int* bp
   else *bps_shift = -(int)bps;  // any chunk count per sample: the kernel divides
   return true;
 }
-
+// fp32 launches use the tile layout; with the tile switch off they are left to the other kernels, which table launches do not have
+template <typename T> static bool tile_switched_off(RowForm form) { return sizeof(T) == 4 && !g_tune.tile && !has_table(form); }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-template <typename T, bool NOISE, int KMAX>
+// The one place that maps a launch form to a kernel instantiation: calls
+// f(type_tag<TR>{}, bool_c<PACE>{}, bool_c<TAB>{}) with the template arguments of the kernel this form runs.
+//   form        TR            PACE                                          TAB
+//   Kernarg     T             g_tune.pace where PACED, else false           false
+//   WholeBatch  T             PACED                                         true
+//   PerSample   PerSample<T>  PACED                                         true
+//   Rolling     Rolling<T>    false                                         false
+// PACED: this operand count has a paced instantiation (1-8-operand k1, noisy 2-11-operand k2; step_kernel_rk1 has no such parameter).
+// TABLE: it has table instantiations (its operands fit a device-resident row); false is returned for a table form without one.
+template <typename T, bool PACED, bool TABLE, typename F>
+static bool with_form(RowForm form, F&& f) {
+  if (form == RowForm::Kernarg) {
+    if (PACED && g_tune.pace) f(type_tag<T>{}, bool_c<PACED>{}, bool_c<false>{});
+    else f(type_tag<T>{}, bool_c<false>{}, bool_c<false>{});
+    return true;
+  }
+  if constexpr (TABLE) {
+    if (form == RowForm::WholeBatch) f(type_tag<T>{}, bool_c<PACED>{}, bool_c<true>{});
+    else if (form == RowForm::PerSample) f(type_tag<PerSample<T>>{}, bool_c<PACED>{}, bool_c<true>{});
+    else f(type_tag<Rolling<T>>{}, bool_c<false>{}, bool_c<false>{});
+  }
+  return TABLE;
+}
+
+template <typename T, bool NOISE>
 static int launch_k1(const StepArgs<float>& args, int bps_shift, hipStream_t stream) {
   constexpr bool TILE = sizeof(T) == 4;  // whole chunks are whole tiles
   const int64_t chunks = args.numel / ((int64_t)BLOCK * VEC);
-  OneTripArgs<KMAX> fa;
-  for (int k = 0; k < KMAX; ++k) { fa.in[k] = k < args.n_terms ? args.in[k] : nullptr; fa.c0[k] = k < args.n_terms ? args.c0[k] : 0.f; }
-  fa.out0 = args.out0; fa.seeds = args.seeds; fa.zeta0 = args.zeta0; fa.stream0 = args.stream0;
-  fa.bps_shift = bps_shift; fa.xmap_lr = xmap_lr_for(chunks);
-  fa.tab = RowRef{args.rows, args.index, args.row_offset};
-#define SKR_K(N) case N: if (args.per_sample == 2) hipLaunchKernelGGL((step_kernel_k1<Rolling<T>, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                        else if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                        else if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                        else if (g_tune.pace) hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, true, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                        else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); break
-  // more than 8 operands: one unpaced instantiation each (plus the table form while the operands fit a device-resident row)
-#define SKR_KB(N) case N: if (args.rows != nullptr) { if constexpr (N <= SKR_ROW_TERMS) { \
-                           if (args.per_sample == 2) hipLaunchKernelGGL((step_kernel_k1<Rolling<T>, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                           else if (args.per_sample) hipLaunchKernelGGL((step_kernel_k1<PerSample<T>, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                           else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); \
-                         } else return SKR_ERR_UNSUPPORTED; } \
-                         else hipLaunchKernelGGL((step_kernel_k1<T, N, NOISE, TILE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa); break
-  if constexpr (KMAX == 4) { switch (args.n_terms) { SKR_K(1); SKR_K(2); SKR_K(3); SKR_K(4); } }
-  else if constexpr (KMAX == 8) { switch (args.n_terms) { SKR_K(5); SKR_K(6); SKR_K(7); SKR_K(8); } }
-  else if constexpr (KMAX == 12) { switch (args.n_terms) { SKR_KB(9); SKR_KB(10); SKR_KB(11); SKR_KB(12); } }
-  else if constexpr (KMAX == 16) { switch (args.n_terms) { SKR_KB(13); SKR_KB(14); SKR_KB(15); SKR_KB(16); } }
-  else { switch (args.n_terms) { SKR_KB(17); SKR_KB(18); SKR_KB(19); SKR_KB(20); } }
-#undef SKR_K
-#undef SKR_KB
-  return finish_launch();
+  bool launched = true;
+  with_count<1, ONE_TRIP_MAX_K>(args.n_terms, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    OneTripArgs<one_trip_kmax(N)> fa;
+    fill_operands(args.in, args.c0, N, fa.in, fa.c0);
+    fa.out0 = args.out0; fa.seeds = args.seeds; fa.zeta0 = args.zeta0; fa.stream0 = args.stream0;
+    fa.bps_shift = bps_shift; fa.xmap_lr = xmap_lr_for(chunks);
+    fa.tab = RowRef{args.rows, args.index, args.row_offset};
+    // more than 8 operands: one unpaced instantiation each (plus the table forms while the operands fit a device-resident row)
+    launched = with_form<T, (N <= 8), (N <= SKR_ROW_TERMS)>(args.form, [&](auto tr, auto pace, auto tab) {
+      hipLaunchKernelGGL((step_kernel_k1<typename decltype(tr)::type, N, NOISE, TILE, decltype(pace)::value, decltype(tab)::value>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa);
+    });
+  });
+  return launched ? finish_launch() : SKR_ERR_UNSUPPORTED;
 }
-
 
 template <typename T>
 int launch_one_trip_k(const StepArgs<float>& args, bool noise, hipStream_t stream, bool& taken) {
   taken = false;
   int bps_shift = 0;
-  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr, args.per_sample != 0) || (sizeof(T) == 4 && !g_tune.tile && args.rows == nullptr)) return SKR_OK;
+  if (!one_trip_ok(args.numel, args.sample_numel, noise, args.form, &bps_shift) || tile_switched_off<T>(args.form)) return SKR_OK;
   if (args.n_terms > ONE_TRIP_MAX_K) return SKR_OK;
   taken = true;
-#define SKR_GO(NOISE)                                                              \
-  switch (one_trip_kmax(args.n_terms)) {                                           \
-    case 4: return launch_k1<T, NOISE, 4>(args, bps_shift, stream);                \
-    case 8: return launch_k1<T, NOISE, 8>(args, bps_shift, stream);                \
-    case 12: return launch_k1<T, NOISE, 12>(args, bps_shift, stream);              \
-    case 16: return launch_k1<T, NOISE, 16>(args, bps_shift, stream);              \
-    default: return launch_k1<T, NOISE, 20>(args, bps_shift, stream);              \
-  }
-  if (noise) { SKR_GO(true) }
-  SKR_GO(false)
-#undef SKR_GO
+  return noise ? launch_k1<T, true>(args, bps_shift, stream) : launch_k1<T, false>(args, bps_shift, stream);
 }
 template int launch_one_trip_k<bf16_t>(const StepArgs<float>&, bool, hipStream_t, bool&);
 template int launch_one_trip_k<f16_t>(const StepArgs<float>&, bool, hipStream_t, bool&);
 template int launch_one_trip_k<float>(const StepArgs<float>&, bool, hipStream_t, bool&);
 
-template <typename T, bool NOISE, int KMAX, int BLK>
+template <typename T, bool NOISE, int BLK>
 static int launch_rk1(const StepArgs<float>& args, unsigned chunks, int bps_shift, hipStream_t stream) {
   constexpr bool TILE = sizeof(T) == 4;
   if constexpr (BLK == 128) {  // half-size chunks: twice as many of them, per sample too
     chunks *= 2;
     bps_shift = bps_shift >= 0 ? bps_shift + 1 : 2 * bps_shift;
   }
-  RkOneTripArgs<KMAX> ra;
-  ra.seeds = args.seeds; ra.zeta1 = args.zeta1; ra.stream1 = args.stream1; ra.bps_shift = bps_shift;
-  for (int k = 0; k < KMAX; ++k) { ra.in[k] = k < args.n_terms ? args.in[k] : nullptr; ra.c1[k] = k < args.n_terms ? args.c1[k] : 0.f; }
-  ra.out0 = args.out0; ra.out1 = args.out1; ra.chain = args.chain;
-  for (int i = 0; i < 4; ++i) ra.ck[i] = (float)args.ck[i];
-  ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.xmap_lr = xmap_lr_for(chunks); ra.tab = RowRef{args.rows, args.index, args.row_offset};
-#define SKR_K(N) case N: if (args.per_sample == 2) hipLaunchKernelGGL((step_kernel_rk1<Rolling<T>, N, TILE, NOISE, false, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
-                        else if (args.per_sample) hipLaunchKernelGGL((step_kernel_rk1<PerSample<T>, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
-                        else if (args.rows != nullptr) hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, true, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); \
-                        else hipLaunchKernelGGL((step_kernel_rk1<T, N, TILE, NOISE, false, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra); break
-  if constexpr (KMAX == 4) { switch (args.n_terms) { SKR_K(2); SKR_K(3); SKR_K(4); } }
-  else { switch (args.n_terms) { SKR_K(5); SKR_K(6); SKR_K(7); SKR_K(8); } }
-#undef SKR_K
+  with_count<2, 8>(args.n_terms, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    RkOneTripArgs<(N <= 4 ? 4 : 8)> ra;
+    fill_operands(args.in, args.c1, N, ra.in, ra.c1);
+    ra.seeds = args.seeds; ra.zeta1 = args.zeta1; ra.stream1 = args.stream1; ra.bps_shift = bps_shift;
+    ra.out0 = args.out0; ra.out1 = args.out1; ra.chain = args.chain;
+    for (int i = 0; i < 4; ++i) ra.ck[i] = (float)args.ck[i];
+    ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.xmap_lr = xmap_lr_for(chunks); ra.tab = RowRef{args.rows, args.index, args.row_offset};
+    with_form<T, false, true>(args.form, [&](auto tr, auto, auto tab) {
+      hipLaunchKernelGGL((step_kernel_rk1<typename decltype(tr)::type, N, TILE, NOISE, decltype(tab)::value, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra);
+    });
+  });
   return finish_launch();
 }
-
 
 template <typename T>
 int launch_one_trip_rk(const StepArgs<float>& args, bool noise, hipStream_t stream, bool& taken) {
   taken = false;
   int bps_shift = 0;
-  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr, args.per_sample != 0) || (sizeof(T) == 4 && !g_tune.tile && args.rows == nullptr)) return SKR_OK;
-  if (noise && args.rows == nullptr && args.zeta0 != 0.f) return SKR_OK;  // (a noisy derivative does not occur; left to the general kernel)
+  if (!one_trip_ok(args.numel, args.sample_numel, noise, args.form, &bps_shift) || tile_switched_off<T>(args.form)) return SKR_OK;
+  if (noise && !has_table(args.form) && args.zeta0 != 0.f) return SKR_OK;  // (a noisy derivative does not occur; left to the general kernel)
   taken = true;
   const unsigned chunks = (unsigned)(args.numel / ((int64_t)BLOCK * VEC));
   // 128-thread workgroups for the 2-6 operand stages (tools/bench_plan.py rk, same box: K=4 33.5 vs 34.0 us, K=5 38.7 vs 39.8, K=6 43.7 vs
   // 45.2, K >= 7 unchanged; round 4, A/B/A/B on one box, profiles/r04_bench_plan_ab.txt: K=2 23.6-23.8 vs 24.1-24.2 us, K=3 29.16-29.26 vs
   // 29.17-29.30 -- round 3 had read K=2 / 3 as 1-2 % slower from runs on different boxes); rk_blk = 128 / 256 forces one size
   const bool small_blocks = g_tune.rk_blk == 128 || (g_tune.rk_blk == 0 && args.n_terms <= 6);
-  if (small_blocks && chunks < 0x40000000u && bps_shift > -0x20000000) {
-    if (args.n_terms <= 4) return noise ? launch_rk1<T, true, 4, 128>(args, chunks, bps_shift, stream) : launch_rk1<T, false, 4, 128>(args, chunks, bps_shift, stream);
-    return noise ? launch_rk1<T, true, 8, 128>(args, chunks, bps_shift, stream) : launch_rk1<T, false, 8, 128>(args, chunks, bps_shift, stream);
-  }
-  if (args.n_terms <= 4) return noise ? launch_rk1<T, true, 4, 256>(args, chunks, bps_shift, stream) : launch_rk1<T, false, 4, 256>(args, chunks, bps_shift, stream);
-  return noise ? launch_rk1<T, true, 8, 256>(args, chunks, bps_shift, stream) : launch_rk1<T, false, 8, 256>(args, chunks, bps_shift, stream);
+  if (small_blocks && chunks < 0x40000000u && bps_shift > -0x20000000)
+    return noise ? launch_rk1<T, true, 128>(args, chunks, bps_shift, stream) : launch_rk1<T, false, 128>(args, chunks, bps_shift, stream);
+  return noise ? launch_rk1<T, true, 256>(args, chunks, bps_shift, stream) : launch_rk1<T, false, 256>(args, chunks, bps_shift, stream);
 }
 template int launch_one_trip_rk<bf16_t>(const StepArgs<float>&, bool, hipStream_t, bool&);
 template int launch_one_trip_rk<f16_t>(const StepArgs<float>&, bool, hipStream_t, bool&);
@@ -675,73 +674,55 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k2(const TwoOutArgs<two_out
   store8<float, float, true, NT>(a.out0, v, s0);
 }
 
-template <typename TA, int NA, int NB, bool NOISE, bool PACE, bool TAB, bool NT = false>
+// PACED, TABLE: see with_form.  NT: non-temporal stores, an instantiation of the kernarg form alone
+template <typename TA, int NA, int NB, bool NOISE, bool PACED, bool TABLE, bool NT = false>
 static int launch_k2(const StepArgs<float>& args, int bps_shift, hipStream_t stream) {
-  constexpr int NMAX = two_out_nmax(NA + NB);
   const int64_t chunks = args.numel / ((int64_t)BLOCK * VEC);
-  TwoOutArgs<NMAX> ta;
-  for (int k = 0; k < NMAX; ++k) {
-    const bool live = k < NA + NB;
-    ta.in[k] = live ? args.in[k] : nullptr; ta.c0[k] = live ? args.c0[k] : 0.f; ta.c1[k] = live ? args.c1[k] : 0.f;
-  }
+  TwoOutArgs<two_out_nmax(NA + NB)> ta;
+  fill_operands(args.in, args.c0, NA + NB, ta.in, ta.c0);
+  fill_operands(args.in, args.c1, NA + NB, ta.in, ta.c1);
   ta.out0 = args.out0; ta.out1 = args.out1; ta.seeds = args.seeds;
   ta.xmap_lr = xmap_lr_for(chunks); ta.bps_shift = bps_shift;
   ta.stream0 = args.stream0; ta.stream1 = args.stream1;
   ta.chain = args.chain; ta.zeta0 = args.zeta0; ta.zeta1 = args.zeta1;
   ta.tab = RowRef{args.rows, args.index, args.row_offset};
-  if constexpr (TAB && !NT) {
-    if (args.per_sample == 2) {
-      hipLaunchKernelGGL((step_kernel_k2<Rolling<TA>, NA, NB, NOISE, false, false>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
-      return finish_launch();
-    }
-    if (args.per_sample) {
-      hipLaunchKernelGGL((step_kernel_k2<PerSample<TA>, NA, NB, NOISE, PACE, true>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
-      return finish_launch();
-    }
-  }
-  hipLaunchKernelGGL((step_kernel_k2<TA, NA, NB, NOISE, PACE, TAB, NT>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
-  return finish_launch();
+  const bool launched = with_form<TA, PACED, TABLE && !NT>(args.form, [&](auto tr, auto pace, auto tab) {
+    hipLaunchKernelGGL((step_kernel_k2<typename decltype(tr)::type, NA, NB, NOISE, decltype(pace)::value, decltype(tab)::value, NT>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
+  });
+  return launched ? finish_launch() : SKR_ERR_UNSUPPORTED;
 }
 
-// the operand counts the samplers emit (tools/trace_plans.py): UniPC / SPC of order n give 2n+2 (+2 with a noise
-// tensor) 16-bit operands and the previous corrected state in fp32; their first steps have no fp32 operand yet
 // store policy of the no-noise two-output launches (see store8): "two_nt" 1 / 0 forces it, -1 = where it measured faster
 static bool nt_stores(int operands) { return g_tune.two_nt >= 0 ? g_tune.two_nt != 0 : NT_FROM_OPERANDS > 0 && operands >= NT_FROM_OPERANDS; }
+
+// TUNED: the operand counts whose load pacing (with noise) and store policy (without) were measured; the others run unpaced, write-through
+template <typename TA, int NA, int NB, bool TUNED>
+static int launch_k2_as(const StepArgs<float>& args, bool noise, int bps_shift, hipStream_t stream) {
+  constexpr bool TABLE = NA + NB <= SKR_ROW_TERMS;
+  if (noise) return launch_k2<TA, NA, NB, true, TUNED, TABLE>(args, bps_shift, stream);
+  if constexpr (TUNED && NA + NB >= NT_FROM_OPERANDS) {
+    if (!has_table(args.form) && nt_stores(NA + NB)) return launch_k2<TA, NA, NB, false, false, false, true>(args, bps_shift, stream);
+  }
+  return launch_k2<TA, NA, NB, false, false, TABLE>(args, bps_shift, stream);
+}
 
 template <typename TA>
 int launch_one_trip_two(const StepArgs<float>& args, bool noise, bool group_b_f32, hipStream_t stream, bool& taken) {
   taken = false;
   const int na = args.n_a, nb = args.n_terms - args.n_a;
-  if (nb > 1 || (nb == 1 && !group_b_f32) || ((!g_tune.tile || !g_tune.two_out) && args.rows == nullptr)) return SKR_OK;
+  const bool table = has_table(args.form);  // (a table launch has no other kernel to go to: the tuning switches below do not apply to it)
+  if (nb > 1 || (nb == 1 && !group_b_f32) || ((!g_tune.tile || !g_tune.two_out) && !table)) return SKR_OK;
   // measured (tools/bench_plan.py, 256x16x128x128): with Philox and <= 7 operands the general kernel is 1-2 % faster
   // (193 vs 197 us at 4+1, 239 vs 241 us at 6+1); from 8+1 on, and without noise, this kernel wins (344 vs 365 us at 10+1)
-  if (noise && na + nb <= 7 && g_tune.two_out != 2 && args.rows == nullptr) return SKR_OK;
+  if (noise && na + nb <= 7 && g_tune.two_out != 2 && !table) return SKR_OK;
   int bps_shift = 0;
-  if (!one_trip_ok(args.numel, args.sample_numel, noise, &bps_shift, args.rows != nullptr, args.per_sample != 0)) return SKR_OK;
-#define SKR_GO(A, B)                                                                             \
-  if (na == A && nb == B) {                                                                      \
-    taken = true;                                                                                \
-    if (args.rows != nullptr) return noise ? launch_k2<TA, A, B, true, true, true>(args, bps_shift, stream) : launch_k2<TA, A, B, false, false, true>(args, bps_shift, stream); \
-    if (!noise) {                                                                                \
-      if constexpr (A + B >= 9) { if (nt_stores(A + B)) return launch_k2<TA, A, B, false, false, false, true>(args, bps_shift, stream); } \
-      return launch_k2<TA, A, B, false, false, false>(args, bps_shift, stream);                  \
-    }                                                                                            \
-    return g_tune.pace ? launch_k2<TA, A, B, true, true, false>(args, bps_shift, stream) : launch_k2<TA, A, B, true, false, false>(args, bps_shift, stream); \
-  }
-  SKR_GO(2, 0) SKR_GO(3, 0) SKR_GO(4, 0) SKR_GO(4, 1) SKR_GO(6, 1) SKR_GO(7, 1) SKR_GO(8, 1) SKR_GO(10, 1)
-#undef SKR_GO
-  // UniPC / SPC of order 5-9 (2n+2 operands, +2 with noise tensors) and the previous state: unpaced, and the table form
-  // while the operands fit a device-resident row (tools/trace_plans.py)
-#define SKR_GO(A, B)                                                                             \
-  if (na == A && nb == B) {                                                                      \
-    if (args.rows != nullptr) {                                                                  \
-      if constexpr (A + B <= SKR_ROW_TERMS) { taken = true; return noise ? launch_k2<TA, A, B, true, false, true>(args, bps_shift, stream) : launch_k2<TA, A, B, false, false, true>(args, bps_shift, stream); } \
-      else return SKR_OK;                                                                        \
-    }                                                                                            \
-    taken = true;                                                                                \
-    return noise ? launch_k2<TA, A, B, true, false, false>(args, bps_shift, stream) : launch_k2<TA, A, B, false, false, false>(args, bps_shift, stream); \
-  }
-  SKR_GO(12, 1) SKR_GO(14, 1) SKR_GO(16, 1) SKR_GO(18, 1) SKR_GO(20, 1) SKR_GO(22, 1)
+  if (!one_trip_ok(args.numel, args.sample_numel, noise, args.form, &bps_shift)) return SKR_OK;
+  // the operand counts the samplers emit (tools/trace_plans.py): UniPC / SPC of order n give 2n+2 (+2 with a noise
+  // tensor) 16-bit operands and the previous corrected state in fp32; their first steps have no fp32 operand yet.
+  // From order 5 on (12 + 1 operands and more) nothing was tuned.
+#define SKR_GO(A, B, TUNED) if (na == A && nb == B) { taken = true; return launch_k2_as<TA, A, B, TUNED>(args, noise, bps_shift, stream); }
+  SKR_GO(2, 0, true) SKR_GO(3, 0, true) SKR_GO(4, 0, true) SKR_GO(4, 1, true) SKR_GO(6, 1, true) SKR_GO(7, 1, true) SKR_GO(8, 1, true) SKR_GO(10, 1, true)
+  SKR_GO(12, 1, false) SKR_GO(14, 1, false) SKR_GO(16, 1, false) SKR_GO(18, 1, false) SKR_GO(20, 1, false) SKR_GO(22, 1, false)
 #undef SKR_GO
   return SKR_OK;
 }

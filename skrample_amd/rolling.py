@@ -37,7 +37,7 @@ from typing import Callable, Sequence
 import torch
 
 from . import _hip
-from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepPlanC, StepRowC
+from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepPlanC, StepRowC, upload_rows
 
 Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py
 
@@ -282,9 +282,7 @@ class RollingBatch:
         if len(traced) != steps:
             raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
         request = _Request(self._rows_of(traced), [t for _, _, t in traced])
-        blob = b"".join(bytes(r) for r in request.rows)
-        at = slot * self.max_steps * self.row_bytes
-        self.rows_dev[at : at + len(blob)].copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
+        upload_rows(self.rows_dev, slot * self.max_steps, request.rows)
         self._x[-1][slot].copy_(latents.reshape(self.unit_shape))
         if noisy:
             value = int(seed) & 0xFFFFFFFFFFFFFFFF

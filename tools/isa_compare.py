@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 device code of the step kernels of two source trees, kernel symbol by kernel symbol (no GPU needed).
+
+    python tools/isa_compare.py OLD_TREE NEW_TREE [--jobs N] [--work DIR]
+
+Compiles skr_step.hip, skr_step_fast.hip, skr_step_backward.hip and skr_tape.hip of each tree with the library's own flags
+(`--save-temps -c`), splits the device assembly per kernel the way tests/test_per_sample_isa.py and tests/test_rolling_isa.py do,
+and reports symbols found in one tree only and, for each common symbol, whether its instruction lines (comments stripped, labels
+kept, numbered within their kernel), TotalNumSgprs, NumVgprs, ScratchSize or its `.amdhsa_*` descriptor lines differ, with a unified
+diff per differing symbol.
+A host-side refactor must end in `0 added, 0 removed, 0 differing` for every file.  Exit status 1 when anything differs.
+With --work DIR the assembly is kept there and reused while it is newer than the tree's sources."""
+
+from __future__ import annotations
+
+import argparse
+import difflib
+import glob
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+FILES = ("skr_step.hip", "skr_step_fast.hip", "skr_step_backward.hip", "skr_tape.hip")
+KERNEL = re.compile(r"^(_Z\w+):.*?^\.Lfunc_end\d+:.*?; TotalNumSgprs: (\d+).*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", re.S | re.M)
+
+
+def per_file_flags(tree: str) -> dict:
+    spec = importlib.util.spec_from_file_location("_entry_of_tree", os.path.join(tree, "__graft_entry__.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.PER_FILE_FLAGS
+
+
+def assembly(tree: str, name: str, work: str, hipcc: str) -> str:
+    "device assembly of one source file of one tree"
+    out = os.path.join(work, name + ".s")
+    deps = glob.glob(os.path.join(tree, "skrample_amd", "csrc", "*.h*")) + [os.path.join(tree, "include", "skrample_hip.h")]
+    if os.path.isfile(out) and os.path.getmtime(out) > max(os.path.getmtime(p) for p in deps):
+        return open(out).read()
+    tmp = os.path.join(work, name + ".tmp")
+    shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(tmp)
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *per_file_flags(tree).get(name, [])]
+    subprocess.run([hipcc, *flags, "--save-temps", "-c", "-o", os.path.join(tmp, "x.o"), os.path.join(tree, "skrample_amd", "csrc", name)], check=True, cwd=tmp)
+    asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
+    assert len(asm) == 1, asm
+    os.replace(os.path.join(tmp, asm[0]), out)
+    shutil.rmtree(tmp)
+    return open(out).read()
+
+
+def kernels(text: str) -> dict:
+    "{symbol: lines to compare}: instructions and labels, then the register / scratch figures, then the kernel descriptor"
+    out = {}
+    for m in KERNEL.finditer(text):
+        body = m.group(0).split(".Lfunc_end")[0]
+        # (a block label carries the function's position in the file, `.LBB<function>_<block>`: dropped, so that the order in which
+        #  the kernels are emitted does not count)
+        lines = [re.sub(r"\.LBB\d+_", ".LBB_", raw.split(";")[0].strip()) for raw in body.splitlines()[1:]]
+        code = [l for l in lines if l and (not l.startswith(".") or l.startswith(".LBB"))]
+        figures = [f"; TotalNumSgprs: {m.group(2)}", f"; NumVgprs: {m.group(3)}", f"; ScratchSize: {m.group(4)}"]
+        out[m.group(1)] = code + figures + [l for l in lines if l.startswith(".amdhsa_")]
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--jobs", type=int, default=8, help="compilations at a time (at most 16)")
+    ap.add_argument("--work", default=None, help="directory that keeps the assembly between runs")
+    a = ap.parse_args()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    work = a.work or tempfile.mkdtemp(prefix="isa_compare_")
+    trees = {"old": os.path.abspath(a.old), "new": os.path.abspath(a.new)}
+    for side in trees:
+        os.makedirs(os.path.join(work, side), exist_ok=True)
+    jobs = [(side, name) for name in FILES for side in trees]
+    with ThreadPoolExecutor(max_workers=max(1, min(16, a.jobs))) as pool:
+        texts = dict(zip(jobs, pool.map(lambda j: assembly(trees[j[0]], j[1], os.path.join(work, j[0]), hipcc), jobs)))
+    bad = 0
+    for name in FILES:
+        old, new = kernels(texts["old", name]), kernels(texts["new", name])
+        added, removed = sorted(set(new) - set(old)), sorted(set(old) - set(new))
+        differing = [k for k in sorted(set(old) & set(new)) if old[k] != new[k]]
+        for k in differing:
+            sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(old[k], new[k], "old/" + k, "new/" + k, lineterm=""))
+        for k in added:
+            print(f"only in new: {k}")
+        for k in removed:
+            print(f"only in old: {k}")
+        print(f"{name}: {len(old)} kernels old, {len(new)} new: {len(added)} added, {len(removed)} removed, {len(differing)} differing")
+        bad += len(added) + len(removed) + len(differing)
+    if a.work is None:
+        shutil.rmtree(work)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -196,6 +196,26 @@ int skr_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs
                             void* stream);
 
 /*
+ * Device-resident positions of a rolling batch: computes, on the device, the sample_index_dev a skr_step_launch_rolling reads and the
+ * timestep vector the network reads, from per-slot state the host wrote (and validated) once when the request was admitted, and
+ * moves every running slot on by one step.  One thread per slot, no allocation, no synchronisation, launched on `stream`
+ * (capturable): a tick needs no host-to-device copy.  For every slot b, with p = position_dev[b] and n = length_dev[b]:
+ *   active    0 <= p < n <= max_steps:  sample_index_dev[b] = b * max_steps + p,  timesteps_dev[b] = times_dev[b * max_steps + p]
+ *             (moved as bits),  position_dev[b] = p + 1;
+ *   inactive  anything else (n = 0 is a free slot, p = n a finished one):  sample_index_dev[b] = -1;  timesteps_dev[b] and
+ *             position_dev[b] keep their bytes -- the timestep stays the last one the slot had, and an idle slot can tick for ever
+ *             without its position overflowing.
+ * An index that reaches the step kernel therefore names a row inside the slot's own run of the table (max_steps rows per slot), by
+ * construction: this kernel is the validation the step kernels do not make.
+ * Checked before the launch, without dereferencing a pointer: any NULL pointer is SKR_ERR_NULL; capacity < 1, max_steps < 1 or
+ * capacity * max_steps > INT32_MAX is SKR_ERR_SHAPE.
+ */
+int skr_rolling_advance(int32_t* position_dev /* [capacity] in / out */, const int32_t* length_dev /* [capacity] run length, 0 = free */,
+                        const float* times_dev /* [capacity * max_steps] timestep of every row */,
+                        int32_t* sample_index_dev /* [capacity] out */, float* timesteps_dev /* [capacity] out */, int32_t capacity,
+                        int32_t max_steps, void* stream);
+
+/*
  * Step programs -- a plan the library keeps, launched by handle.  Replaces the per-step host work of a REPLAYED step
  * (skrample/diffusers.py:565-599 redoes the whole step algebra every call; skrample_amd lowers each distinct step once,
  * sampling/program.py): the plan -- coefficients, dtypes, conversion kinds, sample size -- is handed over and validated once,

@@ -30,6 +30,7 @@ EXPORTS = (
     "skr_step_launch_indexed",
     "skr_step_launch_indexed_per_sample",
     "skr_step_launch_rolling",
+    "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_program_create",
     "skr_program_launch",
@@ -315,6 +316,8 @@ def load() -> ctypes.CDLL:
         for table_launch in (lib.skr_step_launch_indexed, lib.skr_step_launch_indexed_per_sample, lib.skr_step_launch_rolling):
             table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
             table_launch.restype = ctypes.c_int
+        lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+        lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
         lib.skr_step_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]

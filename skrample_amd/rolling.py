@@ -11,6 +11,13 @@ whatever else is resident, and leaves when its own run is over -- the slot is fr
     done = batch.step(model(batch.latents, t))       # ONE skr_step_launch_rolling; the slots that just finished
     x = batch.take(slot)
 
+With `device_positions=True` the positions live on the device and a tick needs no host-to-device copy:
+
+    batch.advance()                                  # ONE skr_rolling_advance: index and timesteps computed on the device
+    done = batch.step(model(batch.latents, batch.timesteps))
+    ticks = batch.capture(model)                     # or: the advance and the network of every ring phase in captured graphs
+    done = ticks.tick()                              # one graph replay + one skr_step_launch_rolling
+
 How it works.  The launch structure is the sampler's steady-state (widest) step, found by a dry run of `make_wrapper()` on one
 sample.  Every operand of it has a ROLE (sampling/program.py: this tick's sample / model output, or the k-th last sample, model
 output or state): the batch binds the roles to whole-batch tensors it rotates itself -- a ring of its own latents, a ring of the
@@ -24,9 +31,13 @@ occupant left in the history rings.
 
 Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
 `Random` noise (drawn in the kernel) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
-`skr_step_launch_indexed` covers (UniPC on fp32 latents is refused, as by the captured loops).  Not covered: the Runge-Kutta wrapper
-classes (the kernel form exists, the stage bookkeeping does not), structured noise, graph capture of ticks, autograd, a
-device-resident position vector.
+`skr_step_launch_indexed` covers (UniPC on fp32 latents is refused, as by the captured loops); a device-resident position vector
+(`device_positions=True`: csrc/skr_rolling.hip advances positions the host validated once at `admit()`, so the index the step
+kernel reads is inside the slot's own run by construction) and graph capture of ticks (`capture()`: one graph per ring phase holds
+the advance and the network; the step launch follows each replay eagerly, which is what lets the graphs' static outputs be the
+model-output history, aliased and never copied).  Not covered: the Runge-Kutta wrapper classes (the kernel form exists, the stage
+bookkeeping does not), structured noise, autograd, runs longer than `max_steps`, the step launch inside the graph (its history
+operands are the other graphs' outputs, which exist only once every graph is captured: it would force a snapshot of every model output).
 """
 
 from __future__ import annotations
@@ -82,6 +93,21 @@ def place_row(wide_roles: Sequence[Role], plan: StepPlanC, roles: Sequence[Role]
     return row
 
 
+def advance_reference(position: list, length: list, times: list, max_steps: int) -> tuple[list, list, list]:
+    """What `skr_rolling_advance` computes, in plain Python: (new position, sample index, timestep or None) per slot.  A slot is active
+    iff 0 <= p < n <= max_steps; an inactive slot reads -1 and keeps its position and its timestep (None: the bytes stay)."""
+    new_position, index, timestep = list(position), [], []
+    for b, (p, n) in enumerate(zip(position, length)):
+        if 0 <= p < n <= max_steps:
+            index.append(b * max_steps + p)
+            timestep.append(times[b * max_steps + p])
+            new_position[b] = p + 1
+        else:
+            index.append(-1)
+            timestep.append(None)
+    return new_position, index, timestep
+
+
 class _Request:
     __slots__ = ("rows", "times", "position")
 
@@ -95,12 +121,17 @@ class RollingBatch:
     `make_wrapper()` returns a fresh `SkrampleWrapperScheduler`: its sampler fixes the launch structure every admitted request must
     share.  `max_steps` bounds a request's run length (the device table holds `capacity * max_steps` rows of 328 bytes).
     `alias_history`: True keeps the caller's model outputs as history operands (0 bytes written; overwriting one that is still
-    held raises), False snapshots each one."""
+    held raises), False snapshots each one.  `device_positions`: True keeps every slot's position, run length and timesteps on
+    the device (`advance()` before each `step()`, or `capture()`); the host publishes nothing per tick."""
 
-    def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True):
+    def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True,
+                 device_positions: bool = False):  # fmt: skip
         if capacity < 1:
             raise ValueError("a rolling batch has at least one slot")
         self.capacity, self.max_steps, self.alias_history = int(capacity), int(max_steps), bool(alias_history)
+        self.device_positions = bool(device_positions)
+        if self.device_positions and (self.max_steps < 1 or self.capacity * self.max_steps > 0x7FFFFFFF):
+            raise ValueError(f"device-resident positions index {self.capacity} x {self.max_steps} rows with an int32")
         self.unit_shape = tuple(example.shape[1:])
         self.dtype, self.device = example.dtype, example.device
         self.sample_numel = 1
@@ -136,6 +167,12 @@ class RollingBatch:
         self._times_host = torch.zeros(self.capacity, dtype=torch.float32)
         self.timesteps = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
         self.ticks = 0
+        self._advanced = False  # device positions: advance() ran and step() has not consumed it yet
+        self._captured: "CapturedTicks | None" = None
+        if self.device_positions:
+            self.position_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+            self.length_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+            self.times_dev = torch.zeros(self.capacity * self.max_steps, dtype=torch.float32, device=self.device)
 
     # ---- what a test replaces to run the bookkeeping without a device ---------------------------------------------------
     def _trace(self, wrapper, steps: int, seed: int | None) -> list[tuple[StepPlanC, list[Role], float]]:
@@ -180,6 +217,12 @@ class RollingBatch:
                                              self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0,
                                              _hip.current_stream_ptr(self.device))  # fmt: skip
         _hip.check(status, "skr_step_launch_rolling")
+
+    def _advance(self) -> None:
+        lib = _hip.load()
+        status = lib.skr_rolling_advance(self.position_dev.data_ptr(), self.length_dev.data_ptr(), self.times_dev.data_ptr(), self.index_dev.data_ptr(),
+                                         self.timesteps.data_ptr(), self.capacity, self.max_steps, _hip.current_stream_ptr(self.device))  # fmt: skip
+        _hip.check(status, "skr_rolling_advance")
 
     # ---- structure ---------------------------------------------------------------------------------------------------------
     def _widest(self, traced) -> tuple[StepPlanC, list[Role]]:
@@ -278,6 +321,8 @@ class RollingBatch:
             raise ValueError("a request that draws noise needs a seed")
         if tuple(latents.shape) not in (self.unit_shape, (1, *self.unit_shape)) or latents.dtype != self.dtype:
             raise ValueError(f"latents of shape {tuple(latents.shape)} / {latents.dtype} in a batch of samples {self.unit_shape} / {self.dtype}")
+        if self._advanced:
+            raise ValueError("admit() between advance() and step(): this tick's index is already on the device; admit between ticks")
         traced = self._trace(wrapper, steps, seed if noisy else None)
         if len(traced) != steps:
             raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
@@ -288,6 +333,12 @@ class RollingBatch:
             value = int(seed) & 0xFFFFFFFFFFFFFFFF
             self.seeds_dev[slot : slot + 1].copy_(torch.tensor([value - (1 << 64) if value >= (1 << 63) else value], dtype=torch.int64))
         self._requests[slot] = request
+        if self.device_positions:
+            # stream-ordered, behind the rows: the slot's timesteps, then its run length and position (the next advance reads them)
+            self.times_dev[slot * self.max_steps : slot * self.max_steps + steps].copy_(torch.tensor(request.times, dtype=torch.float32))
+            self.length_dev[slot : slot + 1].fill_(steps)
+            self.position_dev[slot : slot + 1].zero_()
+            return
         self._times_host[slot] = request.times[0]
         self.timesteps.copy_(self._times_host)
 
@@ -298,6 +349,8 @@ class RollingBatch:
             raise ValueError(f"slot {slot} holds no request" if self._requests[slot] is None else f"slot {slot} has not finished: {self._requests[slot].position} of {len(self._requests[slot].rows)} steps done")
         self._finished.discard(slot)
         self._requests[slot] = None
+        if self.device_positions:
+            self.length_dev[slot : slot + 1].zero_()  # free: inactive whatever its position holds
         return self._results.pop(slot)
 
     # ---- one tick --------------------------------------------------------------------------------------------------------------
@@ -327,9 +380,13 @@ class RollingBatch:
 
     def step(self, model_output: torch.Tensor) -> list[int]:
         "advance every active slot by one step of its own run with ONE launch; returns the slots that finished with this tick"
+        if self._captured is not None:
+            raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
         index = self.index_vector()
         if all(i < 0 for i in index):
             raise ValueError("no active slot: admit() a request before step()")
+        if self.device_positions and not self._advanced:
+            raise ValueError("device-resident positions: advance() publishes this tick's index and timesteps; call it before the network and step()")
         if tuple(model_output.shape) != tuple(self._x[-1].shape) or model_output.dtype != self.dtype or model_output.device != self.device or not model_output.is_contiguous():
             raise ValueError(f"the model output of a tick is a contiguous {tuple(self._x[-1].shape)} {self.dtype} tensor on {self.device}")
         if self.alias_history:
@@ -337,7 +394,8 @@ class RollingBatch:
         elif self.keep:
             model_output = model_output.clone()
         operands = [self._bind(role, model_output) for role in self.roles]
-        self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
+        if not self.device_positions:
+            self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
         arr = (ctypes.c_void_p * max(len(operands), 1))(*[t.data_ptr() for t in operands])
         # the oldest ring entries take this tick's results: no operand of the structure reaches that far back
         new_x = self._x.pop(0)
@@ -357,6 +415,7 @@ class RollingBatch:
                 self._stamps.append((model_output, model_output.data_ptr(), model_output._version))
                 del self._stamps[: max(len(self._stamps) - self.keep, 0)]
         self.ticks += 1
+        self._advanced = False
         done = []
         for b, i in enumerate(index):
             if i < 0:
@@ -367,8 +426,136 @@ class RollingBatch:
                 done.append(b)
                 self._finished.add(b)
                 self._results[b] = new_x[b].clone()
-            else:
+            elif not self.device_positions:
                 self._times_host[b] = req.times[req.position]
         # (the slices of free slots are not touched, by the kernel or here: they hold what an older tick left there)
-        self.timesteps.copy_(self._times_host)
+        if not self.device_positions:
+            self.timesteps.copy_(self._times_host)
+        return done
+
+    # ---- device-resident positions -------------------------------------------------------------------------------------------
+    def advance(self) -> None:
+        """Device-resident positions: ONE skr_rolling_advance computes this tick's `index_dev` and `timesteps` from the slots' device
+        state and moves the running slots on.  Call it once per tick, before the network reads `timesteps`; `step()` consumes it."""
+        if not self.device_positions:
+            raise ValueError("advance() needs device_positions=True: this batch publishes its index from the host in step()")
+        if self._captured is not None:
+            raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
+        if self._advanced:
+            raise ValueError("advance() ran for this tick already: step() comes next")
+        if all(i < 0 for i in self.index_vector()):
+            raise ValueError("no active slot: admit() a request before advance()")
+        self._advance()
+        self._advanced = True
+
+    def capture(self, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], warmup: int = 2) -> "CapturedTicks":
+        "graphs of the advance and the network for every ring phase: see CapturedTicks"
+        if not self.device_positions:
+            raise ValueError("capture() needs device_positions=True: a tick that copies its index from the host cannot be captured")
+        if self._captured is not None:
+            raise ValueError("this batch's ticks are captured already")
+        if any(r is not None for r in self._requests) or self._advanced:
+            raise ValueError("capture() with a resident request: take() every result first (the warm-up runs the network on the rings)")
+        self._captured = CapturedTicks(self, model, warmup)
+        return self._captured
+
+
+class CapturedTicks:
+    """The ticks of a `RollingBatch(device_positions=True)` with the network in captured graphs.
+
+    The latents and states rotate through rings of P = keep + 2 tensors, so a tick has one of P operand bindings: graph p holds, on
+    one stream, the advance launch and `out_p = model(latents of phase p, timesteps)`.  `tick()` replays graph `ticks mod P` and
+    follows it with one eager skr_step_launch_rolling whose operand array was built at capture time.  The step stays outside the
+    graphs because its history operand ("po", k) is the static output of graph (p + k) mod P, which exists only once every graph
+    is captured -- and that is why no model output is ever copied: the P static outputs ARE the model-output ring (it needs
+    keep + 1 of them), they belong to the graphs, and nobody else can overwrite them (no alias guard).  `admit()` / `take()` of
+    the batch work between ticks."""
+
+    def __init__(self, batch: RollingBatch, model, warmup: int):
+        self.batch = batch
+        dev = batch.device
+        self.phases = P = len(batch._x)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(int(warmup), 1)):
+                model(batch._x[-1], batch.timesteps)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        # phase p reads the ring as it stands after p rotations; P rotations bring it back
+        x_ring, state_ring = list(batch._x), list(batch._state)
+        latents = [x_ring[(P - 1 + p) % P] for p in range(P)]
+        self.graphs: list[torch.cuda.CUDAGraph] = []
+        self.outputs: list[torch.Tensor] = []  # referenced here so that the graphs' pool keeps them alive
+        pool = torch.cuda.graph_pool_handle()
+        for p in range(P):
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, pool=pool):
+                batch._advance()
+                out = model(latents[p], batch.timesteps)
+            if tuple(out.shape) != tuple(latents[p].shape) or out.dtype != batch.dtype or out.device != dev or not out.is_contiguous():
+                raise ValueError(f"the model output of a tick is a contiguous {tuple(latents[p].shape)} {batch.dtype} tensor on {dev}")
+            self.graphs.append(graph)
+            self.outputs.append(out)
+        self._launches = []  # per phase: (operand pointers, out0, out1, the tensor that holds the tick's new latents)
+        for p in range(P):
+            ptrs = []
+            for role in batch.roles:
+                kind = role[0]
+                if kind == "x":
+                    t = latents[p]
+                elif kind == "o":
+                    t = self.outputs[p]
+                elif kind == "none":
+                    t = batch._blank
+                elif kind == "pi":  # the latents of -k ticks ago
+                    t = x_ring[(P - 1 + p + role[1]) % P]
+                elif kind == "px":
+                    t = state_ring[(p + role[1]) % P]
+                elif kind == "po":  # the static output of the graph replayed -k ticks ago
+                    t = self.outputs[(p + role[1]) % P]
+                else:
+                    raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (structured noise tensors are not covered)")
+                ptrs.append(t.data_ptr())
+            arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+            new_x = x_ring[p]
+            if batch.two_outputs:
+                self._launches.append((arr, state_ring[p], new_x, new_x))
+            elif batch.plan.out0_dtype != _hip.NONE:
+                self._launches.append((arr, new_x, None, new_x))
+            else:
+                self._launches.append((arr, None, new_x, new_x))
+        self.ticks = 0
+        self.replays = [0] * P
+
+    def tick(self) -> list[int]:
+        "one graph replay (advance + network) and ONE step launch; returns the slots that finished with this tick"
+        batch = self.batch
+        live = []
+        for b, req in enumerate(batch._requests):
+            if req is None or b in batch._finished:
+                continue
+            if not 0 <= req.position < len(req.rows) <= batch.max_steps:  # (as index_vector(): before anything is enqueued)
+                raise ValueError(f"slot {b} is at position {req.position} of a run of {len(req.rows)} steps")
+            live.append((b, req))
+        if not live:
+            raise ValueError("no active slot: admit() a request before tick()")
+        phase = self.ticks % self.phases
+        arr, out0, out1, new_x = self._launches[phase]
+        self.graphs[phase].replay()
+        batch._launch(arr, out0, out1)
+        # the batch's rings follow, so that `latents` is where admit() must write
+        batch._x.append(batch._x.pop(0))
+        if batch.two_outputs:
+            batch._state.append(batch._state.pop(0))
+        self.replays[phase] += 1
+        self.ticks += 1
+        batch.ticks += 1
+        done = []
+        for b, req in live:
+            req.position += 1
+            if req.position == len(req.rows):
+                done.append(b)
+                batch._finished.add(b)
+                batch._results[b] = new_x[b].clone()
         return done

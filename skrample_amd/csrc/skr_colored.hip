@@ -20,8 +20,10 @@
 #include <stdint.h>
 #include <atomic>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "skr_device.h"
+#include "skr_launch.h"
 #include "../../include/skrample_hip.h"
 #include "skr_philox.h"
 #include "skr_pack.h"
@@ -31,30 +33,30 @@
 namespace skr {
 
 
-struct ColoredArgs {
-  float2* spec;         // [batch][d1][d2][d3h]
-  float* real_out;      // [batch][d1][d2][d3] fp32 scratch (pass E)
-  double* partials;     // [2][batch][n_slots][2]  (0: white from pass A, 1: coloured from pass E)
-  const uint64_t* seeds;
-  uint64_t stream;
-  int64_t batch;
-  int32_t d1, d2, d3, d3h;   // d1 = 1 for 2-D
-  int32_t n_slots;           // partial slots in use per sample (white half; coloured half of the unfused path)
-  int32_t n_slots_c;         // coloured-half slots written by the Parseval reduction of the fused 3-D path
-  int32_t has_energy;
-  double energy;
-  void* out;                 // fused paths write the result dtype directly
-  float exponent_half_neg;   // -exponent / 2
-  float eps_clip;
-  float inv_rmax;
-  int32_t raw;               // MODE 1 of the plane kernels: plain inverse transform (no 1/N, no rescale factor) -- colored_planes
-  const float* factors;      // colored_inverse128: [batch] per-sample rescale factors (colored_factors), or null
-  uint32_t* ticket;          // colored_inverse128: the next unclaimed plane, or null = planes dealt out statically
-  uint32_t first_ticket;     // its starting value (2 x the inverse kernel's grid: every block's first two planes are fixed)
-  uint32_t* done_count;      // [batch] blocks of the outer-axis kernel that have stored their Parseval slot; the last one of a sample computes factors[smp]
-  float* factors_out;        // where (null: the factors come from the colored_factors launch)
+struct ColoredArgs {  // (the defaults: a launch without radial weights, rescaling or colored_inverse128 bookkeeping; the host sets what differs)
+  float2* spec = nullptr;         // [batch][d1][d2][d3h]
+  float* real_out = nullptr;      // [batch][d1][d2][d3] fp32 scratch (pass E)
+  double* partials = nullptr;     // [2][batch][n_slots][2]  (0: white from pass A, 1: coloured from pass E)
+  const uint64_t* seeds = nullptr;
+  uint64_t stream = 0;
+  int64_t batch = 0;
+  int32_t d1 = 1, d2 = 0, d3 = 0, d3h = 0;   // d1 = 1 for 2-D
+  int32_t n_slots = 0;           // partial slots in use per sample (white half; coloured half of the unfused path)
+  int32_t n_slots_c = 0;         // coloured-half slots written by the Parseval reduction of the fused 3-D path
+  int32_t has_energy = 0;
+  double energy = 0.0;
+  void* out = nullptr;           // fused paths write the result dtype directly
+  float exponent_half_neg = 0.f; // -exponent / 2
+  float eps_clip = 1.f;
+  float inv_rmax = 1.f;
+  int32_t raw = 0;               // MODE 1 of the plane kernels: plain inverse transform (no 1/N, no rescale factor) -- colored_planes
+  const float* factors = nullptr;  // colored_inverse128: [batch] per-sample rescale factors (colored_factors), or null
+  uint32_t* ticket = nullptr;    // colored_inverse128: the next unclaimed plane, or null = planes dealt out statically
+  uint32_t first_ticket = 0;     // its starting value (2 x the inverse kernel's grid: every block's first two planes are fixed)
+  uint32_t* done_count = nullptr;  // [batch] blocks of the outer-axis kernel that have stored their Parseval slot; the last one of a sample computes factors[smp]
+  float* factors_out = nullptr;  // where (null: the factors come from the colored_factors launch)
 #ifdef SKR_COLORED_TRACE
-  uint64_t* trace;           // tools/tune/tune_colored.hip only: [block][16] phase stamps of the plane kernels (s_memrealtime, 10 ns)
+  uint64_t* trace = nullptr;     // tools/tune/tune_colored.hip only: [block][16] phase stamps of the plane kernels (s_memrealtime, 10 ns)
 #endif
 };
 
@@ -1594,15 +1596,29 @@ __global__ __launch_bounds__(256) void colored_finish(T* out, const ColoredArgs 
 
 }  // namespace skr
 
-// points per block tile; default 4096 (32 KiB of LDS).  SKR_FFT_TILE overrides it for tuning runs.
+// ---- host side --------------------------------------------------------------------------------------------------------------
+// Environment switches of the colored launchers: measurement and test switches, production sets none of them.
+//   Read on every call (tests flip them inside one process):
+//     SKR_FFT_NO_PLANES           colored_planes takes no shape: skr_noise_colored_any transforms every plane itself
+//     SKR_FFT_NO_MIXED            no mixed-radix planes (colored_plane_mixed), in skr_noise_colored and in colored_planes
+//     SKR_FFT_NO_FUSE             power-of-two units take the separate passes even where a plane fits the LDS
+//     SKR_FFT_NO_CONST_SIDE       square 96 / 160 / 192 planes on the run-time-geometry form of colored_plane_mixed
+//     SKR_COLORED_NO_MID          2- and 4-channel units of the separate passes without colored_mid_axes
+//     SKR_COLORED_MID_LOGT        log2 of the tile width of colored_mid_axes
+//   Read once per process:
+//     SKR_FFT_TILE                points per block tile of the separate passes: a power of two, 256 ... 16384 (default 4096, 32 KiB of LDS)
+//     SKR_COLORED_OLD_INVERSE     128 x 128 inverse planes on colored_plane<1>, not on the persistent colored_inverse128
+//     SKR_COLORED_INV_BLOCKS      resident blocks per CU of colored_inverse128: 1 ... 8 (default 2)
+//     SKR_FFT_ODD_LIMIT           colored_planes: largest sum of the odd factors of the two sides of a mixed plane (default: none)
+//     SKR_COLORED_GROUP_MB        skr_noise_colored: draw the batch in groups whose spectrum is at most this many MiB (default: one group)
+//     SKR_COLORED_INV_STATIC      colored_inverse128 deals its planes out statically, without the device ticket
+//     SKR_COLORED_FACTORS_KERNEL  rescale factors by a colored_factors launch, not by the last block of the outer-axis kernel
+static bool env_flag(const char* name) { return getenv(name) != nullptr; }
+static int64_t env_int(const char* name, int64_t unset) { const char* e = getenv(name); return e ? (int64_t)atoll(e) : unset; }
+
 static int fft_tile_points() {
-  static int cached = 0;
-  if (!cached) {
-    const char* e = getenv("SKR_FFT_TILE");
-    int v = e ? atoi(e) : 0;
-    cached = (v >= 256 && v <= 16384 && !(v & (v - 1))) ? v : skr::FFT_MAX_TILE;
-  }
-  return cached;
+  static const int tile = [] { const int64_t v = env_int("SKR_FFT_TILE", 0); return v >= 256 && v <= 16384 && !(v & (v - 1)) ? (int)v : skr::FFT_MAX_TILE; }();
+  return tile;
 }
 
 static int ilog2_exact(int64_t v) {
@@ -1612,52 +1628,50 @@ static int ilog2_exact(int64_t v) {
   return l;
 }
 
-#define SKR_CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return SKR_ERR_LAUNCH; } while (0)
-// kernels that need more than the default 48 KiB of dynamic LDS must opt in
-#define SKR_ALLOW_LDS(kernel, bytes) do { if ((bytes) > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)) != hipSuccess) return SKR_ERR_UNSUPPORTED; } while (0)
-
 namespace skr {
 
-// persistent inverse kernel of 128 x 128 planes (colored_inverse128); -1: not taken (the caller launches colored_plane<1, ...>)
-// grid of the persistent inverse kernel (two resident blocks per CU), 0 when the kernel does not apply
-static int64_t inverse128_blocks(int32_t d2, int32_t d3, int32_t out_dtype, int64_t n_planes) {
-  static const bool off = getenv("SKR_COLORED_OLD_INVERSE") != nullptr;
-  if (off || d2 != 128 || d3 != 128 || n_planes < 1 || (out_dtype != SKR_BF16 && out_dtype != SKR_F16 && out_dtype != SKR_F32)) return 0;
-  static int cus[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 0; }
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) { (void)hipGetLastError(); n = 256; }
-    cus[dev] = n;
+// ---- kernel forms: which instantiation a plane gets ----------------------------------------------------------------------------
+// colored_plane<MODE, T, CH, CW>: (CH, CW) = log2 of the sides at compile time for 128 x 128 and 64 x 64 planes, (0, 0) = at run time (double: only that)
+using PlaneKernel = void (*)(const ColoredArgs, int, int);
+template <int MODE, typename T>
+static PlaneKernel plane_kernel(int l2, int l3) {
+  if constexpr (!std::is_same_v<T, double>) {
+    if (l2 == 7 && l3 == 7) return colored_plane<MODE, T, 7, 7>;
+    if (l2 == 6 && l3 == 6) return colored_plane<MODE, T, 6, 6>;
   }
-  static const int per_cu = [] { const char* e = getenv("SKR_COLORED_INV_BLOCKS"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 8 ? v : 2; }();
-  const int64_t blocks = (int64_t)per_cu * cus[dev];
-  return blocks > n_planes ? n_planes : blocks;
+  return colored_plane<MODE, T, 0, 0>;
 }
 
-// skr_stat("colored_inv128_launches" / "colored_inv128_ticketed"): launches of colored_inverse128, and those of them in which at least one
-// plane was dealt from the device ticket (every block's first two planes are fixed)
-std::atomic<int64_t> g_inv128_launches{0}, g_inv128_ticketed{0};
+// colored_plane_mixed<MODE, T, THREADS, SIDE>: SIDE = the side of a square plane at compile time (96 on 512 threads, 160 and 192 on 1024), 0 = geometry
+// at run time.  const_side: the side of a square plane that may take such a form, else 0.  They serve elements of up to 4 bytes; MODE 2 has none at 192.
+using MixedKernel = void (*)(const ColoredArgs, const MixedGeom);
+template <int MODE, typename T>
+static MixedKernel mixed_kernel(int threads, int const_side) {
+  if constexpr (sizeof(T) <= 4) {
+    if (const_side == 96 && threads == 512) return colored_plane_mixed<MODE, T, 512, 96>;
+    if (const_side == 160 && threads == 1024) return colored_plane_mixed<MODE, T, 1024, 160>;
+    if constexpr (MODE != 2) if (const_side == 192 && threads == 1024) return colored_plane_mixed<MODE, T, 1024, 192>;
+  }
+  return threads == 512 ? MixedKernel(colored_plane_mixed<MODE, T, 512>) : MixedKernel(colored_plane_mixed<MODE, T, 1024>);
+}
+// Never launched: the launch macros that mixed_kernel replaces named the SIDE forms for double too, behind a run-time test that was never true.  They stay
+// instantiated so that the code object keeps exactly the kernels it had; deleting these five lines deletes the five kernels and nothing else.
+template __global__ void colored_plane_mixed<1, double, 512, 96>(const ColoredArgs, const MixedGeom);
+template __global__ void colored_plane_mixed<1, double, 1024, 160>(const ColoredArgs, const MixedGeom);
+template __global__ void colored_plane_mixed<1, double, 1024, 192>(const ColoredArgs, const MixedGeom);
+template __global__ void colored_plane_mixed<2, double, 512, 96>(const ColoredArgs, const MixedGeom);
+template __global__ void colored_plane_mixed<2, double, 1024, 160>(const ColoredArgs, const MixedGeom);
 
-static int launch_inverse128(ColoredArgs a, int32_t out_dtype, int64_t n_planes, float* factors /* [batch] workspace, unused when a.raw */, hipStream_t s) {
-  if (a.d2 != 128 || a.d3 != 128 || n_planes < 1 || (!a.raw && factors == nullptr) || (out_dtype != SKR_BF16 && out_dtype != SKR_F16 && out_dtype != SKR_F32)) return -1;
-  const int64_t blocks = inverse128_blocks(a.d2, a.d3, out_dtype, n_planes);
-  if (blocks < 1) return -1;
-  ++g_inv128_launches;
-  if (a.ticket != nullptr && n_planes > 2 * blocks) ++g_inv128_ticketed;
-  const size_t lds = sizeof(float2) * (64 * 129 + 128);
-  a.factors = factors;
-#ifdef SKR_COLORED_TRACE
-  if (a.trace) a.trace += 65536;  // behind the forward kernel's stamps (4096 blocks x 16 words)
-#endif
-  if (!a.raw && a.factors_out == nullptr) hipLaunchKernelGGL(colored_factors, dim3((unsigned)a.batch), dim3(64), 0, s, a, factors, a.first_ticket);  // (not fused: SKR_COLORED_FACTORS_KERNEL)
-#define SKR_INV128(T) do { SKR_ALLOW_LDS((colored_inverse128<T>), lds); hipLaunchKernelGGL((colored_inverse128<T>), dim3((unsigned)blocks), dim3(512), lds, s, a, n_planes); } while (0)
-  if (out_dtype == SKR_BF16) SKR_INV128(__bf16);
-  else if (out_dtype == SKR_F16) SKR_INV128(_Float16);
-  else SKR_INV128(float);
-#undef SKR_INV128
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+// ---- plane geometry ---------------------------------------------------------------------------------------------------------------
+// A power-of-two d2 x d3 plane on colored_plane.  l2, l3: log2 of the sides (-1: not a power of two); lds: twiddles of both axes (full circle) + the tile;
+// pairs_fit: the LDS is within 150 KiB, and the row pairs of the real plane and of its half spectrum fit one round of PLANE_ITEMS register-staged items
+// per thread; half_plane_fits: the whole half spectrum fits two rounds
+struct PlaneFit { int l2, l3; size_t lds; bool pairs_fit, half_plane_fits; };
+static PlaneFit plane_fit(int32_t d2, int32_t d3) {
+  const int64_t d3h = d3 / 2 + 1, pairs = d2 / 2, items = (int64_t)PLANE_THREADS * PLANE_ITEMS;
+  const int64_t tile_points = pairs * (d3 + 1ll) > d3h * (d2 + 1ll) ? pairs * (d3 + 1ll) : d3h * (d2 + 1ll);
+  const size_t lds = sizeof(float2) * ((size_t)d3 + d2 + (size_t)tile_points);
+  return {ilog2_exact(d2), ilog2_exact(d3), lds, lds <= 150 * 1024 && pairs * d3 <= items && pairs * d3h <= items, (int64_t)d2 * d3h <= 2 * items};
 }
 
 static bool mixed_factor_axis(int d, MixedAxis& x) {
@@ -1675,11 +1689,13 @@ static bool mixed_factor_axis(int d, MixedAxis& x) {
 
 // geometry, LDS bytes and block size of colored_plane_mixed for a d2 x d3 plane (two_d: the plane is a whole 2-D unit, whose
 // half plane is staged in registers once more); false if the plane is not covered
-static bool mixed_plane_geometry(int d2, int d3, bool two_d, MixedGeom& mg, size_t& lds, int& threads) {
+struct MixedPlan { MixedGeom geom; size_t lds = 0; int threads = 0; };
+static bool mixed_plane_geometry(int d2, int d3, bool two_d, MixedPlan& m) {
+  MixedGeom& mg = m.geom;
   if (d2 % 2 != 0 || d3 % 4 != 0 || !mixed_factor_axis(d2, mg.h) || !mixed_factor_axis(d3, mg.w)) return false;
   const int64_t pairs = d2 / 2, wh = d3 / 2 + 1;
   const size_t tile = (size_t)(pairs * mg.w.pitch > wh * mg.h.pitch ? pairs * mg.w.pitch : wh * mg.h.pitch);
-  lds = sizeof(float2) * ((size_t)d3 + d2 + mg.w.m / 2 + mg.h.m / 2 + tile);
+  m.lds = sizeof(float2) * ((size_t)d3 + d2 + mg.w.m / 2 + mg.h.m / 2 + tile);
   mg.magic_wh = (uint32_t)((0x100000000ull + (uint32_t)wh - 1) / (uint32_t)wh);
   // 512-thread blocks while every register-staged transpose fits 18 items per thread, else 1024 (3-D units only need the
   // row-pair transposes to fit; 2-D units also the full half plane)
@@ -1687,8 +1703,68 @@ static bool mixed_plane_geometry(int d2, int d3, bool two_d, MixedGeom& mg, size
     return pairs * d3 <= (int64_t)t * PLANE_ITEMS && pairs * wh <= (int64_t)t * PLANE_ITEMS && (int64_t)d2 * wh <= 2ll * t * PLANE_ITEMS &&
            (!two_d || (int64_t)d2 * wh <= (int64_t)t * PLANE_ITEMS);
   };
-  threads = fits(512) ? 512 : (fits(1024) ? 1024 : 0);
-  return lds <= 156 * 1024 && threads != 0;
+  m.threads = fits(512) ? 512 : (fits(1024) ? 1024 : 0);
+  return m.lds <= 156 * 1024 && m.threads != 0;
+}
+
+// ---- launches ---------------------------------------------------------------------------------------------------------------------
+// one block per plane: grid (a.d1, a.batch)
+template <int MODE, typename T>
+static int launch_plane(const ColoredArgs& a, const PlaneFit& fit, hipStream_t s) {
+  return launch_lds(plane_kernel<MODE, T>(fit.l2, fit.l3), dim3((unsigned)a.d1, (unsigned)a.batch), dim3(PLANE_THREADS), fit.lds, s, a, fit.l2, fit.l3);
+}
+template <int MODE, typename T>
+static int launch_mixed(const ColoredArgs& a, const MixedPlan& m, int const_side, hipStream_t s) {
+  return launch_lds(mixed_kernel<MODE, T>(m.threads, const_side), dim3((unsigned)a.d1, (unsigned)a.batch), dim3((unsigned)m.threads), m.lds, s, a, m.geom);
+}
+
+// Grid of the persistent inverse kernel of 128 x 128 planes (colored_inverse128: two resident blocks per CU); 0 when the kernel
+// does not apply and the caller launches colored_plane<1, ...>.  Every precondition of launch_inverse128 is tested here.
+static int64_t inverse128_blocks(int32_t d2, int32_t d3, int32_t out_dtype, int64_t n_planes) {
+  static const bool off = env_flag("SKR_COLORED_OLD_INVERSE");
+  if (off || d2 != 128 || d3 != 128 || n_planes < 1 || (out_dtype != SKR_BF16 && out_dtype != SKR_F16 && out_dtype != SKR_F32)) return 0;
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 0; }
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) { (void)hipGetLastError(); n = 256; }
+    cus[dev] = n;
+  }
+  static const int per_cu = [] { const int64_t v = env_int("SKR_COLORED_INV_BLOCKS", 2); return v >= 1 && v <= 8 ? (int)v : 2; }();
+  const int64_t blocks = (int64_t)per_cu * cus[dev];
+  return blocks > n_planes ? n_planes : blocks;
+}
+
+// skr_stat("colored_inv128_launches" / "colored_inv128_ticketed"): launches of colored_inverse128, and those of them in which at least one
+// plane was dealt from the device ticket (every block's first two planes are fixed)
+std::atomic<int64_t> g_inv128_launches{0}, g_inv128_ticketed{0};
+
+// blocks: inverse128_blocks(...) > 0; factors: [batch] workspace, unused when a.raw
+static int launch_inverse128(ColoredArgs a, int32_t out_dtype, int64_t n_planes, int64_t blocks, float* factors, hipStream_t s) {
+  ++g_inv128_launches;
+  if (a.ticket != nullptr && n_planes > 2 * blocks) ++g_inv128_ticketed;
+  a.factors = factors;
+#ifdef SKR_COLORED_TRACE
+  if (a.trace) a.trace += 65536;  // behind the forward kernel's stamps (4096 blocks x 16 words)
+#endif
+  if (!a.raw && a.factors_out == nullptr)  // (not fused: SKR_COLORED_FACTORS_KERNEL)
+    if (const int rc = launch_lds(colored_factors, dim3((unsigned)a.batch), dim3(64), 0, s, a, factors, a.first_ticket); rc != SKR_OK) return rc;
+  const size_t lds = sizeof(float2) * (64 * 129 + 128);
+  return with_out_type<false>(out_dtype, [&](auto t) {
+    return launch_lds(colored_inverse128<typename decltype(t)::type>, dim3((unsigned)blocks), dim3(512), lds, s, a, n_planes);
+  });
+}
+
+// Axis 1 of a 3-D unit (length d1 = 2, 4, 8 or 16; stride d2*d3h) in registers: forward, radial weights, inverse in one pass.
+// With a.n_slots_c > 0 every block also stores the Parseval partials of the weighted spectrum, one slot per block: a.n_slots_c
+// becomes the number of blocks per sample.
+static int launch_outer_axis_regs(ColoredArgs& a, hipStream_t s) {
+  const int64_t cols = (int64_t)a.d2 * a.d3h;
+  int64_t bx = (cols + 255) / 256; if (bx > 4096) bx = 4096;
+  if (a.n_slots_c > 0) { if (bx > a.n_slots_c) bx = a.n_slots_c; a.n_slots_c = (int32_t)bx; }
+  const auto kernel = a.d1 == 2 ? colored_outer_axis_regs<2> : (a.d1 == 4 ? colored_outer_axis_regs<4> : (a.d1 == 8 ? colored_outer_axis_regs<8> : colored_outer_axis_regs<16>));
+  return launch_lds(kernel, dim3((unsigned)bx, (unsigned)a.batch), dim3(256), 0, s, a);
 }
 
 // Independent d2 x d3 planes on the LDS plane kernels, for skr_colored_any.hip (3-D units whose leading axis is a direct DFT there:
@@ -1698,62 +1774,209 @@ static bool mixed_plane_geometry(int d2, int d3, bool two_d, MixedGeom& mg, size
 // to real_out[b][p][d2][d3].  SKR_ERR_UNSUPPORTED for a plane shape the kernels do not cover.
 int colored_planes(int mode, float2* spec, double* plane_partials, float* real_out, const uint64_t* seeds, uint64_t stream_id,
                    int64_t batch, int64_t planes, int32_t d2, int32_t d3, hipStream_t s) {
-  if (batch <= 0 || planes <= 0 || batch > 65535 || planes > 0x7fffffffll || d2 < 2 || d3 < 4 || getenv("SKR_FFT_NO_PLANES") != nullptr) return SKR_ERR_UNSUPPORTED;
+  if (batch <= 0 || planes <= 0 || batch > 65535 || planes > 0x7fffffffll || d2 < 2 || d3 < 4 || env_flag("SKR_FFT_NO_PLANES")) return SKR_ERR_UNSUPPORTED;
   ColoredArgs a;
-  a.spec = spec; a.real_out = nullptr; a.partials = plane_partials; a.seeds = seeds; a.stream = stream_id;
+  a.spec = spec; a.partials = plane_partials; a.seeds = seeds; a.stream = stream_id;
   a.batch = batch; a.d1 = (int32_t)planes; a.d2 = d2; a.d3 = d3; a.d3h = d3 / 2 + 1;
-  a.n_slots = (int32_t)planes; a.n_slots_c = 0; a.has_energy = 0; a.energy = 0.0; a.out = real_out;
-  a.exponent_half_neg = 0.f; a.eps_clip = 1.f; a.inv_rmax = 1.f; a.raw = 1; a.factors = nullptr; a.ticket = nullptr; a.first_ticket = 0; a.done_count = nullptr; a.factors_out = nullptr;
-#ifdef SKR_COLORED_TRACE
-  a.trace = nullptr;
-#endif
-  const dim3 grid((unsigned)planes, (unsigned)batch);
-  const int l3 = ilog2_exact(d3), l2 = ilog2_exact(d2);
-  const int64_t d3h = a.d3h;
-  const size_t tile_points = (size_t)(d2 / 2) * (d3 + 1) > (size_t)d3h * (d2 + 1) ? (size_t)(d2 / 2) * (d3 + 1) : (size_t)d3h * (d2 + 1);
-  const size_t lds_plane = sizeof(float2) * ((size_t)d3 + d2 + tile_points);  // twiddles of both axes (full circle) + the tile
-  const bool pow2_plane = l3 >= 2 && l2 >= 1 && lds_plane <= 150 * 1024 && (int64_t)(d2 / 2) * d3 <= PLANE_THREADS * PLANE_ITEMS &&
-                          (int64_t)(d2 / 2) * d3h <= PLANE_THREADS * PLANE_ITEMS && (int64_t)d2 * d3h <= 2ll * PLANE_THREADS * PLANE_ITEMS;
-  if (pow2_plane) {
-#define SKR_PLANES_T(MODE, CH, CW) do { SKR_ALLOW_LDS((colored_plane<MODE, float, CH, CW>), lds_plane); hipLaunchKernelGGL((colored_plane<MODE, float, CH, CW>), grid, dim3(PLANE_THREADS), lds_plane, s, a, l2, l3); } while (0)
-#define SKR_PLANES(MODE)                                \
-    if (l2 == 7 && l3 == 7) SKR_PLANES_T(MODE, 7, 7);   \
-    else if (l2 == 6 && l3 == 6) SKR_PLANES_T(MODE, 6, 6); \
-    else SKR_PLANES_T(MODE, 0, 0)
-    if (mode == 0) { SKR_PLANES(0); }
-    else {
-      const int rc = launch_inverse128(a, SKR_F32, batch * planes, nullptr, s);
-      if (rc >= 0) return rc;
-      SKR_PLANES(1);
-    }
-#undef SKR_PLANES
-#undef SKR_PLANES_T
-    SKR_CHECK_LAUNCH();
-    return SKR_OK;
+  a.n_slots = (int32_t)planes; a.out = real_out; a.raw = 1;
+  const PlaneFit fit = plane_fit(d2, d3);
+  if (fit.l3 >= 2 && fit.l2 >= 1 && fit.pairs_fit && fit.half_plane_fits) {
+    if (mode == 0) return launch_plane<0, float>(a, fit, s);
+    const int64_t inv_blocks = inverse128_blocks(d2, d3, SKR_F32, batch * planes);
+    if (inv_blocks > 0) return launch_inverse128(a, SKR_F32, batch * planes, inv_blocks, nullptr, s);
+    return launch_plane<1, float>(a, fit, s);
   }
-  MixedGeom mg;
-  size_t lds_mixed = 0;
-  int threads = 0;
   // (measurement switch.  Rounds 3-4 stopped at odd parts summing to 10: beyond that hipFFT's 3-D plan was faster than planes here + a direct
   //  outer-axis pass.  The N-D transform is the library's own since (skr_fft_own.hip), and every plane this kernel can hold beats it:
   //  5 x 60 x 104 100 against 196 us, 12 x 168 x 96 115 against 245, 16 x 13 x 60 x 104 322 against 542.)
-  static const int odd_limit = [] { const char* e = getenv("SKR_FFT_ODD_LIMIT"); return e ? atoi(e) : 1 << 20; }();
-  if (getenv("SKR_FFT_NO_MIXED") != nullptr || !mixed_plane_geometry(d2, d3, false, mg, lds_mixed, threads) || mg.h.r + mg.w.r > odd_limit) return SKR_ERR_UNSUPPORTED;
-#define SKR_PLANES_M(MODE) do {                                                                                                                  \
-    if (threads == 512) { SKR_ALLOW_LDS((colored_plane_mixed<MODE, float, 512>), lds_mixed); hipLaunchKernelGGL((colored_plane_mixed<MODE, float, 512>), grid, dim3(512), lds_mixed, s, a, mg); } \
-    else { SKR_ALLOW_LDS((colored_plane_mixed<MODE, float, 1024>), lds_mixed); hipLaunchKernelGGL((colored_plane_mixed<MODE, float, 1024>), grid, dim3(1024), lds_mixed, s, a, mg); }              \
-  } while (0)
-  if (mode == 0) SKR_PLANES_M(0); else SKR_PLANES_M(1);
-#undef SKR_PLANES_M
-  SKR_CHECK_LAUNCH();
-  return SKR_OK;
+  static const int64_t odd_limit = env_int("SKR_FFT_ODD_LIMIT", 1 << 20);
+  MixedPlan m;
+  if (env_flag("SKR_FFT_NO_MIXED") || !mixed_plane_geometry(d2, d3, false, m) || m.geom.h.r + m.geom.w.r > odd_limit) return SKR_ERR_UNSUPPORTED;
+  return mode == 0 ? launch_mixed<0, float>(a, m, 0, s) : launch_mixed<1, float>(a, m, 0, s);
+}
+
+// ---- the partials workspace of skr_noise_colored ------------------------------------------------------------------------------------
+// partials_f64 holds 4 * batch * partial_slots doubles.  The (sum, sum of squares) of the white noise take the first [batch][n_slots][2], one slot per block
+// of the forward kernel: n_slots = d1 (Mixed, FusedPlanes) or the blocks of pass A (Passes).  Routes that take the coloured statistics from the weighted
+// spectrum (Parseval, reduced by the outer-axis kernel) put [batch][n_slots_c][2] right behind: room for 2 * partial_slots - n_slots slots per sample, of
+// which the outer-axis kernel fills at most 4096 (one per block; launch_outer_axis_regs lowers n_slots_c to its grid, colored_mid_axes has one per tile).
+// FusedPlanes keeps one slot per sample back: the last 2 * batch doubles (4 floats per sample) are the bookkeeping of colored_inverse128 -- [batch] rescale
+// factors, the plane ticket, [batch] arrival counters of the outer-axis kernel.
+static int32_t coloured_slots(int64_t partial_slots, int64_t n_slots, int64_t kept_back) {
+  const int64_t room = 2 * partial_slots - n_slots - kept_back;
+  return (int32_t)(room < 4096 ? room : 4096);
+}
+// returns the [batch] factors workspace; inv_blocks > 0: the launch state of colored_inverse128 and of the outer-axis kernel ahead of it
+static float* inverse128_bookkeeping(ColoredArgs& a, double* partials_f64, int64_t partial_slots, int64_t inv_blocks) {
+  float* tail = reinterpret_cast<float*>(partials_f64 + 4 * a.batch * partial_slots - 2 * a.batch);
+  if (inv_blocks > 0) {
+    static const bool static_deal = env_flag("SKR_COLORED_INV_STATIC"), factors_kernel = env_flag("SKR_COLORED_FACTORS_KERNEL");
+    a.first_ticket = (uint32_t)(2 * inv_blocks);
+    a.ticket = static_deal ? nullptr : reinterpret_cast<uint32_t*>(tail + a.batch);
+    if (!factors_kernel) { a.done_count = reinterpret_cast<uint32_t*>(tail + 2 * a.batch); a.factors_out = tail; }
+  }
+  return tail;
+}
+
+// ---- routes: how skr_noise_colored draws a batch of d1 x d2 x d3 units (d1 = 1: 2-D); the table with kernels and grids is in DESIGN.md section 4.3 -----
+//   Mixed        d2, d3 = 2^a x (odd <= 63), not both powers of two, under d1 = 1, 2, 4, 8 or 16: colored_plane_mixed
+//   FusedPlanes  powers of two, a d2 x d3 plane fits the LDS, d1 <= 16: colored_plane
+//   Passes       every other power-of-two unit with sides up to FFT_MAX_TILE: one axis per kernel
+//   Unsupported  the caller takes skr_noise_colored_any
+enum class ColoredRoute { Mixed, FusedPlanes, Passes, Unsupported };
+struct RoutePlan { ColoredRoute route = ColoredRoute::Unsupported; int l1 = -1 /* log2 d1 */; PlaneFit fit /* l2, l3; the FusedPlanes launch */; MixedPlan mixed; };
+static RoutePlan choose_route(int64_t batch, int32_t d1, int32_t d2, int32_t d3, int64_t partial_slots) {
+  RoutePlan p;
+  p.fit = plane_fit(d2, d3);
+  p.l1 = d1 == 1 ? 0 : ilog2_exact(d1);
+  const bool pow2 = p.fit.l3 >= 2 && p.fit.l2 >= 1 && p.l1 >= 0 && d3 <= FFT_MAX_TILE && d2 <= FFT_MAX_TILE && d1 <= FFT_MAX_TILE;
+  const bool mixed = !pow2 && p.l1 >= 0 && d1 <= 16 && !env_flag("SKR_FFT_NO_MIXED") && mixed_plane_geometry(d2, d3, d1 == 1, p.mixed) && d1 <= partial_slots;
+  if ((!pow2 && !mixed) || batch > 65535) return p;
+  const bool fused = p.fit.pairs_fit && d1 <= 16 && d3 % 4 == 0 && !env_flag("SKR_FFT_NO_FUSE");
+  p.route = mixed ? ColoredRoute::Mixed : (fused ? ColoredRoute::FusedPlanes : ColoredRoute::Passes);
+  return p;
+}
+
+// 2-D: one kernel.  3-D: forward planes (white statistics), outer axis (weights, Parseval), inverse planes (rescale, result dtype).
+static int draw_mixed(ColoredArgs& a, int32_t out_dtype, const MixedPlan& m, int64_t partial_slots, hipStream_t s) {
+  a.n_slots = a.d1;
+  const int const_side = a.d2 == a.d3 && !env_flag("SKR_FFT_NO_CONST_SIDE") ? a.d2 : 0;  // 96 / 160 / 192: compile-time geometry
+  if (a.d1 == 1) return with_out_type(out_dtype, [&](auto t) { return launch_mixed<2, typename decltype(t)::type>(a, m, const_side, s); });
+  int rc = launch_mixed<0, float>(a, m, const_side, s);
+  if (rc != SKR_OK) return rc;
+  a.n_slots_c = coloured_slots(partial_slots, a.d1, 0);
+  if ((rc = launch_outer_axis_regs(a, s)) != SKR_OK) return rc;
+  return with_out_type(out_dtype, [&](auto t) { return launch_mixed<1, typename decltype(t)::type>(a, m, const_side, s); });
+}
+
+// as draw_mixed on colored_plane; the inverse of 128 x 128 planes on the persistent colored_inverse128
+static int draw_fused_planes(ColoredArgs& a, int32_t out_dtype, const PlaneFit& fit, double* partials_f64, int64_t partial_slots, hipStream_t s) {
+  if (a.d1 > partial_slots) return SKR_ERR_SHAPE;
+  a.n_slots = a.d1;
+  if (a.d1 == 1) return with_out_type(out_dtype, [&](auto t) { return launch_plane<2, typename decltype(t)::type>(a, fit, s); });
+  const int32_t slots_c = coloured_slots(partial_slots, a.d1, 1);
+  if (slots_c < 1) return SKR_ERR_SHAPE;
+  const int64_t n_planes = a.batch * (int64_t)a.d1, inv_blocks = inverse128_blocks(a.d2, a.d3, out_dtype, n_planes);
+  float* factors = inverse128_bookkeeping(a, partials_f64, partial_slots, inv_blocks);
+  int rc = launch_plane<0, float>(a, fit, s);
+  if (rc != SKR_OK) return rc;
+  a.n_slots_c = slots_c;
+  if ((rc = launch_outer_axis_regs(a, s)) != SKR_OK) return rc;
+  if (inv_blocks > 0) return launch_inverse128(a, out_dtype, n_planes, inv_blocks, factors, s);
+  return with_out_type(out_dtype, [&](auto t) { return launch_plane<1, typename decltype(t)::type>(a, fit, s); });
+}
+
+// one strided axis of the separate passes (colored_strided_axis): MODE 0 forward, 1 inverse, 2 forward + radial weights + inverse
+template <int MODE>
+static int launch_strided(const ColoredArgs& a, int N, int logN, int64_t n_lines, int64_t inner, int64_t outer, int64_t stride, int axis, hipStream_t s) {
+  int logL = 0;
+  while ((2 << logL) * N <= fft_tile_points() && (2 << logL) <= 64) ++logL;  // L = 2^logL lines per tile, <= 64 (512 B runs)
+  const int64_t L = 1 << logL, blocks = (n_lines + L - 1) / L;
+  const size_t lds = sizeof(float2) * ((size_t)N / 2 + (size_t)L * (N + 1));
+  if (lds > 150 * 1024) return SKR_ERR_UNSUPPORTED;
+  return launch_lds(colored_strided_axis<MODE>, dim3((unsigned)blocks, (unsigned)a.batch), dim3(FFT_THREADS), lds, s, a, N, logN, logL, n_lines, inner, outer, stride, axis);
+}
+
+// A short channel axis: columns + channels + inverse columns in one tile residency (colored_mid_axes).  False: not taken; else logT = log2 of the tile width T: N1 T d2 <= 8192 points
+// (66 KB: two blocks per CU; a 132 KB tile left a CU one block of four waves and ran 20 % SLOWER than the three separate passes), halved
+// while the launch has fewer than six blocks per CU; measured on 256 x 256 planes (us per draw, separate passes -> fused): 4 channels x 64
+// 215 -> 188, x 256 755 -> 616, 2 channels x 128 205 -> 159; 8 channels stay on the separate passes (186 vs 211 at T = 4).
+static bool mid_axes_tile(const ColoredArgs& a, int64_t free_slots, int& logT) {
+  if ((a.d1 != 2 && a.d1 != 4) || env_flag("SKR_COLORED_NO_MID")) return false;
+  logT = 0;
+  while ((int64_t)a.d1 * (2 << logT) * a.d2 <= 8192) ++logT;
+  while (logT > 2 && ((a.d3h + (1 << logT) - 1) >> logT) * a.batch < 6 * 256) --logT;
+  const int64_t v = env_int("SKR_COLORED_MID_LOGT", -1);
+  if (v >= 2 && v <= 5 && (int64_t)a.d1 * (1 << v) * a.d2 <= 16384 && (a.d1 << v) <= 64) logT = (int)v;
+  const int64_t tiles = (a.d3h + (1 << logT) - 1) >> logT;
+  return logT >= 2 && tiles <= free_slots && (int64_t)a.d1 * (1 << logT) * a.d2 <= 16384;
+}
+
+// pass F: rescale per sample, fp32 scratch -> result dtype
+static int launch_finish(const ColoredArgs& a, void* out, int32_t out_dtype, hipStream_t s) {
+  const int64_t unit = (int64_t)a.d1 * a.d2 * a.d3;
+  int64_t bx = (unit / 4 + 255) / 256; if (bx > 64) bx = 64;
+  return with_out_type(out_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_lds(colored_finish<T>, dim3((unsigned)bx, (unsigned)a.batch), dim3(256), 0, s, static_cast<T*>(out), a, unit, a.has_energy, a.energy);
+  });
+}
+
+// passes A ... F of the file's head, one axis per kernel
+static int draw_passes(ColoredArgs& a, void* out, int32_t out_dtype, const RoutePlan& p, int64_t partial_slots, hipStream_t s) {
+  const int32_t d1 = a.d1, d2 = a.d2, d3 = a.d3, l1 = p.l1, l2 = p.fit.l2, l3 = p.fit.l3;
+  const int64_t d3h = a.d3h, plane = (int64_t)d2 * d3h;
+  // pass A: last axis forward
+  const int64_t lines_last = (int64_t)d1 * d2;
+  int La = 2 * (fft_tile_points() / d3); if (La > lines_last) La = (int)lines_last; if (La < 2) La = 2;  // real lines per tile (pairs share a transform)
+  const int64_t blocks_a = (lines_last + La - 1) / La;
+  if (blocks_a > partial_slots) return SKR_ERR_SHAPE;
+  a.n_slots = (int32_t)blocks_a;
+  const size_t lds_a = sizeof(float2) * ((size_t)d3 / 2 + (size_t)(La / 2) * (d3 + 1));
+  if (lds_a > 150 * 1024) return SKR_ERR_UNSUPPORTED;
+  const dim3 grid_a((unsigned)blocks_a, (unsigned)a.batch);
+  int rc = launch_lds(colored_last_axis<true>, grid_a, dim3(FFT_THREADS), lds_a, s, a, l3, La);
+  if (rc != SKR_OK) return rc;
+
+  // 3-D units with a short outer axis: Parseval partials from the outer-axis kernel, so that pass E can write the result itself
+  const bool direct_out = d1 > 1 && d1 <= 16 && d3 % 4 == 0 && 2 * partial_slots - blocks_a >= 1;
+  int mid_logT = 0;
+  if (direct_out && mid_axes_tile(a, 2 * partial_slots - blocks_a, mid_logT)) {  // passes B, C, D in one kernel
+    const int T = 1 << mid_logT;
+    const int64_t tiles = (d3h + T - 1) / T;
+    a.n_slots_c = (int32_t)tiles;
+    const size_t lds = sizeof(float2) * ((size_t)d2 / 2 + (size_t)d1 * T * (d2 + 1));
+    rc = launch_lds(d1 == 2 ? colored_mid_axes<2> : colored_mid_axes<4>, dim3((unsigned)tiles, (unsigned)a.batch), dim3(FFT_THREADS), lds, s, a, d2, l2, mid_logT);
+    if (rc != SKR_OK) return rc;
+  } else if (d1 > 1) {
+    // axis 2 (length d2, stride d3h): lines = (i1, k3); axis 1 (length d1, stride d2*d3h): in registers up to 16, else on the LDS tile kernel
+    if ((rc = launch_strided<0>(a, d2, l2, (int64_t)d1 * d3h, d3h, plane, d3h, 2, s)) != SKR_OK) return rc;
+    if (direct_out) a.n_slots_c = coloured_slots(partial_slots, blocks_a, 0);
+    rc = d1 <= 16 ? launch_outer_axis_regs(a, s) : launch_strided<2>(a, d1, l1, plane, plane, 0, plane, 1, s);
+    if (rc != SKR_OK) return rc;
+    if ((rc = launch_strided<1>(a, d2, l2, (int64_t)d1 * d3h, d3h, plane, d3h, 2, s)) != SKR_OK) return rc;
+  } else {
+    if ((rc = launch_strided<2>(a, d2, l2, d3h, d3h, 0, d3h, 2, s)) != SKR_OK) return rc;
+  }
+
+  if (direct_out)  // pass E writes the result dtype; no scratch, no pass F
+    return with_out_type(out_dtype, [&](auto t) { return launch_lds(colored_last_axis_out<typename decltype(t)::type>, grid_a, dim3(FFT_THREADS), lds_a, s, a, l3, La); });
+  // pass E: last axis inverse -> real scratch
+  if ((rc = launch_lds(colored_last_axis<false>, grid_a, dim3(FFT_THREADS), lds_a, s, a, l3, La)) != SKR_OK) return rc;
+  return launch_finish(a, out, out_dtype, s);
 }
 
 }  // namespace skr
 
 static int colored_batch(void* out, int32_t out_dtype, void* spec_c64, float* scratch_f32, double* partials_f64, int64_t partial_slots,
                          const uint64_t* seeds_dev, uint64_t stream_id, int64_t batch, int32_t d1, int32_t d2, int32_t d3,
-                         double exponent, int32_t has_energy, double energy, void* stream);
+                         double exponent, int32_t has_energy, double energy, void* stream) {
+  using namespace skr;
+  const RoutePlan plan = choose_route(batch, d1, d2, d3, partial_slots);
+  if (plan.route == ColoredRoute::Unsupported) return SKR_ERR_UNSUPPORTED;  // (the caller takes skr_noise_colored_any)
+  ColoredArgs a;
+  a.spec = reinterpret_cast<float2*>(spec_c64); a.real_out = scratch_f32; a.partials = partials_f64; a.seeds = seeds_dev;
+  a.stream = stream_id; a.batch = batch; a.d1 = d1; a.d2 = d2; a.d3 = d3; a.d3h = d3 / 2 + 1;
+  a.exponent_half_neg = (float)(-exponent / 2.0);
+  a.out = out; a.has_energy = has_energy; a.energy = energy;
+#ifdef SKR_COLORED_TRACE
+  a.trace = g_colored_trace;
+#endif
+  const int nd = d1 > 1 ? 3 : 2;
+  const double n_eff = nd == 3 ? ((double)d1 + d2 + d3) / 3.0 : ((double)d2 + d3) / 2.0;
+  a.eps_clip = (float)(0.5 / (n_eff > 4.0 ? n_eff : 4.0));
+  // r_max over the rfftn grid: every axis reaches floor(d/2)/d
+  auto fmaxf_axis = [](int d) { return (float)(d / 2) / (float)d; };
+  const float m1 = d1 > 1 ? fmaxf_axis(d1) : 0.f, m2 = fmaxf_axis(d2), m3 = fmaxf_axis(d3);
+  const float rmax = sqrtf(m1 * m1 + m2 * m2 + m3 * m3);
+  a.inv_rmax = rmax > 0.f ? 1.0f / rmax : 1.0f;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  switch (plan.route) {
+    case ColoredRoute::Mixed: return draw_mixed(a, out_dtype, plan.mixed, partial_slots, s);
+    case ColoredRoute::FusedPlanes: return draw_fused_planes(a, out_dtype, plan.fit, partials_f64, partial_slots, s);
+    default: return draw_passes(a, out, out_dtype, plan, partial_slots, s);
+  }
+}
 
 extern "C" int skr_noise_colored(void* out, int32_t out_dtype, void* spec_c64, float* scratch_f32, double* partials_f64, int64_t partial_slots,
                                  const uint64_t* seeds_dev, uint64_t stream_id, int64_t batch, int32_t d1, int32_t d2, int32_t d3,
@@ -1765,7 +1988,7 @@ extern "C" int skr_noise_colored(void* out, int32_t out_dtype, void* spec_c64, f
   // Samples are independent, and the half spectrum of a batch is written once and read three times (forward planes -> channel axis ->
   // inverse planes).  Groups of samples whose spectrum fits the 256 MB Infinity Cache go through the three kernels one after the other,
   // over the SAME spectrum buffer, so that those re-reads are served on the chip instead of from HBM.
-  static const int64_t group_mb = [] { const char* e = getenv("SKR_COLORED_GROUP_MB"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
+  static const int64_t group_mb = env_int("SKR_COLORED_GROUP_MB", 0);
   const int64_t per_sample = (int64_t)d1 * d2 * (d3 / 2 + 1) * (int64_t)sizeof(float2);
   int64_t group = batch;
   if (group_mb > 0 && d1 > 1 && per_sample * batch > group_mb * (1ll << 20)) {
@@ -1782,249 +2005,5 @@ extern "C" int skr_noise_colored(void* out, int32_t out_dtype, void* spec_c64, f
                                  seeds_dev + s0, stream_id, n, d1, d2, d3, exponent, has_energy, energy, stream);
     if (rc != SKR_OK) return rc;
   }
-  return SKR_OK;
-}
-
-static int colored_batch(void* out, int32_t out_dtype, void* spec_c64, float* scratch_f32, double* partials_f64, int64_t partial_slots,
-                         const uint64_t* seeds_dev, uint64_t stream_id, int64_t batch, int32_t d1, int32_t d2, int32_t d3,
-                         double exponent, int32_t has_energy, double energy, void* stream) {
-  using namespace skr;
-  const int l3 = ilog2_exact(d3), l2 = ilog2_exact(d2), l1 = d1 == 1 ? 0 : ilog2_exact(d1);
-  const bool pow2 = l3 >= 2 && l2 >= 1 && l1 >= 0 && d3 <= FFT_MAX_TILE && d2 <= FFT_MAX_TILE && d1 <= FFT_MAX_TILE;
-  // planes whose sides are a power of two times an odd factor up to 63 (96, 112, 144, 160, 192 ...) under a power-of-two channel axis: colored_plane_mixed
-  MixedGeom mg;
-  bool mixed = false;
-  size_t lds_mixed = 0;
-  int mixed_threads = 0;
-  if (!pow2 && l1 >= 0 && d1 <= 16 && getenv("SKR_FFT_NO_MIXED") == nullptr)
-    mixed = mixed_plane_geometry(d2, d3, d1 == 1, mg, lds_mixed, mixed_threads) && d1 <= partial_slots;
-  if (!pow2 && !mixed) return SKR_ERR_UNSUPPORTED;  // (the caller takes skr_noise_colored_any: hipFFT)
-  if (batch > 65535) return SKR_ERR_UNSUPPORTED;
-  ColoredArgs a;
-  a.spec = reinterpret_cast<float2*>(spec_c64); a.real_out = scratch_f32; a.partials = partials_f64; a.seeds = seeds_dev;
-  a.stream = stream_id; a.batch = batch; a.d1 = d1; a.d2 = d2; a.d3 = d3; a.d3h = d3 / 2 + 1;
-  a.exponent_half_neg = (float)(-exponent / 2.0);
-  a.out = out; a.has_energy = has_energy; a.energy = energy; a.n_slots_c = 0; a.raw = 0; a.factors = nullptr; a.ticket = nullptr; a.first_ticket = 0; a.done_count = nullptr; a.factors_out = nullptr;
-#ifdef SKR_COLORED_TRACE
-  a.trace = g_colored_trace;
-#endif
-  const int nd = d1 > 1 ? 3 : 2;
-  const double n_eff = nd == 3 ? ((double)d1 + d2 + d3) / 3.0 : ((double)d2 + d3) / 2.0;
-  a.eps_clip = (float)(0.5 / (n_eff > 4.0 ? n_eff : 4.0));
-  // r_max over the rfftn grid: every axis reaches floor(d/2)/d
-  auto fmaxf_axis = [](int d) { return (float)(d / 2) / (float)d; };
-  const float m1 = d1 > 1 ? fmaxf_axis(d1) : 0.f, m2 = fmaxf_axis(d2), m3 = fmaxf_axis(d3);
-  const float rmax = sqrtf(m1 * m1 + m2 * m2 + m3 * m3);
-  a.inv_rmax = rmax > 0.f ? 1.0f / rmax : 1.0f;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-
-  const int64_t d3h = a.d3h;
-  // fused plane kernels when one d2 x d3 plane (+ its half spectrum) fits the CU's LDS
-  const size_t tile_points = (size_t)(d2 / 2) * (d3 + 1) > (size_t)d3h * (d2 + 1) ? (size_t)(d2 / 2) * (d3 + 1) : (size_t)d3h * (d2 + 1);
-  const size_t lds_plane = sizeof(float2) * ((size_t)d3 + d2 + tile_points);  // twiddles of both axes (full circle) + the tile
-  const bool fused = lds_plane <= 150 * 1024 && (int64_t)(d2 / 2) * d3 <= PLANE_THREADS * PLANE_ITEMS && (int64_t)(d2 / 2) * d3h <= PLANE_THREADS * PLANE_ITEMS &&
-                     (nd == 2 || d1 <= 16) && d3 % 4 == 0 && getenv("SKR_FFT_NO_FUSE") == nullptr;
-  auto outer_axis = [&]() -> int {
-    // axis 1 (length d1, stride d2*d3h): forward, radial weights, inverse in one pass
-    if (d1 <= 16) {
-      const int64_t cols = (int64_t)d2 * d3h;
-      int64_t bx = (cols + 255) / 256; if (bx > 4096) bx = 4096;
-      if (a.n_slots_c > 0) { if (bx > a.n_slots_c) bx = a.n_slots_c; a.n_slots_c = (int32_t)bx; }  // one Parseval slot per block
-      dim3 grid((unsigned)bx, (unsigned)batch);
-      switch (d1) {
-        case 2: hipLaunchKernelGGL(colored_outer_axis_regs<2>, grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL(colored_outer_axis_regs<4>, grid, dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL(colored_outer_axis_regs<8>, grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(colored_outer_axis_regs<16>, grid, dim3(256), 0, s, a); break;
-      }
-      return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
-    }
-    return -1;  // caller uses the LDS tile kernel
-  };
-
-  if (mixed) {
-    a.n_slots = d1;
-    dim3 grid((unsigned)d1, (unsigned)batch);
-    const int const_side = (d2 == d3 && getenv("SKR_FFT_NO_CONST_SIDE") == nullptr) ? d2 : 0;  // 96 / 160 / 192: compile-time geometry
-#define SKR_MIXED_SIDE(MODE, T, THREADS, SIDE) do { SKR_ALLOW_LDS((colored_plane_mixed<MODE, T, THREADS, SIDE>), lds_mixed); hipLaunchKernelGGL((colored_plane_mixed<MODE, T, THREADS, SIDE>), grid, dim3(THREADS), lds_mixed, s, a, mg); } while (0)
-#define SKR_MIXED_T(MODE, T) do {                                                                                                              \
-      if (const_side == 96 && mixed_threads == 512 && sizeof(T) <= 4) SKR_MIXED_SIDE(MODE, T, 512, 96);                                          \
-      else if (const_side == 160 && mixed_threads == 1024 && sizeof(T) <= 4) SKR_MIXED_SIDE(MODE, T, 1024, 160);                                 \
-      else if (const_side == 192 && mixed_threads == 1024 && sizeof(T) <= 4 && MODE != 2) SKR_MIXED_SIDE((MODE == 2 ? 1 : MODE), T, 1024, 192);  \
-      else if (mixed_threads == 512) { SKR_ALLOW_LDS((colored_plane_mixed<MODE, T, 512>), lds_mixed); hipLaunchKernelGGL((colored_plane_mixed<MODE, T, 512>), grid, dim3(512), lds_mixed, s, a, mg); } \
-      else { SKR_ALLOW_LDS((colored_plane_mixed<MODE, T, 1024>), lds_mixed); hipLaunchKernelGGL((colored_plane_mixed<MODE, T, 1024>), grid, dim3(1024), lds_mixed, s, a, mg); }              \
-    } while (0)
-#define SKR_MIXED(MODE)                                             \
-    switch (out_dtype) {                                            \
-      case SKR_BF16: SKR_MIXED_T(MODE, __bf16); break;              \
-      case SKR_F16: SKR_MIXED_T(MODE, _Float16); break;             \
-      case SKR_F32: SKR_MIXED_T(MODE, float); break;                \
-      case SKR_F64: SKR_MIXED_T(MODE, double); break;               \
-      default: return SKR_ERR_DTYPE;                                \
-    }                                                               \
-    SKR_CHECK_LAUNCH()
-    if (nd == 2) {
-      SKR_MIXED(2);
-    } else {
-      SKR_MIXED_T(0, float);
-      SKR_CHECK_LAUNCH();
-      a.n_slots_c = (int32_t)(2 * partial_slots - d1 < 4096 ? 2 * partial_slots - d1 : 4096);
-      const int rc = outer_axis();
-      if (rc != SKR_OK) return rc;
-      SKR_MIXED(1);
-    }
-#undef SKR_MIXED
-#undef SKR_MIXED_T
-#undef SKR_MIXED_SIDE
-    return SKR_OK;
-  }
-  if (fused) {
-    if (d1 > partial_slots) return SKR_ERR_SHAPE;
-    a.n_slots = d1;
-    dim3 grid((unsigned)d1, (unsigned)batch);
-#define SKR_PLANE_T(MODE, T, CH, CW) do { SKR_ALLOW_LDS((colored_plane<MODE, T, CH, CW>), lds_plane); hipLaunchKernelGGL((colored_plane<MODE, T, CH, CW>), grid, dim3(PLANE_THREADS), lds_plane, s, a, l2, l3); } while (0)
-#define SKR_PLANE_SZ(MODE, T)                                                    \
-    if (l2 == 7 && l3 == 7) SKR_PLANE_T(MODE, T, 7, 7);                          \
-    else if (l2 == 6 && l3 == 6) SKR_PLANE_T(MODE, T, 6, 6);                     \
-    else SKR_PLANE_T(MODE, T, 0, 0)
-#define SKR_PLANE(MODE)                                                          \
-    switch (out_dtype) {                                                         \
-      case SKR_BF16: SKR_PLANE_SZ(MODE, __bf16); break;                          \
-      case SKR_F16: SKR_PLANE_SZ(MODE, _Float16); break;                         \
-      case SKR_F32: SKR_PLANE_SZ(MODE, float); break;                            \
-      case SKR_F64: SKR_PLANE_T(MODE, double, 0, 0); break;                      \
-      default: return SKR_ERR_DTYPE;                                             \
-    }                                                                            \
-    SKR_CHECK_LAUNCH()
-    if (nd == 2) {
-      SKR_PLANE(2);
-    } else {
-      // room left in the partials buffer, less one slot per sample: the last 2 * batch doubles (4 floats per sample) are the bookkeeping of
-      // colored_inverse128 -- [batch] rescale factors, the plane ticket, [batch] arrival counters of the outer-axis kernel
-      const int32_t slots_c = (int32_t)(2 * partial_slots - d1 - 1 < 4096 ? 2 * partial_slots - d1 - 1 : 4096);
-      if (slots_c < 1) return SKR_ERR_SHAPE;
-      float* tail = reinterpret_cast<float*>(partials_f64 + 4 * batch * partial_slots - 2 * batch);
-      const int64_t inv_blocks = inverse128_blocks(d2, d3, out_dtype, batch * (int64_t)d1);
-      if (inv_blocks > 0) {
-        static const bool static_deal = getenv("SKR_COLORED_INV_STATIC") != nullptr, factors_kernel = getenv("SKR_COLORED_FACTORS_KERNEL") != nullptr;
-        a.first_ticket = (uint32_t)(2 * inv_blocks);
-        a.ticket = static_deal ? nullptr : reinterpret_cast<uint32_t*>(tail + batch);
-        if (!factors_kernel) { a.done_count = reinterpret_cast<uint32_t*>(tail + 2 * batch); a.factors_out = tail; }
-      }
-      SKR_PLANE_SZ(0, float);
-      SKR_CHECK_LAUNCH();
-      a.n_slots_c = slots_c;
-      const int rc = outer_axis();  // d1 <= 16: register kernel, with the Parseval partials of the weighted spectrum
-      if (rc != SKR_OK) return rc;
-      const int inv = launch_inverse128(a, out_dtype, batch * (int64_t)d1, tail, s);  // 128 x 128 planes: the persistent kernel
-      if (inv >= 0) return inv;
-      SKR_PLANE(1);
-    }
-#undef SKR_PLANE
-#undef SKR_PLANE_SZ
-#undef SKR_PLANE_T
-    return SKR_OK;  // the plane kernels wrote `out` themselves
-  } else {
-  // pass A: last axis forward
-  const int64_t lines_last = (int64_t)d1 * d2;
-  const int tile = fft_tile_points();
-  int La = 2 * (tile / d3); if (La > lines_last) La = (int)lines_last; if (La < 2) La = 2;  // real lines per tile (pairs share a transform)
-  const int64_t blocks_a = (lines_last + La - 1) / La;
-  if (blocks_a > partial_slots) return SKR_ERR_SHAPE;
-  a.n_slots = (int32_t)blocks_a;
-  const size_t lds_a = sizeof(float2) * ((size_t)d3 / 2 + (size_t)(La / 2) * (d3 + 1));
-  if (lds_a > 150 * 1024) return SKR_ERR_UNSUPPORTED;
-  SKR_ALLOW_LDS(colored_last_axis<true>, lds_a);
-  SKR_ALLOW_LDS(colored_last_axis<false>, lds_a);
-  hipLaunchKernelGGL(colored_last_axis<true>, dim3((unsigned)blocks_a, (unsigned)batch), dim3(FFT_THREADS), lds_a, s, a, l3, La);
-  SKR_CHECK_LAUNCH();
-
-  auto strided = [&](int mode, int N, int logN, int64_t n_lines, int64_t inner, int64_t outer, int64_t stride, int axis) -> int {
-    int logL = 0;
-    while ((2 << logL) * N <= tile && (2 << logL) <= 64) ++logL;  // L = 2^logL lines per tile, <= 64 (512 B runs)
-    const int L = 1 << logL;
-    const int64_t blocks = (n_lines + L - 1) / L;
-    const size_t lds = sizeof(float2) * ((size_t)N / 2 + (size_t)L * (N + 1));
-    dim3 grid((unsigned)blocks, (unsigned)batch);
-    if (lds > 150 * 1024) return SKR_ERR_UNSUPPORTED;
-    SKR_ALLOW_LDS(colored_strided_axis<0>, lds);
-    SKR_ALLOW_LDS(colored_strided_axis<1>, lds);
-    SKR_ALLOW_LDS(colored_strided_axis<2>, lds);
-    if (mode == 0) hipLaunchKernelGGL(colored_strided_axis<0>, grid, dim3(FFT_THREADS), lds, s, a, N, logN, logL, n_lines, inner, outer, stride, axis);
-    else if (mode == 1) hipLaunchKernelGGL(colored_strided_axis<1>, grid, dim3(FFT_THREADS), lds, s, a, N, logN, logL, n_lines, inner, outer, stride, axis);
-    else hipLaunchKernelGGL(colored_strided_axis<2>, grid, dim3(FFT_THREADS), lds, s, a, N, logN, logL, n_lines, inner, outer, stride, axis);
-    return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
-  };
-  int rc;
-  // 3-D units with a short outer axis: Parseval partials from the outer-axis kernel, so that pass E can write the result itself
-  const bool direct_out = nd == 3 && d1 <= 16 && d3 % 4 == 0 && 2 * partial_slots - blocks_a >= 1;
-  // a short channel axis: columns + channels + inverse columns in one tile residency (colored_mid_axes).  Tile width T: N1 T d2 <= 8192 points
-  // (66 KB: two blocks per CU; a 132 KB tile left a CU one block of four waves and ran 20 % SLOWER than the three separate passes), halved
-  // while the launch has fewer than six blocks per CU; measured on 256 x 256 planes (us per draw, separate passes -> fused): 4 channels x 64
-  // 215 -> 188, x 256 755 -> 616, 2 channels x 128 205 -> 159; 8 channels stay on the separate passes (186 vs 211 at T = 4).
-  int mid_logT = -1;
-  if (nd == 3 && direct_out && (d1 == 2 || d1 == 4) && getenv("SKR_COLORED_NO_MID") == nullptr) {
-    int logT = 0;
-    while ((int64_t)d1 * (2 << logT) * d2 <= 8192) ++logT;
-    while (logT > 2 && ((d3h + (1 << logT) - 1) >> logT) * batch < 6 * 256) --logT;
-    if (const char* e = getenv("SKR_COLORED_MID_LOGT")) { const int v = atoi(e); if (v >= 2 && (int64_t)d1 * (1 << v) * d2 <= 16384 && (d1 << v) <= 64) logT = v; }
-    const int64_t tiles = (d3h + (1 << logT) - 1) >> logT;
-    if (logT >= 2 && tiles <= 2 * partial_slots - blocks_a && (int64_t)d1 * (1 << logT) * d2 <= 16384) mid_logT = logT;
-  }
-  if (mid_logT >= 0) {
-    const int T = 1 << mid_logT;
-    const int64_t tiles = (d3h + T - 1) / T;
-    a.n_slots_c = (int32_t)tiles;
-    const size_t lds = sizeof(float2) * ((size_t)d2 / 2 + (size_t)d1 * T * (d2 + 1));
-    dim3 grid((unsigned)tiles, (unsigned)batch);
-    switch (d1) {
-      case 2: SKR_ALLOW_LDS(colored_mid_axes<2>, lds); hipLaunchKernelGGL(colored_mid_axes<2>, grid, dim3(FFT_THREADS), lds, s, a, d2, l2, mid_logT); break;
-      case 4: SKR_ALLOW_LDS(colored_mid_axes<4>, lds); hipLaunchKernelGGL(colored_mid_axes<4>, grid, dim3(FFT_THREADS), lds, s, a, d2, l2, mid_logT); break;
-      default: return SKR_ERR_SHAPE;
-    }
-    SKR_CHECK_LAUNCH();
-  } else if (nd == 3) {
-    // axis 2 (length d2, stride d3h): lines = (i1, k3)
-    if ((rc = strided(0, d2, l2, (int64_t)d1 * d3h, d3h, (int64_t)d2 * d3h, d3h, 2)) != SKR_OK) return rc;
-    if (direct_out) a.n_slots_c = (int32_t)(2 * partial_slots - blocks_a < 4096 ? 2 * partial_slots - blocks_a : 4096);
-    rc = outer_axis();
-    if (rc == -1) rc = strided(2, d1, l1, (int64_t)d2 * d3h, (int64_t)d2 * d3h, 0, (int64_t)d2 * d3h, 1);
-    if (rc != SKR_OK) return rc;
-    if ((rc = strided(1, d2, l2, (int64_t)d1 * d3h, d3h, (int64_t)d2 * d3h, d3h, 2)) != SKR_OK) return rc;
-  } else {
-    if ((rc = strided(2, d2, l2, d3h, d3h, 0, d3h, 2)) != SKR_OK) return rc;
-  }
-
-  if (direct_out) {  // pass E writes the result dtype; no scratch, no pass F
-    dim3 grid_e((unsigned)blocks_a, (unsigned)batch);
-    switch (out_dtype) {
-#define SKR_E(T) SKR_ALLOW_LDS(colored_last_axis_out<T>, lds_a); hipLaunchKernelGGL(colored_last_axis_out<T>, grid_e, dim3(FFT_THREADS), lds_a, s, a, l3, La)
-      case SKR_BF16: SKR_E(__bf16); break;
-      case SKR_F16: SKR_E(_Float16); break;
-      case SKR_F32: SKR_E(float); break;
-      case SKR_F64: SKR_E(double); break;
-#undef SKR_E
-      default: return SKR_ERR_DTYPE;
-    }
-    SKR_CHECK_LAUNCH();
-    return SKR_OK;
-  }
-  // pass E: last axis inverse -> real scratch
-  hipLaunchKernelGGL(colored_last_axis<false>, dim3((unsigned)blocks_a, (unsigned)batch), dim3(FFT_THREADS), lds_a, s, a, l3, La);
-  SKR_CHECK_LAUNCH();
-  }
-
-  // pass F
-  const int64_t unit = (int64_t)d1 * d2 * d3;
-  int64_t bx = (unit / 4 + 255) / 256; if (bx > 64) bx = 64;
-  dim3 grid((unsigned)bx, (unsigned)batch);
-  switch (out_dtype) {
-    case SKR_BF16: hipLaunchKernelGGL(colored_finish<__bf16>, grid, dim3(256), 0, s, (__bf16*)out, a, unit, has_energy, energy); break;
-    case SKR_F16: hipLaunchKernelGGL(colored_finish<_Float16>, grid, dim3(256), 0, s, (_Float16*)out, a, unit, has_energy, energy); break;
-    case SKR_F32: hipLaunchKernelGGL(colored_finish<float>, grid, dim3(256), 0, s, (float*)out, a, unit, has_energy, energy); break;
-    case SKR_F64: hipLaunchKernelGGL(colored_finish<double>, grid, dim3(256), 0, s, (double*)out, a, unit, has_energy, energy); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  SKR_CHECK_LAUNCH();
   return SKR_OK;
 }

@@ -15,6 +15,7 @@
 #include <tuple>
 
 #include "skr_device.h"
+#include "skr_launch.h"
 #include "../../include/skrample_hip.h"
 #include "skr_philox.h"
 #include "skr_dft.h"
@@ -621,13 +622,8 @@ static int colored_any_attempt(void* out, int32_t out_dtype, void* spec_c64, flo
       const int64_t lines = sample / d;
       int64_t ab = (lines + AXIS_LINES - 1) / AXIS_LINES; if (ab > 4096) ab = 4096;
       const size_t lds = sizeof(float2) * ((size_t)d + (mode == 2 ? 2 : 1) * (size_t)d * AXIS_LINES);
-      const void* fn = mode == 0 ? reinterpret_cast<const void*>(any_outer_axis<0>) : (mode == 1 ? reinterpret_cast<const void*>(any_outer_axis<1>) : reinterpret_cast<const void*>(any_outer_axis<2>));
-      if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SKR_ERR_UNSUPPORTED;
-      const dim3 grid((unsigned)ab, (unsigned)batch);
-      if (mode == 0) hipLaunchKernelGGL(any_outer_axis<0>, grid, dim3(AXIS_THREADS), lds, s, a, axis);
-      else if (mode == 1) hipLaunchKernelGGL(any_outer_axis<1>, grid, dim3(AXIS_THREADS), lds, s, a, axis);
-      else hipLaunchKernelGGL(any_outer_axis<2>, grid, dim3(AXIS_THREADS), lds, s, a, axis);
-      return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+      void (*const kernels[3])(const AnyArgs, int) = {any_outer_axis<0>, any_outer_axis<1>, any_outer_axis<2>};
+      return skr::launch_lds(kernels[mode], dim3((unsigned)ab, (unsigned)batch), dim3(AXIS_THREADS), lds, s, a, axis);
     };
     int rc;
     if (planes && a.n_outer == 2) {  // one pass for both outer axes
@@ -640,11 +636,8 @@ static int colored_any_attempt(void* out, int32_t out_dtype, void* spec_c64, flo
       int64_t tiles = (plane + L - 1) / L; if (tiles > 65535) tiles = 65535;
       const size_t lds = sizeof(float2) * ((size_t)T + 2 * ((size_t)C * T << logL));
       const dim3 grid((unsigned)tiles, (unsigned)batch);
-#define SKR_TWO(CC) do { if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(any_outer_two<CC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SKR_ERR_UNSUPPORTED; \
-                         hipLaunchKernelGGL(any_outer_two<CC>, grid, dim3(TWO_THREADS), lds, s, a, L, logL); } while (0)
-      switch (C) { case 2: SKR_TWO(2); break; case 4: SKR_TWO(4); break; case 8: SKR_TWO(8); break; default: SKR_TWO(16); break; }
-#undef SKR_TWO
-      if (hipGetLastError() != hipSuccess) return SKR_ERR_LAUNCH;
+      void (*kernel)(const AnyArgs, int, int) = C == 2 ? any_outer_two<2> : (C == 4 ? any_outer_two<4> : (C == 8 ? any_outer_two<8> : any_outer_two<16>));
+      if ((rc = skr::launch_lds(kernel, grid, dim3(TWO_THREADS), lds, s, a, L, logL)) != SKR_OK) return rc;
     } else {
     for (int j = a.n_outer - 1; j >= 1; --j) if ((rc = pass(0, j)) != SKR_OK) return rc;
     if ((rc = pass(2, 0)) != SKR_OK) return rc;  // outermost: forward, weights, inverse
@@ -668,14 +661,10 @@ static int colored_any_attempt(void* out, int32_t out_dtype, void* spec_c64, flo
   int64_t fb = (a.unit + 1023) / 1024;  // (64 blocks per sample starved the chip at small batches: 33 us for one 4.8 M-element sample)
   { const int64_t cap = batch >= 32 ? 64 : 2048 / batch; if (fb > cap) fb = cap; if (fb < 1) fb = 1; }
   dim3 grid((unsigned)fb, (unsigned)batch);
-  switch (out_dtype) {
-    case SKR_BF16: hipLaunchKernelGGL(any_finish<__bf16>, grid, dim3(256), 0, s, (__bf16*)out, a, has_energy, energy); break;
-    case SKR_F16: hipLaunchKernelGGL(any_finish<_Float16>, grid, dim3(256), 0, s, (_Float16*)out, a, has_energy, energy); break;
-    case SKR_F32: hipLaunchKernelGGL(any_finish<float>, grid, dim3(256), 0, s, (float*)out, a, has_energy, energy); break;
-    case SKR_F64: hipLaunchKernelGGL(any_finish<double>, grid, dim3(256), 0, s, (double*)out, a, has_energy, energy); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+  return skr::with_out_type(out_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return skr::launch_lds(any_finish<T>, grid, dim3(256), 0, s, static_cast<T*>(out), a, has_energy, energy);
+  });
 }
 
 static int colored_any_impl(void* out, int32_t out_dtype, void* spec_c64, float* scratch_f32, double* partials_f64,

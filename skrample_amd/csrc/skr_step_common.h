@@ -9,6 +9,7 @@
 #include "../../include/skrample_hip.h"
 #include "skr_philox.h"
 #include "skr_pack.h"
+#include "skr_launch.h"  // type_tag
 
 namespace skr {
 
@@ -369,7 +370,6 @@ extern thread_local int g_last_hip_error;
 int finish_launch();
 
 // ---- host side: run-time values to template arguments, kernarg packing -------------------------------------------------------------
-template <typename T> struct type_tag { using type = T; };
 template <bool B> using bool_c = std::integral_constant<bool, B>;
 
 // calls f(std::integral_constant<int, N>{}) for the N of LO..HI that equals n, and nothing for an n outside

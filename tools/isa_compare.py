@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 device code of the step kernels of two source trees, kernel symbol by kernel symbol (no GPU needed).
+"""Compare the gfx950 device code of two source trees, kernel symbol by kernel symbol (no GPU needed).
 
-    python tools/isa_compare.py OLD_TREE NEW_TREE [--jobs N] [--work DIR]
+    python tools/isa_compare.py OLD_TREE NEW_TREE [--files NAME.hip ...] [--jobs N] [--work DIR]
 
-Compiles skr_step.hip, skr_step_fast.hip, skr_step_backward.hip and skr_tape.hip of each tree with the library's own flags
-(`--save-temps -c`), splits the device assembly per kernel the way tests/test_per_sample_isa.py and tests/test_rolling_isa.py do,
+Compiles the named files of skrample_amd/csrc (default: the step files skr_step.hip, skr_step_fast.hip, skr_step_backward.hip and
+skr_tape.hip) of each tree with the library's own flags, the tree's PER_FILE_FLAGS included (`--save-temps -c`), splits the device assembly per kernel the way tests/test_per_sample_isa.py and tests/test_rolling_isa.py do,
 and reports symbols found in one tree only and, for each common symbol, whether its instruction lines (comments stripped, labels
 kept, numbered within their kernel), TotalNumSgprs, NumVgprs, ScratchSize or its `.amdhsa_*` descriptor lines differ, with a unified
 diff per differing symbol.
@@ -72,6 +72,7 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("old")
     ap.add_argument("new")
+    ap.add_argument("--files", nargs="+", default=list(FILES), metavar="NAME.hip", help="sources of skrample_amd/csrc to compare (default: the four step files)")
     ap.add_argument("--jobs", type=int, default=8, help="compilations at a time (at most 16)")
     ap.add_argument("--work", default=None, help="directory that keeps the assembly between runs")
     a = ap.parse_args()
@@ -80,11 +81,11 @@ def main() -> int:
     trees = {"old": os.path.abspath(a.old), "new": os.path.abspath(a.new)}
     for side in trees:
         os.makedirs(os.path.join(work, side), exist_ok=True)
-    jobs = [(side, name) for name in FILES for side in trees]
+    jobs = [(side, name) for name in a.files for side in trees]
     with ThreadPoolExecutor(max_workers=max(1, min(16, a.jobs))) as pool:
         texts = dict(zip(jobs, pool.map(lambda j: assembly(trees[j[0]], j[1], os.path.join(work, j[0]), hipcc), jobs)))
     bad = 0
-    for name in FILES:
+    for name in a.files:
         old, new = kernels(texts["old", name]), kernels(texts["new", name])
         added, removed = sorted(set(new) - set(old)), sorted(set(old) - set(new))
         differing = [k for k in sorted(set(old) & set(new)) if old[k] != new[k]]

@@ -216,7 +216,46 @@ int skr_rolling_advance(int32_t* position_dev /* [capacity] in / out */, const i
                         int32_t max_steps, void* stream);
 
 /*
- * Step programs -- a plan the library keeps, launched by handle.  Replaces the per-step host work of a REPLAYED step
+ * The masked step -- the keep-region blend of in-painting / masked image-to-image loops, fused into the step launch.  Such a loop
+ * runs, after every scheduler step,  known = add_noise(original, noise, next timestep);  latent = mask * prev + (1 - mask) * known
+ * (a step launch, an add_noise launch and three or four elementwise kernels).  Both the step and the re-noised known region are
+ * linear forms over tensor operands with host coefficients, so one launch evaluates
+ *
+ *     out[e] = m[e] * (sum_k coef0[k] * in_k[e] + zeta0 * N(seed[s(e)], stream0, e))  +  (1 - m[e]) * (sum_k coef1[k] * in_k[e])
+ *
+ * in one pass, with one store and one rounding.  Plan contract: out1_dtype must be SKR_NONE (`out` has out0_dtype); coef1 is the
+ * known-region form; chain, zeta1 and convert_* must be zero (SKR_ERR_UNSUPPORTED otherwise); sample_numel is required, with or
+ * without noise; in-kernel Philox noise (noise_mode == 1, zeta0, stream0) has the keying and block numbering of skr_step_launch; the
+ * dtype groups are those of skr_step_launch; at most SKR_ROW_TERMS operands (SKR_ERR_TERMS beyond).
+ * Arithmetic, in the accumulate type (fp32, fp64 if acc_f64):
+ *     s   the step form exactly as skr_step_launch accumulates it: operands in slot order from 0, one fma each, the noise term last
+ *         (skipped when zeta0 == 0);
+ *     k   the known form, accumulated the same way over the operands whose coef1 is not exactly zero, in slot order;
+ *     out = fma(m, s, (1 - m) * k), rounded once to out0_dtype as the step kernels round.
+ * So where m == 1 (and k is finite) `out` has the bits skr_step_launch gives for coef0 / zeta0 / stream0 alone, and where m == 0 (and s
+ * is finite) the bits it gives for coef1 as its coef0 over exactly the operands present in it, without noise.
+ * Launches of whole 2048-element chunks whose samples are whole chunks, with one 16- or 32-bit dtype for operands, mask and output,
+ * fp32 arithmetic and mask_numel % 8 == 0 take a one-trip vector kernel; everything else (ragged sizes, small samples, other
+ * mask_numel, mixed dtypes, fp64) a grid-stride per-element kernel.  The two agree bit for bit ("one_trip" 0 forces the second).
+ * Checked before the launch, without dereferencing device memory: NULL pointers SKR_ERR_NULL; mask_numel < 1, mask_numel not dividing
+ * sample_numel, sample_numel not dividing numel, or a batch_stride other than 0 or mask_numel SKR_ERR_SHAPE; a misaligned pointer
+ * SKR_ERR_ALIGN.
+ */
+typedef struct skr_step_mask {
+  const void* mask;       /* device, 16-byte aligned */
+  int32_t dtype;          /* skr_dtype of the mask: bf16 / f16 / f32 (f64 only with acc_f64) */
+  int32_t reserved;       /* 0 */
+  int64_t mask_numel;     /* elements of ONE sample's mask; must divide plan->sample_numel.
+                             Element i of a sample (i = e % sample_numel) reads mask[i % mask_numel]:
+                             (C,H,W) latents with a (1,H,W) mask -> H*W; a full mask -> sample_numel */
+  int64_t batch_stride;   /* mask_numel: one mask per sample;  0: one mask for the whole batch */
+} skr_step_mask;
+
+int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs, void* out,
+                           const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
+ * Step programs -- a plan the library keeps, launched by handle. Replaces the per-step host work of a REPLAYED step
  * (skrample/diffusers.py:565-599 redoes the whole step algebra every call; skrample_amd lowers each distinct step once,
  * sampling/program.py): the plan -- coefficients, dtypes, conversion kinds, sample size -- is handed over and validated once,
  * a launch passes only what changes from call to call: operand / output / seed pointers and the two Philox stream ids.

@@ -30,6 +30,7 @@ EXPORTS = (
     "skr_step_launch_indexed",
     "skr_step_launch_indexed_per_sample",
     "skr_step_launch_rolling",
+    "skr_step_launch_masked",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_program_create",
@@ -138,6 +139,18 @@ class StepRowC(ctypes.Structure):
         ("stream0", ctypes.c_uint64),
         ("stream1", ctypes.c_uint64),
         ("convert_k", ctypes.c_double * 4),
+    ]
+
+
+class StepMaskC(ctypes.Structure):
+    "mirror of `skr_step_mask`: the keep-region mask of a masked step launch"
+
+    _fields_ = [
+        ("mask", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("mask_numel", ctypes.c_int64),
+        ("batch_stride", ctypes.c_int64),
     ]
 
 
@@ -316,6 +329,8 @@ def load() -> ctypes.CDLL:
         for table_launch in (lib.skr_step_launch_indexed, lib.skr_step_launch_indexed_per_sample, lib.skr_step_launch_rolling):
             table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
             table_launch.restype = ctypes.c_int
+        lib.skr_step_launch_masked.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp]
+        lib.skr_step_launch_masked.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -418,3 +433,20 @@ def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, 
         current_stream_ptr(device),
     )
     check(status, "skr_step_launch")
+
+
+def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device) -> None:
+    """one masked step launch (skr_step_launch_masked) on torch's current stream of `device`: out = m * (coef0 form + noise) + (1 - m) * (coef1 form).
+    A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, mask) -- a seventh entry no step program is built from.
+    The indexed-rows hook (captured loops with device-resident scalars) has no masked form and refuses."""
+    lib = load()
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError("masked steps are not part of indexed (device-resident row) launches")
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((plan, list(operands), out, None, seeds, numel, mask))
+    n = len(operands)
+    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
+    desc = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
+    status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, numel, current_stream_ptr(device))
+    check(status, "skr_step_launch_masked")

@@ -680,6 +680,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         self._hist_sigs: list = []  # per history record: (sample dtype, model_output dtype, record.sample dtype, shape, device) -- what a replayed step binds blind
         self._run_seq = False  # every call of this run so far took the next schedule index
         self._fast_hits = 0  # steps served by _fast_step (diagnostics / tests)
+        self._inpaint = None  # (mask, original_samples, noise) while in-painting is set (set_inpaint)
 
     @classmethod
     def from_diffusers_config(
@@ -797,10 +798,45 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         idx = self._lookup(self._timestep_table(), timestep, self._index + self._calls)
         return self.sampler.scale_input(sample, Point(*self.schedule_np[idx]))
 
+    # ---- in-painting / masked image-to-image (not in the reference) ---------------------------------------------------------------
+    # The loop around a diffusers-shaped scheduler re-imposes the kept region after every step:
+    #     known  = scheduler.add_noise(original_samples, noise, next timestep);   latents = mask * prev_sample + (1 - mask) * known
+    # While a mask is set, step() returns prev_sample with that blend already applied, from the step's own launch
+    # (lazy.evaluate_masked / skr_step_launch_masked) for the samplers whose step is one single-output launch, and from one more
+    # launch behind the step for the two-output samplers (UniPC, SPC), whose state and history stay what they are.
+    def set_inpaint(self, mask: Tensor, original_samples: Tensor, noise: Tensor) -> None:
+        """blend every following step(): mask == 1 is generated, mask == 0 keeps `original_samples`, re-noised with `noise` to the
+        level of the step's target (after the last step: `original_samples` itself).  `mask` broadcasts over leading axes of the
+        latents -- (B,1,H,W), (1,1,H,W), (B,C,H,W) or (H,W) -- and is cast once to the latents' dtype (bool / uint8 accepted)."""
+        for name, t in (("mask", mask), ("original_samples", original_samples), ("noise", noise)):
+            if not isinstance(t, Tensor):
+                raise lazy.SkrampleHipError(f"set_inpaint: {name} must be a torch tensor, not {type(t).__name__}")
+        lazy._check_tensor(original_samples), lazy._check_tensor(noise)
+        if original_samples.shape != noise.shape:
+            raise lazy.SkrampleHipError(f"set_inpaint: original_samples {tuple(original_samples.shape)} and noise {tuple(noise.shape)} differ in shape")
+        lazy.mask_layout(mask.shape, original_samples.shape)  # (refused here, not at the first step)
+        mask = mask.to(device=original_samples.device, dtype=original_samples.dtype).contiguous()
+        self._inpaint = (mask, original_samples, noise)
+
+    def clear_inpaint(self) -> None:
+        "steps are plain steps again (and take the replayed fast path where they did)"
+        self._inpaint = None
+
+    def _inpaint_blend(self, idx: int, steps: int):
+        "the pending blend of the step at schedule index `idx`: the kept region at the noise level of index idx + 1 (Point.add_noise's algebra, host fp64)"
+        mask, original, noise = self._inpaint
+        if idx + 1 < steps:
+            point = Point(*self.schedule_np[idx + 1])
+            known = Lin.leaf(original) * float(point.alpha) + Lin.leaf(noise) * float(point.sigma)
+        else:
+            known = Lin.leaf(original) * 1.0
+        return lazy.MaskedBlend(known, mask)
+
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
+        inpaint = getattr(self, "_inpaint", None)
         # a step autograd records takes the general path: the replayed steps and step programs bind raw pointers (no autograd node)
         recorded = lazy.grad_recorded(model_output, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
-        if type(timestep) is float and self._fast_ids is not None and not recorded:
+        if type(timestep) is float and self._fast_ids is not None and not recorded and inpaint is None:
             done = self._fast_step(model_output, timestep, sample, generator, return_dict)
             if done is not None:
                 return done
@@ -849,7 +885,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             tuple((rec.sample is raw, getattr(rec.sample, "dtype", None)) for rec, raw in zip(self._previous, self._raw_samples)),
         )  # fmt: skip
         record = None
-        prog = self._programs.get(key) if not recorded else False
+        prog = self._programs.get(key) if not recorded and inpaint is None else False  # (a masked step: no program, no tracing)
+        blend = self._inpaint_blend(idx, len(table)) if inpaint is not None else None
         if prog is not None and prog is not False:
             record = prog.run(roles, step, prediction, sample.device)
             if record is not None and self._run_seq and (self._index, idx) not in self._fast:
@@ -859,13 +896,17 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             if tracing:
                 _hip.trace = []
             try:
-                with lazy.compute_scale(self.compute_scale):
+                # (a pending blend is taken up by a sampler whose step is one single-output launch; anything else steps as ever and its result is blended below)
+                one_launch = blend is not None and type(self.sampler).sample_packed is sampling.StatedSampler.sample_packed
+                with lazy.compute_scale(self.compute_scale), (blend if one_launch else contextlib.nullcontext()):
                     record = self.sampler.sample_packed(
                         SampleInput(sample=sample, prediction=prediction, step=step, noise=noise),
                         model_transform=self.model,
                         schedule=self.schedule,
                         previous=self._previous,
                     )
+                    if blend is not None and not blend.used:
+                        record = dataclasses.replace(record, final=blend.settle(lift(record.final), getattr(record.final, "dtype", None)))
                 if tracing:
                     built = program.StepProgram.build(_hip.trace[0], roles, record, prediction) if len(_hip.trace) == 1 else None
                     self._programs[key] = built if built is not None else False

@@ -372,6 +372,26 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
                 rest[i] = (leaf, c)
         f1 = Lin(rest, f1.shape, f1.device)
 
+    plan, operands, seeds = _lower(conv, f0, f1, chain, out_dtypes, acc_f64)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
+        if conv is not None:
+            plan_a = conversion_gradient(conv.to_kind, conv.from_kind, conv.k)
+        else:
+            plan_a = None
+        outs = _StepFunction.apply(plan, plan_a, seeds, shape, numel, device, *operands)
+        return list(outs) if f1 is not None else [outs]
+    out0 = empty_output(shape, out_dtypes[0], device)
+    out1 = empty_output(shape, out_dtypes[1], device) if f1 is not None else None
+    _hip.launch_step(plan, operands, out0, out1, seeds, numel, device)
+    return [out0] if out1 is None else [out0, out1]
+
+
+def _lower(conv, f0: "Lin", f1: "Lin | None", chain: float, out_dtypes, acc_f64: bool | None, fuse1: bool = True, max_terms: int = _hip.MAX_TERMS):
+    """Two expanded forms over one operand list -> (plan, operands, seeds): leaves merged (a tensor in both forms is ONE operand with both
+    coefficients), at most one fused Philox draw per form, operands in at most two dtype groups.  `out_dtypes` has one entry per OUTPUT:
+    evaluate() stores both forms (two entries when f1 is given), evaluate_masked() blends them into one (one entry; `fuse1` False: a
+    Philox leaf of the second form is realised to a tensor, its launch has no second draw)."""
+    shape, numel = f0.shape, math.prod(f0.shape)
     # split leaves
     tensors: dict[int, torch.Tensor] = {}
     c0: dict[int, float] = {}
@@ -393,17 +413,17 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
     # in-kernel Philox: one draw per output, fusable shapes only; the rest is realised to tensors
     noise_dtype = torch.float64 if torch.float64 in out_dtypes else torch.float32
 
-    def pick(noises):
+    def pick(noises, fuse=True):
         fused, extra = None, []
         for nz, c in noises:
-            if fused is None and nz.fusable() and nz.shape == shape:
+            if fused is None and fuse and nz.fusable() and nz.shape == shape:
                 fused = (nz, c)
             else:
                 extra.append((nz.realize(noise_dtype), c))
         return fused, extra
 
     fused0, extra0 = pick(noise0)
-    fused1, extra1 = pick(noise1)
+    fused1, extra1 = pick(noise1, fuse1)
     if fused0 is not None and fused1 is not None and fused0[0].seeds is not fused1[0].seeds:
         extra1.append((fused1[0].realize(noise_dtype), fused1[1]))
         fused1 = None
@@ -446,8 +466,8 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
         lead = [id(conv.sample), id(conv.output)]
         ids_a = lead + [i for i in ids_a if i not in lead]
     order = ids_a + ids_b
-    if len(order) > _hip.MAX_TERMS:
-        raise SkrampleHipError(f"{len(order)} operands exceed the kernel limit of {_hip.MAX_TERMS}")
+    if len(order) > max_terms:
+        raise SkrampleHipError(f"{len(order)} operands exceed the kernel limit of {max_terms}")
 
     plan = _hip.StepPlanC()
     plan.n_terms = len(order)
@@ -455,7 +475,7 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
     plan.dtype_a = _hip.DTYPE_CODE[group_a]
     plan.dtype_b = _hip.DTYPE_CODE[wide]
     plan.out0_dtype = _hip.DTYPE_CODE[out_dtypes[0]]
-    plan.out1_dtype = _hip.DTYPE_CODE[out_dtypes[1]] if f1 is not None else _hip.NONE
+    plan.out1_dtype = _hip.DTYPE_CODE[out_dtypes[1]] if len(out_dtypes) > 1 else _hip.NONE
     plan.acc_f64 = 1 if acc_f64 else 0
     for k, i in enumerate(order):
         plan.coef0[k] = c0.get(i, 0.0)
@@ -475,18 +495,112 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
             plan.zeta0, plan.stream0 = fused0[1], fused0[0].stream
         if fused1 is not None:
             plan.zeta1, plan.stream1 = fused1[1], fused1[0].stream
-    operands = [prepared[i] for i in order]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
-        if conv is not None:
-            plan_a = conversion_gradient(conv.to_kind, conv.from_kind, conv.k)
-        else:
-            plan_a = None
-        outs = _StepFunction.apply(plan, plan_a, seeds, shape, numel, device, *operands)
-        return list(outs) if f1 is not None else [outs]
-    out0 = empty_output(shape, out_dtypes[0], device)
-    out1 = empty_output(shape, out_dtypes[1], device) if f1 is not None else None
-    _hip.launch_step(plan, operands, out0, out1, seeds, numel, device)
-    return [out0] if out1 is None else [out0, out1]
+    return plan, [prepared[i] for i in order], seeds
+
+
+# ---- masked steps (in-painting): out = m * form + (1 - m) * known, one launch --------------------------------------------------------
+def mask_layout(mask_shape: Sequence[int], shape: Sequence[int]) -> tuple[int, int]:
+    """(mask_numel, batch_stride) of a mask over a (B, *sample) tensor (skr_step_mask).  The mask broadcasts over LEADING axes only:
+    behind its leading 1s (and missing axes) it spells the trailing axes of the sample out in full -- (B,1,H,W), (1,1,H,W), (B,C,H,W),
+    (H,W) over (B,C,H,W).  A batch axis of B selects one mask per sample; it is only accepted on a mask of the tensor's own rank."""
+    shape, mask_shape = tuple(shape), tuple(mask_shape)
+    refuse = f"a mask of shape {mask_shape} does not broadcast over leading axes of {shape}"
+    if len(shape) < 2 or not 1 <= len(mask_shape) <= len(shape):
+        raise SkrampleHipError(refuse)
+    full = (1,) * (len(shape) - len(mask_shape)) + mask_shape
+    if full[0] not in (1, shape[0]):
+        raise SkrampleHipError(f"{refuse}: its batch axis must be 1 or {shape[0]}")
+    inner = 1
+    while inner < len(shape) and full[inner] == 1:
+        inner += 1  # (a leading sample axis the mask is broadcast over)
+    if full[inner:] != shape[inner:]:
+        raise SkrampleHipError(f"{refuse}: behind its leading 1s it must spell out {shape[inner:]}")
+    mask_numel = math.prod(shape[inner:])
+    return mask_numel, (mask_numel if full[0] == shape[0] and shape[0] != 1 else 0)
+
+
+def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtype | None = None, acc_f64: bool | None = None) -> torch.Tensor:
+    """mask * form + (1 - mask) * known in ONE launch (skr_step_launch_masked): `form` is a solver step (it may hold one fused Philox
+    draw), `known` the re-noised kept region.  The leaves of both are merged into one operand list.  Host-resident operands evaluate
+    the same expression with torch ops in the accumulate type."""
+    f0, f1 = lift(form), lift(known)
+    if not isinstance(f0, Lin) or not isinstance(f1, Lin) or not isinstance(mask, torch.Tensor):
+        raise SkrampleHipError("evaluate_masked() takes two tensor forms and a mask tensor")
+    f0, f1 = f0.expanded(), f1.expanded()
+    if f1.shape != f0.shape:
+        raise SkrampleHipError(f"shape mismatch between the step form {f0.shape} and the known form {f1.shape}")
+    if any(isinstance(leaf, Node) for f in (f0, f1) for leaf, _ in f.terms.values()):
+        raise SkrampleHipError("a masked launch has one output: its forms cannot refer to a stored form")
+    shape, device = f0.shape, f0.device
+    _check_tensor(mask)
+    mask_numel, batch_stride = mask_layout(mask.shape, shape)
+    out_dtype = dtype if dtype is not None else _default_dtype(f0)
+    leaves = [leaf for f in (f0, f1) for leaf, _ in f.terms.values() if isinstance(leaf, torch.Tensor)]
+    if grad_recorded(mask, *leaves):
+        raise SkrampleHipError("a masked step has no backward: run it under torch.no_grad() or on operands that do not require grad")
+    if is_host(device) or is_host(f1.device):
+        return _host_evaluate_masked(f0, f1, mask, out_dtype, acc_f64)
+    if not mask.is_cuda or mask.device != device:
+        raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
+    plan, operands, seeds = _lower(None, f0, f1, 0.0, [out_dtype], acc_f64, fuse1=False, max_terms=_hip.ROW_TERMS)
+    if mask.dtype == torch.float64 and not plan.acc_f64:
+        raise SkrampleHipError("a float64 mask needs float64 accumulation")
+    numel = math.prod(shape)
+    plan.sample_numel = numel // shape[0] if shape[0] else 1
+    out = empty_output(shape, out_dtype, device)
+    _hip.launch_step_masked(plan, operands, out, _prepare_tensor(mask), mask_numel, batch_stride, seeds, numel, device)
+    return out
+
+
+# The blend a scheduler wrapper has pending for the step it is about to take (SkrampleWrapperScheduler.set_inpaint): a sampler whose step
+# is one single-output launch settles its form through it (StatedSampler.sample_packed), which makes that launch the masked one.
+_pending_blend: contextvars.ContextVar = contextvars.ContextVar("skr_pending_blend", default=None)
+
+
+class MaskedBlend:
+    "context manager: `with MaskedBlend(known, mask): sampler.sample_packed(...)`; taken up at most once"
+
+    def __init__(self, known: Lin, mask: torch.Tensor):
+        self.known, self.mask, self.used = known, mask, False
+
+    def __enter__(self):
+        self.token = _pending_blend.set(self)
+        return self
+
+    def __exit__(self, *exc):
+        _pending_blend.reset(self.token)
+
+    def settle(self, form: Lin, dtype: torch.dtype | None) -> torch.Tensor:
+        self.used = True
+        return evaluate_masked(form, self.known, self.mask, dtype)
+
+
+def pending_blend() -> "MaskedBlend | None":
+    blend = _pending_blend.get()
+    return blend if blend is not None and not blend.used else None
+
+
+def _host_evaluate_masked(f0: "Lin", f1: "Lin", mask: torch.Tensor, out_dtype: torch.dtype, acc_f64) -> torch.Tensor:
+    "host executor of evaluate_masked (CPU torch tensors): the same expression in the accumulate type, rounded once"
+    leaves = [leaf for form in (f0, f1) for leaf, _ in form.terms.values() if isinstance(leaf, torch.Tensor)]
+    for t in (*leaves, mask):
+        if t.device.type != "cpu":
+            raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
+    if f0.device == NUMPY or f1.device == NUMPY:
+        raise SkrampleHipError("masked steps take torch tensors")
+    wide = torch.float64 if acc_f64 or _compute_dtype.get() == torch.float64 or out_dtype == torch.float64 or any(t.dtype == torch.float64 for t in leaves) else torch.float32
+
+    def total(form):
+        acc = torch.zeros(form.shape, dtype=wide)
+        for leaf, c in form.terms.values():
+            if isinstance(leaf, PhiloxNoise):
+                raise SkrampleHipError("in-kernel Philox noise exists on the HIP device only")
+            if c != 0.0:
+                acc.add_(leaf.to(wide) * c)
+        return acc
+
+    m = mask.to(wide).reshape((1,) * (len(f0.shape) - mask.ndim) + tuple(mask.shape))
+    return (m * total(f0) + (1 - m) * total(f1)).to(out_dtype)
 
 
 # ---- autograd ------------------------------------------------------------------------------------------------------------------------

@@ -116,7 +116,11 @@ class StatedSampler(StructuredSampler):
         if record is not None:
             return record
         form = self._form(packed, model_transform, schedule, previous)
-        final = lazy.settle(form, dtype=_result_dtype(packed.sample))
+        blend = lazy.pending_blend()  # in-painting: the step's one launch is the masked launch (lazy.evaluate_masked)
+        if blend is not None and isinstance(form, Lin):
+            final = blend.settle(form, _result_dtype(packed.sample))
+        else:
+            final = lazy.settle(form, dtype=_result_dtype(packed.sample))
         return SKSamples(packed.sample, packed.prediction, packed.step, packed.noise, final)
 
 

@@ -431,7 +431,8 @@ int skr_power_blend(void* out, int32_t out_dtype, const void* a, int32_t a_dtype
  *     grad_a = g * p * |u|^(1/P - 1) * |a|^(P - 1),   grad_b likewise with c and b
  * evaluated as torch autograd evaluates the host expression spowf(x, f) = |x|^f * sign(x) -- the chain
  * ((g * sgn u) * (1/P) |u|^(1/P-1)) * sgn u, then (p * that * sgn a) * P |a|^(P-1) * sgn a, sgn(0) = 0 -- so that exact zeros give
- * what it gives (0, or NaN where a zero meets a negative exponent).  grad_a has a's dtype, grad_b b's; either may be NULL. */
+ * what it gives (0, or NaN where a zero meets a negative exponent).  grad_a has a's dtype, grad_b b's; either may be NULL.
+ * A 16-bit gradient is the arithmetic's value rounded once to nearest-even, from fp64 arithmetic too. */
 int skr_power_blend_backward(void* grad_a, void* grad_b, const void* g, int32_t g_dtype, const void* a, int32_t a_dtype, const void* b,
                              int32_t b_dtype, double p, double c, double power, int64_t numel, void* stream);
 

@@ -136,13 +136,26 @@ __device__ __forceinline__ float apow_dev(float x, float f) {
 }
 __device__ __forceinline__ double apow_dev(double x, double f) { return pow(fabs(x), f); }
 
+// fp32 stepping stone of a 16-bit store, rounded to odd: where v is no fp32 value the last bit is set instead of rounding to nearest,
+// so the RNE conversion that follows sees on which side of a 16-bit tie v lies and the store rounds v once (a nearest-rounded fp32
+// in between moves a value from just beside a tie onto it: half a 16-bit ULP plus 2^-25 off).  Exact for fp32 arithmetic.
+__device__ __forceinline__ float to_f32_odd(double v) {
+  float f = (float)v;
+  if ((double)f != v && v == v) {
+    uint32_t u = __float_as_uint(f);
+    if (fabs((double)f) > fabs(v)) u -= 1;  // towards zero (from inf: the largest finite value)
+    f = __uint_as_float(u | 1u);
+  }
+  return f;
+}
+
 template <typename T> __device__ __forceinline__ void blend_store(void* p, int64_t i, double v) {
   if constexpr (__is_same(T, __bf16)) {
-    float f = (float)v;
+    float f = to_f32_odd(v);
     asm("" : "+v"(f));
     reinterpret_cast<__bf16*>(p)[i] = (__bf16)f;  // RNE
   } else if constexpr (__is_same(T, _Float16)) {
-    float f = (float)v;
+    float f = to_f32_odd(v);
     asm("" : "+v"(f));
     reinterpret_cast<_Float16*>(p)[i] = (_Float16)f;
   } else {

@@ -759,6 +759,8 @@ def error_mean(a, b: torch.Tensor, power: int) -> float:
     a = _from_numpy(a) if type(a).__module__ == "numpy" and hasattr(a, "__array_interface__") and getattr(a, "ndim", 0) > 0 else a
     b = _from_numpy(b) if type(b).__module__ == "numpy" and hasattr(b, "__array_interface__") else b
     _check_tensor(b)
+    if not isinstance(a, torch.Tensor) and a != 0:
+        raise SkrampleHipError("error norm against a non-zero scalar is not supported")
     if not b.is_cuda:  # host-resident operands: plain torch (fp64 accumulation, as the kernel)
         d = (b.double() if not isinstance(a, torch.Tensor) else a.double() - b.double()).abs()
         return float((d if power == 1 else d.pow(power)).mean())
@@ -767,8 +769,6 @@ def error_mean(a, b: torch.Tensor, power: int) -> float:
         if a.dtype != b.dtype or a.shape != b.shape:
             raise SkrampleHipError("error norm operands must share dtype and shape")
         a = _prepare_tensor(a)
-    elif a != 0:
-        raise SkrampleHipError("error norm against a non-zero scalar is not supported")
     b = _prepare_tensor(b)
     ws = _norm_ws.get(b.device)
     if ws is None:
@@ -791,7 +791,7 @@ def power_blend(a: torch.Tensor, b: torch.Tensor, wa: float, wb: float, power: f
     if dtype not in (torch.float32, torch.float64):
         raise SkrampleHipError("the signed-power blend is evaluated in float32 or float64")
     if not a.is_cuda and not b.is_cuda:  # host-resident operands
-        spow = lambda v, f: v.abs().pow(f) * v.sign()  # noqa: E731
+        spow = lambda v, f: v.abs().pow(f) * torch.where(v < 0, -1.0, 1.0).to(v.dtype)  # noqa: E731  (sign(+-0) = +1, as the kernel and the reference)
         blended = spow(wa * spow(a.to(dtype), power) + wb * spow(b.to(dtype), power), 1 / power)
         return blended.numpy() if as_numpy else blended
     a, b = _prepare_tensor(a), _prepare_tensor(b)

@@ -4,7 +4,7 @@
 #include <stdint.h>
 
 #include "skr_device.h"
-#include "../../include/skrample_hip.h"
+#include "skr_launch.h"
 #include "skr_philox.h"
 #include "skr_pack.h"
 
@@ -66,17 +66,12 @@ template <typename T>
 static void launch_random(void* out, const uint64_t* seeds, uint64_t stream_id, int64_t batch, int64_t sample_numel, hipStream_t s) {
   const bool fast = sample_numel % 8 == 0 && batch <= 65535 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   if (fast) {
-    const int64_t vps = sample_numel / 8;
-    int64_t bx = (vps + 255) / 256;
-    const int64_t cap = (256 * 16 + batch - 1) / batch;  // ~16 blocks per CU over the whole grid
-    if (bx > cap) bx = cap;
+    const int64_t bx = skr::grid_blocks(sample_numel / 8, 256, (256 * 16 + batch - 1) / batch);  // ~16 blocks per CU over the whole grid
     hipLaunchKernelGGL(random_kernel_v8<T>, dim3((unsigned)bx, (unsigned)batch), dim3(256), 0, s, (T*)out, seeds, stream_id, sample_numel);
     return;
   }
   const int64_t bps = (sample_numel + 3) / 4, total = bps * batch;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(random_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (T*)out, seeds, stream_id, sample_numel, bps, total);
+  hipLaunchKernelGGL(random_kernel<T>, dim3((unsigned)skr::grid_blocks(total, 256, 256 * 16)), dim3(256), 0, s, (T*)out, seeds, stream_id, sample_numel, bps, total);
 }
 
 extern "C" int skr_noise_random(void* out, int32_t out_dtype, const uint64_t* seeds_dev, uint64_t stream_id,
@@ -86,14 +81,8 @@ extern "C" int skr_noise_random(void* out, int32_t out_dtype, const uint64_t* se
   if (batch == 0 || sample_numel == 0) return SKR_OK;
   if (!out || !seeds_dev) return SKR_ERR_NULL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (out_dtype) {
-    case SKR_BF16: launch_random<__bf16>(out, seeds_dev, stream_id, batch, sample_numel, s); break;
-    case SKR_F16: launch_random<_Float16>(out, seeds_dev, stream_id, batch, sample_numel, s); break;
-    case SKR_F32: launch_random<float>(out, seeds_dev, stream_id, batch, sample_numel, s); break;
-    case SKR_F64: launch_random<double>(out, seeds_dev, stream_id, batch, sample_numel, s); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+  const int rc = skr::with_out_type(out_dtype, [&](auto t) { launch_random<typename decltype(t)::type>(out, seeds_dev, stream_id, batch, sample_numel, s); });
+  return rc != SKR_OK ? rc : skr::launch_status();
 }
 
 // ---- Brownian increments: difference of two weighted sums of Philox normal streams ---------------------------
@@ -178,19 +167,12 @@ template <typename T>
 static void launch_brownian(void* out, const uint64_t* seeds, const BrownianArgs& a, int64_t batch, int64_t sample_numel, hipStream_t s) {
   const bool fast = sample_numel % 8 == 0 && batch <= 65535 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.cache) & 15) == 0;
   const int64_t bps = (sample_numel + 3) / 4, total = bps * batch;
-  if (fast) {
-    int64_t bx = (sample_numel / 8 + 255) / 256;
-    const int64_t cap = (256 * 16 + batch - 1) / batch;
-    if (bx > cap) bx = cap;
-    dim3 grid((unsigned)bx, (unsigned)batch);
-    if (a.from_cache) hipLaunchKernelGGL((brownian_kernel<T, true, true>), grid, dim3(256), 0, s, (T*)out, seeds, a, sample_numel, bps, total);
-    else hipLaunchKernelGGL((brownian_kernel<T, true, false>), grid, dim3(256), 0, s, (T*)out, seeds, a, sample_numel, bps, total);
-    return;
-  }
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (a.from_cache) hipLaunchKernelGGL((brownian_kernel<T, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, (T*)out, seeds, a, sample_numel, bps, total);
-  else hipLaunchKernelGGL((brownian_kernel<T, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, (T*)out, seeds, a, sample_numel, bps, total);
+  // aligned: x covers one sample's 8-element vectors, ~16 blocks per CU over the whole grid, y = sample; else a flat grid over the Philox blocks
+  const dim3 grid = fast ? dim3((unsigned)skr::grid_blocks(sample_numel / 8, 256, (256 * 16 + batch - 1) / batch), (unsigned)batch)
+                         : dim3((unsigned)skr::grid_blocks(total, 256, 256 * 16));
+  skr::with_bools([&](auto aligned, auto cached) {
+    hipLaunchKernelGGL((brownian_kernel<T, decltype(aligned)::value, decltype(cached)::value>), grid, dim3(256), 0, s, (T*)out, seeds, a, sample_numel, bps, total);
+  }, fast, a.from_cache != 0);
 }
 
 extern "C" int skr_noise_brownian(void* out, int32_t out_dtype, const uint64_t* seeds_dev, const uint64_t* stream_ids, const double* weights_to,
@@ -210,14 +192,8 @@ extern "C" int skr_noise_brownian(void* out, int32_t out_dtype, const uint64_t* 
   }
   a.cache = cache_f32; a.scale = (float)scale; a.n = n_streams; a.from_cache = from_cache ? 1 : 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (out_dtype) {
-    case SKR_BF16: launch_brownian<__bf16>(out, seeds_dev, a, batch, sample_numel, s); break;
-    case SKR_F16: launch_brownian<_Float16>(out, seeds_dev, a, batch, sample_numel, s); break;
-    case SKR_F32: launch_brownian<float>(out, seeds_dev, a, batch, sample_numel, s); break;
-    case SKR_F64: launch_brownian<double>(out, seeds_dev, a, batch, sample_numel, s); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+  const int rc = skr::with_out_type(out_dtype, [&](auto t) { launch_brownian<typename decltype(t)::type>(out, seeds_dev, a, batch, sample_numel, s); });
+  return rc != SKR_OK ? rc : skr::launch_status();
 }
 
 __global__ void philox_dump_kernel(uint32_t* out, uint64_t seed, uint64_t stream_id, uint64_t first, int64_t n) {

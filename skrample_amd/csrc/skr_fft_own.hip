@@ -32,7 +32,7 @@
 #include <tuple>
 
 #include "skr_device.h"
-#include "../../include/skrample_hip.h"
+#include "skr_launch.h"
 #include "skr_fft_tile.h"
 
 namespace skr {
@@ -669,7 +669,7 @@ int own_long_last(int dev, bool inverse, float* real, float2* spec, int64_t line
   const int64_t lines_b = lines * A, lines_a = lines * B, total = lines * h;
   const int La = tile_lines(xa, lines_a), Lb = tile_lines(xb, lines_b);
   if (total > 0x7fffffffffffll) return SKR_ERR_UNSUPPORTED;
-  int64_t blocks = (total + 255) / 256; if (blocks > 256 * 64) blocks = 256 * 64;
+  const int64_t blocks = skr::grid_blocks(total, 256, 256 * 64);
   if (!inverse) {
     if ((rc = launch_strided<false>((lines_b + Lb - 1) / Lb, xb, Lb, s, z, lines_b, (int64_t)A, xb, Lb, ilog2(Lb))) != SKR_OK) return rc;  // over b, stride A
     hipLaunchKernelGGL(own_long_twiddle, dim3((unsigned)blocks), dim3(256), 0, s, z, total, h, A, 0);

@@ -6,7 +6,7 @@
 #include <stdlib.h>
 
 #include "skr_device.h"
-#include "../../include/skrample_hip.h"
+#include "skr_launch.h"
 #include "skr_philox.h"
 #include "skr_pack.h"
 
@@ -121,16 +121,12 @@ static void launch_offset(const OffsetArgs& a, hipStream_t s) {
   const int64_t unit = a.d0 * a.d1 * a.d2 * a.d3;
   const bool fast = a.d3 % 8 == 0 && unit < (1ll << 31) && a.batch <= 65535 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
   if (fast) {
-    int64_t bx = (unit / 8 + 255) / 256;
-    const int64_t cap = (256 * 16 + a.batch - 1) / a.batch;
-    if (bx > cap) bx = cap;
+    const int64_t bx = grid_blocks(unit / 8, 256, (256 * 16 + a.batch - 1) / a.batch);
     hipLaunchKernelGGL(offset_kernel_v8<T>, dim3((unsigned)bx, (unsigned)a.batch), dim3(256), 0, s, a);
     return;
   }
   const int64_t total = ((unit + 3) / 4) * a.batch;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL(offset_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(offset_kernel<T>, dim3((unsigned)grid_blocks(total, 256, 256 * 32)), dim3(256), 0, s, a);
 }
 
 // ---- Pyramid ---------------------------------------------------------------------------------------------
@@ -776,7 +772,15 @@ __global__ __launch_bounds__(256) void pyramid_pass1_any(const PyramidAnyArgs q)
 
 }  // namespace skr
 
-static int status_of_launch() { return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH; }
+// pass 2 of both pyramid generators: the per-sample statistics of `slots` partial pairs, the division and the rounding to the output dtype
+static int normalise(void* out, int32_t out_dtype, const float* scratch_f32, const double* partials_f64, int64_t slots, int64_t unit, int64_t batch,
+                     int32_t with_base, dim3 grid, hipStream_t s) {
+  const int rc = skr::with_out_type(out_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(skr::normalise_pass2<T>, grid, dim3(256), 0, s, (T*)out, scratch_f32, partials_f64, slots, unit, batch, with_base ? -1.0 : 0.0);
+  });
+  return rc != SKR_OK ? rc : skr::launch_status();
+}
 
 extern "C" int skr_noise_offset(void* out, int32_t out_dtype, const uint64_t* seeds_dev, uint64_t stream_base, uint64_t stream_offset,
                                 int64_t batch, const int64_t* unit_shape, int32_t ndim, uint32_t keep_mask, double strength, void* stream) {
@@ -793,14 +797,8 @@ extern "C" int skr_noise_offset(void* out, int32_t out_dtype, const uint64_t* se
   a.mask = (keep_mask & ((1u << ndim) - 1u)) << (4 - ndim);
   a.gain = (float)(strength * strength);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (out_dtype) {
-    case SKR_BF16: skr::launch_offset<__bf16>(a, s); break;
-    case SKR_F16: skr::launch_offset<_Float16>(a, s); break;
-    case SKR_F32: skr::launch_offset<float>(a, s); break;
-    case SKR_F64: skr::launch_offset<double>(a, s); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return status_of_launch();
+  const int rc = skr::with_out_type(out_dtype, [&](auto t) { skr::launch_offset<typename decltype(t)::type>(a, s); });
+  return rc != SKR_OK ? rc : skr::launch_status();
 }
 
 extern "C" int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f32, double* partials_f64, int32_t* level_ws /* [batch*17] */,
@@ -857,14 +855,7 @@ extern "C" int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f3
   int64_t bx = (unit / 4 + 255) / 256;
   if (bx > 64) bx = 64;
   dim3 grid((unsigned)bx, (unsigned)batch);
-  switch (out_dtype) {
-    case SKR_BF16: hipLaunchKernelGGL(skr::normalise_pass2<__bf16>, grid, dim3(256), 0, s, (__bf16*)out, scratch_f32, partials_f64, lead, unit, batch, with_base ? -1.0 : 0.0); break;
-    case SKR_F16: hipLaunchKernelGGL(skr::normalise_pass2<_Float16>, grid, dim3(256), 0, s, (_Float16*)out, scratch_f32, partials_f64, lead, unit, batch, with_base ? -1.0 : 0.0); break;
-    case SKR_F32: hipLaunchKernelGGL(skr::normalise_pass2<float>, grid, dim3(256), 0, s, (float*)out, scratch_f32, partials_f64, lead, unit, batch, with_base ? -1.0 : 0.0); break;
-    case SKR_F64: hipLaunchKernelGGL(skr::normalise_pass2<double>, grid, dim3(256), 0, s, (double*)out, scratch_f32, partials_f64, lead, unit, batch, with_base ? -1.0 : 0.0); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return status_of_launch();
+  return normalise(out, out_dtype, scratch_f32, partials_f64, lead, unit, batch, with_base, grid, s);
 }
 
 static int pyramid_nd_impl(void* out, int32_t out_dtype, float* scratch_f32, float* levels_f32, double* partials_f64, int32_t n_slots,
@@ -906,14 +897,7 @@ static int pyramid_nd_impl(void* out, int32_t out_dtype, float* scratch_f32, flo
   if (bx > 64) bx = 64;
   if (bx < 1) bx = 1;
   dim3 grid((unsigned)bx, (unsigned)batch);
-  switch (out_dtype) {
-    case SKR_BF16: hipLaunchKernelGGL(skr::normalise_pass2<__bf16>, grid, dim3(256), 0, s, (__bf16*)out, scratch_f32, partials_f64, (int64_t)n_slots, unit, batch, with_base ? -1.0 : 0.0); break;
-    case SKR_F16: hipLaunchKernelGGL(skr::normalise_pass2<_Float16>, grid, dim3(256), 0, s, (_Float16*)out, scratch_f32, partials_f64, (int64_t)n_slots, unit, batch, with_base ? -1.0 : 0.0); break;
-    case SKR_F32: hipLaunchKernelGGL(skr::normalise_pass2<float>, grid, dim3(256), 0, s, (float*)out, scratch_f32, partials_f64, (int64_t)n_slots, unit, batch, with_base ? -1.0 : 0.0); break;
-    case SKR_F64: hipLaunchKernelGGL(skr::normalise_pass2<double>, grid, dim3(256), 0, s, (double*)out, scratch_f32, partials_f64, (int64_t)n_slots, unit, batch, with_base ? -1.0 : 0.0); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return status_of_launch();
+  return normalise(out, out_dtype, scratch_f32, partials_f64, n_slots, unit, batch, with_base, grid, s);
 }
 
 extern "C" int skr_noise_pyramid_any(void* out, int32_t out_dtype, float* scratch_f32, float* levels_f32, double* partials_f64, int32_t n_slots,

@@ -4,7 +4,7 @@
 #include <stdint.h>
 
 #include "skr_device.h"
-#include "../../include/skrample_hip.h"
+#include "skr_launch.h"
 
 namespace {
 
@@ -44,18 +44,14 @@ extern "C" int skr_error_mean(const void* a_or_null, const void* b, int32_t dtyp
   if (!b || !out_dev || !partials_dev) return SKR_ERR_NULL;
   if (numel <= 0) return SKR_ERR_SHAPE;
   if (power != 1 && power != 2) return SKR_ERR_UNSUPPORTED;
-  int64_t blocks = (numel + 255) / 256;
-  if (blocks > RED_BLOCKS) blocks = RED_BLOCKS;
+  const int64_t blocks = skr::grid_blocks(numel, 256, RED_BLOCKS);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SKR_BF16: hipLaunchKernelGGL(norm_partials<__bf16>, dim3((unsigned)blocks), dim3(256), 0, s, a_or_null, b, numel, power, partials_dev); break;
-    case SKR_F16: hipLaunchKernelGGL(norm_partials<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, a_or_null, b, numel, power, partials_dev); break;
-    case SKR_F32: hipLaunchKernelGGL(norm_partials<float>, dim3((unsigned)blocks), dim3(256), 0, s, a_or_null, b, numel, power, partials_dev); break;
-    case SKR_F64: hipLaunchKernelGGL(norm_partials<double>, dim3((unsigned)blocks), dim3(256), 0, s, a_or_null, b, numel, power, partials_dev); break;
-    default: return SKR_ERR_DTYPE;
-  }
+  const int rc = skr::with_out_type(dtype, [&](auto t) {
+    hipLaunchKernelGGL(norm_partials<typename decltype(t)::type>, dim3((unsigned)blocks), dim3(256), 0, s, a_or_null, b, numel, power, partials_dev);
+  });
+  if (rc != SKR_OK) return rc;
   hipLaunchKernelGGL(norm_final, dim3(1), dim3(64), 0, s, partials_dev, (int)blocks, numel, out_dev);
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+  return skr::launch_status();
 }
 
 // ---- signed-power blend (SPC with power != 1; reference structured.py:568-572, common.py:187-190) --------------
@@ -85,30 +81,16 @@ __global__ __launch_bounds__(256) void power_blend_kernel(M* out, const void* a,
   }
 }
 
-template <typename TA, typename M>
-static int power_blend_b(M* out, const void* a, const void* b, int32_t b_dtype, double p, double c, double power, int64_t n, hipStream_t s) {
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  const M mp = (M)p, mc = (M)c, mw = (M)power, ip = (M)(1.0 / power);
-  switch (b_dtype) {
-    case SKR_BF16: hipLaunchKernelGGL((power_blend_kernel<TA, __bf16, M>), dim3((unsigned)blocks), dim3(256), 0, s, out, a, b, mp, mc, mw, ip, n); break;
-    case SKR_F16: hipLaunchKernelGGL((power_blend_kernel<TA, _Float16, M>), dim3((unsigned)blocks), dim3(256), 0, s, out, a, b, mp, mc, mw, ip, n); break;
-    case SKR_F32: hipLaunchKernelGGL((power_blend_kernel<TA, float, M>), dim3((unsigned)blocks), dim3(256), 0, s, out, a, b, mp, mc, mw, ip, n); break;
-    case SKR_F64: hipLaunchKernelGGL((power_blend_kernel<TA, double, M>), dim3((unsigned)blocks), dim3(256), 0, s, out, a, b, mp, mc, mw, ip, n); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
-}
-
 template <typename M>
 static int power_blend_a(M* out, const void* a, int32_t a_dtype, const void* b, int32_t b_dtype, double p, double c, double power, int64_t n, hipStream_t s) {
-  switch (a_dtype) {
-    case SKR_BF16: return power_blend_b<__bf16, M>(out, a, b, b_dtype, p, c, power, n, s);
-    case SKR_F16: return power_blend_b<_Float16, M>(out, a, b, b_dtype, p, c, power, n, s);
-    case SKR_F32: return power_blend_b<float, M>(out, a, b, b_dtype, p, c, power, n, s);
-    case SKR_F64: return power_blend_b<double, M>(out, a, b, b_dtype, p, c, power, n, s);
-    default: return SKR_ERR_DTYPE;
-  }
+  const dim3 grid((unsigned)grid_blocks(n, 256, 256 * 32));
+  const M mp = (M)p, mc = (M)c, mw = (M)power, ip = (M)(1.0 / power);
+  const int rc = with_out_type(a_dtype, [&](auto ta) {
+    return with_out_type(b_dtype, [&](auto tb) {
+      hipLaunchKernelGGL((power_blend_kernel<typename decltype(ta)::type, typename decltype(tb)::type, M>), grid, dim3(256), 0, s, out, a, b, mp, mc, mw, ip, n);
+    });
+  });
+  return rc != SKR_OK ? rc : launch_status();
 }
 }  // namespace skr
 
@@ -182,32 +164,17 @@ __global__ __launch_bounds__(256) void power_blend_bwd_kernel(void* ga, void* gb
   }
 }
 
-template <typename TA, typename M>
-static int power_blend_bwd_b(void* ga, void* gb, const M* g, const void* a, const void* b, int32_t b_dtype, double p, double c, double power, int64_t n,
-                             hipStream_t s) {
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  const M mp = (M)p, mc = (M)c, mw = (M)power, ip = (M)(1.0 / power);
-  switch (b_dtype) {
-    case SKR_BF16: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, __bf16, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
-    case SKR_F16: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, _Float16, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
-    case SKR_F32: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, float, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
-    case SKR_F64: hipLaunchKernelGGL((power_blend_bwd_kernel<TA, double, M>), dim3((unsigned)blocks), dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n); break;
-    default: return SKR_ERR_DTYPE;
-  }
-  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
-}
-
 template <typename M>
 static int power_blend_bwd_a(void* ga, void* gb, const M* g, const void* a, int32_t a_dtype, const void* b, int32_t b_dtype, double p, double c, double power,
                              int64_t n, hipStream_t s) {
-  switch (a_dtype) {
-    case SKR_BF16: return power_blend_bwd_b<__bf16, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
-    case SKR_F16: return power_blend_bwd_b<_Float16, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
-    case SKR_F32: return power_blend_bwd_b<float, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
-    case SKR_F64: return power_blend_bwd_b<double, M>(ga, gb, g, a, b, b_dtype, p, c, power, n, s);
-    default: return SKR_ERR_DTYPE;
-  }
+  const dim3 grid((unsigned)grid_blocks(n, 256, 256 * 32));
+  const M mp = (M)p, mc = (M)c, mw = (M)power, ip = (M)(1.0 / power);
+  const int rc = with_out_type(a_dtype, [&](auto ta) {
+    return with_out_type(b_dtype, [&](auto tb) {
+      hipLaunchKernelGGL((power_blend_bwd_kernel<typename decltype(ta)::type, typename decltype(tb)::type, M>), grid, dim3(256), 0, s, ga, gb, g, a, b, mp, mc, mw, ip, n);
+    });
+  });
+  return rc != SKR_OK ? rc : launch_status();
 }
 }  // namespace skr
 

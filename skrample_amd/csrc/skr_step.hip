@@ -317,10 +317,8 @@ static Geometry geometry(int64_t numel, int64_t sample_numel) {
     const int64_t gz = (batch + gy - 1) / gy;
     if (gy * gz == batch) return {dim3((unsigned)bx, (unsigned)gy, (unsigned)gz), 1};
   }
-  int64_t blocks = (nvec + per_block - 1) / per_block;
-  const int64_t cap = NOISE ? 256 * 32 : 256 * 4;  // grid-stride beyond: 4 blocks per CU (32 with Philox)
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+  int64_t blocks = grid_blocks(nvec, per_block, NOISE ? 256 * 32 : 256 * 4);  // grid-stride beyond: 4 blocks per CU (32 with Philox)
+  if (blocks < 1) blocks = 1;  // (fewer than 8 elements: the block of the ragged tail)
   return {dim3((unsigned)blocks, 1, 1), 0};
 }
 
@@ -450,64 +448,44 @@ static int launch(StepArgs<Acc>& args, hipStream_t stream) {
   });
 }
 
-template <typename TA, typename TB, typename TO0, typename TO1, typename Acc>
-static int pick_flags(StepArgs<Acc>& a, bool st0, bool has1, bool noise, bool conv, hipStream_t s) {
-#define SKR_GO(ST0, HAS1, NOISE, CONV) return launch<TA, TB, TO0, TO1, Acc, ST0, HAS1, NOISE, CONV>(a, s)
-  if (!has1) {
-    if (!st0 || conv) return conv ? SKR_ERR_UNSUPPORTED : SKR_ERR_NULL;
-    if (noise) SKR_GO(true, false, true, false);
-    SKR_GO(true, false, false, false);
-  }
-  if (conv) {
-    if (st0) { if (noise) SKR_GO(true, true, true, true); SKR_GO(true, true, false, true); }
-    if (noise) SKR_GO(false, true, true, true);
-    SKR_GO(false, true, false, true);
-  }
-  if (st0) { if (noise) SKR_GO(true, true, true, false); SKR_GO(true, true, false, false); }
-  if (noise) SKR_GO(false, true, true, false);
-  SKR_GO(false, true, false, false);
-#undef SKR_GO
-}
-
-// outputs: each of out0/out1 is either the group-A dtype or fp32 (fp64 when accumulating in double)
-template <typename TA, typename TB, typename Acc>
-static int pick_out(StepArgs<Acc>& a, int dt_a, int o0, int o1, bool noise, bool conv, hipStream_t s) {
-  using Wide = typename std::conditional<std::is_same<Acc, double>::value, double, float>::type;
-  const int wide = std::is_same<Acc, double>::value ? SKR_F64 : SKR_F32;
-  const bool st0 = o0 != SKR_NONE, has1 = o1 != SKR_NONE;
-  const int e0 = st0 ? o0 : dt_a, e1 = has1 ? o1 : dt_a;
-  if ((e0 != dt_a && e0 != wide) || (e1 != dt_a && e1 != wide)) return SKR_ERR_DTYPE;
-  if (e0 == dt_a && e1 == dt_a) return pick_flags<TA, TB, TA, TA, Acc>(a, st0, has1, noise, conv, s);
-  if (e0 == wide && e1 == dt_a) return pick_flags<TA, TB, Wide, TA, Acc>(a, st0, has1, noise, conv, s);
-  if (e0 == dt_a && e1 == wide) return pick_flags<TA, TB, TA, Wide, Acc>(a, st0, has1, noise, conv, s);
-  return pick_flags<TA, TB, Wide, Wide, Acc>(a, st0, has1, noise, conv, s);
-}
-
 // a launch of this plan draws noise by the plan's own scalars (table launches: whether a draw happens is the row's business -- a zero
 // zeta skips it at run time -- so every noise_mode 1 launch of theirs counts as drawing)
 static bool plan_draws(const skr_step_plan& p) { return p.noise_mode == 1 && (p.zeta0 != 0.0 || (p.out1_dtype != SKR_NONE && p.zeta1 != 0.0)); }
 
+// no kernel exists without an output, or with a conversion and no out1: asked at run time for the status and at compile time for the instantiations
+constexpr bool no_kernel(bool st0, bool has1, bool conv) { return !has1 && (!st0 || conv); }
+
+template <typename TA, typename TB, typename TO0, typename TO1, typename Acc>
+static int pick_flags(StepArgs<Acc>& a, bool st0, bool has1, bool noise, bool conv, hipStream_t s) {
+  if (no_kernel(st0, has1, conv)) return conv ? SKR_ERR_UNSUPPORTED : SKR_ERR_NULL;
+  return with_bools([&](auto c_st0, auto c_has1, auto c_noise, auto c_conv) -> int {
+    if constexpr (no_kernel(c_st0, c_has1, c_conv)) return SKR_ERR_UNSUPPORTED;  // (returned above)
+    else return launch<TA, TB, TO0, TO1, Acc, c_st0, c_has1, c_noise, c_conv>(a, s);
+  }, st0, has1, noise, conv);
+}
+
+// The one place that maps a plan's dtypes to the element types of a general kernel.  What the rule of
+// skr_step_common.h admits becomes (TA, TB): group b's own type is that of fp32 operands beside 16-bit ones, and every fp64-arithmetic
+// kernel reads group b as fp64 (16-bit latents under compute_scale=float64, skrample/diffusers.py:575-579, are widened exactly, summed in
+// double and rounded once).  Each output is TA or the wide type Acc; one that is not stored counts as TA.
 template <typename Acc>
-static int pick_in(StepArgs<Acc>& a, const skr_step_plan& p, hipStream_t s) {
+static int pick(StepArgs<Acc>& a, const skr_step_plan& p, hipStream_t s) {
+  constexpr bool F64 = std::is_same<Acc, double>::value;
   const bool noise = p.noise_mode == 1 && (has_table(a.form) || plan_draws(p));
   const int da = p.dtype_a, db = (p.n_group_a == p.n_terms) ? p.dtype_a : p.dtype_b;
   const bool conv = p.convert_to != 0 || p.convert_from != 0;
-  if constexpr (std::is_same<Acc, double>::value) {
-    if (da == SKR_F64 && db == SKR_F64) return pick_out<double, double, double>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    if (da == SKR_F32 && (db == SKR_F32 || db == SKR_F64)) return pick_out<float, double, double>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    // 16-bit latents under compute_scale=float64 (skrample/diffusers.py:575-579 casts whatever it is handed): widened exactly, accumulated in
-    // double, rounded once to the 16-bit result (or kept as fp64 state)
-    if (da == SKR_BF16 && (db == SKR_BF16 || db == SKR_F64)) return pick_out<bf16_t, double, double>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    if (da == SKR_F16 && (db == SKR_F16 || db == SKR_F64)) return pick_out<f16_t, double, double>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    return SKR_ERR_DTYPE;
-  } else {
-    if (da == SKR_BF16 && db == SKR_BF16) return pick_out<bf16_t, bf16_t, float>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    if (da == SKR_BF16 && db == SKR_F32) return pick_out<bf16_t, float, float>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    if (da == SKR_F16 && db == SKR_F16) return pick_out<f16_t, f16_t, float>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    if (da == SKR_F16 && db == SKR_F32) return pick_out<f16_t, float, float>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    if (da == SKR_F32 && db == SKR_F32) return pick_out<float, float, float>(a, da, p.out0_dtype, p.out1_dtype, noise, conv, s);
-    return SKR_ERR_DTYPE;
-  }
+  const bool st0 = p.out0_dtype != SKR_NONE, has1 = p.out1_dtype != SKR_NONE;
+  if (!step_inputs_ok(da, db, F64)) return SKR_ERR_DTYPE;
+  if ((st0 && !step_output_ok(p.out0_dtype, da, F64)) || (has1 && !step_output_ok(p.out1_dtype, da, F64))) return SKR_ERR_DTYPE;
+  return with_step_type<F64>(da, [&](auto ta) {
+    using TA = typename decltype(ta)::type;
+    return with_bools([&](auto b_wide, auto wide0, auto wide1) -> int {
+      using TB = std::conditional_t<F64 || b_wide, Acc, TA>;
+      using TO0 = std::conditional_t<wide0, Acc, TA>;
+      using TO1 = std::conditional_t<wide1, Acc, TA>;
+      return pick_flags<TA, TB, TO0, TO1, Acc>(a, st0, has1, noise, conv, s);
+    }, !F64 && db != da, st0 && p.out0_dtype != da, has1 && p.out1_dtype != da);
+  });
 }
 
 template <typename Acc>
@@ -533,12 +511,12 @@ static int run(const skr_step_plan& p, const void* const* inputs, void* out0, vo
   if (a.conv_to != 0 || a.conv_from != 0) {
     for (int k = 0; k < p.n_terms; ++k) a.c0[k] = 0;  // out0 is the conversion alone
   }
-  return pick_in<Acc>(a, p, s);
+  return pick<Acc>(a, p, s);
 }
 
 }  // namespace skr
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+using skr::aligned16;
 
 // a sample size that divides the launch into samples made of whole `multiple`s of elements
 static int samples_ok(const skr_step_plan& p, int64_t numel, int64_t multiple) {
@@ -571,10 +549,7 @@ static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs
   if (numel == 0) return SKR_OK;  // empty batch: nothing to do (the reference returns empty tensors)
   const bool st0 = p.out0_dtype != SKR_NONE, has1 = p.out1_dtype != SKR_NONE;
   if ((p.n_terms > 0 && !inputs) || (st0 && !out0) || (has1 && !out1)) return SKR_ERR_NULL;
-  for (int k = 0; k < p.n_terms; ++k) {
-    if (!inputs[k]) return SKR_ERR_NULL;
-    if (!aligned16(inputs[k])) return SKR_ERR_ALIGN;
-  }
+  if (const int rc = skr::check_ptrs(inputs, p.n_terms)) return rc;
   if ((st0 && !aligned16(out0)) || (has1 && !aligned16(out1))) return SKR_ERR_ALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (has_table(form)) {

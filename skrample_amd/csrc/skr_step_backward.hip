@@ -60,17 +60,8 @@ struct BwdArgs {
   int32_t n, n_a, dt_a, dt_b, dt_g0, dt_g1;
 };
 
-template <typename Acc> __device__ __forceinline__ Acc load_any(const void* base, int64_t i, int dt) {
-  switch (dt) {
-    case SKR_BF16: return (Acc)load_scalar<bf16_t>(base, i);
-    case SKR_F16: return (Acc)load_scalar<f16_t>(base, i);
-    case SKR_F32: return (Acc)load_scalar<float>(base, i);
-    default: return (Acc)reinterpret_cast<const double*>(base)[i];
-  }
-}
-
 // one rounding from Acc; the same conversions as store8 (fp32 -> 16-bit: RNE of the fp32 value, pinned so that no fused
-// multiply-add-and-convert rounds the exact sum instead)
+// multiply-add-and-convert rounds the exact sum instead).  The same function as store_elem of skr_step_masked.hip, kept apart: see there.
 template <typename Acc> __device__ __forceinline__ void store_any(void* base, int64_t i, int dt, Acc v) {
   switch (dt) {
     case SKR_BF16: {
@@ -93,9 +84,9 @@ template <typename Acc> __device__ __forceinline__ void store_any(void* base, in
 template <typename Acc, bool HAS1>
 __global__ __launch_bounds__(BLOCK) void step_bwd_general(const BwdArgs p) {
   for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < p.numel; e += (int64_t)gridDim.x * BLOCK) {
-    const Acc x0 = load_any<Acc>(p.g0, e, p.dt_g0);
+    const Acc x0 = load_elem<Acc, true>(p.g0, e, p.dt_g0);
     Acc x1 = 0;
-    if constexpr (HAS1) x1 = load_any<Acc>(p.g1, e, p.dt_g1);
+    if constexpr (HAS1) x1 = load_elem<Acc, true>(p.g1, e, p.dt_g1);
     for (int j = 0; j < p.n; ++j) {
       const Acc aj = (Acc)p.a[j];
       const Acc o = HAS1 ? fma_((Acc)p.b[j], x1, mul_(aj, x0)) : mul_(aj, x0);
@@ -117,12 +108,12 @@ static void launch_bwd_k1(const skr_step_grad_plan& pl, const void* g0, const vo
   hipLaunchKernelGGL((step_bwd_k1<T, KMAX, HAS1>), dim3((unsigned)chunks), dim3(BLOCK), 0, s, p);
 }
 
-template <typename T>
-static void launch_bwd_k1_t(const skr_step_grad_plan& pl, const void* g0, const void* g1, void* const* grads, int64_t chunks, hipStream_t s) {
-  const bool has1 = g1 != nullptr;
-  if (pl.n_grads <= 4) has1 ? launch_bwd_k1<T, 4, true>(pl, g0, g1, grads, chunks, s) : launch_bwd_k1<T, 4, false>(pl, g0, g1, grads, chunks, s);
-  else if (pl.n_grads <= 8) has1 ? launch_bwd_k1<T, 8, true>(pl, g0, g1, grads, chunks, s) : launch_bwd_k1<T, 8, false>(pl, g0, g1, grads, chunks, s);
-  else has1 ? launch_bwd_k1<T, 16, true>(pl, g0, g1, grads, chunks, s) : launch_bwd_k1<T, 16, false>(pl, g0, g1, grads, chunks, s);
+// kernarg slots of the one-trip kernel: 4, 8 or 16
+template <typename F>
+static void with_bwd_slots(int n, F&& f) {
+  if (n <= 4) f(std::integral_constant<int, 4>{});
+  else if (n <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
 }
 
 static bool valid_dtype(int32_t d) { return d == SKR_BF16 || d == SKR_F16 || d == SKR_F32 || d == SKR_F64; }
@@ -143,21 +134,19 @@ extern "C" int skr_step_backward_launch(const skr_step_grad_plan* plan, const vo
     return SKR_ERR_DTYPE;
   if (numel == 0) return SKR_OK;
   if (!g0 || (has1 != (g1 != nullptr))) return SKR_ERR_NULL;
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-  if (!aligned(g0) || (has1 && !aligned(g1))) return SKR_ERR_ALIGN;
-  for (int k = 0; k < p.n_grads; ++k) {
-    if (!grads[k]) return SKR_ERR_NULL;
-    if (!aligned(grads[k])) return SKR_ERR_ALIGN;
-  }
+  if (!aligned16(g0) || (has1 && !aligned16(g1))) return SKR_ERR_ALIGN;
+  if (const int rc = check_ptrs(grads, p.n_grads)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
   const int32_t t = p.dtype_a;
   const bool one_dtype = (p.n_group_a == p.n_grads || p.dtype_b == t) && p.g0_dtype == t && (!has1 || p.g1_dtype == t);
   if (g_tune.one_trip && !p.acc_f64 && one_dtype && t != SKR_F64 && p.n_grads <= 16 && numel % CHUNK == 0 && numel / CHUNK <= 0x7fffffffll) {
     const int64_t chunks = numel / CHUNK;
-    if (t == SKR_BF16) launch_bwd_k1_t<bf16_t>(p, g0, g1, grads, chunks, s);
-    else if (t == SKR_F16) launch_bwd_k1_t<f16_t>(p, g0, g1, grads, chunks, s);
-    else launch_bwd_k1_t<float>(p, g0, g1, grads, chunks, s);
+    with_step_type<false>(t, [&](auto tt) {
+      with_bwd_slots(p.n_grads, [&](auto kmax) {
+        with_bools([&](auto h1) { launch_bwd_k1<typename decltype(tt)::type, decltype(kmax)::value, decltype(h1)::value>(p, g0, g1, grads, chunks, s); }, has1);
+      });
+    });
     return finish_launch();
   }
   BwdArgs a;
@@ -170,14 +159,9 @@ extern "C" int skr_step_backward_launch(const skr_step_grad_plan* plan, const vo
   }
   a.g0 = g0; a.g1 = g1; a.numel = numel; a.n = p.n_grads; a.n_a = p.n_group_a;
   a.dt_a = p.dtype_a; a.dt_b = p.dtype_b; a.dt_g0 = p.g0_dtype; a.dt_g1 = p.g1_dtype;
-  int64_t blocks = (numel + BLOCK - 1) / BLOCK;
-  if (blocks > 256 * 64) blocks = 256 * 64;
-  if (p.acc_f64) {
-    if (has1) hipLaunchKernelGGL((step_bwd_general<double, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((step_bwd_general<double, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-  } else {
-    if (has1) hipLaunchKernelGGL((step_bwd_general<float, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((step_bwd_general<float, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-  }
+  const dim3 grid((unsigned)grid_blocks(numel, BLOCK, 256 * 64));
+  with_bools([&](auto f64, auto h1) {
+    hipLaunchKernelGGL((step_bwd_general<std::conditional_t<decltype(f64)::value, double, float>, decltype(h1)::value>), grid, dim3(BLOCK), 0, s, a);
+  }, p.acc_f64 != 0, has1);
   return finish_launch();
 }

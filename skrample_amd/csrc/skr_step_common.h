@@ -9,7 +9,7 @@
 #include "../../include/skrample_hip.h"
 #include "skr_philox.h"
 #include "skr_pack.h"
-#include "skr_launch.h"  // type_tag
+#include "skr_launch.h"  // type_tag, bool_c, with_dtype
 
 namespace skr {
 
@@ -43,6 +43,20 @@ constexpr int MAXK = SKR_MAX_TERMS;
 
 struct bf16_t { uint16_t v; };
 struct f16_t { _Float16 v; };
+
+// The step kernels' element types for a dtype code (skr_launch.h, with_dtype), and THE rule of which dtypes one step combines
+// (skr_step_launch and skr_step_launch_masked both ask it): with `wide` the dtype of the arithmetic -- fp32, or
+// fp64 under acc_f64 -- group a is bf16, f16, fp32 or, in fp64 arithmetic, fp64; group b has group a's dtype or the wide one; an output too.
+struct StepTypes { using bf16 = bf16_t; using f16 = f16_t; };
+template <bool WITH_F64 = true, typename F>
+static inline int with_step_type(int32_t dtype, F&& f) { return with_dtype<StepTypes, WITH_F64>(dtype, f); }
+
+constexpr int32_t wide_dtype(bool acc_f64) { return acc_f64 ? SKR_F64 : SKR_F32; }
+static inline bool step_inputs_ok(int32_t dtype_a, int32_t dtype_b, bool acc_f64) {
+  const bool a_ok = dtype_a == SKR_BF16 || dtype_a == SKR_F16 || dtype_a == SKR_F32 || (acc_f64 && dtype_a == SKR_F64);
+  return a_ok && (dtype_b == dtype_a || dtype_b == wide_dtype(acc_f64));
+}
+static inline bool step_output_ok(int32_t out_dtype, int32_t dtype_a, bool acc_f64) { return out_dtype == dtype_a || out_dtype == wide_dtype(acc_f64); }
 
 // Where a launch gets its scalars (coefficients, zetas, Philox streams, conversion constants) from:
 //   Kernarg     the plan's values, packed into the kernarg                                      skr_step_launch
@@ -269,6 +283,27 @@ __device__ __forceinline__ void store_scalar(void* base, int64_t i, Acc v) {
   else reinterpret_cast<T*>(base)[i] = (T)v;
 }
 
+// ---- per-element load with a run-time dtype (the general kernels of skr_step_masked.hip and skr_step_backward.hip) -------------------
+// (their stores stay apart: one shared body changes the instructions of one kernel or the other)
+// WITH_F64 = false: no fp64 tensor reaches the kernel (every other code reads as fp32)
+template <typename Acc, bool WITH_F64>
+__device__ __forceinline__ Acc load_elem(const void* base, int64_t i, int dt) {
+  if constexpr (WITH_F64) {
+    switch (dt) {
+      case SKR_BF16: return (Acc)load_scalar<bf16_t>(base, i);
+      case SKR_F16: return (Acc)load_scalar<f16_t>(base, i);
+      case SKR_F32: return (Acc)load_scalar<float>(base, i);
+      default: return (Acc)reinterpret_cast<const double*>(base)[i];
+    }
+  } else {
+    switch (dt) {
+      case SKR_BF16: return (Acc)load_scalar<bf16_t>(base, i);
+      case SKR_F16: return (Acc)load_scalar<f16_t>(base, i);
+      default: return (Acc)load_scalar<float>(base, i);
+    }
+  }
+}
+
 // ---- rounded pair conversion (Runge-Kutta wrapper) ---------------------------------------------------
 // The reference's RK wrapper converts the network output to derivative space in the INPUT dtype,
 // one rounded tensor op at a time, before any cast to compute_scale (skrample/diffusers.py:819-834 with
@@ -370,8 +405,6 @@ extern thread_local int g_last_hip_error;
 int finish_launch();
 
 // ---- host side: run-time values to template arguments, kernarg packing -------------------------------------------------------------
-template <bool B> using bool_c = std::integral_constant<bool, B>;
-
 // calls f(std::integral_constant<int, N>{}) for the N of LO..HI that equals n, and nothing for an n outside
 template <int LO, int HI, typename F>
 static inline void with_count(int n, F&& f) {

@@ -706,6 +706,23 @@ static int launch_k2_as(const StepArgs<float>& args, bool noise, int bps_shift, 
   return launch_k2<TA, NA, NB, false, false, TABLE>(args, bps_shift, stream);
 }
 
+// The operand counts the samplers emit (tools/trace_plans.py): UniPC / SPC of order n give 2n+2 (+2 with a noise tensor) 16-bit operands
+// and the previous corrected state in fp32; their first steps have no fp32 operand yet.  From order 5 on (12 + 1 operands and more)
+// nothing was tuned.
+template <int NA, int NB, bool TUNED> struct TwoOut { static constexpr int na = NA, nb = NB; static constexpr bool tuned = TUNED; };
+template <typename... C> struct TwoOutList {};
+using TwoOutCounts = TwoOutList<TwoOut<2, 0, true>, TwoOut<3, 0, true>, TwoOut<4, 0, true>, TwoOut<4, 1, true>, TwoOut<6, 1, true>, TwoOut<7, 1, true>, TwoOut<8, 1, true>,
+                                TwoOut<10, 1, true>, TwoOut<12, 1, false>, TwoOut<14, 1, false>, TwoOut<16, 1, false>, TwoOut<18, 1, false>, TwoOut<20, 1, false>,
+                                TwoOut<22, 1, false>>;
+
+// launches the first entry of the list that has these operand counts (`taken`); none: SKR_OK, nothing launched
+template <typename TA, typename... C>
+static int launch_k2_of(TwoOutList<C...>, int na, int nb, const StepArgs<float>& args, bool noise, int bps_shift, hipStream_t stream, bool& taken) {
+  int rc = SKR_OK;
+  (void)((na == C::na && nb == C::nb && (taken = true, rc = launch_k2_as<TA, C::na, C::nb, C::tuned>(args, noise, bps_shift, stream), true)) || ...);
+  return rc;
+}
+
 template <typename TA>
 int launch_one_trip_two(const StepArgs<float>& args, bool noise, bool group_b_f32, hipStream_t stream, bool& taken) {
   taken = false;
@@ -717,14 +734,7 @@ int launch_one_trip_two(const StepArgs<float>& args, bool noise, bool group_b_f3
   if (noise && na + nb <= 7 && g_tune.two_out != 2 && !table) return SKR_OK;
   int bps_shift = 0;
   if (!one_trip_ok(args.numel, args.sample_numel, noise, args.form, &bps_shift)) return SKR_OK;
-  // the operand counts the samplers emit (tools/trace_plans.py): UniPC / SPC of order n give 2n+2 (+2 with a noise
-  // tensor) 16-bit operands and the previous corrected state in fp32; their first steps have no fp32 operand yet.
-  // From order 5 on (12 + 1 operands and more) nothing was tuned.
-#define SKR_GO(A, B, TUNED) if (na == A && nb == B) { taken = true; return launch_k2_as<TA, A, B, TUNED>(args, noise, bps_shift, stream); }
-  SKR_GO(2, 0, true) SKR_GO(3, 0, true) SKR_GO(4, 0, true) SKR_GO(4, 1, true) SKR_GO(6, 1, true) SKR_GO(7, 1, true) SKR_GO(8, 1, true) SKR_GO(10, 1, true)
-  SKR_GO(12, 1, false) SKR_GO(14, 1, false) SKR_GO(16, 1, false) SKR_GO(18, 1, false) SKR_GO(20, 1, false) SKR_GO(22, 1, false)
-#undef SKR_GO
-  return SKR_OK;
+  return launch_k2_of<TA>(TwoOutCounts{}, na, nb, args, noise, bps_shift, stream, taken);
 }
 template int launch_one_trip_two<bf16_t>(const StepArgs<float>&, bool, bool, hipStream_t, bool&);
 template int launch_one_trip_two<f16_t>(const StepArgs<float>&, bool, bool, hipStream_t, bool&);

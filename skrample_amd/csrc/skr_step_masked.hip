@@ -123,25 +123,9 @@ struct MaskedGenArgs {
   int32_t n, n_a, dt_a, dt_b, dt_out, dt_mask, noise;
 };
 
-template <typename Acc> __device__ __forceinline__ Acc load_elem(const void* base, int64_t i, int dt) {
-  if constexpr (std::is_same<Acc, double>::value) {
-    switch (dt) {
-      case SKR_BF16: return load_scalar_d<bf16_t>(base, i);
-      case SKR_F16: return load_scalar_d<f16_t>(base, i);
-      case SKR_F32: return load_scalar_d<float>(base, i);
-      default: return load_scalar_d<double>(base, i);
-    }
-  } else {
-    switch (dt) {
-      case SKR_BF16: return load_scalar<bf16_t>(base, i);
-      case SKR_F16: return load_scalar<f16_t>(base, i);
-      default: return load_scalar<float>(base, i);
-    }
-  }
-}
-
 // one rounding from Acc, the conversions of store8 (to a 16-bit dtype through the fp32 value, pinned in a register so that no fused
-// multiply-add-and-convert rounds the exact sum instead)
+// multiply-add-and-convert rounds the exact sum instead).  The same function as store_any of skr_step_backward.hip, kept apart: either
+// body, used by both general kernels, changes the instructions of the other one.
 template <typename Acc> __device__ __forceinline__ void store_elem(void* base, int64_t i, int dt, Acc v) {
   if (dt == SKR_BF16 || dt == SKR_F16) {
     float f = (float)v;
@@ -157,12 +141,13 @@ template <typename Acc> __device__ __forceinline__ void store_elem(void* base, i
 
 template <typename Acc>
 __global__ __launch_bounds__(BLOCK) void masked_kernel_gen(const MaskedGenArgs a) {
+  constexpr bool F64 = std::is_same<Acc, double>::value;  // (an fp64 tensor takes part in fp64 arithmetic only)
   for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < a.numel; e += (int64_t)gridDim.x * BLOCK) {
     const int64_t smp = e / a.sample_numel, r = e - smp * a.sample_numel;
-    const Acc m = load_elem<Acc>(a.mask, smp * a.mask_stride + r % a.mask_numel, a.dt_mask);
+    const Acc m = load_elem<Acc, F64>(a.mask, smp * a.mask_stride + r % a.mask_numel, a.dt_mask);
     Acc s = 0, kn = 0;
     for (int j = 0; j < a.n; ++j) {
-      const Acc x = load_elem<Acc>(a.in[j], e, j < a.n_a ? a.dt_a : a.dt_b);
+      const Acc x = load_elem<Acc, F64>(a.in[j], e, j < a.n_a ? a.dt_a : a.dt_b);
       const Acc w0 = (Acc)a.c0[j], w1 = (Acc)a.c1[j];
       s = fma_(w0, x, s);
       if (w1 != (Acc)0) kn = fma_(w1, x, kn);
@@ -197,25 +182,6 @@ static void launch_masked_v1(const skr_step_plan& p, const void* const* inputs, 
   });
 }
 
-template <typename T>
-static void launch_masked_v1_t(const skr_step_plan& p, const void* const* inputs, void* out, const skr_step_mask& mk, const uint64_t* seeds,
-                               bool noise, int64_t chunks, int bps_shift, hipStream_t s) {
-  if (noise) launch_masked_v1<T, true>(p, inputs, out, mk, seeds, chunks, bps_shift, s);
-  else launch_masked_v1<T, false>(p, inputs, out, mk, seeds, chunks, bps_shift, s);
-}
-
-// the dtype combinations of skr_step_launch (pick_in / pick_out of skr_step.hip), with one output
-static int masked_dtypes_ok(const skr_step_plan& p, int mask_dtype) {
-  const int da = p.dtype_a, db = (p.n_group_a == p.n_terms) ? p.dtype_a : p.dtype_b;
-  const int wide = p.acc_f64 ? SKR_F64 : SKR_F32;
-  bool ok;
-  if (p.acc_f64) ok = (da == SKR_F64 && db == SKR_F64) || ((da == SKR_F32 || da == SKR_BF16 || da == SKR_F16) && (db == da || db == SKR_F64));
-  else ok = ((da == SKR_BF16 || da == SKR_F16) && (db == da || db == SKR_F32)) || (da == SKR_F32 && db == SKR_F32);
-  if (!ok || (p.out0_dtype != da && p.out0_dtype != wide)) return SKR_ERR_DTYPE;
-  if (mask_dtype != SKR_BF16 && mask_dtype != SKR_F16 && mask_dtype != SKR_F32 && !(mask_dtype == SKR_F64 && p.acc_f64)) return SKR_ERR_DTYPE;
-  return SKR_OK;
-}
-
 }  // namespace skr
 
 extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_mask* mask,
@@ -234,15 +200,14 @@ extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* con
   if (mk.mask_numel < 1 || p.sample_numel % mk.mask_numel != 0 || (mk.batch_stride != 0 && mk.batch_stride != mk.mask_numel)) return SKR_ERR_SHAPE;
   const bool noise = p.noise_mode == 1 && p.zeta0 != 0.0;
   if (noise && p.sample_numel % 8 != 0) return SKR_ERR_UNSUPPORTED;  // fused Philox needs every 8-element group inside one sample, as in skr_step_launch
-  if (const int rc = masked_dtypes_ok(p, mk.dtype)) return rc;
+  // the dtype combinations of skr_step_launch, with one output; the mask: a 16-bit dtype or the arithmetic's
+  const int32_t db = p.n_group_a == p.n_terms ? p.dtype_a : p.dtype_b;
+  if (!step_inputs_ok(p.dtype_a, db, p.acc_f64) || !step_output_ok(p.out0_dtype, p.dtype_a, p.acc_f64)) return SKR_ERR_DTYPE;
+  if (mk.dtype != SKR_BF16 && mk.dtype != SKR_F16 && mk.dtype != SKR_F32 && !(mk.dtype == SKR_F64 && p.acc_f64)) return SKR_ERR_DTYPE;
   if (numel == 0) return SKR_OK;
   if ((p.n_terms > 0 && !inputs) || !out || !mk.mask || (noise && !seeds_dev)) return SKR_ERR_NULL;
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-  for (int k = 0; k < p.n_terms; ++k) {
-    if (!inputs[k]) return SKR_ERR_NULL;
-    if (!aligned(inputs[k])) return SKR_ERR_ALIGN;
-  }
-  if (!aligned(out) || !aligned(mk.mask)) return SKR_ERR_ALIGN;
+  if (const int rc = check_ptrs(inputs, p.n_terms)) return rc;
+  if (!aligned16(out) || !aligned16(mk.mask)) return SKR_ERR_ALIGN;
   DeviceGuard device_guard(out);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 
@@ -255,9 +220,9 @@ extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* con
     int bps_shift = 0;
     if ((bps & (bps - 1)) == 0) { while ((1ll << bps_shift) < bps) ++bps_shift; }
     else bps_shift = -(int)bps;  // any chunk count per sample: the kernel divides
-    if (t == SKR_BF16) launch_masked_v1_t<bf16_t>(p, inputs, out, mk, seeds_dev, noise, chunks, bps_shift, s);
-    else if (t == SKR_F16) launch_masked_v1_t<f16_t>(p, inputs, out, mk, seeds_dev, noise, chunks, bps_shift, s);
-    else launch_masked_v1_t<float>(p, inputs, out, mk, seeds_dev, noise, chunks, bps_shift, s);
+    with_step_type<false>(t, [&](auto tt) {
+      with_bools([&](auto nz) { launch_masked_v1<typename decltype(tt)::type, decltype(nz)::value>(p, inputs, out, mk, seeds_dev, chunks, bps_shift, s); }, noise);
+    });
     return finish_launch();
   }
 
@@ -272,9 +237,7 @@ extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* con
   a.numel = numel; a.sample_numel = p.sample_numel; a.mask_numel = mk.mask_numel; a.mask_stride = mk.batch_stride;
   a.n = p.n_terms; a.n_a = p.n_group_a; a.dt_a = p.dtype_a; a.dt_b = p.dtype_b; a.dt_out = p.out0_dtype; a.dt_mask = mk.dtype;
   a.noise = noise ? 1 : 0;
-  int64_t blocks = (numel + BLOCK - 1) / BLOCK;
-  if (blocks > 256 * 64) blocks = 256 * 64;
-  if (p.acc_f64) hipLaunchKernelGGL((masked_kernel_gen<double>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-  else hipLaunchKernelGGL((masked_kernel_gen<float>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+  const dim3 grid((unsigned)grid_blocks(numel, BLOCK, 256 * 64));
+  with_bools([&](auto f64) { hipLaunchKernelGGL((masked_kernel_gen<std::conditional_t<decltype(f64)::value, double, float>>), grid, dim3(BLOCK), 0, s, a); }, p.acc_f64 != 0);
   return finish_launch();
 }

@@ -236,8 +236,7 @@ template <typename T, typename M, int NW>
 static int launch_tape_words(const TapeArgs& a, int regs, hipStream_t s) {
   constexpr int WE = TapeElems<T>::value;
   const int64_t n_words = (a.numel + WE - 1) / WE;
-  int64_t blocks = (n_words + (int64_t)TAPE_THREADS * NW - 1) / ((int64_t)TAPE_THREADS * NW);
-  if (blocks > 256 * 32) blocks = 256 * 32;  // chunk-stride beyond 32 blocks per CU
+  const int64_t blocks = grid_blocks(n_words, (int64_t)TAPE_THREADS * NW, 256 * 32);  // chunk-stride beyond 32 blocks per CU
   const size_t lds = sizeof(typename TapeWord<T>::type) * (size_t)regs * NW * TAPE_THREADS;  // per register and word: 4 KiB (16-bit, fp32), 8 KiB (fp64)
   if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(tape_kernel<T, M, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     (void)hipGetLastError();
@@ -308,11 +307,8 @@ extern "C" int skr_tape_launch(const skr_tape* tape, const void* const* inputs, 
     }
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (t.dtype) {
-    case SKR_BF16: return skr::launch_tape<skr::bf16_t, float>(a, s);
-    case SKR_F16: return skr::launch_tape<skr::f16_t, float>(a, s);
-    case SKR_F32: return skr::launch_tape<float, float>(a, s);
-    case SKR_F64: return skr::launch_tape<double, double>(a, s);
-    default: return SKR_ERR_DTYPE;
-  }
+  return skr::with_step_type(t.dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    return skr::launch_tape<T, typename skr::OpMath<T>::type>(a, s);
+  });
 }

@@ -314,15 +314,25 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
   using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLK + threadIdx.x;
-  [[maybe_unused]] const skr_step_row* rolling = nullptr;  // Rolling form: the inactive exit only (a Runge-Kutta step has no ramp-up)
+  // Rolling form: the inactive exit, and the operands behind the conversion pair that the row lacks are neither loaded nor summed (the
+  // contract of skr_step_launch_rolling; a Runge-Kutta step has no ramp-up, so the samplers' own rows lack none)
+  [[maybe_unused]] const skr_step_row* rolling = nullptr;
+  [[maybe_unused]] bool on[K];
   if constexpr (RowsBy<TR>::rolling) {
     uint32_t smp, within;
     rolling = rolling_row(a.tab, c, a.bps_shift, smp, within);
     if (rolling == nullptr) return;
+#pragma unroll
+    for (int j = 0; j < K; ++j) on[j] = j < 2 || row_has(rolling, j);
   }
   Raw<T> raw[K];
+  if constexpr (RowsBy<TR>::rolling) {
 #pragma unroll
-  for (int j = 0; j < K; ++j) raw[j] = load_raw<T, TILE>(a.in[j], v);
+    for (int j = 0; j < K; ++j) if (on[j]) raw[j] = load_raw<T, TILE>(a.in[j], v);
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; ++j) raw[j] = load_raw<T, TILE>(a.in[j], v);
+  }
   __builtin_amdgcn_sched_barrier(0);  // every load is out before the first scalar of the arithmetic is fetched
   float k[4] = {a.ck[0], a.ck[1], a.ck[2], a.ck[3]}, cf[K], chain = a.chain, zeta1 = a.zeta1;
   uint64_t stream1 = a.stream1;
@@ -362,6 +372,7 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
   }
 #pragma unroll
   for (int j = 2; j < K; ++j) {
+    if constexpr (RowsBy<TR>::rolling) { if (!on[j]) continue; }
     float w[VEC];
     widen<T, float>(raw[j], w);
     const float cj = cf[j];

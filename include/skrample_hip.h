@@ -255,6 +255,44 @@ int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs,
                            const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * The masked step with device-resident scalars: skr_step_launch_masked as skr_step_launch_indexed and
+ * skr_step_launch_indexed_per_sample make skr_step_launch, so that one captured in-painting loop serves any schedule of its length
+ * (other sigmas, shift, begin index / strength, stochasticity), keeps several schedules resident and lets every sample follow its own.
+ * `plan` fixes the structure only: operand count and dtype groups, out0_dtype (out1_dtype must be SKR_NONE), noise_mode, sample_numel,
+ * acc_f64 == 0, convert_* == 0.  Its coef0 / coef1 / zeta0 / stream0 values are ignored; when the kernel runs it reads them from
+ *     indexed      rows_dev[(index_dev ? index_dev[0] : 0) + row_offset]
+ *     per sample   rows_dev[sample_index_dev[s] + row_offset]            for the workgroups of sample s
+ * skr_step_row is used unchanged; the row's chain, zeta1, stream1 and convert_k are not read.  The mask descriptor is skr_step_mask
+ * unchanged: the mask's pointer, layout and dtype are launch arguments (frozen into a captured graph), its contents are data.
+ * Arithmetic: that of skr_step_launch_masked, and bit for bit what skr_step_launch_masked gives with the row's values in its plan: s is
+ * accumulated in slot order, one fma per operand, the noise last -- a row whose zeta0 is exactly zero skips the draw, as in the other
+ * row forms --; k over the operands whose row coef1 is not exactly zero; out = fma(m, s, (1 - m) * k), rounded once.  The row's
+ * doubles are narrowed to fp32 on the device with the conversion the host applies to a plan's doubles.  A sample of a per-sample
+ * launch has the bits the indexed launch gives it with that row for the whole batch.
+ * Covered: exactly what the one-trip kernel of skr_step_launch_masked takes -- whole 2048-element chunks, samples made of whole chunks,
+ * one 16- or 32-bit dtype for operands, mask and output, fp32 arithmetic, 1..SKR_ROW_TERMS operands, mask_numel % 8 == 0.  Anything
+ * else is SKR_ERR_UNSUPPORTED ("one_trip" 0 and fp32 tensors with "tile" 0 included): there is no grid-stride row form.
+ * Checked before the launch, without dereferencing device memory, in the order and with the codes of skr_step_launch_masked; on top of
+ * them a NULL rows_dev is SKR_ERR_NULL, a NULL sample_index_dev in the per-sample entry is SKR_ERR_NULL, and a launch with
+ * noise_mode == 1 needs seeds_dev whatever its rows hold.  out1_dtype != SKR_NONE, acc_f64 or a non-zero convert_* is
+ * SKR_ERR_UNSUPPORTED, as is a negative row_offset.
+ * Index validity is the caller's business, as with skr_step_launch_indexed: index_dev[0] + row_offset, and every
+ * sample_index_dev[s] + row_offset, must name a row of the table.  The kernel neither checks nor clamps an index -- an entry outside
+ * the table reads whatever lies there (or faults) -- so validate on the host before uploading (skrample_amd.graphs.CapturedLoop does).
+ * There is no rolling form: no negative index, no absent-operand semantics.
+ */
+int skr_step_launch_masked_indexed(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                   const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel,
+                                   const skr_step_row* rows_dev, const int32_t* index_dev /* device int32, may be NULL */,
+                                   int32_t row_offset, void* stream);
+
+int skr_step_launch_masked_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                              const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel,
+                                              const skr_step_row* rows_dev,
+                                              const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                              int32_t row_offset, void* stream);
+
+/*
  * Step programs -- a plan the library keeps, launched by handle. Replaces the per-step host work of a REPLAYED step
  * (skrample/diffusers.py:565-599 redoes the whole step algebra every call; skrample_amd lowers each distinct step once,
  * sampling/program.py): the plan -- coefficients, dtypes, conversion kinds, sample size -- is handed over and validated once,

@@ -31,6 +31,8 @@ EXPORTS = (
     "skr_step_launch_indexed_per_sample",
     "skr_step_launch_rolling",
     "skr_step_launch_masked",
+    "skr_step_launch_masked_indexed",
+    "skr_step_launch_masked_indexed_per_sample",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_program_create",
@@ -154,10 +156,15 @@ class StepMaskC(ctypes.Structure):
     ]
 
 
-def plan_structure(plan: StepPlanC, sample_numel: bool = True) -> tuple:
-    "what a captured launch freezes: everything of a plan except the scalars a row carries (`sample_numel` = False: and the sample size)"
-    return (plan.n_terms, plan.n_group_a, plan.dtype_a, plan.dtype_b, plan.out0_dtype, plan.out1_dtype, plan.acc_f64, plan.noise_mode,
-            plan.sample_numel if sample_numel else None, plan.convert_to, plan.convert_from)  # fmt: skip
+def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None) -> tuple:
+    """what a captured launch freezes: everything of a plan except the scalars a row carries (`sample_numel` = False: and the sample size).
+    A masked launch (`mask`: its descriptor) adds that it is one, the mask's dtype and whether one mask serves the whole batch
+    (batch_stride == 0), and -- shape-like, dropped with the sample size -- the mask's elements per sample."""
+    plain = (plan.n_terms, plan.n_group_a, plan.dtype_a, plan.dtype_b, plan.out0_dtype, plan.out1_dtype, plan.acc_f64, plan.noise_mode,
+             plan.sample_numel if sample_numel else None, plan.convert_to, plan.convert_from)  # fmt: skip
+    if mask is None:
+        return plain
+    return (*plain, "masked", mask.dtype, mask.batch_stride == 0, mask.mask_numel if sample_numel else None)
 
 
 def upload_rows(rows_dev: torch.Tensor, first_row: int, rows) -> None:
@@ -227,26 +234,56 @@ class IndexedRows:
             while len(self.host) < need:
                 self.host.append(StepRowC())
 
-    def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int) -> int:
+    def _uncovered(self, plan: StepPlanC, mask: "StepMaskC", numel: int) -> str | None:
+        "why the masked row kernel does not cover this launch (include/skrample_hip.h, skr_step_launch_masked_indexed), or None"
+        if plan.acc_f64:
+            return "masked rows are evaluated in float32, not under compute_scale=float64"
+        one = plan.dtype_a
+        if (plan.n_group_a != plan.n_terms and plan.dtype_b != one) or plan.out0_dtype != one or mask.dtype != one or one not in (BF16, F16, F32):
+            return "masked rows need one 16- or 32-bit dtype for operands, mask and output"
+        if plan.sample_numel <= 0 or plan.sample_numel % PER_SAMPLE_CHUNK != 0 or numel % PER_SAMPLE_CHUNK != 0:
+            return f"masked rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {plan.sample_numel} elements"
+        if mask.mask_numel % 8 != 0:
+            return f"masked rows need a mask of a multiple of 8 elements per sample, not {mask.mask_numel}"
+        if plan.n_terms < 1:
+            return "masked rows need at least one operand"
+        return None
+
+    def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int, mask: "StepMaskC | None" = None) -> int:
+        "one launch of the loop; `mask` (its descriptor): a masked one (skr_step_launch_masked and its row forms; out1_ptr is None)"
         k = self.cursor
         self.cursor += 1
+
+        def run_now() -> int:  # the launch itself, with the plan's own scalars
+            if mask is not None:
+                return lib.skr_step_launch_masked(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, stream_ptr)
+            return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
+
         if self.mode == "record":
             if self.batch is not None and (numel % self.batch != 0 or (numel // self.batch) % PER_SAMPLE_CHUNK != 0):
                 # (what skr_step_launch_indexed_per_sample would answer during the capture: said here, before a stream is capturing)
                 raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, "
                                        f"not {numel} elements for {self.batch} samples")
-            self.structures.append(plan_structure(plan))
-            self.shapeless.append(plan_structure(plan, sample_numel=False))
-            self.host.append(self.row_from(plan))
-            return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
+            if mask is not None:
+                why = self._uncovered(plan, mask, numel)
+                if why is not None:  # (what skr_step_launch_masked_indexed would answer during the capture)
+                    raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
+            row = self.row_from(plan)
+            self.structures.append(plan_structure(plan, mask=mask))
+            self.shapeless.append(plan_structure(plan, sample_numel=False, mask=mask))
+            self.host.append(row)
+            return run_now()
         if k >= self.length:
             raise SkrampleHipError("more launches than the captured loop has")
         if self.mode == "refill":
-            if plan_structure(plan, sample_numel=False) != self.shapeless[k]:
+            found = plan_structure(plan, sample_numel=False, mask=mask)
+            if mask is not None and len(found) == len(self.shapeless[k]) and numel == plan.sample_numel:
+                found = (*found[:-2], self.shapeless[k][-2], found[-1])  # (a dry run on one sample has no batch stride to compare)
+            if found != self.shapeless[k]:
                 raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
             self.host[self.slot * self.length + k] = self.row_from(plan)
-            return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
-        if plan_structure(plan) != self.structures[k]:
+            return run_now()
+        if plan_structure(plan, mask=mask) != self.structures[k]:
             raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
         if self.sample_index_dev is not None:
             if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
@@ -254,7 +291,11 @@ class IndexedRows:
                 plan.sample_numel = numel // self.batch
             if numel != self.batch * plan.sample_numel:
                 raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {self.batch} samples of {plan.sample_numel} the per-sample index holds")
+            if mask is not None:
+                return lib.skr_step_launch_masked_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
             return lib.skr_step_launch_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
+        if mask is not None:
+            return lib.skr_step_launch_masked_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
         return lib.skr_step_launch_indexed(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
 
 
@@ -331,6 +372,9 @@ def load() -> ctypes.CDLL:
             table_launch.restype = ctypes.c_int
         lib.skr_step_launch_masked.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp]
         lib.skr_step_launch_masked.restype = ctypes.c_int
+        for masked_table_launch in (lib.skr_step_launch_masked_indexed, lib.skr_step_launch_masked_indexed_per_sample):
+            masked_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp, vp, i32, vp]
+            masked_table_launch.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -438,15 +482,19 @@ def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, 
 def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device) -> None:
     """one masked step launch (skr_step_launch_masked) on torch's current stream of `device`: out = m * (coef0 form + noise) + (1 - m) * (coef1 form).
     A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, mask) -- a seventh entry no step program is built from.
-    The indexed-rows hook (captured loops with device-resident scalars) has no masked form and refuses."""
+    Under the indexed-rows hook (captured loops with device-resident scalars) the launch is recorded, emitted as
+    skr_step_launch_masked_indexed[_per_sample] or refilled, as a plain step launch is (IndexedRows.launch)."""
     lib = load()
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError("masked steps are not part of indexed (device-resident row) launches")
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append((plan, list(operands), out, None, seeds, numel, mask))
     n = len(operands)
     arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
     desc = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
-    status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, numel, current_stream_ptr(device))
+    seeds_ptr = seeds.data_ptr() if seeds is not None else None
+    rows = getattr(_hooks, "indexed", None)
+    if rows is not None:
+        status = rows.launch(lib, plan, arr, out.data_ptr(), None, seeds_ptr, numel, current_stream_ptr(device), mask=desc)
+    else:
+        status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds_ptr, numel, current_stream_ptr(device))
     check(status, "skr_step_launch_masked")

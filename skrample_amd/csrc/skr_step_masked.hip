@@ -11,49 +11,10 @@
 //   * general kernel (masked_kernel_gen): grid-stride, one element per lane and trip, any size, any dtype combination skr_step_launch
 //     takes, fp32 or fp64 arithmetic.
 // Both evaluate the same operations in the same order on every element, so they agree bit for bit where both apply.
-#include "skr_step_common.h"
+#include "skr_step_masked.h"
 #include "skr_device.h"
 
 namespace skr {
-
-constexpr int masked_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : 16)); }
-
-// Kernarg of the one-trip kernel: what the first instructions need (operand pointers, chunk map) leads, as in OneTripArgs.
-template <int KMAX>
-struct MaskedArgs {
-  const void* in[KMAX];
-  const void* mask;
-  void* out;
-  int32_t xmap_lr;      // log2(run length) of the XCD chunk map
-  int32_t bps_shift;    // chunks per sample: log2 when >= 0, minus the count otherwise (see chunk_sample)
-  uint32_t mask_numel;  // elements of one sample's mask (a multiple of 8, below 2^31)
-  uint32_t mask_stride; // elements between the masks of two samples: mask_numel or 0
-  const uint64_t* seeds;
-  uint64_t stream0;
-  float zeta0;
-  float c0[KMAX];
-  float c1[KMAX];
-};
-
-// chunk -> (sample, chunk within the sample): a shift for a power-of-two number of chunks per sample, else one uniform division
-__device__ __forceinline__ void chunk_sample(uint32_t c, int32_t bps_shift, uint32_t& smp, uint32_t& within) {
-  if (bps_shift >= 0) { smp = c >> bps_shift; within = c - (smp << bps_shift); }
-  else { const uint32_t bps = (uint32_t)(-bps_shift); smp = c / bps; within = c - smp * bps; }
-}
-
-// The lane's 8 mask values, at elements m0.. and m1.. of the sample's mask (two groups of 4; consecutive without the tile layout).
-// Plain loads, not the operands' non-temporal ones: a (1,H,W) mask is read again by every channel of the sample.
-template <typename T>
-__device__ __forceinline__ Raw<T> load_mask8(const void* base, int64_t m0, int64_t m1) {
-  Raw<T> r;
-  if constexpr (sizeof(T) == 2) {
-    r.q = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint16_t*>(base) + m0);  // (m1 == m0 + 4: one 16-byte access)
-  } else {
-    r.q[0] = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(base) + m0);
-    r.q[1] = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(base) + m1);
-  }
-  return r;
-}
 
 template <typename T, int K, bool NOISE>
 __global__ __launch_bounds__(BLOCK) void masked_kernel_v1(const MaskedArgs<masked_kmax(K)> a) {
@@ -182,14 +143,9 @@ static void launch_masked_v1(const skr_step_plan& p, const void* const* inputs, 
   });
 }
 
-}  // namespace skr
-
-extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_mask* mask,
-                                      const uint64_t* seeds_dev, int64_t numel, void* stream) {
-  using namespace skr;
-  if (!plan || !mask) return SKR_ERR_NULL;
-  const skr_step_plan& p = *plan;
-  const skr_step_mask& mk = *mask;
+int masked_prepare(const skr_step_plan& p, const skr_step_mask& mk, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
+                   bool rows, MaskedLaunch* launch) {
+  launch->noise = launch->one_trip = false;
   if (p.n_terms < 0 || p.n_group_a < 0 || p.n_group_a > p.n_terms || p.n_terms > SKR_ROW_TERMS) return SKR_ERR_TERMS;
   if (numel < 0) return SKR_ERR_SHAPE;
   if (p.out0_dtype == SKR_NONE) return SKR_ERR_NULL;
@@ -198,7 +154,7 @@ extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* con
     return SKR_ERR_UNSUPPORTED;
   if (p.sample_numel <= 0 || numel % p.sample_numel != 0) return SKR_ERR_SHAPE;
   if (mk.mask_numel < 1 || p.sample_numel % mk.mask_numel != 0 || (mk.batch_stride != 0 && mk.batch_stride != mk.mask_numel)) return SKR_ERR_SHAPE;
-  const bool noise = p.noise_mode == 1 && p.zeta0 != 0.0;
+  const bool noise = p.noise_mode == 1 && (rows || p.zeta0 != 0.0);
   if (noise && p.sample_numel % 8 != 0) return SKR_ERR_UNSUPPORTED;  // fused Philox needs every 8-element group inside one sample, as in skr_step_launch
   // the dtype combinations of skr_step_launch, with one output; the mask: a 16-bit dtype or the arithmetic's
   const int32_t db = p.n_group_a == p.n_terms ? p.dtype_a : p.dtype_b;
@@ -208,20 +164,40 @@ extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* con
   if ((p.n_terms > 0 && !inputs) || !out || !mk.mask || (noise && !seeds_dev)) return SKR_ERR_NULL;
   if (const int rc = check_ptrs(inputs, p.n_terms)) return rc;
   if (!aligned16(out) || !aligned16(mk.mask)) return SKR_ERR_ALIGN;
-  DeviceGuard device_guard(out);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  launch->noise = noise;
 
   constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
   const int t = p.dtype_a;
   const bool one_dtype = (p.n_group_a == p.n_terms || p.dtype_b == t) && p.out0_dtype == t && mk.dtype == t && t != SKR_F64;
   if (g_tune.one_trip && !p.acc_f64 && one_dtype && p.n_terms >= 1 && (t != SKR_F32 || g_tune.tile) && numel % CHUNK == 0 &&
       numel / CHUNK <= 0x7fffffffll && p.sample_numel % CHUNK == 0 && p.sample_numel < (1ll << 31) && mk.mask_numel % 8 == 0) {
-    const int64_t chunks = numel / CHUNK, bps = p.sample_numel / CHUNK;
+    const int64_t bps = p.sample_numel / CHUNK;
     int bps_shift = 0;
     if ((bps & (bps - 1)) == 0) { while ((1ll << bps_shift) < bps) ++bps_shift; }
     else bps_shift = -(int)bps;  // any chunk count per sample: the kernel divides
-    with_step_type<false>(t, [&](auto tt) {
-      with_bools([&](auto nz) { launch_masked_v1<typename decltype(tt)::type, decltype(nz)::value>(p, inputs, out, mk, seeds_dev, chunks, bps_shift, s); }, noise);
+    launch->one_trip = true; launch->chunks = numel / CHUNK; launch->bps_shift = bps_shift;
+  }
+  return SKR_OK;
+}
+
+}  // namespace skr
+
+extern "C" int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_mask* mask,
+                                      const uint64_t* seeds_dev, int64_t numel, void* stream) {
+  using namespace skr;
+  if (!plan || !mask) return SKR_ERR_NULL;
+  const skr_step_plan& p = *plan;
+  const skr_step_mask& mk = *mask;
+  MaskedLaunch l;
+  if (const int rc = masked_prepare(p, mk, inputs, out, seeds_dev, numel, false, &l)) return rc;
+  if (numel == 0) return SKR_OK;
+  const bool noise = l.noise;
+  DeviceGuard device_guard(out);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+
+  if (l.one_trip) {
+    with_step_type<false>(p.dtype_a, [&](auto tt) {
+      with_bools([&](auto nz) { launch_masked_v1<typename decltype(tt)::type, decltype(nz)::value>(p, inputs, out, mk, seeds_dev, l.chunks, l.bps_shift, s); }, noise);
     });
     return finish_launch();
   }

@@ -22,6 +22,12 @@ the captured network.  The reference redoes this work on the host every step, wi
 resident schedule -- a batch of requests with different shifts, sigma families, stochasticities or begin indices in one launch per
 step.  With `device_timesteps` the network's `t` is then a 1-D tensor of shape `[batch]` (row i of one `[steps, batch]` device
 tensor), the per-sample form diffusers models accept.  A sample's result is bit-identical to the one the whole-batch `slot=k` gives it.
+
+In-painting (`wrapper.set_inpaint(mask, original_samples, noise)` in force when the loop is captured) goes through all of this: the
+masked steps of an indexed capture are `skr_step_launch_masked_indexed[_per_sample]` launches whose blend coefficients -- the alpha
+and sigma of each step's target -- sit in the rows beside the step's own, so strength (begin index), shift and schedule are data.
+The wrapper's three in-paint tensors are the loop's static buffers (`loop.inpaint`); `loop(latents, inpaint=(mask, original,
+noise))` copies a new request's into them ahead of the replay.
 """
 
 from __future__ import annotations
@@ -36,7 +42,8 @@ class CapturedLoop:
     "replayable sampling loop: `out = loop(initial_latents, seeds=None)`"
 
     def __init__(self, graph: torch.cuda.CUDAGraph, static_in: torch.Tensor, static_out: torch.Tensor, seeds_dev: torch.Tensor | None, rows=None, runner=None,
-                 static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None):
+                 static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None, inpaint: tuple | None = None):
+        self.inpaint = inpaint  # (mask, original_samples, noise) the captured masked steps read, or None: a loop captured without in-painting
         self.graph, self.static_in, self.static_out, self.seeds_dev = graph, static_in, static_out, seeds_dev
         self.rows, self._runner = rows, runner  # _hip.IndexedRows of an indexed capture; runner(wrapper, x) = the captured loop body
         self._filled = {0}  # table slots that hold a schedule (the capture itself fills slot 0; the others start as zero rows)
@@ -88,7 +95,9 @@ class CapturedLoop:
     def retarget(self, wrapper, slot: int = 0) -> None:
         """Load the step scalars of `wrapper` (same sampler structure and number of steps as the captured one, any schedule /
         shift / begin index / stochasticity) into table slot `slot`: a dry run of its loop on one sample fills the rows, one
-        small host-to-device copy publishes them.  The graph itself is untouched."""
+        small host-to-device copy publishes them.  The graph itself is untouched.
+        A loop captured with in-painting takes a wrapper that has `set_inpaint(...)` in force itself (the dry run steps on one-sample
+        views of ITS tensors); only its scalars reach the graph, which goes on reading `loop.inpaint`."""
         from . import _hip
 
         if self.rows is None:
@@ -115,15 +124,26 @@ class CapturedLoop:
             if self.sample_times is not None and slot in self._sample_slots:
                 self._publish_sample_times()  # the columns of the samples that follow this slot
 
-    def __call__(self, latents: torch.Tensor, seeds: Sequence[int] | None = None, slot: int | Sequence[int] | torch.Tensor | None = None) -> torch.Tensor:
+    def __call__(self, latents: torch.Tensor, seeds: Sequence[int] | None = None, slot: int | Sequence[int] | torch.Tensor | None = None,
+                 inpaint: Sequence[torch.Tensor] | None = None) -> torch.Tensor:
         """Replay on `latents`.  `slot`: the resident schedule to follow -- an int for the whole batch; on a loop captured with
-        `per_sample=True` also a host sequence or 1-D CPU integer tensor with one slot per sample."""
+        `per_sample=True` also a host sequence or 1-D CPU integer tensor with one slot per sample.  `inpaint`: (mask, original_samples,
+        noise) of the captured shapes, copied into `loop.inpaint` ahead of the replay (a loop captured with in-painting only)."""
+        if inpaint is not None:
+            if self.inpaint is None:
+                raise ValueError("this loop was captured without in-painting: call wrapper.set_inpaint(...) before capture_sampling_loop")
+            given = tuple(inpaint)
+            if len(given) != 3 or any(not isinstance(t, torch.Tensor) or t.shape != held.shape for t, held in zip(given, self.inpaint)):
+                raise ValueError(f"inpaint is (mask, original_samples, noise) of shapes {[tuple(t.shape) for t in self.inpaint]}")
         chosen = None
         if slot is not None and not isinstance(slot, int):
             if not self.per_sample:
                 raise ValueError("one slot per sample needs a loop captured with capture_sampling_loop(..., indexed=True, per_sample=True)")
             chosen = self._check_slots(slot)
         self.static_in.copy_(latents)
+        if inpaint is not None:
+            for held, new in zip(self.inpaint, given):
+                held.copy_(new)  # (stream-ordered ahead of the replay; a bool / uint8 mask is cast as set_inpaint casts it)
         if chosen is not None:
             self.rows.select(chosen)  # sample b reads row slot[b] * length + position in the loop
             if self.sample_times is not None and chosen != self._sample_slots:
@@ -194,8 +214,9 @@ class CapturedLoops:
         "run lengths whose graphs are resident, least recently used first"
         return tuple(self._loops)
 
-    def __call__(self, latents: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, slot: int | Sequence[int] | torch.Tensor | None = None) -> torch.Tensor:
-        return self.loop(steps)(latents, seeds, slot)
+    def __call__(self, latents: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, slot: int | Sequence[int] | torch.Tensor | None = None,
+                 inpaint: Sequence[torch.Tensor] | None = None) -> torch.Tensor:
+        return self.loop(steps)(latents, seeds, slot, inpaint)
 
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
@@ -214,6 +235,11 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     `loop(latents, slot=[...])`; with `device_timesteps` the network receives a 1-D `t` of shape `[batch]`.  Needs latents of whole
     2048-element chunks per sample.  `slots` may be as large as the batch (one schedule per request): the table is
     `slots * launches per loop * 328 bytes` of device memory -- 256 slots of a 30-launch loop are 2.5 MB.
+
+    A wrapper with `set_inpaint(...)` in force is captured with its masked steps; its three in-paint tensors become static buffers of
+    the loop (`loop.inpaint`).  With `indexed=True` the masked row kernel must cover the launches -- samples of whole 2048-element
+    chunks, one 16- or 32-bit dtype for latents and mask, a mask of a multiple of 8 elements per sample, no `compute_scale=float64`
+    -- and anything else is refused during the recording pass, before the stream captures.
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
@@ -256,9 +282,18 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         other.set_timesteps(steps, device=dev) if device_timesteps else other.set_timesteps(steps)
         sub = gen[: x.shape[0]] if gen is not None else None
         ts = other.timesteps
-        for t in ([ts[i] for i in range(ts.numel())] if device_timesteps else ts.tolist()):
-            tm = t.reshape(1).expand(x.shape[0]) if sample_times is not None else t  # (the dry run's samples: `t` of shape [1])
-            x = other.step(model(x, tm), t, x, generator=sub, return_dict=False)[0]
+        held = getattr(other, "_inpaint", None)
+        if held is not None:  # in-painting: the dry run's samples of the new wrapper's own tensors (views; only its scalars reach the rows)
+            mask, original, noise = held
+            n = x.shape[0]
+            other._inpaint = (mask[:n] if mask.dim() == original.dim() and mask.shape[0] > n else mask, original[:n], noise[:n])
+        try:
+            for t in ([ts[i] for i in range(ts.numel())] if device_timesteps else ts.tolist()):
+                tm = t.reshape(1).expand(x.shape[0]) if sample_times is not None else t  # (the dry run's samples: `t` of shape [1])
+                x = other.step(model(x, tm), t, x, generator=sub, return_dict=False)[0]
+        finally:
+            if held is not None:
+                other._inpaint = held
         return x
 
     side = torch.cuda.Stream(device=dev)
@@ -298,4 +333,4 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     from .pytorch.noise import forget_seed_vector
 
     forget_seed_vector(seeds_dev)  # the graph reads this very buffer and replays may overwrite it: no other run may share it from now on
-    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times)
+    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None))

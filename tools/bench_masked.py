@@ -7,11 +7,16 @@ Forms, each in a child process of its own (a fresh HIP context and allocator per
   a  masked step       w.set_inpaint(mask, original, noise);  latents = w.step(out, t, latents)
   b  unfused loop      latents = w.step(out, t, latents);  known = w.add_noise(original, noise, next t);
                        latents = mask * latents + (1 - mask) * known      -- the public API without set_inpaint
-  k  kernels alone     skr_step_launch_masked back to back, beside skr_step_launch of the same operand count: event clock per launch and
+  c  captured loop     w.set_inpaint(...);  loop = capture_sampling_loop(w, model, latents, steps, indexed=True);  loop(latents)
+                       -- the masked steps as skr_step_launch_masked_indexed launches of one HIP graph (device-resident rows); a replay
+                       includes the copy of the latents into the loop's static buffer and the clone of its result
+  k  kernels alone     skr_step_launch_masked back to back, beside skr_step_launch of the same operand count and beside
+                       skr_step_launch_masked_indexed reading the same scalars from a row: event clock per launch and
                        the fraction of 8 TB/s its algorithmic bytes come to (operands + quarter-size mask + one store)
 Per repeat, `steps` steps of a `steps`-step schedule are timed with HIP events (first enqueue to last kernel) and with the wall clock
 (first call to the end of a device synchronisation); reported per form: median and min - max over the repeats, us per step.
-Pass condition: a's wall-clock median is below b's by more than the two forms' min - max spreads put together."""
+Pass conditions: a's wall-clock median is below b's, and c's below a's, each by more than the two forms' min - max spreads put together.
+Reported beside them, not judged: whether the row kernel's median lies within the min - max spread of its kernarg twin."""
 
 import argparse
 import json
@@ -25,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 BATCH, SHAPE, WARMUP = 256, (4, 128, 128), 20
 SAMPLERS = ("dpm2", "euler")
-FORMS = {"a": "masked step()", "b": "step + add_noise + blend"}
+FORMS = {"a": "masked step()", "b": "step + add_noise + blend", "c": "indexed captured loop"}
 PEAK = 8.0e12  # bytes per second
 
 
@@ -58,8 +63,22 @@ def child(form: str, sampler: str, repeats: int, steps: int) -> None:
             plan.coef0[k] = 0.5 if k < n - 2 else 0.0
             plan.coef1[k] = 0.5 if k >= n - 2 else 0.0
         out = torch.empty_like(x0)
+        import ctypes
+
+        lib = _hip.load()
+        table = torch.zeros(ctypes.sizeof(_hip.StepRowC), dtype=torch.uint8, device=dev)
+        _hip.upload_rows(table, 0, [_hip.IndexedRows.row_from(plan)])
+        index = torch.zeros(1, dtype=torch.int32, device=dev)
+        arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ops])
+        desc = _hip.StepMaskC(mask.data_ptr(), _hip.BF16, 0, mask.numel() // BATCH, mask.numel() // BATCH)
+
+        def rows_launch():
+            _hip.check(lib.skr_step_launch_masked_indexed(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), None, out.numel(), table.data_ptr(), index.data_ptr(), 0,
+                                                          _hip.current_stream_ptr(dev)), "skr_step_launch_masked_indexed")  # fmt: skip
+
         launches = {
             "masked": lambda: _hip.launch_step_masked(plan, ops, out, mask, mask.numel() // BATCH, mask.numel() // BATCH, None, out.numel(), dev),
+            "rows": rows_launch,
             "plain": lambda: _hip.launch_step(plan, ops, out, None, None, out.numel(), dev),
         }
         for name, launch in launches.items():
@@ -77,16 +96,43 @@ def child(form: str, sampler: str, repeats: int, steps: int) -> None:
                 per.append(e0.elapsed_time(e1) * 1e3 / steps)
             result[name + "_us"] = per
         result["operands"] = n
-        result["masked_bytes"] = out.numel() * 2 * (n + 1) + mask.numel() * 2
+        result["masked_bytes"] = result["rows_bytes"] = out.numel() * 2 * (n + 1) + mask.numel() * 2
         result["plain_bytes"] = out.numel() * 2 * (n + 1)
         print("RESULT " + json.dumps(result), flush=True)
         return
 
     make = (lambda: PD.SkrampleWrapperScheduler(PT.DPM(order=2), PS.Karras(PS.Scaled()))) if sampler == "dpm2" else (lambda: PD.SkrampleWrapperScheduler(PT.Euler(), PS.Karras(PS.Scaled())))  # fmt: skip
     w = make()
-    if form == "a":
+    if form in ("a", "c"):
         w.set_inpaint(mask, orig, nz)
     inverse = 1 - mask
+
+    if form == "c":
+        from skrample_amd.graphs import capture_sampling_loop
+
+        calls = [0]
+
+        def model(x, t):  # the ring of fixed model outputs, in the order forms a and b read it (the capture freezes the sequence)
+            calls[0] += 1
+            return ring[(calls[0] - 1) & 3]
+
+        loop = capture_sampling_loop(w, model, x0, steps, indexed=True, slots=1)
+        for _ in range(2):
+            loop(x0)
+        torch.cuda.synchronize()
+        event_us, wall_us = [], []
+        for _ in range(repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            loop(x0)
+            e1.record()
+            torch.cuda.synchronize()
+            wall_us.append((time.perf_counter() - t0) * 1e6 / steps)
+            event_us.append(e0.elapsed_time(e1) * 1e3 / steps)
+        result.update(event_us=event_us, wall_us=wall_us, fast_hits=w._fast_hits)
+        print("RESULT " + json.dumps(result), flush=True)
+        return
 
     def loop():
         w.set_timesteps(steps)
@@ -165,8 +211,15 @@ def main() -> int:
         lines.append(f"  wall-clock medians: b - a = {bm - am:.2f} us (b / a = {bm / am:.2f}), the two spreads together {margin:.2f} us: {'PASS' if ok else 'FAIL'} (a below b by more than the spreads)")
         (eam, _, _), (ebm, _, _) = summary(seen["a"]["event_us"]), summary(seen["b"]["event_us"])
         lines.append(f"  event-clock medians: b / a = {ebm / eam:.2f}")
+        cm, clo, chi = summary(seen["c"]["wall_us"])
+        margin = (ahi - alo) + (chi - clo)
+        ok = am - cm > margin
+        failed |= not ok
+        lines.append(f"  wall-clock medians: a - c = {am - cm:.2f} us (a / c = {am / cm:.2f}), the two spreads together {margin:.2f} us: {'PASS' if ok else 'FAIL'} (c below a by more than the spreads)")
         k = seen["k"]
-        for name in ("masked", "plain"):
+        (mm, mlo, mhi), (rm, _, _) = summary(k["masked_us"]), summary(k["rows_us"])
+        lines.append(f"  k  row kernel median {rm:.2f} us against its kernarg twin's {mm:.2f} ({mlo:.2f} - {mhi:.2f}): {'inside' if mlo <= rm <= mhi else 'outside'} the twin's spread")
+        for name in ("masked", "rows", "plain"):
             m, lo, hi = summary(k[name + "_us"])
             lines.append(f"  k  {name:6s} kernel, {k['operands']} operands   event clock {m:8.2f} ({lo:8.2f} - {hi:8.2f}) per launch   {k[name + '_bytes'] / 1e6:7.1f} MB -> {k[name + '_bytes'] / (m * 1e-6) / PEAK * 100:5.1f} % of 8 TB/s")
     text = "\n".join(lines) + "\n"

@@ -1613,8 +1613,8 @@ __global__ __launch_bounds__(256) void colored_finish(T* out, const ColoredArgs 
 //     SKR_COLORED_GROUP_MB        skr_noise_colored: draw the batch in groups whose spectrum is at most this many MiB (default: one group)
 //     SKR_COLORED_INV_STATIC      colored_inverse128 deals its planes out statically, without the device ticket
 //     SKR_COLORED_FACTORS_KERNEL  rescale factors by a colored_factors launch, not by the last block of the outer-axis kernel
-static bool env_flag(const char* name) { return getenv(name) != nullptr; }
-static int64_t env_int(const char* name, int64_t unset) { const char* e = getenv(name); return e ? (int64_t)atoll(e) : unset; }
+using skr::env_flag;  // (skr_launch.h)
+using skr::env_int;
 
 static int fft_tile_points() {
   static const int tile = [] { const int64_t v = env_int("SKR_FFT_TILE", 0); return v >= 256 && v <= 16384 && !(v & (v - 1)) ? (int)v : skr::FFT_MAX_TILE; }();

@@ -480,7 +480,7 @@ static int colored_any_attempt(void* out, int32_t out_dtype, void* spec_c64, flo
   if (planes && rank > 4) return SKR_ERR_UNSUPPORTED;
   // The transforms of the inner axes: the engine's own (skr_fft_own.hip: any length up to 2048, powers of two up to 4096) unless
   // SKR_FFT_HIPFFT is set or an axis is longer than that; hipFFT only then.
-  static const bool env_hipfft = getenv("SKR_FFT_HIPFFT") != nullptr;
+  static const bool env_hipfft = skr::env_flag("SKR_FFT_HIPFFT");
   const bool prefer_hipfft = skr::g_use_hipfft < 0 ? env_hipfft : skr::g_use_hipfft != 0;
   bool own = !planes && !prefer_hipfft;
   for (int i = (rank > fft_rank ? rank - fft_rank : 0); own && i < rank; ++i) own = skr::own_length_ok(dims[i], i == rank - 1);  // (skr_fft_own.hip)
@@ -507,7 +507,7 @@ static int colored_any_attempt(void* out, int32_t out_dtype, void* spec_c64, flo
   int n[3] = {1, 1, 1};
   for (int i = 0; i < rank; ++i) n[3 - rank + i] = dims[i];
   // own transforms of a unit without outer axes and with at least two transformed axes: the outermost one runs forward, weights, inverse fused
-  static const bool no_fuse_outer = getenv("SKR_FFT_NO_FUSE_OUTER") != nullptr;
+  static const bool no_fuse_outer = skr::env_flag("SKR_FFT_NO_FUSE_OUTER");
   const bool own_fused = own && a.n_outer == 0 && n[1] > 1 && !no_fuse_outer;  // (with outer axes the any_outer_axis passes carry the weights: every own axis must then run)
   a.real = scratch_f32; a.spec = reinterpret_cast<float2*>(spec_c64); a.partials = partials_f64; a.seeds = seeds_dev; a.stream = stream_id;
   a.batch = batch; a.d1 = n[0]; a.d2 = n[1]; a.d3 = n[2]; a.d3h = n[2] / 2 + 1; a.unit = d0 * n[0] * n[1] * n[2];
@@ -531,7 +531,7 @@ static int colored_any_attempt(void* out, int32_t out_dtype, void* spec_c64, flo
     if (g_bad_plans.count(key)) return SKR_ERR_LIBRARY;  // failed its self-check before (the defect is persistent): do not re-plan per call
     auto it = g_plans.find(key);
     if (it == g_plans.end()) {
-      static const size_t max_plans = [] { const char* e = getenv("SKR_FFT_MAX_PLANS"); return e ? (size_t)atoll(e) : MAX_PLANS; }();
+      static const size_t max_plans = (size_t)skr::env_int("SKR_FFT_MAX_PLANS", MAX_PLANS);
       if (g_plans.size() >= max_plans) {  // evict the least recently used pair
         auto victim = g_plans.begin();
         for (auto jt = g_plans.begin(); jt != g_plans.end(); ++jt) if (jt->second.last_use < victim->second.last_use) victim = jt;

@@ -136,27 +136,25 @@ static void launch_offset(const OffsetArgs& a, hipStream_t s) {
 // per-sample level geometry on the device (no host round trip); pass 1 writes the un-normalised sum in fp32
 // plus per-block (sum, sum of squares) in double; pass 2 divides by the per-sample unbiased std (fixed
 // summation order => bit-reproducible) and rounds to the output dtype.
-constexpr int PYR_MAX_LEVELS = 8;
-constexpr int PYR_LDS_FLOATS = 38 * 1024;  // up to 152 KiB of level storage per block (dynamic LDS, 160 KiB per CU)
-
-struct PyramidArgs {
-  float* scratch;          // [batch][lead][h][w] fp32
-  double* partials;        // [batch][lead][2]
-  const uint64_t* seeds;
-  int32_t* level_hw;       // [batch][PYR_MAX_LEVELS][2] (h_l, w_l); level 0 is (h, w)
-  int32_t* n_levels;       // [batch]
-  uint64_t stream_base;    // base normal: stream_base + 0
-  uint64_t stream_levels;  // level l normal: stream_levels + 1 + l, geometry uniforms: stream_levels + 255
-  int64_t batch;
-  int32_t lead, h, w;
-  int32_t resize_h, depth, with_base;
-  float strength;
+// (PYR_MAX_LEVELS, PYR_LDS_FLOATS, PYR_UNROLLED and PYR_THREADS stand in skr_launch.h, beside the route decision that shares them)
+struct PyramidArgs {  // (the defaults: a launch of the LDS kernels without a tap table; pyramid_common_args sets what every launch shares)
+  float* scratch = nullptr;          // [batch][lead][h][w] fp32
+  double* partials = nullptr;        // [batch][lead][2]
+  const uint64_t* seeds = nullptr;
+  int32_t* level_hw = nullptr;       // [batch][PYR_MAX_LEVELS][2] (h_l, w_l); level 0 is (h, w)
+  int32_t* n_levels = nullptr;       // [batch]
+  uint64_t stream_base = 0;    // base normal: stream_base + 0
+  uint64_t stream_levels = 0;  // level l normal: stream_levels + 1 + l, geometry uniforms: stream_levels + 255
+  int64_t batch = 0;
+  int32_t lead = 1, h = 1, w = 0;
+  int32_t resize_h = 0, depth = 0, with_base = 1;
+  float strength = 0.f;
   // any-dims path (pyramid_pass1_any): the unit as up to four axes, h = dim[axis_a] (axis_a = -1: one resized axis),
   // w = dim[axis_b], lead = product of the other axes.  Level tensors keep the unit's axis ORDER (reference
   // noise.py:162-165 draws `randn(running_shape)` before permuting), so level l, element (i0..i3) is normal number
   // sum_j i_j * stride_l[j] of that level's stream.
-  int32_t nd, dim[4], axis_a, axis_b;
-  int32_t ytab_off;  // UNI kernels: float offset of the vertical tap table inside the dynamic LDS (behind the level planes)
+  int32_t nd = 0, dim[4] = {1, 1, 1, 1}, axis_a = -1, axis_b = 3;
+  int32_t ytab_off = -1;  // UNI kernels: float offset of the vertical tap table inside the dynamic LDS (behind the level planes)
 };
 
 // level geometry (reference noise.py:157-162,195-196): level i shrinks the RUNNING size by r_i**i,
@@ -222,9 +220,6 @@ __device__ __forceinline__ void src_index(int dst, float scale, int in_size, int
   i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
   l1 = src - (float)i0;
 }
-
-constexpr int PYR_UNROLLED = 5;  // levels 1..4 are unrolled (and cached per column strip); deeper levels are rare and tiny
-constexpr int PYR_THREADS = 512;  // 8 waves per block (the strip kernel's 165 registers allow one such block per CU; 128 registers with spills were no faster)
 
 // STRIP: the block width divides THREADS, so a thread keeps its 4 columns for a RUN of consecutive rows: the
 // horizontally interpolated level rows (top / bottom) stay in registers while the coarse source row does not change
@@ -773,11 +768,13 @@ __global__ __launch_bounds__(256) void pyramid_pass1_any(const PyramidAnyArgs q)
 }  // namespace skr
 
 // pass 2 of both pyramid generators: the per-sample statistics of `slots` partial pairs, the division and the rounding to the output dtype
-static int normalise(void* out, int32_t out_dtype, const float* scratch_f32, const double* partials_f64, int64_t slots, int64_t unit, int64_t batch,
-                     int32_t with_base, dim3 grid, hipStream_t s) {
+static int normalise(void* out, int32_t out_dtype, const skr::PyramidArgs& a, int64_t slots, int64_t unit, hipStream_t s) {
+  int64_t bx = skr::grid_blocks(unit / 4, 256, 64);
+  if (bx < 1) bx = 1;  // (units of fewer than four values: the any-shape entries only, the LDS kernels take widths of a multiple of 4)
+  const dim3 grid((unsigned)bx, (unsigned)a.batch);
   const int rc = skr::with_out_type(out_dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(skr::normalise_pass2<T>, grid, dim3(256), 0, s, (T*)out, scratch_f32, partials_f64, slots, unit, batch, with_base ? -1.0 : 0.0);
+    hipLaunchKernelGGL(skr::normalise_pass2<T>, grid, dim3(256), 0, s, (T*)out, a.scratch, a.partials, slots, unit, a.batch, a.with_base ? -1.0 : 0.0);
   });
   return rc != SKR_OK ? rc : skr::launch_status();
 }
@@ -801,6 +798,31 @@ extern "C" int skr_noise_offset(void* out, int32_t out_dtype, const uint64_t* se
   return rc != SKR_OK ? rc : skr::launch_status();
 }
 
+namespace skr {
+// the limits the three Pyramid entry points share: the sides of a plane, and the samples of a batch (gridDim.y of pass 2)
+constexpr int64_t PYR_MAX_SIDE = 32767, PYR_MAX_BATCH = 65535;
+
+// the fields every Pyramid launch shares; the any-shape entries add their axis descriptor
+static void pyramid_common_args(PyramidArgs& a, float* scratch_f32, double* partials_f64, int32_t* level_ws, const uint64_t* seeds_dev, uint64_t stream_base,
+                                uint64_t stream_levels, int64_t batch, int64_t lead, int64_t h, int64_t w, bool resize_h, double strength, int32_t depth, int32_t with_base) {
+  a.scratch = scratch_f32; a.partials = partials_f64; a.seeds = seeds_dev;
+  a.level_hw = level_ws; a.n_levels = level_ws + batch * PYR_MAX_LEVELS * 2;
+  a.stream_base = stream_base; a.stream_levels = stream_levels; a.batch = batch; a.lead = (int32_t)lead; a.h = (int32_t)h; a.w = (int32_t)w;
+  a.resize_h = resize_h ? 1 : 0; a.depth = depth; a.with_base = with_base; a.strength = (float)strength;
+}
+
+using PyramidKernel = void (*)(const PyramidArgs);
+static PyramidKernel pyramid_kernel(PyramidForm form) {
+  switch (form) {
+    case PyramidForm::Strip256: return pyramid_pass1<true, 256>;
+    case PyramidForm::Strip512: return pyramid_pass1<true, 512>;
+    case PyramidForm::Strip1024: return pyramid_pass1<true, 1024>;
+    case PyramidForm::Uni: return pyramid_pass1<true, 1024, true>;
+    default: return pyramid_pass1<false, 512>;
+  }
+}
+}  // namespace skr
+
 extern "C" int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f32, double* partials_f64, int32_t* level_ws /* [batch*17] */,
                                  const uint64_t* seeds_dev, uint64_t stream_base, uint64_t stream_levels, int64_t batch, int64_t lead, int64_t h, int64_t w,
                                  int32_t resize_h, double strength, int32_t depth, int32_t with_base, void* stream) {
@@ -808,54 +830,21 @@ extern "C" int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f3
   if (batch < 0 || lead < 1 || h < 1 || w < 1 || depth < 0) return SKR_ERR_SHAPE;
   if (batch == 0) return SKR_OK;
   if (!out || !scratch_f32 || !partials_f64 || !seeds_dev || !level_ws) return SKR_ERR_NULL;
-  if (w % 4 != 0 || h > 32767 || w > 32767) return SKR_ERR_UNSUPPORTED;
+  if (w % 4 != 0 || h > skr::PYR_MAX_SIDE || w > skr::PYR_MAX_SIDE) return SKR_ERR_UNSUPPORTED;
   if (!resize_h && h != 1) return SKR_ERR_SHAPE;
-  if (batch * lead > 0x7fffffffll || batch > 65535) return SKR_ERR_UNSUPPORTED;
-  // LDS stage for levels >= 1: every level is at most half the previous size per resized axis (r >= 2, and
-  // level i >= 2 shrinks by r^i >= 4), so sum_{l>=1} h_l*w_l <= h*w/4 * (1 + 1/16 + ...) (1-D: w/2 * (1 + 1/4 + ...))
-  const int64_t bound = resize_h ? (h / 2) * (w / 2) + (h / 8) * (w / 8) + (h / 32) * (w / 32) + 64 : w / 2 + w / 8 + w / 32 + 64;
-  if (bound > skr::PYR_LDS_FLOATS) return SKR_ERR_UNSUPPORTED;
+  if (batch * lead > 0x7fffffffll || batch > skr::PYR_MAX_BATCH) return SKR_ERR_UNSUPPORTED;
+  // tuning switches, read at the first draw: SKR_PYR_NO_UNI, and SKR_PYR_MODE = 1 generic, 2 strip/512, 3 strip/256, 4 strip/1024
+  static const bool no_uni = skr::env_flag("SKR_PYR_NO_UNI");
+  static const int forced = (int)skr::env_int("SKR_PYR_MODE", 0);
+  const skr::PyramidRoute route = skr::choose_pyramid_route(h, w, resize_h != 0, no_uni, forced);
+  if (route.status != SKR_OK) return route.status;
   skr::PyramidArgs a;
-  a.scratch = scratch_f32; a.partials = partials_f64; a.seeds = seeds_dev;
-  a.level_hw = level_ws; a.n_levels = level_ws + batch * skr::PYR_MAX_LEVELS * 2;
-  a.stream_base = stream_base; a.stream_levels = stream_levels; a.batch = batch; a.lead = (int32_t)lead; a.h = (int32_t)h; a.w = (int32_t)w;
-  a.resize_h = resize_h; a.depth = depth; a.with_base = with_base; a.strength = (float)strength;
+  skr::pyramid_common_args(a, scratch_f32, partials_f64, level_ws, seeds_dev, stream_base, stream_levels, batch, lead, h, w, resize_h != 0, strength, depth, with_base);
+  a.ytab_off = route.ytab_off;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  size_t lds_bytes = sizeof(float) * (size_t)bound;  // (the level geometry is worked out inside pass 1)
-  // rows a whole number of waves wide (w % 256 == 0) under 1024-lane strips: the vertical taps of the cached levels in a table behind the level planes
-  static const bool no_uni = getenv("SKR_PYR_NO_UNI") != nullptr;
-  const size_t ytab_bytes = sizeof(float2) * (size_t)(skr::PYR_UNROLLED - 1) * (size_t)h;
-  const bool uni = !no_uni && resize_h && (w / 4) % 64 == 0 && 1024 % (w / 4) == 0 && h / (1024 / (w / 4)) >= 12 && lds_bytes + ytab_bytes <= 156 * 1024;
-  a.ytab_off = uni ? (int32_t)((bound + 1) & ~(int64_t)1) : -1;  // (8-byte entries)
-  if (uni) lds_bytes = sizeof(float) * (size_t)a.ytab_off + ytab_bytes;
-  if (lds_bytes > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(skr::pyramid_pass1<true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return SKR_ERR_UNSUPPORTED;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(skr::pyramid_pass1<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return SKR_ERR_UNSUPPORTED;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(skr::pyramid_pass1<true, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return SKR_ERR_UNSUPPORTED;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(skr::pyramid_pass1<true, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return SKR_ERR_UNSUPPORTED;
-  }
-  const int64_t w4 = w / 4;
-  const dim3 grid1((unsigned)(batch * lead));
-  static const int forced = [] { const char* e = getenv("SKR_PYR_MODE"); return e ? atoi(e) : 0; }();  // tuning switch: 1 generic, 2 strip/512, 3 strip/256, 4 strip/1024
-  // strips pay off when a thread visits enough rows to amortise its tap table; small planes get there with 256-lane blocks
-  const bool strip512 = skr::PYR_THREADS % w4 == 0 && h / (skr::PYR_THREADS / w4) >= 12;
-  const bool strip256 = lds_bytes <= 48 * 1024 && 256 % w4 == 0 && h / (256 / w4) >= 12;
-  // the strip kernel holds 165 registers, so a CU runs ONE 512-lane block (2 waves per SIMD) whatever the LDS would allow: where the
-  // runs stay long enough, 1024 lanes (4 waves per SIMD at 128 registers, 19 of them spilled) hide more of the Philox / Box-Muller
-  // dependency chains -- 72.9 against 75.9 us per draw at 64 x (4, 256, 256)
-  const bool strip1024 = 1024 % w4 == 0 && h / (1024 / w4) >= 12;
-  const int mode = forced ? forced : (strip1024 ? 4 : (strip512 ? 2 : (strip256 ? 3 : 1)));
-  if (mode == 4 && strip1024 && uni) hipLaunchKernelGGL((skr::pyramid_pass1<true, 1024, true>), grid1, dim3(1024), lds_bytes, s, a);
-  else if (mode == 4 && strip1024) hipLaunchKernelGGL((skr::pyramid_pass1<true, 1024>), grid1, dim3(1024), lds_bytes, s, a);
-  else if (mode == 2 && strip512) hipLaunchKernelGGL((skr::pyramid_pass1<true, 512>), grid1, dim3(512), lds_bytes, s, a);
-  else if (mode == 3 && strip256) hipLaunchKernelGGL((skr::pyramid_pass1<true, 256>), grid1, dim3(256), lds_bytes, s, a);
-  else hipLaunchKernelGGL((skr::pyramid_pass1<false, 512>), grid1, dim3(512), lds_bytes, s, a);
-  if (hipGetLastError() != hipSuccess) return SKR_ERR_LAUNCH;
-  const int64_t unit = lead * h * w;
-  int64_t bx = (unit / 4 + 255) / 256;
-  if (bx > 64) bx = 64;
-  dim3 grid((unsigned)bx, (unsigned)batch);
-  return normalise(out, out_dtype, scratch_f32, partials_f64, lead, unit, batch, with_base, grid, s);
+  const int rc = skr::launch_lds(skr::pyramid_kernel(route.form), dim3((unsigned)(batch * lead)), dim3((unsigned)route.threads), route.lds_bytes, s, a);
+  if (rc != SKR_OK) return rc;
+  return normalise(out, out_dtype, a, lead, lead * h * w, s);
 }
 
 static int pyramid_nd_impl(void* out, int32_t out_dtype, float* scratch_f32, float* levels_f32, double* partials_f64, int32_t n_slots,
@@ -867,37 +856,29 @@ static int pyramid_nd_impl(void* out, int32_t out_dtype, float* scratch_f32, flo
   for (int i = 0; i < nd; ++i) if (shape[i] < 1 || shape[i] > 0x7fffffffll) return SKR_ERR_SHAPE;
   if (batch == 0) return SKR_OK;
   if (!out || !scratch_f32 || !levels_f32 || !partials_f64 || !seeds_dev || !level_ws) return SKR_ERR_NULL;
-  skr::PyramidAnyArgs q;
-  skr::PyramidArgs& a = q.p;
-  // right-align the axes in the 4-slot descriptor
-  const int pad = 4 - nd;
-  for (int i = 0; i < 4; ++i) a.dim[i] = i < pad ? 1 : (int32_t)shape[i - pad];
-  a.nd = nd; a.axis_a = axis_a < 0 ? -1 : axis_a + pad; a.axis_b = axis_b + pad; a.ytab_off = -1;
   const int64_t h = axis_a < 0 ? 1 : shape[axis_a], w = shape[axis_b];
   int64_t unit = 1;
   for (int i = 0; i < nd; ++i) unit *= shape[i];
   const int64_t lead = unit / (h * w);
-  if (h > 32767 || w > 32767 || batch > 65535 || n_slots > 65535 || lead > 0x7fffffffll) return SKR_ERR_UNSUPPORTED;
-  a.scratch = scratch_f32; a.partials = partials_f64; a.seeds = seeds_dev;
-  a.level_hw = level_ws; a.n_levels = level_ws + batch * skr::PYR_MAX_LEVELS * 2;
-  a.stream_base = stream_base; a.stream_levels = stream_levels; a.batch = batch; a.lead = (int32_t)lead; a.h = (int32_t)h; a.w = (int32_t)w;
-  a.resize_h = axis_a >= 0 ? 1 : 0; a.depth = depth; a.with_base = with_base; a.strength = (float)strength;
+  if (h > skr::PYR_MAX_SIDE || w > skr::PYR_MAX_SIDE || batch > skr::PYR_MAX_BATCH || n_slots > 65535 || lead > 0x7fffffffll) return SKR_ERR_UNSUPPORTED;
+  skr::PyramidAnyArgs q;
+  skr::PyramidArgs& a = q.p;
+  skr::pyramid_common_args(a, scratch_f32, partials_f64, level_ws, seeds_dev, stream_base, stream_levels, batch, lead, h, w, axis_a >= 0, strength, depth, with_base);
+  // right-align the axes in the 4-slot descriptor
+  const int pad = 4 - nd;
+  for (int i = 0; i < 4; ++i) a.dim[i] = i < pad ? 1 : (int32_t)shape[i - pad];
+  a.nd = nd; a.axis_a = axis_a < 0 ? -1 : axis_a + pad; a.axis_b = axis_b + pad;
   q.levels = levels_f32; q.cap = unit; q.n_slots = n_slots;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(skr::pyramid_geometry, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, a);
-  if (hipGetLastError() != hipSuccess) return SKR_ERR_LAUNCH;
-  int64_t lb = (unit / 16 + 255) / 256;  // the levels >= 1 together hold fewer than `unit` values
+  if (const int rc = skr::launch_status(); rc != SKR_OK) return rc;
+  int64_t lb = skr::grid_blocks(unit / 16, 256, 1024);  // the levels >= 1 together hold fewer than `unit` values
   if (lb < 1) lb = 1;
-  if (lb > 1024) lb = 1024;
   hipLaunchKernelGGL(skr::pyramid_levels_any, dim3((unsigned)lb, (unsigned)batch), dim3(256), 0, s, q);
-  if (hipGetLastError() != hipSuccess) return SKR_ERR_LAUNCH;
+  if (const int rc = skr::launch_status(); rc != SKR_OK) return rc;
   hipLaunchKernelGGL(skr::pyramid_pass1_any, dim3((unsigned)n_slots, (unsigned)batch), dim3(256), 0, s, q);
-  if (hipGetLastError() != hipSuccess) return SKR_ERR_LAUNCH;
-  int64_t bx = (unit / 4 + 255) / 256;
-  if (bx > 64) bx = 64;
-  if (bx < 1) bx = 1;
-  dim3 grid((unsigned)bx, (unsigned)batch);
-  return normalise(out, out_dtype, scratch_f32, partials_f64, n_slots, unit, batch, with_base, grid, s);
+  if (const int rc = skr::launch_status(); rc != SKR_OK) return rc;
+  return normalise(out, out_dtype, a, n_slots, unit, s);
 }
 
 extern "C" int skr_noise_pyramid_any(void* out, int32_t out_dtype, float* scratch_f32, float* levels_f32, double* partials_f64, int32_t n_slots,

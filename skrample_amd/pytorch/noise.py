@@ -360,69 +360,65 @@ class Pyramid(TensorNoiseCommon):
         return self._batch(tuple(self.shape), self._seeds, self._next_stream(), None, self.props, self.dtype, self._state, with_base=False)[0]
 
     @classmethod
+    def _plan(cls, unit_shape, props) -> tuple[str, tuple, tuple]:
+        """How a unit is drawn: (entry point, its shape arguments, what its workspaces are keyed by).  Resized axes at the end of the
+        unit: the LDS kernels (skr_noise_pyramid: lead, h, w, resize_h), which leave the shapes they refuse to skr_noise_pyramid_any
+        under the same arguments; resized axes anywhere else: the any-shape kernels with an axis descriptor (skr_noise_pyramid_nd)."""
+        geometry = cls._geometry(unit_shape, props)
+        if geometry is not None:
+            lead, h, w, resize_h = geometry
+            return "skr_noise_pyramid", (lead, h, w, 1 if resize_h else 0), ("ws", lead, h, w)
+        shape, axis_a, axis_b = cls._axes_nd(unit_shape, props)
+        return "skr_noise_pyramid_nd", (len(shape), (ctypes.c_int64 * len(shape))(*shape), axis_a, axis_b), ("ws_nd", tuple(shape), axis_a, axis_b)
+
+    @staticmethod
+    def _workspace(state: dict, key, allocate) -> tuple:
+        "the buffers under `key`, allocated at first use; a new key (another batch or shape) drops all else but the frozen stream of a static generator"
+        if key not in state:
+            for k in [k for k in state if k != "static_stream"]:
+                del state[k]  # (also the any-shape workspaces of a previous shape)
+            state[key] = allocate()
+        return state[key]
+
+    @classmethod
     def _batch(cls, unit_shape, seeds, stream, step, props, dtype, state, with_base: bool = True):
         # static: the pyramid component is frozen at the first draw (same streams every time), only the base changes
         stream_levels = state.setdefault("static_stream", stream) if props.static else stream
-        geometry = cls._geometry(unit_shape, props)
-        if geometry is None:
-            return cls._batch_nd(unit_shape, seeds, stream, stream_levels, props, dtype, state, with_base)
-        lead, h, w, resize_h = geometry
-        batch = seeds.shape[0]
-        dev = seeds.device
-        key = ("ws", batch, lead, h, w)
-        if key not in state:
-            for k in [k for k in state if k != "static_stream"]:
-                del state[k]  # (also drops the any-shape workspaces of a previous shape)
-            state[key] = (
-                torch.empty(batch * lead * h * w, dtype=torch.float32, device=dev),
-                torch.empty(batch * lead * 2, dtype=torch.float64, device=dev),
-                torch.empty(batch * (PYRAMID_MAX_LEVELS * 2 + 1), dtype=torch.int32, device=dev),
-            )
-        scratch, partials, levels = state[key]
-        out = torch.empty((batch, *unit_shape), dtype=dtype, device=dev)
-        lib, hstream = _launch_ctx(seeds)
-        tail = (seeds.data_ptr(), stream, stream_levels, batch, lead, h, w, 1 if resize_h else 0, float(props.strength), int(min(props.depth, 1 << 20)), 1 if with_base else 0, hstream)
-        status = _hip.SKR_ERR_UNSUPPORTED if state.get("any_shape") else lib.skr_noise_pyramid(out.data_ptr(), _hip.DTYPE_CODE[dtype], scratch.data_ptr(), partials.data_ptr(), levels.data_ptr(), *tail)
-        if status == _hip.SKR_ERR_UNSUPPORTED:
-            # planes too large for the LDS level stage, or a width that is not a multiple of 4: levels in global memory
-            if "any_shape" not in state:
-                slots = max(1, min(1024, -(-(lead * h * w) // (4 * 256 * 8))))
-                state["any_shape"] = (torch.empty(batch * lead * h * w, dtype=torch.float32, device=dev), torch.empty(batch * slots * 2, dtype=torch.float64, device=dev), slots)
-            level_ws, partials_any, slots = state["any_shape"]
-            status = lib.skr_noise_pyramid_any(out.data_ptr(), _hip.DTYPE_CODE[dtype], scratch.data_ptr(), level_ws.data_ptr(), partials_any.data_ptr(), slots, levels.data_ptr(), *tail)
-            _hip.check(status, "skr_noise_pyramid_any")
-        else:
-            _hip.check(status, "skr_noise_pyramid")
-        state["levels"] = levels  # device table of the last draw: [batch][8][2] sizes, then [batch] counts
-        return out
-
-    @classmethod
-    def _batch_nd(cls, unit_shape, seeds, stream, stream_levels, props, dtype, state, with_base: bool):
-        "resized axes anywhere in the unit: the any-shape kernels with an axis descriptor (skr_noise_pyramid_nd)"
-        shape, axis_a, axis_b = cls._axes_nd(unit_shape, props)
+        entry, shape_args, (kind, *shape_key) = cls._plan(unit_shape, props)
         batch, dev, unit = seeds.shape[0], seeds.device, math.prod(unit_shape)
-        key = ("ws_nd", batch, tuple(shape), axis_a, axis_b)
-        if key not in state:
-            for k in [k for k in state if k != "static_stream"]:
-                del state[k]
-            slots = max(1, min(1024, -(-unit // (4 * 256 * 8))))
-            state[key] = (
-                torch.empty(batch * unit, dtype=torch.float32, device=dev),  # scratch
-                torch.empty(batch * unit, dtype=torch.float32, device=dev),  # level normals
-                torch.empty(batch * slots * 2, dtype=torch.float64, device=dev),
-                torch.empty(batch * (PYRAMID_MAX_LEVELS * 2 + 1), dtype=torch.int32, device=dev),
-                slots,
-            )
-        scratch, level_ws, partials, levels, slots = state[key]
+        slots = max(1, min(1024, -(-unit // (4 * 256 * 8))))  # partial (sum, sum of squares) pairs per sample of the any-shape kernels
+
+        def empty(per_sample, kind=torch.float32):
+            return torch.empty(batch * per_sample, dtype=kind, device=dev)
+
+        def any_shape():  # what the any-shape kernels add: the level normals in global memory, and their partial pairs
+            return empty(unit), empty(2 * slots, torch.float64)
+
+        def allocate():  # pass 1's sums, the level table ([8][2] sizes and a count), then the entry's own (LDS kernels: a partial pair per leading slice)
+            own = (empty(2 * shape_args[0], torch.float64),) if entry == "skr_noise_pyramid" else any_shape()
+            return empty(unit), empty(PYRAMID_MAX_LEVELS * 2 + 1, torch.int32), *own
+
+        scratch, levels, *own = cls._workspace(state, (kind, batch, *shape_key), allocate)
         out = torch.empty((batch, *unit_shape), dtype=dtype, device=dev)
         lib, hstream = _launch_ctx(seeds)
-        status = lib.skr_noise_pyramid_nd(
-            out.data_ptr(), _hip.DTYPE_CODE[dtype], scratch.data_ptr(), level_ws.data_ptr(), partials.data_ptr(), slots, levels.data_ptr(), seeds.data_ptr(),
-            stream, stream_levels, batch, len(shape), (ctypes.c_int64 * len(shape))(*shape), axis_a, axis_b, float(props.strength), int(min(props.depth, 1 << 20)),
-            1 if with_base else 0, hstream,
-        )  # fmt: skip
-        _hip.check(status, "skr_noise_pyramid_nd")
-        state["levels"] = levels
+        common = (levels.data_ptr(), seeds.data_ptr(), stream, stream_levels, batch, *shape_args, float(props.strength), int(min(props.depth, 1 << 20)), 1 if with_base else 0, hstream)
+
+        def launch(name, buffers, *n_slots):
+            return getattr(lib, name)(out.data_ptr(), _hip.DTYPE_CODE[dtype], scratch.data_ptr(), *[b.data_ptr() for b in buffers], *n_slots, *common)
+
+        if entry == "skr_noise_pyramid_nd":
+            status = launch(entry, own, slots)
+        else:
+            status = _hip.SKR_ERR_UNSUPPORTED if "any_shape" in state else launch(entry, own)
+            if status == _hip.SKR_ERR_UNSUPPORTED:
+                # planes too large for the LDS level stage, or a width that is not a multiple of 4: levels in global memory.  Their buffers
+                # are allocated only now, and remembered, so that later draws of this shape go there at once
+                entry = "skr_noise_pyramid_any"
+                if "any_shape" not in state:
+                    state["any_shape"] = any_shape()
+                status = launch(entry, state["any_shape"], slots)
+        _hip.check(status, entry)
+        state["levels"] = levels  # device table of the last draw: [batch][8][2] sizes, then [batch] counts
         return out
 
 

@@ -1,6 +1,7 @@
 """The status every elementwise entry point answers a malformed raw call with, and the order of its checks: what tests/test_masked_gpu.py
 pins for skr_step_launch_masked, for skr_step_launch, the three table forms, skr_program_create, skr_step_backward_launch, skr_error_mean,
-skr_power_blend, skr_power_blend_backward and skr_noise_random.
+skr_power_blend, skr_power_blend_backward, skr_noise_random and the three Pyramid generators (skr_noise_pyramid, skr_noise_pyramid_any,
+skr_noise_pyramid_nd; their units and the one exception to "before anything is launched" stand with their tables at the end).
 
 One 2048-element chunk per operand, three operands, bf16 (and one fp32 case per entry point).  Every table row is refused before anything is
 launched -- the outputs stay zero --; the one well-formed control per entry point follows its table.  A row that is wrong in two ways pins
@@ -413,3 +414,143 @@ def test_noise_random(bf, f32):
         torch.cuda.synchronize()
         assert b.out0.any()
         b.out0.zero_()
+
+
+# ---- the Pyramid generators: 2 samples of a 256-element unit, bf16 ----------------------------------------------------------------------------
+# Every row but the dtype rows is refused before anything is launched.  The generators learn their output dtype last, in pass 2: a
+# call that is well formed but for its dtype runs pass 1 on its (valid) workspaces and leaves `out` alone, so those rows carry whole
+# buffers.  Rows that name a shape beyond the buffers are refused by the check they pin, ahead of any launch.
+PYR_BATCH, PYR_UNIT = 2, 256
+PYR_POINTERS = {"skr_noise_pyramid": ("out", "scratch", "partials", "table", "seeds"), "skr_noise_pyramid_any": ("out", "scratch", "normals", "partials", "table", "seeds")}
+PYR_POINTERS["skr_noise_pyramid_nd"] = PYR_POINTERS["skr_noise_pyramid_any"]
+
+
+class PyramidBox:
+    def __init__(self, dev):
+        self.out = torch.zeros(PYR_BATCH * PYR_UNIT, dtype=torch.bfloat16, device=dev)
+        self.scratch, self.normals = (torch.zeros(PYR_BATCH * PYR_UNIT, dtype=torch.float32, device=dev) for _ in range(2))
+        self.partials = torch.zeros(PYR_BATCH * 2, dtype=torch.float64, device=dev)  # one pair per sample: lead = 1, n_slots = 1
+        self.table = torch.zeros(PYR_BATCH * 17, dtype=torch.int32, device=dev)
+        self.seeds = torch.tensor([11, 12], dtype=torch.int64, device=dev)
+        self.stream = _hip.current_stream_ptr(dev)
+
+    def call(self, entry, **change):
+        "the well-formed call of `entry` with `change` applied: a pointer's name -> None, or an argument's name -> its value"
+        a = dict(dtype=_hip.BF16, n_slots=1, batch=PYR_BATCH, lead=1, h=16, w=16, resize_h=1, depth=99, nd=3, shape=(8, 2, 16), axis_a=0, axis_b=2)
+        a.update({name: getattr(self, name).data_ptr() for name in PYR_POINTERS[entry]})
+        assert not set(change) - set(a), change
+        a.update(change)
+        lib = _hip.load()
+        tail = (0.3, a["depth"], 1, self.stream)
+        if entry == "skr_noise_pyramid":
+            return lib.skr_noise_pyramid(a["out"], a["dtype"], a["scratch"], a["partials"], a["table"], a["seeds"], 0, 0, a["batch"], a["lead"], a["h"], a["w"], a["resize_h"], *tail)
+        head = (a["out"], a["dtype"], a["scratch"], a["normals"], a["partials"], a["n_slots"], a["table"], a["seeds"], 0, 0, a["batch"])
+        if entry == "skr_noise_pyramid_any":
+            return lib.skr_noise_pyramid_any(*head, a["lead"], a["h"], a["w"], a["resize_h"], *tail)
+        shape = None if a["shape"] is None else (ctypes.c_int64 * len(a["shape"]))(*a["shape"])
+        return lib.skr_noise_pyramid_nd(*head, a["nd"], shape, a["axis_a"], a["axis_b"], *tail)
+
+    def run(self, entry, rows, controls):
+        for label, change, status in rows:
+            assert self.call(entry, **change) == status, (entry, label)
+        torch.cuda.synchronize()
+        assert not self.out.any(), entry
+        for change in controls:
+            assert self.call(entry, **change) == OK, (entry, change)
+            torch.cuda.synchronize()
+            assert self.out.any(), (entry, change)
+            self.out.zero_()
+
+
+@pytest.fixture(scope="module")
+def pyr(dev):
+    return PyramidBox(dev)
+
+
+def null_rows(entry):
+    nothing = {name: None for name in PYR_POINTERS[entry]}
+    return [("an empty batch before the pointers and the dtype", dict(batch=0, dtype=BAD, **nothing), OK)] + [(f"no {name}", {name: None}, ERR_NULL) for name in nothing]
+
+
+def test_noise_pyramid(pyr):
+    rows = [  # (label, what differs from the well-formed call, status)
+        ("batch negative", dict(batch=-1), ERR_SHAPE),
+        ("no leading slice", dict(lead=0), ERR_SHAPE),
+        ("no row", dict(h=0), ERR_SHAPE),
+        ("no column", dict(w=0), ERR_SHAPE),
+        ("depth negative", dict(depth=-1), ERR_SHAPE),
+        ("the sizes before the empty batch", dict(batch=0, lead=0), ERR_SHAPE),
+        ("the sizes before the pointers", dict(out=None, depth=-1), ERR_SHAPE),
+        ("an empty batch before the width", dict(batch=0, w=18), OK),
+        *null_rows("skr_noise_pyramid"),
+        ("the pointers before the width", dict(seeds=None, w=18), ERR_NULL),
+        ("a width of no multiple of 4", dict(w=18), ERR_UNSUPPORTED),
+        ("h above 32767", dict(h=32768), ERR_UNSUPPORTED),
+        ("w above 32767", dict(w=32768), ERR_UNSUPPORTED),
+        ("the width before the rows of a unit without resized rows", dict(resize_h=0, h=2, w=18), ERR_UNSUPPORTED),
+        ("the sides before the rows of a unit without resized rows", dict(resize_h=0, h=32768), ERR_UNSUPPORTED),
+        ("rows without resized rows", dict(resize_h=0, h=2), ERR_SHAPE),
+        ("rows without resized rows before the batch", dict(resize_h=0, h=2, batch=65536), ERR_SHAPE),
+        ("batch above 65535", dict(batch=65536), ERR_UNSUPPORTED),
+        ("more than 2^31 - 1 slices", dict(lead=1 << 31), ERR_UNSUPPORTED),
+        ("the level stage: 42 708 floats for 38 * 1024", dict(h=400, w=400), ERR_UNSUPPORTED),
+        ("the level stage at its edge", dict(h=384, w=380), ERR_UNSUPPORTED),
+        ("the level stage before the dtype", dict(h=400, w=400, dtype=BAD), ERR_UNSUPPORTED),
+        ("no such dtype", dict(dtype=BAD), ERR_DTYPE),
+        ("dtype absent", dict(dtype=_hip.NONE), ERR_DTYPE),
+    ]
+    pyr.run("skr_noise_pyramid", rows, [dict(), dict(resize_h=0, h=1, w=256)])
+
+
+ND_ROWS = [  # the checks of the any-shape kernels, shared by skr_noise_pyramid_any and skr_noise_pyramid_nd
+    ("batch negative", dict(batch=-1), ERR_SHAPE),
+    ("depth negative", dict(depth=-1), ERR_SHAPE),
+    ("no partial slot", dict(n_slots=0), ERR_SHAPE),
+    ("the counts before the empty batch", dict(batch=0, n_slots=0), ERR_SHAPE),
+    ("the counts before the pointers", dict(out=None, depth=-1), ERR_SHAPE),
+    ("batch above 65535", dict(batch=65536), ERR_UNSUPPORTED),
+    ("more than 65535 partial slots", dict(n_slots=65536), ERR_UNSUPPORTED),
+    ("the pointers before the limits", dict(table=None, n_slots=65536), ERR_NULL),
+    ("the limits before the dtype", dict(n_slots=65536, dtype=BAD), ERR_UNSUPPORTED),
+    ("no such dtype", dict(dtype=BAD), ERR_DTYPE),
+    ("dtype absent", dict(dtype=_hip.NONE), ERR_DTYPE),
+]
+
+
+def test_noise_pyramid_any(pyr):
+    rows = [
+        ("no leading slice", dict(lead=0), ERR_SHAPE),
+        ("no row", dict(h=0), ERR_SHAPE),
+        ("no column", dict(w=0), ERR_SHAPE),
+        ("rows without resized rows", dict(resize_h=0, h=2), ERR_SHAPE),
+        ("the sizes before the empty batch", dict(batch=0, resize_h=0, h=2), ERR_SHAPE),
+        ("more than 2^31 - 1 slices", dict(lead=1 << 31), ERR_SHAPE),
+        *null_rows("skr_noise_pyramid_any"),
+        *ND_ROWS,
+        ("h above 32767", dict(h=32768), ERR_UNSUPPORTED),
+        ("w above 32767", dict(w=32768), ERR_UNSUPPORTED),
+    ]
+    pyr.run("skr_noise_pyramid_any", rows, [dict(), dict(h=14, w=18), dict(resize_h=0, h=1, w=250)])
+
+
+def test_noise_pyramid_nd(pyr):
+    rows = [
+        ("no axis", dict(nd=0), ERR_SHAPE),
+        ("five axes", dict(nd=5), ERR_SHAPE),
+        ("no shape", dict(shape=None), ERR_SHAPE),
+        ("the axis count before the empty batch", dict(batch=0, nd=0), ERR_SHAPE),
+        ("axis b negative", dict(axis_b=-1), ERR_SHAPE),
+        ("axis b beyond the unit", dict(axis_b=3), ERR_SHAPE),
+        ("axis a not ahead of axis b", dict(axis_a=2), ERR_SHAPE),
+        ("axis a below -1", dict(axis_a=-2), ERR_SHAPE),
+        ("the axes before the empty batch", dict(batch=0, axis_a=2), ERR_SHAPE),
+        ("an empty axis", dict(shape=(8, 0, 16)), ERR_SHAPE),
+        ("an axis of 2^31", dict(shape=(1 << 31, 2, 16)), ERR_SHAPE),
+        ("the shape before the pointers", dict(out=None, shape=(8, 0, 16)), ERR_SHAPE),
+        *null_rows("skr_noise_pyramid_nd"),
+        *ND_ROWS,
+        ("h above 32767", dict(shape=(32768, 2, 16)), ERR_UNSUPPORTED),
+        ("w above 32767", dict(shape=(8, 2, 32768)), ERR_UNSUPPORTED),
+        ("more than 2^31 - 1 slices", dict(shape=((1 << 31) - 1, 2, 16), axis_a=-1), ERR_UNSUPPORTED),
+    ]
+    pyr.run("skr_noise_pyramid_nd", rows, [dict(), dict(axis_a=-1), dict(nd=2, shape=(16, 16), axis_a=0, axis_b=1)])

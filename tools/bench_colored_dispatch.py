@@ -1,13 +1,16 @@
 """Host cost of enqueueing a launch: wall time of a loop of calls of one entry point with no synchronisation inside (one after), per
 call.  The units are small, so that the GPU drains the queue faster than the host fills it and the loop measures the launchers' own
-dispatch -- checks, route decision, dtype dispatch, `hipFuncSetAttribute`, `getenv`, the launches.  Two unit sets: colored draws
-(`skr_noise_colored` / `skr_noise_colored_any`, the default; the tool is named after them) and the step family.
+dispatch -- checks, route decision, dtype dispatch, `hipFuncSetAttribute`, `getenv`, the launches.  Three unit sets: colored draws
+(`skr_noise_colored` / `skr_noise_colored_any`, the default; the tool is named after them), the step family and Pyramid draws.
 
     python tools/bench_colored_dispatch.py                       # the library SKR_HIP_LIB names, else the in-tree one: one JSON line
     python tools/bench_colored_dispatch.py --ab OLD.so NEW.so    # A/B: fresh processes, alternating, --rounds each (default 3)
     python tools/bench_colored_dispatch.py --units step ...      # the step family instead: one small launch each of skr_step_launch (bf16,
                                                                  # 4 operands, one chunk per sample), the masked and the backward launch,
                                                                  # skr_power_blend and skr_error_mean
+    python tools/bench_colored_dispatch.py --units pyramid ...   # Pyramid draws, a unit per arm: generic, strip / 256, UNI (LDS opt-in), a
+                                                                 # width skr_noise_pyramid refuses followed by skr_noise_pyramid_any (what
+                                                                 # the Python layer does at such a shape's first draw), skr_noise_pyramid_nd
 
 Per process and unit: the median over --loops loops (default 15) of --calls calls (default 200), in microseconds per call.  --ab
 prints every process's medians, then per unit the median of each library's medians, their difference and the old library's own
@@ -68,6 +71,42 @@ def step_calls() -> dict:
     }
 
 
+def pyramid_calls() -> dict:
+    "{unit: call} of the Pyramid entry points: 2 samples, bf16"
+    import torch
+    from skrample_amd import _hip
+    from skrample_amd.pytorch import noise as PN
+
+    lib, dev = _hip.load(), torch.device("cuda:0")
+    st, seeds = _hip.current_stream_ptr(dev), PN.seeds_tensor([7, 8], dev)
+    def calls_of(unit):
+        "the calls that draw `unit` = (lead, h, w), or its axes 0 and 2, into buffers of their own"
+        n = unit[0] * unit[1] * unit[2]
+        res = torch.empty((BATCH, *unit), dtype=torch.bfloat16, device=dev)
+        scratch, normals = (torch.empty(BATCH * n, dtype=torch.float32, device=dev) for _ in range(2))
+        partials = torch.empty(BATCH * unit[0] * 2, dtype=torch.float64, device=dev)  # (a pair per leading slice; the any-shape calls ask for one slot)
+        table = torch.empty(BATCH * 17, dtype=torch.int32, device=dev)
+        shape = (ctypes.c_int64 * 3)(*unit)
+        head, tail = (res.data_ptr(), _hip.BF16, scratch.data_ptr()), (table.data_ptr(), seeds.data_ptr(), 0, 0, BATCH)
+
+        def lds():
+            return lib.skr_noise_pyramid(*head, partials.data_ptr(), *tail, *unit, 1, 0.3, 99, 1, st)
+
+        def any_shape():
+            return lib.skr_noise_pyramid_any(*head, normals.data_ptr(), partials.data_ptr(), 1, *tail, *unit, 1, 0.3, 99, 1, st)
+
+        def refused():
+            return any_shape() if lds() == _hip.SKR_ERR_UNSUPPORTED else -1
+
+        def nd():
+            return lib.skr_noise_pyramid_nd(*head, normals.data_ptr(), partials.data_ptr(), 1, *tail, 3, shape, 0, 2, 0.3, 99, 1, st)
+
+        return {"lds": lds, "refused": refused, "nd": nd}
+
+    units = (("generic 1x16x16", (1, 16, 16), "lds"), ("strip256 1x96x128", (1, 96, 128), "lds"), ("uni 1x192x256", (1, 192, 256), "lds"), ("refused 1x30x90", (1, 30, 90), "refused"), ("nd 8x3x16 (0,2)", (8, 3, 16), "nd"))
+    return {name: calls_of(unit)[which] for name, unit, which in units}
+
+
 def measure(calls: int, loops: int, units: str = "colored") -> dict:
     sys.path.insert(0, ROOT)
     import torch
@@ -76,6 +115,8 @@ def measure(calls: int, loops: int, units: str = "colored") -> dict:
 
     if units == "step":
         return {name: timed(call, name, calls, loops) for name, call in step_calls().items()}
+    if units == "pyramid":
+        return {name: timed(call, name, calls, loops) for name, call in pyramid_calls().items()}
     lib, dev = _hip.load(), torch.device("cuda:0")
     out = {}
     for unit in UNITS:
@@ -103,7 +144,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--loops", type=int, default=15)
-    ap.add_argument("--units", choices=("colored", "step"), default="colored")
+    ap.add_argument("--units", choices=("colored", "step", "pyramid"), default="colored")
     a = ap.parse_args()
     if not a.ab:
         print(json.dumps({"lib": os.environ.get("SKR_HIP_LIB", "in-tree"), "us_per_call": measure(a.calls, a.loops, a.units)}))
@@ -118,13 +159,13 @@ def main() -> int:
                 return 1
             runs[side].append(json.loads(p.stdout.strip().splitlines()[-1])["us_per_call"])
             print(f"round {r + 1} {side}: {runs[side][-1]}", flush=True)
-    print("unit          old median  new median  new - old  old spread (max - min)   [us per call]")
+    print("unit              old median  new median  new - old  old spread (max - min)   [us per call]")
     inside = True
     for unit in runs["old"][0]:
         old, new = [x[unit] for x in runs["old"]], [x[unit] for x in runs["new"]]
         mo, mn, spread = statistics.median(old), statistics.median(new), max(old) - min(old)
         inside &= mn - mo <= spread
-        print(f"{unit:<13} {mo:10.3f}  {mn:10.3f}  {mn - mo:+9.3f}  {spread:10.3f}   {'inside' if mn - mo <= spread else 'OUTSIDE'}")
+        print(f"{unit:<17} {mo:10.3f}  {mn:10.3f}  {mn - mo:+9.3f}  {spread:10.3f}   {'inside' if mn - mo <= spread else 'OUTSIDE'}")
     return 0 if inside else 2
 
 

@@ -6,7 +6,9 @@
 //
 // Walks every dtype code from -2 to 5 through both families of with_dtype with a counting functor, every flag combination through
 // with_bools, check_ptrs over arrays with a missing / misaligned entry at every position (and n = 0 with no array), grid_blocks at its
-// edges, and the dtype rule against the nine (group a, group b, arithmetic) triples the step kernels exist for.
+// edges, the dtype rule against the nine (group a, group b, arithmetic) triples the step kernels exist for, and choose_pyramid_route over
+// a table of edge shapes, each with its neighbour across the threshold (the values: an exhaustive comparison with the decision this
+// function replaced, every h <= 1024, every w <= 1024, both switches).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -32,7 +34,84 @@ static void walk_dtypes() {
   }
 }
 
+// (h, w, resize_h, SKR_PYR_NO_UNI, SKR_PYR_MODE) -> status, form, threads, dynamic LDS bytes, offset of the tap table
+struct RouteRow { int64_t h, w; bool resize_h, no_uni; int forced; int status; skr::PyramidForm form; int threads; size_t lds_bytes; int32_t ytab_off; };
+using F = skr::PyramidForm;
+static const RouteRow ROUTES[] = {
+    // small planes: generic
+    {16, 16, true, false, 0, SKR_OK, F::Generic, 512, 528, -1},
+    // one resized axis: generic at every width
+    {1, 64, false, false, 0, SKR_OK, F::Generic, 512, 424, -1},
+    {1, 1024, false, false, 0, SKR_OK, F::Generic, 512, 2944, -1},
+    // w / 4 divides no block size: generic, 16043 floats of levels, LDS opt-in
+    {200, 300, true, false, 0, SKR_OK, F::Generic, 512, 64172, -1},
+    // 12 rows per 256-lane strip
+    {95, 128, true, false, 0, SKR_OK, F::Generic, 512, 13024, -1},
+    {96, 128, true, false, 0, SKR_OK, F::Strip256, 256, 13360, -1},
+    // 12 rows per 512-lane strip
+    {191, 128, true, false, 0, SKR_OK, F::Strip256, 256, 26128, -1},
+    {192, 128, true, false, 0, SKR_OK, F::Strip512, 512, 26464, -1},
+    // 12 rows per 1024-lane strip; rows of half a wave: no UNI (52 672 B, opt-in)
+    {383, 128, true, false, 0, SKR_OK, F::Strip512, 512, 52336, -1},
+    {384, 128, true, false, 0, SKR_OK, F::Strip1024, 1024, 52672, -1},
+    // UNI: rows a whole number of waves wide and 12 rows per 1024-lane strip
+    {191, 256, true, false, 0, SKR_OK, F::Strip512, 512, 52000, -1},
+    {192, 256, true, false, 0, SKR_OK, F::Uni, 1024, 58816, 13168},
+    {95, 512, true, false, 0, SKR_OK, F::Strip512, 512, 51328, -1},
+    {96, 512, true, false, 0, SKR_OK, F::Uni, 1024, 55744, 13168},
+    {47, 1024, true, false, 0, SKR_OK, F::Strip512, 512, 50048, -1},
+    {48, 1024, true, false, 0, SKR_OK, F::Uni, 1024, 54144, 13152},
+    // the cfg5 plane
+    {256, 256, true, false, 0, SKR_OK, F::Uni, 1024, 78336, 17536},
+    // rows of 256 lanes: one row per 256-lane strip
+    {11, 1024, true, false, 0, SKR_OK, F::Generic, 512, 11008, -1},
+    {12, 1024, true, false, 0, SKR_OK, F::Strip256, 256, 13056, -1},
+    // the tap table must fit 156 KiB behind the levels
+    {523, 256, true, false, 0, SKR_OK, F::Uni, 1024, 159456, 35680},
+    {524, 256, true, false, 0, SKR_OK, F::Strip1024, 1024, 143232, -1},
+    // the level stage holds 38 * 1024 floats
+    {383, 380, true, false, 0, SKR_OK, F::Generic, 512, 154736, -1},
+    {384, 380, true, false, 0, SKR_ERR_UNSUPPORTED, F::Generic, 0, 0, -1},
+    // (bound 42 708)
+    {400, 400, true, false, 0, SKR_ERR_UNSUPPORTED, F::Generic, 0, 0, -1},
+    // (30, 90) with a width the entry point takes
+    {30, 92, true, false, 0, SKR_OK, F::Generic, 512, 3148, -1},
+    // SKR_PYR_NO_UNI
+    {256, 256, true, true, 0, SKR_OK, F::Strip1024, 1024, 70144, -1},
+    {96, 512, true, true, 0, SKR_OK, F::Strip1024, 1024, 52672, -1},
+    // forced forms: the tap table stays laid out under a forced generic form
+    {256, 256, true, false, 1, SKR_OK, F::Generic, 512, 78336, 17536},
+    {256, 256, true, false, 2, SKR_OK, F::Strip512, 512, 78336, 17536},
+    // strip / 256 refuses more than 48 KiB: generic
+    {256, 256, true, false, 3, SKR_OK, F::Generic, 512, 78336, 17536},
+    {256, 256, true, false, 4, SKR_OK, F::Uni, 1024, 78336, 17536},
+    {96, 128, true, false, 1, SKR_OK, F::Generic, 512, 13360, -1},
+    // a forced form whose run is too short: generic
+    {96, 128, true, false, 2, SKR_OK, F::Generic, 512, 13360, -1},
+    {96, 128, true, false, 3, SKR_OK, F::Strip256, 256, 13360, -1},
+    {96, 128, true, false, 4, SKR_OK, F::Generic, 512, 13360, -1},
+    // forcing a smaller block than the shape would get
+    {192, 128, true, false, 3, SKR_OK, F::Strip256, 256, 26464, -1},
+    {384, 128, true, false, 2, SKR_OK, F::Strip512, 512, 52672, -1},
+    // (52 672 B)
+    {384, 128, true, false, 3, SKR_OK, F::Generic, 512, 52672, -1},
+    {16, 16, true, false, 4, SKR_OK, F::Generic, 512, 528, -1},
+    // no such mode: generic
+    {192, 128, true, false, 7, SKR_OK, F::Generic, 512, 26464, -1},
+};
+
+static void walk_pyramid_routes() {
+  for (const RouteRow& x : ROUTES) {
+    const skr::PyramidRoute r = skr::choose_pyramid_route(x.h, x.w, x.resize_h, x.no_uni, x.forced);
+    const bool same = r.status == x.status && (r.status != SKR_OK || (r.form == x.form && r.threads == x.threads && r.lds_bytes == x.lds_bytes && r.ytab_off == x.ytab_off));
+    if (!same) std::fprintf(stderr, "route of (%ld, %ld, %d, %d, %d): status %d form %d threads %d lds %zu ytab %d\n", (long)x.h, (long)x.w, (int)x.resize_h, (int)x.no_uni, x.forced,
+                            r.status, (int)r.form, r.threads, r.lds_bytes, (int)r.ytab_off);
+    CHECK(same);
+  }
+}
+
 int main() {
+  walk_pyramid_routes();
   walk_dtypes<skr::NoiseTypes, true>();
   walk_dtypes<skr::NoiseTypes, false>();
   walk_dtypes<skr::StepTypes, true>();

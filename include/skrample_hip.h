@@ -279,7 +279,7 @@ int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs,
  * Index validity is the caller's business, as with skr_step_launch_indexed: index_dev[0] + row_offset, and every
  * sample_index_dev[s] + row_offset, must name a row of the table.  The kernel neither checks nor clamps an index -- an entry outside
  * the table reads whatever lies there (or faults) -- so validate on the host before uploading (skrample_amd.graphs.CapturedLoop does).
- * There is no rolling form: no negative index, no absent-operand semantics.
+ * Neither entry takes a negative index or skips an operand: the rolling form is skr_step_launch_masked_rolling, below.
  */
 int skr_step_launch_masked_indexed(const skr_step_plan* plan, const void* const* inputs, void* out,
                                    const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel,
@@ -291,6 +291,37 @@ int skr_step_launch_masked_indexed_per_sample(const skr_step_plan* plan, const v
                                               const skr_step_row* rows_dev,
                                               const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
                                               int32_t row_offset, void* stream);
+
+/*
+ * The masked step of a rolling batch: skr_step_launch_masked_indexed_per_sample with samples that may sit at different positions of
+ * their in-painting loops, be plain (unmasked) requests, or be absent -- what skr_step_launch_rolling is to
+ * skr_step_launch_indexed_per_sample.  Structure, coverage, checks and error codes are those of
+ * skr_step_launch_masked_indexed_per_sample: `plan` fixes the structure only, skr_step_row and skr_step_mask are used unchanged, whole
+ * 2048-element chunks, samples made of whole chunks, one 16- or 32-bit dtype for operands, mask and output, fp32 arithmetic,
+ * 1..SKR_ROW_TERMS operands, mask_numel % 8 == 0, batch_stride mask_numel or 0; anything else is SKR_ERR_UNSUPPORTED ("one_trip" 0 and
+ * fp32 tensors with "tile" 0 included).  A NULL rows_dev or sample_index_dev is SKR_ERR_NULL, a negative row_offset
+ * SKR_ERR_UNSUPPORTED, and a launch with noise_mode == 1 needs seeds_dev whatever its rows hold.  On top of that contract
+ *   inactive sample  sample_index_dev[s] < 0 (tested before row_offset is added): the workgroups of sample s return before their
+ *                    first vector-memory instruction.  No operand, mask, seed or row of that sample is read; `out` keeps its bytes there.
+ *   absent operand   an operand k whose coef0[k] and coef1[k] are both exactly zero (+0 or -0) in the sample's row is not loaded and
+ *                    adds nothing to either form: its bytes may be anything, NaN and inf included (the history a request in its
+ *                    multistep ramp-up does not have yet, the re-noising tensor on the last step, the original and the re-noising
+ *                    tensor of a plain request that shares the batch).  The mask is always read for an active sample.
+ *   operand order    the operands that are present are accumulated in slot order with the arithmetic of skr_step_launch_masked,
+ *                    operation for operation: s over every present operand, one fma each (a present operand whose coef0 is zero
+ *                    included), the noise last and skipped when the row's zeta0 narrows to zero; k over the present operands whose
+ *                    coef1 is not exactly zero; out = fma(m, s, (1 - m) * k), rounded once.  A sample's result therefore has the bits
+ *                    skr_step_launch_masked gives for that sample alone with a plan that holds exactly the present operands in that
+ *                    order, with the row's values.
+ * `plan` is therefore the WIDEST masked step of the sampler.  Index validity stays the caller's business: every non-negative
+ * sample_index_dev[s] + row_offset must name a row of the table; the kernel neither checks nor clamps
+ * (skrample_amd.rolling.RollingBatch validates on the host).
+ */
+int skr_step_launch_masked_rolling(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                   const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel,
+                                   const skr_step_row* rows_dev,
+                                   const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */,
+                                   int32_t row_offset, void* stream);
 
 /*
  * Step programs -- a plan the library keeps, launched by handle. Replaces the per-step host work of a REPLAYED step

@@ -33,6 +33,7 @@ EXPORTS = (
     "skr_step_launch_masked",
     "skr_step_launch_masked_indexed",
     "skr_step_launch_masked_indexed_per_sample",
+    "skr_step_launch_masked_rolling",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_program_create",
@@ -372,7 +373,7 @@ def load() -> ctypes.CDLL:
             table_launch.restype = ctypes.c_int
         lib.skr_step_launch_masked.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp]
         lib.skr_step_launch_masked.restype = ctypes.c_int
-        for masked_table_launch in (lib.skr_step_launch_masked_indexed, lib.skr_step_launch_masked_indexed_per_sample):
+        for masked_table_launch in (lib.skr_step_launch_masked_indexed, lib.skr_step_launch_masked_indexed_per_sample, lib.skr_step_launch_masked_rolling):
             masked_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp, vp, i32, vp]
             masked_table_launch.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
@@ -498,3 +499,9 @@ def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch
     else:
         status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds_ptr, numel, current_stream_ptr(device))
     check(status, "skr_step_launch_masked")
+
+
+def launch_step_masked_rolling_raw(plan: StepPlanC, arr, out_ptr, mask: StepMaskC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:
+    """one masked rolling step launch (skr_step_launch_masked_rolling) from raw pointers; returns the status code.  `arr`: the operand
+    pointer array, `mask`: its descriptor; the caller owns every check of the index (rolling.RollingBatch)."""
+    return load().skr_step_launch_masked_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(mask), seeds_ptr, numel, rows_ptr, sample_index_ptr, row_offset, stream_ptr)

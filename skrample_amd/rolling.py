@@ -11,6 +11,13 @@ whatever else is resident, and leaves when its own run is over -- the slot is fr
     done = batch.step(model(batch.latents, t))       # ONE skr_step_launch_rolling; the slots that just finished
     x = batch.take(slot)
 
+In-painting requests (`SkrampleWrapperScheduler.set_inpaint`) join a batch built with the shape of one sample's mask; plain requests
+share it, and a tick is still one launch (`skr_step_launch_masked_rolling`, csrc/skr_step_masked_rolling.hip):
+
+    batch = RollingBatch(make_wrapper, example, capacity=B, inpaint_mask_shape=(1, H, W))
+    batch.admit(slot, latents, wrapper, steps, seed=None, inpaint=(mask, original_samples, noise))   # one sample each
+    batch.admit(other, latents, wrapper, steps)      # a plain request: its slot of `batch.mask` is ones
+
 With `device_positions=True` the positions live on the device and a tick needs no host-to-device copy:
 
     batch.advance()                                  # ONE skr_rolling_advance: index and timesteps computed on the device
@@ -28,6 +35,17 @@ free or finished slot, with one small stream-ordered copy.  The kernels (csrc/sk
 before their first vector-memory instruction, and neither load nor accumulate an operand whose coefficients are zero in the
 sample's row: a sample in its multistep ramp-up has the bits of the narrower launch its lone run makes, whatever the slot's previous
 occupant left in the history rings.
+
+A masked batch (`inpaint_mask_shape`) owns three more whole-batch tensors -- `mask[capacity, *mask_shape]` (ones until a request brings
+its own), `original` and `noise[capacity, *unit_shape]` -- and two more roles, ("orig",) and ("znoise",), bound to the last two.  Its
+launch structure is the widest step of a dry run with in-painting set on scratch one-sample tensors, so both have slots; the launch is
+always per slot (`batch_stride = mask_numel`), its mask descriptor built once.  `admit(..., inpaint=...)` copies the request's three
+tensors into the slot's slices and dry-runs the wrapper with `set_inpaint` on one-sample views of them (the `retarget` mechanism): the
+rows carry the step form in `coef0` and the re-noised known form in `coef1`; the last step's known form is the original alone, a row with
+a zero in the `znoise` slot, which the kernel then does not load.  A plain request's rows come from the plain dry run -- every `coef1`
+zero, `orig` / `znoise` absent -- under a mask of ones.  `step()`, `advance()`, `capture()` and `CapturedTicks.tick()` mean what they
+mean on a plain batch.  Covered there: the samplers whose masked step is one single-output launch -- Euler, DPM 1-3, Adams 2-4, UniP
+2-3.  UniPC and SPC blend with a second launch and are refused when the batch is built ("not one fused launch").
 
 Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
 `Random` noise (drawn in the kernel) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
@@ -48,9 +66,10 @@ from typing import Callable, Sequence
 import torch
 
 from . import _hip
-from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepPlanC, StepRowC, upload_rows
+from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepMaskC, StepPlanC, StepRowC, upload_rows
+from .sampling import lazy
 
-Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py
+Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py; ("orig",) ("znoise",): a masked batch's original / re-noising tensor
 
 ALIAS_HELP = (
     "a model output passed to an earlier step() is still a history operand of this batch and {what}; RollingBatch aliases the caller's "
@@ -125,9 +144,10 @@ class RollingBatch:
     the device (`advance()` before each `step()`, or `capture()`); the host publishes nothing per tick."""
 
     def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True,
-                 device_positions: bool = False):  # fmt: skip
+                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None):  # fmt: skip
         if capacity < 1:
             raise ValueError("a rolling batch has at least one slot")
+        self.masked = inpaint_mask_shape is not None
         self.capacity, self.max_steps, self.alias_history = int(capacity), int(max_steps), bool(alias_history)
         self.device_positions = bool(device_positions)
         if self.device_positions and (self.max_steps < 1 or self.capacity * self.max_steps > 0x7FFFFFFF):
@@ -141,6 +161,8 @@ class RollingBatch:
             raise ValueError(f"per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {self.sample_numel} elements per sample")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
+        if self.masked:
+            self._init_inpaint(tuple(int(n) for n in inpaint_mask_shape), first)
         self.structure = sampler_structure(first)
         self.keep = int(first.sampler.require_previous)
         self.draws_noise = bool(first.sampler.require_noise)
@@ -174,10 +196,36 @@ class RollingBatch:
             self.length_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
             self.times_dev = torch.zeros(self.capacity * self.max_steps, dtype=torch.float32, device=self.device)
 
+    def _init_inpaint(self, mask_shape: tuple, first) -> None:
+        """A masked batch: the three whole-batch in-paint tensors (every slot's mask starts as ones: generate everything), the mask
+        descriptor of every tick's launch -- one mask per slot, always -- and in-painting set on the wrapper whose dry run gives the
+        launch structure, on scratch one-sample tensors, so that `orig` and `znoise` get their slots."""
+        unit = (1, *self.unit_shape)
+        try:
+            self.mask_numel, _ = lazy.mask_layout((1, *mask_shape), unit)
+        except SkrampleHipError as refused:
+            raise ValueError(f"inpaint_mask_shape {mask_shape} is not the mask of one {self.unit_shape} sample: {refused}") from None
+        if self.mask_numel % 8 != 0:
+            raise ValueError(f"masked rows need a mask of a multiple of 8 elements per sample, not {self.mask_numel}")
+        if self.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"masked rows need one 16- or 32-bit dtype for operands, mask and output, not {self.dtype}")
+        self.mask_shape = mask_shape
+        self.mask = torch.ones((self.capacity, *mask_shape), dtype=self.dtype, device=self.device)
+        self.original = torch.zeros((self.capacity, *self.unit_shape), dtype=self.dtype, device=self.device)
+        self.noise = torch.zeros((self.capacity, *self.unit_shape), dtype=self.dtype, device=self.device)
+        self._mask_desc = StepMaskC(self.mask.data_ptr(), _hip.DTYPE_CODE[self.dtype], 0, self.mask_numel, self.mask_numel)
+        scratch = [torch.ones((1, *mask_shape), dtype=self.dtype, device=self.device)] + [torch.zeros(unit, dtype=self.dtype, device=self.device) for _ in range(2)]
+        first.set_inpaint(*scratch)
+
     # ---- what a test replaces to run the bookkeeping without a device ---------------------------------------------------
     def _trace(self, wrapper, steps: int, seed: int | None) -> list[tuple[StepPlanC, list[Role], float]]:
         """Dry run of `wrapper` for `steps` steps on one sample: (plan, operand roles, timestep) of every step's single launch.
-        Coefficients depend on the schedule and the step alone, never on tensor contents, so the model outputs are zeros."""
+        Coefficients depend on the schedule and the step alone, never on tensor contents, so the model outputs are zeros.
+        A wrapper with `set_inpaint` in force (a masked batch's in-painting request) must issue masked launches -- the seven-entry
+        trace tuple of `_hip.launch_step_masked` -- and one without it plain ones."""
+        inpaint = getattr(wrapper, "_inpaint", None)
+        if inpaint is not None and not self.masked:
+            raise SkrampleHipError("this wrapper has set_inpaint in force and the batch was built without inpaint_mask_shape")
         wrapper.set_timesteps(steps)
         x = torch.zeros((1, *self.unit_shape), dtype=self.dtype, device=self.device)
         found = []
@@ -199,8 +247,12 @@ class RollingBatch:
                 _hip.trace = held
             if len(launches) != 1:
                 raise SkrampleHipError(f"a step of this wrapper is {len(launches)} launches, not one fused launch: it cannot join a rolling batch")
+            if (len(launches[0]) == 7) != (inpaint is not None):
+                raise SkrampleHipError("a step of this wrapper is not the masked launch its in-painting asks for" if inpaint is not None else "a step of this wrapper is a masked launch although no in-painting is set")
             plan, inputs = StepPlanC.from_buffer_copy(launches[0][0]), launches[0][1]
             known[x.data_ptr()], known[out.data_ptr()] = ("x",), ("o",)
+            if inpaint is not None:
+                known[inpaint[1].data_ptr()], known[inpaint[2].data_ptr()] = ("orig",), ("znoise",)
             if wrapper._raw_samples:  # (a wrapper that snapshots its history stepped on its own copies of this call's tensors)
                 known[wrapper._raw_samples[-1].data_ptr()], known[wrapper._raw_outputs[-1].data_ptr()] = ("x",), ("o",)
             roles = [known.get(tensor.data_ptr()) for tensor in inputs]
@@ -212,6 +264,11 @@ class RollingBatch:
         return found
 
     def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None) -> None:
+        if self.masked:  # (one output: a masked step is one single-output launch)
+            status = _hip.launch_step_masked_rolling_raw(self.plan, arr, out0.data_ptr(), self._mask_desc, self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel,
+                                                         self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0, _hip.current_stream_ptr(self.device))  # fmt: skip
+            _hip.check(status, "skr_step_launch_masked_rolling")
+            return
         lib = _hip.load()
         status = lib.skr_step_launch_rolling(ctypes.byref(self.plan), arr, out0.data_ptr() if out0 is not None else None, out1.data_ptr() if out1 is not None else None,
                                              self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0,
@@ -258,6 +315,9 @@ class RollingBatch:
             wide.noise_mode = 1
         if self.dtype == torch.float32 and wide.out0_dtype != _hip.NONE and wide.out1_dtype != _hip.NONE:
             raise SkrampleHipError("skr_step_launch_rolling: request outside kernel coverage (the two-output table kernels take 16-bit operands)")
+        if self.masked and (wide.out0_dtype == _hip.NONE or wide.out1_dtype != _hip.NONE or wide.acc_f64 or wide.n_group_a != wide.n_terms
+                            or wide.dtype_a != wide.out0_dtype or wide.dtype_a != _hip.DTYPE_CODE[self.dtype]):  # fmt: skip
+            raise SkrampleHipError("skr_step_launch_masked_rolling: request outside kernel coverage (one single-output launch of one 16- or 32-bit dtype, evaluated in float32)")
         return wide, list(roles)
 
     def _rows_of(self, traced) -> list[StepRowC]:
@@ -265,6 +325,8 @@ class RollingBatch:
         for plan, roles, _ in traced:
             if (plan.dtype_a, plan.acc_f64, plan.convert_to, plan.convert_from) != (self.plan.dtype_a, self.plan.acc_f64, self.plan.convert_to, self.plan.convert_from):
                 raise SkrampleHipError("a step of this request differs in dtype or conversion from the batch's launch structure")
+            if self.masked and (plan.out0_dtype != self.plan.out0_dtype or plan.out1_dtype != _hip.NONE or plan.n_group_a != plan.n_terms):
+                raise SkrampleHipError("a step of this request is not one single-output launch of the masked batch's dtype")
             rows.append(place_row(self.roles, plan, roles, self.two_outputs))
         return rows
 
@@ -303,9 +365,13 @@ class RollingBatch:
             out.append(b * self.max_steps + req.position)
         return out
 
-    def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None) -> None:
+    def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None, inpaint: Sequence[torch.Tensor] | None = None) -> None:
         """Start a request in a free slot: `latents` of one sample, `wrapper` with this request's schedule / stochasticity (same
-        sampler structure as the batch; it is consumed by the dry run that produces the rows), `steps` its run length."""
+        sampler structure as the batch; it is consumed by the dry run that produces the rows), `steps` its run length.
+        `inpaint` (a batch built with `inpaint_mask_shape` only): (mask, original_samples, noise) of ONE sample -- the request is an
+        in-painting one, stepped as `wrapper.set_inpaint` would step it alone; the batch copies the three into the slot's slices of
+        its own tensors (the mask cast to the latents' dtype, as set_inpaint casts it).  None there: a plain request sharing the
+        batch -- its mask is ones and its rows name neither the original nor the re-noising tensor."""
         self._check_slot(slot)
         if self._requests[slot] is not None:
             raise ValueError(f"slot {slot} is busy: take() its result first" if slot in self._finished else f"slot {slot} is busy")
@@ -323,6 +389,28 @@ class RollingBatch:
             raise ValueError(f"latents of shape {tuple(latents.shape)} / {latents.dtype} in a batch of samples {self.unit_shape} / {self.dtype}")
         if self._advanced:
             raise ValueError("admit() between advance() and step(): this tick's index is already on the device; admit between ticks")
+        if inpaint is not None:
+            if not self.masked:
+                raise ValueError("inpaint= needs a batch built with inpaint_mask_shape: this one steps with skr_step_launch_rolling")
+            given = tuple(inpaint)
+            if len(given) != 3 or any(not isinstance(t, torch.Tensor) for t in given):
+                raise ValueError("inpaint is (mask, original_samples, noise): three tensors for one sample")
+            if tuple(given[0].shape) not in (self.mask_shape, (1, *self.mask_shape)):
+                raise ValueError(f"a mask of shape {tuple(given[0].shape)} in a batch of masks {self.mask_shape}")
+            for name, t in (("original_samples", given[1]), ("noise", given[2])):
+                if tuple(t.shape) not in (self.unit_shape, (1, *self.unit_shape)) or t.dtype != self.dtype:
+                    raise ValueError(f"{name} of shape {tuple(t.shape)} / {t.dtype} in a batch of samples {self.unit_shape} / {self.dtype}")
+        if self.masked:
+            if inpaint is None:
+                if getattr(wrapper, "_inpaint", None) is not None:
+                    raise ValueError("this wrapper has set_inpaint in force: hand its tensors to admit(inpaint=...), the batch steps on its own copies")
+                self.mask[slot].fill_(1.0)
+            else:
+                self.mask[slot].copy_(given[0].reshape(self.mask_shape))
+                self.original[slot].copy_(given[1].reshape(self.unit_shape))
+                self.noise[slot].copy_(given[2].reshape(self.unit_shape))
+                # (the dry run steps on one-sample views of the batch's own tensors: the mechanism of CapturedLoop.retarget)
+                wrapper.set_inpaint(self.mask[slot : slot + 1], self.original[slot : slot + 1], self.noise[slot : slot + 1])
         traced = self._trace(wrapper, steps, seed if noisy else None)
         if len(traced) != steps:
             raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
@@ -369,6 +457,10 @@ class RollingBatch:
             return model_output
         if kind == "none":
             return self._blank
+        if kind in ("orig", "znoise") and self.masked:
+            return self.original if kind == "orig" else self.noise
+        if len(role) < 2:
+            raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (structured noise tensors are not covered)")
         k = role[1]
         if kind == "pi":
             return self._x[k - 1]
@@ -508,6 +600,8 @@ class CapturedTicks:
                     t = self.outputs[p]
                 elif kind == "none":
                     t = batch._blank
+                elif kind in ("orig", "znoise") and batch.masked:  # the batch's own in-paint tensors: the same in every phase
+                    t = batch.original if kind == "orig" else batch.noise
                 elif kind == "pi":  # the latents of -k ticks ago
                     t = x_ring[(P - 1 + p + role[1]) % P]
                 elif kind == "px":

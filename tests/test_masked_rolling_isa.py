@@ -1,0 +1,118 @@
+"""The masked rolling step kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
+
+`skr_step_launch_masked_rolling` runs `masked_rolling_kernel_v1<T, K, NOISE>` (csrc/skr_step_masked_rolling.hip).  Its contract is
+visible in the instruction stream, as that of the `Rolling<>` step kernels is (tests/test_rolling_isa.py): a workgroup of an inactive
+sample ends before its first vector-memory instruction, every decision taken from the sample's row is a scalar branch with exec never
+masked, operands are global loads, and nothing spills.  The VGPR counts are printed beside those of the per-sample twins
+`masked_rows_kernel_v1<T, K, NOISE, true>` (csrc/skr_step_masked_rows.hip) for DESIGN.md section 4.6; no occupancy bracket is
+asserted."""
+
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+from conftest import ROOT
+
+import __graft_entry__ as G
+
+CSRC = os.path.join(ROOT, "skrample_amd", "csrc")
+HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
+BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
+SYMBOL = re.compile(r"masked_rolling_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")
+TWIN = re.compile(r"masked_rows_kernel_v1I(\w+?)Li(\d+)ELb([01])ELb1EE")
+TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
+
+
+def waves_per_simd(vgprs: int) -> int:
+    "gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, at most 8 waves"
+    return min(8, 512 // (max(1, -(-vgprs // 8)) * 8))
+
+
+def compiled(name: str, work: str) -> dict:
+    "{symbol: (instructions and labels, VGPRs, scratch bytes, private segment size)} of every kernel of one source file"
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *G.PER_FILE_FLAGS.get(name, [])]
+    os.makedirs(work)
+    subprocess.run([HIPCC, *flags, "--save-temps", "-c", "-o", os.path.join(work, "x.o"), os.path.join(CSRC, name)], check=True, cwd=work, capture_output=True)
+    asm = [f for f in os.listdir(work) if f.endswith("gfx950.s")]
+    assert len(asm) == 1, asm
+    text = open(os.path.join(work, asm[0])).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):.*?^\.Lfunc_end\d+:.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", text, re.S | re.M):
+        body = m.group(0).split(".Lfunc_end")[0]
+        lines = [raw.split(";")[0].strip() for raw in body.splitlines()[1:]]
+        private = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(0))
+        out[m.group(1)] = ([l for l in lines if l and (not l.startswith(".") or l.startswith(".LBB"))], int(m.group(2)), int(m.group(3)), int(private.group(1)) if private else None)
+    return out
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    if HIPCC is None:
+        pytest.skip("no hipcc on this box")
+    found = compiled("skr_step_masked_rolling.hip", str(tmp_path_factory.mktemp("isa") / "rolling"))
+    return {k: v for k, v in found.items() if SYMBOL.search(k)}
+
+
+@pytest.fixture(scope="module")
+def twins(tmp_path_factory):
+    if HIPCC is None:
+        pytest.skip("no hipcc on this box")
+    found = compiled("skr_step_masked_rows.hip", str(tmp_path_factory.mktemp("isa_rows") / "rows"))
+    return {TWIN.search(k).groups(): v for k, v in found.items() if TWIN.search(k)}
+
+
+def test_all_96_instantiations_exist(kernels):
+    have = {SYMBOL.search(k).groups() for k in kernels}
+    want = {(t, str(n), nz) for t in TYPES.values() for n in range(1, 17) for nz in "01"}
+    assert have == want and len(kernels) == 96, (sorted(want - have), sorted(have - want))
+
+
+def test_inactive_exit_precedes_the_first_vector_memory_instruction(kernels):
+    "a conditional scalar branch whose target runs into s_endpgm without touching vector memory, ahead of the first vector-memory instruction"
+    for k, (lines, *_) in kernels.items():
+        first = next(i for i, l in enumerate(lines) if VMEM.match(l))
+        labels = {l[:-1]: i for i, l in enumerate(lines) if l.startswith(".LBB") and l.endswith(":")}
+        exits = False
+        for l in lines[:first]:
+            if l.startswith(BRANCH):
+                tail = [t for t in lines[labels[l.split()[-1]] :] if not t.startswith(".LBB")]
+                exits = exits or tail[0] == "s_endpgm"
+        assert exits, (k, lines[:first][-12:])
+
+
+def test_row_decisions_are_scalar_branches(kernels):
+    "no exec masking anywhere; a K-operand kernel has at least K + 1 conditional scalar branches (the exit and one per operand)"
+    for k, (lines, *_) in kernels.items():
+        assert not any("saveexec" in l for l in lines), k
+        assert sum(1 for l in lines if l.startswith(BRANCH)) >= int(SYMBOL.search(k).group(2)) + 1, k
+
+
+def test_operands_are_global_loads(kernels):
+    for k, (lines, *_) in kernels.items():
+        assert not any(l.startswith("flat_") for l in lines), k
+        assert sum(1 for l in lines if l.startswith("global_load")) >= int(SYMBOL.search(k).group(2)) + 1, k  # every operand and the mask
+
+
+def test_no_scratch(kernels):
+    for k, (lines, _, scratch, private) in kernels.items():
+        assert scratch == 0 and private == 0, (k, scratch, private)
+        assert not any(l.startswith("scratch_") for l in lines), k
+
+
+def test_vgpr_table_against_the_per_sample_twins(kernels, twins):
+    "printed for DESIGN.md section 4.6 (run with -s); every kernel has a twin, and nothing else is asserted: no occupancy bracket"
+    names = {v: k for k, v in TYPES.items()}
+    print("\nVGPRs (waves per SIMD): masked_rolling_kernel_v1 vs masked_rows_kernel_v1<..., PER_SAMPLE = true>")
+    short = []
+    for key in sorted((SYMBOL.search(k).groups() for k in kernels), key=lambda g: (g[0], g[2], int(g[1]))):
+        symbol = next(k for k in kernels if SYMBOL.search(k).groups() == key)
+        assert key in twins, key
+        mine, theirs = kernels[symbol][1], twins[key][1]
+        what = f"{names[key[0]]} K={int(key[1]):2d} noise={key[2]}"
+        print(f"  {what}: {mine:3d} ({waves_per_simd(mine)}) vs {theirs:3d} ({waves_per_simd(theirs)})")
+        if waves_per_simd(mine) < waves_per_simd(theirs):
+            short.append(what)
+    print("  fewer waves per SIMD than the twin:", ", ".join(short) if short else "none")

@@ -255,6 +255,33 @@ int skr_step_launch_masked(const skr_step_plan* plan, const void* const* inputs,
                            const skr_step_mask* mask, const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * The transposed masked step (autograd of skr_step_launch_masked).  The masked step is linear in its operands, its coefficients are
+ * host numbers and its mask is data, so the gradient of operand k needs no saved operand:
+ *
+ *     grad_k[e] = (a[k] * m[e] + b[k] * (1 - m[e])) * g[e]        (forward: a[k] = coef0[k], b[k] = coef1[k])
+ *
+ * `plan` is skr_step_grad_plan unchanged: a / b as above, g0_dtype the dtype of `g`, g1_dtype SKR_NONE (SKR_ERR_UNSUPPORTED otherwise),
+ * gradients grouped by dtype as in skr_step_backward_launch, 1..SKR_ROW_TERMS of them (SKR_ERR_TERMS beyond: the forward takes no
+ * more operands).  `mask` is skr_step_mask unchanged, with the forward's meaning of mask_numel and batch_stride; `sample_numel` is the
+ * forward plan's.  The noise term has no gradient, and neither has the mask.
+ * Arithmetic, in the accumulate type (fp32, fp64 if acc_f64):
+ *     t = 1 - m;   w = fma(a, m, b * t);   grad = w * g
+ * rounded once to the gradient's dtype as skr_step_backward_launch rounds.  So where m == 1 a gradient is a * g with the bits
+ * skr_step_backward_launch gives for that a, and where m == 0 it is b * g.  One pass over HBM: g and the mask read once, one
+ * gradient written per operand.
+ * Launches of whole 2048-element chunks whose samples are whole chunks, with one 16- or 32-bit dtype for g, mask and every gradient,
+ * fp32 arithmetic and mask_numel % 8 == 0 take a one-trip vector kernel (kernarg slots of 4 / 8 / 16 gradients); everything else
+ * (ragged sizes, samples below a chunk, other mask_numel, two dtype groups, fp64) a grid-stride per-element kernel.  The two agree
+ * bit for bit ("one_trip" 0 forces the second).
+ * Checked before the launch, without dereferencing device memory: a NULL plan, mask, g, mask->mask, grads or gradient SKR_ERR_NULL;
+ * a dtype code that names no tensor dtype SKR_ERR_DTYPE; n_grads outside 1..SKR_ROW_TERMS SKR_ERR_TERMS; a misaligned pointer
+ * SKR_ERR_ALIGN; mask_numel < 1, mask_numel not dividing sample_numel, sample_numel not dividing numel, or a batch_stride other than 0
+ * or mask_numel SKR_ERR_SHAPE; an fp64 mask without acc_f64 SKR_ERR_UNSUPPORTED.  numel == 0 is SKR_OK with nothing launched.
+ */
+int skr_step_masked_backward_launch(const skr_step_grad_plan* plan, const void* g, const skr_step_mask* mask, void* const* grads,
+                                    int64_t numel, int64_t sample_numel, void* stream);
+
+/*
  * The masked step with device-resident scalars: skr_step_launch_masked as skr_step_launch_indexed and
  * skr_step_launch_indexed_per_sample make skr_step_launch, so that one captured in-painting loop serves any schedule of its length
  * (other sigmas, shift, begin index / strength, stochasticity), keeps several schedules resident and lets every sample follow its own.

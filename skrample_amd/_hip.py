@@ -36,6 +36,7 @@ EXPORTS = (
     "skr_step_launch_masked_rolling",
     "skr_rolling_advance",
     "skr_step_backward_launch",
+    "skr_step_masked_backward_launch",
     "skr_program_create",
     "skr_program_launch",
     "skr_program_destroy",
@@ -380,6 +381,8 @@ def load() -> ctypes.CDLL:
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
         lib.skr_step_backward_launch.restype = ctypes.c_int
+        lib.skr_step_masked_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, ctypes.POINTER(StepMaskC), ctypes.POINTER(vp), i64, i64, vp]
+        lib.skr_step_masked_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]
         lib.skr_program_create.restype = ctypes.c_int
         lib.skr_program_launch.argtypes = [vp, ctypes.POINTER(vp), vp, vp, vp, u64, u64, vp]

@@ -60,27 +60,6 @@ struct BwdArgs {
   int32_t n, n_a, dt_a, dt_b, dt_g0, dt_g1;
 };
 
-// one rounding from Acc; the same conversions as store8 (fp32 -> 16-bit: RNE of the fp32 value, pinned so that no fused
-// multiply-add-and-convert rounds the exact sum instead).  The same function as store_elem of skr_step_masked.hip, kept apart: see there.
-template <typename Acc> __device__ __forceinline__ void store_any(void* base, int64_t i, int dt, Acc v) {
-  switch (dt) {
-    case SKR_BF16: {
-      float f = (float)v;
-      asm("" : "+v"(f));
-      reinterpret_cast<uint16_t*>(base)[i] = (uint16_t)(pack_bf16(f, 0.f) & 0xFFFFu);
-      break;
-    }
-    case SKR_F16: {
-      float f = (float)v;
-      asm("" : "+v"(f));
-      reinterpret_cast<_Float16*>(base)[i] = (_Float16)f;
-      break;
-    }
-    case SKR_F32: reinterpret_cast<float*>(base)[i] = (float)v; break;
-    default: reinterpret_cast<double*>(base)[i] = (double)v; break;
-  }
-}
-
 template <typename Acc, bool HAS1>
 __global__ __launch_bounds__(BLOCK) void step_bwd_general(const BwdArgs p) {
   for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < p.numel; e += (int64_t)gridDim.x * BLOCK) {

@@ -283,8 +283,8 @@ __device__ __forceinline__ void store_scalar(void* base, int64_t i, Acc v) {
   else reinterpret_cast<T*>(base)[i] = (T)v;
 }
 
-// ---- per-element load with a run-time dtype (the general kernels of skr_step_masked.hip and skr_step_backward.hip) -------------------
-// (their stores stay apart: one shared body changes the instructions of one kernel or the other)
+// ---- per-element load with a run-time dtype (the general kernels of skr_step_masked.hip and the two backward files) -----------------
+// (the forward's store stays apart from the backwards': one shared body changes the instructions of one kernel or the other)
 // WITH_F64 = false: no fp64 tensor reaches the kernel (every other code reads as fp32)
 template <typename Acc, bool WITH_F64>
 __device__ __forceinline__ Acc load_elem(const void* base, int64_t i, int dt) {
@@ -301,6 +301,29 @@ __device__ __forceinline__ Acc load_elem(const void* base, int64_t i, int dt) {
       case SKR_F16: return (Acc)load_scalar<f16_t>(base, i);
       default: return (Acc)load_scalar<float>(base, i);
     }
+  }
+}
+
+// one rounding from Acc; the same conversions as store8 (fp32 -> 16-bit: RNE of the fp32 value, pinned so that no fused
+// multiply-add-and-convert rounds the exact sum instead).
+// The per-element store of the two backward general kernels (skr_step_backward.hip, skr_step_masked_backward.hip); store_elem of
+// skr_step_masked.hip is the same function, kept apart: see there.
+template <typename Acc> __device__ __forceinline__ void store_any(void* base, int64_t i, int dt, Acc v) {
+  switch (dt) {
+    case SKR_BF16: {
+      float f = (float)v;
+      asm("" : "+v"(f));
+      reinterpret_cast<uint16_t*>(base)[i] = (uint16_t)(pack_bf16(f, 0.f) & 0xFFFFu);
+      break;
+    }
+    case SKR_F16: {
+      float f = (float)v;
+      asm("" : "+v"(f));
+      reinterpret_cast<_Float16*>(base)[i] = (_Float16)f;
+      break;
+    }
+    case SKR_F32: reinterpret_cast<float*>(base)[i] = (float)v; break;
+    default: reinterpret_cast<double*>(base)[i] = (double)v; break;
   }
 }
 

@@ -85,7 +85,7 @@ struct MaskedGenArgs {
 };
 
 // one rounding from Acc, the conversions of store8 (to a 16-bit dtype through the fp32 value, pinned in a register so that no fused
-// multiply-add-and-convert rounds the exact sum instead).  The same function as store_any of skr_step_backward.hip, kept apart: either
+// multiply-add-and-convert rounds the exact sum instead).  The same function as store_any of skr_step_common.h (the backward kernels' store), kept apart: either
 // body, used by both general kernels, changes the instructions of the other one.
 template <typename Acc> __device__ __forceinline__ void store_elem(void* base, int64_t i, int dt, Acc v) {
   if (dt == SKR_BF16 || dt == SKR_F16) {

@@ -522,7 +522,11 @@ def mask_layout(mask_shape: Sequence[int], shape: Sequence[int]) -> tuple[int, i
 def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtype | None = None, acc_f64: bool | None = None) -> torch.Tensor:
     """mask * form + (1 - mask) * known in ONE launch (skr_step_launch_masked): `form` is a solver step (it may hold one fused Philox
     draw), `known` the re-noised kept region.  The leaves of both are merged into one operand list.  Host-resident operands evaluate
-    the same expression with torch ops in the accumulate type."""
+    the same expression with torch ops in the accumulate type.
+    Autograd: device operands that require grad while autograd records go through `_MaskedStepFunction`, whose backward is one
+    skr_step_masked_backward_launch; the forward's bits are those of the launch without autograd.  The mask has no gradient (it would
+    need the operands and a reduction over the broadcast axes): a mask that requires grad is refused.  Host-resident operands that
+    require grad stay refused: the host executor of a masked step has no backward."""
     f0, f1 = lift(form), lift(known)
     if not isinstance(f0, Lin) or not isinstance(f1, Lin) or not isinstance(mask, torch.Tensor):
         raise SkrampleHipError("evaluate_masked() takes two tensor forms and a mask tensor")
@@ -536,9 +540,12 @@ def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtyp
     mask_numel, batch_stride = mask_layout(mask.shape, shape)
     out_dtype = dtype if dtype is not None else _default_dtype(f0)
     leaves = [leaf for f in (f0, f1) for leaf, _ in f.terms.values() if isinstance(leaf, torch.Tensor)]
-    if grad_recorded(mask, *leaves):
-        raise SkrampleHipError("a masked step has no backward: run it under torch.no_grad() or on operands that do not require grad")
+    if grad_recorded(mask):
+        raise SkrampleHipError("the mask of a masked step has no gradient: detach it, or run the step under torch.no_grad()")
+    recorded = grad_recorded(*leaves)
     if is_host(device) or is_host(f1.device):
+        if recorded:
+            raise SkrampleHipError("a masked step has no backward: run it under torch.no_grad() or on operands that do not require grad")
         return _host_evaluate_masked(f0, f1, mask, out_dtype, acc_f64)
     if not mask.is_cuda or mask.device != device:
         raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
@@ -547,6 +554,8 @@ def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtyp
         raise SkrampleHipError("a float64 mask needs float64 accumulation")
     numel = math.prod(shape)
     plan.sample_numel = numel // shape[0] if shape[0] else 1
+    if recorded:
+        return _MaskedStepFunction.apply(plan, seeds, shape, numel, device, _prepare_tensor(mask), mask_numel, batch_stride, *operands)
     out = empty_output(shape, out_dtype, device)
     _hip.launch_step_masked(plan, operands, out, _prepare_tensor(mask), mask_numel, batch_stride, seeds, numel, device)
     return out
@@ -699,6 +708,62 @@ class _Like:
 
     def __init__(self, shape, dtype):
         self.shape, self.dtype = shape, dtype
+
+
+def launch_masked_backward(g, mask: torch.Tensor, mask_numel: int, batch_stride: int, a: Sequence[float], b: Sequence[float], like: Sequence, sample_numel: int, acc_f64: bool) -> list[torch.Tensor]:
+    """grads[k] = (a[k] * m + b[k] * (1 - m)) * g in one skr_step_masked_backward_launch; grads[k] has like[k]'s dtype and shape.
+    `like` must be grouped by dtype (at most two groups), as for launch_backward."""
+    device = g.device
+    g = _prepare_tensor(g)
+    grads = [torch.empty(t.shape, dtype=t.dtype, device=device) for t in like]
+    plan = _hip.StepGradPlanC()
+    plan.n_grads = len(grads)
+    plan.dtype_a = _hip.DTYPE_CODE[grads[0].dtype]
+    plan.n_group_a = sum(1 for t in grads if t.dtype == grads[0].dtype)
+    plan.dtype_b = _hip.DTYPE_CODE[grads[-1].dtype]
+    if any(t.dtype != grads[0].dtype for t in grads[: plan.n_group_a]) or len({t.dtype for t in grads}) > 2:
+        raise SkrampleHipError("gradients must come in at most two dtype groups")
+    plan.g0_dtype, plan.g1_dtype = _hip.DTYPE_CODE[g.dtype], _hip.NONE
+    plan.acc_f64 = 1 if acc_f64 else 0
+    for k in range(len(grads)):
+        plan.a[k], plan.b[k] = a[k], b[k]
+    arr = (ctypes.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
+    desc = _hip.StepMaskC(mask.data_ptr(), _hip.DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
+    status = _hip.load().skr_step_masked_backward_launch(ctypes.byref(plan), g.data_ptr(), ctypes.byref(desc), arr, g.numel(), sample_numel, _hip.current_stream_ptr(device))
+    _hip.check(status, "skr_step_masked_backward_launch")
+    return grads
+
+
+class _MaskedStepFunction(torch.autograd.Function):
+    "one masked step launch (forward) and its transposed step (backward); the mask is the only tensor kept"
+
+    @staticmethod
+    def forward(ctx, plan, seeds, shape, numel, device, mask, mask_numel, batch_stride, *operands):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mask)
+        ctx.plan, ctx.mask_numel, ctx.batch_stride = plan, mask_numel, batch_stride
+        # a plain tensor, as in _StepFunction: no view whose later in-place modification would raise
+        out = torch.empty(shape, dtype=_hip.CODE_DTYPE[plan.out0_dtype], device=device)
+        _hip.launch_step_masked(plan, list(operands), out, mask, mask_numel, batch_stride, seeds, numel, device)
+        ctx.like = [(t.shape, t.dtype) for t in operands]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        n = len(ctx.like)
+        skip = 8
+        want = [k for k in range(n) if ctx.needs_input_grad[skip + k]]
+        result: list = [None] * (skip + n)
+        if not want or g is None:
+            return tuple(result)
+        plan, (mask,) = ctx.plan, ctx.saved_tensors
+        like = [_Like(*ctx.like[k]) for k in want]
+        grads = launch_masked_backward(g, mask, ctx.mask_numel, ctx.batch_stride, [plan.coef0[k] for k in want], [plan.coef1[k] for k in want],
+                                       like, plan.sample_numel, bool(plan.acc_f64))
+        for k, grad in zip(want, grads):
+            result[skip + k] = grad
+        return tuple(result)
 
 
 

@@ -438,6 +438,26 @@ int skr_noise_offset(void* out, int32_t out_dtype, const uint64_t* seeds_dev, ui
                      uint64_t stream_offset, int64_t batch, const int64_t* unit_shape, int32_t ndim,
                      uint32_t keep_mask, double strength, void* stream);
 
+/* skr_noise_offset for a rolling batch: every sample at its own draw, inactive samples at no cost.  sample_index_dev[batch] is the vector a
+ * skr_step_launch_rolling reads (published by the host, or computed by skr_rolling_advance; no other device state).  For every sample b:
+ *   inactive  sample_index_dev[b] < 0: the workgroups of sample b return on a scalar branch before their first vector-memory
+ *             instruction and before any LDS or Philox work.  Nothing of the sample is read, its seed included; `out` keeps its bytes there.
+ *   active    its draw number is d = sample_index_dev[b] - b * rows_per_slot, the sample's position in its own run (the caller guarantees
+ *             0 <= d < rows_per_slot; skrample_amd.rolling.RollingBatch and skr_rolling_advance validate it), and its streams are those of
+ *             draw d of a whole-batch generator: stream_base = d * stream_stride, stream_offset = stream_base + 1, or 1 (the first
+ *             draw's) with static_offset != 0.
+ * An active sample's slice of `out` has the bits skr_noise_offset writes for that sample alone (batch 1, its seed, those streams): the
+ * same kernel code behind one scalar load, independent of the slot and of which other slots are active.  Covered: what the aligned
+ * kernel of skr_noise_offset covers -- the innermost axis of unit_shape a multiple of 8, a unit below 2^31 elements, batch <= 65535,
+ * `out` 16-byte aligned -- in bf16, fp16 or fp32; anything else, SKR_F64 included, is SKR_ERR_UNSUPPORTED.
+ * Checked before the launch, without dereferencing device memory: rows_per_slot < 1, stream_stride == 0 or
+ * batch * rows_per_slot > INT32_MAX is SKR_ERR_SHAPE; then the checks of skr_noise_offset in their order (batch == 0 or an empty unit
+ * is SKR_OK with nothing launched); a NULL sample_index_dev is SKR_ERR_NULL.  Allocates nothing, never synchronises: capturable. */
+int skr_noise_offset_rolling(void* out, int32_t out_dtype, const uint64_t* seeds_dev,
+                             const int32_t* sample_index_dev /* device int32[batch], < 0: inactive */, int32_t rows_per_slot,
+                             uint64_t stream_stride, int32_t static_offset, int64_t batch, const int64_t* unit_shape, int32_t ndim,
+                             uint32_t keep_mask, double strength, void* stream);
+
 /* Pyramid.generate (noise.py:146-207) over the last two dims (resize_h = 1) or the last dim (resize_h = 0,
  * h must be 1) of a [batch][lead][h][w] tensor:
  *   out = (N(base) + sum_{l >= skip} strength^l * upsample_bilinear(N(level l)))  /  per-sample unbiased std
@@ -453,6 +473,29 @@ int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f32, double* 
                       const uint64_t* seeds_dev, uint64_t stream_base, uint64_t stream_levels, int64_t batch,
                       int64_t lead, int64_t h, int64_t w, int32_t resize_h, double strength, int32_t depth,
                       int32_t with_base, void* stream);
+
+/* skr_noise_pyramid (with_base = 1) for a rolling batch, under the contract of skr_noise_offset_rolling: sample b is inactive when
+ * sample_index_dev[b] < 0 -- its workgroups of pass 1 AND of the normalising pass return on a scalar branch before their first
+ * vector-memory instruction and before any LDS or Philox work; neither its seed, nor level_ws, nor its partials are read, and `out`,
+ * scratch_f32, partials_f64 and level_ws keep their bytes there -- else its draw number is d = sample_index_dev[b] - b * rows_per_slot
+ * and its streams are stream_base = d * stream_stride, stream_levels = stream_base, or 0 (the first draw's) with static_levels != 0.
+ * An active sample's slice of `out` has the bits skr_noise_pyramid writes for that sample alone (batch 1, its seed, those streams): the
+ * same five pass-1 forms, picked by the same route decision, and the same normalising pass, behind one scalar load.  Workspaces as for
+ * skr_noise_pyramid.  Covered: what skr_noise_pyramid covers, in bf16, fp16 or fp32; a shape its LDS route refuses and SKR_F64 are
+ * SKR_ERR_UNSUPPORTED with nothing launched (there is no rolling form of the any-shape kernels).
+ * Checked before any launch, without dereferencing device memory: rows_per_slot < 1, stream_stride == 0 or
+ * batch * rows_per_slot > INT32_MAX is SKR_ERR_SHAPE; then the checks of skr_noise_pyramid in their order (batch == 0 is SKR_OK with
+ * nothing launched; sample_index_dev is one of the pointers: NULL is SKR_ERR_NULL), then the output type.  Capturable. */
+int skr_noise_pyramid_rolling(void* out, int32_t out_dtype, float* scratch_f32, double* partials_f64, int32_t* level_ws,
+                              const uint64_t* seeds_dev, const int32_t* sample_index_dev /* device int32[batch], < 0: inactive */,
+                              int32_t rows_per_slot, uint64_t stream_stride, int32_t static_levels, int64_t batch, int64_t lead,
+                              int64_t h, int64_t w, int32_t resize_h, double strength, int32_t depth, void* stream);
+
+/* What the two rolling entries answer for a batch of such units, with nothing launched and no pointer looked at: their own shape checks
+ * and route decision (SKR_OK, SKR_ERR_SHAPE, or SKR_ERR_UNSUPPORTED for a unit outside the aligned Offset kernel / a plane the LDS route of
+ * the Pyramid kernels refuses).  A caller that owns long-lived buffers (skrample_amd.rolling.RollingBatch) asks before it allocates them. */
+int skr_noise_offset_rolling_covers(int64_t batch, const int64_t* unit_shape, int32_t ndim);
+int skr_noise_pyramid_rolling_covers(int64_t batch, int64_t lead, int64_t h, int64_t w, int32_t resize_h);
 
 /* Same generator for any plane size and width (no `w % 4`, no LDS limit): the level normals are generated into
  * levels_f32 ([batch * lead*h*w] fp32) and sampled from global memory.  partials_f64 = [batch * n_slots * 2],

@@ -43,8 +43,12 @@ EXPORTS = (
     "skr_tape_launch",
     "skr_noise_random",
     "skr_noise_offset",
+    "skr_noise_offset_rolling",
+    "skr_noise_offset_rolling_covers",
     "skr_noise_brownian",
     "skr_noise_pyramid",
+    "skr_noise_pyramid_rolling",
+    "skr_noise_pyramid_rolling_covers",
     "skr_noise_pyramid_any",
     "skr_noise_pyramid_nd",
     "skr_noise_colored",
@@ -395,10 +399,18 @@ def load() -> ctypes.CDLL:
         lib.skr_noise_random.restype = ctypes.c_int
         lib.skr_noise_offset.argtypes = [vp, i32, vp, u64, u64, i64, ctypes.POINTER(i64), i32, ctypes.c_uint32, ctypes.c_double, vp]
         lib.skr_noise_offset.restype = ctypes.c_int
+        lib.skr_noise_offset_rolling.argtypes = [vp, i32, vp, vp, i32, u64, i32, i64, ctypes.POINTER(i64), i32, ctypes.c_uint32, ctypes.c_double, vp]
+        lib.skr_noise_offset_rolling.restype = ctypes.c_int
+        lib.skr_noise_offset_rolling_covers.argtypes = [i64, ctypes.POINTER(i64), i32]
+        lib.skr_noise_offset_rolling_covers.restype = ctypes.c_int
         lib.skr_noise_brownian.argtypes = [vp, i32, vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), i32, ctypes.c_double, vp, i32, i64, i64, vp]
         lib.skr_noise_brownian.restype = ctypes.c_int
         lib.skr_noise_pyramid.argtypes = [vp, i32, vp, vp, vp, vp, u64, u64, i64, i64, i64, i64, i32, ctypes.c_double, i32, i32, vp]
         lib.skr_noise_pyramid.restype = ctypes.c_int
+        lib.skr_noise_pyramid_rolling.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, u64, i32, i64, i64, i64, i64, i32, ctypes.c_double, i32, vp]
+        lib.skr_noise_pyramid_rolling.restype = ctypes.c_int
+        lib.skr_noise_pyramid_rolling_covers.argtypes = [i64, i64, i64, i64, i32]
+        lib.skr_noise_pyramid_rolling_covers.restype = ctypes.c_int
         lib.skr_noise_pyramid_any.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, u64, u64, i64, i64, i64, i64, i32, ctypes.c_double, i32, i32, vp]
         lib.skr_noise_pyramid_any.restype = ctypes.c_int
         lib.skr_noise_pyramid_nd.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, u64, u64, i64, i32, ctypes.POINTER(i64), i32, i32, ctypes.c_double, i32, i32, vp]

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "skr_device.h"
 #include "skr_launch.h"
@@ -40,6 +41,29 @@ __device__ __forceinline__ float add_offset(float z, float off, float gain) {
   return z + scaled;
 }
 
+// ---- rolling batches: every sample at its own draw (include/skrample_hip.h, skr_noise_offset_rolling / skr_noise_pyramid_rolling) ------------
+// The sample index vector of skr_step_launch_rolling names the draw: sample b is inactive when index[b] < 0, else its draw number is
+// index[b] - b * rows_per_slot and its streams are those the whole-batch entries get for that draw.  The kernels whose blockIdx names the
+// sample (offset_kernel_v8, pyramid_pass1, normalise_pass2) take their arguments' type as a template parameter: with the Rolling type the
+// index is one scalar load, the exit a scalar branch ahead of every vector-memory, LDS and Philox instruction, and the sample's streams
+// live in SGPRs; everything else is the whole-batch kernel's own code.
+struct RollingDraw {
+  const int32_t* index;    // [batch]
+  int32_t rows_per_slot;
+  int32_t is_static;       // the auxiliary streams (offset / pyramid levels) are the first draw's
+  uint64_t stream_stride;  // stream ids per draw
+};
+// false: the sample is inactive; else stream_base of its draw
+__device__ __forceinline__ bool rolling_stream(const RollingDraw& r, const int smp, uint64_t& stream_base) {
+  const int32_t at = r.index[smp];
+  if (at < 0) return false;
+  stream_base = (uint64_t)(uint32_t)(at - smp * r.rows_per_slot) * r.stream_stride;
+  return true;
+}
+struct OffsetRollingArgs : OffsetArgs {
+  RollingDraw r;
+};
+
 template <typename T>
 __global__ __launch_bounds__(256) void offset_kernel(const OffsetArgs a) {
   const int64_t unit = a.d0 * a.d1 * a.d2 * a.d3;
@@ -73,8 +97,14 @@ __global__ __launch_bounds__(256) void offset_kernel(const OffsetArgs a) {
 // consecutive elements of one innermost row, so the index decomposition is done once (32-bit) and the offset
 // normal is drawn once per thread unless the innermost axis itself is kept, in which case the 8 reduced indices
 // are consecutive and cost two Philox blocks.  Same per-element arithmetic as the kernel above.
-template <typename T>
-__global__ __launch_bounds__(256) void offset_kernel_v8(const OffsetArgs a) {
+template <typename T, typename Args = OffsetArgs>
+__global__ __launch_bounds__(256) void offset_kernel_v8(const Args a) {
+  constexpr bool ROLLING = std::is_same<Args, OffsetRollingArgs>::value;
+  uint64_t stream_base = a.stream_base, stream_offset = a.stream_offset;
+  if constexpr (ROLLING) {
+    if (!rolling_stream(a.r, (int)blockIdx.y, stream_base)) return;
+    stream_offset = a.r.is_static ? 1 : stream_base + 1;
+  }
   const uint32_t d1 = (uint32_t)a.d1, d2 = (uint32_t)a.d2, d3 = (uint32_t)a.d3;
   const uint32_t unit = (uint32_t)(a.d0 * a.d1 * a.d2 * a.d3), vps = unit >> 3;
   const uint32_t r1 = (a.mask & 2) ? d1 : 1, r2 = (a.mask & 4) ? d2 : 1, r3 = (a.mask & 8) ? d3 : 1;
@@ -87,13 +117,13 @@ __global__ __launch_bounds__(256) void offset_kernel_v8(const OffsetArgs a) {
   const uint32_t n_off = ((a.mask & 1) ? (uint32_t)a.d0 : 1u) * r1 * r2 * r3;
   const bool staged = !(a.mask & 8) && n_off <= 256u;
   if (staged) {
-    if (threadIdx.x < n_off) offs[threadIdx.x] = normal1(seed, a.stream_offset, (uint64_t)threadIdx.x);
+    if (threadIdx.x < n_off) offs[threadIdx.x] = normal1(seed, stream_offset, (uint64_t)threadIdx.x);
     __syncthreads();
   }
   for (uint32_t v = blockIdx.x * 256 + threadIdx.x; v < vps; v += gridDim.x * 256) {
     float z[8];
-    normal4(seed, a.stream_base, (uint64_t)(2 * v), z);
-    normal4(seed, a.stream_base, (uint64_t)(2 * v) + 1, z + 4);
+    normal4(seed, stream_base, (uint64_t)(2 * v), z);
+    normal4(seed, stream_base, (uint64_t)(2 * v) + 1, z + 4);
     uint32_t rem = v * 8;
     const uint32_t i3 = rem % d3; rem /= d3;
     const uint32_t i2 = rem % d2; rem /= d2;
@@ -103,12 +133,12 @@ __global__ __launch_bounds__(256) void offset_kernel_v8(const OffsetArgs a) {
     if (a.mask & 8) {
       // i3 % 8 == 0 and r3 = d3 % 8 == 0 => ridx % 8 == 0: two whole Philox blocks
       float o[8];
-      normal4(seed, a.stream_offset, ridx >> 2, o);
-      normal4(seed, a.stream_offset, (ridx >> 2) + 1, o + 4);
+      normal4(seed, stream_offset, ridx >> 2, o);
+      normal4(seed, stream_offset, (ridx >> 2) + 1, o + 4);
 #pragma unroll
       for (int j = 0; j < 8; ++j) z[j] = add_offset(z[j], o[j], a.gain);
     } else {
-      const float off = staged ? offs[(uint32_t)ridx] : normal1(seed, a.stream_offset, ridx);
+      const float off = staged ? offs[(uint32_t)ridx] : normal1(seed, stream_offset, ridx);
 #pragma unroll
       for (int j = 0; j < 8; ++j) z[j] = add_offset(z[j], off, a.gain);
     }
@@ -116,13 +146,19 @@ __global__ __launch_bounds__(256) void offset_kernel_v8(const OffsetArgs a) {
   }
 }
 
+// what offset_kernel_v8 takes, and its grid: blockIdx.y = sample, blockIdx.x strides over the sample's groups of 8
+static bool offset_v8_covers(const OffsetArgs& a) {
+  return a.d3 % 8 == 0 && a.d0 * a.d1 * a.d2 * a.d3 < (1ll << 31) && a.batch <= 65535 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+}
+static dim3 offset_v8_grid(const OffsetArgs& a) {
+  return dim3((unsigned)grid_blocks(a.d0 * a.d1 * a.d2 * a.d3 / 8, 256, (256 * 16 + a.batch - 1) / a.batch), (unsigned)a.batch);
+}
+
 template <typename T>
 static void launch_offset(const OffsetArgs& a, hipStream_t s) {
   const int64_t unit = a.d0 * a.d1 * a.d2 * a.d3;
-  const bool fast = a.d3 % 8 == 0 && unit < (1ll << 31) && a.batch <= 65535 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
-  if (fast) {
-    const int64_t bx = grid_blocks(unit / 8, 256, (256 * 16 + a.batch - 1) / a.batch);
-    hipLaunchKernelGGL(offset_kernel_v8<T>, dim3((unsigned)bx, (unsigned)a.batch), dim3(256), 0, s, a);
+  if (offset_v8_covers(a)) {
+    hipLaunchKernelGGL(offset_kernel_v8<T>, offset_v8_grid(a), dim3(256), 0, s, a);
     return;
   }
   const int64_t total = ((unit + 3) / 4) * a.batch;
@@ -156,13 +192,16 @@ struct PyramidArgs {  // (the defaults: a launch of the LDS kernels without a ta
   int32_t nd = 0, dim[4] = {1, 1, 1, 1}, axis_a = -1, axis_b = 3;
   int32_t ytab_off = -1;  // UNI kernels: float offset of the vertical tap table inside the dynamic LDS (behind the level planes)
 };
+struct PyramidRollingArgs : PyramidArgs {  // (rolling batches: see RollingDraw)
+  RollingDraw r;
+};
 
 // level geometry (reference noise.py:157-162,195-196): level i shrinks the RUNNING size by r_i**i,
 // r_i = 2 + 2*u_i, u_i = (philox word i of stream_base+255 >> 8) * 2^-24; stop at the first level with a
 // resized dimension of 1.  Same arithmetic as skrample_amd/pytorch/noise.py::pyramid_level_tables.
 // shrink factor of level i: r_i ** i, r_i = 2 + 2 u_i from word i of the geometry stream (Philox block i / 4)
-__device__ __forceinline__ double pyramid_level_shrink(const PyramidArgs& a, uint64_t seed, int i) {
-  u32x4 c{(uint32_t)(i >> 2), 0u, (uint32_t)(a.stream_levels + 255), (uint32_t)((a.stream_levels + 255) >> 32)};
+__device__ __forceinline__ double pyramid_level_shrink(const uint64_t stream_levels, uint64_t seed, int i) {
+  u32x4 c{(uint32_t)(i >> 2), 0u, (uint32_t)(stream_levels + 255), (uint32_t)((stream_levels + 255) >> 32)};
   c = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const uint32_t word = (i & 3) == 0 ? c.x : ((i & 3) == 1 ? c.y : ((i & 3) == 2 ? c.z : c.w));
   const double r = (double)(word >> 8) * 5.9604644775390625e-08 * 2.0 + 2.0;
@@ -205,7 +244,7 @@ __global__ void pyramid_geometry(const PyramidArgs a) {  // (the any-shape kerne
   if (smp >= a.batch) return;
   const uint64_t seed = a.seeds[smp];
   double shrink[PYR_MAX_LEVELS];
-  for (int i = 0; i < PYR_MAX_LEVELS; ++i) shrink[i] = pyramid_level_shrink(a, seed, i);
+  for (int i = 0; i < PYR_MAX_LEVELS; ++i) shrink[i] = pyramid_level_shrink(a.stream_levels, seed, i);
   a.n_levels[smp] = pyramid_level_walk(a, shrink, [&](int i, int32_t h, int32_t w) {
     a.level_hw[(smp * PYR_MAX_LEVELS + i) * 2] = h;
     a.level_hw[(smp * PYR_MAX_LEVELS + i) * 2 + 1] = w;
@@ -231,8 +270,14 @@ __device__ __forceinline__ void src_index(int dst, float scale, int in_size, int
 // compares, ly is a scalar operand.  The cached source rows are kept as T = wl top and D = wl (bottom - top), so a pixel costs an add and
 // an FMA per level (was three FMA-class operations after nine VALU operations of tap arithmetic per level and row), and the per-row sums
 // stay in fp32 for eight rows before they are widened.  Measured on 64 x (4, 256, 256): see profiles/r05_prof_pyramid.txt.
-template <bool STRIP, int THREADS, bool UNI = false>
-__global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 256 ? 2 : 4)) void pyramid_pass1(const PyramidArgs a) {
+template <bool STRIP, int THREADS, bool UNI = false, typename Args = PyramidArgs>
+__global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 256 ? 2 : 4)) void pyramid_pass1(const Args a) {
+  constexpr bool ROLLING = std::is_same<Args, PyramidRollingArgs>::value;
+  uint64_t stream_base = a.stream_base, stream_levels = a.stream_levels;
+  if constexpr (ROLLING) {  // (blockIdx.x = smp * lead + c)
+    if (!rolling_stream(a.r, (int)blockIdx.x / a.lead, stream_base)) return;
+    stream_levels = a.r.is_static ? 0 : stream_base;
+  }
   extern __shared__ float lds[];  // levels >= 1, back to back
   __shared__ double red[2][THREADS / 64];
   __shared__ int s_lh[PYR_MAX_LEVELS], s_lw[PYR_MAX_LEVELS], s_off[PYR_MAX_LEVELS];
@@ -256,12 +301,12 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 
       for (int j = 0; j < 4; ++j) { ahead_v[r][j] = 0.f; ahead_z[r][j] = 0.f; }
       if (ys + r < a.h && r < rs) {
         const int64_t e0 = ((int64_t)c * a.h + ys + r) * a.w + xs;
-        if (a.with_base) normal4(seed, a.stream_base, (uint64_t)e0 >> 2, ahead_v[r]);
-        normal4(seed, a.stream_levels + 1, (uint64_t)e0 >> 2, ahead_z[r]);
+        if (a.with_base) normal4(seed, stream_base, (uint64_t)e0 >> 2, ahead_v[r]);
+        normal4(seed, stream_levels + 1, (uint64_t)e0 >> 2, ahead_z[r]);
       }
     }
   }
-  if (threadIdx.x < PYR_MAX_LEVELS) s_shrink[threadIdx.x] = pyramid_level_shrink(a, seed, (int)threadIdx.x);
+  if (threadIdx.x < PYR_MAX_LEVELS) s_shrink[threadIdx.x] = pyramid_level_shrink(stream_levels, seed, (int)threadIdx.x);
   __syncthreads();
   if (threadIdx.x < 2) {  // the running sizes (pyramid_level_walk's arithmetic), widths in lane 0 and heights in lane 1
     const bool heights = threadIdx.x == 1;
@@ -304,7 +349,7 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 
     const int64_t e_lo = (int64_t)c * n, b_hi = (e_lo + n + 3) >> 2;
     for (int64_t b = (e_lo >> 2) + threadIdx.x; b < b_hi; b += THREADS) {
       float z[4];
-      normal4(seed, a.stream_levels + 1 + l, (uint64_t)b, z);
+      normal4(seed, stream_levels + 1 + l, (uint64_t)b, z);
       const int at = (int)((b << 2) - e_lo);  // -3 .. n - 1
 #pragma unroll
       for (int j = 0; j < 4; ++j) if (at + j >= 0 && at + j < n) g[at + j] = z[j];
@@ -332,10 +377,10 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 
   auto pixel_group = [&](int y, int x0, int q, auto&& taps) {
     const int64_t e0 = ((int64_t)c * a.h + y) * a.w + x0;  // element index inside the sample
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (a.with_base) normal4(seed, a.stream_base, (uint64_t)e0 >> 2, v);
+    if (a.with_base) normal4(seed, stream_base, (uint64_t)e0 >> 2, v);
     if (w0 != 0.f) {
       float z[4];
-      normal4(seed, a.stream_levels + 1, (uint64_t)e0 >> 2, z);
+      normal4(seed, stream_levels + 1, (uint64_t)e0 >> 2, z);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = fmaf(z[j], w0, v[j]);
     }
@@ -400,13 +445,13 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 
       if (drawn_v) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = drawn_v[j];
-      } else if (a.with_base) normal4(seed, a.stream_base, (uint64_t)e0 >> 2, v);
+      } else if (a.with_base) normal4(seed, stream_base, (uint64_t)e0 >> 2, v);
       if (w0 != 0.f) {
         float z[4];
         if (drawn_z) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) z[j] = drawn_z[j];
-        } else normal4(seed, a.stream_levels + 1, (uint64_t)e0 >> 2, z);
+        } else normal4(seed, stream_levels + 1, (uint64_t)e0 >> 2, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = fmaf(z[j], w0, v[j]);
       }
@@ -522,13 +567,13 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 
       if (drawn_v) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = drawn_v[j];
-      } else if (a.with_base) normal4(seed, a.stream_base, (uint64_t)e0 >> 2, v);
+      } else if (a.with_base) normal4(seed, stream_base, (uint64_t)e0 >> 2, v);
       if (w0 != 0.f) {
         float z[4];
         if (drawn_z) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) z[j] = drawn_z[j];
-        } else normal4(seed, a.stream_levels + 1, (uint64_t)e0 >> 2, z);
+        } else normal4(seed, stream_levels + 1, (uint64_t)e0 >> 2, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = fmaf(z[j], w0, v[j]);
       }
@@ -617,9 +662,13 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 1 : (STRIP && THREADS > 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void normalise_pass2(T* out, const float* scratch, const double* partials, int64_t lead, int64_t unit, int64_t batch, double target /* <0: unit std, 0: no rescale */) {
+// (Rolling...: nothing, or the sample index vector of a rolling batch -- an inactive sample's partials are not read, its slice of `out` keeps its bytes)
+template <typename T, typename... Rolling>
+__global__ __launch_bounds__(256) void normalise_pass2(T* out, const float* scratch, const double* partials, int64_t lead, int64_t unit, int64_t batch, double target /* <0: unit std, 0: no rescale */, Rolling... index) {
   const int64_t smp = blockIdx.y;
+  if constexpr (sizeof...(Rolling) != 0) {
+    if ((index[smp], ...) < 0) return;
+  }
   double s1 = 0.0, s2 = 0.0;
   for (int64_t c = 0; c < lead; ++c) { s1 += partials[(smp * lead + c) * 2]; s2 += partials[(smp * lead + c) * 2 + 1]; }
   const double n = (double)unit;
@@ -779,23 +828,79 @@ static int normalise(void* out, int32_t out_dtype, const skr::PyramidArgs& a, in
   return rc != SKR_OK ? rc : skr::launch_status();
 }
 
+namespace skr {
+// what the rolling entries check of their draw arguments, ahead of the whole-batch entries' own checks
+static int rolling_draw_checks(int64_t batch, int32_t rows_per_slot, uint64_t stream_stride) {
+  if (rows_per_slot < 1 || stream_stride == 0) return SKR_ERR_SHAPE;
+  if (batch > 0 && batch * (int64_t)rows_per_slot > 0x7fffffffll) return SKR_ERR_SHAPE;
+  return SKR_OK;
+}
+// the output types of a rolling batch: its latents', so no fp64
+static int rolling_out_type(int32_t out_dtype) {
+  if (out_dtype == SKR_F64) return SKR_ERR_UNSUPPORTED;
+  return out_dtype == SKR_BF16 || out_dtype == SKR_F16 || out_dtype == SKR_F32 ? SKR_OK : SKR_ERR_DTYPE;
+}
+}  // namespace skr
+
+// The checks of the two Offset entries, in their one order, and the unit as four merged axes.  `empty`: SKR_OK with nothing to launch.
+static int offset_unit(skr::OffsetArgs& a, int64_t batch, const int64_t* unit_shape, int32_t ndim, bool& empty) {
+  empty = false;
+  if (batch < 0 || ndim < 1 || ndim > 4 || !unit_shape) return SKR_ERR_SHAPE;
+  int64_t d[4] = {1, 1, 1, 1};
+  for (int i = 0; i < ndim; ++i) { if (unit_shape[i] < 0) return SKR_ERR_SHAPE; d[4 - ndim + i] = unit_shape[i]; }
+  a.d0 = d[0]; a.d1 = d[1]; a.d2 = d[2]; a.d3 = d[3]; a.batch = batch;
+  empty = batch == 0 || d[0] * d[1] * d[2] * d[3] == 0;
+  return SKR_OK;
+}
+static int offset_args(skr::OffsetArgs& a, void* out, const uint64_t* seeds_dev, int64_t batch, const int64_t* unit_shape, int32_t ndim, uint32_t keep_mask,
+                       double strength, bool& empty) {
+  if (const int rc = offset_unit(a, batch, unit_shape, ndim, empty); rc != SKR_OK || empty) return rc;
+  if (!out || !seeds_dev) return SKR_ERR_NULL;
+  a.out = out; a.seeds = seeds_dev;
+  a.mask = (keep_mask & ((1u << ndim) - 1u)) << (4 - ndim);
+  a.gain = (float)(strength * strength);
+  return SKR_OK;
+}
+
 extern "C" int skr_noise_offset(void* out, int32_t out_dtype, const uint64_t* seeds_dev, uint64_t stream_base, uint64_t stream_offset,
                                 int64_t batch, const int64_t* unit_shape, int32_t ndim, uint32_t keep_mask, double strength, void* stream) {
   skr::DeviceGuard device_guard(out);
-  if (batch < 0 || ndim < 1 || ndim > 4 || !unit_shape) return SKR_ERR_SHAPE;
   skr::OffsetArgs a;
-  int64_t d[4] = {1, 1, 1, 1};
-  for (int i = 0; i < ndim; ++i) { if (unit_shape[i] < 0) return SKR_ERR_SHAPE; d[4 - ndim + i] = unit_shape[i]; }
-  a.d0 = d[0]; a.d1 = d[1]; a.d2 = d[2]; a.d3 = d[3];
-  const int64_t unit = d[0] * d[1] * d[2] * d[3];
-  if (batch == 0 || unit == 0) return SKR_OK;
-  if (!out || !seeds_dev) return SKR_ERR_NULL;
-  a.out = out; a.seeds = seeds_dev; a.stream_base = stream_base; a.stream_offset = stream_offset; a.batch = batch;
-  a.mask = (keep_mask & ((1u << ndim) - 1u)) << (4 - ndim);
-  a.gain = (float)(strength * strength);
+  bool empty;
+  if (const int rc = offset_args(a, out, seeds_dev, batch, unit_shape, ndim, keep_mask, strength, empty); rc != SKR_OK || empty) return rc;
+  a.stream_base = stream_base; a.stream_offset = stream_offset;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int rc = skr::with_out_type(out_dtype, [&](auto t) { skr::launch_offset<typename decltype(t)::type>(a, s); });
   return rc != SKR_OK ? rc : skr::launch_status();
+}
+
+extern "C" int skr_noise_offset_rolling(void* out, int32_t out_dtype, const uint64_t* seeds_dev, const int32_t* sample_index_dev, int32_t rows_per_slot,
+                                        uint64_t stream_stride, int32_t static_offset, int64_t batch, const int64_t* unit_shape, int32_t ndim,
+                                        uint32_t keep_mask, double strength, void* stream) {
+  skr::DeviceGuard device_guard(out);
+  if (const int rc = skr::rolling_draw_checks(batch, rows_per_slot, stream_stride); rc != SKR_OK) return rc;
+  skr::OffsetRollingArgs q;
+  skr::OffsetArgs& a = q;
+  bool empty;
+  if (const int rc = offset_args(a, out, seeds_dev, batch, unit_shape, ndim, keep_mask, strength, empty); rc != SKR_OK || empty) return rc;
+  if (!sample_index_dev) return SKR_ERR_NULL;
+  if (!skr::offset_v8_covers(a)) return SKR_ERR_UNSUPPORTED;  // (there is no rolling form of the any-alignment kernel)
+  if (const int rc = skr::rolling_out_type(out_dtype); rc != SKR_OK) return rc;
+  a.stream_base = 0; a.stream_offset = 0;
+  q.r = {sample_index_dev, rows_per_slot, static_offset ? 1 : 0, stream_stride};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return skr::with_out_type<false>(out_dtype, [&](auto t) {
+    hipLaunchKernelGGL((skr::offset_kernel_v8<typename decltype(t)::type, skr::OffsetRollingArgs>), skr::offset_v8_grid(a), dim3(256), 0, s, q);
+    return skr::launch_status();
+  });
+}
+
+extern "C" int skr_noise_offset_rolling_covers(int64_t batch, const int64_t* unit_shape, int32_t ndim) {
+  skr::OffsetArgs a;
+  a.out = nullptr;
+  bool empty;
+  if (const int rc = offset_unit(a, batch, unit_shape, ndim, empty); rc != SKR_OK || empty) return rc;
+  return skr::offset_v8_covers(a) ? SKR_OK : SKR_ERR_UNSUPPORTED;
 }
 
 namespace skr {
@@ -823,21 +928,45 @@ static PyramidKernel pyramid_kernel(PyramidForm form) {
 }
 }  // namespace skr
 
+namespace skr {
+// The checks of the two LDS entries (skr_noise_pyramid, skr_noise_pyramid_rolling), in their one order, and the route of the plane.
+// `empty`: batch == 0, SKR_OK with nothing to launch.  Nothing here dereferences device memory.
+static int pyramid_lds_checks(const void* const* ptrs, int n_ptrs, int64_t batch, int64_t lead, int64_t h, int64_t w, int32_t resize_h, int32_t depth,
+                              PyramidRoute& route, bool& empty) {
+  empty = false;
+  if (batch < 0 || lead < 1 || h < 1 || w < 1 || depth < 0) return SKR_ERR_SHAPE;
+  if (batch == 0) { empty = true; return SKR_OK; }
+  for (int k = 0; k < n_ptrs; ++k) if (!ptrs[k]) return SKR_ERR_NULL;
+  if (w % 4 != 0 || h > PYR_MAX_SIDE || w > PYR_MAX_SIDE) return SKR_ERR_UNSUPPORTED;
+  if (!resize_h && h != 1) return SKR_ERR_SHAPE;
+  if (batch * lead > 0x7fffffffll || batch > PYR_MAX_BATCH) return SKR_ERR_UNSUPPORTED;
+  // tuning switches, read at the first draw: SKR_PYR_NO_UNI, and SKR_PYR_MODE = 1 generic, 2 strip/512, 3 strip/256, 4 strip/1024
+  static const bool no_uni = env_flag("SKR_PYR_NO_UNI");
+  static const int forced = (int)env_int("SKR_PYR_MODE", 0);
+  route = choose_pyramid_route(h, w, resize_h != 0, no_uni, forced);
+  return route.status;
+}
+
+using PyramidRollingKernel = void (*)(const PyramidRollingArgs);
+static PyramidRollingKernel pyramid_rolling_kernel(PyramidForm form) {
+  switch (form) {
+    case PyramidForm::Strip256: return pyramid_pass1<true, 256, false, PyramidRollingArgs>;
+    case PyramidForm::Strip512: return pyramid_pass1<true, 512, false, PyramidRollingArgs>;
+    case PyramidForm::Strip1024: return pyramid_pass1<true, 1024, false, PyramidRollingArgs>;
+    case PyramidForm::Uni: return pyramid_pass1<true, 1024, true, PyramidRollingArgs>;
+    default: return pyramid_pass1<false, 512, false, PyramidRollingArgs>;
+  }
+}
+}  // namespace skr
+
 extern "C" int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f32, double* partials_f64, int32_t* level_ws /* [batch*17] */,
                                  const uint64_t* seeds_dev, uint64_t stream_base, uint64_t stream_levels, int64_t batch, int64_t lead, int64_t h, int64_t w,
                                  int32_t resize_h, double strength, int32_t depth, int32_t with_base, void* stream) {
   skr::DeviceGuard device_guard(out);
-  if (batch < 0 || lead < 1 || h < 1 || w < 1 || depth < 0) return SKR_ERR_SHAPE;
-  if (batch == 0) return SKR_OK;
-  if (!out || !scratch_f32 || !partials_f64 || !seeds_dev || !level_ws) return SKR_ERR_NULL;
-  if (w % 4 != 0 || h > skr::PYR_MAX_SIDE || w > skr::PYR_MAX_SIDE) return SKR_ERR_UNSUPPORTED;
-  if (!resize_h && h != 1) return SKR_ERR_SHAPE;
-  if (batch * lead > 0x7fffffffll || batch > skr::PYR_MAX_BATCH) return SKR_ERR_UNSUPPORTED;
-  // tuning switches, read at the first draw: SKR_PYR_NO_UNI, and SKR_PYR_MODE = 1 generic, 2 strip/512, 3 strip/256, 4 strip/1024
-  static const bool no_uni = skr::env_flag("SKR_PYR_NO_UNI");
-  static const int forced = (int)skr::env_int("SKR_PYR_MODE", 0);
-  const skr::PyramidRoute route = skr::choose_pyramid_route(h, w, resize_h != 0, no_uni, forced);
-  if (route.status != SKR_OK) return route.status;
+  const void* const ptrs[] = {out, scratch_f32, partials_f64, seeds_dev, level_ws};
+  skr::PyramidRoute route;
+  bool empty;
+  if (const int rc = skr::pyramid_lds_checks(ptrs, 5, batch, lead, h, w, resize_h, depth, route, empty); rc != SKR_OK || empty) return rc;
   skr::PyramidArgs a;
   skr::pyramid_common_args(a, scratch_f32, partials_f64, level_ws, seeds_dev, stream_base, stream_levels, batch, lead, h, w, resize_h != 0, strength, depth, with_base);
   a.ytab_off = route.ytab_off;
@@ -845,6 +974,39 @@ extern "C" int skr_noise_pyramid(void* out, int32_t out_dtype, float* scratch_f3
   const int rc = skr::launch_lds(skr::pyramid_kernel(route.form), dim3((unsigned)(batch * lead)), dim3((unsigned)route.threads), route.lds_bytes, s, a);
   if (rc != SKR_OK) return rc;
   return normalise(out, out_dtype, a, lead, lead * h * w, s);
+}
+
+extern "C" int skr_noise_pyramid_rolling(void* out, int32_t out_dtype, float* scratch_f32, double* partials_f64, int32_t* level_ws /* [batch*17] */,
+                                         const uint64_t* seeds_dev, const int32_t* sample_index_dev, int32_t rows_per_slot, uint64_t stream_stride,
+                                         int32_t static_levels, int64_t batch, int64_t lead, int64_t h, int64_t w, int32_t resize_h, double strength,
+                                         int32_t depth, void* stream) {
+  skr::DeviceGuard device_guard(out);
+  if (const int rc = skr::rolling_draw_checks(batch, rows_per_slot, stream_stride); rc != SKR_OK) return rc;
+  const void* const ptrs[] = {out, scratch_f32, partials_f64, seeds_dev, level_ws, sample_index_dev};
+  skr::PyramidRoute route;
+  bool empty;
+  if (const int rc = skr::pyramid_lds_checks(ptrs, 6, batch, lead, h, w, resize_h, depth, route, empty); rc != SKR_OK || empty) return rc;
+  if (const int rc = skr::rolling_out_type(out_dtype); rc != SKR_OK) return rc;
+  skr::PyramidRollingArgs q;
+  skr::pyramid_common_args(q, scratch_f32, partials_f64, level_ws, seeds_dev, 0, 0, batch, lead, h, w, resize_h != 0, strength, depth, 1);
+  q.ytab_off = route.ytab_off;
+  q.r = {sample_index_dev, rows_per_slot, static_levels ? 1 : 0, stream_stride};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = skr::launch_lds(skr::pyramid_rolling_kernel(route.form), dim3((unsigned)(batch * lead)), dim3((unsigned)route.threads), route.lds_bytes, s, q);
+  if (rc != SKR_OK) return rc;
+  const int64_t unit = lead * h * w;
+  const dim3 grid((unsigned)skr::grid_blocks(unit / 4, 256, 64), (unsigned)batch);  // (normalise()'s grid: w % 4 == 0, so at least one block)
+  return skr::with_out_type<false>(out_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((skr::normalise_pass2<T, const int32_t*>), grid, dim3(256), 0, s, (T*)out, (const float*)scratch_f32, (const double*)partials_f64, lead, unit, batch, -1.0, sample_index_dev);
+    return skr::launch_status();
+  });
+}
+
+extern "C" int skr_noise_pyramid_rolling_covers(int64_t batch, int64_t lead, int64_t h, int64_t w, int32_t resize_h) {
+  skr::PyramidRoute route;
+  bool empty;
+  return skr::pyramid_lds_checks(nullptr, 0, batch, lead, h, w, resize_h, 0, route, empty);
 }
 
 static int pyramid_nd_impl(void* out, int32_t out_dtype, float* scratch_f32, float* levels_f32, double* partials_f64, int32_t n_slots,

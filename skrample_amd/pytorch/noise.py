@@ -209,18 +209,12 @@ class Offset(TensorNoiseCommon):
         noise = PhiloxNoise(self._seeds, self._next_stream() + 1, (1, *reduced), self._device)
         return _lazy.settle(_lazy.lift(noise) * float(self.props.strength) ** 2, dtype=self.dtype)[0]
 
-    @classmethod
-    def _batch(cls, unit_shape, seeds, stream, step, props, dtype, state):
-        import ctypes
-
-        if props.static:  # the offset is drawn once (first call) and reused
-            offset_stream = state.setdefault("offset_stream", stream + 1)
-        else:
-            offset_stream = stream + 1
+    @staticmethod
+    def _merged(unit_shape, props) -> tuple[list[int], int]:
+        """The unit as the kernels see it: (sizes, keep mask).  Neighbouring dimensions that are both kept or both broadcast index the
+        offset tensor as one merged dimension (row-major), so any rank collapses to its runs; the kernel handles four."""
         nd_full = len(unit_shape)
         kept_dims = {d + nd_full if d < 0 else d for d in props.dims}
-        # neighbouring dimensions that are both kept or both broadcast index the offset tensor as one merged dimension
-        # (row-major), so any rank collapses to its runs; the kernel handles four
         merged: list[list] = []
         for i, size in enumerate(unit_shape):
             keep = i in kept_dims
@@ -230,16 +224,48 @@ class Offset(TensorNoiseCommon):
                 merged.append([size, keep])
         if len(merged) > 4:
             raise SkrampleHipError("Offset noise supports up to four alternating runs of kept / broadcast dimensions per sample")
-        nd = len(merged)
-        mask = sum(1 << i for i, (_, keep) in enumerate(merged) if keep)
+        return [m[0] for m in merged], sum(1 << i for i, (_, keep) in enumerate(merged) if keep)
+
+    @classmethod
+    def _batch(cls, unit_shape, seeds, stream, step, props, dtype, state):
+        if props.static:  # the offset is drawn once (first call) and reused
+            offset_stream = state.setdefault("offset_stream", stream + 1)
+        else:
+            offset_stream = stream + 1
+        sizes, mask = cls._merged(unit_shape, props)
         out = torch.empty((seeds.shape[0], *unit_shape), dtype=dtype, device=seeds.device)
         lib, hstream = _launch_ctx(seeds)
-        shape_arr = (ctypes.c_int64 * nd)(*[m[0] for m in merged])
+        shape_arr = (ctypes.c_int64 * len(sizes))(*sizes)
         _hip.check(
-            lib.skr_noise_offset(out.data_ptr(), _hip.DTYPE_CODE[dtype], seeds.data_ptr(), stream, offset_stream, seeds.shape[0], shape_arr, nd, mask, float(props.strength), hstream),
+            lib.skr_noise_offset(out.data_ptr(), _hip.DTYPE_CODE[dtype], seeds.data_ptr(), stream, offset_stream, seeds.shape[0], shape_arr, len(sizes), mask, float(props.strength), hstream),
             "skr_noise_offset",
         )
         return out
+
+    # ---- rolling batches (skrample_amd.rolling): every sample at its own draw, one launch, nothing allocated per call ----
+    @classmethod
+    def rolling_refusal(cls, unit_shape, props, capacity: int) -> str | None:
+        "why skr_noise_offset_rolling does not draw this unit (asked of the library's own checks, nothing launched), or None"
+        sizes, _ = cls._merged(unit_shape, props)
+        status = _hip.load().skr_noise_offset_rolling_covers(capacity, (ctypes.c_int64 * len(sizes))(*sizes), len(sizes))
+        if status == _hip.SKR_ERR_UNSUPPORTED:
+            return f"units of merged axes {sizes} are outside the aligned Offset kernel (innermost merged axis a multiple of 8, fewer than 2^31 elements, at most 65535 samples)"
+        _hip.check(status, "skr_noise_offset_rolling_covers")
+        return None
+
+    @classmethod
+    def rolling_workspace(cls, unit_shape, props, capacity: int, device) -> tuple:
+        return ()
+
+    @classmethod
+    def _rolling(cls, out, workspace, seeds, index, rows_per_slot: int, props) -> None:
+        """Draw, into `out` [capacity, *unit], the sample of every slot whose `index` entry is not negative, at draw number
+        index[b] - b * rows_per_slot of its own generator: the bits `_batch` gives that sample alone at stream draw * SUBSTREAMS."""
+        sizes, mask = cls._merged(tuple(out.shape[1:]), props)
+        lib, hstream = _launch_ctx(seeds)
+        status = lib.skr_noise_offset_rolling(out.data_ptr(), _hip.DTYPE_CODE[out.dtype], seeds.data_ptr(), index.data_ptr(), rows_per_slot, SUBSTREAMS, 1 if props.static else 0,
+                                              out.shape[0], (ctypes.c_int64 * len(sizes))(*sizes), len(sizes), mask, float(props.strength), hstream)  # fmt: skip
+        _hip.check(status, "skr_noise_offset_rolling")
 
 
 @dataclass(frozen=True)
@@ -380,6 +406,41 @@ class Pyramid(TensorNoiseCommon):
             state[key] = allocate()
         return state[key]
 
+    @staticmethod
+    def _lds_workspace(batch: int, unit: int, lead: int, dev) -> tuple:
+        "what the LDS kernels keep between their passes: fp32 sums [batch * unit], the level table int32 [batch * 17], a partial pair per leading slice"
+        return (torch.empty(batch * unit, dtype=torch.float32, device=dev), torch.empty(batch * (PYRAMID_MAX_LEVELS * 2 + 1), dtype=torch.int32, device=dev),
+                torch.empty(batch * 2 * lead, dtype=torch.float64, device=dev))  # fmt: skip
+
+    # ---- rolling batches (skrample_amd.rolling): every sample at its own draw, nothing allocated per call -------------------
+    @classmethod
+    def rolling_refusal(cls, unit_shape, props, capacity: int) -> str | None:
+        "why skr_noise_pyramid_rolling does not draw this unit (the route decision `_batch` shares, asked of the library with nothing launched), or None"
+        entry, shape_args, _ = cls._plan(unit_shape, props)
+        if entry != "skr_noise_pyramid":
+            return f"Pyramid dims {tuple(props.dims)} are not the trailing axes of the unit: the any-shape kernels have no rolling form"
+        status = _hip.load().skr_noise_pyramid_rolling_covers(capacity, *shape_args)
+        if status == _hip.SKR_ERR_UNSUPPORTED:
+            return f"planes of {shape_args[1]} x {shape_args[2]} are outside the LDS route of the Pyramid kernels (the any-shape kernels have no rolling form)"
+        _hip.check(status, "skr_noise_pyramid_rolling_covers")
+        return None
+
+    @classmethod
+    def rolling_workspace(cls, unit_shape, props, capacity: int, device) -> tuple:
+        _, shape_args, _ = cls._plan(unit_shape, props)
+        return cls._lds_workspace(capacity, math.prod(unit_shape), shape_args[0], device)
+
+    @classmethod
+    def _rolling(cls, out, workspace, seeds, index, rows_per_slot: int, props) -> None:
+        """Draw, into `out` [capacity, *unit], the sample of every slot whose `index` entry is not negative, at draw number
+        index[b] - b * rows_per_slot of its own generator: the bits `_batch` gives that sample alone at stream draw * SUBSTREAMS."""
+        _, shape_args, _ = cls._plan(tuple(out.shape[1:]), props)
+        scratch, levels, partials = workspace
+        lib, hstream = _launch_ctx(seeds)
+        status = lib.skr_noise_pyramid_rolling(out.data_ptr(), _hip.DTYPE_CODE[out.dtype], scratch.data_ptr(), partials.data_ptr(), levels.data_ptr(), seeds.data_ptr(), index.data_ptr(),
+                                               rows_per_slot, SUBSTREAMS, 1 if props.static else 0, out.shape[0], *shape_args, float(props.strength), int(min(props.depth, 1 << 20)), hstream)  # fmt: skip
+        _hip.check(status, "skr_noise_pyramid_rolling")
+
     @classmethod
     def _batch(cls, unit_shape, seeds, stream, step, props, dtype, state, with_base: bool = True):
         # static: the pyramid component is frozen at the first draw (same streams every time), only the base changes
@@ -395,8 +456,9 @@ class Pyramid(TensorNoiseCommon):
             return empty(unit), empty(2 * slots, torch.float64)
 
         def allocate():  # pass 1's sums, the level table ([8][2] sizes and a count), then the entry's own (LDS kernels: a partial pair per leading slice)
-            own = (empty(2 * shape_args[0], torch.float64),) if entry == "skr_noise_pyramid" else any_shape()
-            return empty(unit), empty(PYRAMID_MAX_LEVELS * 2 + 1, torch.int32), *own
+            if entry == "skr_noise_pyramid":
+                return cls._lds_workspace(batch, unit, shape_args[0], dev)
+            return empty(unit), empty(PYRAMID_MAX_LEVELS * 2 + 1, torch.int32), *any_shape()
 
         scratch, levels, *own = cls._workspace(state, (kind, batch, *shape_key), allocate)
         out = torch.empty((batch, *unit_shape), dtype=dtype, device=dev)

@@ -47,14 +47,31 @@ zero, `orig` / `znoise` absent -- under a mask of ones.  `step()`, `advance()`, 
 mean on a plain batch.  Covered there: the samplers whose masked step is one single-output launch -- Euler, DPM 1-3, Adams 2-4, UniP
 2-3.  UniPC and SPC blend with a second launch and are refused when the batch is built ("not one fused launch").
 
+Structured noise.  A batch whose `make_wrapper()` has `noise_type` Offset or Pyramid (pytorch/noise.py) and a sampler that draws is
+a structured-noise batch: the noise is a whole-batch TENSOR the batch owns, `[capacity, *unit_shape]` in the latents' dtype, and an
+operand of the step like any other -- role ("n",) for this tick's draw and ("pn", k) for the draw of -k ticks ago (UniPC's corrector
+re-evaluates the previous step with the previous draw), its coefficient in `coef0` / `coef1`; the plan's `noise_mode` is 0 and the step
+launch gets no seeds.  A tick draws with ONE call of the generator's rolling entry (`skr_noise_offset_rolling` /
+`skr_noise_pyramid_rolling`, csrc/skr_noise.hip) after the index is on the device and before the step launch: the kernels read the same
+index vector, draw slot b at draw number `index[b] - b * max_steps` -- its position in its own run, the wrappers draw exactly once per
+step -- with the streams its lone generator would use, and leave inactive slots alone.  Where a ("pn", k) occurs the noise tensors form a
+ring as long as the latents ring (so that the phases of `CapturedTicks` close); the generator's workspaces for `capacity` samples are
+allocated once, when the batch is built.  A new request never reads its slot's previous occupant's noise: its first row has zeros in
+every ("pn", k) slot.  `admit()` refuses a wrapper whose `noise_props` differ from the batch's (strength, depth, dims and static are
+launch arguments).  Refused when the batch is built: Colored, Brownian and custom generator classes, `prefetch_noise=True`, a unit
+the rolling entry does not cover (asked of the library's route decision, nothing launched), and `inpaint_mask_shape` beside
+structured noise.
+
 Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
-`Random` noise (drawn in the kernel) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
+`Random` noise (drawn in the kernel), `Offset` / `Pyramid` noise (drawn per slot, above) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
 `skr_step_launch_indexed` covers (UniPC on fp32 latents is refused, as by the captured loops); a device-resident position vector
 (`device_positions=True`: csrc/skr_rolling.hip advances positions the host validated once at `admit()`, so the index the step
 kernel reads is inside the slot's own run by construction) and graph capture of ticks (`capture()`: one graph per ring phase holds
 the advance and the network; the step launch follows each replay eagerly, which is what lets the graphs' static outputs be the
 model-output history, aliased and never copied).  Not covered: the Runge-Kutta wrapper classes (the kernel form exists, the stage
-bookkeeping does not), structured noise, autograd, runs longer than `max_steps`, the step launch inside the graph (its history
+bookkeeping does not), Colored and Brownian noise (Colored's persistent plane kernels claim planes by ticket, Brownian's weights are a host
+walk per step interval), Pyramid units of the any-shape / nd routes and Offset units outside the aligned kernel, structured noise in
+masked batches, the draw inside the captured graph, autograd, runs longer than `max_steps`, the step launch inside the graph (its history
 operands are the other graphs' outputs, which exist only once every graph is captured: it would force a snapshot of every model output).
 """
 
@@ -69,7 +86,8 @@ from . import _hip
 from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepMaskC, StepPlanC, StepRowC, upload_rows
 from .sampling import lazy
 
-Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py; ("orig",) ("znoise",): a masked batch's original / re-noising tensor
+Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py; ("orig",) ("znoise",): a masked batch's original / re-noising tensor;
+# ("n",) ("pn", k): a structured-noise batch's draw of this tick / of -k ticks ago
 
 ALIAS_HELP = (
     "a model output passed to an earlier step() is still a history operand of this batch and {what}; RollingBatch aliases the caller's "
@@ -127,6 +145,19 @@ def advance_reference(position: list, length: list, times: list, max_steps: int)
     return new_position, index, timestep
 
 
+def draw_reference(index: list, max_steps: int, static: bool, stride: int = 256) -> list:
+    """What the rolling generator entries derive from the index vector, in plain Python: per slot None (inactive: nothing drawn, nothing
+    read) or (stream_base, auxiliary stream) -- the auxiliary stream is `stream_levels` of Pyramid; Offset's `stream_offset` is one more."""
+    out = []
+    for b, at in enumerate(index):
+        if at < 0:
+            out.append(None)
+            continue
+        base = (at - b * max_steps) * stride
+        out.append((base, 0 if static else base))
+    return out
+
+
 class _Request:
     __slots__ = ("rows", "times", "position")
 
@@ -161,11 +192,12 @@ class RollingBatch:
             raise ValueError(f"per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {self.sample_numel} elements per sample")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
+        self.draws_noise = bool(first.sampler.require_noise)
+        self.structured = self.draws_noise and self._init_noise(first)
         if self.masked:
             self._init_inpaint(tuple(int(n) for n in inpaint_mask_shape), first)
         self.structure = sampler_structure(first)
         self.keep = int(first.sampler.require_previous)
-        self.draws_noise = bool(first.sampler.require_noise)
         self.plan, self.roles = self._widest(self._trace(first, self.keep + 4, seed=0 if self.draws_noise else None))
         self.two_outputs = self.plan.out0_dtype != _hip.NONE and self.plan.out1_dtype != _hip.NONE
         if self.plan.n_terms > ROW_TERMS:
@@ -177,6 +209,10 @@ class RollingBatch:
         state_dtype = _hip.CODE_DTYPE[self.plan.out0_dtype] if self.two_outputs else None
         self._state = [torch.zeros(shape, dtype=state_dtype, device=self.device) for _ in range(depth + 1)] if self.two_outputs else []
         self._blank = torch.zeros(shape, dtype=self.dtype, device=self.device)  # stands for a model output no tick has produced yet
+        if self.structured:
+            # the noise tensors, oldest first: [-1] is the latest draw; a ring as long as the latents ring where a step reads an earlier draw
+            self._n = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1 if any(r[0] == "pn" for r in self.roles) else 1)]
+            self._noise_ws = self.noise_type.rolling_workspace(self.unit_shape, self.noise_props, self.capacity, self.device)
         self._outputs: list[torch.Tensor] = []
         self._stamps: list[tuple[torch.Tensor, int, int]] = []
         self._results: dict[int, torch.Tensor] = {}
@@ -195,6 +231,29 @@ class RollingBatch:
             self.position_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
             self.length_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
             self.times_dev = torch.zeros(self.capacity * self.max_steps, dtype=torch.float32, device=self.device)
+
+    def _init_noise(self, first) -> bool:
+        "a wrapper whose sampler draws: False for `Random` (drawn in the step kernel), True for a generator the batch draws per slot, or the refusal"
+        from .pytorch import noise as generators
+
+        kind = first.noise_type
+        if kind is generators.Random:
+            return False
+        defaults = {generators.Offset: generators.OffsetProps(), generators.Pyramid: generators.PyramidProps()}
+        if kind not in defaults:
+            why = {generators.Colored: "its persistent plane kernels claim planes by ticket and have no per-slot form",
+                   generators.Brownian: "its weights are a host walk per step interval"}.get(kind, "a custom generator class has no per-slot kernel form")  # fmt: skip
+            raise SkrampleHipError(f"{getattr(kind, '__name__', kind)} noise cannot join a rolling batch ({why}): a rolling batch draws Random, Offset or Pyramid noise")
+        if self.masked:
+            raise ValueError(f"inpaint_mask_shape together with {kind.__name__} noise: a masked rolling batch draws Random noise or none")
+        if getattr(first, "prefetch_noise", False):
+            raise ValueError("prefetch_noise=True draws a step's noise ahead on a side stream of the wrapper: a rolling batch draws every slot's noise itself, per tick")
+        self.noise_type = kind
+        self.noise_props = first.noise_props if first.noise_props is not None else defaults[kind]
+        refused = kind.rolling_refusal(self.unit_shape, self.noise_props, self.capacity)
+        if refused is not None:
+            raise SkrampleHipError(f"{kind.__name__} noise on samples {self.unit_shape}: {refused}")
+        return True
 
     def _init_inpaint(self, mask_shape: tuple, first) -> None:
         """A masked batch: the three whole-batch in-paint tensors (every slot's mask starts as ones: generate everything), the mask
@@ -229,13 +288,21 @@ class RollingBatch:
         wrapper.set_timesteps(steps)
         x = torch.zeros((1, *self.unit_shape), dtype=self.dtype, device=self.device)
         found = []
+        draws = self.structured and bool(wrapper.sampler.require_noise)
         for t in wrapper.timesteps.tolist():
             out = torch.zeros_like(x)
             known: dict[int, Role] = {}
+            if draws:
+                # the step's realised noise: handed to the wrapper in place of a draw of its generator (the wrapper consumes one draw per
+                # step either way, and the coefficient of the operand does not depend on its contents)
+                wrapper._predrawn_noise = torch.zeros_like(x)
+                known[wrapper._predrawn_noise.data_ptr()] = ("n",)
             for k in range(-len(wrapper._previous), 0):
                 state = wrapper._previous[k].sample
                 if isinstance(state, torch.Tensor):
                     known[state.data_ptr()] = ("px", k)
+                if draws and isinstance(wrapper._previous[k].noise, torch.Tensor):
+                    known[wrapper._previous[k].noise.data_ptr()] = ("pn", k)
                 known[wrapper._raw_outputs[k].data_ptr()] = ("po", k)
                 known[wrapper._raw_samples[k].data_ptr()] = ("pi", k)
             held = _hip.trace
@@ -271,9 +338,14 @@ class RollingBatch:
             return
         lib = _hip.load()
         status = lib.skr_step_launch_rolling(ctypes.byref(self.plan), arr, out0.data_ptr() if out0 is not None else None, out1.data_ptr() if out1 is not None else None,
-                                             self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0,
+                                             self.seeds_dev.data_ptr() if self.draws_noise and not self.structured else None, self.numel, self.rows_dev.data_ptr(),
+                                             self.index_dev.data_ptr(), 0,
                                              _hip.current_stream_ptr(self.device))  # fmt: skip
         _hip.check(status, "skr_step_launch_rolling")
+
+    def _draw(self, out: torch.Tensor) -> None:
+        "a structured-noise batch: ONE launch of the generator's rolling entry draws, into `out`, every slot the index on the device names"
+        self.noise_type._rolling(out, self._noise_ws, self.seeds_dev, self.index_dev, self.max_steps, self.noise_props)
 
     def _advance(self) -> None:
         lib = _hip.load()
@@ -311,7 +383,7 @@ class RollingBatch:
                 wide.n_group_a += 1
                 wide.n_terms += 1
         wide.sample_numel = self.sample_numel
-        if self.draws_noise:
+        if self.draws_noise and not self.structured:  # (structured noise is an operand, drawn by a launch of its own)
             wide.noise_mode = 1
         if self.dtype == torch.float32 and wide.out0_dtype != _hip.NONE and wide.out1_dtype != _hip.NONE:
             raise SkrampleHipError("skr_step_launch_rolling: request outside kernel coverage (the two-output table kernels take 16-bit operands)")
@@ -350,7 +422,7 @@ class RollingBatch:
 
     def ring_tensors(self) -> list[torch.Tensor]:
         "every whole-batch tensor a history operand may be bound to: the batch's own latents and states, snapshots of model outputs"
-        owned = self._x[:-1] + list(self._state) + [self._blank]
+        owned = self._x[:-1] + list(self._state) + [self._blank] + (list(self._n) if self.structured else [])
         return owned + ([] if self.alias_history else list(self._outputs))
 
     def index_vector(self) -> list[int]:
@@ -383,6 +455,11 @@ class RollingBatch:
         noisy = bool(wrapper.sampler.require_noise)
         if noisy and not self.draws_noise:
             raise ValueError("this wrapper draws noise and the batch's sampler structure does not")
+        if noisy and self.structured:
+            if (wrapper.noise_props if wrapper.noise_props is not None else type(self.noise_props)()) != self.noise_props:
+                raise ValueError(f"this wrapper's noise_props {wrapper.noise_props} are not the batch's {self.noise_props}: they are arguments of the one draw launch")
+            if getattr(wrapper, "prefetch_noise", False):
+                raise ValueError("prefetch_noise=True: a rolling batch draws every slot's noise itself")
         if noisy and seed is None:
             raise ValueError("a request that draws noise needs a seed")
         if tuple(latents.shape) not in (self.unit_shape, (1, *self.unit_shape)) or latents.dtype != self.dtype:
@@ -459,8 +536,10 @@ class RollingBatch:
             return self._blank
         if kind in ("orig", "znoise") and self.masked:
             return self.original if kind == "orig" else self.noise
+        if kind in ("n", "pn") and self.structured:  # (bound after this tick's rotation: [-1] is the tensor this tick draws into)
+            return self._n[-1] if kind == "n" else self._n[(role[1] - 1) % len(self._n)]
         if len(role) < 2:
-            raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (structured noise tensors are not covered)")
+            raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
         k = role[1]
         if kind == "pi":
             return self._x[k - 1]
@@ -468,7 +547,7 @@ class RollingBatch:
             return self._state[k]
         if kind == "po":
             return self._outputs[k] if -k <= len(self._outputs) else self._blank
-        raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (structured noise tensors are not covered)")
+        raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
 
     def step(self, model_output: torch.Tensor) -> list[int]:
         "advance every active slot by one step of its own run with ONE launch; returns the slots that finished with this tick"
@@ -485,9 +564,13 @@ class RollingBatch:
             self._guard(model_output)
         elif self.keep:
             model_output = model_output.clone()
+        if self.structured:
+            self._n.append(self._n.pop(0))  # the oldest draw's tensor takes this tick's
         operands = [self._bind(role, model_output) for role in self.roles]
         if not self.device_positions:
             self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
+        if self.structured:
+            self._draw(self._n[-1])  # behind the index, ahead of the step launch that reads it
         arr = (ctypes.c_void_p * max(len(operands), 1))(*[t.data_ptr() for t in operands])
         # the oldest ring entries take this tick's results: no operand of the structure reaches that far back
         new_x = self._x.pop(0)
@@ -557,7 +640,8 @@ class CapturedTicks:
 
     The latents and states rotate through rings of P = keep + 2 tensors, so a tick has one of P operand bindings: graph p holds, on
     one stream, the advance launch and `out_p = model(latents of phase p, timesteps)`.  `tick()` replays graph `ticks mod P` and
-    follows it with one eager skr_step_launch_rolling whose operand array was built at capture time.  The step stays outside the
+    follows it with one eager skr_step_launch_rolling whose operand array was built at capture time (a structured-noise batch: with the
+    one draw launch of the phase's noise tensor between the two, eager for the same reason).  The step stays outside the
     graphs because its history operand ("po", k) is the static output of graph (p + k) mod P, which exists only once every graph
     is captured -- and that is why no model output is ever copied: the P static outputs ARE the model-output ring (it needs
     keep + 1 of them), they belong to the graphs, and nobody else can overwrite them (no alias guard).  `admit()` / `take()` of
@@ -575,8 +659,7 @@ class CapturedTicks:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         # phase p reads the ring as it stands after p rotations; P rotations bring it back
-        x_ring, state_ring = list(batch._x), list(batch._state)
-        latents = [x_ring[(P - 1 + p) % P] for p in range(P)]
+        latents = [batch._x[(P - 1 + p) % P] for p in range(P)]
         self.graphs: list[torch.cuda.CUDAGraph] = []
         self.outputs: list[torch.Tensor] = []  # referenced here so that the graphs' pool keeps them alive
         pool = torch.cuda.graph_pool_handle()
@@ -589,6 +672,18 @@ class CapturedTicks:
                 raise ValueError(f"the model output of a tick is a contiguous {tuple(latents[p].shape)} {batch.dtype} tensor on {dev}")
             self.graphs.append(graph)
             self.outputs.append(out)
+        self._bind_phases()
+        self.ticks = 0
+        self.replays = [0] * P
+
+    def _bind_phases(self) -> None:
+        "the operand arrays and outputs of every phase's step launch, and the tensor its draw goes to, from the rings as they stand and the graphs' outputs"
+        batch, P = self.batch, self.phases
+        x_ring, state_ring = list(batch._x), list(batch._state)
+        latents = [x_ring[(P - 1 + p) % P] for p in range(P)]
+        # a structured-noise batch: the tick of phase p draws into n_ring[p mod its length] -- one tensor, or a ring of P (the eager rotation of step())
+        n_ring = list(batch._n) if batch.structured else []
+        self._draws = [n_ring[p % len(n_ring)] for p in range(P)] if batch.structured else None
         self._launches = []  # per phase: (operand pointers, out0, out1, the tensor that holds the tick's new latents)
         for p in range(P):
             ptrs = []
@@ -602,6 +697,8 @@ class CapturedTicks:
                     t = batch._blank
                 elif kind in ("orig", "znoise") and batch.masked:  # the batch's own in-paint tensors: the same in every phase
                     t = batch.original if kind == "orig" else batch.noise
+                elif kind in ("n", "pn") and batch.structured:  # phase p draws into n_ring[p]; the draw of -k ticks ago is k places before it
+                    t = n_ring[(p + (role[1] if kind == "pn" else 0)) % len(n_ring)]
                 elif kind == "pi":  # the latents of -k ticks ago
                     t = x_ring[(P - 1 + p + role[1]) % P]
                 elif kind == "px":
@@ -609,7 +706,7 @@ class CapturedTicks:
                 elif kind == "po":  # the static output of the graph replayed -k ticks ago
                     t = self.outputs[(p + role[1]) % P]
                 else:
-                    raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (structured noise tensors are not covered)")
+                    raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
                 ptrs.append(t.data_ptr())
             arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
             new_x = x_ring[p]
@@ -619,11 +716,9 @@ class CapturedTicks:
                 self._launches.append((arr, new_x, None, new_x))
             else:
                 self._launches.append((arr, None, new_x, new_x))
-        self.ticks = 0
-        self.replays = [0] * P
 
     def tick(self) -> list[int]:
-        "one graph replay (advance + network) and ONE step launch; returns the slots that finished with this tick"
+        "one graph replay (advance + network), the draw of a structured-noise batch, and ONE step launch; returns the slots that finished with this tick"
         batch = self.batch
         live = []
         for b, req in enumerate(batch._requests):
@@ -637,6 +732,9 @@ class CapturedTicks:
         phase = self.ticks % self.phases
         arr, out0, out1, new_x = self._launches[phase]
         self.graphs[phase].replay()
+        if self._draws is not None:  # eager like the step launch, between the advance (in the graph) and the step that reads the draw
+            batch._draw(self._draws[phase])
+            batch._n.append(batch._n.pop(0))
         batch._launch(arr, out0, out1)
         # the batch's rings follow, so that `latents` is where admit() must write
         batch._x.append(batch._x.pop(0))

@@ -1,0 +1,114 @@
+"""The rolling forms of the Offset and Pyramid generator kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
+
+`skr_noise_offset_rolling` and `skr_noise_pyramid_rolling` run `offset_kernel_v8<T, OffsetRollingArgs>`, the five
+`pyramid_pass1<STRIP, THREADS, UNI, PyramidRollingArgs>` and `normalise_pass2<T, const int32_t*>` (csrc/skr_noise.hip): the whole-batch
+kernels' own code behind one scalar load of the sample's index.  The contract is visible in the instruction stream, as that of the
+rolling step kernels is (tests/test_masked_rolling_isa.py): a workgroup of an inactive sample ends on a scalar branch before its first
+vector-memory instruction -- and before any LDS or Philox work, which the position of the branch shows -- no access is a flat one, and
+no rolling kernel spills more than its whole-batch twin (the 1024-lane strips spill by design).  VGPR counts and waves per SIMD are
+printed beside the twins' for DESIGN.md section 4.3; no occupancy bracket is asserted."""
+
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+from conftest import ROOT
+
+import __graft_entry__ as G
+
+CSRC = os.path.join(ROOT, "skrample_amd", "csrc")
+HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
+LDS = re.compile(r"^ds_")
+BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
+# (rolling symbol pattern, whole-batch twin pattern): the groups name the instantiation
+FAMILIES = {
+    "offset_kernel_v8": (re.compile(r"offset_kernel_v8I(\w+?)NS_17OffsetRollingArgsEEE"), re.compile(r"offset_kernel_v8I(\w+?)NS_10OffsetArgsEEE")),
+    "pyramid_pass1": (re.compile(r"pyramid_pass1ILb([01])ELi(\d+)ELb([01])ENS_18PyramidRollingArgsEEE"), re.compile(r"pyramid_pass1ILb([01])ELi(\d+)ELb([01])ENS_11PyramidArgsEEE")),
+    "normalise_pass2": (re.compile(r"normalise_pass2I(\w+?)JPKiEEE"), re.compile(r"normalise_pass2I(\w+?)JEEE")),
+}
+TYPES = {"DF16b", "DF16_", "f"}  # bf16, fp16, fp32: a rolling batch holds no fp64 latents
+WANT = {
+    "offset_kernel_v8": {(t,) for t in TYPES},
+    "pyramid_pass1": {("0", "512", "0"), ("1", "256", "0"), ("1", "512", "0"), ("1", "1024", "0"), ("1", "1024", "1")},
+    "normalise_pass2": {(t,) for t in TYPES},
+}
+
+
+def waves_per_simd(vgprs: int) -> int:
+    "gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, at most 8 waves"
+    return min(8, 512 // (max(1, -(-vgprs // 8)) * 8))
+
+
+@pytest.fixture(scope="module")
+def compiled(tmp_path_factory):
+    "{symbol: (instructions and labels, VGPRs, scratch bytes)} of every kernel of skr_noise.hip"
+    if HIPCC is None:
+        pytest.skip("no hipcc on this box")
+    work = str(tmp_path_factory.mktemp("isa") / "noise")
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *G.PER_FILE_FLAGS.get("skr_noise.hip", [])]
+    os.makedirs(work)
+    subprocess.run([HIPCC, *flags, "--save-temps", "-c", "-o", os.path.join(work, "x.o"), os.path.join(CSRC, "skr_noise.hip")], check=True, cwd=work, capture_output=True)
+    asm = [f for f in os.listdir(work) if f.endswith("gfx950.s")]
+    assert len(asm) == 1, asm
+    text = open(os.path.join(work, asm[0])).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):.*?^\.Lfunc_end\d+:.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", text, re.S | re.M):
+        body = m.group(0).split(".Lfunc_end")[0]
+        lines = [raw.split(";")[0].strip() for raw in body.splitlines()[1:]]
+        out[m.group(1)] = ([l for l in lines if l and (not l.startswith(".") or l.startswith(".LBB"))], int(m.group(2)), int(m.group(3)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def pairs(compiled):
+    "{(family, instantiation): (rolling kernel, whole-batch twin)}"
+    found = {}
+    for family, (rolling, twin) in FAMILIES.items():
+        mine = {rolling.search(k).groups(): v for k, v in compiled.items() if rolling.search(k)}
+        theirs = {twin.search(k).groups(): v for k, v in compiled.items() if twin.search(k)}
+        assert set(mine) == WANT[family], (family, sorted(mine))
+        for key, kernel in mine.items():
+            assert key in theirs, (family, key)
+            found[family, key] = (kernel, theirs[key])
+    return found
+
+
+def test_all_eleven_rolling_instantiations_exist(pairs):
+    assert len(pairs) == 11
+
+
+def test_inactive_exit_precedes_the_first_vector_memory_and_lds_instruction(pairs):
+    "a conditional scalar branch whose target runs into s_endpgm, ahead of the first vector-memory and the first LDS instruction"
+    for key, ((lines, *_), _) in pairs.items():
+        first = min(i for i, l in enumerate(lines) if VMEM.match(l) or LDS.match(l))
+        labels = {l[:-1]: i for i, l in enumerate(lines) if l.startswith(".LBB") and l.endswith(":")}
+        exit_at = None
+        for i, l in enumerate(lines[:first]):
+            if exit_at is None and l.startswith(BRANCH):
+                tail = [t for t in lines[labels[l.split()[-1]] :] if not t.startswith(".LBB")]
+                if tail[0] == "s_endpgm":
+                    exit_at = i
+        assert exit_at is not None, (key, lines[:first][-12:])
+        # the index itself came through the scalar cache, and no exec masking stands in for the branch
+        assert any(l.startswith("s_load_dword ") for l in lines[:exit_at]), key
+        assert not any("saveexec" in l for l in lines[:exit_at]), key
+
+
+def test_no_flat_access(pairs):
+    for key, ((lines, *_), _) in pairs.items():
+        assert not any(l.startswith("flat_") for l in lines), key
+
+
+def test_scratch_no_larger_than_the_twin(pairs):
+    for key, ((_, _, scratch), (_, _, twin_scratch)) in pairs.items():
+        assert scratch <= twin_scratch, (key, scratch, twin_scratch)
+
+
+def test_vgpr_table_against_the_whole_batch_twins(pairs):
+    "printed for DESIGN.md section 4.3 (run with -s); nothing is asserted: no occupancy bracket"
+    print("\nVGPRs (waves per SIMD) / scratch bytes: rolling form vs whole-batch twin")
+    for (family, key), ((_, vgprs, scratch), (_, twin_vgprs, twin_scratch)) in sorted(pairs.items()):
+        print(f"  {family}<{', '.join(key)}>: {vgprs:3d} ({waves_per_simd(vgprs)}) / {scratch:4d}  vs  {twin_vgprs:3d} ({waves_per_simd(twin_vgprs)}) / {twin_scratch:4d}")

@@ -1,5 +1,6 @@
 // Shared device helpers of the fused step kernels (skr_step.hip: general + grid-stride kernels; skr_step_fast.hip:
-// one-trip compile-time kernels): lane ownership, loads / stores, rounded conversion, tuning switches.
+// one-trip compile-time kernels; skr_step_masked.hip and the two backward files): lane ownership, loads / stores, the device-resident
+// row and chunk -> sample helpers, rounded conversion, tuning switches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -100,6 +101,34 @@ struct RowRef {
 };
 __device__ __forceinline__ const skr_step_row* row_of(const RowRef& r) {  // (only called by the TAB instantiations: rows != nullptr)
   return r.rows + ((r.index != nullptr ? r.index[0] : 0) + r.row_offset);
+}
+
+// chunk -> (sample, chunk within the sample).  bps_shift >= 0: a power-of-two number of chunks per sample (shift);
+// bps_shift < 0: -bps_shift chunks per sample (e.g. 18 for 4x96x96 latents), one uniform integer division per wave.
+__device__ __forceinline__ void sample_of(uint32_t c, int32_t bps_shift, uint32_t& smp, uint32_t& within) {
+  if (bps_shift >= 0) { smp = c >> bps_shift; within = c - (smp << bps_shift); }
+  else { const uint32_t bps = (uint32_t)(-bps_shift); smp = c / bps; within = c - smp * bps; }
+}
+// what the host puts into bps_shift for `bps` chunks per sample
+static inline int bps_shift_of(int64_t bps) {
+  if ((bps & (bps - 1)) != 0) return -(int)bps;  // any chunk count per sample: the kernel divides
+  int shift = 0;
+  while ((1ll << shift) < bps) ++shift;
+  return shift;
+}
+
+// Rolling form: the row of chunk c's sample, or nullptr for an inactive sample (index entry < 0, tested before row_offset is added).
+// sample_of keeps its branch here (nothing stands in front of it that the division could be hoisted over, and power-of-two samples
+// then never divide); the sample id goes through readfirstlane so that the index entry and the row are scalar loads.
+__device__ __forceinline__ const skr_step_row* rolling_row(const RowRef& r, uint32_t c, int32_t bps_shift, uint32_t& smp, uint32_t& within) {
+  sample_of(c, bps_shift, smp, within);
+  smp = __builtin_amdgcn_readfirstlane(smp);
+  const int32_t at = r.index[smp];
+  return at < 0 ? nullptr : r.rows + (at + r.row_offset);
+}
+// an operand is present unless both of its coefficients are exactly zero (either sign): decided on the row's doubles, in SGPRs
+__device__ __forceinline__ bool row_has(const skr_step_row* row, int j) {
+  return ((__builtin_bit_cast(uint64_t, row->coef0[j]) | __builtin_bit_cast(uint64_t, row->coef1[j])) << 1) != 0;
 }
 
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }

@@ -31,12 +31,8 @@ struct OneTripArgs {
   RowRef tab;
 };
 
-// chunk -> (sample, chunk within the sample).  bps_shift >= 0: a power-of-two number of chunks per sample (shift);
-// bps_shift < 0: -bps_shift chunks per sample (e.g. 18 for 4x96x96 latents), one uniform integer division per wave.
-__device__ __forceinline__ void sample_of(uint32_t c, int32_t bps_shift, uint32_t& smp, uint32_t& within) {
-  if (bps_shift >= 0) { smp = c >> bps_shift; within = c - (smp << bps_shift); }
-  else { const uint32_t bps = (uint32_t)(-bps_shift); smp = c / bps; within = c - smp * bps; }
-}
+// (chunk -> sample: sample_of; the rolling form's row and its present operands: rolling_row / row_has -- all three in skr_step_common.h,
+//  shared with the masked step kernels of skr_step_masked.hip)
 
 // Per-sample rows (skr_step_launch_indexed_per_sample) are a compile-time form of the TAB instantiations, selected by wrapping the
 // element type: step_kernel_k1<PerSample<bf16_t>, ...> is step_kernel_k1<bf16_t, ...> with the row chosen by the workgroup's sample.
@@ -73,20 +69,6 @@ __device__ __forceinline__ const skr_step_row* row_at(const RowRef& r, uint32_t 
   } else {
     return row_of(r);
   }
-}
-
-// Rolling form: the row of chunk c's sample, or nullptr for an inactive sample (index entry < 0, tested before row_offset is added).
-// sample_of keeps its branch here (nothing stands in front of it that the division could be hoisted over, and power-of-two samples
-// then never divide); the sample id goes through readfirstlane so that the index entry and the row are scalar loads.
-__device__ __forceinline__ const skr_step_row* rolling_row(const RowRef& r, uint32_t c, int32_t bps_shift, uint32_t& smp, uint32_t& within) {
-  sample_of(c, bps_shift, smp, within);
-  smp = __builtin_amdgcn_readfirstlane(smp);
-  const int32_t at = r.index[smp];
-  return at < 0 ? nullptr : r.rows + (at + r.row_offset);
-}
-// an operand is present unless both of its coefficients are exactly zero (either sign): decided on the row's doubles, in SGPRs
-__device__ __forceinline__ bool row_has(const skr_step_row* row, int j) {
-  return ((__builtin_bit_cast(uint64_t, row->coef0[j]) | __builtin_bit_cast(uint64_t, row->coef1[j])) << 1) != 0;
 }
 
 // Rolling form: one operand's terms, added in two halves of four elements.  In this form every operand is summed in a block of its
@@ -397,8 +379,7 @@ static bool one_trip_ok(int64_t numel, int64_t sample_numel, bool noise, RowForm
   if (sample_numel % CHUNK != 0) return false;
   const int64_t bps = sample_numel / CHUNK;
   if (bps > 0x3fffffffll) return false;
-  if ((bps & (bps - 1)) == 0) { while ((1ll << *bps_shift) < bps) ++*bps_shift; }
-  else *bps_shift = -(int)bps;  // any chunk count per sample: the kernel divides
+  *bps_shift = bps_shift_of(bps);
   return true;
 }
 // fp32 launches use the tile layout; with the tile switch off they are left to the other kernels, which table launches do not have

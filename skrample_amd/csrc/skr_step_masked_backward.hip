@@ -26,7 +26,7 @@ struct MaskedBwdArgs {
   const void* g;
   const void* mask;
   int32_t xmap_lr;
-  int32_t bps_shift;     // chunks per sample, as chunk_sample takes them
+  int32_t bps_shift;     // chunks per sample, as sample_of takes them
   uint32_t mask_numel;   // elements of one sample's mask (a multiple of 8, below 2^31)
   uint32_t mask_stride;  // elements between the masks of two samples: mask_numel or 0
   int32_t n;             // gradients written (<= KMAX)
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(BLOCK) void masked_bwd_k1(const MaskedBwdArgs<KMAX>
   Raw<T> rg = load_raw<T, TILE>(p.g, v);
   // the lane-vector's mask elements, looked up as masked_kernel_v1 does: per group of 4 under the tile layout, never across a wrap
   uint32_t smp, within;
-  chunk_sample(c, p.bps_shift, smp, within);
+  sample_of(c, p.bps_shift, smp, within);
   const uint32_t vs = within * BLOCK + threadIdx.x;  // lane-vector within the sample (sample_numel < 2^31)
   const uint32_t m0 = (4u * (uint32_t)group0<TILE>((int64_t)vs)) % p.mask_numel;
   uint32_t m1 = m0 + 4u;
@@ -147,10 +147,8 @@ extern "C" int skr_step_masked_backward_launch(const skr_step_grad_plan* plan, c
   const bool one_dtype = (p.n_group_a == p.n_grads || p.dtype_b == t) && p.g0_dtype == t && mk.dtype == t && t != SKR_F64;
   if (g_tune.one_trip && !p.acc_f64 && one_dtype && numel % CHUNK == 0 && numel / CHUNK <= 0x7fffffffll && sample_numel % CHUNK == 0 &&
       sample_numel < (1ll << 31) && mk.mask_numel % 8 == 0) {
-    const int64_t chunks = numel / CHUNK, bps = sample_numel / CHUNK;
-    int bps_shift = 0;
-    if ((bps & (bps - 1)) == 0) { while ((1ll << bps_shift) < bps) ++bps_shift; }
-    else bps_shift = -(int)bps;  // any chunk count per sample: the kernel divides
+    const int64_t chunks = numel / CHUNK;
+    const int bps_shift = bps_shift_of(sample_numel / CHUNK);
     with_step_type<false>(t, [&](auto tt) {
       with_masked_bwd_slots(p.n_grads, [&](auto kmax) { launch_masked_bwd_k1<typename decltype(tt)::type, decltype(kmax)::value>(p, g, mk, grads, chunks, bps_shift, s); });
     });

@@ -12,7 +12,7 @@ whatever else is resident, and leaves when its own run is over -- the slot is fr
     x = batch.take(slot)
 
 In-painting requests (`SkrampleWrapperScheduler.set_inpaint`) join a batch built with the shape of one sample's mask; plain requests
-share it, and a tick is still one launch (`skr_step_launch_masked_rolling`, csrc/skr_step_masked_rolling.hip):
+share it, and a tick is still one launch (`skr_step_launch_masked_rolling`, csrc/skr_step_masked.hip):
 
     batch = RollingBatch(make_wrapper, example, capacity=B, inpaint_mask_shape=(1, H, W))
     batch.admit(slot, latents, wrapper, steps, seed=None, inpaint=(mask, original_samples, noise))   # one sample each

@@ -1,11 +1,11 @@
 """The masked rolling step kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_masked_rolling` runs `masked_rolling_kernel_v1<T, K, NOISE>` (csrc/skr_step_masked_rolling.hip).  Its contract is
+`skr_step_launch_masked_rolling` runs `masked_kernel_v1<T, K, NOISE, RowForm::Rolling>` (csrc/skr_step_masked.hip).  Its contract is
 visible in the instruction stream, as that of the `Rolling<>` step kernels is (tests/test_rolling_isa.py): a workgroup of an inactive
 sample ends before its first vector-memory instruction, every decision taken from the sample's row is a scalar branch with exec never
 masked, operands are global loads, and nothing spills.  The VGPR counts are printed beside those of the per-sample twins
-`masked_rows_kernel_v1<T, K, NOISE, true>` (csrc/skr_step_masked_rows.hip) for DESIGN.md section 4.6; no occupancy bracket is
-asserted."""
+`masked_kernel_v1<T, K, NOISE, RowForm::PerSample>`, the same template compiled once, for DESIGN.md section 4.6; no occupancy bracket
+is asserted.  The census counts every one-trip instantiation of the template: 3 dtypes x 16 operand counts x noise x 4 row forms."""
 
 import os
 import re
@@ -21,8 +21,10 @@ CSRC = os.path.join(ROOT, "skrample_amd", "csrc")
 HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
-SYMBOL = re.compile(r"masked_rolling_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")
-TWIN = re.compile(r"masked_rows_kernel_v1I(\w+?)Li(\d+)ELb([01])ELb1EE")
+# masked_kernel_v1<T, K, NOISE, RowForm F>; RowForm (skr_step_common.h): Kernarg 0, WholeBatch 1, PerSample 2, Rolling 3
+ONE_TRIP = re.compile(r"masked_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([0-3])EE")
+SYMBOL = re.compile(r"masked_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE3EE")
+TWIN = re.compile(r"masked_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE2EE")
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 
 
@@ -49,25 +51,31 @@ def compiled(name: str, work: str) -> dict:
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
+def one_trip(tmp_path_factory):
+    "every masked_kernel_v1 instantiation of the one translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = compiled("skr_step_masked_rolling.hip", str(tmp_path_factory.mktemp("isa") / "rolling"))
-    return {k: v for k, v in found.items() if SYMBOL.search(k)}
+    found = compiled("skr_step_masked.hip", str(tmp_path_factory.mktemp("isa") / "masked"))
+    return {k: v for k, v in found.items() if ONE_TRIP.search(k)}
 
 
 @pytest.fixture(scope="module")
-def twins(tmp_path_factory):
-    if HIPCC is None:
-        pytest.skip("no hipcc on this box")
-    found = compiled("skr_step_masked_rows.hip", str(tmp_path_factory.mktemp("isa_rows") / "rows"))
-    return {TWIN.search(k).groups(): v for k, v in found.items() if TWIN.search(k)}
+def kernels(one_trip):
+    return {k: v for k, v in one_trip.items() if SYMBOL.search(k)}
 
 
-def test_all_96_instantiations_exist(kernels):
+@pytest.fixture(scope="module")
+def twins(one_trip):
+    return {TWIN.search(k).groups(): v for k, v in one_trip.items() if TWIN.search(k)}
+
+
+def test_all_96_instantiations_exist(kernels, one_trip):
     have = {SYMBOL.search(k).groups() for k in kernels}
     want = {(t, str(n), nz) for t in TYPES.values() for n in range(1, 17) for nz in "01"}
     assert have == want and len(kernels) == 96, (sorted(want - have), sorted(have - want))
+    have = {ONE_TRIP.search(k).groups() for k in one_trip}
+    want = {(t, str(n), nz, f) for t in TYPES.values() for n in range(1, 17) for nz in "01" for f in "0123"}
+    assert have == want and len(one_trip) == 384, (sorted(want - have), sorted(have - want))
 
 
 def test_inactive_exit_precedes_the_first_vector_memory_instruction(kernels):
@@ -105,7 +113,7 @@ def test_no_scratch(kernels):
 def test_vgpr_table_against_the_per_sample_twins(kernels, twins):
     "printed for DESIGN.md section 4.6 (run with -s); every kernel has a twin, and nothing else is asserted: no occupancy bracket"
     names = {v: k for k, v in TYPES.items()}
-    print("\nVGPRs (waves per SIMD): masked_rolling_kernel_v1 vs masked_rows_kernel_v1<..., PER_SAMPLE = true>")
+    print("\nVGPRs (waves per SIMD): masked_kernel_v1<..., Rolling> vs masked_kernel_v1<..., PerSample>")
     short = []
     for key in sorted((SYMBOL.search(k).groups() for k in kernels), key=lambda g: (g[0], g[2], int(g[1]))):
         symbol = next(k for k in kernels if SYMBOL.search(k).groups() == key)

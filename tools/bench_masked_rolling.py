@@ -11,7 +11,7 @@ Forms, each in a child process of its own (a fresh HIP context and allocator per
                             kernels: every slot's alpha and sigma of its NEXT schedule point in one [2, B, 1, 1, 1] device tensor uploaded
                             per tick, latents.copy_(mask * latents + (1 - mask) * (alpha * original + sigma * noise)), 1 - mask precomputed
   k  kernels alone          skr_step_launch_masked_rolling back to back on full rows of the tick's operand count, beside
-                            skr_step_launch_masked_indexed_per_sample (masked_rows_kernel_v1<..., true>) on the same rows: event clock
+                            skr_step_launch_masked_indexed_per_sample (masked_kernel_v1<..., PerSample>) on the same rows: event clock
                             per launch and the fraction of 8 TB/s its algorithmic bytes come to (operands + quarter-size mask + one store)
 Every slot is admitted once with a run long enough for the warm-up and all repeats, so no slot finishes inside a timed region.  Per
 repeat, `ticks` ticks are timed with HIP events (first enqueue to last kernel) and with the wall clock (first call to the end of a device
@@ -197,7 +197,7 @@ def main() -> int:
         (eam, _, _), (ebm, _, _) = summary(seen["a"]["event_us"]), summary(seen["b"]["event_us"])
         lines.append(f"  event-clock medians: b / a = {ebm / eam:.2f}")
         k = seen["k"]
-        for name, kernel in (("rolling", "masked_rolling_kernel_v1"), ("rows", "masked_rows_kernel_v1 per sample")):
+        for name, kernel in (("rolling", "masked_kernel_v1<..., Rolling>"), ("rows", "masked_kernel_v1<..., PerSample>")):
             m, lo, hi = summary(k[name + "_us"])
             lines.append(f"  k  {kernel:32s} {k['operands']} operands   event clock {m:8.2f} ({lo:8.2f} - {hi:8.2f}) per launch   {k['bytes'] / 1e6:6.1f} MB -> {k['bytes'] / (m * 1e-6) / PEAK * 100:5.1f} % of 8 TB/s")
     text = "\n".join(lines) + "\n"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two source trees, kernel symbol by kernel symbol (no GPU needed).
 
-    python tools/isa_compare.py OLD_TREE NEW_TREE [--files NAME.hip ...] [--jobs N] [--work DIR] [--renames FILE]
+    python tools/isa_compare.py OLD_TREE NEW_TREE [--files NAME.hip ...] [--jobs N] [--work DIR] [--renames FILE] [--pooled]
 
 Compiles the named files of skrample_amd/csrc (default: the step files skr_step.hip, skr_step_fast.hip, skr_step_backward.hip and
 skr_tape.hip) of each tree with the library's own flags, the tree's PER_FILE_FLAGS included (`--save-temps -c`), splits the device assembly per kernel the way tests/test_per_sample_isa.py and tests/test_rolling_isa.py do,
@@ -11,7 +11,9 @@ diff per differing symbol.
 A host-side refactor must end in `0 added, 0 removed, 0 differing` for every file.  Exit status 1 when anything differs.
 With --work DIR the assembly is kept there and reused while it is newer than the tree's sources.
 With --renames FILE (lines of `OLD_SYMBOL NEW_SYMBOL`: a kernel template that gained a parameter) an old kernel is compared under its new
-name; the map is printed ahead of the report."""
+name; the map is printed ahead of the report (its size alone when it is long).
+With --pooled (kernels that moved between files, files merged or split) the kernels of all named files of a tree are pooled and the two
+pools compared; a named file may then be missing from either tree, and a symbol defined twice in one pool is an error."""
 
 from __future__ import annotations
 
@@ -78,21 +80,37 @@ def main() -> int:
     ap.add_argument("--jobs", type=int, default=8, help="compilations at a time (at most 16)")
     ap.add_argument("--work", default=None, help="directory that keeps the assembly between runs")
     ap.add_argument("--renames", default=None, metavar="FILE", help="lines of `OLD_SYMBOL NEW_SYMBOL`: old kernels compared under their new names")
+    ap.add_argument("--pooled", action="store_true", help="compare the union of the kernels of the named files of each tree (a file may be missing from one)")
     a = ap.parse_args()
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     work = a.work or tempfile.mkdtemp(prefix="isa_compare_")
     trees = {"old": os.path.abspath(a.old), "new": os.path.abspath(a.new)}
     for side in trees:
         os.makedirs(os.path.join(work, side), exist_ok=True)
-    jobs = [(side, name) for name in a.files for side in trees]
+    jobs = [(side, name) for name in a.files for side in trees if not a.pooled or os.path.isfile(os.path.join(trees[side], "skrample_amd", "csrc", name))]
     with ThreadPoolExecutor(max_workers=max(1, min(16, a.jobs))) as pool:
         texts = dict(zip(jobs, pool.map(lambda j: assembly(trees[j[0]], j[1], os.path.join(work, j[0]), hipcc), jobs)))
     renames = dict(line.split() for line in open(a.renames) if line.strip()) if a.renames else {}
-    for was, now in renames.items():
-        print(f"renamed: {was} -> {now}")
+    if len(renames) > 16:
+        print(f"renamed: {len(renames)} symbols ({a.renames})")
+    else:
+        for was, now in renames.items():
+            print(f"renamed: {was} -> {now}")
+
+    def pooled(side: str) -> dict:
+        "the kernels of every named file that the tree has"
+        out, census = {}, []
+        for name in a.files:
+            found = kernels(texts[side, name]) if (side, name) in texts else None
+            census.append(f"{name} absent" if found is None else f"{name} {len(found)}")
+            assert not set(found or ()) & set(out), (side, name, sorted(set(found) & set(out))[:3])
+            out.update(found or {})
+        print(f"{side}: " + ", ".join(census))
+        return out
+
     bad = 0
-    for name in a.files:
-        old, new = kernels(texts["old", name]), kernels(texts["new", name])
+    for name in ["pooled"] if a.pooled else a.files:
+        old, new = (pooled("old"), pooled("new")) if a.pooled else (kernels(texts["old", name]), kernels(texts["new", name]))
         old = {renames.get(k, k): [l.replace(k, renames[k]) for l in v] if k in renames else v for k, v in old.items()}
         added, removed = sorted(set(new) - set(old)), sorted(set(old) - set(new))
         differing = [k for k in sorted(set(old) & set(new)) if old[k] != new[k]]

@@ -1,6 +1,6 @@
 // Shared device helpers of the fused step kernels (skr_step.hip: general + grid-stride kernels; skr_step_fast.hip:
-// one-trip compile-time kernels; skr_step_masked.hip and the two backward files): lane ownership, loads / stores, the device-resident
-// row and chunk -> sample helpers, rounded conversion, tuning switches.
+// one-trip compile-time kernels; skr_step_masked.hip; skr_step_backward.hip: both backward launches): lane ownership, loads / stores,
+// the device-resident row and chunk -> sample helpers, rounded conversion, tuning switches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -67,6 +67,10 @@ static inline bool step_output_ok(int32_t out_dtype, int32_t dtype_a, bool acc_f
 enum class RowForm : int32_t { Kernarg, WholeBatch, PerSample, Rolling };
 constexpr bool has_table(RowForm f) { return f != RowForm::Kernarg; }
 constexpr bool per_sample_rows(RowForm f) { return f == RowForm::PerSample || f == RowForm::Rolling; }
+// the scalars are fetched from a row BEHIND the operand loads (a rolling workgroup asks its row in front of them: skr_step_fast.hip)
+constexpr bool row_behind_loads(RowForm f) { return f == RowForm::WholeBatch || f == RowForm::PerSample; }
+// a tensor dtype of the C ABI (SKR_NONE is none)
+static inline bool tensor_dtype(int32_t d) { return d == SKR_BF16 || d == SKR_F16 || d == SKR_F32 || d == SKR_F64; }
 
 template <typename Acc>
 struct StepArgs {
@@ -99,7 +103,7 @@ struct RowRef {
   const int32_t* index;
   int32_t row_offset;
 };
-__device__ __forceinline__ const skr_step_row* row_of(const RowRef& r) {  // (only called by the TAB instantiations: rows != nullptr)
+__device__ __forceinline__ const skr_step_row* row_of(const RowRef& r) {  // (only called by the whole-batch instantiations: rows != nullptr)
   return r.rows + ((r.index != nullptr ? r.index[0] : 0) + r.row_offset);
 }
 
@@ -312,7 +316,7 @@ __device__ __forceinline__ void store_scalar(void* base, int64_t i, Acc v) {
   else reinterpret_cast<T*>(base)[i] = (T)v;
 }
 
-// ---- per-element load with a run-time dtype (the general kernels of skr_step_masked.hip and the two backward files) -----------------
+// ---- per-element load with a run-time dtype (the general kernels of skr_step_masked.hip and skr_step_backward.hip) ------------------
 // (the forward's store stays apart from the backwards': one shared body changes the instructions of one kernel or the other)
 // WITH_F64 = false: no fp64 tensor reaches the kernel (every other code reads as fp32)
 template <typename Acc, bool WITH_F64>
@@ -335,7 +339,7 @@ __device__ __forceinline__ Acc load_elem(const void* base, int64_t i, int dt) {
 
 // one rounding from Acc; the same conversions as store8 (fp32 -> 16-bit: RNE of the fp32 value, pinned so that no fused
 // multiply-add-and-convert rounds the exact sum instead).
-// The per-element store of the two backward general kernels (skr_step_backward.hip, skr_step_masked_backward.hip); store_elem of
+// The per-element store of the two backward general kernels (skr_step_backward.hip); store_elem of
 // skr_step_masked.hip is the same function, kept apart: see there.
 template <typename Acc> __device__ __forceinline__ void store_any(void* base, int64_t i, int dt, Acc v) {
   switch (dt) {
@@ -457,6 +461,15 @@ extern thread_local int g_last_hip_error;
 int finish_launch();
 
 // ---- host side: run-time values to template arguments, kernarg packing -------------------------------------------------------------
+// f(std::integral_constant<RowForm, F>{}) for the F that equals form
+template <typename Fn>
+static inline void with_row_form(RowForm form, Fn&& f) {
+  if (form == RowForm::Kernarg) f(std::integral_constant<RowForm, RowForm::Kernarg>{});
+  else if (form == RowForm::WholeBatch) f(std::integral_constant<RowForm, RowForm::WholeBatch>{});
+  else if (form == RowForm::PerSample) f(std::integral_constant<RowForm, RowForm::PerSample>{});
+  else f(std::integral_constant<RowForm, RowForm::Rolling>{});
+}
+
 // calls f(std::integral_constant<int, N>{}) for the N of LO..HI that equals n, and nothing for an n outside
 template <int LO, int HI, typename F>
 static inline void with_count(int n, F&& f) {

@@ -34,25 +34,17 @@ struct OneTripArgs {
 // (chunk -> sample: sample_of; the rolling form's row and its present operands: rolling_row / row_has -- all three in skr_step_common.h,
 //  shared with the masked step kernels of skr_step_masked.hip)
 
-// Per-sample rows (skr_step_launch_indexed_per_sample) are a compile-time form of the TAB instantiations, selected by wrapping the
-// element type: step_kernel_k1<PerSample<bf16_t>, ...> is step_kernel_k1<bf16_t, ...> with the row chosen by the workgroup's sample.
-// (A tag on an existing parameter, not a new one: the kernels that existed before keep their symbols and their instruction streams,
-// which tests/test_per_sample_isa.py and the headline number rely on.)
-template <typename T> struct PerSample {};
-template <typename T> struct RowsBy { using elem = T; static constexpr bool per_sample = false, rolling = false; };
-template <typename T> struct RowsBy<PerSample<T>> { using elem = T; static constexpr bool per_sample = true, rolling = false; };
-// Rolling batches (skr_step_launch_rolling): a third form, Rolling<T>.  Per-sample rows in which a workgroup first asks its own sample's
+// The three kernels take the launch's RowForm (skr_step_common.h) as a template argument F.  WholeBatch and PerSample fetch their
+// scalars from a row behind the loads (row_behind_loads(F)); per-sample rows (skr_step_launch_indexed_per_sample) are the whole-batch
+// form with the row chosen by the workgroup's sample (tests/test_per_sample_isa.py compares the two).
+// Rolling batches (skr_step_launch_rolling): RowForm::Rolling.  Per-sample rows in which a workgroup first asks its own sample's
 // index entry and row what to touch: a negative entry ends the workgroup before its first vector-memory instruction, and an operand
 // whose two coefficients are zero in the row is neither loaded nor accumulated (the history a sample in its multistep ramp-up does not
 // have yet -- its bytes are the slot's previous occupant's, possibly NaN, and fma(0, NaN, s) is NaN).  The row is uniform over the
 // workgroup, so every such decision is a scalar branch.  The row fetch therefore stands IN FRONT of the loads here, the order the
 // other forms avoid (see step_kernel_k1): two dependent scalar round trips per wave, measured in tools/bench_rolling.py.
-// (These instantiations carry TAB = false in their symbols -- a row is not optional for them, the tag alone selects it -- which keeps
-// the one-to-one census of TAB symbols and per-sample forms in tests/test_per_sample_isa.py what it was.)
-template <typename T> struct Rolling {};
-template <typename T> struct RowsBy<Rolling<T>> { using elem = T; static constexpr bool per_sample = true, rolling = true; };
 
-// The device-resident row of chunk c (TAB instantiations).  PER_SAMPLE: index holds one entry per sample and a workgroup reads its
+// The device-resident row of chunk c (WholeBatch and PerSample instantiations).  PER_SAMPLE: index holds one entry per sample and a workgroup reads its
 // own sample's -- launches of whole chunks per sample only, so the sample, and with it the row, zeta and the draw / no-draw branch,
 // is uniform over the workgroup.  The sample id goes through readfirstlane (the dividing form of sample_of runs on the vector ALU):
 // the index fetch and the row fetch stay scalar loads, two dependent ones as in the whole-batch form.  No bounds check, no clamp.
@@ -125,12 +117,11 @@ __device__ __forceinline__ void add_operand2(Raw<T>& r, float c0, float c1, floa
 constexpr int one_trip_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 16 ? 16 : 20))); }
 constexpr int ONE_TRIP_MAX_K = 20;
 
-template <typename TR, int K, bool NOISE, bool TILE, bool PACE, bool TAB>  // TR: the element type, PerSample<element type> (TAB only) or Rolling<element type>
+template <typename T, int K, bool NOISE, bool TILE, bool PACE, RowForm F>
 __global__ __launch_bounds__(BLOCK) void step_kernel_k1(const OneTripArgs<one_trip_kmax(K)> a) {
-  using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
-  if constexpr (RowsBy<TR>::rolling) {
+  if constexpr (F == RowForm::Rolling) {
     uint32_t smp, within;
     const skr_step_row* row = rolling_row(a.tab, c, a.bps_shift, smp, within);
     if (row == nullptr) return;  // inactive sample: nothing read, nothing written
@@ -175,7 +166,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k1(const OneTripArgs<one_tr
   }
   Raw<T> raw[K];
   float z[VEC];
-  // The step's scalars come from the kernarg or, in the TAB instantiation (indexed launches), from the device-resident row
+  // The step's scalars come from the kernarg or, in the WholeBatch and PerSample instantiations (indexed launches), from the device-resident row
   // (two dependent scalar loads).  They are fetched AFTER the first global loads have been issued, and the choice is a
   // template parameter: as a run-time branch in front it put three scalar round trips before the first load of every wave
   // (+0.3 us on the headline launch), and the compiler sank the loads behind the branch wherever it stood.
@@ -185,8 +176,8 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k1(const OneTripArgs<one_tr
   __builtin_amdgcn_sched_barrier(0);                                         \
   zeta0 = a.zeta0; stream0 = a.stream0;                                      \
   _Pragma("unroll") for (int j = 0; j < K; ++j) cf[j] = a.c0[j];             \
-  if constexpr (TAB) {                                                       \
-    const skr_step_row* row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift); \
+  if constexpr (row_behind_loads(F)) {                                       \
+    const skr_step_row* row = row_at<per_sample_rows(F)>(a.tab, c, a.bps_shift); \
     _Pragma("unroll") for (int j = 0; j < K; ++j) cf[j] = (float)row->coef0[j]; \
     zeta0 = (float)row->zeta0;                                               \
     stream0 = row->stream0;                                                  \
@@ -291,16 +282,15 @@ struct RkOneTripArgs {
 
 // NOISE: the step's last stage of a stochastic tableau step adds zeta1 * N(stream1) to out1 (the derivative out0 is never noisy)
 // BLK: threads per workgroup (256, or 128 = 1024-element chunks: tools/tune/tune_r3.hip measured the 5-operand stage 1-4 % faster so)
-template <typename TR, int K, bool TILE, bool NOISE, bool TAB, int BLK>  // TR: as for step_kernel_k1
+template <typename T, int K, bool TILE, bool NOISE, RowForm F, int BLK>
 __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <= 4 ? 4 : 8)> a) {
-  using T = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLK + threadIdx.x;
   // Rolling form: the inactive exit, and the operands behind the conversion pair that the row lacks are neither loaded nor summed (the
   // contract of skr_step_launch_rolling; a Runge-Kutta step has no ramp-up, so the samplers' own rows lack none)
   [[maybe_unused]] const skr_step_row* rolling = nullptr;
   [[maybe_unused]] bool on[K];
-  if constexpr (RowsBy<TR>::rolling) {
+  if constexpr (F == RowForm::Rolling) {
     uint32_t smp, within;
     rolling = rolling_row(a.tab, c, a.bps_shift, smp, within);
     if (rolling == nullptr) return;
@@ -308,7 +298,7 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
     for (int j = 0; j < K; ++j) on[j] = j < 2 || row_has(rolling, j);
   }
   Raw<T> raw[K];
-  if constexpr (RowsBy<TR>::rolling) {
+  if constexpr (F == RowForm::Rolling) {
 #pragma unroll
     for (int j = 0; j < K; ++j) if (on[j]) raw[j] = load_raw<T, TILE>(a.in[j], v);
   } else {
@@ -320,9 +310,9 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
   uint64_t stream1 = a.stream1;
 #pragma unroll
   for (int j = 0; j < K; ++j) cf[j] = a.c1[j];
-  if constexpr (TAB || RowsBy<TR>::rolling) {
+  if constexpr (has_table(F)) {
     const skr_step_row* row;
-    if constexpr (RowsBy<TR>::rolling) row = rolling; else row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift);
+    if constexpr (F == RowForm::Rolling) row = rolling; else row = row_at<per_sample_rows(F)>(a.tab, c, a.bps_shift);
 #pragma unroll
     for (int j = 0; j < K; ++j) cf[j] = (float)row->coef1[j];
 #pragma unroll
@@ -354,7 +344,7 @@ __global__ __launch_bounds__(BLK) void step_kernel_rk1(const RkOneTripArgs<(K <=
   }
 #pragma unroll
   for (int j = 2; j < K; ++j) {
-    if constexpr (RowsBy<TR>::rolling) { if (!on[j]) continue; }
+    if constexpr (F == RowForm::Rolling) { if (!on[j]) continue; }
     float w[VEC];
     widen<T, float>(raw[j], w);
     const float cj = cf[j];
@@ -387,27 +377,27 @@ template <typename T> static bool tile_switched_off(RowForm form) { return sizeo
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // The one place that maps a launch form to a kernel instantiation: calls
-// f(type_tag<TR>{}, bool_c<PACE>{}, bool_c<TAB>{}) with the template arguments of the kernel this form runs.
-//   form        TR            PACE                                          TAB
-//   Kernarg     T             g_tune.pace where PACED, else false           false
-//   WholeBatch  T             PACED                                         true
-//   PerSample   PerSample<T>  PACED                                         true
-//   Rolling     Rolling<T>    false                                         false
+// f(type_tag<T>{}, bool_c<PACE>{}, std::integral_constant<RowForm, F>{}) with the template arguments of the kernel this form runs.
+//   form        PACE
+//   Kernarg     g_tune.pace where PACED, else false
+//   WholeBatch  PACED
+//   PerSample   PACED
+//   Rolling     false
 // PACED: this operand count has a paced instantiation (1-8-operand k1, noisy 2-11-operand k2; step_kernel_rk1 has no such parameter).
 // TABLE: it has table instantiations (its operands fit a device-resident row); false is returned for a table form without one.
-template <typename T, bool PACED, bool TABLE, typename F>
-static bool with_form(RowForm form, F&& f) {
-  if (form == RowForm::Kernarg) {
-    if (PACED && g_tune.pace) f(type_tag<T>{}, bool_c<PACED>{}, bool_c<false>{});
-    else f(type_tag<T>{}, bool_c<false>{}, bool_c<false>{});
-    return true;
-  }
-  if constexpr (TABLE) {
-    if (form == RowForm::WholeBatch) f(type_tag<T>{}, bool_c<PACED>{}, bool_c<true>{});
-    else if (form == RowForm::PerSample) f(type_tag<PerSample<T>>{}, bool_c<PACED>{}, bool_c<true>{});
-    else f(type_tag<Rolling<T>>{}, bool_c<false>{}, bool_c<false>{});
-  }
-  return TABLE;
+template <typename T, bool PACED, bool TABLE, typename Fn>
+static bool with_form(RowForm form, Fn&& f) {
+  if (!TABLE && has_table(form)) return false;
+  with_row_form(form, [&](auto fm) {
+    constexpr RowForm F = decltype(fm)::value;
+    if constexpr (F == RowForm::Kernarg) {
+      if (PACED && g_tune.pace) f(type_tag<T>{}, bool_c<PACED>{}, fm);
+      else f(type_tag<T>{}, bool_c<false>{}, fm);
+    } else if constexpr (TABLE) {
+      f(type_tag<T>{}, bool_c<PACED && F != RowForm::Rolling>{}, fm);
+    }
+  });
+  return true;
 }
 
 template <typename T, bool NOISE>
@@ -423,8 +413,8 @@ static int launch_k1(const StepArgs<float>& args, int bps_shift, hipStream_t str
     fa.bps_shift = bps_shift; fa.xmap_lr = xmap_lr_for(chunks);
     fa.tab = RowRef{args.rows, args.index, args.row_offset};
     // more than 8 operands: one unpaced instantiation each (plus the table forms while the operands fit a device-resident row)
-    launched = with_form<T, (N <= 8), (N <= SKR_ROW_TERMS)>(args.form, [&](auto tr, auto pace, auto tab) {
-      hipLaunchKernelGGL((step_kernel_k1<typename decltype(tr)::type, N, NOISE, TILE, decltype(pace)::value, decltype(tab)::value>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa);
+    launched = with_form<T, (N <= 8), (N <= SKR_ROW_TERMS)>(args.form, [&](auto tt, auto pace, auto fm) {
+      hipLaunchKernelGGL((step_kernel_k1<typename decltype(tt)::type, N, NOISE, TILE, decltype(pace)::value, decltype(fm)::value>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, fa);
     });
   });
   return launched ? finish_launch() : SKR_ERR_UNSUPPORTED;
@@ -458,8 +448,8 @@ static int launch_rk1(const StepArgs<float>& args, unsigned chunks, int bps_shif
     ra.out0 = args.out0; ra.out1 = args.out1; ra.chain = args.chain;
     for (int i = 0; i < 4; ++i) ra.ck[i] = (float)args.ck[i];
     ra.conv_to = args.conv_to; ra.conv_from = args.conv_from; ra.xmap_lr = xmap_lr_for(chunks); ra.tab = RowRef{args.rows, args.index, args.row_offset};
-    with_form<T, false, true>(args.form, [&](auto tr, auto, auto tab) {
-      hipLaunchKernelGGL((step_kernel_rk1<typename decltype(tr)::type, N, TILE, NOISE, decltype(tab)::value, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra);
+    with_form<T, false, true>(args.form, [&](auto tt, auto, auto fm) {
+      hipLaunchKernelGGL((step_kernel_rk1<typename decltype(tt)::type, N, TILE, NOISE, decltype(fm)::value, BLK>), dim3(chunks), dim3(BLK), 0, stream, ra);
     });
   });
   return finish_launch();
@@ -510,12 +500,11 @@ struct TwoOutArgs {
 constexpr int NT_FROM_OPERANDS = 9;
 constexpr int two_out_nmax(int n) { return n <= 4 ? 4 : (n <= 8 ? 8 : (n <= 12 ? 12 : (n <= 16 ? 16 : (n <= 20 ? 20 : 24)))); }
 
-template <typename TR, int NA, int NB, bool NOISE, bool PACE, bool TAB, bool NT = false>  // TR: as for step_kernel_k1
+template <typename TA, int NA, int NB, bool NOISE, bool PACE, RowForm F, bool NT = false>
 __global__ __launch_bounds__(BLOCK) void step_kernel_k2(const TwoOutArgs<two_out_nmax(NA + NB)> a) {
-  using TA = typename RowsBy<TR>::elem;
   const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
   const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
-  if constexpr (RowsBy<TR>::rolling) {  // see step_kernel_k1: inactive exit, absent operands skipped, present ones in slot order
+  if constexpr (F == RowForm::Rolling) {  // see step_kernel_k1: inactive exit, absent operands skipped, present ones in slot order
     uint32_t smp, within;
     const skr_step_row* row = rolling_row(a.tab, c, a.bps_shift, smp, within);
     if (row == nullptr) return;
@@ -572,8 +561,8 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_k2(const TwoOutArgs<two_out
   __builtin_amdgcn_sched_barrier(0);                                                       \
   chain = a.chain; zeta0 = a.zeta0; zeta1 = a.zeta1; stream0 = a.stream0; stream1 = a.stream1; \
   _Pragma("unroll") for (int j = 0; j < NA + NB; ++j) { cf0[j] = a.c0[j]; cf1[j] = a.c1[j]; } \
-  if constexpr (TAB) {                                                                     \
-    const skr_step_row* row = row_at<RowsBy<TR>::per_sample>(a.tab, c, a.bps_shift);       \
+  if constexpr (row_behind_loads(F)) {                                                     \
+    const skr_step_row* row = row_at<per_sample_rows(F)>(a.tab, c, a.bps_shift);           \
     _Pragma("unroll") for (int j = 0; j < NA + NB; ++j) { cf0[j] = (float)row->coef0[j]; cf1[j] = (float)row->coef1[j]; } \
     chain = (float)row->chain; zeta0 = (float)row->zeta0; zeta1 = (float)row->zeta1;       \
     stream0 = row->stream0; stream1 = row->stream1;                                        \
@@ -678,8 +667,8 @@ static int launch_k2(const StepArgs<float>& args, int bps_shift, hipStream_t str
   ta.stream0 = args.stream0; ta.stream1 = args.stream1;
   ta.chain = args.chain; ta.zeta0 = args.zeta0; ta.zeta1 = args.zeta1;
   ta.tab = RowRef{args.rows, args.index, args.row_offset};
-  const bool launched = with_form<TA, PACED, TABLE && !NT>(args.form, [&](auto tr, auto pace, auto tab) {
-    hipLaunchKernelGGL((step_kernel_k2<typename decltype(tr)::type, NA, NB, NOISE, decltype(pace)::value, decltype(tab)::value, NT>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
+  const bool launched = with_form<TA, PACED, TABLE && !NT>(args.form, [&](auto tt, auto pace, auto fm) {
+    hipLaunchKernelGGL((step_kernel_k2<typename decltype(tt)::type, NA, NB, NOISE, decltype(pace)::value, decltype(fm)::value, NT>), dim3((unsigned)chunks), dim3(BLOCK), 0, stream, ta);
   });
   return launched ? finish_launch() : SKR_ERR_UNSUPPORTED;
 }

@@ -1,4 +1,4 @@
-// What the masked step (skr_step_masked.hip) and its backward (skr_step_masked_backward.hip) share: the load of a lane's mask values.
+// What the masked step (skr_step_masked.hip) and its backward (masked_bwd_k1 of skr_step_backward.hip) share: the load of a lane's mask values.
 // (The index arithmetic in front of it is stated in each of the two kernel templates.  As a shared function, however little of it the function
 //  holds, it is simplified on its own before it is inlined, apart from the Philox block numbers that share its terms in the forward
 //  kernel, and some forward instantiations then come out with other instructions or registers.)

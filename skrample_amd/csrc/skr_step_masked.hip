@@ -16,7 +16,7 @@
 //   Kernarg     skr_step_launch_masked                      coef0 / coef1 / zeta0 / stream0 from the plan, narrowed on the host
 //   WholeBatch  skr_step_launch_masked_indexed              from rows[index[0] + row_offset], read by the kernel behind its loads, so that a
 //   PerSample   skr_step_launch_masked_indexed_per_sample   captured in-painting loop serves any schedule; per sample: rows[index[sample] + row_offset]
-//   Rolling     skr_step_launch_masked_rolling              per-sample rows with the three semantics of Rolling<T> (skr_step_fast.hip), for the
+//   Rolling     skr_step_launch_masked_rolling              per-sample rows with the three semantics of step_kernel_k1's Rolling form (skr_step_fast.hip), for the
 //                                                           slots of a rolling.RollingBatch: the row fetch stands IN FRONT of the loads,
 //       inactive sample   a negative index entry (tested before row_offset is added) ends the workgroup before its first vector-memory
 //                         instruction: no operand, mask, seed or row is read, `out` keeps its bytes;
@@ -234,15 +234,6 @@ struct MaskedLaunch {
   int64_t chunks;  // 2048-element chunks of the launch, and
   int bps_shift;   // chunks per sample as the kernels take them (sample_of); both set when one_trip
 };
-
-// f(std::integral_constant<RowForm, F>{}) for the F that equals form
-template <typename Fn>
-static void with_row_form(RowForm form, Fn&& f) {
-  if (form == RowForm::Kernarg) f(std::integral_constant<RowForm, RowForm::Kernarg>{});
-  else if (form == RowForm::WholeBatch) f(std::integral_constant<RowForm, RowForm::WholeBatch>{});
-  else if (form == RowForm::PerSample) f(std::integral_constant<RowForm, RowForm::PerSample>{});
-  else f(std::integral_constant<RowForm, RowForm::Rolling>{});
-}
 
 // the one-trip launch of any form: dtype x noise x form x operand count to the instantiation, and its kernarg
 static void launch_masked_v1(const skr_step_plan& p, const void* const* inputs, void* out, const skr_step_mask& mk, const uint64_t* seeds,

@@ -31,7 +31,7 @@ output or state): the batch binds the roles to whole-batch tensors it rotates it
 caller's last model outputs, a ring of fp32 states (UniPC / SPC).  An admitted request's rows come from a dry run of ITS wrapper on
 one sample (the mechanism of `CapturedLoop.retarget`); each row is placed into the wide structure by role, zeros elsewhere, and
 uploaded into the slot's region of one device table.  Per tick the host publishes `index[b] = base[b] + position[b]`, or -1 for a
-free or finished slot, with one small stream-ordered copy.  The kernels (csrc/skr_step_fast.hip, `Rolling<T>`) skip inactive samples
+free or finished slot, with one small stream-ordered copy.  The kernels (csrc/skr_step_fast.hip, `RowForm::Rolling`) skip inactive samples
 before their first vector-memory instruction, and neither load nor accumulate an operand whose coefficients are zero in the
 sample's row: a sample in its multistep ramp-up has the bits of the narrower launch its lone run makes, whatever the slot's previous
 occupant left in the history rings.

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import pytest
 from conftest import ROOT
 
 
@@ -96,3 +97,24 @@ def test_bench_cli_parses_without_a_gpu():
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--config", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_bench_needles_name_compiled_step_kernels(tmp_path):
+    """bench.py picks the kernels of its live counter pass by a needle in the demangled kernel name (`pmc_kernels`).  Every
+    `step_kernel_*` needle names a kernel skr_step_fast.hip compiles, and the headline's matches include the kernarg form
+    (RowForm 0) that the benchmark launches: a template parameter list that moves under a needle shows here, not as an empty
+    `traffic_by_kernel` entry on the device."""
+    import isa_cases
+
+    if isa_cases.HIPCC is None or isa_cases.CXXFILT is None:
+        pytest.skip("no hipcc or no c++filt on this box")
+    import bench
+
+    workloads = bench._wl()
+    needles = {needle for wl in workloads.values() for needle, _ in wl.pmc_kernels if needle.startswith("step_kernel_")}
+    assert len(needles) >= 5, needles
+    names = list(isa_cases.demangle(isa_cases.kernels_of(isa_cases.compile_asm("skr_step_fast.hip", str(tmp_path / "fast")))).values())
+    for needle in sorted(needles):
+        assert any(needle in name for name in names), needle
+    headline = workloads["headline"].pmc_kernels[0][0]
+    assert any(headline in name and "(skr::RowForm)0>" in name for name in names), headline

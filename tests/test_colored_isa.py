@@ -9,33 +9,16 @@ compiles the file with the library's own flags and checks the three on every pat
 each output type -- so that a compiler version that copies, spills or reorders the register fails here and not on the device."""
 
 import heapq
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
-from conftest import ROOT
+from isa_cases import HIPCC, compile_asm
 
-import __graft_entry__ as G
-
-SRC = os.path.join(ROOT, "skrample_amd", "csrc", "skr_colored.hip")
-HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 KERNELS = {"DF16b": "bf16", "DF16_": "f16", "f": "f32"}  # mangled template argument of colored_inverse128<T>
 WAIT = "s_waitcnt vmcnt(17)"
 VMEM = ("global_", "buffer_", "flat_", "scratch_")  # every instruction vmcnt counts on gfx950 (loads, stores and atomics)
 BRANCH = re.compile(r"s_(c?branch\w*)\s+(\S+)")
 VMCNT = re.compile(r"s_waitcnt\b.*\bvmcnt\((\d+)\)")
-
-
-def compile_asm(src: str, workdir: str) -> str:
-    "the gfx950 assembly of `src`, compiled with the flags build() gives it"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *G.PER_FILE_FLAGS.get(os.path.basename(src), [])]
-    subprocess.run([HIPCC, *flags, "--save-temps", "-c", "-o", os.path.join(workdir, "x.o"), src], check=True, cwd=workdir, capture_output=True)
-    asm = [f for f in os.listdir(workdir) if f.endswith("gfx950.s")]
-    assert len(asm) == 1, asm
-    with open(os.path.join(workdir, asm[0])) as fh:
-        return fh.read()
 
 
 def inverse128_kernels(text: str) -> dict[str, list[str]]:
@@ -166,8 +149,7 @@ def check_claim(lines: list[str]) -> dict:
 def kernels(tmp_path_factory):
     if HIPCC is None:
         pytest.skip("hipcc not found")
-    work = str(tmp_path_factory.mktemp("isa"))  # (--save-temps writes into the working directory of the compile, never into the tree)
-    found = inverse128_kernels(compile_asm(SRC, work))
+    found = inverse128_kernels(compile_asm("skr_colored.hip", str(tmp_path_factory.mktemp("isa") / "colored")))
     assert sorted(found) == sorted(KERNELS.values()), sorted(found)
     return found
 

@@ -1,24 +1,17 @@
 """The masked rolling step kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
 `skr_step_launch_masked_rolling` runs `masked_kernel_v1<T, K, NOISE, RowForm::Rolling>` (csrc/skr_step_masked.hip).  Its contract is
-visible in the instruction stream, as that of the `Rolling<>` step kernels is (tests/test_rolling_isa.py): a workgroup of an inactive
+visible in the instruction stream, as that of the `RowForm::Rolling` step kernels is (tests/test_rolling_isa.py): a workgroup of an inactive
 sample ends before its first vector-memory instruction, every decision taken from the sample's row is a scalar branch with exec never
 masked, operands are global loads, and nothing spills.  The VGPR counts are printed beside those of the per-sample twins
 `masked_kernel_v1<T, K, NOISE, RowForm::PerSample>`, the same template compiled once, for DESIGN.md section 4.6; no occupancy bracket
 is asserted.  The census counts every one-trip instantiation of the template: 3 dtypes x 16 operand counts x noise x 4 row forms."""
 
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
-from conftest import ROOT
+from isa_cases import HIPCC, compile_asm, kernels_of, waves_per_simd
 
-import __graft_entry__ as G
-
-CSRC = os.path.join(ROOT, "skrample_amd", "csrc")
-HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
 # masked_kernel_v1<T, K, NOISE, RowForm F>; RowForm (skr_step_common.h): Kernarg 0, WholeBatch 1, PerSample 2, Rolling 3
@@ -28,34 +21,12 @@ TWIN = re.compile(r"masked_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE2EE")
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 
 
-def waves_per_simd(vgprs: int) -> int:
-    "gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, at most 8 waves"
-    return min(8, 512 // (max(1, -(-vgprs // 8)) * 8))
-
-
-def compiled(name: str, work: str) -> dict:
-    "{symbol: (instructions and labels, VGPRs, scratch bytes, private segment size)} of every kernel of one source file"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *G.PER_FILE_FLAGS.get(name, [])]
-    os.makedirs(work)
-    subprocess.run([HIPCC, *flags, "--save-temps", "-c", "-o", os.path.join(work, "x.o"), os.path.join(CSRC, name)], check=True, cwd=work, capture_output=True)
-    asm = [f for f in os.listdir(work) if f.endswith("gfx950.s")]
-    assert len(asm) == 1, asm
-    text = open(os.path.join(work, asm[0])).read()
-    out = {}
-    for m in re.finditer(r"^(_Z\w+):.*?^\.Lfunc_end\d+:.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", text, re.S | re.M):
-        body = m.group(0).split(".Lfunc_end")[0]
-        lines = [raw.split(";")[0].strip() for raw in body.splitlines()[1:]]
-        private = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(0))
-        out[m.group(1)] = ([l for l in lines if l and (not l.startswith(".") or l.startswith(".LBB"))], int(m.group(2)), int(m.group(3)), int(private.group(1)) if private else None)
-    return out
-
-
 @pytest.fixture(scope="module")
 def one_trip(tmp_path_factory):
     "every masked_kernel_v1 instantiation of the one translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = compiled("skr_step_masked.hip", str(tmp_path_factory.mktemp("isa") / "masked"))
+    found = kernels_of(compile_asm("skr_step_masked.hip", str(tmp_path_factory.mktemp("isa") / "masked")))
     return {k: v for k, v in found.items() if ONE_TRIP.search(k)}
 
 

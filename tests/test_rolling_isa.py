@@ -1,49 +1,27 @@
 """The rolling step kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_rolling` runs `Rolling<>` forms of the one-trip kernels (csrc/skr_step_fast.hip).  Their contract is visible in the
+`skr_step_launch_rolling` runs the `RowForm::Rolling` forms of the one-trip kernels (csrc/skr_step_fast.hip).  Their contract is visible in the
 instruction stream: a workgroup of an inactive sample ends before its first vector-memory instruction, every decision taken from
 the sample's row is a scalar branch, and nothing is written through the scalar unit.  Occupancy is compared with the per-sample
 form of the same instantiation; the VGPR counts of both are printed by a failure and quoted in DESIGN.md section 4.1."""
 
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
-from conftest import ROOT
+from isa_cases import HIPCC, compile_asm, kernels_of, waves_per_simd
 
-import __graft_entry__ as G
-
-SRC = os.path.join(ROOT, "skrample_amd", "csrc", "skr_step_fast.hip")
-HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 SCALAR_WRITE = re.compile(r"^s_(buffer_|scratch_)?(store|atomic)|^s_dcache_(wb|discard)")
-TAG = "NS_7RollingI"
-
-
-def waves_per_simd(vgprs: int) -> int:
-    "gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, at most 8 waves"
-    return min(8, 512 // (max(1, -(-vgprs // 8)) * 8))
+# the mangled RowForm argument of the three kernels (skr_step_common.h): Kernarg 0, WholeBatch 1, PerSample 2, Rolling 3
+TAG, PER_SAMPLE = "LNS_7RowFormE3E", "LNS_7RowFormE2E"
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    "{symbol: (instructions and labels, VGPRs)} of every kernel of skr_step_fast.hip"
+    "{symbol: (instructions and labels, VGPRs, ...)} of every kernel of skr_step_fast.hip"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    work = str(tmp_path_factory.mktemp("isa"))
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *G.PER_FILE_FLAGS.get(os.path.basename(SRC), [])]
-    subprocess.run([HIPCC, *flags, "--save-temps", "-c", "-o", os.path.join(work, "x.o"), SRC], check=True, cwd=work, capture_output=True)
-    asm = [f for f in os.listdir(work) if f.endswith("gfx950.s")]
-    assert len(asm) == 1, asm
-    text = open(os.path.join(work, asm[0])).read()
-    out = {}
-    for m in re.finditer(r"^(_Z\w+):.*?^\.Lfunc_end\d+:.*?; NumVgprs: (\d+)", text, re.S | re.M):
-        body = m.group(0).split(".Lfunc_end")[0]
-        lines = [raw.split(";")[0].strip() for raw in body.splitlines()[1:]]
-        out[m.group(1)] = ([l for l in lines if l and (not l.startswith(".") or l.startswith(".LBB"))], int(m.group(2)))
-    return out
+    return kernels_of(compile_asm("skr_step_fast.hip", str(tmp_path_factory.mktemp("isa") / "fast")))
 
 
 def rolling(kernels):
@@ -51,8 +29,8 @@ def rolling(kernels):
 
 
 def per_sample_twin(symbol: str) -> str:
-    "step_kernel_k1<Rolling<T>, N, NOISE, TILE, false, false> -> <PerSample<T>, N, NOISE, TILE, PACE, true>, and likewise for _k2 / _rk1"
-    return symbol.replace(TAG, "NS_9PerSampleI")
+    "step_kernel_k1<T, N, NOISE, TILE, false, Rolling> -> <T, N, NOISE, TILE, PACE, PerSample>, and likewise for _k2 / _rk1"
+    return symbol.replace(TAG, PER_SAMPLE)
 
 
 def test_every_table_kernel_has_a_rolling_form(kernels):
@@ -86,7 +64,7 @@ def test_no_scalar_writes(kernels):
 def test_absent_operands_are_skipped_by_scalar_branches(kernels):
     "the K-operand single-output form: at least K conditional scalar branches stand between the row fetch and the stores, and exec is never masked"
     for k in rolling(kernels):
-        m = re.search(r"14step_kernel_k1INS_7RollingI\w+?EELi(\d+)E", k)
+        m = re.search(r"14step_kernel_k1I\w+?Li(\d+)E", k)
         if not m:
             continue
         lines = kernels[k][0]
@@ -103,7 +81,7 @@ def test_occupancy_is_not_below_the_per_sample_form(kernels):
     (csrc/skr_step_fast.hip, add_operand)."""
     table, short = [], []
     for k in rolling(kernels):
-        twins = [t for t in kernels if "PerSample" in t and re.sub(r"Lb[01]E", "", t) == re.sub(r"Lb[01]E", "", per_sample_twin(k))
+        twins = [t for t in kernels if PER_SAMPLE in t and re.sub(r"Lb[01]E", "", t) == re.sub(r"Lb[01]E", "", per_sample_twin(k))
                  and re.findall(r"Li\d+E", t) == re.findall(r"Li\d+E", k)]  # fmt: skip
         twins = [t for t in twins if noise_flag(t) == noise_flag(k)]
         assert twins, ("no per-sample form of", k)

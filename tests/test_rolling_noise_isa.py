@@ -8,18 +8,11 @@ vector-memory instruction -- and before any LDS or Philox work, which the positi
 no rolling kernel spills more than its whole-batch twin (the 1024-lane strips spill by design).  VGPR counts and waves per SIMD are
 printed beside the twins' for DESIGN.md section 4.3; no occupancy bracket is asserted."""
 
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
-from conftest import ROOT
+from isa_cases import HIPCC, compile_asm, kernels_of, waves_per_simd
 
-import __graft_entry__ as G
-
-CSRC = os.path.join(ROOT, "skrample_amd", "csrc")
-HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 LDS = re.compile(r"^ds_")
 BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
@@ -37,29 +30,13 @@ WANT = {
 }
 
 
-def waves_per_simd(vgprs: int) -> int:
-    "gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, at most 8 waves"
-    return min(8, 512 // (max(1, -(-vgprs // 8)) * 8))
-
-
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     "{symbol: (instructions and labels, VGPRs, scratch bytes)} of every kernel of skr_noise.hip"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    work = str(tmp_path_factory.mktemp("isa") / "noise")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *G.PER_FILE_FLAGS.get("skr_noise.hip", [])]
-    os.makedirs(work)
-    subprocess.run([HIPCC, *flags, "--save-temps", "-c", "-o", os.path.join(work, "x.o"), os.path.join(CSRC, "skr_noise.hip")], check=True, cwd=work, capture_output=True)
-    asm = [f for f in os.listdir(work) if f.endswith("gfx950.s")]
-    assert len(asm) == 1, asm
-    text = open(os.path.join(work, asm[0])).read()
-    out = {}
-    for m in re.finditer(r"^(_Z\w+):.*?^\.Lfunc_end\d+:.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+)", text, re.S | re.M):
-        body = m.group(0).split(".Lfunc_end")[0]
-        lines = [raw.split(";")[0].strip() for raw in body.splitlines()[1:]]
-        out[m.group(1)] = ([l for l in lines if l and (not l.startswith(".") or l.startswith(".LBB"))], int(m.group(2)), int(m.group(3)))
-    return out
+    found = kernels_of(compile_asm("skr_noise.hip", str(tmp_path_factory.mktemp("isa") / "noise")))
+    return {k: v[:3] for k, v in found.items()}
 
 
 @pytest.fixture(scope="module")

@@ -4,13 +4,13 @@
     python tools/isa_compare.py OLD_TREE NEW_TREE [--files NAME.hip ...] [--jobs N] [--work DIR] [--renames FILE] [--pooled]
 
 Compiles the named files of skrample_amd/csrc (default: the step files skr_step.hip, skr_step_fast.hip, skr_step_backward.hip and
-skr_tape.hip) of each tree with the library's own flags, the tree's PER_FILE_FLAGS included (`--save-temps -c`), splits the device assembly per kernel the way tests/test_per_sample_isa.py and tests/test_rolling_isa.py do,
+skr_tape.hip) of each tree with the library's own flags, the tree's PER_FILE_FLAGS included (`--save-temps -c`), splits the device assembly per kernel the way tests/isa_cases.py does,
 and reports symbols found in one tree only and, for each common symbol, whether its instruction lines (comments stripped, labels
 kept, numbered within their kernel), TotalNumSgprs, NumVgprs, ScratchSize or its `.amdhsa_*` descriptor lines differ, with a unified
 diff per differing symbol.
 A host-side refactor must end in `0 added, 0 removed, 0 differing` for every file.  Exit status 1 when anything differs.
 With --work DIR the assembly is kept there and reused while it is newer than the tree's sources.
-With --renames FILE (lines of `OLD_SYMBOL NEW_SYMBOL`: a kernel template that gained a parameter) an old kernel is compared under its new
+With --renames FILE (lines of `OLD_SYMBOL NEW_SYMBOL`, written by hand or by tools/isa_renames.py: a kernel template that gained a parameter) an old kernel is compared under its new
 name; the map is printed ahead of the report (its size alone when it is long).
 With --pooled (kernels that moved between files, files merged or split) the kernels of all named files of a tree are pooled and the two
 pools compared; a named file may then be missing from either tree, and a symbol defined twice in one pool is an error."""

@@ -18,7 +18,7 @@ import os
 RAW = os.environ.get("SKR_PROF_RAW", "gpurun_out")   # where the rocprofv3 pass directories (prof_trace, prof_fetch, ...) are
 OUT = os.environ.get("SKR_PROF_OUT", "profiles")     # where the summaries go
 round_tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
-needle = sys.argv[2] if len(sys.argv) > 2 else "step_kernel_k1<skr::bf16_t, 4, true, false, true, false>"  # headline: K=4 bf16 + Philox, one-trip paced kernel, kernarg scalars
+needle = sys.argv[2] if len(sys.argv) > 2 else "step_kernel_k1<skr::bf16_t, 4, true, false, true, (skr::RowForm)0>"  # headline: K=4 bf16 + Philox, one-trip paced kernel, kernarg scalars
 HEADLINE_GRID = 256 * 4 * 128 * 128 // 8  # threads of a B=256 launch: bench.py's extra graph-loop key runs the same kernel at B=64
 
 

@@ -366,6 +366,36 @@ int skr_program_launch(const skr_program* prog, const void* const* inputs, void*
 void skr_program_destroy(skr_program* prog);
 
 /*
+ * Channels-last steps.  Every operand and output holds each sample as `plane` x `channels` elements with the channel innermost
+ * (torch.channels_last / channels_last_3d storage): storage position p of a sample is the logical element
+ *     l(p) = (p % channels) * plane + p / channels.
+ * A step is elementwise, so over operands that share one dense layout only the Philox draw depends on the layout.  The output at p
+ * has, bit for bit, the value skr_step_launch writes at l(p) for the same plan over the logically equal contiguous operands: same
+ * operand slot order, one fma per operand, noise last, `chain`, one rounding -- and the normal of element l(p), so a seed gives the
+ * same noise in either memory format.
+ * Checks: those of skr_step_launch, in its order and with its codes; then a NULL layout SKR_ERR_NULL; channels < 1, plane < 1 or
+ * channels * plane != plan->sample_numel SKR_ERR_SHAPE; a launch that draws with a non-zero convert_* SKR_ERR_UNSUPPORTED.
+ * A launch that does not draw (noise_mode 0, both zetas zero, channels == 1 or plane == 1) is skr_step_launch itself.  A launch that
+ * draws runs the one-trip channels-last kernel -- bf16 / fp16, one dtype for operands and out0, no out1, fp32 arithmetic, 1..8
+ * operands, channels 4 / 8 / 16, plane % 4 == 0, whole 2048-element chunks, samples made of whole chunks -- or the general
+ * grid-stride one (everything else skr_step_launch draws for); the two agree bit for bit, and skr_set_tuning("one_trip", 0) forces
+ * the general kernel.
+ */
+typedef struct skr_step_layout {
+  int64_t channels;  /* C: innermost storage axis of a sample */
+  int64_t plane;     /* product of the other sample axes (H*W, D*H*W) */
+} skr_step_layout;
+
+int skr_step_launch_channels_last(const skr_step_plan* plan, const void* const* inputs,
+                                  void* out0, void* out1, const uint64_t* seeds_dev,
+                                  const skr_step_layout* layout, int64_t numel, void* stream);
+
+/* A program that remembers the layout: skr_program_launch launches it as skr_step_launch_channels_last does.  The checks of
+ * skr_program_create, then the layout's (NULL, channels, plane, convert_*) as above. */
+int skr_program_create_channels_last(const skr_step_plan* plan, int64_t numel,
+                                     const skr_step_layout* layout, skr_program** out);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the
@@ -579,7 +609,8 @@ int skr_power_blend_backward(void* grad_a, void* grad_b, const void* g, int32_t 
  * created so far, "hipfft_execs" = forward hipFFT transforms run so far, "own_fft_execs" = forward N-D transforms run by the library's
  * own any-length kernels so far, "colored_inv128_launches" = launches of the persistent 128 x 128 inverse kernel of Colored noise so far,
  * "colored_inv128_ticketed" = those of its launches in which at least one plane was claimed from the device ticket (more than two planes
- * per block, ticket not disabled); -1 for an unknown key. */
+ * per block, ticket not disabled), "channels_last_one_trip" / "channels_last_general" = launches of skr_step_launch_channels_last
+ * (program launches included) that ran its one-trip / its general kernel so far; -1 for an unknown key. */
 int64_t skr_stat(const char* key);
 
 int skr_abi_version(void);

@@ -30,6 +30,7 @@ EXPORTS = (
     "skr_step_launch_indexed",
     "skr_step_launch_indexed_per_sample",
     "skr_step_launch_rolling",
+    "skr_step_launch_channels_last",
     "skr_step_launch_masked",
     "skr_step_launch_masked_indexed",
     "skr_step_launch_masked_indexed_per_sample",
@@ -38,6 +39,7 @@ EXPORTS = (
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
     "skr_program_create",
+    "skr_program_create_channels_last",
     "skr_program_launch",
     "skr_program_destroy",
     "skr_tape_launch",
@@ -95,6 +97,12 @@ class StepPlanC(ctypes.Structure):
         ("convert_from", ctypes.c_int32),
         ("convert_k", ctypes.c_double * 4),
     ]
+
+
+class StepLayoutC(ctypes.Structure):
+    "mirror of `skr_step_layout`: a sample stored as plane x channels elements, channel innermost"
+
+    _fields_ = [("channels", ctypes.c_int64), ("plane", ctypes.c_int64)]
 
 
 class StepGradPlanC(ctypes.Structure):
@@ -376,6 +384,8 @@ def load() -> ctypes.CDLL:
         for table_launch in (lib.skr_step_launch_indexed, lib.skr_step_launch_indexed_per_sample, lib.skr_step_launch_rolling):
             table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
             table_launch.restype = ctypes.c_int
+        lib.skr_step_launch_channels_last.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, ctypes.POINTER(StepLayoutC), i64, vp]
+        lib.skr_step_launch_channels_last.restype = ctypes.c_int
         lib.skr_step_launch_masked.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp]
         lib.skr_step_launch_masked.restype = ctypes.c_int
         for masked_table_launch in (lib.skr_step_launch_masked_indexed, lib.skr_step_launch_masked_indexed_per_sample, lib.skr_step_launch_masked_rolling):
@@ -389,6 +399,8 @@ def load() -> ctypes.CDLL:
         lib.skr_step_masked_backward_launch.restype = ctypes.c_int
         lib.skr_program_create.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(vp)]
         lib.skr_program_create.restype = ctypes.c_int
+        lib.skr_program_create_channels_last.argtypes = [ctypes.POINTER(StepPlanC), i64, ctypes.POINTER(StepLayoutC), ctypes.POINTER(vp)]
+        lib.skr_program_create_channels_last.restype = ctypes.c_int
         lib.skr_program_launch.argtypes = [vp, ctypes.POINTER(vp), vp, vp, vp, u64, u64, vp]
         lib.skr_program_launch.restype = ctypes.c_int
         lib.skr_program_destroy.argtypes = [vp]
@@ -493,6 +505,32 @@ def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, 
         current_stream_ptr(device),
     )
     check(status, "skr_step_launch")
+
+
+def launch_step_channels_last(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, layout: tuple[int, int], numel: int, device: torch.device) -> None:
+    """one fused launch over operands and outputs that all share the dense channels-last `layout` = (channels, plane)
+    (skr_step_launch_channels_last) on torch's current stream of `device`.  The `_hip.trace` entry is launch_step's: the layout is read
+    off the tensors.  The indexed-rows hook has no channels-last form: the caller takes the contiguous route while one is installed."""
+    lib = load()
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError("captured loops with device-resident rows take contiguous operands")
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((plan, list(inputs), out0, out1, seeds, numel))
+    n = len(inputs)
+    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in inputs])
+    desc = StepLayoutC(layout[0], layout[1])
+    status = lib.skr_step_launch_channels_last(
+        ctypes.byref(plan),
+        arr,
+        out0.data_ptr() if out0 is not None else None,
+        out1.data_ptr() if out1 is not None else None,
+        seeds.data_ptr() if seeds is not None else None,
+        ctypes.byref(desc),
+        numel,
+        current_stream_ptr(device),
+    )
+    check(status, "skr_step_launch_channels_last")
 
 
 def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device) -> None:

@@ -708,6 +708,8 @@ extern "C" int skr_colorize(void* out, int32_t out_dtype, void* spec_c64, float*
   return colored_any_impl(out, out_dtype, spec_c64, white_f32, partials_f64, nullptr, 0, batch, rank, dims, exponent, has_energy, energy, stream, true);
 }
 
+namespace skr { extern std::atomic<int64_t> g_cl_one_trip_launches, g_cl_general_launches; }  // skr_step_channels_last.hip
+
 extern "C" int64_t skr_stat(const char* key) {
   if (!key) return -1;
   std::lock_guard<std::mutex> lock(g_mutex);
@@ -716,5 +718,7 @@ extern "C" int64_t skr_stat(const char* key) {
   if (!strcmp(key, "own_fft_execs")) return g_own_execs;
   if (!strcmp(key, "colored_inv128_launches")) return skr::g_inv128_launches;
   if (!strcmp(key, "colored_inv128_ticketed")) return skr::g_inv128_ticketed;
+  if (!strcmp(key, "channels_last_one_trip")) return skr::g_cl_one_trip_launches;
+  if (!strcmp(key, "channels_last_general")) return skr::g_cl_general_launches;
   return -1;
 }

@@ -448,10 +448,6 @@ static int launch(StepArgs<Acc>& args, hipStream_t stream) {
   });
 }
 
-// a launch of this plan draws noise by the plan's own scalars (table launches: whether a draw happens is the row's business -- a zero
-// zeta skips it at run time -- so every noise_mode 1 launch of theirs counts as drawing)
-static bool plan_draws(const skr_step_plan& p) { return p.noise_mode == 1 && (p.zeta0 != 0.0 || (p.out1_dtype != SKR_NONE && p.zeta1 != 0.0)); }
-
 // no kernel exists without an output, or with a conversion and no out1: asked at run time for the status and at compile time for the instantiations
 constexpr bool no_kernel(bool st0, bool has1, bool conv) { return !has1 && (!st0 || conv); }
 
@@ -538,19 +534,30 @@ static int validate_plan(const skr_step_plan& p, int64_t numel) {
   return SKR_OK;
 }
 
-static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
-                            void* stream, skr::RowForm form, const skr_step_row* rows, const int32_t* index, int32_t row_offset) {
-  skr::DeviceGuard device_guard(out0 ? out0 : out1);
+// the checks every step launch makes before anything form-specific, in their order; `empty`: numel == 0, SKR_OK and nothing to launch
+int skr::step_launch_checks(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
+                            skr::RowForm form, const skr_step_row* rows, const int32_t* index, bool& empty) {
+  empty = false;
   if (!plan || (has_table(form) && (!rows || (per_sample_rows(form) && !index)))) return SKR_ERR_NULL;  // (from here on: rows != nullptr exactly when has_table(form))
   const skr_step_plan& p = *plan;
   // (ahead of the plan's own checks: a launch that draws without seeds is told so whatever else is wrong with its sample size)
   if (p.noise_mode == 1 && (has_table(form) || skr::plan_draws(p)) && numel > 0 && !seeds_dev) return SKR_ERR_NULL;
   if (const int rc = validate_plan(p, numel)) return rc;
-  if (numel == 0) return SKR_OK;  // empty batch: nothing to do (the reference returns empty tensors)
+  if (numel == 0) { empty = true; return SKR_OK; }  // empty batch: nothing to do (the reference returns empty tensors)
   const bool st0 = p.out0_dtype != SKR_NONE, has1 = p.out1_dtype != SKR_NONE;
   if ((p.n_terms > 0 && !inputs) || (st0 && !out0) || (has1 && !out1)) return SKR_ERR_NULL;
   if (const int rc = skr::check_ptrs(inputs, p.n_terms)) return rc;
   if ((st0 && !aligned16(out0)) || (has1 && !aligned16(out1))) return SKR_ERR_ALIGN;
+  return SKR_OK;
+}
+
+static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
+                            void* stream, skr::RowForm form, const skr_step_row* rows, const int32_t* index, int32_t row_offset) {
+  skr::DeviceGuard device_guard(out0 ? out0 : out1);
+  bool empty = false;
+  if (const int rc = skr::step_launch_checks(plan, inputs, out0, out1, seeds_dev, numel, form, rows, index, empty)) return rc;
+  if (empty) return SKR_OK;
+  const skr_step_plan& p = *plan;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (has_table(form)) {
     // one row per sample: the batch is numel / sample_numel, and a workgroup (2048 elements) must lie inside one sample
@@ -593,13 +600,23 @@ extern "C" int skr_step_launch_rolling(const skr_step_plan* plan, const void* co
 struct skr_program {
   skr_step_plan plan;
   int64_t numel;
+  skr_step_layout layout;  // channels == 0: none (skr_program_create)
 };
 
 extern "C" int skr_program_create(const skr_step_plan* plan, int64_t numel, skr_program** out) {
   if (!plan || !out) return SKR_ERR_NULL;
   *out = nullptr;
   if (const int rc = validate_plan(*plan, numel)) return rc;
-  *out = new (std::nothrow) skr_program{*plan, numel};
+  *out = new (std::nothrow) skr_program{*plan, numel, skr_step_layout{0, 0}};
+  return *out ? SKR_OK : SKR_ERR_LAUNCH;
+}
+
+extern "C" int skr_program_create_channels_last(const skr_step_plan* plan, int64_t numel, const skr_step_layout* layout, skr_program** out) {
+  if (!plan || !out) return SKR_ERR_NULL;
+  *out = nullptr;
+  if (const int rc = validate_plan(*plan, numel)) return rc;
+  if (const int rc = skr::channels_last_checks(*plan, layout)) return rc;
+  *out = new (std::nothrow) skr_program{*plan, numel, *layout};
   return *out ? SKR_OK : SKR_ERR_LAUNCH;
 }
 
@@ -609,6 +626,7 @@ extern "C" int skr_program_launch(const skr_program* prog, const void* const* in
   skr_step_plan p = prog->plan;  // (a private copy: one program may be launched from several threads at once)
   p.stream0 = stream0;
   p.stream1 = stream1;
+  if (prog->layout.channels != 0) return skr_step_launch_channels_last(&p, inputs, out0, out1, seeds_dev, &prog->layout, prog->numel, stream);
   return step_launch_impl(&p, inputs, out0, out1, seeds_dev, prog->numel, stream, skr::RowForm::Kernarg, nullptr, nullptr, 0);
 }
 

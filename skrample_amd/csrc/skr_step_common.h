@@ -460,6 +460,16 @@ static inline int xmap_lr_for(int64_t chunks) {
 extern thread_local int g_last_hip_error;
 int finish_launch();
 
+// a launch of this plan draws noise by the plan's own scalars (table launches: whether a draw happens is the row's business -- a zero
+// zeta skips it at run time -- so every noise_mode 1 launch of theirs counts as drawing)
+static inline bool plan_draws(const skr_step_plan& p) { return p.noise_mode == 1 && (p.zeta0 != 0.0 || (p.out1_dtype != SKR_NONE && p.zeta1 != 0.0)); }
+
+// the checks every step launch makes, in their order (skr_step.hip); `empty`: numel == 0, nothing to launch
+int step_launch_checks(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
+                       RowForm form, const skr_step_row* rows, const int32_t* index, bool& empty);
+// what a channels-last launch checks on top of them (skr_step_channels_last.hip)
+int channels_last_checks(const skr_step_plan& plan, const skr_step_layout* layout);
+
 // ---- host side: run-time values to template arguments, kernarg packing -------------------------------------------------------------
 // f(std::integral_constant<RowForm, F>{}) for the F that equals form
 template <typename Fn>

@@ -922,7 +922,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         self._hist_ptrs.append((sample.data_ptr(), model_output.data_ptr(), record.sample.data_ptr() if isinstance(record.sample, Tensor) else 0) if on_device else None)
         # what the pointers point at: a replayed step binds them without looking (its kernel was built for ONE dtype / size per operand), so
         # the signature of every record is compared against the one the entry was learned under (_fast_step)
-        self._hist_sigs.append((sample.dtype, model_output.dtype, record.sample.dtype if isinstance(record.sample, Tensor) else None, tuple(sample.shape), sample.device) if on_device else None)
+        self._hist_sigs.append((sample.dtype, model_output.dtype, record.sample.dtype if isinstance(record.sample, Tensor) else None, tuple(sample.shape), sample.device,
+                                _memory_format(sample), _memory_format(model_output), _memory_format(record.sample)) if on_device else None)
         self._previous = self._previous[max(len(self._previous) - keep, 0) :]
         self._raw_outputs = self._raw_outputs[max(len(self._raw_outputs) - keep, 0) :]
         self._raw_samples = self._raw_samples[max(len(self._raw_samples) - keep, 0) :]
@@ -982,9 +983,16 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         final_dtype = prog.out_dtypes[prog.final_out]
         if final_dtype != model_output.dtype:
             return
+        layout = prog.layout  # channels-last operands: the handle remembers the layout, and this call's two tensors must have it
+        if layout is not None and (tuple(sample.stride()) != prog.strides or tuple(model_output.stride()) != prog.strides):
+            return
         lib = _hip.load()
         handle = ctypes.c_void_p()
-        if lib.skr_program_create(ctypes.byref(prog.plan), prog.numel, ctypes.byref(handle)) != 0 or not handle.value:
+        if layout is None:
+            status = lib.skr_program_create(ctypes.byref(prog.plan), prog.numel, ctypes.byref(handle))
+        else:
+            status = lib.skr_program_create_channels_last(ctypes.byref(prog.plan), prog.numel, ctypes.byref(_hip.StepLayoutC(*layout)), ctypes.byref(handle))
+        if status != 0 or not handle.value:
             return
         entry = _FastEntry()
         weakref.finalize(entry, lib.skr_program_destroy, handle.value)
@@ -993,7 +1001,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         entry.sdt, entry.odt, entry.shape, entry.device, entry.dev_index = sample.dtype, model_output.dtype, sample.shape, sample.device, sample.device.index
         entry.step, entry.keep, entry.hist = step, keep, nprev
         entry.hist_sigs = list(self._hist_sigs)  # the records this step's history operands were lowered against
-        entry.sig = (sample.dtype, model_output.dtype, prog.out_dtypes[0] if prog.state_out is not None else sample.dtype, tuple(sample.shape), sample.device)
+        entry.layout, entry.strides = layout, (sample.stride() if layout is not None else None)
+        entry.sig = (sample.dtype, model_output.dtype, prog.out_dtypes[0] if prog.state_out is not None else sample.dtype, tuple(sample.shape), sample.device,
+                     layout, layout, layout)
         entry.o0dt, entry.o1dt = prog.out_dtypes
         small = sample.numel() * sample.element_size() < (16 << 20)  # (larger results get lazy.empty_output's staggered placement)
         entry.like0, entry.like1 = small and entry.o0dt == sample.dtype, small and entry.o1dt == sample.dtype
@@ -1028,7 +1038,10 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             return None
         shape = entry.shape
         if (type(sample) is not Tensor or type(model_output) is not Tensor or sample.dtype is not entry.sdt or model_output.dtype is not entry.odt
-                or sample.shape != shape or model_output.shape != shape or not sample.is_contiguous() or not model_output.is_contiguous()):  # fmt: skip
+                or sample.shape != shape or model_output.shape != shape):  # fmt: skip
+            return None
+        strides = entry.strides  # None: a contiguous entry; else the dense channels-last strides it was learned on
+        if (not sample.is_contiguous() or not model_output.is_contiguous()) if strides is None else (sample.stride() != strides or model_output.stride() != strides):
             return None
         sp, op = sample.data_ptr(), model_output.data_ptr()
         device = entry.device
@@ -1085,6 +1098,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             arr[j] = sp if code == 0 else op if code == 1 else hp[k][f]
             j += 1
         # (results below the staggering size that share the sample's dtype: empty_like skips the shape / dtype / device argument parsing)
+        empty_output = lazy.empty_output if strides is None else lazy.empty_output_channels_last
         out0 = torch.empty_like(sample) if entry.like0 else empty_output(shape, entry.o0dt, device)
         p0 = out0.data_ptr()
         if entry.o1dt is not None:
@@ -1131,11 +1145,18 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         return attr_dict(prev_sample=final, pred_original_sample=prediction) if return_dict else (final, prediction)
 
 
+def _memory_format(t):
+    "what a history record's signature says of a tensor's storage: None contiguous, (channels, plane) dense channels-last, else \"strided\""
+    if not isinstance(t, Tensor) or t.is_contiguous():
+        return None
+    return lazy.layout_of(t) or "strided"
+
+
 class _FastEntry:
     "what a replayed step of an in-order run needs besides today's tensors (SkrampleWrapperScheduler._fast_learn)"
 
     __slots__ = ("handle", "prog", "srcs", "draws", "noise", "arr", "sdt", "odt", "shape", "device", "dev_index", "step", "keep", "hist", "o0dt", "o1dt",
-                 "final_out", "state_out", "pred", "stream0", "stream1", "launch", "like0", "like1", "hist_sigs", "sig", "__weakref__")  # fmt: skip
+                 "final_out", "state_out", "pred", "stream0", "stream1", "launch", "like0", "like1", "hist_sigs", "sig", "layout", "strides", "__weakref__")  # fmt: skip
 
 
 @dataclasses.dataclass

@@ -339,6 +339,79 @@ def _prepare_tensor(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
+# ---- channels-last operands ------------------------------------------------------------------------------------------------
+# A step is elementwise, so over operands that all share one dense layout it runs on the storage order as it stands
+# (skr_step_launch_channels_last: only the fused Philox draw looks at the layout).  False restores the contiguous copies of every
+# non-contiguous operand (tests and tools/bench_channels_last.py compare the two).
+channels_last = True
+
+
+def layout_of(t: torch.Tensor) -> "tuple[int, int] | None":
+    """(channels, plane) of a dense channels-last tensor (torch.channels_last / channels_last_3d: axis 1 innermost in storage, the
+    other axes in order), None for everything else -- contiguous tensors, rank < 3, C == 1 or a single-position plane (their storage
+    order is the logical one), slices, other permutations."""
+    if t.ndim < 3 or t.is_contiguous():
+        return None
+    shape, strides = t.shape, t.stride()
+    channels, plane = shape[1], 1
+    for d in shape[2:]:
+        plane *= d
+    if channels <= 1 or plane <= 1 or shape[0] < 1:
+        return None
+    want, acc = [0] * t.ndim, channels
+    want[1] = 1
+    for axis in range(t.ndim - 1, 1, -1):
+        want[axis] = acc
+        acc *= shape[axis]
+    want[0] = acc
+    for axis in range(t.ndim):
+        if shape[axis] != 1 and strides[axis] != want[axis]:
+            return None
+    return channels, plane
+
+
+def shared_layout(tensors, shape) -> "tuple[int, int] | None":
+    "the layout every tensor of `tensors` has (all of `shape`, all dense channels-last), or None"
+    layout, shape = None, tuple(shape)
+    for t in tensors:
+        layout = layout_of(t) if tuple(t.shape) == shape else None
+        if layout is None:
+            return None
+    return layout
+
+
+def _prepare_keeping_layout(t: torch.Tensor) -> torch.Tensor:
+    "a channels-last operand as it is; an alignment clone keeps the format"
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.preserve_format)
+    return t
+
+
+def _channels_last_strides(shape) -> tuple:
+    strides, acc = [0] * len(shape), shape[1]
+    strides[1] = 1
+    for axis in range(len(shape) - 1, 1, -1):
+        strides[axis] = acc
+        acc *= shape[axis]
+    strides[0] = acc
+    return tuple(strides)
+
+
+def empty_output_channels_last(shape, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
+    "empty_output in channels-last storage: the same staggered placement for large tensors"
+    global _stagger_next
+    shape = tuple(shape)
+    strides = _channels_last_strides(shape)
+    numel = math.prod(shape)
+    item = _ITEMSIZE.get(dtype, 4)
+    if numel * item < (16 << 20):
+        return torch.empty_strided(shape, strides, dtype=dtype, device=device)
+    k = _stagger_next
+    _stagger_next = (k + 1) % _STAGGER_SLOTS
+    flat = torch.empty(numel + (4096 + _STAGGER_SLOTS * _STAGGER_BYTES) // item, dtype=dtype, device=device)
+    return flat.as_strided(shape, strides, (4096 + k * _STAGGER_BYTES) // item)
+
+
 def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64: bool | None = None) -> list[torch.Tensor]:
     """Materialise one or two forms in a single fused launch.  forms[1] may reference forms[0]
     through a Node leaf (then out1 = chain*out0 + ...)."""
@@ -372,7 +445,18 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
                 rest[i] = (leaf, c)
         f1 = Lin(rest, f1.shape, f1.device)
 
-    plan, operands, seeds = _lower(conv, f0, f1, chain, out_dtypes, acc_f64)
+    # channels-last route: every tensor operand in one dense channels-last layout, no rounded conversion (Runge-Kutta stages), no capture
+    # hook, no autograd recording
+    leaves = [leaf for f in (f0, f1) if f is not None for leaf, _ in f.terms.values() if isinstance(leaf, torch.Tensor)]
+    keep_layout = channels_last and conv is None and _hip.indexed is None and not grad_recorded(*leaves)
+    plan, operands, seeds = _lower(conv, f0, f1, chain, out_dtypes, acc_f64, keep_layout=keep_layout)
+    layout = shared_layout(operands, shape) if keep_layout else None
+    if layout is not None:
+        plan.sample_numel = layout[0] * layout[1]
+        out0 = empty_output_channels_last(shape, out_dtypes[0], device)
+        out1 = empty_output_channels_last(shape, out_dtypes[1], device) if f1 is not None else None
+        _hip.launch_step_channels_last(plan, operands, out0, out1, seeds, layout, numel, device)
+        return [out0] if out1 is None else [out0, out1]
     if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
         if conv is not None:
             plan_a = conversion_gradient(conv.to_kind, conv.from_kind, conv.k)
@@ -386,7 +470,8 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
     return [out0] if out1 is None else [out0, out1]
 
 
-def _lower(conv, f0: "Lin", f1: "Lin | None", chain: float, out_dtypes, acc_f64: bool | None, fuse1: bool = True, max_terms: int = _hip.MAX_TERMS):
+def _lower(conv, f0: "Lin", f1: "Lin | None", chain: float, out_dtypes, acc_f64: bool | None, fuse1: bool = True, max_terms: int = _hip.MAX_TERMS,
+           keep_layout: bool = False):
     """Two expanded forms over one operand list -> (plan, operands, seeds): leaves merged (a tensor in both forms is ONE operand with both
     coefficients), at most one fused Philox draw per form, operands in at most two dtype groups.  `out_dtypes` has one entry per OUTPUT:
     evaluate() stores both forms (two entries when f1 is given), evaluate_masked() blends them into one (one entry; `fuse1` False: a
@@ -440,7 +525,9 @@ def _lower(conv, f0: "Lin", f1: "Lin | None", chain: float, out_dtypes, acc_f64:
         acc_f64 = wide == torch.float64 or _compute_dtype.get() == torch.float64
     if acc_f64:
         wide = torch.float64
-    prepared = {i: _prepare_tensor(t) for i, t in tensors.items()}
+    # (keep_layout: operands that all share one dense channels-last layout go in as they are -- evaluate() reads the layout off them)
+    prepare = _prepare_keeping_layout if keep_layout and shared_layout(tensors.values(), shape) is not None else _prepare_tensor
+    prepared = {i: prepare(t) for i, t in tensors.items()}
     for t in prepared.values():
         if t.shape != shape and t.numel() != numel:
             raise SkrampleHipError(f"operand shape {tuple(t.shape)} does not match {shape}")

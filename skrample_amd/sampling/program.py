@@ -18,7 +18,7 @@ from typing import Any, Sequence
 import torch
 
 from .. import _hip
-from .lazy import LazyTensor, Lin, PhiloxNoise, empty_output
+from .lazy import LazyTensor, Lin, PhiloxNoise, empty_output, empty_output_channels_last, layout_of, shared_layout
 from .structured import SKSamples
 
 Role = tuple  # ("x",) ("o",) ("n",) ("px", k) ("pi", k) ("po", k) ("pn", k)   k = negative index into the history
@@ -68,7 +68,7 @@ class Roles:
 
 
 class StepProgram:
-    __slots__ = ("plan", "roles", "dtypes", "shape", "numel", "out_dtypes", "noise_roles", "final_out", "state_out", "pred", "ptr_array")
+    __slots__ = ("plan", "roles", "dtypes", "shape", "numel", "out_dtypes", "noise_roles", "final_out", "state_out", "pred", "ptr_array", "layout", "strides")
 
     def __init__(self):
         self.ptr_array = None
@@ -86,6 +86,14 @@ class StepProgram:
             prog.roles.append(role)
         prog.dtypes = [t.dtype for t in inputs]
         prog.shape, prog.numel = tuple(record.final.shape), numel
+        # the operands' memory format: contiguous (layout None), or one dense channels-last layout that the outputs share
+        # (skr_step_launch_channels_last); replayed operands must have the very strides
+        prog.layout = shared_layout(inputs, prog.shape) if inputs and not inputs[0].is_contiguous() else None
+        prog.strides = tuple(inputs[0].stride()) if prog.layout is not None else None
+        if prog.layout is None and any(not t.is_contiguous() for t in (*inputs, out0)):
+            return None
+        if prog.layout is not None and any(o is not None and (tuple(o.shape) != prog.shape or tuple(o.stride()) != prog.strides) for o in (out0, out1)):
+            return None
         prog.out_dtypes = (out0.dtype, out1.dtype if out1 is not None else None)
         # which Philox draw feeds which output
         prog.noise_roles = [None, None]
@@ -131,7 +139,9 @@ class StepProgram:
         ops = []
         for role, dt in zip(self.roles, self.dtypes):
             t = roles.get(role)
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != self.numel or not t.is_contiguous() or t.data_ptr() % 16 or t.device != device:
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != self.numel or t.data_ptr() % 16 or t.device != device:
+                return None
+            if not t.is_contiguous() if self.strides is None else (tuple(t.shape) != self.shape or t.stride() != self.strides):
                 return None
             ops.append(t)
         plan = self.plan
@@ -150,8 +160,11 @@ class StepProgram:
             if seeds_ptr is not None and ptr != seeds_ptr:
                 return None
             seeds_ptr = ptr
-        out0 = empty_output(self.shape, self.out_dtypes[0], device)
-        out1 = empty_output(self.shape, self.out_dtypes[1], device) if self.out_dtypes[1] is not None else None
+        if self.layout is not None and _hip.indexed is not None:
+            return None  # (captured loops with device-resident rows take contiguous operands: the general path makes them)
+        empty = empty_output if self.layout is None else empty_output_channels_last
+        out0 = empty(self.shape, self.out_dtypes[0], device)
+        out1 = empty(self.shape, self.out_dtypes[1], device) if self.out_dtypes[1] is not None else None
         n = len(ops)
         if self.ptr_array is None:
             self.ptr_array = (ctypes.c_void_p * max(n, 1))()
@@ -161,7 +174,12 @@ class StepProgram:
         lib = _hip.load()
         if _hip.trace is not None:
             _hip.trace.append((plan, ops, out0, out1, None, self.numel))
-        status = _hip.step_launch_raw(plan, arr, out0.data_ptr(), out1.data_ptr() if out1 is not None else None, seeds_ptr, self.numel, _hip.current_stream_ptr(device))
+        if self.layout is not None:
+            desc = _hip.StepLayoutC(*self.layout)
+            status = lib.skr_step_launch_channels_last(ctypes.byref(plan), arr, out0.data_ptr(), out1.data_ptr() if out1 is not None else None, seeds_ptr,
+                                                       ctypes.byref(desc), self.numel, _hip.current_stream_ptr(device))
+        else:
+            status = _hip.step_launch_raw(plan, arr, out0.data_ptr(), out1.data_ptr() if out1 is not None else None, seeds_ptr, self.numel, _hip.current_stream_ptr(device))
         _hip.check(status, "skr_step_launch")
         outs = (out0, out1)
         final = outs[self.final_out]

@@ -396,6 +396,29 @@ int skr_program_create_channels_last(const skr_step_plan* plan, int64_t numel,
                                      const skr_step_layout* layout, skr_program** out);
 
 /*
+ * The masked step on channels-last operands: skr_step_launch_masked over operands and `out` that hold each sample as plane x channels,
+ * channel innermost, exactly as for skr_step_launch_channels_last.  The mask stays in LOGICAL order and skr_step_mask is unchanged:
+ * storage position p of sample s reads mask[s * batch_stride + l(p) % mask_numel].  A mask that spells out only trailing plane axes
+ * (mask_numel divides plane: (B,1,H,W), (1,1,H,W), (H,W), (W,), or (B,1,1,H,W) over 5-D latents) therefore reads
+ * mask[(p / channels) % mask_numel]; a full-size mask (mask_numel == sample_numel) reads mask[l(p)].
+ * The output at p has, bit for bit, the value skr_step_launch_masked writes at l(p) for the same plan over the logically equal
+ * contiguous operands and the same mask: s in slot order with one fma per operand and the noise last, k over the operands whose coef1
+ * is not exactly zero, out = fma(m, s, (1 - m) * k) rounded once, and the normal of element l(p) (Philox block l >> 2, lane l & 3).
+ * Checks, before any launch and without reading device memory: those of skr_step_launch_masked, in its order and with its codes; then
+ * a NULL layout SKR_ERR_NULL; channels < 1, plane < 1 or channels * plane != plan->sample_numel SKR_ERR_SHAPE.  numel == 0 is SKR_OK
+ * with nothing launched.
+ * channels == 1 or plane == 1 (l(p) = p) is skr_step_launch_masked itself.  Otherwise the one-trip channels-last kernel runs -- bf16 /
+ * fp16, one dtype for operands, mask and out, fp32 arithmetic, 1..8 operands, channels 4 / 8 / 16, plane % 4 == 0, whole 2048-element
+ * chunks, samples made of whole chunks, mask_numel even and dividing plane -- or the general grid-stride one (everything else
+ * skr_step_launch_masked accepts: fp32 tensors, fp64 accumulation, two dtype groups, up to SKR_ROW_TERMS operands, any channel count,
+ * any plane, ragged sizes, full-size masks, odd mask_numel, a mask of another dtype); the two agree bit for bit, and
+ * skr_set_tuning("one_trip", 0) forces the general kernel.  There are no row forms (indexed / per-sample / rolling) in channels-last.
+ */
+int skr_step_launch_masked_channels_last(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                         const skr_step_mask* mask, const uint64_t* seeds_dev,
+                                         const skr_step_layout* layout, int64_t numel, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the
@@ -610,7 +633,8 @@ int skr_power_blend_backward(void* grad_a, void* grad_b, const void* g, int32_t 
  * own any-length kernels so far, "colored_inv128_launches" = launches of the persistent 128 x 128 inverse kernel of Colored noise so far,
  * "colored_inv128_ticketed" = those of its launches in which at least one plane was claimed from the device ticket (more than two planes
  * per block, ticket not disabled), "channels_last_one_trip" / "channels_last_general" = launches of skr_step_launch_channels_last
- * (program launches included) that ran its one-trip / its general kernel so far; -1 for an unknown key. */
+ * (program launches included) that ran its one-trip / its general kernel so far, "masked_channels_last_one_trip" /
+ * "masked_channels_last_general" = the same for skr_step_launch_masked_channels_last; -1 for an unknown key. */
 int64_t skr_stat(const char* key);
 
 int skr_abi_version(void);

@@ -35,6 +35,7 @@ EXPORTS = (
     "skr_step_launch_masked_indexed",
     "skr_step_launch_masked_indexed_per_sample",
     "skr_step_launch_masked_rolling",
+    "skr_step_launch_masked_channels_last",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -391,6 +392,8 @@ def load() -> ctypes.CDLL:
         for masked_table_launch in (lib.skr_step_launch_masked_indexed, lib.skr_step_launch_masked_indexed_per_sample, lib.skr_step_launch_masked_rolling):
             masked_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp, vp, i32, vp]
             masked_table_launch.restype = ctypes.c_int
+        lib.skr_step_launch_masked_channels_last.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, ctypes.POINTER(StepLayoutC), i64, vp]
+        lib.skr_step_launch_masked_channels_last.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -552,6 +555,28 @@ def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch
     else:
         status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds_ptr, numel, current_stream_ptr(device))
     check(status, "skr_step_launch_masked")
+
+
+def launch_step_masked_channels_last(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds,
+                                      layout: tuple[int, int], numel: int, device: torch.device) -> None:
+    """one masked step launch over operands and an output that all share the dense channels-last `layout` = (channels, plane)
+    (skr_step_launch_masked_channels_last) on torch's current stream of `device`; `mask` is contiguous, in logical order.  The
+    `_hip.trace` entry is launch_step_masked's seven-entry tuple: the layout is read off the tensors.  The indexed-rows hook has no
+    channels-last form: the caller takes the contiguous route while one is installed."""
+    lib = load()
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError("captured loops with device-resident rows take contiguous operands")
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((plan, list(operands), out, None, seeds, numel, mask))
+    n = len(operands)
+    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
+    desc = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
+    where = StepLayoutC(layout[0], layout[1])
+    status = lib.skr_step_launch_masked_channels_last(
+        ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, ctypes.byref(where), numel, current_stream_ptr(device)
+    )
+    check(status, "skr_step_launch_masked_channels_last")
 
 
 def launch_step_masked_rolling_raw(plan: StepPlanC, arr, out_ptr, mask: StepMaskC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:

@@ -709,6 +709,7 @@ extern "C" int skr_colorize(void* out, int32_t out_dtype, void* spec_c64, float*
 }
 
 namespace skr { extern std::atomic<int64_t> g_cl_one_trip_launches, g_cl_general_launches; }  // skr_step_channels_last.hip
+namespace skr { extern std::atomic<int64_t> g_mcl_one_trip_launches, g_mcl_general_launches; }  // skr_step_masked_channels_last.hip
 
 extern "C" int64_t skr_stat(const char* key) {
   if (!key) return -1;
@@ -720,5 +721,7 @@ extern "C" int64_t skr_stat(const char* key) {
   if (!strcmp(key, "colored_inv128_ticketed")) return skr::g_inv128_ticketed;
   if (!strcmp(key, "channels_last_one_trip")) return skr::g_cl_one_trip_launches;
   if (!strcmp(key, "channels_last_general")) return skr::g_cl_general_launches;
+  if (!strcmp(key, "masked_channels_last_one_trip")) return skr::g_mcl_one_trip_launches;
+  if (!strcmp(key, "masked_channels_last_general")) return skr::g_mcl_general_launches;
   return -1;
 }

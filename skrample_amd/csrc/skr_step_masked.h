@@ -21,4 +21,16 @@ __device__ __forceinline__ Raw<T> load_mask8(const void* base, int64_t m0, int64
   return r;
 }
 
+// What the entry checks of a masked launch leave behind for its launcher.
+struct MaskedLaunch {
+  bool noise;      // the launch may draw: the plan's zeta0 decides for the kernarg form, noise_mode alone for the row forms (the row's zeta0 is data)
+  bool one_trip;   // the one-trip vector kernel covers it (the row forms have no other)
+  int64_t chunks;  // 2048-element chunks of the launch, and
+  int bps_shift;   // chunks per sample as the kernels take them (sample_of); both set when one_trip
+};
+
+// every check of a masked launch behind its NULL tests (skr_step_masked.hip); also asked by skr_step_launch_masked_channels_last
+int masked_prepare(const skr_step_plan& p, const skr_step_mask& mk, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
+                   bool rows, MaskedLaunch* launch);
+
 }  // namespace skr

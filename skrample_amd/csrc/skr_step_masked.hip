@@ -227,14 +227,6 @@ __global__ __launch_bounds__(BLOCK) void masked_kernel_gen(const MaskedGenArgs a
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-// What the entry checks of a masked launch leave behind for its launcher.
-struct MaskedLaunch {
-  bool noise;      // the launch may draw: the plan's zeta0 decides for the kernarg form, noise_mode alone for the row forms (the row's zeta0 is data)
-  bool one_trip;   // the one-trip vector kernel covers it (the row forms have no other)
-  int64_t chunks;  // 2048-element chunks of the launch, and
-  int bps_shift;   // chunks per sample as the kernels take them (sample_of); both set when one_trip
-};
-
 // the one-trip launch of any form: dtype x noise x form x operand count to the instantiation, and its kernarg
 static void launch_masked_v1(const skr_step_plan& p, const void* const* inputs, void* out, const skr_step_mask& mk, const uint64_t* seeds,
                              const MaskedLaunch& l, RowForm form, const RowRef& tab, hipStream_t s) {
@@ -264,8 +256,8 @@ static void launch_masked_v1(const skr_step_plan& p, const void* const* inputs, 
 }
 
 // Every check of a masked launch behind its NULL tests, in skr_step_launch_masked's order and with its codes; `rows`: for a row form, whose
-// plan scalars are ignored.  SKR_OK with numel == 0 means "nothing to do".
-static int masked_prepare(const skr_step_plan& p, const skr_step_mask& mk, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
+// plan scalars are ignored.  SKR_OK with numel == 0 means "nothing to do".  (Declared in skr_step_masked.h: the channels-last entry asks it too.)
+int masked_prepare(const skr_step_plan& p, const skr_step_mask& mk, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
                           bool rows, MaskedLaunch* launch) {
   launch->noise = launch->one_trip = false;
   if (p.n_terms < 0 || p.n_group_a < 0 || p.n_group_a > p.n_terms || p.n_terms > SKR_ROW_TERMS) return SKR_ERR_TERMS;

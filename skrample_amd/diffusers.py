@@ -804,6 +804,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     # While a mask is set, step() returns prev_sample with that blend already applied, from the step's own launch
     # (lazy.evaluate_masked / skr_step_launch_masked) for the samplers whose step is one single-output launch, and from one more
     # launch behind the step for the two-output samplers (UniPC, SPC), whose state and history stay what they are.
+    # Channels-last latents: when sample, model output, history, `original_samples` and `noise` all share one dense channels-last layout
+    # the masked launch runs on them as they are (skr_step_launch_masked_channels_last): no copy, a channels-last prev_sample with the
+    # bits of the contiguous run.  The mask is kept contiguous, in logical order.  A mixed layout takes the copying path as before.
     def set_inpaint(self, mask: Tensor, original_samples: Tensor, noise: Tensor) -> None:
         """blend every following step(): mask == 1 is generated, mask == 0 keeps `original_samples`, re-noised with `noise` to the
         level of the step's target (after the last step: `original_samples` itself).  `mask` broadcasts over leading axes of the

@@ -341,30 +341,45 @@ def _prepare_tensor(t: torch.Tensor) -> torch.Tensor:
 
 # ---- channels-last operands ------------------------------------------------------------------------------------------------
 # A step is elementwise, so over operands that all share one dense layout it runs on the storage order as it stands
-# (skr_step_launch_channels_last: only the fused Philox draw looks at the layout).  False restores the contiguous copies of every
-# non-contiguous operand (tests and tools/bench_channels_last.py compare the two).
+# (skr_step_launch_channels_last: only the fused Philox draw looks at the layout; skr_step_launch_masked_channels_last for masked
+# steps, whose mask index looks at it too).  False restores the contiguous copies of every non-contiguous operand (tests,
+# tools/bench_channels_last.py and tools/bench_masked_channels_last.py compare the two).
 channels_last = True
+
+
+_layout_cache: dict = {}  # (shape, strides) -> layout_of's answer: the walk below costs microseconds, and every step of a loop asks for the same few
 
 
 def layout_of(t: torch.Tensor) -> "tuple[int, int] | None":
     """(channels, plane) of a dense channels-last tensor (torch.channels_last / channels_last_3d: axis 1 innermost in storage, the
     other axes in order), None for everything else -- contiguous tensors, rank < 3, C == 1 or a single-position plane (their storage
     order is the logical one), slices, other permutations."""
-    if t.ndim < 3 or t.is_contiguous():
+    key = (t.shape, t.stride())
+    try:
+        return _layout_cache[key]
+    except KeyError:
+        if len(_layout_cache) >= 256:
+            _layout_cache.clear()
+        found = _layout_cache[key] = _layout_from(*key)
+        return found
+
+
+def _layout_from(shape, strides) -> "tuple[int, int] | None":
+    ndim = len(shape)
+    if ndim < 3:
         return None
-    shape, strides = t.shape, t.stride()
     channels, plane = shape[1], 1
     for d in shape[2:]:
         plane *= d
     if channels <= 1 or plane <= 1 or shape[0] < 1:
         return None
-    want, acc = [0] * t.ndim, channels
+    want, acc = [0] * ndim, channels
     want[1] = 1
-    for axis in range(t.ndim - 1, 1, -1):
+    for axis in range(ndim - 1, 1, -1):
         want[axis] = acc
         acc *= shape[axis]
     want[0] = acc
-    for axis in range(t.ndim):
+    for axis in range(ndim):
         if shape[axis] != 1 and strides[axis] != want[axis]:
             return None
     return channels, plane
@@ -372,11 +387,16 @@ def layout_of(t: torch.Tensor) -> "tuple[int, int] | None":
 
 def shared_layout(tensors, shape) -> "tuple[int, int] | None":
     "the layout every tensor of `tensors` has (all of `shape`, all dense channels-last), or None"
-    layout, shape = None, tuple(shape)
+    layout, shape, first = None, tuple(shape), None
     for t in tensors:
-        layout = layout_of(t) if tuple(t.shape) == shape else None
-        if layout is None:
+        if tuple(t.shape) != shape:
             return None
+        strides = t.stride()
+        if strides != first:  # (the same strides as the tensor before: the same answer)
+            layout = layout_of(t)
+            if layout is None:
+                return None
+            first = strides
     return layout
 
 
@@ -610,6 +630,10 @@ def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtyp
     """mask * form + (1 - mask) * known in ONE launch (skr_step_launch_masked): `form` is a solver step (it may hold one fused Philox
     draw), `known` the re-noised kept region.  The leaves of both are merged into one operand list.  Host-resident operands evaluate
     the same expression with torch ops in the accumulate type.
+    Channels-last: when every tensor leaf of both forms shares one dense channels-last layout (`shared_layout`), `lazy.channels_last`
+    is on, no `_hip.indexed` hook is installed and nothing is grad-recorded, the launch is skr_step_launch_masked_channels_last: no
+    operand is copied, the result is channels-last and has the bits of the contiguous launch; the mask goes in logical order.
+    Mixed layouts, captured loops and recorded steps take the contiguous path.
     Autograd: device operands that require grad while autograd records go through `_MaskedStepFunction`, whose backward is one
     skr_step_masked_backward_launch; the forward's bits are those of the launch without autograd.  The mask has no gradient (it would
     need the operands and a reduction over the broadcast axes): a mask that requires grad is refused.  Host-resident operands that
@@ -636,11 +660,20 @@ def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtyp
         return _host_evaluate_masked(f0, f1, mask, out_dtype, acc_f64)
     if not mask.is_cuda or mask.device != device:
         raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
-    plan, operands, seeds = _lower(None, f0, f1, 0.0, [out_dtype], acc_f64, fuse1=False, max_terms=_hip.ROW_TERMS)
+    # channels-last route: every tensor leaf of both forms in one dense channels-last layout, no capture hook, no autograd recording
+    keep_layout = channels_last and _hip.indexed is None and not recorded
+    plan, operands, seeds = _lower(None, f0, f1, 0.0, [out_dtype], acc_f64, fuse1=False, max_terms=_hip.ROW_TERMS, keep_layout=keep_layout)
     if mask.dtype == torch.float64 and not plan.acc_f64:
         raise SkrampleHipError("a float64 mask needs float64 accumulation")
     numel = math.prod(shape)
     plan.sample_numel = numel // shape[0] if shape[0] else 1
+    layout = shared_layout(operands, shape) if keep_layout else None
+    if layout is not None:
+        # the operands stay as they are and the result is channels-last; the mask keeps its logical order (a single-channel mask is
+        # contiguous in either memory format: no copy)
+        out = empty_output_channels_last(shape, out_dtype, device)
+        _hip.launch_step_masked_channels_last(plan, operands, out, _prepare_tensor(mask), mask_numel, batch_stride, seeds, layout, numel, device)
+        return out
     if recorded:
         return _MaskedStepFunction.apply(plan, seeds, shape, numel, device, _prepare_tensor(mask), mask_numel, batch_stride, *operands)
     out = empty_output(shape, out_dtype, device)

@@ -419,6 +419,56 @@ int skr_step_launch_masked_channels_last(const skr_step_plan* plan, const void* 
                                          const skr_step_layout* layout, int64_t numel, void* stream);
 
 /*
+ * The guided step -- classifier-free guidance fused into the step launch.  A guided loop evaluates the network on a doubled batch,
+ * splits the output into `uncond` and `cond` and forms, with three tensor ops,
+ *     d = cond - uncond;   m = guidance_scale * d;   noise_pred = uncond + m
+ * before the scheduler step reads noise_pred.  Guidance replaces one operand of the step's linear form by a value computed from two,
+ * so one launch evaluates, with T the dtype of the dtype group `slot` lies in, u = inputs[slot][e], c = cond[e]:
+ *
+ *     p          = rn_T( u + rn_T( g_M * rn_T(c - u) ) )
+ *     out[e]     = rn( sum_k coef0[k] * v_k + zeta0 * N(seed[s(e)], stream0, e) ),   v_slot = p,  v_k = inputs[k][e] otherwise
+ *     guided_out[e] = p                                                              (when guided_out is given)
+ *
+ * Arithmetic of p: torch's.  Every operation is a separate one in the op-math type M -- fp32 for bf16, fp16 and fp32 tensors, fp64 for
+ * fp64 tensors --, g_M is `scale` converted to M once, nothing is contracted (for T = float the multiply and the add stay two
+ * instructions), and for a 16-bit T each fp32 result is rounded to fp32 first and to T after.  So p has the bits of the three torch
+ * lines over tensors of dtype T with a Python-number scale.  Under acc_f64 with a 16-bit T the guidance is still fp32 op-math, and p is
+ * widened exactly.
+ * One exception, torch's own: for T = fp16 the elements from the last multiple of 2048 below numel on -- the partial last block of
+ * torch's elementwise kernel on gfx950 -- have g_M * d rounded to fp16 ONCE, from the exact product, because torch's kernel fuses
+ * the multiply with the conversion there.  The entry does the same for those elements, so p still has torch's bits on ragged sizes.
+ * Arithmetic of out: that of skr_step_launch -- from zero, operands in slot order, one fma each, the noise term last (skipped when
+ * zeta0 == 0), one rounding by the store.  `out` therefore has, bit for bit, what skr_step_launch writes for the same plan over the
+ * operand list whose entry `slot` is a tensor holding p; guided_out is that tensor.
+ * Plan contract (the masked launch's): out1_dtype must be SKR_NONE (`out` has out0_dtype); chain, zeta1 and convert_* must be zero
+ * (SKR_ERR_UNSUPPORTED otherwise); coef1 is ignored; at most SKR_ROW_TERMS operands (SKR_ERR_TERMS beyond); the dtype groups are those
+ * of skr_step_launch; sample_numel is read by a launch that draws only, with skr_step_launch's rules.
+ * Guidance-only form: out0_dtype == SKR_NONE with out == NULL and n_terms == 1 (so slot == 0) stores p alone; guided_out is then
+ * required, and nothing is drawn.
+ * Launches of whole 2048-element chunks (samples made of whole chunks when the launch draws) with one 16- or 32-bit dtype for operands,
+ * cond and both outputs and fp32 arithmetic take a one-trip vector kernel; everything else (ragged sizes, small samples, two dtype
+ * groups, fp64, the guidance-only form) a grid-stride per-element kernel.  The two agree bit for bit ("one_trip" 0 forces the second).
+ * Checked before the launch, without dereferencing device memory, in this order (skr_step_launch's, with what the guidance adds):
+ *   a NULL plan or guide SKR_ERR_NULL;  a launch that draws without seeds SKR_ERR_NULL;  n_terms outside 0..SKR_ROW_TERMS or n_group_a
+ *   outside 0..n_terms SKR_ERR_TERMS;  slot outside 0..n_terms-1 SKR_ERR_TERMS;  numel < 0 SKR_ERR_SHAPE;  no output at all (out0_dtype
+ *   SKR_NONE and no guided_out) SKR_ERR_NULL;  a noise_mode other than 0 / 1, a second output, chain, zeta1, convert_*, a non-zero
+ *   `reserved`, or out0_dtype SKR_NONE outside the guidance-only form SKR_ERR_UNSUPPORTED;  the sample size of a launch that draws
+ *   SKR_ERR_SHAPE / SKR_ERR_UNSUPPORTED as in skr_step_launch;  numel == 0 SKR_OK with nothing launched;  a NULL inputs, operand, out or
+ *   cond SKR_ERR_NULL;  a misaligned operand, out, cond or guided_out SKR_ERR_ALIGN;  a dtype combination skr_step_launch does not take
+ *   -- an fp64 group, the slot's or not, without acc_f64 among them -- SKR_ERR_DTYPE.
+ */
+typedef struct skr_step_guidance {
+  const void* cond;     /* device, 16-byte aligned; dtype, shape and layout of inputs[slot] */
+  void* guided_out;     /* device, 16-byte aligned, that dtype; NULL: the guided prediction is not stored */
+  double scale;         /* guidance scale g */
+  int32_t slot;         /* inputs[slot] is uncond; the guided value takes ITS place in the sum */
+  int32_t reserved;     /* 0 */
+} skr_step_guidance;
+
+int skr_step_launch_guided(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                           const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

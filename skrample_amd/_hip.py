@@ -36,6 +36,7 @@ EXPORTS = (
     "skr_step_launch_masked_indexed_per_sample",
     "skr_step_launch_masked_rolling",
     "skr_step_launch_masked_channels_last",
+    "skr_step_launch_guided",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -168,6 +169,18 @@ class StepMaskC(ctypes.Structure):
         ("reserved", ctypes.c_int32),
         ("mask_numel", ctypes.c_int64),
         ("batch_stride", ctypes.c_int64),
+    ]
+
+
+class StepGuidanceC(ctypes.Structure):
+    "mirror of `skr_step_guidance`: the second network output, the scale and the operand a guided step launch replaces"
+
+    _fields_ = [
+        ("cond", ctypes.c_void_p),
+        ("guided_out", ctypes.c_void_p),
+        ("scale", ctypes.c_double),
+        ("slot", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -394,6 +407,8 @@ def load() -> ctypes.CDLL:
             masked_table_launch.restype = ctypes.c_int
         lib.skr_step_launch_masked_channels_last.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, ctypes.POINTER(StepLayoutC), i64, vp]
         lib.skr_step_launch_masked_channels_last.restype = ctypes.c_int
+        lib.skr_step_launch_guided.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp]
+        lib.skr_step_launch_guided.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -577,6 +592,27 @@ def launch_step_masked_channels_last(plan: StepPlanC, operands: list[torch.Tenso
         ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, ctypes.byref(where), numel, current_stream_ptr(device)
     )
     check(status, "skr_step_launch_masked_channels_last")
+
+
+def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, scale: float, slot: int, seeds, numel: int, device: torch.device) -> None:
+    """one guided step launch (skr_step_launch_guided) on torch's current stream of `device`: operands[slot] is `uncond`, and the value
+    p = uncond + scale * (cond - uncond), rounded as torch's three tensor ops round it, takes its place in the step's sum; `guided_out`
+    (or None) receives p.  `out` None with a plan whose out0_dtype is NONE is the guidance-only form.
+    A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, cond, guided_out, scale, slot) -- ten entries no step program
+    is built from.  Under the indexed-rows hook (captured loops with device-resident scalars) it raises: a guided launch has no row form."""
+    lib = load()
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError("guided steps are not part of captured loops: skr_step_launch_guided has no form that reads device-resident rows")
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((plan, list(operands), out, None, seeds, numel, cond, guided_out, scale, slot))
+    n = len(operands)
+    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
+    desc = StepGuidanceC(cond.data_ptr(), guided_out.data_ptr() if guided_out is not None else None, float(scale), int(slot), 0)
+    status = lib.skr_step_launch_guided(
+        ctypes.byref(plan), arr, out.data_ptr() if out is not None else None, ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, numel, current_stream_ptr(device)
+    )
+    check(status, "skr_step_launch_guided")
 
 
 def launch_step_masked_rolling_raw(plan: StepPlanC, arr, out_ptr, mask: StepMaskC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:

@@ -843,6 +843,37 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             done = self._fast_step(model_output, timestep, sample, generator, return_dict)
             if done is not None:
                 return done
+        return self._step_general(model_output, timestep, sample, generator, return_dict, recorded, None)
+
+    # ---- classifier-free guidance (not in the reference) --------------------------------------------------------------------------
+    # The loop around a diffusers-shaped scheduler evaluates the network on a doubled batch and forms, with three tensor ops,
+    #     noise_pred = uncond + guidance_scale * (cond - uncond)
+    # before step() reads it.  step_guided() takes the two halves and the scale instead: for the samplers whose step is one
+    # single-output launch (Euler, DPM, Adams, UniP) the three ops run inside that launch (lazy.evaluate_guided /
+    # skr_step_launch_guided), which also stores the guided prediction that history, pred_original_sample and callbacks read.
+    # Everything else -- the two-output samplers (UniPC, SPC), a step under set_inpaint, compute_scale=None, channels-last or strided
+    # operands -- forms the prediction in one guidance-only launch and steps as ever; host-resident operands and operands that autograd
+    # records form it with torch's own three lines.  Either way prev_sample and pred_original_sample have the bits of
+    # step(uncond + guidance_scale * (cond - uncond), ...) on a wrapper in the same state, and calls of both kinds may be mixed in a run.
+    def step_guided(self, model_output_uncond: Tensor, model_output_cond: Tensor, guidance_scale: float, timestep, sample: Tensor, generator=None, return_dict: bool = True):
+        guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale)
+        recorded = lazy.grad_recorded(model_output_uncond, model_output_cond, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
+        return self._step_general(model_output_uncond, timestep, sample, generator, return_dict, recorded, guidance)
+
+    def _step_general(self, model_output: Tensor, timestep, sample: Tensor, generator, return_dict: bool, recorded: bool, guidance):
+        """the general path of step() and step_guided(): index lookup, alias guard, noise, the sampler's step, history upkeep.
+        `guidance` (step_guided: a lazy.Guidance, and `model_output` is its uncond half, which stands in for the network output
+        wherever only its address, dtype or layout is asked): the prediction is engine-owned -- never cloned -- and the call builds no
+        step program and learns no replayed entry."""
+        inpaint = getattr(self, "_inpaint", None)
+        guided_call = guidance is not None
+        if guided_call:
+            # one launch: a sampler that settles one form through StatedSampler.sample_packed, over contiguous device tensors
+            fused = (type(self.sampler).sample_packed is sampling.StatedSampler.sample_packed and inpaint is None and self.compute_scale is not None
+                          and not recorded and isinstance(sample, Tensor) and sample.is_cuda and sample.is_contiguous()
+                          and model_output.is_contiguous() and guidance.cond.is_contiguous())  # fmt: skip
+            if not fused:
+                guidance, model_output = None, lazy.guide_only(guidance)
         table = self._timestep_table()
         idx = self._lookup(table, timestep, self._index + self._calls)
         if self._calls == 0:
@@ -854,11 +885,16 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         keep = self.sampler.require_previous  # (a computed property: read once per step)
         aliasing = keep > 0 and self._alias_now(model_output, sample)
         if keep > 0 and not aliasing:
-            sample, model_output = sample.clone(), model_output.clone()
+            sample = sample.clone()
+            if not guided_call:  # (a guided prediction is the engine's own tensor)
+                model_output = model_output.clone()
         elif aliasing:
             self._alias_check(model_output, sample)
 
-        prediction = LazyTensor(-Lin.leaf(model_output), model_output.dtype) if self.invert_prediction else model_output
+        if guidance is not None:  # the guided prediction as a leaf of the sampler's form; under invert_prediction just a sign
+            prediction = LazyTensor(-guidance.node() if self.invert_prediction else guidance.node(), model_output.dtype)
+        else:
+            prediction = LazyTensor(-Lin.leaf(model_output), model_output.dtype) if self.invert_prediction else model_output
         if self.invert_prediction and self.compute_scale is None and isinstance(model_output, Tensor) and isinstance(sample, Tensor):
             # no compute scale: the sampler runs the reference's rounded tensor ops on what it is handed (sampling/native.py), and the
             # reference hands it the negated TENSOR (diffusers.py:563-564) -- an exact op, one launch
@@ -888,8 +924,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             tuple((rec.sample is raw, getattr(rec.sample, "dtype", None)) for rec, raw in zip(self._previous, self._raw_samples)),
         )  # fmt: skip
         record = None
-        prog = self._programs.get(key) if not recorded and inpaint is None else False  # (a masked step: no program, no tracing)
+        prog = self._programs.get(key) if not recorded and inpaint is None and not guided_call else False  # (a masked or guided step: no program, no tracing)
         blend = self._inpaint_blend(idx, len(table)) if inpaint is not None else None
+        guide = lazy.GuidedStep(guidance) if guidance is not None else None
         if prog is not None and prog is not False:
             record = prog.run(roles, step, prediction, sample.device)
             if record is not None and self._run_seq and (self._index, idx) not in self._fast:
@@ -901,7 +938,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             try:
                 # (a pending blend is taken up by a sampler whose step is one single-output launch; anything else steps as ever and its result is blended below)
                 one_launch = blend is not None and type(self.sampler).sample_packed is sampling.StatedSampler.sample_packed
-                with lazy.compute_scale(self.compute_scale), (blend if one_launch else contextlib.nullcontext()):
+                with lazy.compute_scale(self.compute_scale), (blend if one_launch else contextlib.nullcontext()), (guide if guide is not None else contextlib.nullcontext()):
                     record = self.sampler.sample_packed(
                         SampleInput(sample=sample, prediction=prediction, step=step, noise=noise),
                         model_transform=self.model,
@@ -910,6 +947,10 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
                     )
                     if blend is not None and not blend.used:
                         record = dataclasses.replace(record, final=blend.settle(lift(record.final), getattr(record.final, "dtype", None)))
+                if guide is not None:
+                    # the record that goes into history holds the stored tensor, as the unfused run's does (negated lazily under invert_prediction)
+                    model_output = guide.guided if guide.used else lazy.guide_only(guidance)
+                    record = dataclasses.replace(record, prediction=LazyTensor(-Lin.leaf(model_output), model_output.dtype) if self.invert_prediction else model_output)
                 if tracing:
                     built = program.StepProgram.build(_hip.trace[0], roles, record, prediction) if len(_hip.trace) == 1 else None
                     self._programs[key] = built if built is not None else False

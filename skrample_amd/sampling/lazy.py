@@ -123,6 +123,39 @@ class RoundedConversion:
         return self
 
 
+class Guidance:
+    """The classifier-free-guidance prediction  uncond + scale * (cond - uncond)  as ONE leaf of a step's form: its value is torch's --
+    three tensor ops, each rounded in the tensors' dtype, the Python scalar kept in the op-math type -- and `evaluate_guided` computes
+    it inside the launch that consumes it (include/skrample_hip.h, skr_step_launch_guided).  `node()` is a `Lin` leaf, as
+    `RoundedConversion.node()` is: a sampler's algebra carries it wherever the prediction stands, with whatever coefficient it gets."""
+
+    def __init__(self, uncond: torch.Tensor, cond: torch.Tensor, scale: float):
+        if not isinstance(uncond, torch.Tensor) or not isinstance(cond, torch.Tensor):
+            raise SkrampleHipError(f"guidance takes two torch tensors, not {type(uncond).__name__} and {type(cond).__name__}")
+        _check_tensor(uncond), _check_tensor(cond)
+        if uncond.dtype != cond.dtype or uncond.shape != cond.shape or uncond.device != cond.device:
+            raise SkrampleHipError(
+                f"guidance needs uncond and cond of one dtype, shape and device: {uncond.dtype} {tuple(uncond.shape)} {uncond.device} vs {cond.dtype} {tuple(cond.shape)} {cond.device}"
+            )
+        if isinstance(scale, bool) or not isinstance(scale, NUMBER):
+            raise SkrampleHipError(f"the guidance scale is a Python number, not {type(scale).__name__}")
+        self.uncond, self.cond, self.scale = uncond, cond, float(scale)
+        self.shape, self.device, self.dtype = tuple(uncond.shape), uncond.device, uncond.dtype
+
+    def node(self) -> "Lin":
+        n = Node(self)
+        return Lin({id(n): (n, 1.0)}, self.shape, self.device)
+
+    def expanded(self, keep=None):
+        return self
+
+    def torch_lines(self) -> torch.Tensor:
+        "the pipeline's three lines, by torch itself (host-resident operands; operands that autograd records)"
+        d = self.cond - self.uncond
+        m = self.scale * d
+        return self.uncond + m
+
+
 def _check_tensor(t: torch.Tensor) -> torch.Tensor:
     if t.device.type not in ("cuda", "cpu"):
         _hip.require_device(t, "sampler operand")
@@ -242,6 +275,8 @@ class Lin:
             if isinstance(leaf, Node) and leaf.form is not keep:
                 if isinstance(leaf.form, RoundedConversion):
                     raise SkrampleHipError("a rounded conversion can only be consumed by the launch that stores it")
+                if isinstance(leaf.form, Guidance):
+                    raise SkrampleHipError("a guided prediction is not a linear form: it is settled by evaluate_guided()")
                 acc = acc._plus(leaf.form.expanded(keep)._scaled(c), 1.0)
             else:
                 acc = acc._plus(Lin({i: (leaf, c)}, self.shape, self.device), 1.0)
@@ -707,6 +742,96 @@ class MaskedBlend:
 def pending_blend() -> "MaskedBlend | None":
     blend = _pending_blend.get()
     return blend if blend is not None and not blend.used else None
+
+
+# ---- guided steps (classifier-free guidance): the three torch lines in front of a step, inside its launch ----------------------------
+def guide_only(guidance: Guidance) -> torch.Tensor:
+    """the guided prediction as a tensor of its own, with torch's bits: one guidance-only launch of skr_step_launch_guided on the HIP
+    device (uncond and cond in one dense channels-last layout: on the storage order as it stands, the result channels-last); torch's own
+    three lines for host-resident operands and for operands that autograd records (torch records them)."""
+    u, c = guidance.uncond, guidance.cond
+    if is_host(guidance.device) or grad_recorded(u, c):
+        return guidance.torch_lines()
+    if channels_last and _hip.indexed is None and shared_layout((u, c), guidance.shape) is not None:
+        u, c = _prepare_keeping_layout(u), _prepare_keeping_layout(c)
+        out = empty_output_channels_last(guidance.shape, guidance.dtype, guidance.device)
+    else:
+        u, c = _prepare_tensor(u), _prepare_tensor(c)
+        out = empty_output(guidance.shape, guidance.dtype, guidance.device)
+    plan = _hip.StepPlanC()
+    plan.n_terms = plan.n_group_a = 1
+    plan.dtype_a = plan.dtype_b = _hip.DTYPE_CODE[guidance.dtype]
+    plan.out0_dtype = plan.out1_dtype = _hip.NONE
+    plan.acc_f64 = 1 if guidance.dtype == torch.float64 else 0
+    plan.coef0[0] = 1.0
+    _hip.launch_step_guided(plan, [u], None, c, out, guidance.scale, 0, None, math.prod(guidance.shape), guidance.device)
+    return out
+
+
+def evaluate_guided(form: Lin, guidance: Guidance, dtype: torch.dtype | None = None, acc_f64: bool | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(final, guided): `form`, which holds `guidance.node()` wherever the prediction stands, and the guided prediction itself, in ONE
+    launch (skr_step_launch_guided).  The node is lowered as the operand `uncond` at its natural position in the operand list -- that
+    position is the launch's `slot` -- so `final` has the bits of evaluate() over the form with the tensor `guided` in the node's place,
+    and `guided` the bits of torch's three lines.
+    What the one launch does not cover takes the guidance-only launch (`guide_only`) and then evaluate(): contiguous copies would be
+    needed (channels-last or strided operands), the node's coefficient is zero, `uncond` is an operand of the form in its own right or
+    is cast to another dtype group, or the form has more than 16 operands.  Host-resident operands and operands that autograd records
+    evaluate the three lines with torch and then the existing executors.  Mixed residency is refused as everywhere."""
+    f = lift(form)
+    if not isinstance(f, Lin) or not isinstance(guidance, Guidance):
+        raise SkrampleHipError("evaluate_guided() takes a tensor form and a Guidance")
+    f = f.expanded(keep=guidance)
+    if any(isinstance(leaf, Node) and leaf.form is not guidance for leaf, _ in f.terms.values()):
+        raise SkrampleHipError("a guided launch has one step output: its form cannot refer to another stored form")
+    if f.shape != guidance.shape:
+        raise SkrampleHipError(f"shape mismatch between the step form {f.shape} and the guidance operands {guidance.shape}")
+    leaves = [leaf for leaf, _ in f.terms.values() if isinstance(leaf, torch.Tensor)]
+    host = [is_host(t.device) for t in (*leaves, guidance.uncond)] + ([True] if f.device == NUMPY else [])
+    if any(host) and not all(host):
+        raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
+    out_dtype = dtype if dtype is not None else guidance.dtype
+    u, c = guidance.uncond, guidance.cond
+    fused = not any(host) and not grad_recorded(*leaves, u, c) and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (*leaves, u, c))
+    fused = fused and id(u) not in f.terms and any(isinstance(leaf, Node) and k != 0.0 for leaf, k in f.terms.values())
+    if fused:
+        plan, operands, seeds = _lower(None, f.substitute(guidance, u), None, 0.0, [out_dtype], acc_f64)
+        slot = next((k for k, t in enumerate(operands) if t is u), None)
+        if slot is not None and len(operands) <= _hip.ROW_TERMS:
+            final = empty_output(f.shape, out_dtype, guidance.device)
+            guided = empty_output(f.shape, guidance.dtype, guidance.device)
+            _hip.launch_step_guided(plan, operands, final, c, guided, guidance.scale, slot, seeds, math.prod(f.shape), guidance.device)
+            return final, guided
+    guided = guide_only(guidance)
+    return evaluate([f.substitute(guidance, guided)], [out_dtype], acc_f64)[0], guided
+
+
+# The guidance a scheduler wrapper has pending for the step it is about to take (SkrampleWrapperScheduler.step_guided): a sampler whose
+# step is one single-output launch settles its form through it (StatedSampler.sample_packed), which makes that launch the guided one.
+_pending_guidance: contextvars.ContextVar = contextvars.ContextVar("skr_pending_guidance", default=None)
+
+
+class GuidedStep:
+    "context manager: `with GuidedStep(guidance): sampler.sample_packed(...)`; taken up at most once, and keeps the stored prediction"
+
+    def __init__(self, guidance: Guidance):
+        self.guidance, self.used, self.guided = guidance, False, None
+
+    def __enter__(self):
+        self.token = _pending_guidance.set(self)
+        return self
+
+    def __exit__(self, *exc):
+        _pending_guidance.reset(self.token)
+
+    def settle(self, form: Lin, dtype: torch.dtype | None) -> torch.Tensor:
+        self.used = True
+        final, self.guided = evaluate_guided(form, self.guidance, dtype)
+        return final
+
+
+def pending_guidance() -> "GuidedStep | None":
+    pending = _pending_guidance.get()
+    return pending if pending is not None and not pending.used else None
 
 
 def _host_evaluate_masked(f0: "Lin", f1: "Lin", mask: torch.Tensor, out_dtype: torch.dtype, acc_f64) -> torch.Tensor:

@@ -117,8 +117,11 @@ class StatedSampler(StructuredSampler):
             return record
         form = self._form(packed, model_transform, schedule, previous)
         blend = lazy.pending_blend()  # in-painting: the step's one launch is the masked launch (lazy.evaluate_masked)
+        guided = lazy.pending_guidance()  # classifier-free guidance: the step's one launch is the guided launch (lazy.evaluate_guided)
         if blend is not None and isinstance(form, Lin):
             final = blend.settle(form, _result_dtype(packed.sample))
+        elif guided is not None and isinstance(form, Lin):
+            final = guided.settle(form, _result_dtype(packed.sample))
         else:
             final = lazy.settle(form, dtype=_result_dtype(packed.sample))
         return SKSamples(packed.sample, packed.prediction, packed.step, packed.noise, final)

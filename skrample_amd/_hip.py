@@ -505,93 +505,63 @@ def current_stream_ptr(device: torch.device) -> int:
 # samplers emit and replay them through the C ABI.
 
 
-def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, numel: int, device: torch.device) -> None:
-    "one fused kernel launch on torch's current stream of `device`"
-    load()
-    trace = getattr(_hooks, "trace", None)
-    if trace is not None:
-        trace.append((plan, list(inputs), out0, out1, seeds, numel))
-    n = len(inputs)
-    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in inputs])
-    status = step_launch_raw(
-        plan,
-        arr,
-        out0.data_ptr() if out0 is not None else None,
-        out1.data_ptr() if out1 is not None else None,
-        seeds.data_ptr() if seeds is not None else None,
-        numel,
-        current_stream_ptr(device),
-    )
-    check(status, "skr_step_launch")
+def _ptr(t):
+    "`data_ptr()` of a tensor, None (a NULL argument) for None"
+    return t.data_ptr() if t is not None else None
 
 
-def launch_step_channels_last(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, layout: tuple[int, int], numel: int, device: torch.device) -> None:
-    """one fused launch over operands and outputs that all share the dense channels-last `layout` = (channels, plane)
-    (skr_step_launch_channels_last) on torch's current stream of `device`.  The `_hip.trace` entry is launch_step's: the layout is read
-    off the tensors.  The indexed-rows hook has no channels-last form: the caller takes the contiguous route while one is installed."""
-    lib = load()
-    if getattr(_hooks, "indexed", None) is not None:
+def _operand_array(tensors):
+    "the operand pointer array of a step launch"
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+
+
+def _no_rows_with_layout(layout) -> None:
+    "the indexed-rows hook has no channels-last form: the caller takes the contiguous route while one is installed"
+    if layout is not None and getattr(_hooks, "indexed", None) is not None:
         raise SkrampleHipError("captured loops with device-resident rows take contiguous operands")
+
+
+def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, numel: int, device: torch.device, layout: tuple[int, int] | None = None) -> None:
+    """one fused kernel launch on torch's current stream of `device`.  With `layout` = (channels, plane) the operands and outputs all share
+    that dense channels-last layout (skr_step_launch_channels_last); the `_hip.trace` entry is the same: the layout is read off the tensors."""
+    lib = load()
+    _no_rows_with_layout(layout)
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append((plan, list(inputs), out0, out1, seeds, numel))
-    n = len(inputs)
-    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in inputs])
-    desc = StepLayoutC(layout[0], layout[1])
-    status = lib.skr_step_launch_channels_last(
-        ctypes.byref(plan),
-        arr,
-        out0.data_ptr() if out0 is not None else None,
-        out1.data_ptr() if out1 is not None else None,
-        seeds.data_ptr() if seeds is not None else None,
-        ctypes.byref(desc),
-        numel,
-        current_stream_ptr(device),
-    )
-    check(status, "skr_step_launch_channels_last")
+    arr, stream = _operand_array(inputs), current_stream_ptr(device)
+    if layout is None:
+        check(step_launch_raw(plan, arr, _ptr(out0), _ptr(out1), _ptr(seeds), numel, stream), "skr_step_launch")
+    else:
+        status = lib.skr_step_launch_channels_last(ctypes.byref(plan), arr, _ptr(out0), _ptr(out1), _ptr(seeds), ctypes.byref(StepLayoutC(*layout)), numel, stream)
+        check(status, "skr_step_launch_channels_last")
 
 
-def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device) -> None:
+def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device,
+                       layout: tuple[int, int] | None = None) -> None:
     """one masked step launch (skr_step_launch_masked) on torch's current stream of `device`: out = m * (coef0 form + noise) + (1 - m) * (coef1 form).
     A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, mask) -- a seventh entry no step program is built from.
     Under the indexed-rows hook (captured loops with device-resident scalars) the launch is recorded, emitted as
-    skr_step_launch_masked_indexed[_per_sample] or refilled, as a plain step launch is (IndexedRows.launch)."""
+    skr_step_launch_masked_indexed[_per_sample] or refilled, as a plain step launch is (IndexedRows.launch).
+    With `layout` = (channels, plane) the operands and the output all share that dense channels-last layout
+    (skr_step_launch_masked_channels_last); `mask` stays contiguous, in logical order, and the trace entry is the same."""
     lib = load()
+    _no_rows_with_layout(layout)
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append((plan, list(operands), out, None, seeds, numel, mask))
-    n = len(operands)
-    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
+    arr, stream = _operand_array(operands), current_stream_ptr(device)
     desc = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
-    seeds_ptr = seeds.data_ptr() if seeds is not None else None
+    if layout is not None:
+        status = lib.skr_step_launch_masked_channels_last(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), _ptr(seeds), ctypes.byref(StepLayoutC(*layout)), numel, stream)
+        check(status, "skr_step_launch_masked_channels_last")
+        return
     rows = getattr(_hooks, "indexed", None)
     if rows is not None:
-        status = rows.launch(lib, plan, arr, out.data_ptr(), None, seeds_ptr, numel, current_stream_ptr(device), mask=desc)
+        status = rows.launch(lib, plan, arr, out.data_ptr(), None, _ptr(seeds), numel, stream, mask=desc)
     else:
-        status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds_ptr, numel, current_stream_ptr(device))
+        status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), _ptr(seeds), numel, stream)
     check(status, "skr_step_launch_masked")
-
-
-def launch_step_masked_channels_last(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds,
-                                      layout: tuple[int, int], numel: int, device: torch.device) -> None:
-    """one masked step launch over operands and an output that all share the dense channels-last `layout` = (channels, plane)
-    (skr_step_launch_masked_channels_last) on torch's current stream of `device`; `mask` is contiguous, in logical order.  The
-    `_hip.trace` entry is launch_step_masked's seven-entry tuple: the layout is read off the tensors.  The indexed-rows hook has no
-    channels-last form: the caller takes the contiguous route while one is installed."""
-    lib = load()
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError("captured loops with device-resident rows take contiguous operands")
-    trace = getattr(_hooks, "trace", None)
-    if trace is not None:
-        trace.append((plan, list(operands), out, None, seeds, numel, mask))
-    n = len(operands)
-    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
-    desc = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
-    where = StepLayoutC(layout[0], layout[1])
-    status = lib.skr_step_launch_masked_channels_last(
-        ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, ctypes.byref(where), numel, current_stream_ptr(device)
-    )
-    check(status, "skr_step_launch_masked_channels_last")
 
 
 def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, scale: float, slot: int, seeds, numel: int, device: torch.device) -> None:
@@ -606,12 +576,8 @@ def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond:
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append((plan, list(operands), out, None, seeds, numel, cond, guided_out, scale, slot))
-    n = len(operands)
-    arr = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in operands])
-    desc = StepGuidanceC(cond.data_ptr(), guided_out.data_ptr() if guided_out is not None else None, float(scale), int(slot), 0)
-    status = lib.skr_step_launch_guided(
-        ctypes.byref(plan), arr, out.data_ptr() if out is not None else None, ctypes.byref(desc), seeds.data_ptr() if seeds is not None else None, numel, current_stream_ptr(device)
-    )
+    desc = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
+    status = lib.skr_step_launch_guided(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(desc), _ptr(seeds), numel, current_stream_ptr(device))
     check(status, "skr_step_launch_guided")
 
 

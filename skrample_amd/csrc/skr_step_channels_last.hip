@@ -6,7 +6,7 @@
 // itself; a launch that draws takes one of the two kernels of this file, which give every position the bits skr_step_launch gives
 // its logical element.
 #include "skr_device.h"
-#include "skr_step_common.h"
+#include "skr_channels_last.h"
 #include <atomic>
 
 namespace skr {
@@ -15,16 +15,8 @@ std::atomic<int64_t> g_cl_one_trip_launches{0}, g_cl_general_launches{0};  // sk
 
 // ---- one-trip kernel ---------------------------------------------------------------------------------------------------------------
 // step_kernel_k1's unpaced Kernarg form (skr_step_fast.hip) -- a lane owns one 16-byte vector of 8 storage elements, XCD chunk map,
-// every load first, scalars and Philox while they are in flight, store8 -- with the draw distributed over lane groups.
-// A Philox block is 4 consecutive pixels of one channel (plane % 4 == 0), and a lane's vector is
-//   C = 4   two pixels x 4 channels       C = 8   one pixel x 8 channels       C = 16  half a pixel (8 of its 16 channels)
-// so G = C / 2 adjacent lanes own 4 pixels x C channels = C blocks: two per lane, the contiguous kernel's count.  Each lane draws two
-// WHOLE blocks (channels ch0 and ch0 + 1 of the group's pixel quad) and the group exchanges normals in registers:
-//   C = 8   lane j of 4 draws channels 2j, 2j+1 and needs pixel j of all 8: per block a 4x4 transpose over lane bits 0 and 1
-//   C = 16  the 4 lanes that hold the same channel half (lane bit 0) transpose among themselves, over lane bits 1 and 2
-//   C = 4   lane j of 2 draws channels 2j, 2j+1 and needs pixels 2j, 2j+1 of all 4: it swaps two normals of each block with its neighbour
-// Lane bits 0 and 1 are crossed with DPP quad permutes (full-rate VALU moves), bit 2 with ds_swizzle (the LDS crossbar, no LDS memory).
-// The register index a normal lands in depends on the lane, so every exchange is framed by v_cndmask selects: 16 per transpose.
+// every load first, scalars and Philox while they are in flight, store8 -- with the draw distributed over lane groups (cl_draw8,
+// skr_channels_last.h).
 template <int KMAX>
 struct ClOneTripArgs {
   const void* in[KMAX];
@@ -37,33 +29,6 @@ struct ClOneTripArgs {
   float zeta0;
   uint32_t quads;       // plane / 4: Philox blocks per channel
 };
-
-template <int M>
-__device__ __forceinline__ float lane_xor(float x) {  // the value of lane ^ M (M = 1, 2, 4; every lane of the wave is active)
-  const int i = __builtin_bit_cast(int, x);
-  int r;
-  if constexpr (M == 1) r = __builtin_amdgcn_update_dpp(i, i, 0xB1, 0xF, 0xF, false);       // quad_perm:[1,0,3,2]
-  else if constexpr (M == 2) r = __builtin_amdgcn_update_dpp(i, i, 0x4E, 0xF, 0xF, false);  // quad_perm:[2,3,0,1]
-  else r = __builtin_amdgcn_ds_swizzle(i, 0x101F);  // bit-mask mode: and 0x1f, or 0, xor 4
-  return __builtin_bit_cast(float, r);
-}
-
-// one butterfly stage: lanes that differ in the bit `up` tests exchange a[i + S] (bit clear) for a[i] (bit set)
-template <int M, int S>
-__device__ __forceinline__ void butterfly(float a[4], bool up, int i) {
-  const float keep = up ? a[i + S] : a[i];
-  const float got = lane_xor<M>(up ? a[i] : a[i + S]);
-  a[i] = up ? got : keep;
-  a[i + S] = up ? keep : got;
-}
-// 4x4 transpose over the four lanes spanned by lane bits M1 (lo) and M2 (hi): a[k] becomes element 2*hi + lo of lane k's a
-template <int M1, int M2>
-__device__ __forceinline__ void transpose4(float a[4], bool lo, bool hi) {
-  butterfly<M1, 1>(a, lo, 0);
-  butterfly<M1, 1>(a, lo, 2);
-  butterfly<M2, 2>(a, hi, 0);
-  butterfly<M2, 2>(a, hi, 1);
-}
 
 template <typename T, int K, int C>
 __global__ __launch_bounds__(BLOCK) void step_kernel_cl1(const ClOneTripArgs<(K <= 4 ? 4 : 8)> a) {
@@ -83,40 +48,8 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_cl1(const ClOneTripArgs<(K 
   sample_of(c, a.bps_shift, smp, within);
   const uint64_t seed = a.seeds[smp];
   const uint32_t vs = within * BLOCK + threadIdx.x;  // lane-vector within the sample
-  // (the lane's place in its group is in threadIdx's low bits: BLOCK is a multiple of every group size)
-  const uint32_t t = threadIdx.x;
-  constexpr int LG = C == 4 ? 1 : (C == 8 ? 2 : 3);  // log2(lanes per group)
-  const uint32_t quad = vs >> LG;                    // the group's pixel quad: pixels 4 quad .. 4 quad + 3
-  // The lane draws channels ch0 and ch0 + 1 of that quad: ch0 = 2 (t & 1) for C = 4, 2 (t & 3) for C = 8, 8 (t & 1) + 2 ((t >> 1) & 3) for
-  // C = 16.  Block ch0 * quads + quad, put together from scalar multiples of `quads` chosen by the lane's bits: a vector multiply here
-  // would be one more full-width multiply than the contiguous kernel spends.
-  // (sample_numel / 4 fits 32 bits: the host sends larger samples to the general kernel)
-  const uint32_t q2 = a.quads * 2, q4 = a.quads * 4, q8 = a.quads * 8;
-  uint32_t blk = quad;
-  if constexpr (C == 16) blk += ((t & 1) ? q8 : 0u) + ((t & 2) ? q2 : 0u) + ((t & 4) ? q4 : 0u);
-  else blk += ((t & 1) ? q2 : 0u) + ((C == 8 && (t & 2)) ? q4 : 0u);
-  float za[4], zb[4], z[VEC];
-  normal4(seed, stream0, (uint64_t)blk, za);
-  normal4(seed, stream0, (uint64_t)(blk + a.quads), zb);
-  if constexpr (C == 4) {
-    // storage order of the vector: pixel 2j + pl (pl = 0, 1), channels 0..3; own channels 2j + b, the neighbour's 2(1 - j) + b
-    const bool up = (t & 1) != 0;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      const float keep_a = up ? za[2 + pl] : za[pl], keep_b = up ? zb[2 + pl] : zb[pl];
-      const float got_a = lane_xor<1>(up ? za[pl] : za[2 + pl]), got_b = lane_xor<1>(up ? zb[pl] : zb[2 + pl]);
-      z[4 * pl + 0] = up ? got_a : keep_a;
-      z[4 * pl + 1] = up ? got_b : keep_b;
-      z[4 * pl + 2] = up ? keep_a : got_a;
-      z[4 * pl + 3] = up ? keep_b : got_b;
-    }
-  } else {
-    // after the transposes za[k] / zb[k] hold this lane's pixel of the channels lane k of the group drew: storage offsets 2k, 2k + 1
-    if constexpr (C == 8) { transpose4<1, 2>(za, (t & 1) != 0, (t & 2) != 0); transpose4<1, 2>(zb, (t & 1) != 0, (t & 2) != 0); }
-    else { transpose4<2, 4>(za, (t & 2) != 0, (t & 4) != 0); transpose4<2, 4>(zb, (t & 2) != 0, (t & 4) != 0); }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { z[2 * k] = za[k]; z[2 * k + 1] = zb[k]; }
-  }
+  float z[VEC];
+  cl_draw8<C>(seed, stream0, a.quads, vs, threadIdx.x, z);
   float s[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) s[i] = 0.f;
@@ -184,11 +117,15 @@ __global__ __launch_bounds__(BLOCK) void step_kernel_cl(const ClGeneralArgs<Acc>
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-int channels_last_checks(const skr_step_plan& p, const skr_step_layout* layout) {
+int layout_check(const skr_step_plan& p, const skr_step_layout* layout) {
   if (!layout) return SKR_ERR_NULL;
-  if (layout->channels < 1 || layout->plane < 1 || p.sample_numel < 1 || p.sample_numel % layout->channels != 0 ||
-      p.sample_numel / layout->channels != layout->plane)
-    return SKR_ERR_SHAPE;
+  if (layout->channels < 1 || layout->plane < 1 || p.sample_numel % layout->channels != 0 || p.sample_numel / layout->channels != layout->plane)
+    return SKR_ERR_SHAPE;  // (this refuses every sample_numel < 1 as well)
+  return SKR_OK;
+}
+
+int channels_last_checks(const skr_step_plan& p, const skr_step_layout* layout) {
+  if (const int rc = layout_check(p, layout)) return rc;
   if (plan_draws(p) && (p.convert_to != 0 || p.convert_from != 0)) return SKR_ERR_UNSUPPORTED;
   return SKR_OK;
 }
@@ -196,16 +133,9 @@ int channels_last_checks(const skr_step_plan& p, const skr_step_layout* layout) 
 // layout plays no part: no draw, or a sample whose storage order is its logical order
 static bool layout_blind(const skr_step_plan& p, const skr_step_layout& l) { return !plan_draws(p) || l.channels == 1 || l.plane == 1; }
 
-// what the one-trip kernel takes (the header's list)
+// what the one-trip kernel takes (the header's list): one output, and a sample whose Philox block numbers fit 32 bits
 static bool cl_one_trip_ok(const skr_step_plan& p, const skr_step_layout& l, int64_t numel, int* bps_shift) {
-  constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
-  const int32_t db = p.n_group_a == p.n_terms ? p.dtype_a : p.dtype_b;
-  if (!g_tune.one_trip || p.acc_f64 || p.out1_dtype != SKR_NONE || p.n_terms < 1 || p.n_terms > 8) return false;
-  if ((p.dtype_a != SKR_BF16 && p.dtype_a != SKR_F16) || db != p.dtype_a || p.out0_dtype != p.dtype_a) return false;
-  if ((l.channels != 4 && l.channels != 8 && l.channels != 16) || l.plane % 4 != 0) return false;
-  if (numel % CHUNK != 0 || numel / CHUNK > 0x7fffffffll || p.sample_numel % CHUNK != 0 || p.sample_numel > (1ll << 32)) return false;
-  *bps_shift = bps_shift_of(p.sample_numel / CHUNK);
-  return true;
+  return p.out1_dtype == SKR_NONE && cl_one_trip_geometry(p, l, numel, 1ll << 32, bps_shift);
 }
 
 template <typename T>
@@ -221,9 +151,7 @@ static int launch_cl1(const skr_step_plan& p, const skr_step_layout& l, const vo
     fa.out0 = out0; fa.seeds = seeds; fa.zeta0 = (float)p.zeta0; fa.stream0 = p.stream0;
     fa.bps_shift = bps_shift; fa.xmap_lr = xmap_lr_for(chunks); fa.quads = (uint32_t)(l.plane / 4);
     const dim3 grid((unsigned)chunks), block(BLOCK);
-    if (l.channels == 4) hipLaunchKernelGGL((step_kernel_cl1<T, N, 4>), grid, block, 0, stream, fa);
-    else if (l.channels == 8) hipLaunchKernelGGL((step_kernel_cl1<T, N, 8>), grid, block, 0, stream, fa);
-    else hipLaunchKernelGGL((step_kernel_cl1<T, N, 16>), grid, block, 0, stream, fa);
+    with_channels(l.channels, [&](auto c) { hipLaunchKernelGGL((step_kernel_cl1<T, N, decltype(c)::value>), grid, block, 0, stream, fa); });
   });
   return finish_launch();
 }

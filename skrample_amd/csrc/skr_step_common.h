@@ -467,7 +467,9 @@ static inline bool plan_draws(const skr_step_plan& p) { return p.noise_mode == 1
 // the checks every step launch makes, in their order (skr_step.hip); `empty`: numel == 0, nothing to launch
 int step_launch_checks(const skr_step_plan* plan, const void* const* inputs, void* out0, void* out1, const uint64_t* seeds_dev, int64_t numel,
                        RowForm form, const skr_step_row* rows, const int32_t* index, bool& empty);
-// what a channels-last launch checks on top of them (skr_step_channels_last.hip)
+// what a channels-last launch checks on top of them (skr_step_channels_last.hip): the layout against the plan's sample (every
+// channels-last entry), and with it that a drawing plan has no rounded conversion (the plain launch and its program)
+int layout_check(const skr_step_plan& plan, const skr_step_layout* layout);
 int channels_last_checks(const skr_step_plan& plan, const skr_step_layout* layout);
 
 // ---- host side: run-time values to template arguments, kernarg packing -------------------------------------------------------------

@@ -11,93 +11,17 @@
 // channels == 1 or plane == 1 is skr_step_launch_masked itself.  There are no row forms here.
 #include "skr_step_masked.h"
 #include "skr_device.h"
+#include "skr_channels_last.h"
 #include <atomic>
 
 namespace skr {
 
 std::atomic<int64_t> g_mcl_one_trip_launches{0}, g_mcl_general_launches{0};  // skr_stat("masked_channels_last_one_trip" / "..._general")
 
-// ---- the draw of a lane's 8 storage elements, spread over lane groups -----------------------------------------------------------------
-// step_kernel_cl1's exchange (skr_step_channels_last.hip), as a copy of this file's own: with the sequence in a header that both files
-// include, 10 instantiations of step_kernel_cl1 came out with other registers (tools/isa_compare.py against the parent), so that file
-// stays as it is.
-// A Philox block is 4 consecutive pixels of one channel (plane % 4 == 0), and a lane's vector is
-//   C = 4   two pixels x 4 channels       C = 8   one pixel x 8 channels       C = 16  half a pixel (8 of its 16 channels)
-// so G = C / 2 adjacent lanes own 4 pixels x C channels = C blocks: two per lane, the contiguous kernel's count.  Each lane draws two
-// WHOLE blocks (channels ch0 and ch0 + 1 of the group's pixel quad) and the group exchanges normals in registers: a 4x4 transpose per
-// block over lane bits 0 and 1 (C = 8) or 1 and 2 (C = 16), a swap of two normals per block with the neighbour lane (C = 4).
-// Lane bits 0 and 1 are crossed with DPP quad permutes, bit 2 with ds_swizzle (the LDS crossbar, no LDS memory).
-template <int M>
-__device__ __forceinline__ float lane_xor(float x) {  // the value of lane ^ M (M = 1, 2, 4; every lane of the wave is active)
-  const int i = __builtin_bit_cast(int, x);
-  int r;
-  if constexpr (M == 1) r = __builtin_amdgcn_update_dpp(i, i, 0xB1, 0xF, 0xF, false);       // quad_perm:[1,0,3,2]
-  else if constexpr (M == 2) r = __builtin_amdgcn_update_dpp(i, i, 0x4E, 0xF, 0xF, false);  // quad_perm:[2,3,0,1]
-  else r = __builtin_amdgcn_ds_swizzle(i, 0x101F);  // bit-mask mode: and 0x1f, or 0, xor 4
-  return __builtin_bit_cast(float, r);
-}
-
-// one butterfly stage: lanes that differ in the bit `up` tests exchange a[i + S] (bit clear) for a[i] (bit set)
-template <int M, int S>
-__device__ __forceinline__ void butterfly(float a[4], bool up, int i) {
-  const float keep = up ? a[i + S] : a[i];
-  const float got = lane_xor<M>(up ? a[i] : a[i + S]);
-  a[i] = up ? got : keep;
-  a[i + S] = up ? keep : got;
-}
-// 4x4 transpose over the four lanes spanned by lane bits M1 (lo) and M2 (hi): a[k] becomes element 2*hi + lo of lane k's a
-template <int M1, int M2>
-__device__ __forceinline__ void transpose4(float a[4], bool lo, bool hi) {
-  butterfly<M1, 1>(a, lo, 0);
-  butterfly<M1, 1>(a, lo, 2);
-  butterfly<M2, 2>(a, hi, 0);
-  butterfly<M2, 2>(a, hi, 1);
-}
-
-// The normals of the 8 storage elements of lane-vector `vs` of a sample (t = threadIdx.x: the lane's place in its group is in its low
-// bits, BLOCK being a multiple of every group size; quads = plane / 4, the Philox blocks per channel): z[i] is the normal of logical
-// element l(8 vs + i).  Every lane of the wave must be active.
-template <int C>
-__device__ __forceinline__ void cl_draw8(uint64_t seed, uint64_t stream0, uint32_t quads, uint32_t vs, uint32_t t, float z[VEC]) {
-  static_assert(C == 4 || C == 8 || C == 16, "lane groups of 2, 4 or 8");
-  constexpr int LG = C == 4 ? 1 : (C == 8 ? 2 : 3);  // log2(lanes per group)
-  const uint32_t quad = vs >> LG;                    // the group's pixel quad: pixels 4 quad .. 4 quad + 3
-  // The lane draws channels ch0 and ch0 + 1 of that quad: ch0 = 2 (t & 1) for C = 4, 2 (t & 3) for C = 8, 8 (t & 1) + 2 ((t >> 1) & 3) for
-  // C = 16.  Block ch0 * quads + quad, put together from scalar multiples of `quads` chosen by the lane's bits: a vector multiply here
-  // would be one more full-width multiply than the contiguous kernel spends.
-  // (sample_numel / 4 fits 32 bits: the host sends larger samples to the general kernel)
-  const uint32_t q2 = quads * 2, q4 = quads * 4, q8 = quads * 8;
-  uint32_t blk = quad;
-  if constexpr (C == 16) blk += ((t & 1) ? q8 : 0u) + ((t & 2) ? q2 : 0u) + ((t & 4) ? q4 : 0u);
-  else blk += ((t & 1) ? q2 : 0u) + ((C == 8 && (t & 2)) ? q4 : 0u);
-  float za[4], zb[4];
-  normal4(seed, stream0, (uint64_t)blk, za);
-  normal4(seed, stream0, (uint64_t)(blk + quads), zb);
-  if constexpr (C == 4) {
-    // storage order of the vector: pixel 2j + pl (pl = 0, 1), channels 0..3; own channels 2j + b, the neighbour's 2(1 - j) + b
-    const bool up = (t & 1) != 0;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      const float keep_a = up ? za[2 + pl] : za[pl], keep_b = up ? zb[2 + pl] : zb[pl];
-      const float got_a = lane_xor<1>(up ? za[pl] : za[2 + pl]), got_b = lane_xor<1>(up ? zb[pl] : zb[2 + pl]);
-      z[4 * pl + 0] = up ? got_a : keep_a;
-      z[4 * pl + 1] = up ? got_b : keep_b;
-      z[4 * pl + 2] = up ? keep_a : got_a;
-      z[4 * pl + 3] = up ? keep_b : got_b;
-    }
-  } else {
-    // after the transposes za[k] / zb[k] hold this lane's pixel of the channels lane k of the group drew: storage offsets 2k, 2k + 1
-    if constexpr (C == 8) { transpose4<1, 2>(za, (t & 1) != 0, (t & 2) != 0); transpose4<1, 2>(zb, (t & 1) != 0, (t & 2) != 0); }
-    else { transpose4<2, 4>(za, (t & 2) != 0, (t & 4) != 0); transpose4<2, 4>(zb, (t & 2) != 0, (t & 4) != 0); }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { z[2 * k] = za[k]; z[2 * k + 1] = zb[k]; }
-  }
-}
-
 // ---- one-trip kernel ---------------------------------------------------------------------------------------------------------------
 // step_kernel_cl1 (skr_step_channels_last.hip) with masked_kernel_v1's two coefficient sets: a lane owns one 16-byte vector of 8 storage
 // elements, XCD chunk map, every operand load first and the mask load right behind them, the scalars and the Philox rounds while they
-// are in flight, the draw exchanged over lane groups (cl_draw8), store8.
+// are in flight, the draw exchanged over lane groups (cl_draw8, skr_channels_last.h), store8.
 // The mask is indexed by pixel.  A lane's vector is two pixels (C = 4), one pixel (C = 8) or half a pixel (C = 16), so a lane needs two
 // mask elements or one: one 32-bit load of two 16-bit elements at C = 4 (mask_numel is even, so pixels 2 vs and 2 vs + 1 never straddle
 // a wrap, and the address is 4-byte aligned), one 16-bit load otherwise.  Plain loads, not non-temporal ones: neighbouring lanes share
@@ -217,17 +141,11 @@ __global__ __launch_bounds__(BLOCK) void masked_kernel_cl(const MaskedClGenArgs 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-// what the one-trip kernel takes (the header's list)
+// what the one-trip kernel takes (the header's list): the shared geometry with sample_numel < 2^31, and a mask of the tensors' dtype
+// with an even element count that divides the plane
 static bool mcl_one_trip_ok(const skr_step_plan& p, const skr_step_mask& mk, const skr_step_layout& l, int64_t numel, int* bps_shift) {
-  constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
-  const int32_t t = p.dtype_a, db = p.n_group_a == p.n_terms ? t : p.dtype_b;
-  if (!g_tune.one_trip || p.acc_f64 || p.n_terms < 1 || p.n_terms > 8) return false;
-  if ((t != SKR_BF16 && t != SKR_F16) || db != t || p.out0_dtype != t || mk.dtype != t) return false;
-  if ((l.channels != 4 && l.channels != 8 && l.channels != 16) || l.plane % 4 != 0) return false;
-  if (numel % CHUNK != 0 || numel / CHUNK > 0x7fffffffll || p.sample_numel % CHUNK != 0 || p.sample_numel >= (1ll << 31)) return false;
-  if (l.plane % mk.mask_numel != 0 || mk.mask_numel % 2 != 0) return false;
-  *bps_shift = bps_shift_of(p.sample_numel / CHUNK);
-  return true;
+  if (mk.dtype != p.dtype_a || l.plane % mk.mask_numel != 0 || mk.mask_numel % 2 != 0) return false;
+  return cl_one_trip_geometry(p, l, numel, (1ll << 31) - 1, bps_shift);
 }
 
 template <typename T>
@@ -249,9 +167,7 @@ static int launch_mcl1(const skr_step_plan& p, const skr_step_mask& mk, const sk
       a.mask_numel = (uint32_t)mk.mask_numel; a.mask_stride = (uint32_t)mk.batch_stride;
       a.stream0 = p.stream0; a.zeta0 = (float)p.zeta0; a.quads = (uint32_t)(l.plane / 4);
       const dim3 grid((unsigned)chunks), block(BLOCK);
-      if (l.channels == 4) hipLaunchKernelGGL((masked_kernel_cl1<T, N, 4, NOISE>), grid, block, 0, stream, a);
-      else if (l.channels == 8) hipLaunchKernelGGL((masked_kernel_cl1<T, N, 8, NOISE>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((masked_kernel_cl1<T, N, 16, NOISE>), grid, block, 0, stream, a);
+      with_channels(l.channels, [&](auto c) { hipLaunchKernelGGL((masked_kernel_cl1<T, N, decltype(c)::value, NOISE>), grid, block, 0, stream, a); });
     });
   }, noise);
   return finish_launch();
@@ -286,9 +202,8 @@ extern "C" int skr_step_launch_masked_channels_last(const skr_step_plan* plan, c
   const skr_step_mask& mk = *mask;
   skr::MaskedLaunch ml;
   if (const int rc = skr::masked_prepare(p, mk, inputs, out, seeds_dev, numel, false, &ml)) return rc;
-  if (!layout) return SKR_ERR_NULL;
+  if (const int rc = skr::layout_check(p, layout)) return rc;
   const skr_step_layout& l = *layout;
-  if (l.channels < 1 || l.plane < 1 || p.sample_numel % l.channels != 0 || p.sample_numel / l.channels != l.plane) return SKR_ERR_SHAPE;
   if (numel == 0) return SKR_OK;
   if (l.channels == 1 || l.plane == 1) return skr_step_launch_masked(plan, inputs, out, mask, seeds_dev, numel, stream);  // l(p) = p
   skr::DeviceGuard device_guard(out);

@@ -1142,11 +1142,10 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             arr[j] = sp if code == 0 else op if code == 1 else hp[k][f]
             j += 1
         # (results below the staggering size that share the sample's dtype: empty_like skips the shape / dtype / device argument parsing)
-        empty_output = lazy.empty_output if strides is None else lazy.empty_output_channels_last
-        out0 = torch.empty_like(sample) if entry.like0 else empty_output(shape, entry.o0dt, device)
+        out0 = torch.empty_like(sample) if entry.like0 else lazy.empty_output(shape, entry.o0dt, device, strides is not None)
         p0 = out0.data_ptr()
         if entry.o1dt is not None:
-            out1 = torch.empty_like(sample) if entry.like1 else empty_output(shape, entry.o1dt, device)
+            out1 = torch.empty_like(sample) if entry.like1 else lazy.empty_output(shape, entry.o1dt, device, strides is not None)
             status = entry.launch(entry.handle, arr, p0, out1.data_ptr(), seeds_ptr, s0, s1, _hip._raw_stream(entry.dev_index))
             final = out1 if entry.final_out else out0
         else:

@@ -345,23 +345,42 @@ _ITEMSIZE = {torch.bfloat16: 2, torch.float16: 2, torch.float32: 4, torch.float6
 _strides_cache: dict = {}
 
 
-def empty_output(shape, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
-    "uninitialised result tensor whose start is shifted by 4 KiB + k*8 KiB (k cycles) inside its allocation"
+def _channels_last_strides(shape) -> tuple:
+    "strides of dense channels-last storage (torch.channels_last / channels_last_3d): axis 1 innermost, the other axes in order"
+    strides, acc = [0] * len(shape), shape[1]
+    strides[1] = 1
+    for axis in range(len(shape) - 1, 1, -1):
+        strides[axis] = acc
+        acc *= shape[axis]
+    strides[0] = acc
+    return tuple(strides)
+
+
+def empty_output(shape, dtype: torch.dtype, device: torch.device, channels_last: bool = False) -> torch.Tensor:
+    """uninitialised result tensor, contiguous or in channels-last storage, whose start is shifted by 4 KiB + k*8 KiB (k cycles) inside
+    its allocation"""
     global _stagger_next
     shape = tuple(shape)
     numel = math.prod(shape)
     item = _ITEMSIZE.get(dtype, 4)
-    if numel * item < (16 << 20):  # small tensors are launch/host-bound and live in L2 / MALL anyway
+    small = numel * item < (16 << 20)  # small tensors are launch/host-bound and live in L2 / MALL anyway
+    if small and not channels_last:
         return torch.empty(shape, dtype=dtype, device=device)
+    strides = _strides_cache.get((shape, channels_last))
+    if strides is None:
+        if channels_last:
+            strides = _channels_last_strides(shape)
+        else:
+            acc, rev = 1, []
+            for d in reversed(shape):
+                rev.append(acc)
+                acc *= d
+            strides = tuple(reversed(rev))
+        _strides_cache[shape, channels_last] = strides
+    if small:
+        return torch.empty_strided(shape, strides, dtype=dtype, device=device)
     k = _stagger_next
     _stagger_next = (k + 1) % _STAGGER_SLOTS
-    strides = _strides_cache.get(shape)
-    if strides is None:
-        acc, rev = 1, []
-        for d in reversed(shape):
-            rev.append(acc)
-            acc *= d
-        strides = _strides_cache[shape] = tuple(reversed(rev))
     flat = torch.empty(numel + (4096 + _STAGGER_SLOTS * _STAGGER_BYTES) // item, dtype=dtype, device=device)
     return flat.as_strided(shape, strides, (4096 + k * _STAGGER_BYTES) // item)
 
@@ -408,12 +427,7 @@ def _layout_from(shape, strides) -> "tuple[int, int] | None":
         plane *= d
     if channels <= 1 or plane <= 1 or shape[0] < 1:
         return None
-    want, acc = [0] * ndim, channels
-    want[1] = 1
-    for axis in range(ndim - 1, 1, -1):
-        want[axis] = acc
-        acc *= shape[axis]
-    want[0] = acc
+    want = _channels_last_strides(shape)
     for axis in range(ndim):
         if shape[axis] != 1 and strides[axis] != want[axis]:
             return None
@@ -442,29 +456,13 @@ def _prepare_keeping_layout(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def _channels_last_strides(shape) -> tuple:
-    strides, acc = [0] * len(shape), shape[1]
-    strides[1] = 1
-    for axis in range(len(shape) - 1, 1, -1):
-        strides[axis] = acc
-        acc *= shape[axis]
-    strides[0] = acc
-    return tuple(strides)
-
-
-def empty_output_channels_last(shape, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
-    "empty_output in channels-last storage: the same staggered placement for large tensors"
-    global _stagger_next
-    shape = tuple(shape)
-    strides = _channels_last_strides(shape)
-    numel = math.prod(shape)
-    item = _ITEMSIZE.get(dtype, 4)
-    if numel * item < (16 << 20):
-        return torch.empty_strided(shape, strides, dtype=dtype, device=device)
-    k = _stagger_next
-    _stagger_next = (k + 1) % _STAGGER_SLOTS
-    flat = torch.empty(numel + (4096 + _STAGGER_SLOTS * _STAGGER_BYTES) // item, dtype=dtype, device=device)
-    return flat.as_strided(shape, strides, (4096 + k * _STAGGER_BYTES) // item)
+def in_place_layout(tensors, shape, allowed: bool = True) -> "tuple[int, int] | None":
+    """Does a launch over `tensors` run in place on channels-last storage, and in which layout: (channels, plane) when the caller allows
+    it (nothing grad-recorded), `channels_last` is on, no `_hip.indexed` hook is installed and every tensor has `shape` in one dense
+    channels-last layout; None: the contiguous route."""
+    if not (allowed and channels_last and _hip.indexed is None):
+        return None
+    return shared_layout(tensors, shape)
 
 
 def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64: bool | None = None) -> list[torch.Tensor]:
@@ -503,14 +501,14 @@ def evaluate(forms: Sequence[Lin], dtypes: Sequence[torch.dtype | None], acc_f64
     # channels-last route: every tensor operand in one dense channels-last layout, no rounded conversion (Runge-Kutta stages), no capture
     # hook, no autograd recording
     leaves = [leaf for f in (f0, f1) if f is not None for leaf, _ in f.terms.values() if isinstance(leaf, torch.Tensor)]
-    keep_layout = channels_last and conv is None and _hip.indexed is None and not grad_recorded(*leaves)
+    keep_layout = conv is None and not grad_recorded(*leaves)
     plan, operands, seeds = _lower(conv, f0, f1, chain, out_dtypes, acc_f64, keep_layout=keep_layout)
-    layout = shared_layout(operands, shape) if keep_layout else None
+    layout = in_place_layout(operands, shape, keep_layout)
     if layout is not None:
         plan.sample_numel = layout[0] * layout[1]
-        out0 = empty_output_channels_last(shape, out_dtypes[0], device)
-        out1 = empty_output_channels_last(shape, out_dtypes[1], device) if f1 is not None else None
-        _hip.launch_step_channels_last(plan, operands, out0, out1, seeds, layout, numel, device)
+        out0 = empty_output(shape, out_dtypes[0], device, channels_last=True)
+        out1 = empty_output(shape, out_dtypes[1], device, channels_last=True) if f1 is not None else None
+        _hip.launch_step(plan, operands, out0, out1, seeds, numel, device, layout)
         return [out0] if out1 is None else [out0, out1]
     if torch.is_grad_enabled() and any(t.requires_grad for t in operands):
         if conv is not None:
@@ -581,7 +579,7 @@ def _lower(conv, f0: "Lin", f1: "Lin | None", chain: float, out_dtypes, acc_f64:
     if acc_f64:
         wide = torch.float64
     # (keep_layout: operands that all share one dense channels-last layout go in as they are -- evaluate() reads the layout off them)
-    prepare = _prepare_keeping_layout if keep_layout and shared_layout(tensors.values(), shape) is not None else _prepare_tensor
+    prepare = _prepare_keeping_layout if in_place_layout(tensors.values(), shape, keep_layout) is not None else _prepare_tensor
     prepared = {i: prepare(t) for i, t in tensors.items()}
     for t in prepared.values():
         if t.shape != shape and t.numel() != numel:
@@ -696,18 +694,17 @@ def evaluate_masked(form: Lin, known: Lin, mask: torch.Tensor, dtype: torch.dtyp
     if not mask.is_cuda or mask.device != device:
         raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
     # channels-last route: every tensor leaf of both forms in one dense channels-last layout, no capture hook, no autograd recording
-    keep_layout = channels_last and _hip.indexed is None and not recorded
-    plan, operands, seeds = _lower(None, f0, f1, 0.0, [out_dtype], acc_f64, fuse1=False, max_terms=_hip.ROW_TERMS, keep_layout=keep_layout)
+    plan, operands, seeds = _lower(None, f0, f1, 0.0, [out_dtype], acc_f64, fuse1=False, max_terms=_hip.ROW_TERMS, keep_layout=not recorded)
     if mask.dtype == torch.float64 and not plan.acc_f64:
         raise SkrampleHipError("a float64 mask needs float64 accumulation")
     numel = math.prod(shape)
     plan.sample_numel = numel // shape[0] if shape[0] else 1
-    layout = shared_layout(operands, shape) if keep_layout else None
+    layout = in_place_layout(operands, shape, not recorded)
     if layout is not None:
         # the operands stay as they are and the result is channels-last; the mask keeps its logical order (a single-channel mask is
         # contiguous in either memory format: no copy)
-        out = empty_output_channels_last(shape, out_dtype, device)
-        _hip.launch_step_masked_channels_last(plan, operands, out, _prepare_tensor(mask), mask_numel, batch_stride, seeds, layout, numel, device)
+        out = empty_output(shape, out_dtype, device, channels_last=True)
+        _hip.launch_step_masked(plan, operands, out, _prepare_tensor(mask), mask_numel, batch_stride, seeds, numel, device, layout)
         return out
     if recorded:
         return _MaskedStepFunction.apply(plan, seeds, shape, numel, device, _prepare_tensor(mask), mask_numel, batch_stride, *operands)
@@ -752,12 +749,10 @@ def guide_only(guidance: Guidance) -> torch.Tensor:
     u, c = guidance.uncond, guidance.cond
     if is_host(guidance.device) or grad_recorded(u, c):
         return guidance.torch_lines()
-    if channels_last and _hip.indexed is None and shared_layout((u, c), guidance.shape) is not None:
-        u, c = _prepare_keeping_layout(u), _prepare_keeping_layout(c)
-        out = empty_output_channels_last(guidance.shape, guidance.dtype, guidance.device)
-    else:
-        u, c = _prepare_tensor(u), _prepare_tensor(c)
-        out = empty_output(guidance.shape, guidance.dtype, guidance.device)
+    in_place = in_place_layout((u, c), guidance.shape) is not None
+    prepare = _prepare_keeping_layout if in_place else _prepare_tensor
+    u, c = prepare(u), prepare(c)
+    out = empty_output(guidance.shape, guidance.dtype, guidance.device, channels_last=in_place)
     plan = _hip.StepPlanC()
     plan.n_terms = plan.n_group_a = 1
     plan.dtype_a = plan.dtype_b = _hip.DTYPE_CODE[guidance.dtype]

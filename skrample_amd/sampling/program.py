@@ -18,7 +18,7 @@ from typing import Any, Sequence
 import torch
 
 from .. import _hip
-from .lazy import LazyTensor, Lin, PhiloxNoise, empty_output, empty_output_channels_last, layout_of, shared_layout
+from .lazy import LazyTensor, Lin, PhiloxNoise, empty_output, layout_of, shared_layout
 from .structured import SKSamples
 
 Role = tuple  # ("x",) ("o",) ("n",) ("px", k) ("pi", k) ("po", k) ("pn", k)   k = negative index into the history
@@ -162,9 +162,8 @@ class StepProgram:
             seeds_ptr = ptr
         if self.layout is not None and _hip.indexed is not None:
             return None  # (captured loops with device-resident rows take contiguous operands: the general path makes them)
-        empty = empty_output if self.layout is None else empty_output_channels_last
-        out0 = empty(self.shape, self.out_dtypes[0], device)
-        out1 = empty(self.shape, self.out_dtypes[1], device) if self.out_dtypes[1] is not None else None
+        out0 = empty_output(self.shape, self.out_dtypes[0], device, self.layout is not None)
+        out1 = empty_output(self.shape, self.out_dtypes[1], device, self.layout is not None) if self.out_dtypes[1] is not None else None
         n = len(ops)
         if self.ptr_array is None:
             self.ptr_array = (ctypes.c_void_p * max(n, 1))()

@@ -1,5 +1,6 @@
 """What the ISA test modules share (no GPU needed: hipcc cross-compiles gfx950): one source file of skrample_amd/csrc compiled to
-assembly with the library's own flags, the assembly split per kernel, occupancy from a VGPR count, demangled symbols."""
+assembly with the library's own flags, the assembly split per kernel, occupancy from a VGPR count, demangled symbols, a file's
+kernels by demangled name, the count of a Philox round's wide multiplies."""
 
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ import __graft_entry__ as G
 CSRC = os.path.join(ROOT, "skrample_amd", "csrc")
 HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 CXXFILT = shutil.which("c++filt")
+WIDE_MUL = ("v_mul_hi_u32", "v_mad_u64_u32")  # what a 32 x 32 -> 64 bit product of a Philox round compiles to
 _asm: dict[str, str] = {}
 
 
@@ -54,3 +56,14 @@ def demangle(symbols) -> dict:
     symbols = list(symbols)
     out = subprocess.run([CXXFILT], input="\n".join(s.replace("DF16b", "u6__bf16") for s in symbols), capture_output=True, text=True, check=True).stdout.split("\n")
     return {s: (name if name and not name.startswith("_Z") else s) for s, name in zip(symbols, out)}
+
+
+def named(source, work):
+    "{demangled name: kernels_of's entry} of every kernel of csrc/<source>"
+    kernels = kernels_of(compile_asm(source, work))
+    names = demangle(kernels)
+    return {names[sym]: body for sym, body in kernels.items()}
+
+
+def wide_multiplies(lines, which):
+    return sum(1 for l in lines if l.split()[0] in which)

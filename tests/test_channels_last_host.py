@@ -1,6 +1,6 @@
 """Channels-last steps without a device: the two C ABI entries are declared in the header, listed by the binding and exported by the
-built library; the ABI version has not moved; the header is still plain C; the layout checks answer before any pointer is
-dereferenced; and lazy.layout_of tells a dense channels-last tensor from everything else."""
+built library; the ABI version has not moved; the header is still plain C; the layout checks of every entry that takes a layout answer
+before any pointer is dereferenced; and lazy.layout_of tells a dense channels-last tensor from everything else."""
 
 import ctypes
 import os
@@ -70,33 +70,45 @@ def make_plan(sample_numel=4096, **fields):
 
 
 def test_layout_checks_answer_before_any_pointer_is_dereferenced():
-    "host buffers that are never read stand in for device pointers: every status below is returned ahead of the launch"
+    """host buffers that are never read stand in for device pointers: every status below is returned ahead of the launch.  The three
+    entries that take a layout -- the plain launch, the program made for it, the masked launch -- answer the same bad layouts alike"""
     lib = _hip.load()
     blob = (ctypes.c_char * 4096)()
     base = (ctypes.addressof(blob) + 15) & ~15  # 16-byte aligned stand-ins (the alignment check of skr_step_launch comes first)
     arr = (ctypes.c_void_p * 2)(base, base + 64)
     out, seeds, numel = base + 128, base + 256, 2 * 4096
+    handle = ctypes.c_void_p()
+    mask = _hip.StepMaskC(base + 512, _hip.BF16, 0, 1024, 1024)
+
+    def ref(layout):
+        return ctypes.byref(layout) if layout is not None else None
 
     def launch(plan, layout, out1=None):
-        return lib.skr_step_launch_channels_last(ctypes.byref(plan), arr, out, out1, seeds, ctypes.byref(layout) if layout is not None else None, numel, None)
+        return lib.skr_step_launch_channels_last(ctypes.byref(plan), arr, out, out1, seeds, ref(layout), numel, None)
 
-    assert launch(make_plan(), None) == ERR_NULL
-    for channels, plane in ((4, 1000), (0, 4096), (4, 0), (-4, -1024), (3, 1024)):
-        assert launch(make_plan(), _hip.StepLayoutC(channels, plane)) == ERR_SHAPE, (channels, plane)
-    assert launch(make_plan(sample_numel=4096, noise_mode=0, zeta0=0.0), _hip.StepLayoutC(4, 1000)) == ERR_SHAPE  # (with or without a draw)
+    def create(plan, layout, out1=None):
+        status = lib.skr_program_create_channels_last(ctypes.byref(plan), numel, ref(layout), ctypes.byref(handle))
+        assert bool(handle.value) == (status == OK)
+        return status
+
+    def masked(plan, layout, out1=None):
+        plan.coef1[1] = 0.25
+        return lib.skr_step_launch_masked_channels_last(ctypes.byref(plan), arr, out, ctypes.byref(mask), seeds, ref(layout), numel, None)
+
     convert = dict(out1_dtype=_hip.BF16, convert_to=1, convert_from=1)
-    assert launch(make_plan(**convert), _hip.StepLayoutC(4, 1024), out1=base + 512) == ERR_UNSUPPORTED  # a draw together with a conversion
+    for entry in (launch, create, masked):
+        assert entry(make_plan(), None) == ERR_NULL, entry.__name__
+        for channels, plane in ((4, 1000), (0, 4096), (4, 0), (-4, -1024), (3, 1024)):  # channels * plane != sample_numel, channels < 1, plane < 1
+            assert entry(make_plan(), _hip.StepLayoutC(channels, plane)) == ERR_SHAPE, (entry.__name__, channels, plane)
+        assert entry(make_plan(sample_numel=4096, noise_mode=0, zeta0=0.0), _hip.StepLayoutC(4, 1000)) == ERR_SHAPE  # (with or without a draw)
+        if entry is not masked:  # a draw together with a rounded conversion (a masked launch has no conversion)
+            assert entry(make_plan(**convert), _hip.StepLayoutC(4, 1024), out1=base + 512) == ERR_UNSUPPORTED, entry.__name__
     # skr_step_launch's own checks keep their place in front: a NULL plan, a missing seed pointer, a sample size that does not divide
     assert lib.skr_step_launch_channels_last(None, arr, out, None, seeds, ctypes.byref(_hip.StepLayoutC(4, 1024)), numel, None) == ERR_NULL
     assert lib.skr_step_launch_channels_last(ctypes.byref(make_plan()), arr, out, None, None, None, numel, None) == ERR_NULL
     assert launch(make_plan(sample_numel=4095), _hip.StepLayoutC(4, 1024)) == ERR_SHAPE
-    # programs: the same checks when the handle is made
-    handle = ctypes.c_void_p()
-    create = lib.skr_program_create_channels_last
-    assert create(ctypes.byref(make_plan()), numel, None, ctypes.byref(handle)) == ERR_NULL and not handle.value
-    assert create(ctypes.byref(make_plan()), numel, ctypes.byref(_hip.StepLayoutC(4, 1000)), ctypes.byref(handle)) == ERR_SHAPE and not handle.value
-    assert create(ctypes.byref(make_plan(**convert)), numel, ctypes.byref(_hip.StepLayoutC(4, 1024)), ctypes.byref(handle)) == ERR_UNSUPPORTED
-    assert create(ctypes.byref(make_plan()), numel, ctypes.byref(_hip.StepLayoutC(4, 1024)), ctypes.byref(handle)) == OK and handle.value
+    # programs: a good layout makes a handle
+    assert create(make_plan(), _hip.StepLayoutC(4, 1024)) == OK and handle.value
     lib.skr_program_destroy(handle.value)
 
 

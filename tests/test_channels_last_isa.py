@@ -9,17 +9,11 @@ exchange did not cost a single extra full-width multiply of the Philox rounds.""
 import re
 
 import pytest
-from isa_cases import CXXFILT, HIPCC, compile_asm, demangle, kernels_of, waves_per_simd
+from isa_cases import CXXFILT, HIPCC, WIDE_MUL, named, waves_per_simd, wide_multiplies
 
 ONE_TRIP = re.compile(r"step_kernel_cl1<skr::(bf16_t|f16_t), (\d+), (\d+)>")
 TWIN = "step_kernel_k1<skr::{t}, 4, true, false, false, (skr::RowForm)0>"
-WIDE_MUL = ("v_mul_hi_u32", "v_mad_u64_u32")  # what a 32 x 32 -> 64 bit product of a Philox round compiles to
-
-
-def named(source, work):
-    kernels = kernels_of(compile_asm(source, work))
-    names = demangle(kernels)
-    return {names[sym]: body for sym, body in kernels.items()}
+EXCHANGE = {4: (4, 0), 8: (8, 0), 16: (4, 4)}  # (DPP quad permutes, ds_swizzle) of cl_draw8 per channel count
 
 
 @pytest.fixture(scope="module")
@@ -57,10 +51,6 @@ def test_no_scratch_and_no_flat_memory_operation(mine):
         assert waves_per_simd(vgprs) == 8, (key, vgprs)  # the exchange's temporaries cost no wave
 
 
-def wide_multiplies(lines, which):
-    return sum(1 for l in lines if l.split()[0] in which)
-
-
 def test_the_exchange_costs_no_philox_multiply_and_the_register_table(mine, fast):
     "two whole blocks per lane, as in the contiguous kernel: no more 32 x 32 multiplies than its twin has"
     kernels = one_trip(mine)
@@ -85,4 +75,4 @@ def test_the_exchange_runs_in_registers(mine):
         dpp = sum(1 for l in lines if "quad_perm" in l)
         swizzle = sum(1 for l in lines if l.startswith("ds_swizzle_b32"))
         assert not any(l.startswith(("ds_read", "ds_write", "ds_bpermute", "ds_permute")) for l in lines), (t, k, c)
-        assert (dpp, swizzle) == {4: (4, 0), 8: (8, 0), 16: (4, 4)}[c], (t, k, c, dpp, swizzle)
+        assert (dpp, swizzle) == EXCHANGE[c], (t, k, c, dpp, swizzle)

@@ -11,19 +11,12 @@ scratch"."""
 import re
 
 import pytest
-from isa_cases import CXXFILT, HIPCC, compile_asm, demangle, kernels_of, waves_per_simd
+from isa_cases import CXXFILT, HIPCC, WIDE_MUL, named, waves_per_simd, wide_multiplies
+from test_channels_last_isa import EXCHANGE  # (DPP quad permutes, ds_swizzle) of step_kernel_cl1
 
 ONE_TRIP = re.compile(r"masked_kernel_cl1<skr::(bf16_t|f16_t), (\d+), (\d+), (true|false)>")
 TWIN = "masked_kernel_v1<skr::{t}, 4, true, (skr::RowForm)0>"
 QUIET_TWIN = "masked_kernel_v1<skr::{t}, 4, false, (skr::RowForm)0>"
-WIDE_MUL = ("v_mul_hi_u32", "v_mad_u64_u32")  # what a 32 x 32 -> 64 bit product of a Philox round compiles to
-EXCHANGE = {4: (4, 0), 8: (8, 0), 16: (4, 4)}  # (DPP quad permutes, ds_swizzle) of step_kernel_cl1 (test_channels_last_isa.py)
-
-
-def named(source, work):
-    kernels = kernels_of(compile_asm(source, work))
-    names = demangle(kernels)
-    return {names[sym]: body for sym, body in kernels.items()}
 
 
 @pytest.fixture(scope="module")
@@ -77,10 +70,6 @@ def test_the_exchange_is_step_kernel_cl1s_and_runs_in_registers(mine):
         swizzle = sum(1 for l in lines if l.startswith("ds_swizzle_b32"))
         assert not any(l.startswith(("ds_read", "ds_write", "ds_bpermute", "ds_permute")) for l in lines), (t, k, c, nz)
         assert (dpp, swizzle) == (EXCHANGE[c] if nz else (0, 0)), (t, k, c, nz, dpp, swizzle)
-
-
-def wide_multiplies(lines, which):
-    return sum(1 for l in lines if l.split()[0] in which)
 
 
 def test_the_draw_costs_no_philox_multiply_and_the_register_table(mine, masked):

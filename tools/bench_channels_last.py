@@ -1,7 +1,7 @@
 """Cost of a scheduler step on channels-last latents: run in place (skr_step_launch_channels_last) against the copies made before.
 256 x (4, 128, 128) bf16 through SkrampleWrapperScheduler.step, DPM-2 eta = 1 (the headline step: Philox noise in registers) and eta = 0.
 
-  python tools/bench_channels_last.py [--repeats 5] [--steps 200] [--out profiles/channels_last.txt]
+  python tools/bench_channels_last.py [--repeats 5] [--steps 200] [--out profiles/channels_last.txt] [--operands 4] [--channels 4]
 
 Forms, each in a child process of its own (a fresh HIP context and allocator per form; the parent never opens the GPU):
   a  channels-last, in place    sample and model_output in torch.channels_last: one launch on the caller's tensors, channels-last result
@@ -11,7 +11,8 @@ Forms, each in a child process of its own (a fresh HIP context and allocator per
   k  kernels alone              skr_step_launch_channels_last (step_kernel_cl1<bf16, 4, 4>) on channels-last operands beside skr_step_launch on
                                 contiguous ones (step_kernel_k1<bf16, 4, noise>, paced as shipped and with "pace" 0 -- the form the new kernel was
                                 derived from), 4 operands + Philox, rounds interleaved in one process: event clock per launch and the fraction
-                                of 8 TB/s the algorithmic bytes (4 loads + 1 store) come to; and the general kernel ("one_trip" 0) on the same
+                                of 8 TB/s the algorithmic bytes (4 loads + 1 store) come to; and the general kernel ("one_trip" 0) on the same.
+                                --operands K --channels C time step_kernel_cl1<bf16, K, C> instead, on 256 x (C, 128, 512 / C)
 A run is `steps` steps of one schedule; the result of a step is the next step's sample, the model outputs rotate through six distinct
 tensors in the form's layout (form a and b: a channels-last network hands back channels-last; distinct buffers, as a network's are, let
 the wrapper's history alias them instead of taking snapshots).  Three warm-up runs (from the second on the replayed
@@ -35,7 +36,7 @@ FORMS = {"a": "channels-last, in place", "b": "channels-last, copied", "c": "con
 PEAK = 8.0e12  # bytes per second
 
 
-def child(form: str, sampler: str, repeats: int, steps: int) -> None:
+def child(form: str, sampler: str, repeats: int, steps: int, operands: int = 4, channels: int = 4) -> None:
     import ctypes
 
     import torch
@@ -48,12 +49,13 @@ def child(form: str, sampler: str, repeats: int, steps: int) -> None:
 
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(1)
-    fresh = lambda: torch.randn(SHAPE, generator=g).bfloat16().to(dev)  # noqa: E731
+    shape = SHAPE if form != "k" else (SHAPE[0], channels, SHAPE[2], SHAPE[3] * SHAPE[1] // channels)  # (as many elements whatever the channel count)
+    fresh = lambda: torch.randn(shape, generator=g).bfloat16().to(dev)  # noqa: E731
     result = {"form": form, "sampler": sampler, "device": torch.cuda.get_device_name(0)}
     lib = _hip.load()
 
     if form == "k":
-        n = 4
+        n = operands
         ops = [fresh() for _ in range(n)]
         ops_cl = [t.contiguous(memory_format=torch.channels_last) for t in ops]
         out, out_cl = torch.empty_like(ops[0]), torch.empty_like(ops_cl[0])
@@ -63,10 +65,10 @@ def child(form: str, sampler: str, repeats: int, steps: int) -> None:
         plan.dtype_b, plan.out1_dtype = _hip.F32, _hip.NONE
         plan.sample_numel, plan.noise_mode, plan.zeta0, plan.stream0 = out[0].numel(), 1, 0.3, 256
         for k in range(n):
-            plan.coef0[k] = 0.25
+            plan.coef0[k] = 1.0 / n
         seeds = torch.arange(1, SHAPE[0] + 1, dtype=torch.int64, device=dev)
         arr, arr_cl = ((ctypes.c_void_p * n)(*[t.data_ptr() for t in group]) for group in (ops, ops_cl))
-        layout = _hip.StepLayoutC(SHAPE[1], SHAPE[2] * SHAPE[3])
+        layout = _hip.StepLayoutC(shape[1], shape[2] * shape[3])
         stream = _hip.current_stream_ptr(dev)
 
         def contiguous():
@@ -94,7 +96,7 @@ def child(form: str, sampler: str, repeats: int, steps: int) -> None:
                 if rep:
                     result[name + "_us"].append(e0.elapsed_time(e1) * 1e3 / count)
         assert torch.equal(out_cl, out)  # the same bits, viewed logically
-        result["operands"] = n
+        result["operands"], result["channels"] = n, channels
         result["bytes"] = out.numel() * 2 * (n + 1)
         print("RESULT " + json.dumps(result), flush=True)
         return
@@ -142,11 +144,16 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "channels_last.txt"))
     ap.add_argument("--child", nargs=2, metavar=("FORM", "SAMPLER"))
+    ap.add_argument("--tree", default=None, help="time the package of this source tree instead (tools/bench_channels_last_shared.py: a parent commit beside this one)")
+    ap.add_argument("--operands", type=int, default=4, choices=range(1, 9), help="form k: operands of the launch")
+    ap.add_argument("--channels", type=int, default=4, choices=(4, 8, 16), help="form k: channels of the latents")
     args = ap.parse_args()
     if args.repeats < 5 or args.steps < 200:
         ap.error("at least 5 repeats of at least 200 steps")
+    if args.tree:
+        sys.path.insert(0, os.path.abspath(args.tree))
     if args.child:
-        child(args.child[0], args.child[1], args.repeats, args.steps)
+        child(args.child[0], args.child[1], args.repeats, args.steps, args.operands, args.channels)
         return 0
     lines = [f"scheduler steps on channels-last latents: {SHAPE[0]} x {SHAPE[1:]} bf16 through SkrampleWrapperScheduler.step; "
              f"{args.repeats} repeats of {args.steps} steps after {WARMUP_RUNS} warm-up runs",
@@ -154,7 +161,8 @@ def main() -> int:
     failed = False
 
     def spawn(form, sampler):
-        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--repeats", str(args.repeats), "--steps", str(args.steps), "--child", form, sampler],
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--repeats", str(args.repeats), "--steps", str(args.steps), "--operands", str(args.operands),
+                              "--channels", str(args.channels), "--child", form, sampler],
                              capture_output=True, text=True, timeout=600)  # fmt: skip
         found = [line for line in run.stdout.splitlines() if line.startswith("RESULT ")]
         if run.returncode != 0 or not found:
@@ -187,8 +195,9 @@ def main() -> int:
     if k is None:
         return 1
     lines.append(f"kernels alone  ({k['operands']} bf16 operands + Philox, {k['bytes'] / 1e6:.1f} MB of algorithmic bytes per launch; rounds interleaved in one process)")
-    for name, kernel in (("k1_paced", "step_kernel_k1<bf16, 4, noise, paced>   contiguous"), ("k1_unpaced", "step_kernel_k1<bf16, 4, noise, unpaced> contiguous"),
-                         ("cl1", "step_kernel_cl1<bf16, 4, 4>             channels-last"), ("cl_general", "step_kernel_cl<float> (general)         channels-last")):  # fmt: skip
+    n, c = k["operands"], k["channels"]
+    for name, kernel in (("k1_paced", f"step_kernel_k1<bf16, {n}, noise, paced>   contiguous"), ("k1_unpaced", f"step_kernel_k1<bf16, {n}, noise, unpaced> contiguous"),
+                         ("cl1", f"step_kernel_cl1<bf16, {n}, {c}>".ljust(40) + "channels-last"), ("cl_general", "step_kernel_cl<float> (general)         channels-last")):  # fmt: skip
         m, lo, hi = summary(k[name + "_us"])
         lines.append(f"  k  {kernel:56s} event clock {m:8.2f} ({lo:8.2f} - {hi:8.2f}) per launch   {k['bytes'] / (m * 1e-6) / PEAK * 100:5.1f} % of 8 TB/s")
     (cm, clo, chi), (um, ulo, uhi) = summary(k["cl1_us"]), summary(k["k1_unpaced_us"])

@@ -156,9 +156,12 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "masked_channels_last.txt"))
     ap.add_argument("--child", nargs=2, metavar=("FORM", "SAMPLER"))
+    ap.add_argument("--tree", default=None, help="time the package of this source tree instead (tools/bench_channels_last_shared.py: a parent commit beside this one)")
     args = ap.parse_args()
     if args.repeats < 5 or args.steps < 200:
         ap.error("at least 5 repeats of at least 200 steps")
+    if args.tree:
+        sys.path.insert(0, os.path.abspath(args.tree))
     if args.child:
         child(args.child[0], args.child[1], args.repeats, args.steps)
         return 0

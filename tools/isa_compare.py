@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two source trees, kernel symbol by kernel symbol (no GPU needed).
 
-    python tools/isa_compare.py OLD_TREE NEW_TREE [--files NAME.hip ...] [--jobs N] [--work DIR] [--renames FILE] [--pooled]
+    python tools/isa_compare.py OLD_TREE NEW_TREE [--files NAME.hip ...] [--jobs N] [--work DIR] [--renames FILE] [--pooled] [--classify]
 
 Compiles the named files of skrample_amd/csrc (default: the step files skr_step.hip, skr_step_fast.hip, skr_step_backward.hip and
 skr_tape.hip) of each tree with the library's own flags, the tree's PER_FILE_FLAGS included (`--save-temps -c`), splits the device assembly per kernel the way tests/isa_cases.py does,
@@ -13,11 +13,15 @@ With --work DIR the assembly is kept there and reused while it is newer than the
 With --renames FILE (lines of `OLD_SYMBOL NEW_SYMBOL`, written by hand or by tools/isa_renames.py: a kernel template that gained a parameter) an old kernel is compared under its new
 name; the map is printed ahead of the report (its size alone when it is long).
 With --pooled (kernels that moved between files, files merged or split) the kernels of all named files of a tree are pooled and the two
-pools compared; a named file may then be missing from either tree, and a symbol defined twice in one pool is an error."""
+pools compared; a named file may then be missing from either tree, and a symbol defined twice in one pool is an error.
+With --classify (a device-side refactor that may only reorder) every differing symbol is named `reordered only` -- the same NumVgprs,
+TotalNumSgprs and ScratchSize, the same `.amdhsa_*` lines and, with s_waitcnt and s_nop set aside, the same multiset of opcodes -- or
+by the first of these it fails, and the exit status is 0 when every difference is of the first kind."""
 
 from __future__ import annotations
 
 import argparse
+import collections
 import difflib
 import glob
 import importlib.util
@@ -72,6 +76,26 @@ def kernels(text: str) -> dict:
     return out
 
 
+def verdict(old: list, new: list) -> str:
+    "`reordered only`, or the first criterion a differing symbol fails (--classify)"
+
+    def part(lines, keep):
+        return [l for l in lines if keep(l)]
+
+    for what, keep in (("register / scratch figures", lambda l: l.startswith("; ")), (".amdhsa_ lines", lambda l: l.startswith(".amdhsa_"))):
+        if part(old, keep) != part(new, keep):
+            return what + " differ"
+
+    def opcodes(lines):
+        code = part(lines, lambda l: not l.startswith((";", ".")) and not l.endswith(":"))
+        return collections.Counter(op for op in (l.split()[0] for l in code) if op not in ("s_waitcnt", "s_nop"))
+
+    a, b = opcodes(old), opcodes(new)
+    if a != b:
+        return "opcode multiset differs: " + ", ".join(f"{op} {a[op]} -> {b[op]}" for op in sorted(set(a) | set(b)) if a[op] != b[op])
+    return "reordered only"
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("old")
@@ -81,6 +105,7 @@ def main() -> int:
     ap.add_argument("--work", default=None, help="directory that keeps the assembly between runs")
     ap.add_argument("--renames", default=None, metavar="FILE", help="lines of `OLD_SYMBOL NEW_SYMBOL`: old kernels compared under their new names")
     ap.add_argument("--pooled", action="store_true", help="compare the union of the kernels of the named files of each tree (a file may be missing from one)")
+    ap.add_argument("--classify", action="store_true", help="name each differing symbol `reordered only` or the criterion it fails; exit 0 when all are the former")
     a = ap.parse_args()
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     work = a.work or tempfile.mkdtemp(prefix="isa_compare_")
@@ -121,6 +146,11 @@ def main() -> int:
         for k in removed:
             print(f"only in old: {k}")
         print(f"{name}: {len(old)} kernels old, {len(new)} new: {len(added)} added, {len(removed)} removed, {len(differing)} differing")
+        if a.classify:
+            verdicts = {k: verdict(old[k], new[k]) for k in differing}
+            for k in differing:
+                print(f"{k}: {verdicts[k]}")
+            differing = [k for k in differing if verdicts[k] != "reordered only"]
         bad += len(added) + len(removed) + len(differing)
     if a.work is None:
         shutil.rmtree(work)

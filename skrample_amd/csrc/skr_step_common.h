@@ -312,8 +312,13 @@ __device__ __forceinline__ void store8(void* base, int64_t vec, const Acc v[VEC]
 template <typename T, typename Acc>
 __device__ __forceinline__ void store_scalar(void* base, int64_t i, Acc v) {
   if constexpr (std::is_same<T, bf16_t>::value) reinterpret_cast<uint16_t*>(base)[i] = (uint16_t)(pack_bf16((float)v, 0.f) & 0xFFFFu);
-  else if constexpr (std::is_same<T, f16_t>::value) reinterpret_cast<_Float16*>(base)[i] = (_Float16)(float)v;
-  else reinterpret_cast<T*>(base)[i] = (T)v;
+  else if constexpr (std::is_same<T, f16_t>::value) {
+    // the fp32 value is rounded, as in pack_f16: without the pin the ragged tail of step_kernel stored out1 through
+    // v_fma_mixlo_f16 -- the chain fma and the conversion in one instruction, the exact sum rounded once
+    float f = (float)v;
+    asm("" : "+v"(f));
+    reinterpret_cast<_Float16*>(base)[i] = (_Float16)f;
+  } else reinterpret_cast<T*>(base)[i] = (T)v;
 }
 
 // ---- per-element load with a run-time dtype (the general kernels of skr_step_masked.hip and skr_step_backward.hip) ------------------

@@ -14,6 +14,12 @@ fp32 accumulate-and-round contract (tests/bit_model.py) cannot keep the contract
             unrelated normals a last-place difference of the fp32 value survives the rounding to a 16-bit output once in 2^15; here a
             split fma or another order shows in most elements.
 
+  stage launches (conversion_inputs, stage_cancelling, stage_chain_cancels): for the rounded conversion, every pattern of a 16-bit dtype
+            as s against a permutation as o and the reverse, under two sets of k; fp32 normals and a chunk of specials whose products
+            overflow and whose quotients underflow.  For out1, an s that cancels itself (coefficients 0.3 and -0.3 at both ends, all
+            else scaled by 2^-16) and a chain that cancels coef1[1]: the order of the operands, of the chain and of the noise, and a
+            split fma, show through a 16-bit output in thousands of elements.
+
 Every set is padded with 1.0 to whole 2048-element chunks.  `ragged` adds three elements for the launches that must miss the
 whole-chunk kernels; they repeat elements of the set instead of 1.0, so that the scalar tail of a grid-stride kernel rounds ties too.
 Nothing in this module needs a GPU."""
@@ -237,6 +243,114 @@ def specials32() -> tuple:
     x0 = np.concatenate([head, sub.view(np.float32), big, np.tile(head, 8), plain])[:CHUNK].copy()
     x1 = np.roll(x0, 7)
     return torch.from_numpy(x0), torch.from_numpy(x1.copy())
+
+
+# ---- Runge-Kutta stage launches -------------------------------------------------------------------------------------------------------
+KINDS = tuple((t, f) for t in range(4) for f in range(4) if (t, f) != (0, 0))  # the 15 rounded conversions
+KINDS_FIVE = ((1, 0), (2, 0), (3, 3), (0, 1), (0, 2))  # between them every operation of convert_rounded
+# (k0 .. k3): the constants of tests/test_step_gpu.py::test_rounded_conversion_equals_torch_op_by_op; a negative k0 (as
+# table_cases.CONVERT_K row 3) with a power of two as k1, which divides in to_x kind 1 and multiplies in kind 2
+CONVERT_KS = ((0.9, 0.09999999999999998, 0.7310585786300049, 0.35), (-0.55, 0.25, 0.8810585786300049, 0.53))
+# fp32 specials: 3 * FLT_MAX overflows in the product, anything / 3e38 below 3.5 is a subnormal quotient, FLT_MIN * 0.75 a subnormal product
+SPECIALS_K = (3.0, 3e38, 0.75, 3e38)
+STAGE_KS = (2, 4, 5, 8)  # operands on both sides of the kernarg slot size of RkOneTripArgs
+STAGE_SCALE = 2.0**-16
+STAGE_ZETA = 0.625
+
+
+def stage_slot_sizes() -> list[int]:
+    "the kernarg slot sizes of step_kernel_rk1, `RkOneTripArgs<(K <= A ? A : B)>`, and the operand counts its launcher instantiates"
+    src = _source("skr_step_fast.hip")
+    a, a2, b = re.search(r"void step_kernel_rk1\(const RkOneTripArgs<\(K <= (\d+) \? (\d+) : (\d+)\)> a\)", src).groups()
+    assert a == a2
+    lo, hi = re.search(r"static int launch_rk1\(.*?with_count<(\d+), (\d+)>\(args\.n_terms", src, re.S).groups()
+    assert (int(lo), int(hi)) == (2, int(b)), (lo, hi, b)
+    return [int(a), int(b)]
+
+
+@functools.lru_cache(maxsize=None)
+def conversion_patterns(name: str) -> tuple:
+    "((s, o), (o, s)): s all 65 536 patterns of the dtype, o a fixed permutation of them"
+    s = patterns(name)
+    o = s[torch.randperm(65536, generator=torch.Generator().manual_seed(1492))].clone()
+    return (s, o), (o, s)
+
+
+def _specials14() -> np.ndarray:
+    info = np.finfo(np.float32)
+    sub = np.array([1, 0x7FFFFF], dtype=np.uint32).view(np.float32)  # the smallest and the largest subnormal
+    return np.array([0.0, -0.0, np.inf, -np.inf, np.nan, sub[0], -sub[0], sub[1], -sub[1], info.tiny, -info.tiny, info.max, -info.max, 1.0], dtype=np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def conversion_specials32() -> tuple:
+    """(s, o), one chunk of fp32: the 14 x 14 block of (+-0, +-inf, NaN, the smallest and the largest subnormal of both signs, +-FLT_MIN,
+    +-FLT_MAX, 1) against each other, both ways round; 400 subnormals beside normals and 400 normals beside subnormals; 300 numbers beyond
+    FLT_MAX / 3 beside normals, and the reverse; numbers within a factor 4 of FLT_MIN beside each other; normals"""
+    sp = _specials14()
+    rng = np.random.default_rng(1777)
+    sub = (rng.integers(1, 2**23, 400, dtype=np.uint32) | (rng.integers(0, 2, 400, dtype=np.uint32) << np.uint32(31))).view(np.float32)
+    big = (rng.uniform(1.14e38, 3.4e38, 300) * rng.choice([-1.0, 1.0], 300)).astype(np.float32)
+    small = (rng.uniform(1.0, 4.0, 200) * np.finfo(np.float32).tiny * rng.choice([-1.0, 1.0], 200)).astype(np.float32)
+    nrm = lambda n: rng.standard_normal(n).astype(np.float32)  # noqa: E731
+    s = np.concatenate([np.repeat(sp, 14), sub, nrm(400), big, nrm(300), small, nrm(CHUNK)])[:CHUNK].copy()
+    o = np.concatenate([np.tile(sp, 14), nrm(400), sub, nrm(300), big, small[::-1], nrm(CHUNK)])[:CHUNK].copy()
+    return torch.from_numpy(s), torch.from_numpy(o)
+
+
+@functools.lru_cache(maxsize=None)
+def stage_extras(name: str, n: int, count: int = 7) -> tuple:
+    "`count` operands of n seeded normals at the scales of table_cases.pool: what stands behind a conversion's pair in a stage launch"
+    g = torch.Generator().manual_seed(random.Random(f"bits/stage/{name}/{n}").randrange(2**31))
+    return tuple((torch.randn(n, generator=g) * SCALES[(j + 2) % len(SCALES)]).to(DTYPES[name]) for j in range(count))
+
+
+STAGE_DTYPES = {**DTYPES, "fp64": torch.float64}
+
+
+def conversion_inputs(name: str) -> list:
+    """[(what, s, o, k sets)], the conversion inputs of one dtype.  16-bit: the patterns both ways round under CONVERT_KS.  fp32 (and fp64:
+    the same numbers widened): SAMPLES * SAMPLE seeded normals under CONVERT_KS, the specials under CONVERT_KS and SPECIALS_K."""
+    if name in NARROW:
+        return [(f"patterns {i}", s, o, CONVERT_KS) for i, (s, o) in enumerate(conversion_patterns(name))]
+    s, o = random_operands("fp32", 2, "cancel")
+    sp = conversion_specials32()
+    dt = STAGE_DTYPES[name]
+    return [("normals", s.to(dt), o.to(dt), CONVERT_KS), ("specials", sp[0].to(dt), sp[1].to(dt), (*CONVERT_KS, SPECIALS_K))]
+
+
+def stage_coefs(k: int, salt: str = "stage") -> list[float]:
+    "coef1 of a stage over unrelated operands: random_coefs (a -0.0 and, from three operands on, a 0.0 among them)"
+    return random_coefs(k, salt)
+
+
+def stage_operands(name: str, pair: tuple, k: int) -> tuple:
+    "a conversion's pair with k - 2 operands of seeded normals behind it"
+    return (*pair, *stage_extras(name, pair[0].numel())[: k - 2])
+
+
+def stage_cancelling(name: str, k: int, scale: float = STAGE_SCALE) -> tuple:
+    """(operands, coef1, chain, zeta1): operand 0 (s) has coefficient 0.3 and the last operand is the same tensor with coefficient -0.3
+    (k = 2: o is s), so that fma(-0.3, s, ... fl32(0.3 s)) leaves the rounding residue of the first product.  Every other coefficient, the
+    chain and zeta1 carry `scale`: all that stands between the two is of the residue's size, and another order of the operands, a chain
+    in front of them or a product rounded apart from its sum shows through a 16-bit output in thousands of elements (among unrelated
+    normals: once in 2^15).  SAMPLES * SAMPLE elements, s and o seeded normals."""
+    s, o = random_operands(name, 2, "cancel")
+    mid = stage_extras(name, s.numel())[: max(k - 3, 0)]
+    ops = (s, s.clone()) if k == 2 else (s, o, *mid, s.clone())
+    rng = random.Random(f"bits/cancel/{k}")
+    coefs = [0.3] + [rng.uniform(0.5, 3) * rng.choice([-1, 1]) * scale for _ in range(k - 2)] + [-0.3]
+    return ops, coefs, -0.4375 * scale, STAGE_ZETA * scale
+
+
+def stage_chain_cancels(name: str, scale: float = STAGE_SCALE) -> tuple:
+    """(operands, coef1, chain, zeta1, kinds, k) for the order of the last two fmas: kinds (3, 0) with k0 = 1 make the derivative o bit for
+    bit, and coef1[1] = -chain, so the chain fma cancels the sum down to what the scaled terms (s, a third operand, the noise) left.
+    A noise fma in front of the chain's is rounded at the size of chain * o instead."""
+    s, o = random_operands(name, 2, "cancel")
+    (w,) = stage_extras(name, s.numel())[:1]
+    chain = 0.8125
+    return (s, o, w), [1.25 * scale, -chain, -0.75 * scale], chain, STAGE_ZETA * scale, (3, 0), (1.0, 1.0, 1.0, 1.0)
 
 
 # ---- masks ----------------------------------------------------------------------------------------------------------------------------

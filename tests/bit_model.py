@@ -3,13 +3,15 @@ in numpy, the contract of every step-family launch written with them, and a bit-
 
 The contract, as the kernels' header comments state it: coefficients are narrowed to fp32 once; a sum starts from zero and takes one
 fma per operand in slot order; the noise fma comes last (and is skipped, as a launch without noise, when zeta narrows to zero); the fp32
-value is rounded once, to nearest even, to the output dtype.
+value is rounded once, to nearest even, to the output dtype.  A Runge-Kutta stage launch first evaluates out0 = from_x(s, to_x(s, o)) one
+operation at a time -- multiply, subtract, divide, each rounded to fp32 and then to the tensor dtype (`convert`) -- and chains that
+rounded derivative into out1 behind the operands and in front of the noise (`rk_stage`).
 
 Exactness.  The product of two fp32 numbers has at most 48 significant bits and is exact in float64.  Adding a third fp32 number in
 float64 rounds once; the TwoSum residual says in which direction, and moving an even float64 sum one place towards a non-zero residual
 ("round to odd") keeps that information in the last bit.  float64 carries 53 >= 2 * 24 + 2 bits, so rounding the odd-rounded sum to fp32
-is the correctly rounded fp32 result -- overflow to inf and fp32 subnormals included.  inf, NaN and signed zeros go through float64's own
-IEEE rules.  tests/test_bit_model_host.py holds all of this against exact rational arithmetic.
+is the correctly rounded fp32 result -- overflow to inf and fp32 subnormals included.  The float64 quotient of two fp32 numbers, narrowed
+once, is the correctly rounded fp32 quotient (`div32`).  inf, NaN and signed zeros go through float64's own IEEE rules.  tests/test_bit_model_host.py holds all of this against exact rational arithmetic.
 
 Nothing here needs a GPU, and nothing is imported from conftest."""
 
@@ -27,7 +29,8 @@ def widen(x) -> np.ndarray:
 
 
 def _wide(x) -> np.ndarray:
-    return np.asarray(x, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):  # (a signalling NaN pattern among the operands)
+        return np.asarray(x, dtype=np.float32).astype(np.float64)
 
 
 def _sum_to_odd(p: np.ndarray, c: np.ndarray) -> np.ndarray:
@@ -68,6 +71,14 @@ def add32(a, b) -> np.ndarray:
 def sub32(a, b) -> np.ndarray:
     "fl32(a - b)"
     return _narrow(_sum_to_odd(_wide(a), -_wide(b)))
+
+
+def div32(a, b) -> np.ndarray:
+    """fl32(a / b): the float64 quotient, narrowed once.  A quotient of two 24-bit numbers that is not itself a rounding boundary of fp32
+    (a number of at most 25 bits; fewer in the subnormal range) lies further than 2^-(2 * 24 + 1) of its size from one, so the float64
+    rounding (53 >= 2 * 24 + 2 bits) never moves it onto or across a boundary: the second rounding decides as one rounding would."""
+    with np.errstate(all="ignore"):
+        return _narrow(_wide(a) / _wide(b))
 
 
 def round_to(dtype: torch.dtype, x32) -> torch.Tensor:
@@ -141,6 +152,67 @@ def masked_backward(a, b, m, g, out: torch.dtype = torch.float32) -> torch.Tenso
     t = sub32(np.float32(1), m)
     w = fma32(np.float32(a), m, mul32(np.float32(b), t))
     return round_to(out, mul32(w, widen(g)))
+
+
+# ---- Runge-Kutta stage launches (convert_rounded of skr_step_common.h; step_kernel_rk1, step_kernel_rk, step_kernel<..., CONV>) ------------
+#   to_x   kinds: 0 o | 1 ((s - k0*o) / k1) | 2 (k1*s - k0*o) | 3 (o * k0)
+#   from_x kinds: 0 x | 1 ((s - k2*x) / k3) | 2 ((k2*s - x) / k3) | 3 (x / k2)
+def _convert(s, o, kinds, k, mul, sub, div, R):
+    "from_x(s, to_x(s, o)) with every operation's result passed through R, in the order of the header's comment"
+    to_kind, from_kind = kinds
+    if to_kind == 1:
+        x = R(div(R(sub(s, R(mul(k[0], o)))), k[1]))
+    elif to_kind == 2:
+        x = R(sub(R(mul(k[1], s)), R(mul(k[0], o))))
+    elif to_kind == 3:
+        x = R(mul(o, k[0]))
+    else:
+        x = o
+    if from_kind == 1:
+        return R(div(R(sub(s, R(mul(k[2], x)))), k[3]))
+    if from_kind == 2:
+        return R(div(R(sub(R(mul(k[2], s)), x)), k[3]))
+    if from_kind == 3:
+        return R(div(x, k[2]))
+    return x
+
+
+def convert32(dtype: torch.dtype, s, o, kinds, k, keep_last: bool = False) -> np.ndarray:
+    """the stage's derivative as fp32 numbers that are values of `dtype`: k narrowed to fp32 once, every operation rounded to fp32 and
+    then to `dtype`.  keep_last: the last operation's fp32 result without its rounding to `dtype` (what a wrong kernel might chain)"""
+    k = [np.float32(v) for v in k]
+    last = []
+
+    def R(v):
+        last[:] = [v]
+        return widen(round_to(dtype, v))
+
+    d = _convert(widen(s), widen(o), kinds, k, mul32, sub32, div32, R)
+    return last[0] if keep_last and last else d
+
+
+def convert(dtype: torch.dtype, s, o, kinds, k) -> torch.Tensor:
+    """out0 of a stage launch: from_x(s, to_x(s, o)), one rounded operation at a time, a tensor of `dtype`.  torch.float64 (acc_f64
+    launches over fp64 operands): the same operations in float64, k as the doubles they are, no second rounding."""
+    if dtype == torch.float64:
+        as64 = lambda t: t.detach().cpu().double().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)  # noqa: E731
+        with np.errstate(all="ignore"):
+            d = _convert(as64(s), as64(o), kinds, [np.float64(v) for v in k], np.multiply, np.subtract, np.divide, lambda v: v)
+        return torch.from_numpy(np.ascontiguousarray(d).copy())
+    return round_to(dtype, convert32(dtype, s, o, kinds, k))  # (exact: the values are values of `dtype`)
+
+
+def rk_stage(coef1, chain, xs, kinds, k, zeta1=None, z1=None, out: torch.dtype | None = None):
+    """skr_step_launch with a rounded conversion (fp32 arithmetic): out0 = convert(xs[0], xs[1]) in the pair's dtype; out1 accumulates
+    coef1 over ALL operands from zero in slot order, then fma(chain, out0 widened to fp32, .) -- the derivative AFTER its rounding to the
+    tensor dtype, in the general kernel's mixed launches too --, then the noise fma (none when zeta1 narrows to zero), then one
+    rounding to `out` (the pair's dtype unless given).  Returns (out0, out1)."""
+    dt = xs[0].dtype
+    out0 = convert(dt, xs[0], xs[1], kinds, k)
+    s1 = _accumulate(coef1, xs)
+    s1 = fma32(np.float32(chain), widen(out0), s1)
+    s1 = _noise(s1, zeta1, z1)
+    return out0, round_to(out if out is not None else dt, s1)
 
 
 # ---- comparison -----------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Helpers of tests/test_table_forms_gpu.py and tests/test_table_forms_host.py: the case grid of the table-form step kernels, the
-builders of rows, plans and index vectors, the float64 reference with its bound, and a host emulation of the kernels' fp32 order.
+builders of rows, plans and index vectors, the float64 reference with its bound, and a host emulation of the kernels' fp32 order (on
+bit_model.fma32, the correctly rounded fma).
 
 The table forms are the launches that take their scalars from a `skr_step_row` in device memory (include/skrample_hip.h):
 skr_step_launch_indexed ("whole"), skr_step_launch_indexed_per_sample ("per_sample") and skr_step_launch_rolling ("rolling").
@@ -12,6 +13,7 @@ import functools
 import random
 from dataclasses import dataclass
 
+import bit_model as BM
 import numpy as np
 import torch
 from skr_oracle import noise as ON
@@ -315,13 +317,6 @@ def reference64(case: Case, td: torch.dtype, x: torch.Tensor, row, present, seed
 
 
 # ---- host emulation of the kernels' order --------------------------------------------------------------------------------------------
-def _fma32(a, b, c):
-    """fl32(a * b + c) without math.fma: the product of two fp32 numbers is exact in float64, the sum is rounded to float64 and then to
-    float32.  That double rounding differs from a true fma only when the float64 sum lands exactly on an fp32 tie -- a last-place
-    difference in a handful of elements at most, far inside the bound the emulation is held to; it is not a bit-level model."""
-    return (np.float64(a) * np.asarray(b, dtype=np.float64) + np.asarray(c, dtype=np.float64)).astype(np.float32)
-
-
 def emulate32(case: Case, td: torch.dtype, x32: np.ndarray, row, present, z0, z1, conv: torch.Tensor | None = None) -> dict:
     """The kernels' arithmetic on the host: fp32 coefficients, one fma per present operand in slot order, then the noise fma, then `chain`
     (rk1: chain before its noise), one rounding to the output dtype.  x32 [slots, sample] float32; z0 / z1 float32 normals or None.
@@ -331,7 +326,7 @@ def emulate32(case: Case, td: torch.dtype, x32: np.ndarray, row, present, z0, z1
     def accumulate(coefs):
         s = zero
         for j in present:
-            s = _fma32(np.float32(coefs[j]), x32[j], s)
+            s = BM.fma32(np.float32(coefs[j]), x32[j], s)
         return s
 
     def rounded(s, od):
@@ -341,19 +336,19 @@ def emulate32(case: Case, td: torch.dtype, x32: np.ndarray, row, present, z0, z1
     use1 = case.draws and row.zeta1 != 0.0 and z1 is not None
     if case.family == "rk1":
         s1 = accumulate(row.coef1)
-        s1 = _fma32(np.float32(row.chain), conv.float().numpy(), s1)
+        s1 = BM.fma32(np.float32(row.chain), conv.float().numpy(), s1)
         if use1:
-            s1 = _fma32(np.float32(row.zeta1), z1, s1)
+            s1 = BM.fma32(np.float32(row.zeta1), z1, s1)
         return {"out1": rounded(s1, td)}
     s0 = accumulate(row.coef0)
     if use0:
-        s0 = _fma32(np.float32(row.zeta0), z0, s0)
+        s0 = BM.fma32(np.float32(row.zeta0), z0, s0)
     if case.family == "k1":
         return {"out0": rounded(s0, td)}
     s1 = accumulate(row.coef1)
-    s1 = _fma32(np.float32(row.chain), s0, s1)
+    s1 = BM.fma32(np.float32(row.chain), s0, s1)
     if use1:
-        s1 = _fma32(np.float32(row.zeta1), z1, s1)
+        s1 = BM.fma32(np.float32(row.zeta1), z1, s1)
     return {"out0": rounded(s0, torch.float32), "out1": rounded(s1, td)}
 
 

@@ -11,6 +11,11 @@ gives other bits; tests/test_bit_model_host.py counts, on the host, how many ele
   skr_step_launch_masked                  masked_kernel_v1; masked_kernel_gen ("one_trip" 0, ragged samples, fp32 operands under a 16-bit mask)
   skr_step_backward_launch                step_bwd_k1, step_bwd_general; one and two incoming gradients
   skr_step_masked_backward_launch         masked_bwd_k1, masked_bwd_general
+  skr_step_launch, rounded conversion     step_kernel_rk1 (128 and 256 threads, K = 2, 4, 5, 8, the noisy last stage), step_kernel_rk (1, 2, 4
+  (Runge-Kutta stages)                    vectors per lane, tile and no tile), step_kernel<..., CONV> (ragged body and scalar tail, more than 8
+                                          operands, mixed dtypes, noise, acc_f64 out0): the routing table in front of the stage tests below.
+                                          The table forms of step_kernel_rk1 stand on these through tests/test_table_forms_gpu.py, which holds
+                                          every table instantiation bit for bit to the narrow launch.
 
 In-kernel noise.  The Philox normals are not reproducible on the host to the bit (the oracle bar is table_cases.NORMAL_BAR), so they
 are an INPUT of the model: an fp32-output launch of the same geometry, seeds and stream over one operand of zeros with coefficient 0
@@ -18,6 +23,7 @@ and zeta0 = 1 returns exactly z.  The extraction is anchored (the one-trip, the 
 within the bar of the oracle's normals), then every noisy launch must have the bits of the model fed with that z."""
 
 import contextlib
+from dataclasses import dataclass
 
 import bit_cases as BC
 import bit_model as BM
@@ -331,13 +337,18 @@ SEEDS = TC.seeds_for(BC.SAMPLES)
 _z_cache = {}
 
 
-def extract_z(stream, **switches):
-    "the normals a launch of ROWS elements in samples of BC.SAMPLE draws from `stream`: an fp32 launch over zeros at coefficient 0 with zeta0 = 1"
-    key = (stream, tuple(sorted(switches.items())))
+def extract_z(stream, sample=BC.SAMPLE, numel=ROWS, **switches):
+    """the normals a launch of `numel` elements in samples of `sample` draws from `stream` under the seeds TC.seeds_for(numel // sample)
+    (ROWS elements in samples of BC.SAMPLE: SEEDS): an fp32 launch over zeros at coefficient 0 with zeta0 = 1"""
+    key = (stream, sample, numel, tuple(sorted(switches.items())))
     if key not in _z_cache:
         with tuning(**switches):
-            (_z_cache[key],) = launch([torch.zeros(ROWS)], [0.0], torch.float32, zeta0=1.0, stream0=stream, seeds=TC.seeds_tensor(SEEDS), sample=BC.SAMPLE)
+            (_z_cache[key],) = launch([torch.zeros(numel)], [0.0], torch.float32, zeta0=1.0, stream0=stream, seeds=TC.seeds_tensor(TC.seeds_for(numel // sample)), sample=sample)
     return _z_cache[key]
+
+
+PATTERNS3 = 65536 // BC.SAMPLE * BC.SAMPLE  # the patterns in samples of three chunks: the first 61 440
+STAGE_GEOMETRIES = ((BC.CHUNK, ROWS), (BC.CHUNK, BC.CHUNK), (BC.CHUNK, 65536), (BC.SAMPLE, PATTERNS3))  # (sample, numel) beside (BC.SAMPLE, ROWS)
 
 
 def test_the_extracted_normals_are_anchored():
@@ -349,6 +360,16 @@ def test_the_extracted_normals_are_anchored():
         worst = float(np.abs(z.double().numpy() - ref).max())
         print(f"stream {stream}: device normal - oracle normal, worst {worst:.3g} (bar {TC.NORMAL_BAR})")
         assert worst <= TC.NORMAL_BAR, (stream, worst)
+    # the geometries of the noisy stage launches: samples of one chunk, and the 65 536 patterns in samples of one and of three chunks
+    stream = TC.STREAMS[1]
+    for sample, numel in STAGE_GEOMETRIES:
+        z = extract_z(stream, sample, numel)
+        for switches in ({"one_trip": 0}, {"tile": 0}):
+            BM.same_bits(extract_z(stream, sample, numel, **switches), z, what=f"normals of stream {stream}, samples of {sample} in {numel}, under {switches}")
+        ref = np.concatenate([ON.philox_normal(s, stream, sample) for s in TC.seeds_for(numel // sample)])
+        worst = float(np.abs(z.double().numpy() - ref).max())
+        print(f"stream {stream}, samples of {sample} in {numel}: device normal - oracle normal, worst {worst:.3g} (bar {TC.NORMAL_BAR})")
+        assert worst <= TC.NORMAL_BAR, (stream, sample, numel, worst)
 
 
 def check_noisy(got, model, z, what, operands=()):
@@ -414,3 +435,215 @@ def test_noisy_two_outputs(name):
                 what = f"{name} noisy two outputs {na}+{nb} zetas=({zeta0}, {zeta1}) {mode}"
                 BM.same_bits(g0, BM.step_two(c0, c1, chain, ops, zeta0, z0, zeta1, z1, torch.float32, dt)[0], operands=ops, what=what + " out0")
                 check_noisy(g1, lambda zz: BM.step_two(c0, c1, chain, ops, zeta0, z0, zeta1, zz, torch.float32, dt)[1], z1, what + " out1", ops)
+
+
+# ---- Runge-Kutta stage launches -------------------------------------------------------------------------------------------------------
+# out0 = convert_rounded(in[0], in[1]), out1 = sum c1[k] in_k + chain * out0 (+ zeta1 z) against bit_model.rk_stage, both outputs over all
+# elements.  Which kernel a launch reaches (launch, launch_rk of skr_step.hip; launch_one_trip_rk, one_trip_ok of skr_step_fast.hip):
+#
+#   step_kernel_rk1<BLK>    uniform dtype in and out, 2 <= n_terms <= 8, numel % 2048 == 0, "one_trip" on (fp32: "tile" on too);
+#                           BLK = 128 when "rk_blk" == 128 or ("rk_blk" == 0 and n_terms <= 6), else 256; with noise: zeta0 == 0 and
+#                           sample_numel % 2048 == 0 -- bps_shift >= 0 for a power-of-two number of chunks per sample, else the dividing form
+#   step_kernel_rk<UV>      the same launches without noise when the one-trip kernel is not taken: "one_trip" 0, or numel % 8 == 0 and
+#                           numel % 2048 != 0 with every switch at its default, or fp32 with "tile" 0; UV = "rk_uv" (0: 1);
+#                           fp32 in the tile layout when "tile" is on and numel % 512 == 0
+#   step_kernel<..., CONV>  everything else: numel % 8 != 0 (vector body and the scalar tail of store_scalar), n_terms > 8, an fp32
+#                           operand behind a 16-bit pair, an fp32 out1 beside 16-bit operands, noise with "one_trip" 0, acc_f64
+#
+# The table forms of step_kernel_rk1 need no cases here: tests/test_table_forms_gpu.py holds every table instantiation bit for bit to the
+# narrow launch (skr_step_launch) of the row's scalars, and the narrow launch is what this file puts under the model.
+# acc_f64 launches: out0 alone is claimed (convert in the operands' dtype, or in float64 for fp64 operands); out1 needs an exact float64 fma.
+
+@dataclass(frozen=True)
+class Stage:
+    what: str
+    ops: tuple
+    coef1: tuple
+    chain: float
+    kinds: tuple
+    k: tuple
+    zeta1: float = 0.0
+
+
+def launch_stage(dev_ops, c, out1=None, stream1=0, seeds=None, sample=None, acc_f64=False, noisy=False):
+    "one skr_step_launch with a rounded conversion over operands on the device; (out0, out1) on the host"
+    n, da = len(dev_ops), dev_ops[0].dtype
+    na = next((j for j, t in enumerate(dev_ops) if t.dtype != da), n)
+    numel = dev_ops[0].numel()
+    assert all(t.numel() == numel and t.is_contiguous() for t in dev_ops) and all(t.dtype == dev_ops[-1].dtype for t in dev_ops[na:])
+    plan = _hip.StepPlanC()
+    plan.n_terms, plan.n_group_a, plan.dtype_a = n, na, CODE[da]
+    plan.dtype_b = CODE[dev_ops[-1].dtype] if na < n else CODE[da]
+    plan.out0_dtype, plan.out1_dtype, plan.acc_f64 = CODE[da], CODE[out1 if out1 is not None else da], int(acc_f64)
+    for j in range(n):
+        plan.coef0[j], plan.coef1[j] = 0.0, c.coef1[j]
+    plan.chain, plan.convert_to, plan.convert_from = c.chain, *c.kinds
+    for i in range(4):
+        plan.convert_k[i] = c.k[i]
+    if noisy:
+        plan.noise_mode, plan.zeta1, plan.stream1 = 1, c.zeta1, stream1
+    plan.sample_numel = sample if sample is not None else numel
+    o0 = torch.full((numel,), 7.0, dtype=da, device=DEV)
+    o1 = torch.full((numel,), 7.0, dtype=out1 if out1 is not None else da, device=DEV)
+    _hip.launch_step(plan, list(dev_ops), o0, o1, seeds.to(DEV) if seeds is not None else None, numel, DEV)
+    torch.cuda.synchronize()
+    return o0.cpu(), o1.cpu()
+
+
+# the shapes of a launch over a set of whole chunks (host or device tensors)
+SHAPES = {
+    "whole": lambda t: t,
+    "eights": lambda t: t[: t.numel() - 1032],  # a multiple of 8, not of 512
+    "tiles": lambda t: t[: t.numel() - 512],  # a multiple of 512, not of 2048
+    "ragged": BC.ragged,  # three elements more than whole chunks
+}
+RK1_ROUTES = [("rk1 128 threads", {"rk_blk": 128}, "whole"), ("rk1 256 threads", {"rk_blk": 256}, "whole")]
+RK_ROUTES = [(f"rk {uv} per lane", {"one_trip": 0, "rk_uv": uv}, "whole") for uv in (1, 2, 4)] + [("rk, all default", {}, "eights"), ("rk 4 per lane, eights", {"rk_uv": 4}, "eights")]
+RK_ROUTES32 = [("rk no tile", {"tile": 0}, "whole"), ("rk 2 per lane no tile", {"one_trip": 0, "tile": 0, "rk_uv": 2}, "whole"), ("rk tiles", {}, "tiles"), ("rk 4 per lane tiles", {"rk_uv": 4}, "tiles")]
+ONE_TRIP = ("rk1", {}, "whole")
+GENERAL = ("general, ragged", {}, "ragged")
+
+
+def uniform_routes(name):
+    return RK1_ROUTES + RK_ROUTES + (RK_ROUTES32 if name == "fp32" else []) + [GENERAL]
+
+
+_stage_models = {}
+
+
+def stage_model(c: Stage, out1=None, z1=None, key=None):
+    "bit_model.rk_stage of a case, computed once (the model is elementwise: every shape of a launch is a slice of it)"
+    key = (c.what, out1, key)
+    if key not in _stage_models:
+        assert (z1 is None) == (key[2] is None)
+        _stage_models[key] = BM.rk_stage(c.coef1, c.chain, c.ops, c.kinds, c.k, c.zeta1 if z1 is not None else None, z1, out=out1)
+    return _stage_models[key]
+
+
+def check_stage(c: Stage, routes, out1=None):
+    w0, w1 = stage_model(c, out1)
+    dev = on_device(c.ops)
+    for label, switches, shape in routes:
+        cut = SHAPES[shape]
+        with tuning(**switches):
+            g0, g1 = launch_stage([cut(t).contiguous() for t in dev], c, out1)
+        seen = [cut(t) for t in c.ops]
+        BM.same_bits(g0, cut(w0), operands=seen, what=f"{c.what}, {label}: out0")
+        BM.same_bits(g1, cut(w1), operands=seen, what=f"{c.what}, {label}: out1")
+
+
+def conversion_stages(name, pairs, k_sets=None, operands=None):
+    """the dtype's conversion inputs (BC.conversion_inputs) as stage launches: per input, k set and kinds pair one case; K runs over
+    BC.STAGE_KS with the case, seeded normals behind the pair, coef1 as BC.random_coefs, the chains of table_cases.CHAINS.
+    operands(pair, K) -> (operands, what) builds another operand list around the pair."""
+    out = []
+    for i, (what, s, o, ks) in enumerate(BC.conversion_inputs(name)):
+        for j, k in enumerate(ks):
+            if k_sets is not None and j not in k_sets:
+                continue
+            for kinds in pairs:
+                at = 4 * kinds[0] + kinds[1] + i + j
+                K = BC.STAGE_KS[at % len(BC.STAGE_KS)]
+                ops, how = operands((s, o), K) if operands is not None else (BC.stage_operands(name, (s, o), K), f"K={K}")
+                out.append(Stage(f"{name} {what} kinds={kinds} k[{j}] {how}", tuple(ops), tuple(BC.stage_coefs(len(ops))), TC.CHAINS[at % len(TC.CHAINS)], kinds, k))
+    return out
+
+
+def cancelling_stages(name, Ks=BC.STAGE_KS, last=None):
+    "BC.stage_cancelling at every K, under kinds (1, 2) and one of BC.KINDS_FIVE; last(s) -> the last operand in another dtype"
+    out = []
+    for i, K in enumerate(Ks):
+        ops, coefs, chain, zeta1 = BC.stage_cancelling(name, K)
+        if last is not None:
+            ops = (*ops[:-1], last(ops[-1]))
+        for kinds in ((1, 2), BC.KINDS_FIVE[i % len(BC.KINDS_FIVE)]):
+            out.append(Stage(f"{name} cancelling K={K} kinds={kinds}{'' if last is None else ' wide last'}", ops, tuple(coefs), chain, kinds, BC.CONVERT_KS[i % 2], zeta1))
+    return out
+
+
+REST = [kd for kd in BC.KINDS if kd not in BC.KINDS_FIVE]
+
+
+@pytest.mark.parametrize("name", ("bf16", "fp16", "fp32"))
+def test_stage_conversion(name):
+    """16-bit: every bit pattern as s against a permutation as o and the reverse; fp32: normals, and the specials block (with k that
+    overflow products and underflow quotients).  All 15 kinds pairs through the one-trip kernel and the general kernel's ragged launch,
+    the five pairs that hold every operation through every other route."""
+    for c in conversion_stages(name, BC.KINDS_FIVE):
+        check_stage(c, uniform_routes(name))
+    for c in conversion_stages(name, REST):
+        check_stage(c, [ONE_TRIP, GENERAL])
+
+
+@pytest.mark.parametrize("name", ("bf16", "fp16", "fp32"))
+def test_stage_cancelling(name):
+    "the self-cancelling s at K = 2, 4, 5, 8 through every route: the order of the operands, the place of the chain, whole fmas"
+    for c in cancelling_stages(name):
+        check_stage(c, uniform_routes(name))
+
+
+@pytest.mark.parametrize("name", ("bf16", "fp16", "fp32"))
+def test_stage_general_kernel_launches(name):
+    """step_kernel<..., CONV> on the launches no stage kernel takes: nine operands (whole chunks: the vector body alone; fp32 with and
+    without the tile layout); a 16-bit pair with one fp32 operand behind it; an fp32 out1 beside 16-bit operands"""
+    both = [("general", {}, "whole"), GENERAL]
+    nine = both + ([("general no tile", {"tile": 0}, "whole")] if name == "fp32" else [])
+    many = lambda pair, K: (BC.stage_operands(name, pair, 9), "K=9")  # noqa: E731
+    for c in conversion_stages(name, BC.KINDS_FIVE, operands=many) + cancelling_stages(name, Ks=(9,)):
+        check_stage(c, nine)
+    if name == "fp32":
+        return
+    wide = lambda pair, K: ((*pair, BC.stage_extras("fp32", pair[0].numel())[0]), "fp32 operand")  # noqa: E731
+    for c in conversion_stages(name, BC.KINDS_FIVE, operands=wide) + cancelling_stages(name, Ks=(3, 5), last=lambda s: s.float()):
+        check_stage(c, both)
+    for c in conversion_stages(name, BC.KINDS_FIVE, k_sets=(0,)) + cancelling_stages(name, Ks=(2, 5)):
+        check_stage(c, both, out1=torch.float32)
+
+
+def noisy_stage_cases(name, sample):
+    "(case, numel): the chain as the canceller and the self-cancelling s (ROWS elements); the conversion inputs under the first k set"
+    ops, coefs, chain, zeta1, kinds, k = BC.stage_chain_cancels(name)
+    cases = [Stage(f"{name} chain cancels", ops, tuple(coefs), chain, kinds, k, zeta1)] + cancelling_stages(name, Ks=(2, 5))
+    for c in conversion_stages(name, BC.KINDS_FIVE, k_sets=(0,)):
+        cases.append(Stage(c.what, c.ops, c.coef1, c.chain, c.kinds, c.k, TC.ZETAS[2]))
+    return [c for c in cases if c.ops[0].numel() // sample * sample > 0]
+
+
+@pytest.mark.parametrize("sample", (BC.CHUNK, BC.SAMPLE))
+@pytest.mark.parametrize("name", ("bf16", "fp16", "fp32"))
+def test_noisy_stage(name, sample):
+    """the last stage of a stochastic step: zeta1 != 0, the draw on out1 alone.  Samples of one chunk (chunk -> sample by a shift) and of
+    three (by a division), step_kernel_rk1 at both block sizes and the general kernel ("one_trip" 0; fp32 also without the tile layout)"""
+    stream = TC.STREAMS[1]
+    routes = [(label, switches) for label, switches, _ in RK1_ROUTES] + [("general", {"one_trip": 0})] + ([("general no tile", {"tile": 0})] if name == "fp32" else [])
+    for c in noisy_stage_cases(name, sample):
+        numel = c.ops[0].numel() // sample * sample
+        z1 = extract_z(stream, sample, numel)
+        seeds = TC.seeds_tensor(TC.seeds_for(numel // sample))
+        cut = Stage(c.what, tuple(t[:numel] for t in c.ops), c.coef1, c.chain, c.kinds, c.k, c.zeta1)
+        w0, w1 = stage_model(cut, None, z1, key=(sample, numel))
+        dev = on_device(cut.ops)
+        for label, switches in routes:
+            with tuning(**switches):
+                g0, g1 = launch_stage(dev, cut, None, stream, seeds, sample, noisy=True)
+            BM.same_bits(g0, w0, operands=cut.ops, what=f"{c.what}, noisy, samples of {sample}, {label}: out0")
+            BM.same_bits(g1, w1, operands=cut.ops, what=f"{c.what}, noisy, samples of {sample}, {label}: out1")
+
+
+@pytest.mark.parametrize("name", BC.STAGE_DTYPES)
+def test_stage_acc_f64_derivative(name):
+    """acc_f64 launches (the general kernel, float64 sums): out0 is the conversion in the operands' dtype -- convert_rounded in fp32 with
+    both roundings for 16-bit and fp32 operands, in float64 for fp64 operands -- on whole chunks and three elements more.  out1 is not
+    compared (the float64 sum needs a model of its own)."""
+    dt = BC.STAGE_DTYPES[name]
+    for what, s, o, ks in BC.conversion_inputs(name):
+        extras = [t.to(dt) for t in BC.stage_extras("fp32" if name == "fp64" else name, s.numel())[:3]]
+        dev = on_device([s, o, *extras])
+        for j, k in enumerate(ks):
+            for kinds in BC.KINDS_FIVE:
+                want = BM.convert(dt, s, o, kinds, k)
+                for K in (2, 5):
+                    c = Stage(f"{name} acc_f64 {what} kinds={kinds} k[{j}] K={K}", (), tuple(BC.stage_coefs(K)), TC.CHAINS[j], kinds, k)
+                    for label, shape in (("whole", "whole"), ("ragged", "ragged")):
+                        g0, _ = launch_stage([SHAPES[shape](t).contiguous() for t in dev[:K]], c, acc_f64=True)
+                        BM.same_bits(g0, SHAPES[shape](want), operands=[SHAPES[shape](s), SHAPES[shape](o)], what=f"{c.what} {label}: out0")

@@ -62,7 +62,7 @@ def ratios(sample: Sample, outs: dict) -> float:
 
 @pytest.mark.parametrize("dtype", list(TC.DTYPES))
 def test_the_reference_accepts_the_kernels_order(dtype):
-    "an fp32 evaluation in the kernels' order (table_cases._fma32 says how faithful) meets the float64 bound with ratio <= 1"
+    "an fp32 evaluation in the kernels' order (on bit_model.fma32, the correctly rounded fma) meets the float64 bound with ratio <= 1"
     worst = 0.0
     for case in CASES:
         if dtype not in TC.FAMILY_DTYPES[case.family]:

@@ -469,6 +469,46 @@ int skr_step_launch_guided(const skr_step_plan* plan, const void* const* inputs,
                            const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * The guided step with device-resident scalars: skr_step_launch_guided as skr_step_launch_indexed and
+ * skr_step_launch_indexed_per_sample make skr_step_launch, so that one captured classifier-free-guidance loop serves any schedule of its
+ * length AND any guidance scale, keeps several of them resident and lets every sample follow its own.
+ * What is frozen and what is data: `plan` fixes the structure only -- operand count and dtype groups, out0_dtype (out1_dtype must be
+ * SKR_NONE), noise_mode, sample_numel, acc_f64 == 0, chain == zeta1 == 0, convert_* == 0.  guide->cond, guide->guided_out and guide->slot
+ * are launch arguments, frozen into a captured graph (a device-resident slot would index the kernel's register arrays at run time).
+ * The plan's coef0 / zeta0 / stream0 values and guide->scale are ignored; when the kernel runs it reads coef0[k], zeta0, stream0 and the
+ * guidance scale from
+ *     indexed      rows_dev[(index_dev ? index_dev[0] : 0) + row_offset]
+ *     per sample   rows_dev[sample_index_dev[s] + row_offset]            for the workgroups of sample s
+ * skr_step_row is used unchanged.  The guidance scale is the row's convert_k[0]: a guided launch has no rounded conversion (the plan's
+ * convert_* must be zero), so that field is free.  The row's coef1, chain, zeta1, stream1 and convert_k[1..3] are not read.
+ * Arithmetic: that of skr_step_launch_guided, and bit for bit what skr_step_launch_guided gives with the row's values in its plan and in
+ * guide->scale: g is narrowed to fp32 once; the row's doubles are narrowed on the device with the conversion the host applies to a plan's
+ * doubles; the operands are accumulated in slot order, one fma each, with p in the place of inputs[slot]; the noise comes last -- a row
+ * whose zeta0 is exactly zero skips the draw, as in the other row forms --; one rounding by the store; guided_out = p when guided_out is
+ * given.  A sample of a per-sample launch has the bits the indexed launch gives it with that row for the whole batch.
+ * Covered: exactly what the one-trip kernel of skr_step_launch_guided takes -- whole 2048-element chunks (samples made of whole chunks when
+ * noise_mode == 1), one 16- or 32-bit dtype for operands, cond and both outputs, fp32 arithmetic, 1..SKR_ROW_TERMS operands.  In the
+ * per-sample entry a workgroup must lie inside one sample: plan->sample_numel must be a positive multiple of 2048 that divides numel, with
+ * or without noise (SKR_ERR_SHAPE / SKR_ERR_UNSUPPORTED otherwise).  Anything else is SKR_ERR_UNSUPPORTED -- ragged sizes, two dtype
+ * groups, fp64, acc_f64, the guidance-only form, "one_trip" 0 and fp32 tensors with "tile" 0 included: there is no grid-stride row form.
+ * Checked before the launch, without dereferencing device memory, in the order and with the codes of skr_step_launch_guided; on top of
+ * them a NULL rows_dev is SKR_ERR_NULL, a NULL sample_index_dev in the per-sample entry is SKR_ERR_NULL (both beside the NULL plan), a
+ * launch with noise_mode == 1 needs seeds_dev whatever its rows hold, and a negative row_offset is SKR_ERR_UNSUPPORTED.
+ * Index validity is the caller's business, as with skr_step_launch_indexed: index_dev[0] + row_offset, and every
+ * sample_index_dev[s] + row_offset, must name a row of the table.  The kernel neither checks nor clamps an index -- an entry outside
+ * the table reads whatever lies there (or faults) -- so validate on the host before uploading (skrample_amd.graphs.CapturedLoop does).
+ */
+int skr_step_launch_guided_indexed(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                   const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                   const int32_t* index_dev /* device int32, may be NULL */, int32_t row_offset, void* stream);
+
+int skr_step_launch_guided_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                              const skr_step_guidance* guide, const uint64_t* seeds_dev, int64_t numel,
+                                              const skr_step_row* rows_dev,
+                                              const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                              int32_t row_offset, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

@@ -37,6 +37,8 @@ EXPORTS = (
     "skr_step_launch_masked_rolling",
     "skr_step_launch_masked_channels_last",
     "skr_step_launch_guided",
+    "skr_step_launch_guided_indexed",
+    "skr_step_launch_guided_indexed_per_sample",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -184,12 +186,16 @@ class StepGuidanceC(ctypes.Structure):
     ]
 
 
-def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None) -> tuple:
+def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None, guide: "StepGuidanceC | None" = None) -> tuple:
     """what a captured launch freezes: everything of a plan except the scalars a row carries (`sample_numel` = False: and the sample size).
     A masked launch (`mask`: its descriptor) adds that it is one, the mask's dtype and whether one mask serves the whole batch
-    (batch_stride == 0), and -- shape-like, dropped with the sample size -- the mask's elements per sample."""
+    (batch_stride == 0), and -- shape-like, dropped with the sample size -- the mask's elements per sample.
+    A guided launch (`guide`: its descriptor) adds that it is one, the operand the guided value replaces (`slot`) and whether that value
+    is stored; its scale is a row value."""
     plain = (plan.n_terms, plan.n_group_a, plan.dtype_a, plan.dtype_b, plan.out0_dtype, plan.out1_dtype, plan.acc_f64, plan.noise_mode,
              plan.sample_numel if sample_numel else None, plan.convert_to, plan.convert_from)  # fmt: skip
+    if guide is not None:
+        return (*plain, "guided", guide.slot, bool(guide.guided_out))
     if mask is None:
         return plain
     return (*plain, "masked", mask.dtype, mask.batch_stride == 0, mask.mask_numel if sample_numel else None)
@@ -208,14 +214,19 @@ class IndexedRows:
     `batch` (a per-sample capture): the emitted launches are skr_step_launch_indexed_per_sample launches, and `sample_index_dev`
     -- int32[batch], beside `index_dev` -- holds every sample's `slot * length`; sample b of the captured batch reads row
     `sample_index_dev[b] + k`.
+    `guided` (a capture with guidance): guided launches go through the recorder as well (skr_step_launch_guided_indexed[_per_sample]),
+    each row carrying its launch's guidance scale.
 
     mode "record": launches run normally and append one row each (their structure is remembered);
     mode "emit"  : launches become indexed launches reading row `base + k` (k = position in the loop) -- used under graph capture;
     mode "refill": launches run normally (on whatever tensors the dry run uses) and overwrite row `slot*length + k` after checking
                    that the structure is the captured one -- how a captured loop is re-targeted to another schedule."""
 
-    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None):
+    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None, guided: bool = False):
         self.device, self.slots, self.batch = device, slots, batch
+        # a capture with guidance: launch_step_guided goes through this hook (skr_step_launch_guided_indexed[_per_sample]), and a row
+        # carries the guidance scale in convert_k[0]; any other hook refuses a guided launch
+        self.guided = guided
         self.mode, self.cursor, self.length = "record", 0, 0
         self.structures: list[tuple] = []  # plan_structure of every recorded launch,
         self.shapeless: list[tuple] = []  # and without its sample size (what a refill must match)
@@ -226,7 +237,8 @@ class IndexedRows:
         self.slot = 0
 
     @staticmethod
-    def row_from(plan: StepPlanC) -> StepRowC:
+    def row_from(plan: StepPlanC, scale: float | None = None) -> StepRowC:
+        "the row of a launch; `scale`: a guided one's guidance scale, kept in convert_k[0] (such a plan has no rounded conversion)"
         if plan.n_terms > ROW_TERMS:
             raise SkrampleHipError(f"a launch with {plan.n_terms} operands does not fit a device-resident row ({ROW_TERMS})")
         row = StepRowC()
@@ -235,6 +247,8 @@ class IndexedRows:
         row.chain, row.zeta0, row.zeta1, row.stream0, row.stream1 = plan.chain, plan.zeta0, plan.zeta1, plan.stream0, plan.stream1
         for k in range(4):
             row.convert_k[k] = plan.convert_k[k]
+        if scale is not None:
+            row.convert_k[0] = scale
         return row
 
     def finish_recording(self) -> None:
@@ -277,12 +291,33 @@ class IndexedRows:
             return "masked rows need at least one operand"
         return None
 
-    def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int, mask: "StepMaskC | None" = None) -> int:
-        "one launch of the loop; `mask` (its descriptor): a masked one (skr_step_launch_masked and its row forms; out1_ptr is None)"
+    def _uncovered_guided(self, plan: StepPlanC, numel: int) -> str | None:
+        "why the guided row kernel does not cover this launch (include/skrample_hip.h, skr_step_launch_guided_indexed), or None"
+        if plan.out0_dtype == NONE:
+            return ("the guidance-only launch has no row form: it serves the two-output samplers (UniPC, SPC), a guided step under set_inpaint, "
+                    "compute_scale=None and channels-last or strided operands")
+        if plan.acc_f64:
+            return "guided rows are evaluated in float32, not under compute_scale=float64"
+        one = plan.dtype_a
+        if (plan.n_group_a != plan.n_terms and plan.dtype_b != one) or plan.out0_dtype != one or one not in (BF16, F16, F32):
+            return "guided rows need one 16- or 32-bit dtype for operands, cond and both outputs"
+        if numel % PER_SAMPLE_CHUNK != 0 or (plan.noise_mode == 1 and (plan.sample_numel <= 0 or plan.sample_numel % PER_SAMPLE_CHUNK != 0)):
+            return f"guided rows need whole {PER_SAMPLE_CHUNK}-element chunks, not {numel} elements in samples of {plan.sample_numel}"
+        if plan.n_terms < 1:
+            return "guided rows need at least one operand"
+        return None
+
+    def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int, mask: "StepMaskC | None" = None,
+               guide: "StepGuidanceC | None" = None) -> int:
+        """one launch of the loop; `mask` (its descriptor): a masked one (skr_step_launch_masked and its row forms; out1_ptr is None);
+        `guide` (its descriptor): a guided one (skr_step_launch_guided and its row forms; out1_ptr is None), whose scale goes into the row"""
         k = self.cursor
         self.cursor += 1
+        scale = guide.scale if guide is not None else None
 
         def run_now() -> int:  # the launch itself, with the plan's own scalars
+            if guide is not None:
+                return lib.skr_step_launch_guided(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, stream_ptr)
             if mask is not None:
                 return lib.skr_step_launch_masked(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, stream_ptr)
             return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
@@ -296,22 +331,26 @@ class IndexedRows:
                 why = self._uncovered(plan, mask, numel)
                 if why is not None:  # (what skr_step_launch_masked_indexed would answer during the capture)
                     raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
-            row = self.row_from(plan)
-            self.structures.append(plan_structure(plan, mask=mask))
-            self.shapeless.append(plan_structure(plan, sample_numel=False, mask=mask))
+            if guide is not None:
+                why = self._uncovered_guided(plan, numel)
+                if why is not None:  # (what skr_step_launch_guided_indexed would answer during the capture)
+                    raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
+            row = self.row_from(plan, scale)
+            self.structures.append(plan_structure(plan, mask=mask, guide=guide))
+            self.shapeless.append(plan_structure(plan, sample_numel=False, mask=mask, guide=guide))
             self.host.append(row)
             return run_now()
         if k >= self.length:
             raise SkrampleHipError("more launches than the captured loop has")
         if self.mode == "refill":
-            found = plan_structure(plan, sample_numel=False, mask=mask)
+            found = plan_structure(plan, sample_numel=False, mask=mask, guide=guide)
             if mask is not None and len(found) == len(self.shapeless[k]) and numel == plan.sample_numel:
                 found = (*found[:-2], self.shapeless[k][-2], found[-1])  # (a dry run on one sample has no batch stride to compare)
             if found != self.shapeless[k]:
                 raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
-            self.host[self.slot * self.length + k] = self.row_from(plan)
+            self.host[self.slot * self.length + k] = self.row_from(plan, scale)
             return run_now()
-        if plan_structure(plan, mask=mask) != self.structures[k]:
+        if plan_structure(plan, mask=mask, guide=guide) != self.structures[k]:
             raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
         if self.sample_index_dev is not None:
             if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
@@ -319,9 +358,13 @@ class IndexedRows:
                 plan.sample_numel = numel // self.batch
             if numel != self.batch * plan.sample_numel:
                 raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {self.batch} samples of {plan.sample_numel} the per-sample index holds")
+            if guide is not None:
+                return lib.skr_step_launch_guided_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
             if mask is not None:
                 return lib.skr_step_launch_masked_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
             return lib.skr_step_launch_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
+        if guide is not None:
+            return lib.skr_step_launch_guided_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
         if mask is not None:
             return lib.skr_step_launch_masked_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
         return lib.skr_step_launch_indexed(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
@@ -409,6 +452,9 @@ def load() -> ctypes.CDLL:
         lib.skr_step_launch_masked_channels_last.restype = ctypes.c_int
         lib.skr_step_launch_guided.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp]
         lib.skr_step_launch_guided.restype = ctypes.c_int
+        for guided_table_launch in (lib.skr_step_launch_guided_indexed, lib.skr_step_launch_guided_indexed_per_sample):
+            guided_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp, vp, i32, vp]
+            guided_table_launch.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -569,15 +615,22 @@ def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond:
     p = uncond + scale * (cond - uncond), rounded as torch's three tensor ops round it, takes its place in the step's sum; `guided_out`
     (or None) receives p.  `out` None with a plan whose out0_dtype is NONE is the guidance-only form.
     A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, cond, guided_out, scale, slot) -- ten entries no step program
-    is built from.  Under the indexed-rows hook (captured loops with device-resident scalars) it raises: a guided launch has no row form."""
+    is built from.  Under an indexed-rows hook created for a guided capture (IndexedRows(guided=True): capture_sampling_loop with
+    `guidance_scale`) the launch is recorded, emitted as skr_step_launch_guided_indexed[_per_sample] -- the scale a row value -- or
+    refilled, as a plain step launch is (IndexedRows.launch).  Under any other hook it raises: that loop was captured without guidance."""
     lib = load()
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError("guided steps are not part of captured loops: skr_step_launch_guided has no form that reads device-resident rows")
+    rows = getattr(_hooks, "indexed", None)
+    if rows is not None and not getattr(rows, "guided", False):
+        raise SkrampleHipError("guided steps are not part of captured loops unless the loop is captured for them: pass guidance_scale= to capture_sampling_loop")
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append((plan, list(operands), out, None, seeds, numel, cond, guided_out, scale, slot))
     desc = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
-    status = lib.skr_step_launch_guided(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(desc), _ptr(seeds), numel, current_stream_ptr(device))
+    arr, stream = _operand_array(operands), current_stream_ptr(device)
+    if rows is not None:
+        status = rows.launch(lib, plan, arr, _ptr(out), None, _ptr(seeds), numel, stream, guide=desc)
+    else:
+        status = lib.skr_step_launch_guided(ctypes.byref(plan), arr, _ptr(out), ctypes.byref(desc), _ptr(seeds), numel, stream)
     check(status, "skr_step_launch_guided")
 
 

@@ -16,38 +16,13 @@
 // Both evaluate the same operations in the same order on every element, so they agree bit for bit where both apply.
 // One exception follows torch's own device op: for fp16 the elements past the last whole 2048 of the tensor have  g * d  rounded once
 // (mul_once_f16 below).  Only the general kernel meets such elements.
-#include "skr_step_common.h"
+// The row forms of the one-trip kernel (skr_step_launch_guided_indexed[_per_sample]) are skr_step_guided_rows.hip; guided_value and the
+// entry checks, which both files use, are skr_step_guided.h.
+#include "skr_step_guided.h"
 #include "skr_device.h"
 
 namespace skr {
 
-constexpr int guided_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : 16)); }
-
-// an individually rounded add: the twin of sub_ / mul_ (skr_step_common.h), contraction off so that no neighbour fuses with it
-__device__ __forceinline__ float add_(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ double add_(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-// torch's  uncond + g * (cond - uncond)  on tensors of dtype T: three ops in fp32, each result rounded to fp32 and then to T.
-// Each fp32 result is pinned in a register of its own: three plain instructions per element, neither fused nor paired into packed ones
-// (a packed fp32 instruction issues at 1.75x a plain one on gfx950, and the shuffles that line its operands up cost more than it saves).
-template <typename T>
-__device__ __forceinline__ float guided_value(float u, float c, float g) {
-  float d = sub_(c, u);
-  asm("" : "+v"(d));
-  d = rnd<T>(d);
-  float m = mul_(g, d);
-  asm("" : "+v"(m));
-  m = rnd<T>(m);
-  float p = add_(u, m);
-  asm("" : "+v"(p));
-  return rnd<T>(p);
-}
 // fp16 elements of the partial last block of torch's vectorised elementwise kernel (TORCH_TAIL below).  Its compiler fuses the scalar
 // multiply with the conversion there (v_fma_mixlo_f16), so  g * d  is rounded ONCE, from the exact product, where the whole blocks round
 // the fp32 product again.  (d is an fp16 value and g an fp32 one: the product has up to 35 significant bits.  c - u and u + m are sums
@@ -217,14 +192,13 @@ static void launch_guided_v1(const skr_step_plan& p, const void* const* inputs, 
   });
 }
 
-static int guided_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide, const uint64_t* seeds_dev,
-                              int64_t numel, void* stream) {
-  // the checks of skr_step_launch in its order, with what the guidance adds where the like of it stands there
-  if (!plan || !guide) return SKR_ERR_NULL;
-  const skr_step_plan& p = *plan;
-  const skr_step_guidance& gd = *guide;
+// Every check of a guided launch behind its NULL plan / guide tests: those of skr_step_launch in its order, with what the guidance adds
+// where the like of it stands there.  (Declared in skr_step_guided.h: the row entries ask it too.)
+int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
+                   bool rows, GuidedLaunch* launch) {
+  launch->step_out = launch->noise = launch->one_trip = false;
   const bool step_out = p.out0_dtype != SKR_NONE;
-  const bool noise = step_out && p.noise_mode == 1 && p.zeta0 != 0.0;
+  const bool noise = step_out && p.noise_mode == 1 && (rows || p.zeta0 != 0.0);
   if (noise && numel > 0 && !seeds_dev) return SKR_ERR_NULL;
   if (p.n_terms < 0 || p.n_terms > SKR_ROW_TERMS || p.n_group_a < 0 || p.n_group_a > p.n_terms) return SKR_ERR_TERMS;
   if (gd.slot < 0 || gd.slot >= p.n_terms) return SKR_ERR_TERMS;
@@ -244,16 +218,34 @@ static int guided_launch_impl(const skr_step_plan* plan, const void* const* inpu
   // the dtype combinations of skr_step_launch, with one output; an fp64 group (the slot's or not) needs fp64 arithmetic
   const int32_t db = p.n_group_a == p.n_terms ? p.dtype_a : p.dtype_b;
   if (!step_inputs_ok(p.dtype_a, db, p.acc_f64) || (step_out && !step_output_ok(p.out0_dtype, p.dtype_a, p.acc_f64))) return SKR_ERR_DTYPE;
-  const int32_t dt_g = gd.slot < p.n_group_a ? p.dtype_a : db;
+  launch->step_out = step_out; launch->noise = noise;
+  launch->dtype_b = db; launch->dtype_g = gd.slot < p.n_group_a ? p.dtype_a : db;
 
-  DeviceGuard device_guard(step_out ? out : gd.guided_out);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
   const int t = p.dtype_a;
   const bool one_dtype = db == t && p.out0_dtype == t && t != SKR_F64;
   if (g_tune.one_trip && step_out && !p.acc_f64 && one_dtype && (t != SKR_F32 || g_tune.tile) && numel % CHUNK == 0 && numel / CHUNK <= 0x7fffffffll &&
       (!noise || (p.sample_numel % CHUNK == 0 && p.sample_numel < (1ll << 31)))) {
-    launch_guided_v1(p, inputs, out, gd, seeds_dev, noise, numel / CHUNK, noise ? bps_shift_of(p.sample_numel / CHUNK) : 0, s);
+    launch->one_trip = true; launch->chunks = numel / CHUNK; launch->bps_shift = noise ? bps_shift_of(p.sample_numel / CHUNK) : 0;
+  }
+  return SKR_OK;
+}
+
+static int guided_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide, const uint64_t* seeds_dev,
+                              int64_t numel, void* stream) {
+  if (!plan || !guide) return SKR_ERR_NULL;
+  const skr_step_plan& p = *plan;
+  const skr_step_guidance& gd = *guide;
+  GuidedLaunch l;
+  if (const int rc = guided_prepare(p, gd, inputs, out, seeds_dev, numel, false, &l)) return rc;
+  if (numel == 0) return SKR_OK;
+  const bool step_out = l.step_out, noise = l.noise;
+  const int32_t db = l.dtype_b, dt_g = l.dtype_g;
+
+  DeviceGuard device_guard(step_out ? out : gd.guided_out);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (l.one_trip) {
+    launch_guided_v1(p, inputs, out, gd, seeds_dev, noise, l.chunks, l.bps_shift, s);
     return finish_launch();
   }
 

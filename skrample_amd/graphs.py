@@ -28,21 +28,45 @@ masked steps of an indexed capture are `skr_step_launch_masked_indexed[_per_samp
 and sigma of each step's target -- sit in the rows beside the step's own, so strength (begin index), shift and schedule are data.
 The wrapper's three in-paint tensors are the loop's static buffers (`loop.inpaint`); `loop(latents, inpaint=(mask, original,
 noise))` copies a new request's into them ahead of the replay.
+
+Classifier-free guidance (`guidance_scale=`): `model(x, t)` returns `(uncond, cond)` and the loop body is `wrapper.step_guided(uncond,
+cond, guidance_scale, t, x)`, whose guidance runs inside the step launch.  A plain capture freezes the scale into the graph; an indexed
+one keeps it in the rows (`skr_step_launch_guided_indexed[_per_sample]`), so `retarget(wrapper, slot, guidance_scale=...)` loads another
+scale beside another schedule, several scales stay resident, and with `per_sample=True` every sample of a replay follows its own.
 """
 
 from __future__ import annotations
 
+import contextlib
+import gc
 from collections import OrderedDict
 from typing import Callable, Sequence
 
 import torch
 
 
+@contextlib.contextmanager
+def _no_collection():
+    """No cyclic garbage collection while a stream captures.  A dead reference cycle may hold a CapturedLoop (an exception kept with its
+    traceback is enough), and the collector runs wherever an allocation tips its counters -- inside a step of the loop being captured, for
+    one.  Destroying a graph there ends the process: on ROCm torch's graph destructor synchronises the device, which a capturing stream
+    forbids, and the error leaves a destructor.  The cycle is collected after the capture instead."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
 class CapturedLoop:
     "replayable sampling loop: `out = loop(initial_latents, seeds=None)`"
 
     def __init__(self, graph: torch.cuda.CUDAGraph, static_in: torch.Tensor, static_out: torch.Tensor, seeds_dev: torch.Tensor | None, rows=None, runner=None,
-                 static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None, inpaint: tuple | None = None):
+                 static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None, inpaint: tuple | None = None,
+                 guidance_scale: float | None = None):
+        self.guidance_scale = guidance_scale  # the scale the loop was captured with, or None: a loop captured without guidance
         self.inpaint = inpaint  # (mask, original_samples, noise) the captured masked steps read, or None: a loop captured without in-painting
         self.graph, self.static_in, self.static_out, self.seeds_dev = graph, static_in, static_out, seeds_dev
         self.rows, self._runner = rows, runner  # _hip.IndexedRows of an indexed capture; runner(wrapper, x) = the captured loop body
@@ -92,10 +116,11 @@ class CapturedLoop:
         if self.sample_times is not None:
             self.sample_times.copy_(self._assemble_times(self._sample_slots))  # one copy, stream-ordered ahead of the replay
 
-    def retarget(self, wrapper, slot: int = 0) -> None:
+    def retarget(self, wrapper, slot: int = 0, guidance_scale: float | None = None) -> None:
         """Load the step scalars of `wrapper` (same sampler structure and number of steps as the captured one, any schedule /
         shift / begin index / stochasticity) into table slot `slot`: a dry run of its loop on one sample fills the rows, one
         small host-to-device copy publishes them.  The graph itself is untouched.
+        A loop captured with `guidance_scale` loads a scale into the slot as well: `guidance_scale`, or the captured one when None.
         A loop captured with in-painting takes a wrapper that has `set_inpaint(...)` in force itself (the dry run steps on one-sample
         views of ITS tensors); only its scalars reach the graph, which goes on reading `loop.inpaint`."""
         from . import _hip
@@ -104,10 +129,15 @@ class CapturedLoop:
             raise ValueError("capture the loop with indexed=True to re-target it")
         if not 0 <= slot < self.rows.slots:
             raise ValueError(f"slot {slot} outside 0..{self.rows.slots - 1}")
+        if guidance_scale is not None and self.guidance_scale is None:
+            raise ValueError("this loop was captured without guidance: pass guidance_scale= to capture_sampling_loop")
         self.rows.begin("refill", slot)
         _hip.indexed = self.rows
         try:
-            self._runner(wrapper, self.static_in[:1].clone())
+            if self.guidance_scale is None:
+                self._runner(wrapper, self.static_in[:1].clone())
+            else:
+                self._runner(wrapper, self.static_in[:1].clone(), guidance_scale if guidance_scale is not None else self.guidance_scale)
         finally:
             _hip.indexed = None
         if self.rows.cursor != self.rows.length:
@@ -220,7 +250,8 @@ class CapturedLoops:
 
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
-                          indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False) -> CapturedLoop:
+                          indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False,
+                          guidance_scale: float | None = None) -> CapturedLoop:
     """Capture `for t in wrapper.timesteps: x = wrapper.step(model(x, t), t, x)` for `steps` steps.
 
     `wrapper` is any scheduler wrapper of skrample_amd.diffusers; `model(x, t)` must be capturable (pure device
@@ -240,6 +271,14 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     the loop (`loop.inpaint`).  With `indexed=True` the masked row kernel must cover the launches -- samples of whole 2048-element
     chunks, one 16- or 32-bit dtype for latents and mask, a mask of a multiple of 8 elements per sample, no `compute_scale=float64`
     -- and anything else is refused during the recording pass, before the stream captures.
+
+    `guidance_scale` (None: nothing changes): `model(x, t)` returns `(uncond, cond)` and the loop body is
+    `x = wrapper.step_guided(uncond, cond, guidance_scale, t, x)`.  With `indexed=False` the scale is frozen into the graph, and every
+    sampler `step_guided` serves is captured.  With `indexed=True` the scale is a row value beside the step's scalars
+    (`loop.retarget(wrapper, slot, guidance_scale=...)`; per sample with `per_sample=True`), and the guided row kernel must cover the
+    launches: a sampler whose step is one single-output launch (Euler, DPM, Adams, UniP), contiguous latents of whole 2048-element chunks
+    in one 16- or 32-bit dtype, no `set_inpaint`, no `compute_scale=None` / `float64`.  Anything else -- UniPC and SPC among them, whose
+    guidance is a launch of its own -- is refused during the recording pass, before the stream captures.
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
@@ -247,12 +286,13 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
 
     _noise._private_vectors[0] += 1  # the loop's seed vector is overwritten in place by replays with new seeds: it is this loop's alone
     try:
-        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample)
+        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale)
     finally:
         _noise._private_vectors[0] -= 1
 
 
-def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False) -> CapturedLoop:
+def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False,
+             guidance_scale: float | None = None) -> CapturedLoop:
     dev = example.device
     static_in = example.clone()
     gen = list(seeds) if seeds is not None else None
@@ -272,13 +312,19 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     sample_times = static_times.detach().clone().unsqueeze(1).repeat(1, example.shape[0]).contiguous() if per_sample and device_timesteps else None
     model_times = [sample_times[i] for i in range(sample_times.shape[0])] if sample_times is not None else times
 
+    def step_of(w, x, t, tm, generator, scale):  # the loop body: a guided capture's network returns (uncond, cond)
+        if scale is None:
+            return w.step(model(x, tm), t, x, generator=generator, return_dict=False)[0]
+        uncond, cond = model(x, tm)
+        return w.step_guided(uncond, cond, scale, t, x, generator=generator, return_dict=False)[0]
+
     def run(x):
         wrapper.reset_run()  # same schedule, same device seed vector; history and draw counter rewound
         for t, tm in zip(times, model_times):
-            x = wrapper.step(model(x, tm), t, x, generator=gen, return_dict=False)[0]
+            x = step_of(wrapper, x, t, tm, gen, guidance_scale)
         return x
 
-    def run_other(other, x):  # the same loop body on another scheduler instance (re-targeting dry run, one sample)
+    def run_other(other, x, scale=None):  # the same loop body on another scheduler instance (re-targeting dry run, one sample); `scale`: its guidance scale
         other.set_timesteps(steps, device=dev) if device_timesteps else other.set_timesteps(steps)
         sub = gen[: x.shape[0]] if gen is not None else None
         ts = other.timesteps
@@ -290,7 +336,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         try:
             for t in ([ts[i] for i in range(ts.numel())] if device_timesteps else ts.tolist()):
                 tm = t.reshape(1).expand(x.shape[0]) if sample_times is not None else t  # (the dry run's samples: `t` of shape [1])
-                x = other.step(model(x, tm), t, x, generator=sub, return_dict=False)[0]
+                x = step_of(other, x, t, tm, sub, scale)
         finally:
             if held is not None:
                 other._inpaint = held
@@ -310,7 +356,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     if indexed:
         from . import _hip
 
-        rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None)
+        rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None, guided=guidance_scale is not None)
         _hip.indexed = rows
         try:
             rows.begin("record")
@@ -319,7 +365,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
             rows.finish_recording()
             rows.begin("emit")
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with _no_collection(), torch.cuda.graph(graph):
                 static_out = run(static_in)
         finally:
             _hip.indexed = None
@@ -327,10 +373,10 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
             raise _hip.SkrampleHipError("the captured loop issued a different number of launches than the recording pass")
     else:
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with _no_collection(), torch.cuda.graph(graph):
             static_out = run(static_in)
     seeds_dev = getattr(getattr(wrapper, "_noise_generator", None), "_seeds", None)
     from .pytorch.noise import forget_seed_vector
 
     forget_seed_vector(seeds_dev)  # the graph reads this very buffer and replays may overwrite it: no other run may share it from now on
-    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None))
+    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale)

@@ -554,6 +554,12 @@ int skr_tape_launch(const skr_tape* tape, const void* const* inputs, void* const
  * One launch (or a short fixed chain of launches) produces the whole [batch, *unit] tensor; every
  * reduction is per sample.  `seeds_dev` holds one 64-bit seed per batch item; `stream` numbers the
  * draw (the wrapper passes the step index) so repeated calls give fresh, reproducible noise.
+ * Output dtype, every entry below (skr_noise_random, _brownian, _offset, _pyramid*, _colored*, skr_colorize and the rolling forms):
+ * all arithmetic is fp32 and does not depend on out_dtype; a bf16 / fp16 element is the fp32 value rounded ONCE to nearest even, a
+ * float64 element the fp32 value widened -- on every store path (packed or scalar, any alignment of `out`, any position of the sample
+ * in the batch).  So draw(bf16 / fp16) has the bits of RNE(draw(fp32)), and a sample's bits depend on its seed and streams alone.
+ * Exception, float64 only: the Colored plane kernels exist for double in their run-time-geometry form alone and colored_inverse128
+ * not at all, so a float64 draw of those planes agrees with the fp32 draw to fp32 rounding (tests/test_noise_dtype_contract_gpu.py).
  */
 
 /* Random.generate (noise.py:58-74): out = N() */

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void random_kernel(T* out, const uint64_t* see
     const int64_t r0 = blk * 4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (r0 + j < sample_numel) out[smp * sample_numel + r0 + j] = (T)z[j];
+      if (r0 + j < sample_numel) skr::put<T>(out, smp * sample_numel + r0 + j, z[j]);
     }
   }
 }
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void brownian_kernel(T* out, const uint64_t* s
       skr::store8_from_f32<T>(out, e0 >> 3, r);
     } else {
 #pragma unroll
-      for (int j = 0; j < W; ++j) if (j < limit) out[e0 + j] = (T)r[j];
+      for (int j = 0; j < W; ++j) if (j < limit) skr::put<T>(out, e0 + j, r[j]);
     }
   };
   if constexpr (ALIGNED) {

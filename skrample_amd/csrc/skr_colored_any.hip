@@ -19,6 +19,7 @@
 #include "../../include/skrample_hip.h"
 #include "skr_philox.h"
 #include "skr_dft.h"
+#include "skr_pack.h"
 
 namespace skr {
 int g_fft_rank = 0;
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(256) void any_finish(T* out, const AnyArgs a, int h
   }
   __syncthreads();
   const float factor = factor_sh;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.unit; e += (int64_t)gridDim.x * 256) out[smp * a.unit + e] = (T)(a.real[smp * a.unit + e] * factor);
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.unit; e += (int64_t)gridDim.x * 256) skr::put<T>(out, smp * a.unit + e, a.real[smp * a.unit + e] * factor);
 }
 
 // ---- plan self-check -------------------------------------------------------------------------------------------------------

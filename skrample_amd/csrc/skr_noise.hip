@@ -13,8 +13,6 @@
 
 namespace skr {
 
-template <typename T> __device__ __forceinline__ void put(T* p, int64_t i, float v) { p[i] = (T)v; }
-
 __device__ __forceinline__ float normal1(uint64_t seed, uint64_t stream, uint64_t idx) {
   float z[4];
   normal4(seed, stream, idx >> 2, z);

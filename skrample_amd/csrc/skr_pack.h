@@ -1,4 +1,8 @@
-// 8-element packed, non-temporal stores from fp32 registers for the noise generators (one rounding, RNE).
+// The stores of the noise generators, from fp32 registers: 8- and 4-element packed streaming stores, and `put`, the one scalar store.
+// Contract of all of them: the fp32 VALUE is rounded once, to nearest even, to the output dtype (float64: widened), so a 16-bit draw has
+// the bits of the rounded fp32 draw whichever store an element takes.  For fp16 that needs a pin (pack_pair, put): the compiler otherwise
+// fuses a last multiply into the conversion (v_fma_mixlo_f16 rounds the exact product).  tests/test_noise_dtype_contract_gpu.py holds
+// every generator to it over 2^21 elements per store path.
 // 16-bit halves are packed as scalars: hipcc 7.2 mis-compiles a dword -> _Float16x2 vector bit_cast.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,6 +50,15 @@ __device__ __forceinline__ uint32_t pack_pair(float a, float b) {
     const uint32_t hi = __builtin_bit_cast(uint16_t, (_Float16)b);
     return lo | (hi << 16);
   }
+}
+
+// One value at p[i]: the scalar store of every generator path that cannot take a packed one (ragged sizes, unaligned bases).  fp16 rounds
+// the fp32 VALUE, as pack_pair does: without the pin a store of `a * b` is one v_fma_mixlo_f16 -- the product and the conversion in one
+// instruction, the exact product rounded once -- and differs from the packed paths where the fp32 product lands on an fp16 tie.
+template <typename T>
+__device__ __forceinline__ void put(T* p, int64_t i, float v) {
+  if constexpr (__is_same(T, _Float16)) asm("" : "+v"(v));
+  p[i] = (T)v;
 }
 
 // element index of the first value = 8 * vec; `base` must be 16-byte aligned at that element

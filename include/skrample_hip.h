@@ -509,6 +509,41 @@ int skr_step_launch_guided_indexed_per_sample(const skr_step_plan* plan, const v
                                               int32_t row_offset, void* stream);
 
 /*
+ * The guided step of a rolling batch: skr_step_launch_guided_indexed_per_sample with samples that may sit at different positions of
+ * their guided loops, each under its own guidance scale, or be absent -- what skr_step_launch_rolling is to
+ * skr_step_launch_indexed_per_sample.  Structure, coverage, checks, their order and their codes are those of
+ * skr_step_launch_guided_indexed_per_sample: `plan` fixes the structure only, skr_step_row and skr_step_guidance are used unchanged (the
+ * scale is the row's convert_k[0]; guide->scale is ignored; guide->cond, guide->guided_out and guide->slot are launch arguments), whole
+ * 2048-element chunks, samples made of whole chunks with or without noise, one 16- or 32-bit dtype for operands, cond and both outputs,
+ * fp32 arithmetic, 1..SKR_ROW_TERMS operands; anything else is SKR_ERR_UNSUPPORTED (ragged sizes, two dtype groups, fp64, acc_f64, the
+ * guidance-only form, "one_trip" 0 and fp32 tensors with "tile" 0 included): there is no grid-stride form, so the fp16 ragged-tail rule
+ * of skr_step_launch_guided cannot arise.  A NULL rows_dev or sample_index_dev is SKR_ERR_NULL, a negative row_offset
+ * SKR_ERR_UNSUPPORTED, and a launch with noise_mode == 1 needs seeds_dev whatever its rows hold.  On top of that contract
+ *   inactive sample  sample_index_dev[s] < 0 (tested before row_offset is added): the workgroups of sample s return before their
+ *                    first vector-memory instruction.  No operand, cond, seed or row of that sample is read; `out` and `guided_out`
+ *                    keep their bytes there.
+ *   absent operand   an operand k != slot whose coef0[k] is exactly zero (+0 or -0) in the sample's row is neither loaded nor summed:
+ *                    its bytes may be anything, NaN and inf included (the history a request in its multistep ramp-up does not have
+ *                    yet, the slot's previous occupant's).  The row's coef1 is not read.  inputs[slot] and cond are always loaded for
+ *                    an active sample, and p takes its one fma whatever coef0[slot] is, as in skr_step_launch_guided.
+ *   operand order    the operands that are present are accumulated in slot order, one fma each, with p in the place of inputs[slot];
+ *                    the noise comes last and is skipped when the row's zeta0 narrows to zero; one rounding by the store;
+ *                    guided_out = p when guided_out is given.  An active sample therefore has, bit for bit, what
+ *                    skr_step_launch_guided gives for that sample alone with a plan that holds exactly the present operands in that
+ *                    order, the row's values and guide->scale = convert_k[0] -- in `out` and in `guided_out`.
+ * `plan` is therefore the WIDEST guided step of the sampler.  Index validity stays the caller's business: every non-negative
+ * sample_index_dev[s] + row_offset must name a row of the table; the kernel neither checks nor clamps
+ * (skrample_amd.rolling.RollingBatch validates on the host).
+ * Measured (profiles/rolling_guided.txt; 64 x 4x128x128 bf16, DPM-2): the launch takes 9.10 us where torch's three
+ * lines plus skr_step_launch_rolling take 20.66 us (0.44; 6 tensor passes against 12); a RollingBatch tick with device-resident positions
+ * 31.07 against 43.43 us; a host-published tick is host-bound (154.80 against 176.33 us, inside the run-to-run spread).
+ */
+int skr_step_launch_guided_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                   const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                   const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */,
+                                   int32_t row_offset, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

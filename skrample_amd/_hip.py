@@ -39,6 +39,7 @@ EXPORTS = (
     "skr_step_launch_guided",
     "skr_step_launch_guided_indexed",
     "skr_step_launch_guided_indexed_per_sample",
+    "skr_step_launch_guided_rolling",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -452,7 +453,7 @@ def load() -> ctypes.CDLL:
         lib.skr_step_launch_masked_channels_last.restype = ctypes.c_int
         lib.skr_step_launch_guided.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp]
         lib.skr_step_launch_guided.restype = ctypes.c_int
-        for guided_table_launch in (lib.skr_step_launch_guided_indexed, lib.skr_step_launch_guided_indexed_per_sample):
+        for guided_table_launch in (lib.skr_step_launch_guided_indexed, lib.skr_step_launch_guided_indexed_per_sample, lib.skr_step_launch_guided_rolling):
             guided_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp, vp, i32, vp]
             guided_table_launch.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
@@ -638,3 +639,10 @@ def launch_step_masked_rolling_raw(plan: StepPlanC, arr, out_ptr, mask: StepMask
     """one masked rolling step launch (skr_step_launch_masked_rolling) from raw pointers; returns the status code.  `arr`: the operand
     pointer array, `mask`: its descriptor; the caller owns every check of the index (rolling.RollingBatch)."""
     return load().skr_step_launch_masked_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(mask), seeds_ptr, numel, rows_ptr, sample_index_ptr, row_offset, stream_ptr)
+
+
+def launch_step_guided_rolling_raw(plan: StepPlanC, arr, out_ptr, guide: StepGuidanceC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:
+    """one guided rolling step launch (skr_step_launch_guided_rolling) from raw pointers; returns the status code.  `arr`: the operand
+    pointer array, `guide`: its descriptor (cond, guided_out or NULL, slot; the scale is each sample's row value); the caller owns every
+    check of the index (rolling.RollingBatch)."""
+    return load().skr_step_launch_guided_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), seeds_ptr, numel, rows_ptr, sample_index_ptr, row_offset, stream_ptr)

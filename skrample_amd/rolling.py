@@ -18,6 +18,15 @@ share it, and a tick is still one launch (`skr_step_launch_masked_rolling`, csrc
     batch.admit(slot, latents, wrapper, steps, seed=None, inpaint=(mask, original_samples, noise))   # one sample each
     batch.admit(other, latents, wrapper, steps)      # a plain request: its slot of `batch.mask` is ones
 
+Classifier-free guidance: a batch built with `guided=True` takes the two halves of the network output and forms every request's guided
+prediction inside the tick's one launch (`skr_step_launch_guided_rolling`, csrc/skr_step_guided_rolling.hip), each request under its own
+scale -- or its own guidance schedule, one scale per step:
+
+    batch = RollingBatch(make_wrapper, example, capacity=B, guided=True)
+    batch.admit(slot, latents, wrapper, steps, seed=None, guidance_scale=7.5)          # or guidance_scale=[g_0, ..., g_{steps-1}]
+    uncond, cond = model(batch.latents, batch.timesteps)                                # two contiguous [B, ...] tensors
+    done = batch.step_guided(uncond, cond)
+
 With `device_positions=True` the positions live on the device and a tick needs no host-to-device copy:
 
     batch.advance()                                  # ONE skr_rolling_advance: index and timesteps computed on the device
@@ -62,6 +71,27 @@ launch arguments).  Refused when the batch is built: Colored, Brownian and custo
 the rolling entry does not cover (asked of the library's route decision, nothing launched), and `inpaint_mask_shape` beside
 structured noise.
 
+Guided batches (`guided=True`).  The launch structure comes from a dry run through `wrapper.step_guided(u, c, 1.0, t, x)`: `uncond` is the
+operand of role ("o",), whose place in the wide structure is the launch's `slot` -- fixed for the batch, checked against every request's
+dry run --; `cond` and `guided_out` are launch arguments, not operands.  The history operands ("po", k) are the GUIDED predictions of
+earlier ticks, which only the launch itself produces: the batch owns a ring of them, oldest first and as long as the latents ring (so
+that the phases of `CapturedTicks` close); a tick's launch stores its prediction into the entry no operand reads.  Nothing of the caller
+is held -- no alias guard, no snapshot (`alias_history` has no effect), `uncond` and `cond` may be overwritten once `step_guided` has
+returned --, and a sampler without history (Euler) passes `guided_out = NULL` and owns no ring.  The scale of a request's step i is the
+row's `convert_k[0]` (a guided plan has no rounded conversion, so the field is free): `admit(..., guidance_scale=g)` takes a float or a
+sequence of exactly `steps` floats, requires it on a guided batch and refuses it on any other.  Rows are placed by role as ever, so the
+first rows of a run have zeros in the history slots and a new request never reads its slot's previous occupant's predictions; an absent
+operand of the guided kernel is one whose `coef0` is zero (`uncond` and `cond` are always read for an active slot).  An unguided request
+shares the batch without a special case: hand it the same prediction in both halves -- cond - uncond is exactly 0 and the guided
+prediction is `uncond` for finite values, whatever its scale.  `step()` on a guided batch and `step_guided()` on any other raise.
+`advance()` and `device_positions=True` work unchanged; `capture(model)` takes a model that returns `(uncond, cond)`, and
+`CapturedTicks.tick()` is one replay plus one eager guided launch whose operand array, `cond` and `guided_out` were bound per phase at
+capture time.  Covered: Euler, DPM 1-3, Adams 2-4 and UniP 2-3, with or without stochasticity, `Random` noise or none, bf16 / fp16 / fp32
+latents under the default compute scale.  Refused when the batch is built, each with its reason: a sampler whose guided step is not one
+fused launch (UniPC, SPC, `compute_scale=None`), `guided` beside `inpaint_mask_shape`, `guided` beside Offset / Pyramid noise, and
+whatever the one-trip guided kernel does not cover.  Not covered: changing a resident request's scale mid-run (admit it with a schedule),
+`guidance_rescale`, channels-last, the Runge-Kutta wrappers, autograd.
+
 Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
 `Random` noise (drawn in the kernel), `Offset` / `Pyramid` noise (drawn per slot, above) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
 `skr_step_launch_indexed` covers (UniPC on fp32 latents is refused, as by the captured loops); a device-resident position vector
@@ -83,7 +113,7 @@ from typing import Callable, Sequence
 import torch
 
 from . import _hip
-from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepMaskC, StepPlanC, StepRowC, upload_rows
+from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepGuidanceC, StepMaskC, StepPlanC, StepRowC, upload_rows
 from .sampling import lazy
 
 Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py; ("orig",) ("znoise",): a masked batch's original / re-noising tensor;
@@ -172,13 +202,17 @@ class RollingBatch:
     share.  `max_steps` bounds a request's run length (the device table holds `capacity * max_steps` rows of 328 bytes).
     `alias_history`: True keeps the caller's model outputs as history operands (0 bytes written; overwriting one that is still
     held raises), False snapshots each one.  `device_positions`: True keeps every slot's position, run length and timesteps on
-    the device (`advance()` before each `step()`, or `capture()`); the host publishes nothing per tick."""
+    the device (`advance()` before each `step()`, or `capture()`); the host publishes nothing per tick.  `guided`: True makes a tick
+    `step_guided(uncond, cond)`, one `skr_step_launch_guided_rolling` with every request's own guidance scale (module docstring)."""
 
     def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True,
-                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None):  # fmt: skip
+                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False):  # fmt: skip
         if capacity < 1:
             raise ValueError("a rolling batch has at least one slot")
         self.masked = inpaint_mask_shape is not None
+        self.guided = bool(guided)
+        if self.guided and self.masked:
+            raise ValueError("guided together with inpaint_mask_shape: a guided step under set_inpaint is not one fused launch (guided in-painting batches are not covered)")
         self.capacity, self.max_steps, self.alias_history = int(capacity), int(max_steps), bool(alias_history)
         self.device_positions = bool(device_positions)
         if self.device_positions and (self.max_steps < 1 or self.capacity * self.max_steps > 0x7FFFFFFF):
@@ -192,6 +226,8 @@ class RollingBatch:
             raise ValueError(f"per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {self.sample_numel} elements per sample")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
+        if self.guided:
+            self._refuse_guided(first)
         self.draws_noise = bool(first.sampler.require_noise)
         self.structured = self.draws_noise and self._init_noise(first)
         if self.masked:
@@ -213,6 +249,9 @@ class RollingBatch:
             # the noise tensors, oldest first: [-1] is the latest draw; a ring as long as the latents ring where a step reads an earlier draw
             self._n = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1 if any(r[0] == "pn" for r in self.roles) else 1)]
             self._noise_ws = self.noise_type.rolling_workspace(self.unit_shape, self.noise_props, self.capacity, self.device)
+        # a guided batch: the guided predictions of the last ticks, oldest first, as long as the latents ring (so that the phases of
+        # CapturedTicks close); [-1] is the tensor this tick's launch stores into, ("po", k) the one of -k ticks ago.  Euler keeps none.
+        self._g = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1)] if self.guided and self.keep else []
         self._outputs: list[torch.Tensor] = []
         self._stamps: list[tuple[torch.Tensor, int, int]] = []
         self._results: dict[int, torch.Tensor] = {}
@@ -255,6 +294,24 @@ class RollingBatch:
             raise SkrampleHipError(f"{kind.__name__} noise on samples {self.unit_shape}: {refused}")
         return True
 
+    def _refuse_guided(self, first) -> None:
+        "a guided batch: what its one launch per tick does not cover, refused by name before anything is allocated or traced"
+        from .pytorch import noise as generators
+        from .sampling import structured as sampling
+
+        sampler = first.sampler
+        if type(sampler).sample_packed is not sampling.StatedSampler.sample_packed:
+            raise SkrampleHipError(f"a guided step of {type(sampler).__name__} is not one fused launch (its two-output step forms the guided prediction with a "
+                                   "guidance-only launch of its own): a guided rolling batch takes Euler, DPM 1-3, Adams 2-4 and UniP 2-3")  # fmt: skip
+        if first.compute_scale is None:
+            raise SkrampleHipError("a guided step under compute_scale=None is not one fused launch (the guidance-only launch, then the reference's rounded tensor ops)")
+        if getattr(first, "_inpaint", None) is not None:
+            raise SkrampleHipError("a guided step under set_inpaint is not one fused launch: guided in-painting batches are not covered")
+        if bool(sampler.require_noise) and first.noise_type in (generators.Offset, generators.Pyramid):
+            raise ValueError(f"guided together with {first.noise_type.__name__} noise: a guided rolling batch draws Random noise or none (structured noise is not covered)")
+        if self.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise SkrampleHipError(f"guided rows need one 16- or 32-bit dtype for operands, cond and both outputs, not {self.dtype}")
+
     def _init_inpaint(self, mask_shape: tuple, first) -> None:
         """A masked batch: the three whole-batch in-paint tensors (every slot's mask starts as ones: generate everything), the mask
         descriptor of every tick's launch -- one mask per slot, always -- and in-painting set on the wrapper whose dry run gives the
@@ -281,7 +338,10 @@ class RollingBatch:
         """Dry run of `wrapper` for `steps` steps on one sample: (plan, operand roles, timestep) of every step's single launch.
         Coefficients depend on the schedule and the step alone, never on tensor contents, so the model outputs are zeros.
         A wrapper with `set_inpaint` in force (a masked batch's in-painting request) must issue masked launches -- the seven-entry
-        trace tuple of `_hip.launch_step_masked` -- and one without it plain ones."""
+        trace tuple of `_hip.launch_step_masked` -- and one without it plain ones.  A guided batch steps the wrapper with
+        `step_guided(uncond, cond, 1.0, ...)` and must see the ten-entry tuple of `_hip.launch_step_guided`: `uncond` is the operand of
+        role ("o",) -- the launch's `slot` --, `cond` and `guided_out` are not operands, and the history operands are the wrapper's
+        stored guided predictions, role ("po", k)."""
         inpaint = getattr(wrapper, "_inpaint", None)
         if inpaint is not None and not self.masked:
             raise SkrampleHipError("this wrapper has set_inpaint in force and the batch was built without inpaint_mask_shape")
@@ -291,6 +351,7 @@ class RollingBatch:
         draws = self.structured and bool(wrapper.sampler.require_noise)
         for t in wrapper.timesteps.tolist():
             out = torch.zeros_like(x)
+            cond = torch.zeros_like(x) if self.guided else None
             known: dict[int, Role] = {}
             if draws:
                 # the step's realised noise: handed to the wrapper in place of a draw of its generator (the wrapper consumes one draw per
@@ -308,12 +369,17 @@ class RollingBatch:
             held = _hip.trace
             _hip.trace = []
             try:
-                new = wrapper.step(out, t, x, generator=[seed] if seed is not None else None, return_dict=False)[0]
+                if self.guided:
+                    new = wrapper.step_guided(out, cond, 1.0, t, x, generator=[seed] if seed is not None else None, return_dict=False)[0]
+                else:
+                    new = wrapper.step(out, t, x, generator=[seed] if seed is not None else None, return_dict=False)[0]
                 launches = _hip.trace
             finally:
                 _hip.trace = held
             if len(launches) != 1:
                 raise SkrampleHipError(f"a step of this wrapper is {len(launches)} launches, not one fused launch: it cannot join a rolling batch")
+            if self.guided and len(launches[0]) != 10:
+                raise SkrampleHipError("a guided step of this wrapper is not one fused guided launch: it cannot join a guided rolling batch")
             if (len(launches[0]) == 7) != (inpaint is not None):
                 raise SkrampleHipError("a step of this wrapper is not the masked launch its in-painting asks for" if inpaint is not None else "a step of this wrapper is a masked launch although no in-painting is set")
             plan, inputs = StepPlanC.from_buffer_copy(launches[0][0]), launches[0][1]
@@ -325,12 +391,20 @@ class RollingBatch:
             roles = [known.get(tensor.data_ptr()) for tensor in inputs]
             if any(r is None for r in roles):
                 raise SkrampleHipError("a step of this wrapper reads a temporary tensor (a cast, a copy, realised noise): it cannot join a rolling batch")
+            if self.guided and (launches[0][1][launches[0][9]] is not out or roles.count(("o",)) != 1):
+                raise SkrampleHipError("the guided launch of this wrapper does not replace its `uncond` operand: it cannot join a guided rolling batch")
             found.append((plan, roles, float(t)))
             x = new
         torch.cuda.synchronize(self.device)
         return found
 
-    def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None) -> None:
+    def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None, cond: torch.Tensor | None = None, guided_out: torch.Tensor | None = None) -> None:
+        if self.guided:  # (one output; `cond` and `guided_out` -- None: not stored -- are launch arguments, the scale each slot's row value)
+            guide = StepGuidanceC(cond.data_ptr(), guided_out.data_ptr() if guided_out is not None else None, 0.0, self.slot, 0)
+            status = _hip.launch_step_guided_rolling_raw(self.plan, arr, out0.data_ptr(), guide, self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel,
+                                                         self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0, _hip.current_stream_ptr(self.device))  # fmt: skip
+            _hip.check(status, "skr_step_launch_guided_rolling")
+            return
         if self.masked:  # (one output: a masked step is one single-output launch)
             status = _hip.launch_step_masked_rolling_raw(self.plan, arr, out0.data_ptr(), self._mask_desc, self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel,
                                                          self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0, _hip.current_stream_ptr(self.device))  # fmt: skip
@@ -390,16 +464,31 @@ class RollingBatch:
         if self.masked and (wide.out0_dtype == _hip.NONE or wide.out1_dtype != _hip.NONE or wide.acc_f64 or wide.n_group_a != wide.n_terms
                             or wide.dtype_a != wide.out0_dtype or wide.dtype_a != _hip.DTYPE_CODE[self.dtype]):  # fmt: skip
             raise SkrampleHipError("skr_step_launch_masked_rolling: request outside kernel coverage (one single-output launch of one 16- or 32-bit dtype, evaluated in float32)")
+        if self.guided:
+            if (wide.out0_dtype == _hip.NONE or wide.out1_dtype != _hip.NONE or wide.acc_f64 or wide.n_group_a != wide.n_terms or wide.convert_to or wide.convert_from
+                    or wide.dtype_a != wide.out0_dtype or wide.dtype_a != _hip.DTYPE_CODE[self.dtype]):  # fmt: skip
+                raise SkrampleHipError("skr_step_launch_guided_rolling: request outside kernel coverage (one single-output launch of one 16- or 32-bit dtype, evaluated in float32)")
+            if roles.count(("o",)) != 1:
+                raise SkrampleHipError("the guided launch structure has no single `uncond` operand for the guided value to replace")
+            self.slot = roles.index(("o",))
         return wide, list(roles)
 
-    def _rows_of(self, traced) -> list[StepRowC]:
+    def _rows_of(self, traced, scales: Sequence[float] | None = None) -> list[StepRowC]:
+        "`scales` (a guided batch): the guidance scale of every step, carried in the row's convert_k[0] (a guided plan has no rounded conversion)"
         rows = []
-        for plan, roles, _ in traced:
+        for step, (plan, roles, _) in enumerate(traced):
             if (plan.dtype_a, plan.acc_f64, plan.convert_to, plan.convert_from) != (self.plan.dtype_a, self.plan.acc_f64, self.plan.convert_to, self.plan.convert_from):
                 raise SkrampleHipError("a step of this request differs in dtype or conversion from the batch's launch structure")
             if self.masked and (plan.out0_dtype != self.plan.out0_dtype or plan.out1_dtype != _hip.NONE or plan.n_group_a != plan.n_terms):
                 raise SkrampleHipError("a step of this request is not one single-output launch of the masked batch's dtype")
-            rows.append(place_row(self.roles, plan, roles, self.two_outputs))
+            row = place_row(self.roles, plan, roles, self.two_outputs)
+            if self.guided:
+                if plan.out0_dtype != self.plan.out0_dtype or plan.out1_dtype != _hip.NONE or plan.n_group_a != plan.n_terms or list(roles).count(("o",)) != 1:
+                    raise SkrampleHipError("a step of this request is not one single-output guided launch of the batch's dtype with one `uncond` operand")
+                if row.coef0[self.slot] != plan.coef0[list(roles).index(("o",))]:  # (place_row put `uncond` where the batch's launches replace it)
+                    raise SkrampleHipError(f"the `uncond` operand of this step is not at the batch's slot {self.slot}")
+                row.convert_k[0] = float(scales[step])
+            rows.append(row)
         return rows
 
     # ---- slots ---------------------------------------------------------------------------------------------------------------
@@ -422,7 +511,7 @@ class RollingBatch:
 
     def ring_tensors(self) -> list[torch.Tensor]:
         "every whole-batch tensor a history operand may be bound to: the batch's own latents and states, snapshots of model outputs"
-        owned = self._x[:-1] + list(self._state) + [self._blank] + (list(self._n) if self.structured else [])
+        owned = self._x[:-1] + list(self._state) + [self._blank] + (list(self._n) if self.structured else []) + list(self._g)
         return owned + ([] if self.alias_history else list(self._outputs))
 
     def index_vector(self) -> list[int]:
@@ -437,13 +526,16 @@ class RollingBatch:
             out.append(b * self.max_steps + req.position)
         return out
 
-    def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None, inpaint: Sequence[torch.Tensor] | None = None) -> None:
+    def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None, inpaint: Sequence[torch.Tensor] | None = None,
+              guidance_scale: "float | Sequence[float] | None" = None) -> None:  # fmt: skip
         """Start a request in a free slot: `latents` of one sample, `wrapper` with this request's schedule / stochasticity (same
         sampler structure as the batch; it is consumed by the dry run that produces the rows), `steps` its run length.
         `inpaint` (a batch built with `inpaint_mask_shape` only): (mask, original_samples, noise) of ONE sample -- the request is an
         in-painting one, stepped as `wrapper.set_inpaint` would step it alone; the batch copies the three into the slot's slices of
         its own tensors (the mask cast to the latents' dtype, as set_inpaint casts it).  None there: a plain request sharing the
-        batch -- its mask is ones and its rows name neither the original nor the re-noising tensor."""
+        batch -- its mask is ones and its rows name neither the original nor the re-noising tensor.
+        `guidance_scale` (a batch built with `guided=True` only, and required there): the request's classifier-free-guidance scale, a
+        float, or a sequence of exactly `steps` floats -- a guidance schedule: the row of step i carries guidance_scale[i]."""
         self._check_slot(slot)
         if self._requests[slot] is not None:
             raise ValueError(f"slot {slot} is busy: take() its result first" if slot in self._finished else f"slot {slot} is busy")
@@ -452,6 +544,21 @@ class RollingBatch:
             raise ValueError(f"a request runs 1..{self.max_steps} steps (max_steps), not {steps}")
         if sampler_structure(wrapper) != self.structure:
             raise ValueError(f"this wrapper's sampler structure {sampler_structure(wrapper)} is not the batch's {self.structure}")
+        scales = None
+        if self.guided:
+            if guidance_scale is None:
+                raise ValueError("guidance_scale is required on a guided batch: a float, or one float per step (an unguided request hands step_guided the same prediction twice)")
+            if isinstance(guidance_scale, (int, float)) and not isinstance(guidance_scale, bool):
+                scales = [float(guidance_scale)] * steps
+            else:
+                try:
+                    scales = [float(g) for g in guidance_scale]
+                except TypeError:
+                    raise ValueError(f"guidance_scale is a float or a sequence of {steps} floats, not {type(guidance_scale).__name__}") from None
+                if len(scales) != steps:
+                    raise ValueError(f"a guidance schedule has one scale per step: {len(scales)} scales for {steps} steps")
+        elif guidance_scale is not None:
+            raise ValueError("guidance_scale= needs a batch built with guided=True: this one steps with step(model_output)")
         noisy = bool(wrapper.sampler.require_noise)
         if noisy and not self.draws_noise:
             raise ValueError("this wrapper draws noise and the batch's sampler structure does not")
@@ -491,7 +598,7 @@ class RollingBatch:
         traced = self._trace(wrapper, steps, seed if noisy else None)
         if len(traced) != steps:
             raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
-        request = _Request(self._rows_of(traced), [t for _, _, t in traced])
+        request = _Request(self._rows_of(traced, scales) if self.guided else self._rows_of(traced), [t for _, _, t in traced])
         upload_rows(self.rows_dev, slot * self.max_steps, request.rows)
         self._x[-1][slot].copy_(latents.reshape(self.unit_shape))
         if noisy:
@@ -545,12 +652,16 @@ class RollingBatch:
             return self._x[k - 1]
         if kind == "px":
             return self._state[k]
+        if kind == "po" and self.guided:  # (bound after this tick's rotation: [-1] is the tensor this tick's launch stores into)
+            return self._g[k - 1]
         if kind == "po":
             return self._outputs[k] if -k <= len(self._outputs) else self._blank
         raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
 
     def step(self, model_output: torch.Tensor) -> list[int]:
         "advance every active slot by one step of its own run with ONE launch; returns the slots that finished with this tick"
+        if self.guided:
+            raise ValueError("this batch was built with guided=True: a tick is step_guided(uncond, cond), the guided prediction is formed inside its launch")
         if self._captured is not None:
             raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
         index = self.index_vector()
@@ -608,6 +719,55 @@ class RollingBatch:
             self.timesteps.copy_(self._times_host)
         return done
 
+    def step_guided(self, uncond: torch.Tensor, cond: torch.Tensor) -> list[int]:
+        """A tick of a guided batch: ONE skr_step_launch_guided_rolling forms every active slot's guided prediction
+        uncond + g * (cond - uncond) -- g the slot's own scale for its own step, from its row --, steps the slot with it and stores it
+        into the batch's ring of guided predictions; returns the slots that finished with this tick.  Nothing of the caller is held: both
+        tensors may be overwritten as soon as the launch is enqueued.  An unguided request sharing the batch gets the same prediction in
+        both halves: cond - uncond is exactly 0 and the guided prediction is uncond (for finite values), whatever its scale."""
+        if not self.guided:
+            raise ValueError("step_guided() needs a batch built with guided=True: this one steps with step(model_output)")
+        if self._captured is not None:
+            raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
+        index = self.index_vector()
+        if all(i < 0 for i in index):
+            raise ValueError("no active slot: admit() a request before step_guided()")
+        if self.device_positions and not self._advanced:
+            raise ValueError("device-resident positions: advance() publishes this tick's index and timesteps; call it before the network and step_guided()")
+        for name, t in (("uncond", uncond), ("cond", cond)):
+            if tuple(t.shape) != tuple(self._x[-1].shape) or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} of a tick is a contiguous {tuple(self._x[-1].shape)} {self.dtype} tensor on {self.device}")
+        if self._g:
+            self._g.append(self._g.pop(0))  # the oldest guided prediction's tensor takes this tick's: no operand of the structure reaches that far back
+        operands = [self._bind(role, uncond) for role in self.roles]
+        if not self.device_positions:
+            self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
+        arr = (ctypes.c_void_p * max(len(operands), 1))(*[t.data_ptr() for t in operands])
+        new_x = self._x.pop(0)
+        self._launch(arr, new_x, None, cond, self._g[-1] if self._g else None)
+        self._x.append(new_x)
+        return self._ticked(index, new_x)
+
+    def _ticked(self, index: list, new_x: torch.Tensor) -> list[int]:
+        "the host bookkeeping behind a guided tick's launch: positions, finished slots, the next timesteps"
+        self.ticks += 1
+        self._advanced = False
+        done = []
+        for b, i in enumerate(index):
+            if i < 0:
+                continue
+            req = self._requests[b]
+            req.position += 1
+            if req.position == len(req.rows):
+                done.append(b)
+                self._finished.add(b)
+                self._results[b] = new_x[b].clone()
+            elif not self.device_positions:
+                self._times_host[b] = req.times[req.position]
+        if not self.device_positions:
+            self.timesteps.copy_(self._times_host)
+        return done
+
     # ---- device-resident positions -------------------------------------------------------------------------------------------
     def advance(self) -> None:
         """Device-resident positions: ONE skr_rolling_advance computes this tick's `index_dev` and `timesteps` from the slots' device
@@ -645,7 +805,9 @@ class CapturedTicks:
     graphs because its history operand ("po", k) is the static output of graph (p + k) mod P, which exists only once every graph
     is captured -- and that is why no model output is ever copied: the P static outputs ARE the model-output ring (it needs
     keep + 1 of them), they belong to the graphs, and nobody else can overwrite them (no alias guard).  `admit()` / `take()` of
-    the batch work between ticks."""
+    the batch work between ticks.  A guided batch: `model` returns `(uncond, cond)`; the uncond halves are `outputs`, the cond halves and
+    the batch's own ring of guided predictions -- the ("po", k) history there -- are bound per phase beside the operand array, and the
+    eager launch is one skr_step_launch_guided_rolling."""
 
     def __init__(self, batch: RollingBatch, model, warmup: int):
         self.batch = batch
@@ -662,12 +824,20 @@ class CapturedTicks:
         latents = [batch._x[(P - 1 + p) % P] for p in range(P)]
         self.graphs: list[torch.cuda.CUDAGraph] = []
         self.outputs: list[torch.Tensor] = []  # referenced here so that the graphs' pool keeps them alive
+        self.conds: list[torch.Tensor] = []  # a guided batch: the cond halves, launch arguments of the phases' step launches
         pool = torch.cuda.graph_pool_handle()
         for p in range(P):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, pool=pool):
                 batch._advance()
                 out = model(latents[p], batch.timesteps)
+            if batch.guided:  # the network returns (uncond, cond): `outputs` holds the uncond halves, the operand of role ("o",)
+                if not isinstance(out, (tuple, list)) or len(out) != 2:
+                    raise ValueError("the model of a guided batch returns (uncond, cond)")
+                out, cond = out
+                if tuple(cond.shape) != tuple(latents[p].shape) or cond.dtype != batch.dtype or cond.device != dev or not cond.is_contiguous():
+                    raise ValueError(f"cond of a tick is a contiguous {tuple(latents[p].shape)} {batch.dtype} tensor on {dev}")
+                self.conds.append(cond)
             if tuple(out.shape) != tuple(latents[p].shape) or out.dtype != batch.dtype or out.device != dev or not out.is_contiguous():
                 raise ValueError(f"the model output of a tick is a contiguous {tuple(latents[p].shape)} {batch.dtype} tensor on {dev}")
             self.graphs.append(graph)
@@ -684,6 +854,9 @@ class CapturedTicks:
         # a structured-noise batch: the tick of phase p draws into n_ring[p mod its length] -- one tensor, or a ring of P (the eager rotation of step())
         n_ring = list(batch._n) if batch.structured else []
         self._draws = [n_ring[p % len(n_ring)] for p in range(P)] if batch.structured else None
+        # a guided batch: the tick of phase p stores its guided prediction into g_ring[p] (the eager rotation of step_guided()); Euler stores none
+        g_ring = list(batch._g) if batch.guided else []
+        self._guides = [(self.conds[p], g_ring[p] if g_ring else None) for p in range(P)] if batch.guided else None
         self._launches = []  # per phase: (operand pointers, out0, out1, the tensor that holds the tick's new latents)
         for p in range(P):
             ptrs = []
@@ -703,6 +876,8 @@ class CapturedTicks:
                     t = x_ring[(P - 1 + p + role[1]) % P]
                 elif kind == "px":
                     t = state_ring[(p + role[1]) % P]
+                elif kind == "po" and batch.guided:  # the batch's own guided prediction of -k ticks ago: k places before this phase's
+                    t = g_ring[(p + role[1]) % P]
                 elif kind == "po":  # the static output of the graph replayed -k ticks ago
                     t = self.outputs[(p + role[1]) % P]
                 else:
@@ -735,7 +910,12 @@ class CapturedTicks:
         if self._draws is not None:  # eager like the step launch, between the advance (in the graph) and the step that reads the draw
             batch._draw(self._draws[phase])
             batch._n.append(batch._n.pop(0))
-        batch._launch(arr, out0, out1)
+        if self._guides is not None:
+            batch._launch(arr, out0, out1, *self._guides[phase])
+            if batch._g:
+                batch._g.append(batch._g.pop(0))
+        else:
+            batch._launch(arr, out0, out1)
         # the batch's rings follow, so that `latents` is where admit() must write
         batch._x.append(batch._x.pop(0))
         if batch.two_outputs:

@@ -544,6 +544,74 @@ int skr_step_launch_guided_rolling(const skr_step_plan* plan, const void* const*
                                    int32_t row_offset, void* stream);
 
 /*
+ * Rescaled guidance -- the line that follows the three guidance lines in SDXL-style, v-prediction and zero-terminal-SNR pipelines
+ * (diffusers' rescale_noise_cfg), with p the guided prediction, c = cond and phi = guidance_rescale:
+ *     std_text = c.std(dim=all but 0, keepdim=True);   std_cfg = p.std(dim=all but 0, keepdim=True)
+ *     resc = p * (std_text / std_cfg);                 p' = phi * resc + (1 - phi) * p
+ * A whole-sample reduction has to finish before the elementwise part starts, so the fused form is two launches: the statistic below
+ * (2 tensor passes), then skr_step_launch_guided_rescaled with its per-sample factor.
+ *
+ * skr_guidance_rescale_factor: per sample s -- the contiguous span of sample_numel elements s * sample_numel .. in storage order --
+ *     p[e]        the guided value of skr_step_launch_guided, fp16 tail rule (by the element's index in the WHOLE launch) included: the
+ *                 tensor torch would have taken the std of; T = dtype, M its op-math type (fp32; fp64 for fp64 tensors), g_M = scale in M
+ *     std_x       the unbiased (n - 1) standard deviation of the T-valued elements x = c, p of the sample, accumulated in DOUBLE as the
+ *                 shifted sums S1 = sum(x - K), S2 = sum((x - K)^2) with the pivot K = the sample's first element (a sample whose mean
+ *                 is far above its std does not cancel);  var = max((S2 - S1 * S1 / n) / (n - 1), 0), std = sqrt(var), each operation
+ *                 a separate IEEE double operation
+ *     r           rn_T( div_M( rn_T(rn_M(std_c)), rn_T(rn_M(std_p)) ) ): IEEE division, nothing guarded -- std_p == 0 gives the inf or
+ *                 NaN torch gives
+ *     factor_dev[s] = r;   stats_dev[2 s] = std_c, stats_dev[2 s + 1] = std_p when stats_dev is given
+ * Order of summation (fixed: two stages, no atomics; it depends on sample_numel and dtype only -- not on the batch, the sample's
+ * position or alignment, a grid heuristic or any skr_set_tuning key -- so a sample has the same factor bits alone and inside any batch):
+ *   stage 1  one workgroup of 256 lanes per 2048-element span j of a sample (span j holds the sample's elements 2048 j .. 2048 j + 2047,
+ *            the last one what is left).  Lane t owns the span's elements 8 t .. 8 t + 7 and adds them in that order to four running
+ *            doubles that start at zero (S1 += d, then S2 = fma(d, d, S2), for c and for p).  The 64 lanes of a wave are reduced by a
+ *            shuffle tree, v += v[lane + o] for o = 32, 16, 8, 4, 2, 1; the four waves through LDS as ((w0 + w1) + w2) + w3.  Four
+ *            doubles per span go to partials_dev: S1c, S2c, S1p, S2p at 4 * (s * spans + j), spans = ceil(sample_numel / 2048).
+ *            A span that is 16-byte aligned and whole is read with 16-byte non-temporal loads, any other element by element: same
+ *            lanes, same order, same bits.
+ *   stage 2  one wave per sample: each of the four quantities is summed over the sample's spans in index order from zero.
+ * partials_dev: SKR_GUIDANCE_PARTIALS(numel, sample_numel) doubles of device workspace, 8-byte aligned, overwritten.
+ * Checked before the launch, without dereferencing device memory: a NULL uncond, cond, factor_dev or partials_dev SKR_ERR_NULL;
+ * numel < 0, sample_numel < 2 or numel % sample_numel != 0 SKR_ERR_SHAPE;  numel == 0 SKR_OK with nothing launched;  uncond or cond
+ * not 16-byte aligned SKR_ERR_ALIGN;  a dtype other than bf16, fp16, fp32 or fp64 SKR_ERR_DTYPE;  more than INT32_MAX spans in all
+ * SKR_ERR_UNSUPPORTED.  Allocates nothing, never synchronises: capturable.
+ */
+#define SKR_GUIDANCE_PARTIALS(numel, sample_numel) (4 * ((numel) / (sample_numel)) * (((sample_numel) + 2047) / 2048))
+
+int skr_guidance_rescale_factor(const void* uncond, const void* cond, int32_t dtype, double scale, int64_t numel, int64_t sample_numel,
+                                void* factor_dev /* T[numel / sample_numel] */,
+                                double* stats_dev /* [2 * samples]: std(cond), std(p); may be NULL */,
+                                double* partials_dev /* [SKR_GUIDANCE_PARTIALS(numel, sample_numel)] */, void* stream);
+
+/*
+ * skr_step_launch_guided_rescaled: skr_step_launch_guided with p replaced by p'.  With r = factor_dev[s(e)], phi_M = phi and
+ * psi_M = 1.0 - phi (evaluated in double, as Python evaluates 1 - guidance_rescale before torch sees it) each narrowed to M once:
+ *     resc = rn_T(p * r);   a = rn_T(phi_M * resc);   b = rn_T(psi_M * p);   p' = rn_T(a + b)
+ * every operation a separate one in M, each result rounded to fp32 and then to T, nothing contracted.  `out` has the bits
+ * skr_step_launch writes with a tensor holding p' in `slot`; guided_out = p' (what history and pred_original_sample read).  phi == 0
+ * is not special-cased.  fp16: p * r is a product of two fp16 values -- exact in fp32, so no rule applies; the two scalar products are
+ * torch's tensor-times-Python-number kernel, as g * d is, and have its single rounding from the last multiple of 2048 below numel on.
+ * Launches the one-trip kernel of skr_step_launch_guided takes, with rescale->sample_numel a multiple of 2048 below 2^31 -- a
+ * workgroup then lies inside one sample and the factor is one uniform load -- take a one-trip kernel of the same shape; everything
+ * else (ragged sizes, small samples, two dtype groups, fp64, the guidance-only form) the grid-stride per-element kernel.  The two
+ * agree bit for bit ("one_trip" 0 forces the second).
+ * Checks: those of skr_step_launch_guided, in its order and with its codes; among them a NULL rescale beside the NULL plan or guide
+ * SKR_ERR_NULL; a non-zero rescale->reserved beside the guide's SKR_ERR_UNSUPPORTED; behind the sample size of a launch that draws:
+ * rescale->sample_numel < 2 or not dividing numel SKR_ERR_SHAPE, then a drawing plan whose sample_numel differs SKR_ERR_SHAPE;
+ * a NULL factor_dev beside the NULL operands SKR_ERR_NULL.  factor_dev needs the alignment of T only.
+ */
+typedef struct skr_step_rescale {
+  const void* factor_dev;  /* device T[numel / sample_numel]: what skr_guidance_rescale_factor wrote */
+  double phi;              /* guidance_rescale */
+  int64_t sample_numel;    /* elements per sample of the statistic */
+  int64_t reserved;        /* 0 */
+} skr_step_rescale;
+
+int skr_step_launch_guided_rescaled(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                    const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

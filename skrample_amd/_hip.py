@@ -40,6 +40,8 @@ EXPORTS = (
     "skr_step_launch_guided_indexed",
     "skr_step_launch_guided_indexed_per_sample",
     "skr_step_launch_guided_rolling",
+    "skr_guidance_rescale_factor",
+    "skr_step_launch_guided_rescaled",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -185,6 +187,25 @@ class StepGuidanceC(ctypes.Structure):
         ("slot", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
     ]
+
+
+class StepRescaleC(ctypes.Structure):
+    "mirror of `skr_step_rescale`: the per-sample factor of the statistics launch, guidance_rescale and the statistic's sample size"
+
+    _fields_ = [
+        ("factor_dev", ctypes.c_void_p),
+        ("phi", ctypes.c_double),
+        ("sample_numel", ctypes.c_int64),
+        ("reserved", ctypes.c_int64),
+    ]
+
+
+GUIDANCE_SPAN = 2048  # elements per partial sum of skr_guidance_rescale_factor (SKR_GUIDANCE_PARTIALS)
+
+
+def guidance_partials(numel: int, sample_numel: int) -> int:
+    "doubles of workspace skr_guidance_rescale_factor needs (include/skrample_hip.h, SKR_GUIDANCE_PARTIALS)"
+    return 4 * (numel // sample_numel) * ((sample_numel + GUIDANCE_SPAN - 1) // GUIDANCE_SPAN)
 
 
 def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None, guide: "StepGuidanceC | None" = None) -> tuple:
@@ -456,6 +477,10 @@ def load() -> ctypes.CDLL:
         for guided_table_launch in (lib.skr_step_launch_guided_indexed, lib.skr_step_launch_guided_indexed_per_sample, lib.skr_step_launch_guided_rolling):
             guided_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp, vp, i32, vp]
             guided_table_launch.restype = ctypes.c_int
+        lib.skr_guidance_rescale_factor.argtypes = [vp, vp, i32, ctypes.c_double, i64, i64, vp, vp, vp, vp]
+        lib.skr_guidance_rescale_factor.restype = ctypes.c_int
+        lib.skr_step_launch_guided_rescaled.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp]
+        lib.skr_step_launch_guided_rescaled.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -633,6 +658,48 @@ def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond:
     else:
         status = lib.skr_step_launch_guided(ctypes.byref(plan), arr, _ptr(out), ctypes.byref(desc), _ptr(seeds), numel, stream)
     check(status, "skr_step_launch_guided")
+
+
+NO_RESCALED_ROWS = ("rescaled guidance (guidance_rescale) has no row form: capture the loop with indexed=False, which freezes guidance_rescale into "
+                    "the graph, or pass guidance_rescale=0.0")
+
+
+def launch_guidance_factor(uncond: torch.Tensor, cond: torch.Tensor, scale: float, sample_numel: int, factor: torch.Tensor, stats: "torch.Tensor | None" = None) -> None:
+    """the statistics launch of rescaled guidance (skr_guidance_rescale_factor) on torch's current stream: factor[s] = std(cond_s) / std(p_s)
+    per sample of `sample_numel` elements in storage order, rounded as torch rounds it; `stats` (float64[2 * samples] or None) receives
+    the two standard deviations.  The workspace comes from torch's allocator, which is safe under graph capture.
+    A `_hip.trace` list receives ("guidance_factor", uncond, cond, scale, sample_numel, factor, stats): no plan leads it, no step program
+    is built from it.  Under the indexed-rows hook it raises: there is no row form of rescaled guidance."""
+    lib = load()
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError(NO_RESCALED_ROWS)
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append(("guidance_factor", uncond, cond, scale, sample_numel, factor, stats))
+    numel = uncond.numel()
+    partials = torch.empty(max(guidance_partials(numel, sample_numel), 1), dtype=torch.float64, device=uncond.device)
+    status = lib.skr_guidance_rescale_factor(uncond.data_ptr(), cond.data_ptr(), DTYPE_CODE[uncond.dtype], float(scale), numel, int(sample_numel), factor.data_ptr(),
+                                             _ptr(stats), partials.data_ptr(), current_stream_ptr(uncond.device))
+    check(status, "skr_guidance_rescale_factor")
+
+
+def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, scale: float, slot: int, factor: torch.Tensor, phi: float,
+                                sample_numel: int, seeds, numel: int, device: torch.device) -> None:
+    """one rescaled guided step launch (skr_step_launch_guided_rescaled): launch_step_guided with the guided value p replaced by
+    phi * (p * factor[sample]) + (1 - phi) * p, rounded as torch's four tensor ops round it; `guided_out` (or None) receives that value.
+    A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, cond, guided_out, scale, slot, factor, phi, sample_numel) --
+    thirteen entries no step program is built from.  Under the indexed-rows hook it raises: there is no row form of rescaled guidance."""
+    lib = load()
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError(NO_RESCALED_ROWS)
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((plan, list(operands), out, None, seeds, numel, cond, guided_out, scale, slot, factor, phi, sample_numel))
+    desc = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
+    rescale = StepRescaleC(factor.data_ptr(), float(phi), int(sample_numel), 0)
+    arr, stream = _operand_array(operands), current_stream_ptr(device)
+    status = lib.skr_step_launch_guided_rescaled(ctypes.byref(plan), arr, _ptr(out), ctypes.byref(desc), ctypes.byref(rescale), _ptr(seeds), numel, stream)
+    check(status, "skr_step_launch_guided_rescaled")
 
 
 def launch_step_masked_rolling_raw(plan: StepPlanC, arr, out_ptr, mask: StepMaskC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:

@@ -15,43 +15,14 @@
 //     takes, fp32 or fp64 arithmetic, and the guidance-only form (no step output).
 // Both evaluate the same operations in the same order on every element, so they agree bit for bit where both apply.
 // One exception follows torch's own device op: for fp16 the elements past the last whole 2048 of the tensor have  g * d  rounded once
-// (mul_once_f16 below).  Only the general kernel meets such elements.
-// The row forms of the one-trip kernel (skr_step_launch_guided_indexed[_per_sample]) are skr_step_guided_rows.hip; guided_value and the
-// entry checks, which both files use, are skr_step_guided.h.
+// (mul_once_f16, skr_step_guided.h).  Only the general kernel meets such elements.
+// The row forms of the one-trip kernel (skr_step_launch_guided_indexed[_per_sample]) are skr_step_guided_rows.hip, the rescaled step
+// (skr_step_launch_guided_rescaled) skr_step_guided_rescaled.hip; the guided value and the entry checks, which they share, are
+// skr_step_guided.h.
 #include "skr_step_guided.h"
 #include "skr_device.h"
 
 namespace skr {
-
-// fp16 elements of the partial last block of torch's vectorised elementwise kernel (TORCH_TAIL below).  Its compiler fuses the scalar
-// multiply with the conversion there (v_fma_mixlo_f16), so  g * d  is rounded ONCE, from the exact product, where the whole blocks round
-// the fp32 product again.  (d is an fp16 value and g an fp32 one: the product has up to 35 significant bits.  c - u and u + m are sums
-// of two fp16 values, for which the second rounding never changes the result.)  The single rounding is made of plain operations: the
-// fp32 product is moved to its odd neighbour when it is inexact and even, after which the rounding to fp16 cannot meet a false tie.
-__device__ __forceinline__ float mul_once_f16(float g, float d) {
-  float m = mul_(g, d);
-  asm("" : "+v"(m));
-  const float err = fma_(g, d, -m);  // exact: what the fp32 rounding dropped
-  uint32_t b = __builtin_bit_cast(uint32_t, m);
-  const bool finite_nonzero = (b & 0x7f800000u) != 0x7f800000u && (b << 1) != 0;
-  if (finite_nonzero && err != 0.f && (b & 1u) == 0) b += ((err > 0.f) == (m > 0.f)) ? 1u : 0xffffffffu;
-  return rnd<f16_t>(__builtin_bit_cast(float, b));
-}
-__device__ __forceinline__ float guided_value_f16_tail(float u, float c, float g) {
-  float d = sub_(c, u);
-  asm("" : "+v"(d));
-  d = rnd<f16_t>(d);
-  const float m = mul_once_f16(g, d);
-  float p = add_(u, m);
-  asm("" : "+v"(p));
-  return rnd<f16_t>(p);
-}
-// the block of that torch kernel for 16-bit tensors on gfx950 (256 threads of 8 elements): elements from the last multiple of it on are
-// its tail.  The one-trip kernel's chunk has the same size, so a tensor of whole chunks has no tail.
-constexpr int64_t TORCH_TAIL = 2048;
-static_assert(TORCH_TAIL == (int64_t)BLOCK * VEC, "whole chunks must be whole blocks of torch's kernel: the one-trip kernel has no tail path");
-
-__device__ __forceinline__ double guide_d(double u, double c, double g) { return add_(u, mul_(g, sub_(c, u))); }
 
 // Kernarg of the one-trip kernel: what the first instructions need (operand pointers, chunk map) leads, as in MaskedArgs.
 template <int KMAX>
@@ -195,7 +166,7 @@ static void launch_guided_v1(const skr_step_plan& p, const void* const* inputs, 
 // Every check of a guided launch behind its NULL plan / guide tests: those of skr_step_launch in its order, with what the guidance adds
 // where the like of it stands there.  (Declared in skr_step_guided.h: the row entries ask it too.)
 int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
-                   bool rows, GuidedLaunch* launch) {
+                   bool rows, GuidedLaunch* launch, const skr_step_rescale* rescale) {
   launch->step_out = launch->noise = launch->one_trip = false;
   const bool step_out = p.out0_dtype != SKR_NONE;
   const bool noise = step_out && p.noise_mode == 1 && (rows || p.zeta0 != 0.0);
@@ -206,13 +177,18 @@ int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const vo
   if (!step_out && !gd.guided_out) return SKR_ERR_NULL;  // no output at all
   if (p.noise_mode != 0 && p.noise_mode != 1) return SKR_ERR_UNSUPPORTED;
   if (p.out1_dtype != SKR_NONE || p.chain != 0.0 || p.zeta1 != 0.0 || p.convert_to != 0 || p.convert_from != 0 || gd.reserved != 0) return SKR_ERR_UNSUPPORTED;
+  if (rescale && rescale->reserved != 0) return SKR_ERR_UNSUPPORTED;
   if (!step_out && (out != nullptr || p.n_terms != 1)) return SKR_ERR_UNSUPPORTED;  // the guidance-only form: one operand, p alone
   if (noise && numel > 0) {  // fused Philox needs every 8-element group inside one sample, as in skr_step_launch
     if (p.sample_numel <= 0 || numel % p.sample_numel != 0) return SKR_ERR_SHAPE;
     if (p.sample_numel % 8 != 0) return SKR_ERR_UNSUPPORTED;
   }
+  if (rescale) {  // the statistic's sample: at least two elements (an unbiased std), and the one the noise is drawn by
+    if (rescale->sample_numel < 2 || numel % rescale->sample_numel != 0) return SKR_ERR_SHAPE;
+    if (noise && numel > 0 && p.sample_numel != rescale->sample_numel) return SKR_ERR_SHAPE;
+  }
   if (numel == 0) return SKR_OK;
-  if (!inputs || (step_out && !out) || !gd.cond) return SKR_ERR_NULL;
+  if (!inputs || (step_out && !out) || !gd.cond || (rescale && !rescale->factor_dev)) return SKR_ERR_NULL;
   if (const int rc = check_ptrs(inputs, p.n_terms)) return rc;
   if ((step_out && !aligned16(out)) || !aligned16(gd.cond) || !aligned16(gd.guided_out)) return SKR_ERR_ALIGN;
   // the dtype combinations of skr_step_launch, with one output; an fp64 group (the slot's or not) needs fp64 arithmetic

@@ -855,8 +855,13 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     # operands -- forms the prediction in one guidance-only launch and steps as ever; host-resident operands and operands that autograd
     # records form it with torch's own three lines.  Either way prev_sample and pred_original_sample have the bits of
     # step(uncond + guidance_scale * (cond - uncond), ...) on a wrapper in the same state, and calls of both kinds may be mixed in a run.
-    def step_guided(self, model_output_uncond: Tensor, model_output_cond: Tensor, guidance_scale: float, timestep, sample: Tensor, generator=None, return_dict: bool = True):
-        guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale)
+    # guidance_rescale (diffusers' rescale_noise_cfg, the line SDXL-style, v-prediction and zero-terminal-SNR pipelines put behind the three;
+    # 0.0 -- diffusers' own `if guidance_rescale > 0` -- changes nothing): one statistics launch over uncond and cond
+    # (skr_guidance_rescale_factor: per sample std(cond) / std(prediction)), then the same routes with the rescaled prediction
+    # (skr_step_launch_guided_rescaled), which is what history and pred_original_sample read.
+    def step_guided(self, model_output_uncond: Tensor, model_output_cond: Tensor, guidance_scale: float, timestep, sample: Tensor, generator=None, return_dict: bool = True,
+                    guidance_rescale: float = 0.0):
+        guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale, guidance_rescale)
         recorded = lazy.grad_recorded(model_output_uncond, model_output_cond, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
         return self._step_general(model_output_uncond, timestep, sample, generator, return_dict, recorded, guidance)
 

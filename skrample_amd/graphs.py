@@ -251,7 +251,7 @@ class CapturedLoops:
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
                           indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False,
-                          guidance_scale: float | None = None) -> CapturedLoop:
+                          guidance_scale: float | None = None, guidance_rescale: float = 0.0) -> CapturedLoop:
     """Capture `for t in wrapper.timesteps: x = wrapper.step(model(x, t), t, x)` for `steps` steps.
 
     `wrapper` is any scheduler wrapper of skrample_amd.diffusers; `model(x, t)` must be capturable (pure device
@@ -279,20 +279,27 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     launches: a sampler whose step is one single-output launch (Euler, DPM, Adams, UniP), contiguous latents of whole 2048-element chunks
     in one 16- or 32-bit dtype, no `set_inpaint`, no `compute_scale=None` / `float64`.  Anything else -- UniPC and SPC among them, whose
     guidance is a launch of its own -- is refused during the recording pass, before the stream captures.
+
+    `guidance_rescale` (with `guidance_scale`; 0.0: nothing changes): the loop body is `wrapper.step_guided(..., guidance_rescale=...)`.
+    With `indexed=False` the statistics launch and the rescaled step are captured, guidance_rescale frozen into the graph.  There is no
+    row form of rescaled guidance: `indexed=True` (and so `per_sample`) with a non-zero guidance_rescale is refused during the recording
+    pass, before the stream captures.
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
+    if guidance_rescale != 0.0 and guidance_scale is None:
+        raise ValueError("guidance_rescale belongs to a guided loop: pass guidance_scale= as well")
     from .pytorch import noise as _noise
 
     _noise._private_vectors[0] += 1  # the loop's seed vector is overwritten in place by replays with new seeds: it is this loop's alone
     try:
-        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale)
+        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale)
     finally:
         _noise._private_vectors[0] -= 1
 
 
 def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False,
-             guidance_scale: float | None = None) -> CapturedLoop:
+             guidance_scale: float | None = None, guidance_rescale: float = 0.0) -> CapturedLoop:
     dev = example.device
     static_in = example.clone()
     gen = list(seeds) if seeds is not None else None
@@ -316,7 +323,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         if scale is None:
             return w.step(model(x, tm), t, x, generator=generator, return_dict=False)[0]
         uncond, cond = model(x, tm)
-        return w.step_guided(uncond, cond, scale, t, x, generator=generator, return_dict=False)[0]
+        return w.step_guided(uncond, cond, scale, t, x, generator=generator, return_dict=False, guidance_rescale=guidance_rescale)[0]
 
     def run(x):
         wrapper.reset_run()  # same schedule, same device seed vector; history and draw counter rewound

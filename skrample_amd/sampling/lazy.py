@@ -127,9 +127,12 @@ class Guidance:
     """The classifier-free-guidance prediction  uncond + scale * (cond - uncond)  as ONE leaf of a step's form: its value is torch's --
     three tensor ops, each rounded in the tensors' dtype, the Python scalar kept in the op-math type -- and `evaluate_guided` computes
     it inside the launch that consumes it (include/skrample_hip.h, skr_step_launch_guided).  `node()` is a `Lin` leaf, as
-    `RoundedConversion.node()` is: a sampler's algebra carries it wherever the prediction stands, with whatever coefficient it gets."""
+    `RoundedConversion.node()` is: a sampler's algebra carries it wherever the prediction stands, with whatever coefficient it gets.
+    `rescale` (guidance_rescale; 0.0: nothing changes): the prediction is diffusers' rescale_noise_cfg of it -- the four lines in
+    `torch_lines` -- with dim 0 the sample; on the HIP device the two per-sample stds are one statistics launch (`factor`,
+    skr_guidance_rescale_factor) and the elementwise part runs inside the consuming launch (skr_step_launch_guided_rescaled)."""
 
-    def __init__(self, uncond: torch.Tensor, cond: torch.Tensor, scale: float):
+    def __init__(self, uncond: torch.Tensor, cond: torch.Tensor, scale: float, rescale: float = 0.0):
         if not isinstance(uncond, torch.Tensor) or not isinstance(cond, torch.Tensor):
             raise SkrampleHipError(f"guidance takes two torch tensors, not {type(uncond).__name__} and {type(cond).__name__}")
         _check_tensor(uncond), _check_tensor(cond)
@@ -139,7 +142,13 @@ class Guidance:
             )
         if isinstance(scale, bool) or not isinstance(scale, NUMBER):
             raise SkrampleHipError(f"the guidance scale is a Python number, not {type(scale).__name__}")
-        self.uncond, self.cond, self.scale = uncond, cond, float(scale)
+        if isinstance(rescale, bool) or not isinstance(rescale, NUMBER):
+            raise SkrampleHipError(f"guidance_rescale is a Python number, not {type(rescale).__name__}")
+        if not rescale >= 0.0:
+            raise SkrampleHipError(f"guidance_rescale must be >= 0, not {rescale}")
+        if rescale != 0.0 and (uncond.ndim < 2 or uncond.numel() // max(uncond.shape[0], 1) < 2):
+            raise SkrampleHipError(f"rescaled guidance takes the std of every sample: it needs tensors of ndim >= 2 (dim 0 the sample) with at least 2 elements per sample, not {tuple(uncond.shape)}")
+        self.uncond, self.cond, self.scale, self.rescale = uncond, cond, float(scale), float(rescale)
         self.shape, self.device, self.dtype = tuple(uncond.shape), uncond.device, uncond.dtype
 
     def node(self) -> "Lin":
@@ -150,10 +159,37 @@ class Guidance:
         return self
 
     def torch_lines(self) -> torch.Tensor:
-        "the pipeline's three lines, by torch itself (host-resident operands; operands that autograd records)"
+        "the pipeline's three lines -- and, rescaled, the four of rescale_noise_cfg -- by torch itself (host-resident operands; operands that autograd records)"
         d = self.cond - self.uncond
         m = self.scale * d
-        return self.uncond + m
+        p = self.uncond + m
+        if self.rescale != 0.0:
+            c, phi = self.cond, self.rescale
+            std_text = c.std(dim=list(range(1, c.ndim)), keepdim=True)
+            std_cfg = p.std(dim=list(range(1, p.ndim)), keepdim=True)
+            resc = p * (std_text / std_cfg)
+            p = phi * resc + (1 - phi) * p
+        return p
+
+    def factor(self) -> torch.Tensor:
+        """std(cond) / std(p) per sample as a tensor of the operands' dtype and shape (B, 1, ...): one statistics launch
+        (skr_guidance_rescale_factor), summed in storage order -- a dense channels-last sample is one contiguous span, so such operands
+        are read as they stand; torch's own two stds and division for host-resident operands and operands that autograd records."""
+        u, c = self.uncond, self.cond
+        if len(self.shape) < 2:
+            raise SkrampleHipError(f"rescaled guidance needs tensors of ndim >= 2 (dim 0 the sample), not {self.shape}")
+        if is_host(self.device) or grad_recorded(u, c):
+            p = u + self.scale * (c - u)
+            return c.std(dim=list(range(1, c.ndim)), keepdim=True) / p.std(dim=list(range(1, p.ndim)), keepdim=True)
+        prepare = _prepare_keeping_layout if in_place_layout((u, c), self.shape) is not None else _prepare_tensor
+        return self.device_factor(prepare(u), prepare(c))
+
+    def device_factor(self, u: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+        "`factor` over device operands a launch takes as they stand (16-byte aligned; contiguous or dense channels-last, both alike)"
+        factor = torch.empty((self.shape[0],) + (1,) * (len(self.shape) - 1), dtype=self.dtype, device=self.device)
+        if u.numel():
+            _hip.launch_guidance_factor(u, c, self.scale, u.numel() // self.shape[0], factor)
+        return factor
 
 
 def _check_tensor(t: torch.Tensor) -> torch.Tensor:
@@ -745,7 +781,9 @@ def pending_blend() -> "MaskedBlend | None":
 def guide_only(guidance: Guidance) -> torch.Tensor:
     """the guided prediction as a tensor of its own, with torch's bits: one guidance-only launch of skr_step_launch_guided on the HIP
     device (uncond and cond in one dense channels-last layout: on the storage order as it stands, the result channels-last); torch's own
-    three lines for host-resident operands and for operands that autograd records (torch records them)."""
+    three lines for host-resident operands and for operands that autograd records (torch records them).
+    A rescaled guidance (`guidance.rescale != 0`) is the statistics launch and the guidance-only form of skr_step_launch_guided_rescaled
+    under the same conditions, and torch's lines with rescale_noise_cfg's four otherwise."""
     u, c = guidance.uncond, guidance.cond
     if is_host(guidance.device) or grad_recorded(u, c):
         return guidance.torch_lines()
@@ -759,7 +797,11 @@ def guide_only(guidance: Guidance) -> torch.Tensor:
     plan.out0_dtype = plan.out1_dtype = _hip.NONE
     plan.acc_f64 = 1 if guidance.dtype == torch.float64 else 0
     plan.coef0[0] = 1.0
-    _hip.launch_step_guided(plan, [u], None, c, out, guidance.scale, 0, None, math.prod(guidance.shape), guidance.device)
+    numel = math.prod(guidance.shape)
+    if guidance.rescale != 0.0:  # the statistic over the same storage order, then the rescaled guidance-only launch
+        _hip.launch_step_guided_rescaled(plan, [u], None, c, out, guidance.scale, 0, guidance.device_factor(u, c), guidance.rescale, numel // guidance.shape[0], None, numel, guidance.device)
+    else:
+        _hip.launch_step_guided(plan, [u], None, c, out, guidance.scale, 0, None, numel, guidance.device)
     return out
 
 
@@ -771,7 +813,9 @@ def evaluate_guided(form: Lin, guidance: Guidance, dtype: torch.dtype | None = N
     What the one launch does not cover takes the guidance-only launch (`guide_only`) and then evaluate(): contiguous copies would be
     needed (channels-last or strided operands), the node's coefficient is zero, `uncond` is an operand of the form in its own right or
     is cast to another dtype group, or the form has more than 16 operands.  Host-resident operands and operands that autograd records
-    evaluate the three lines with torch and then the existing executors.  Mixed residency is refused as everywhere."""
+    evaluate the three lines with torch and then the existing executors.  Mixed residency is refused as everywhere.
+    A rescaled guidance takes the same routes with one statistics launch in front (skr_guidance_rescale_factor, then
+    skr_step_launch_guided_rescaled); `guided` is then the rescaled prediction."""
     f = lift(form)
     if not isinstance(f, Lin) or not isinstance(guidance, Guidance):
         raise SkrampleHipError("evaluate_guided() takes a tensor form and a Guidance")
@@ -794,7 +838,12 @@ def evaluate_guided(form: Lin, guidance: Guidance, dtype: torch.dtype | None = N
         if slot is not None and len(operands) <= _hip.ROW_TERMS:
             final = empty_output(f.shape, out_dtype, guidance.device)
             guided = empty_output(f.shape, guidance.dtype, guidance.device)
-            _hip.launch_step_guided(plan, operands, final, c, guided, guidance.scale, slot, seeds, math.prod(f.shape), guidance.device)
+            numel = math.prod(f.shape)
+            if guidance.rescale != 0.0:  # the statistics launch, then the step with its per-sample factor
+                _hip.launch_step_guided_rescaled(plan, operands, final, c, guided, guidance.scale, slot, guidance.device_factor(u, c), guidance.rescale, numel // f.shape[0],
+                                                 seeds, numel, guidance.device)
+            else:
+                _hip.launch_step_guided(plan, operands, final, c, guided, guidance.scale, slot, seeds, numel, guidance.device)
             return final, guided
     guided = guide_only(guidance)
     return evaluate([f.substitute(guidance, guided)], [out_dtype], acc_f64)[0], guided

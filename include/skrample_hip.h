@@ -612,6 +612,61 @@ int skr_step_launch_guided_rescaled(const skr_step_plan* plan, const void* const
                                     const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,
+ * rows_dev[sample_index_dev[s] + row_offset] -- convert_k[0] the guidance scale (as in skr_step_launch_guided_rolling), convert_k[1]
+ * phi = guidance_rescale (skr_step_launch_guided_rolling does not read it).  convert_k[2..3], coef1, chain, zeta1 and stream1 are not
+ * read.  Neither entry has a grid-stride form.  A tick is the statistics launch, then the step launch, with the same index, rows and
+ * row_offset; index validity is the caller's business, as in skr_step_launch_guided_rolling.
+ *
+ * skr_guidance_rescale_factor_rolling: skr_guidance_rescale_factor with the scale of sample s its row's convert_k[0], and
+ *   inactive sample    sample_index_dev[s] < 0 (tested before row_offset is added): every workgroup of the sample, in both stages,
+ *                      returns before its first vector-memory instruction.  Nothing of the sample is read; factor_dev[s],
+ *                      stats_dev[2 s .. 2 s + 1] and the sample's partials keep their bytes.
+ *   unrescaled sample  the row's convert_k[1] is exactly zero (+0 or -0): the same exit in both stages.  A request that does not
+ *                      rescale costs no statistics traffic, and its factor is never written.
+ *   active, rescaled   factor_dev[s] -- and stats_dev[2 s .. 2 s + 1] when given -- have, bit for bit, what
+ *                      skr_guidance_rescale_factor writes for that sample alone with scale = convert_k[0]: the documented order of
+ *                      summation (2048-element spans, lane t owning elements 8 t .. 8 t + 7, the shuffle tree o = 32 .. 1,
+ *                      ((w0 + w1) + w2) + w3, stage 2 in span order) and the partials layout SKR_GUIDANCE_PARTIALS, unchanged.
+ * Coverage is the rolling step's: bf16, fp16 or fp32, sample_numel a positive multiple of 2048 that divides numel.  Every span is then
+ * whole and 16-byte aligned -- the kernels have the vector path only -- and the fp16 tail rule cannot arise (numel % 2048 == 0).
+ * Checked before the launch, without dereferencing device memory, in this order: a NULL uncond, cond, factor_dev, partials_dev,
+ * rows_dev or sample_index_dev SKR_ERR_NULL;  numel < 0, sample_numel < 2 or sample_numel not dividing numel SKR_ERR_SHAPE;
+ * numel == 0 SKR_OK with nothing launched;  uncond or cond not 16-byte aligned SKR_ERR_ALIGN;  a dtype that is no tensor dtype
+ * SKR_ERR_DTYPE;  fp64, sample_numel % 2048 != 0, a negative row_offset or more than INT32_MAX spans SKR_ERR_UNSUPPORTED.
+ * Allocates nothing, never synchronises: capturable.
+ */
+int skr_guidance_rescale_factor_rolling(const void* uncond, const void* cond, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                        const skr_step_row* rows_dev,
+                                        const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */,
+                                        int32_t row_offset, void* factor_dev /* T[numel / sample_numel] */,
+                                        double* stats_dev /* [2 * samples]: std(cond), std(p); may be NULL */,
+                                        double* partials_dev /* [SKR_GUIDANCE_PARTIALS(numel, sample_numel)] */, void* stream);
+
+/*
+ * skr_step_launch_guided_rescaled_rolling: skr_step_launch_guided_rolling whose guided value is p' for the samples that rescale.
+ * Structure, coverage, checks, their order and their codes are those of skr_step_launch_guided_rolling; on top of them, in the places
+ * where skr_step_launch_guided_rescaled puts its own: a NULL rescale SKR_ERR_NULL (beside the NULL plan), a non-zero
+ * rescale->reserved SKR_ERR_UNSUPPORTED, a NULL rescale->factor_dev SKR_ERR_NULL (beside the NULL operands), and
+ * rescale->sample_numel != plan->sample_numel SKR_ERR_SHAPE.  rescale->phi and guide->scale are ignored: both are row values.
+ * Inactive sample, absent operand and operand order are exactly those of skr_step_launch_guided_rolling, and
+ *   rescaled sample    the row's convert_k[1] is not +-0.  phi_M is that value narrowed once, psi_M = 1.0 - convert_k[1] formed in
+ *                      double on the device and narrowed once, r = factor_dev[s] one uniform load behind the operand loads, and
+ *                      p' = rn_T(rn_T(phi_M * rn_T(p * r)) + rn_T(psi_M * p)) as in skr_step_launch_guided_rescaled.  `out` and
+ *                      `guided_out` have, bit for bit, what skr_step_launch_guided_rescaled gives that sample alone with a plan
+ *                      holding exactly the present operands in order, the row's values, guide->scale = convert_k[0] and
+ *                      rescale = {&factor_dev[s], convert_k[1], sample_numel, 0}.
+ *   unrescaled sample  the row's convert_k[1] is exactly +-0.  factor_dev[s] is NOT read -- it may hold NaN or be uninitialised --,
+ *                      p' = p, and the sample has the bits skr_step_launch_guided_rolling gives it.  A branch, uniform over the
+ *                      workgroup, not arithmetic: 0 * inf does not leak through.
+ */
+int skr_step_launch_guided_rescaled_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                            const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel,
+                                            const skr_step_row* rows_dev,
+                                            const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */,
+                                            int32_t row_offset, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

@@ -42,6 +42,8 @@ EXPORTS = (
     "skr_step_launch_guided_rolling",
     "skr_guidance_rescale_factor",
     "skr_step_launch_guided_rescaled",
+    "skr_guidance_rescale_factor_rolling",
+    "skr_step_launch_guided_rescaled_rolling",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -481,6 +483,10 @@ def load() -> ctypes.CDLL:
         lib.skr_guidance_rescale_factor.restype = ctypes.c_int
         lib.skr_step_launch_guided_rescaled.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp]
         lib.skr_step_launch_guided_rescaled.restype = ctypes.c_int
+        lib.skr_guidance_rescale_factor_rolling.argtypes = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp]
+        lib.skr_guidance_rescale_factor_rolling.restype = ctypes.c_int
+        lib.skr_step_launch_guided_rescaled_rolling.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp, vp, i32, vp]
+        lib.skr_step_launch_guided_rescaled_rolling.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -713,3 +719,21 @@ def launch_step_guided_rolling_raw(plan: StepPlanC, arr, out_ptr, guide: StepGui
     pointer array, `guide`: its descriptor (cond, guided_out or NULL, slot; the scale is each sample's row value); the caller owns every
     check of the index (rolling.RollingBatch)."""
     return load().skr_step_launch_guided_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), seeds_ptr, numel, rows_ptr, sample_index_ptr, row_offset, stream_ptr)
+
+
+def launch_guidance_factor_rolling_raw(uncond_ptr, cond_ptr, dtype_code: int, numel: int, sample_numel: int, rows_ptr, sample_index_ptr, row_offset: int, factor_ptr, stats_ptr,
+                                       partials_ptr, stream_ptr) -> int:
+    """the statistics launch of a rescaled guided rolling batch (skr_guidance_rescale_factor_rolling) from raw pointers; returns the status
+    code.  Scale and phi are each sample's row values (convert_k[0], convert_k[1]); inactive samples and samples whose phi is zero are
+    skipped, their factor left alone.  `stats_ptr` may be None; the caller owns the partials workspace and every check of the index."""
+    return load().skr_guidance_rescale_factor_rolling(uncond_ptr, cond_ptr, dtype_code, numel, sample_numel, rows_ptr, sample_index_ptr, row_offset, factor_ptr, stats_ptr,
+                                                      partials_ptr, stream_ptr)
+
+
+def launch_step_guided_rescaled_rolling_raw(plan: StepPlanC, arr, out_ptr, guide: StepGuidanceC, rescale: StepRescaleC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr,
+                                            row_offset: int, stream_ptr) -> int:
+    """one rescaled guided rolling step launch (skr_step_launch_guided_rescaled_rolling) from raw pointers; returns the status code.
+    `guide` as in launch_step_guided_rolling_raw; `rescale`: the factor tensor the statistics launch wrote and the sample size (its phi is
+    ignored: each sample's is its row's convert_k[1]); the caller owns every check of the index (rolling.RollingBatch)."""
+    return load().skr_step_launch_guided_rescaled_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), ctypes.byref(rescale), seeds_ptr, numel, rows_ptr,
+                                                          sample_index_ptr, row_offset, stream_ptr)

@@ -10,33 +10,11 @@
 //     loads per operand and lane, any other span -- the last of a ragged sample, every span of a sample that starts off a 16-byte
 //     boundary -- element by element with a bounds test.
 //   stage 2 (rescale_stats_final<T>): one wave per sample; lanes 0..3 each sum one of the four quantities over the sample's spans.
-#include "skr_step_guided.h"
+// The sums behind the loads and the last operations are shared with the rolling form (skr_guidance_stats.h, skr_guidance_stats_rolling.hip).
+#include "skr_guidance_stats.h"
 #include "skr_device.h"
 
 namespace skr {
-
-constexpr int64_t SPAN = (int64_t)BLOCK * VEC;  // elements per stage-1 workgroup; 4 doubles of partials each
-static_assert(SPAN == 2048, "the span is part of the documented summation order (SKR_GUIDANCE_PARTIALS)");
-
-// the guided value of element e of the launch in the op-math type M of T
-template <typename T, typename M>
-__device__ __forceinline__ M stat_guided(M u, M c, M g, int64_t e, int64_t tail_from) {
-  if constexpr (std::is_same<T, double>::value) return guide_d(u, c, g);
-  else if constexpr (std::is_same<T, f16_t>::value) return e >= tail_from ? guided_value_f16_tail(u, c, g) : guided_value<f16_t>(u, c, g);
-  else return guided_value<T>(u, c, g);
-}
-
-template <typename T, typename M>
-__device__ __forceinline__ M stat_load(const void* base, int64_t e) {
-  if constexpr (std::is_same<T, double>::value) return reinterpret_cast<const double*>(base)[e];
-  else return load_scalar<T>(base, e);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);  // (a double shuffle is two 32-bit moves)
-  return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void rescale_stats_spans(const void* uncond, const void* cond, double scale, int64_t numel, int64_t sample_numel, uint32_t spans,
@@ -69,38 +47,11 @@ __global__ __launch_bounds__(BLOCK) void rescale_stats_spans(const void* uncond,
   const M c_first = stat_load<T, M>(cond, first);
   const double kc = (double)c_first, kp = (double)stat_guided<T, M>(stat_load<T, M>(uncond, first), c_first, g, first, tail_from);
 
-  double s1c = 0.0, s2c = 0.0, s1p = 0.0, s2p = 0.0;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    if (at + i < len) {
-      const double dc = sub_((double)c[i], kc);
-      const double dp = sub_((double)stat_guided<T, M>(u[i], c[i], g, start + at + i, tail_from), kp);
-      s1c = add_(s1c, dc);
-      s2c = fma_(dc, dc, s2c);
-      s1p = add_(s1p, dp);
-      s2p = fma_(dp, dp, s2p);
-    }
-  }
-
-  __shared__ double red[4][4];
-  s1c = wave_sum(s1c), s2c = wave_sum(s2c), s1p = wave_sum(s1p), s2p = wave_sum(s2p);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = s1c; red[1][wave] = s2c; red[2][wave] = s1p; red[3][wave] = s2p; }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const double* r = red[threadIdx.x];
-    partials[(int64_t)blockIdx.x * 4 + threadIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
-  }
-}
-
-__device__ __forceinline__ double unbiased_std(double s1, double s2, double n) {
-  const double var = div_(sub_(s2, div_(mul_(s1, s1), n)), sub_(n, 1.0));
-  return __dsqrt_rn(var > 0.0 || var != var ? var : 0.0);  // max(var, 0); a NaN stays one
+  span_sums<T, M, false>(u, c, g, kc, kp, at, len, start, tail_from, partials + (int64_t)blockIdx.x * 4);
 }
 
 template <typename T>
 __global__ __launch_bounds__(64) void rescale_stats_final(const double* partials, uint32_t spans, int64_t sample_numel, void* factor, double* stats) {
-  using M = typename OpMath<T>::type;
   const int64_t smp = blockIdx.x;
   double acc = 0.0;
   if (threadIdx.x < 4) {
@@ -109,16 +60,7 @@ __global__ __launch_bounds__(64) void rescale_stats_final(const double* partials
   }
   const double s1c = __shfl(acc, 0), s2c = __shfl(acc, 1), s1p = __shfl(acc, 2), s2p = __shfl(acc, 3);
   if (threadIdx.x != 0) return;
-  const double n = (double)sample_numel;
-  const double std_c = unbiased_std(s1c, s2c, n), std_p = unbiased_std(s1p, s2p, n);
-  if (stats != nullptr) { stats[2 * smp] = std_c; stats[2 * smp + 1] = std_p; }
-  if constexpr (std::is_same<T, double>::value) {
-    reinterpret_cast<double*>(factor)[smp] = div_(std_c, std_p);
-  } else {
-    // torch: std() of a T tensor is its fp32 result rounded to T; T / T is an fp32 division rounded to T
-    const M r = div_(rnd<T>((M)std_c), rnd<T>((M)std_p));
-    store_scalar<T, M>(factor, smp, r);
-  }
+  stats_finish<T>(s1c, s2c, s1p, s2p, sample_numel, smp, factor, stats);
 }
 
 }  // namespace skr

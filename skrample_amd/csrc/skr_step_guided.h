@@ -34,6 +34,25 @@ __device__ __forceinline__ float guided_value(float u, float c, float g) {
   return rnd<T>(p);
 }
 
+// diffusers' rescale_noise_cfg of the guided value p with the sample's factor r (skr_step_guided_rescaled.hip and its rolling form): the
+// four torch ops behind the guided value, one rounded operation at a time, each fp32 result pinned in a register of its own (neither
+// fused nor paired into packed instructions: see guided_value)
+template <typename T>
+__device__ __forceinline__ float rescaled_value(float p, float r, float phi, float psi) {
+  float resc = mul_(p, r);
+  asm("" : "+v"(resc));
+  resc = rnd<T>(resc);
+  float a = mul_(phi, resc);
+  asm("" : "+v"(a));
+  a = rnd<T>(a);
+  float b = mul_(psi, p);
+  asm("" : "+v"(b));
+  b = rnd<T>(b);
+  float q = add_(a, b);
+  asm("" : "+v"(q));
+  return rnd<T>(q);
+}
+
 // fp16 elements of the partial last block of torch's vectorised elementwise kernel (TORCH_TAIL below).  Its compiler fuses the scalar
 // multiply with the conversion there (v_fma_mixlo_f16), so  g * d  is rounded ONCE, from the exact product, where the whole blocks round
 // the fp32 product again.  (d is an fp16 value and g an fp32 one: the product has up to 35 significant bits.  c - u and u + m are sums
@@ -63,6 +82,10 @@ constexpr int64_t TORCH_TAIL = 2048;
 static_assert(TORCH_TAIL == (int64_t)BLOCK * VEC, "whole chunks must be whole blocks of torch's kernel: the one-trip kernel has no tail path");
 
 __device__ __forceinline__ double guide_d(double u, double c, double g) { return add_(u, mul_(g, sub_(c, u))); }
+
+// the rolling forms (skr_step_guided_rolling.hip, skr_step_guided_rescaled_rolling.hip): an operand other than the slot is present unless
+// its coef0 is exactly zero (either sign): decided on the row's double, in SGPRs
+__device__ __forceinline__ bool guided_row_has(const skr_step_row* row, int j) { return (__builtin_bit_cast(uint64_t, row->coef0[j]) << 1) != 0; }
 
 // What the entry checks of a guided launch leave behind for its launcher.
 struct GuidedLaunch {

@@ -18,23 +18,6 @@
 
 namespace skr {
 
-// the four torch ops behind the guided value, one rounded operation at a time, each fp32 result pinned in a register of its own (neither
-// fused nor paired into packed instructions: see guided_value)
-template <typename T>
-__device__ __forceinline__ float rescaled_value(float p, float r, float phi, float psi) {
-  float resc = mul_(p, r);
-  asm("" : "+v"(resc));
-  resc = rnd<T>(resc);
-  float a = mul_(phi, resc);
-  asm("" : "+v"(a));
-  a = rnd<T>(a);
-  float b = mul_(psi, p);
-  asm("" : "+v"(b));
-  b = rnd<T>(b);
-  float q = add_(a, b);
-  asm("" : "+v"(q));
-  return rnd<T>(q);
-}
 // fp16 elements of the partial last block of torch's elementwise kernels: the scalar products are rounded once (p * r is exact in fp32,
 // a + b is a sum of two fp16 values: neither is changed by its second rounding).  Measured against torch on the device: the fused
 // multiply-and-convert of that block is a multiply-ADD with +0 (v_fma_mixlo_f16 k, x, 0), so a product that is exactly zero comes out

@@ -1,0 +1,154 @@
+// The rescaled guided solver step for the slots of a rolling batch (include/skrample_hip.h, skr_step_launch_guided_rescaled_rolling):
+// guided_rolling_kernel_v1 (skr_step_guided_rolling.hip) whose guided value is diffusers' rescale_noise_cfg of it for the samples that
+// rescale, each under its own phi -- the row's convert_k[1] -- and its own factor r = factor_dev[s], what the rolling statistics launch
+// wrote for it (skr_guidance_stats_rolling.hip).
+//
+//   p   = rn_T( u + rn_T( g * rn_T(c - u) ) )       u = inputs[slot], c = cond;  g = (float)row.convert_k[0]
+//   p'  = rn_T( rn_T(phi * rn_T(p * r)) + rn_T(psi * p) )   phi = (float)row.convert_k[1], psi = (float)(1.0 - row.convert_k[1]): the row's phi not +-0
+//   p'  = p                                                  the row's phi exactly +-0: factor_dev[s] is NOT read (it may hold NaN)
+//   out = sum_k c0[k]*v_k + zeta0*N(stream0)        v_slot = p', v_k = in_k otherwise, over the PRESENT operands
+//   guided_out = p'                                 (when asked for)
+//
+// Inactive sample, absent operand and operand order are those of guided_rolling_kernel_v1, and so is the statement order: the row first,
+// the row's doubles into SGPRs, the loads of the present operands and cond, the factor behind them inside the `phi != 0` branch, the
+// Philox rounds while all of them are in flight.  Whether a sample rescales is a real branch, uniform over the workgroup (a scalar one,
+// exec never masked), not arithmetic: the lone step_guided(..., guidance_rescale=0.0) is the unrescaled launch, and 0 * inf would
+// otherwise leak through.  guided_value and rescaled_value are the shared ones (skr_step_guided.h), so a rescaled sample has the bits of
+// skr_step_launch_guided_rescaled and an unrescaled one those of skr_step_launch_guided_rolling.  There is no grid-stride form.
+#include "skr_step_guided.h"
+#include "skr_device.h"
+
+namespace skr {
+
+// Kernarg: GuidedRollingArgs (skr_step_guided_rolling.hip) with the factor.  What the first instructions need (chunk map, row reference)
+// is read first; an operand's pointer, and the factor's, is read inside the branch that loads it.
+template <int KMAX>
+struct GuidedRescaledRollingArgs {
+  const void* in[KMAX];
+  const void* cond;
+  void* out;
+  void* guided;         // nullptr: p' is not stored
+  int32_t xmap_lr;      // log2(run length) of the XCD chunk map
+  int32_t bps_shift;    // chunks per sample: log2 when >= 0, minus the count otherwise (see sample_of)
+  const uint64_t* seeds;
+  const void* factor;   // T[samples]: read for the samples that rescale
+  RowRef tab;
+  int32_t slot;         // the operand that p' replaces in the sum
+};
+
+template <typename T, int K, bool NOISE>
+__global__ __launch_bounds__(BLOCK) void guided_rescaled_rolling_kernel_v1(const GuidedRescaledRollingArgs<guided_kmax(K)> a) {
+  constexpr bool TILE = sizeof(T) == 4;  // whole chunks are whole tiles, as in guided_rolling_kernel_v1
+  const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
+  const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
+  uint32_t smp, within;
+  const skr_step_row* row = rolling_row(a.tab, c, a.bps_shift, smp, within);
+  if (row == nullptr) return;  // inactive sample: nothing read, nothing written
+  const int32_t slot = a.slot;
+  // (a row's doubles stay in SGPRs and are narrowed where they are used)
+  double c0[K];
+  bool on[K];  // operand j is present
+#pragma unroll
+  for (int j = 0; j < K; ++j) { c0[j] = row->coef0[j]; on[j] = j == slot || guided_row_has(row, j); }
+  const float zeta0 = (float)row->zeta0, g = (float)row->convert_k[0];
+  const double phi_d = row->convert_k[1];
+  const bool rescales = (__builtin_bit_cast(uint64_t, phi_d) << 1) != 0;  // (uniform) phi is not +-0
+  [[maybe_unused]] const uint64_t stream0 = row->stream0;
+  Raw<T> raw[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) if (on[j]) raw[j] = load_raw<T, TILE>(a.in[j], v);
+  Raw<T> rc = load_raw<T, TILE>(a.cond, v);
+  float r = 0.f, phi = 0.f, psi = 0.f;
+  if (rescales) {  // one uniform load behind the operand loads; an unrescaled sample's factor is never touched
+    r = load_scalar<T>(a.factor, (int64_t)smp);
+    phi = (float)phi_d;
+    psi = (float)sub_(1.0, phi_d);  // 1 - phi formed in double, narrowed once
+  }
+  // A NOISE instantiation serves every row: one whose zeta0 narrows to zero skips the draw (a uniform branch), as a launch without noise does.
+  float z[VEC];
+  [[maybe_unused]] bool n0 = false;
+  if constexpr (NOISE) {
+    n0 = zeta0 != 0.f;
+    if (n0) {
+      const uint32_t vs = within * BLOCK + threadIdx.x;  // lane-vector within the sample (sample_numel < 2^31)
+      const uint64_t seed = a.seeds[smp];
+      normal4(seed, stream0, (uint64_t)group0<TILE>((int64_t)vs), z);
+      normal4(seed, stream0, (uint64_t)group1<TILE>((int64_t)vs), z + 4);
+    }
+  }
+  float s[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) s[i] = 0.f;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    if (on[j]) {  // (uniform: the row's) present operands in slot order: the bits of the narrower launch that holds exactly these
+      float w[VEC];
+      widen<T, float>(raw[j], w);
+      if (j == slot) {  // (uniform: a kernarg scalar against the unrolled operand's number) the guided value takes this operand's place
+        float cf[VEC];
+        widen<T, float>(rc, cf);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) w[i] = guided_value<T>(w[i], cf[i], g);
+        if (rescales) {  // (uniform: the row's) a real branch: p' = p otherwise
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) w[i] = rescaled_value<T>(w[i], r, phi, psi);
+        }
+        if (a.guided != nullptr) store8<T, float, TILE>(a.guided, v, w);  // (p' is a value of T: the store's rounding is exact)
+      }
+      const float w0 = (float)c0[j];
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) s[i] = fma_(w0, w[i], s[i]);
+    }
+  }
+  if constexpr (NOISE) { if (n0) fma_noise8<float>(zeta0, z, s); }
+  store8<T, float, TILE>(a.out, v, s);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+// dtype x noise x operand count to the instantiation, and its kernarg
+static void launch_guided_rescaled_rolling_v1(const skr_step_plan& p, const void* const* inputs, void* out, const skr_step_guidance& gd, const skr_step_rescale& rs,
+                                              const uint64_t* seeds, const GuidedLaunch& l, const RowRef& tab, hipStream_t s) {
+  with_step_type<false>(p.dtype_a, [&](auto tt) {
+    with_bools([&](auto nz) {
+      with_count<1, SKR_ROW_TERMS>(p.n_terms, [&](auto n) {
+        using T = typename decltype(tt)::type;
+        constexpr int N = decltype(n)::value, KMAX = guided_kmax(N);
+        GuidedRescaledRollingArgs<KMAX> a;
+        for (int k = 0; k < KMAX; ++k) a.in[k] = k < N ? inputs[k] : nullptr;
+        a.cond = gd.cond; a.out = out; a.guided = gd.guided_out; a.seeds = seeds; a.factor = rs.factor_dev;
+        a.xmap_lr = xmap_lr_for(l.chunks); a.bps_shift = l.bps_shift;
+        a.tab = tab; a.slot = gd.slot;
+        hipLaunchKernelGGL((guided_rescaled_rolling_kernel_v1<T, N, decltype(nz)::value>), dim3((unsigned)l.chunks), dim3(BLOCK), 0, s, a);
+      });
+    }, l.noise);
+  });
+}
+
+// The entry: the checks of skr_step_launch_guided_rolling, in its order and with its codes, and what skr_step_launch_guided_rescaled adds
+// where it adds it (guided_prepare, skr_step_guided.hip).
+static int guided_rescaled_rolling_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                               const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, void* stream, const skr_step_row* rows,
+                                               const int32_t* index, int32_t row_offset) {
+  if (!plan || !guide || !rescale || !rows || !index) return SKR_ERR_NULL;
+  const skr_step_plan& p = *plan;
+  GuidedLaunch l;
+  if (const int rc = guided_prepare(p, *guide, inputs, out, seeds_dev, numel, true, &l, rescale)) return rc;
+  if (numel == 0) return SKR_OK;
+  if (!l.one_trip || row_offset < 0) return SKR_ERR_UNSUPPORTED;
+  // a workgroup lies inside one sample, with or without noise, and that sample is the statistic's
+  constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
+  if (p.sample_numel <= 0 || numel % p.sample_numel != 0 || rescale->sample_numel != p.sample_numel) return SKR_ERR_SHAPE;
+  if (p.sample_numel % CHUNK != 0 || p.sample_numel >= (1ll << 31)) return SKR_ERR_UNSUPPORTED;
+  l.bps_shift = bps_shift_of(p.sample_numel / CHUNK);
+  DeviceGuard device_guard(out);
+  launch_guided_rescaled_rolling_v1(p, inputs, out, *guide, *rescale, seeds_dev, l, RowRef{rows, index, row_offset}, reinterpret_cast<hipStream_t>(stream));
+  return finish_launch();
+}
+
+}  // namespace skr
+
+extern "C" int skr_step_launch_guided_rescaled_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                                       const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel,
+                                                       const skr_step_row* rows_dev, const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
+  return skr::guided_rescaled_rolling_launch_impl(plan, inputs, out, guide, rescale, seeds_dev, numel, stream, rows_dev, sample_index_dev, row_offset);
+}

@@ -39,9 +39,6 @@ struct GuidedRollingArgs {
   int32_t slot;         // the operand that p replaces in the sum
 };
 
-// an operand other than the slot is present unless its coef0 is exactly zero (either sign): decided on the row's double, in SGPRs
-__device__ __forceinline__ bool guided_row_has(const skr_step_row* row, int j) { return (__builtin_bit_cast(uint64_t, row->coef0[j]) << 1) != 0; }
-
 template <typename T, int K, bool NOISE>
 __global__ __launch_bounds__(BLOCK) void guided_rolling_kernel_v1(const GuidedRollingArgs<guided_kmax(K)> a) {
   constexpr bool TILE = sizeof(T) == 4;  // whole chunks are whole tiles: 32-bit tensors take the whole-line layout, as in guided_kernel_v1

@@ -90,7 +90,27 @@ capture time.  Covered: Euler, DPM 1-3, Adams 2-4 and UniP 2-3, with or without 
 latents under the default compute scale.  Refused when the batch is built, each with its reason: a sampler whose guided step is not one
 fused launch (UniPC, SPC, `compute_scale=None`), `guided` beside `inpaint_mask_shape`, `guided` beside Offset / Pyramid noise, and
 whatever the one-trip guided kernel does not cover.  Not covered: changing a resident request's scale mid-run (admit it with a schedule),
-`guidance_rescale`, channels-last, the Runge-Kutta wrappers, autograd.
+channels-last, the Runge-Kutta wrappers, autograd.
+
+Rescaled guidance (`guided=True, rescaled=True`): diffusers' `rescale_noise_cfg` with a `guidance_rescale` (phi) per request, or per step:
+
+    batch = RollingBatch(make_wrapper, example, capacity=B, guided=True, rescaled=True)
+    batch.admit(slot, latents, wrapper, steps, guidance_scale=7.5, guidance_rescale=0.7)   # or one phi per step; 0.0 (the default): not rescaled
+    done = batch.step_guided(uncond, cond)
+
+phi travels in the row's `convert_k[1]` beside the scale in `convert_k[0]` (zero in every other batch's rows).  A tick is two launches on
+the current stream with the same index, rows and row offset: `skr_guidance_rescale_factor_rolling` (csrc/skr_guidance_stats_rolling.hip)
+writes std(cond) / std(prediction) of every active slot whose phi is not zero into the batch's `factor` tensor, `[capacity]` in the latents'
+dtype, through a partial-sum workspace -- both allocated once, when the batch is built, the same in every phase of `CapturedTicks` --; then
+`skr_step_launch_guided_rescaled_rolling` (csrc/skr_step_guided_rescaled_rolling.hip) steps every active slot, with the rescaled prediction
+where phi is not zero and with the plain guided one -- its factor unread -- where it is.  Free slots, finished slots and requests that do
+not rescale cost no statistics traffic; the tick has the same two launches whether or not a resident request rescales.  Every request has
+the bits of its lone `step_guided(uncond, cond, g, t, x, guidance_rescale=phi)` run, and a request with phi = 0 throughout those of a
+guided batch built without `rescaled`.  Ring upkeep, `guided_out` (NULL for Euler), the returned slots, "nothing of the caller is held",
+`advance()`, `device_positions=True`, `capture(model)` (`CapturedTicks.tick()`: one replay plus the two eager launches) and the refusals
+of a guided batch are unchanged.  `rescaled=True` without `guided=True`, a negative, NaN or non-number `guidance_rescale`, a schedule of
+the wrong length and a non-zero `guidance_rescale` on a batch built without `rescaled` are refused.  Not covered: changing a resident
+request's phi mid-run (admit it with a schedule), skipping the statistics launch from the host when nobody rescales.
 
 Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
 `Random` noise (drawn in the kernel), `Offset` / `Pyramid` noise (drawn per slot, above) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
@@ -113,7 +133,7 @@ from typing import Callable, Sequence
 import torch
 
 from . import _hip
-from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepGuidanceC, StepMaskC, StepPlanC, StepRowC, upload_rows
+from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepGuidanceC, StepMaskC, StepPlanC, StepRescaleC, StepRowC, upload_rows
 from .sampling import lazy
 
 Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py; ("orig",) ("znoise",): a masked batch's original / re-noising tensor;
@@ -203,14 +223,19 @@ class RollingBatch:
     `alias_history`: True keeps the caller's model outputs as history operands (0 bytes written; overwriting one that is still
     held raises), False snapshots each one.  `device_positions`: True keeps every slot's position, run length and timesteps on
     the device (`advance()` before each `step()`, or `capture()`); the host publishes nothing per tick.  `guided`: True makes a tick
-    `step_guided(uncond, cond)`, one `skr_step_launch_guided_rolling` with every request's own guidance scale (module docstring)."""
+    `step_guided(uncond, cond)`, one `skr_step_launch_guided_rolling` with every request's own guidance scale (module docstring).
+    `rescaled` (with `guided`): True makes that tick two launches -- `skr_guidance_rescale_factor_rolling`, then
+    `skr_step_launch_guided_rescaled_rolling` -- with every request's own `guidance_rescale` beside its scale (module docstring)."""
 
     def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True,
-                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False):  # fmt: skip
+                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False, rescaled: bool = False):  # fmt: skip
         if capacity < 1:
             raise ValueError("a rolling batch has at least one slot")
         self.masked = inpaint_mask_shape is not None
         self.guided = bool(guided)
+        self.rescaled = bool(rescaled)
+        if self.rescaled and not self.guided:
+            raise ValueError("rescaled=True needs guided=True: guidance_rescale is applied to the guided prediction a guided batch forms")
         if self.guided and self.masked:
             raise ValueError("guided together with inpaint_mask_shape: a guided step under set_inpaint is not one fused launch (guided in-painting batches are not covered)")
         self.capacity, self.max_steps, self.alias_history = int(capacity), int(max_steps), bool(alias_history)
@@ -252,6 +277,12 @@ class RollingBatch:
         # a guided batch: the guided predictions of the last ticks, oldest first, as long as the latents ring (so that the phases of
         # CapturedTicks close); [-1] is the tensor this tick's launch stores into, ("po", k) the one of -k ticks ago.  Euler keeps none.
         self._g = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1)] if self.guided and self.keep else []
+        if self.rescaled:
+            # a rescaled batch: every slot's factor std(cond) / std(p) and the partial sums behind it, written by the tick's statistics
+            # launch and read by its step launch; allocated once, the same in every phase of CapturedTicks
+            self.factor = torch.zeros(self.capacity, dtype=self.dtype, device=self.device)
+            self._partials = torch.zeros(_hip.guidance_partials(self.numel, self.sample_numel), dtype=torch.float64, device=self.device)
+            self._rescale_desc = StepRescaleC(self.factor.data_ptr(), 0.0, self.sample_numel, 0)
         self._outputs: list[torch.Tensor] = []
         self._stamps: list[tuple[torch.Tensor, int, int]] = []
         self._results: dict[int, torch.Tensor] = {}
@@ -401,6 +432,15 @@ class RollingBatch:
     def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None, cond: torch.Tensor | None = None, guided_out: torch.Tensor | None = None) -> None:
         if self.guided:  # (one output; `cond` and `guided_out` -- None: not stored -- are launch arguments, the scale each slot's row value)
             guide = StepGuidanceC(cond.data_ptr(), guided_out.data_ptr() if guided_out is not None else None, 0.0, self.slot, 0)
+            if self.rescaled:  # (the statistics launch, then the step launch: same stream, same index, same rows, same row_offset)
+                rows, index, stream = self.rows_dev.data_ptr(), self.index_dev.data_ptr(), _hip.current_stream_ptr(self.device)
+                status = _hip.launch_guidance_factor_rolling_raw(arr[self.slot], cond.data_ptr(), _hip.DTYPE_CODE[self.dtype], self.numel, self.sample_numel, rows, index, 0,
+                                                                 self.factor.data_ptr(), None, self._partials.data_ptr(), stream)  # fmt: skip
+                _hip.check(status, "skr_guidance_rescale_factor_rolling")
+                status = _hip.launch_step_guided_rescaled_rolling_raw(self.plan, arr, out0.data_ptr(), guide, self._rescale_desc, self.seeds_dev.data_ptr() if self.draws_noise else None,
+                                                                      self.numel, rows, index, 0, stream)  # fmt: skip
+                _hip.check(status, "skr_step_launch_guided_rescaled_rolling")
+                return
             status = _hip.launch_step_guided_rolling_raw(self.plan, arr, out0.data_ptr(), guide, self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel,
                                                          self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0, _hip.current_stream_ptr(self.device))  # fmt: skip
             _hip.check(status, "skr_step_launch_guided_rolling")
@@ -473,8 +513,9 @@ class RollingBatch:
             self.slot = roles.index(("o",))
         return wide, list(roles)
 
-    def _rows_of(self, traced, scales: Sequence[float] | None = None) -> list[StepRowC]:
-        "`scales` (a guided batch): the guidance scale of every step, carried in the row's convert_k[0] (a guided plan has no rounded conversion)"
+    def _rows_of(self, traced, scales: Sequence[float] | None = None, rescales: Sequence[float] | None = None) -> list[StepRowC]:
+        """`scales` (a guided batch): the guidance scale of every step, carried in the row's convert_k[0] (a guided plan has no rounded
+        conversion); `rescales` (a rescaled batch): guidance_rescale of every step, in convert_k[1] -- zero in every other batch's rows"""
         rows = []
         for step, (plan, roles, _) in enumerate(traced):
             if (plan.dtype_a, plan.acc_f64, plan.convert_to, plan.convert_from) != (self.plan.dtype_a, self.plan.acc_f64, self.plan.convert_to, self.plan.convert_from):
@@ -488,6 +529,8 @@ class RollingBatch:
                 if row.coef0[self.slot] != plan.coef0[list(roles).index(("o",))]:  # (place_row put `uncond` where the batch's launches replace it)
                     raise SkrampleHipError(f"the `uncond` operand of this step is not at the batch's slot {self.slot}")
                 row.convert_k[0] = float(scales[step])
+                if self.rescaled and rescales is not None:
+                    row.convert_k[1] = float(rescales[step])
             rows.append(row)
         return rows
 
@@ -527,7 +570,7 @@ class RollingBatch:
         return out
 
     def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None, inpaint: Sequence[torch.Tensor] | None = None,
-              guidance_scale: "float | Sequence[float] | None" = None) -> None:  # fmt: skip
+              guidance_scale: "float | Sequence[float] | None" = None, guidance_rescale: "float | Sequence[float]" = 0.0) -> None:  # fmt: skip
         """Start a request in a free slot: `latents` of one sample, `wrapper` with this request's schedule / stochasticity (same
         sampler structure as the batch; it is consumed by the dry run that produces the rows), `steps` its run length.
         `inpaint` (a batch built with `inpaint_mask_shape` only): (mask, original_samples, noise) of ONE sample -- the request is an
@@ -535,7 +578,9 @@ class RollingBatch:
         its own tensors (the mask cast to the latents' dtype, as set_inpaint casts it).  None there: a plain request sharing the
         batch -- its mask is ones and its rows name neither the original nor the re-noising tensor.
         `guidance_scale` (a batch built with `guided=True` only, and required there): the request's classifier-free-guidance scale, a
-        float, or a sequence of exactly `steps` floats -- a guidance schedule: the row of step i carries guidance_scale[i]."""
+        float, or a sequence of exactly `steps` floats -- a guidance schedule: the row of step i carries guidance_scale[i].
+        `guidance_rescale` (non-zero on a batch built with `rescaled=True` only): the request's phi of diffusers' rescale_noise_cfg, a
+        Python number >= 0, or a sequence of exactly `steps` of them -- a rescale schedule; a step whose phi is zero is not rescaled."""
         self._check_slot(slot)
         if self._requests[slot] is not None:
             raise ValueError(f"slot {slot} is busy: take() its result first" if slot in self._finished else f"slot {slot} is busy")
@@ -559,6 +604,7 @@ class RollingBatch:
                     raise ValueError(f"a guidance schedule has one scale per step: {len(scales)} scales for {steps} steps")
         elif guidance_scale is not None:
             raise ValueError("guidance_scale= needs a batch built with guided=True: this one steps with step(model_output)")
+        rescales = self._rescales_of(guidance_rescale, steps)
         noisy = bool(wrapper.sampler.require_noise)
         if noisy and not self.draws_noise:
             raise ValueError("this wrapper draws noise and the batch's sampler structure does not")
@@ -598,7 +644,7 @@ class RollingBatch:
         traced = self._trace(wrapper, steps, seed if noisy else None)
         if len(traced) != steps:
             raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
-        request = _Request(self._rows_of(traced, scales) if self.guided else self._rows_of(traced), [t for _, _, t in traced])
+        request = _Request(self._rows_of(traced, scales, rescales) if self.guided else self._rows_of(traced), [t for _, _, t in traced])
         upload_rows(self.rows_dev, slot * self.max_steps, request.rows)
         self._x[-1][slot].copy_(latents.reshape(self.unit_shape))
         if noisy:
@@ -613,6 +659,30 @@ class RollingBatch:
             return
         self._times_host[slot] = request.times[0]
         self.timesteps.copy_(self._times_host)
+
+    def _rescales_of(self, guidance_rescale, steps: int) -> list[float]:
+        "guidance_rescale of every step of a request: a Python number >= 0 or exactly `steps` of them, non-zero on a rescaled batch only"
+
+        def one(phi) -> float:
+            if isinstance(phi, bool) or not isinstance(phi, lazy.NUMBER):
+                raise ValueError(f"guidance_rescale is a Python number, not {type(phi).__name__}")
+            if not phi >= 0.0:
+                raise ValueError(f"guidance_rescale must be >= 0, not {phi}")
+            return float(phi)
+
+        if isinstance(guidance_rescale, (str, bytes, torch.Tensor)) or isinstance(guidance_rescale, lazy.NUMBER):
+            rescales = [one(guidance_rescale)] * steps
+        else:
+            try:
+                given = list(guidance_rescale)
+            except TypeError:
+                raise ValueError(f"guidance_rescale is a Python number, not {type(guidance_rescale).__name__}") from None
+            rescales = [one(phi) for phi in given]
+            if len(rescales) != steps:
+                raise ValueError(f"a rescale schedule has one guidance_rescale per step: {len(rescales)} values for {steps} steps")
+        if not self.rescaled and any(phi != 0.0 for phi in rescales):
+            raise ValueError("guidance_rescale= needs a batch built with guided=True, rescaled=True: this one's tick has no statistics launch")
+        return rescales
 
     def take(self, slot: int) -> torch.Tensor:
         "the result of a finished slot; the slot is free again"

@@ -667,6 +667,75 @@ int skr_step_launch_guided_rescaled_rolling(const skr_step_plan* plan, const voi
                                             int32_t row_offset, void* stream);
 
 /*
+ * Rescaled guidance in captured loops: the two launches of rescaled guidance with every per-row scalar taken from the row that
+ * skr_step_launch_guided_indexed[_per_sample] reads --
+ *     indexed      rows_dev[(index_dev ? index_dev[0] : 0) + row_offset]
+ *     per sample   rows_dev[sample_index_dev[s] + row_offset]            for the workgroups of sample s
+ * -- convert_k[0] the guidance scale, convert_k[1] phi = guidance_rescale (skr_step_launch_guided_indexed[_per_sample] do not read it).
+ * convert_k[2..3], coef1, chain, zeta1 and stream1 are not read.  A captured loop then serves any schedule, any scale and any
+ * guidance_rescale, zero included, without a re-capture.  A step is the statistics launch, then the step launch, with the same index,
+ * rows and row_offset.  There is no inactive-sample semantic: every index names a row.  Index validity is the caller's business, as with
+ * skr_step_launch_guided_indexed: index_dev[0] + row_offset, and every sample_index_dev[s] + row_offset, must name a row of the table;
+ * the kernels neither check nor clamp an index (skrample_amd.graphs.CapturedLoop validates on the host).  No entry has a grid-stride form.
+ *
+ * skr_guidance_rescale_factor_indexed[_per_sample]: skr_guidance_rescale_factor with the scale of sample s its row's convert_k[0], and
+ *   unrescaled row   the row's convert_k[1] is exactly zero (+0 or -0): every workgroup that reads the row, in both stages, returns
+ *                    before its first vector-memory instruction -- in the indexed form every workgroup of the launch.  Nothing is
+ *                    read; factor_dev, stats_dev and the partials keep their bytes there.
+ *   rescaled row     factor_dev[s] -- and stats_dev[2 s .. 2 s + 1] when given -- and the sample's partials have, bit for bit, what
+ *                    skr_guidance_rescale_factor writes for that sample alone with scale = convert_k[0]: the documented order of
+ *                    summation and the partials layout SKR_GUIDANCE_PARTIALS, unchanged.
+ * Coverage and checks are those of skr_guidance_rescale_factor_rolling, in its order and with its codes: bf16, fp16 or fp32,
+ * sample_numel a positive multiple of 2048 that divides numel; a NULL uncond, cond, factor_dev, partials_dev or rows_dev -- or a NULL
+ * sample_index_dev in the per-sample entry; index_dev may be NULL -- SKR_ERR_NULL;  numel < 0, sample_numel < 2 or sample_numel not
+ * dividing numel SKR_ERR_SHAPE;  numel == 0 SKR_OK with nothing launched;  uncond or cond not 16-byte aligned SKR_ERR_ALIGN;  a dtype
+ * that is no tensor dtype SKR_ERR_DTYPE;  fp64, sample_numel % 2048 != 0, a negative row_offset or more than INT32_MAX spans
+ * SKR_ERR_UNSUPPORTED.  Allocates nothing, never synchronises: capturable.
+ */
+int skr_guidance_rescale_factor_indexed(const void* uncond, const void* cond, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                        const skr_step_row* rows_dev, const int32_t* index_dev /* device int32, may be NULL */,
+                                        int32_t row_offset, void* factor_dev /* T[numel / sample_numel] */,
+                                        double* stats_dev /* [2 * samples]: std(cond), std(p); may be NULL */,
+                                        double* partials_dev /* [SKR_GUIDANCE_PARTIALS(numel, sample_numel)] */, void* stream);
+
+int skr_guidance_rescale_factor_indexed_per_sample(const void* uncond, const void* cond, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                                   const skr_step_row* rows_dev,
+                                                   const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                                   int32_t row_offset, void* factor_dev /* T[numel / sample_numel] */,
+                                                   double* stats_dev /* [2 * samples]: std(cond), std(p); may be NULL */,
+                                                   double* partials_dev /* [SKR_GUIDANCE_PARTIALS(numel, sample_numel)] */, void* stream);
+
+/*
+ * skr_step_launch_guided_rescaled_indexed[_per_sample]: skr_step_launch_guided_indexed[_per_sample] whose guided value is p' when the
+ * row rescales.  Structure, coverage, checks, their order and their codes are those of skr_step_launch_guided_indexed[_per_sample]; on
+ * top of them, in the places where skr_step_launch_guided_rescaled_rolling puts them: a NULL rescale SKR_ERR_NULL (beside the NULL
+ * plan), a non-zero rescale->reserved SKR_ERR_UNSUPPORTED, a NULL rescale->factor_dev SKR_ERR_NULL (beside the NULL operands), and
+ * rescale->sample_numel != plan->sample_numel SKR_ERR_SHAPE.  The factor is per sample, so in BOTH entries a workgroup must lie inside
+ * one sample: plan->sample_numel must be a positive multiple of 2048 that divides numel, with or without noise (SKR_ERR_SHAPE /
+ * SKR_ERR_UNSUPPORTED otherwise).  rescale->phi and guide->scale are ignored: both are row values.  Every operand takes its fma, zero
+ * coefficients included: there is no absent-operand rule here.
+ *   rescaled row     the row's convert_k[1] is not +-0.  phi_M is that value narrowed once, psi_M = 1.0 - convert_k[1] formed in double
+ *                    on the device and narrowed once, r = factor_dev[s] one uniform load behind the operand loads, and
+ *                    p' = rn_T(rn_T(phi_M * rn_T(p * r)) + rn_T(psi_M * p)) as in skr_step_launch_guided_rescaled.  `out` and
+ *                    `guided_out` have, bit for bit, what skr_step_launch_guided_rescaled gives with the row's values in its plan, in
+ *                    guide->scale and in rescale->phi -- for a sample of the per-sample entry: that launch on the sample alone with
+ *                    rescale->factor_dev = &factor_dev[s].
+ *   unrescaled row   the row's convert_k[1] is exactly +-0.  factor_dev is NOT read -- it may hold NaN or be uninitialised --, p' = p,
+ *                    and the launch (the sample) has the bits skr_step_launch_guided_indexed[_per_sample] gives it.  A branch, uniform
+ *                    over the workgroup, not arithmetic: 0 * inf does not leak through.
+ */
+int skr_step_launch_guided_rescaled_indexed(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                            const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel,
+                                            const skr_step_row* rows_dev, const int32_t* index_dev /* device int32, may be NULL */,
+                                            int32_t row_offset, void* stream);
+
+int skr_step_launch_guided_rescaled_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                                       const skr_step_guidance* guide, const skr_step_rescale* rescale,
+                                                       const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                                       const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                                       int32_t row_offset, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

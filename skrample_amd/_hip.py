@@ -44,6 +44,10 @@ EXPORTS = (
     "skr_step_launch_guided_rescaled",
     "skr_guidance_rescale_factor_rolling",
     "skr_step_launch_guided_rescaled_rolling",
+    "skr_guidance_rescale_factor_indexed",
+    "skr_guidance_rescale_factor_indexed_per_sample",
+    "skr_step_launch_guided_rescaled_indexed",
+    "skr_step_launch_guided_rescaled_indexed_per_sample",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -210,12 +214,15 @@ def guidance_partials(numel: int, sample_numel: int) -> int:
     return 4 * (numel // sample_numel) * ((sample_numel + GUIDANCE_SPAN - 1) // GUIDANCE_SPAN)
 
 
-def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None, guide: "StepGuidanceC | None" = None) -> tuple:
+def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None, guide: "StepGuidanceC | None" = None,
+                   rescale: "StepRescaleC | None" = None) -> tuple:
     """what a captured launch freezes: everything of a plan except the scalars a row carries (`sample_numel` = False: and the sample size).
     A masked launch (`mask`: its descriptor) adds that it is one, the mask's dtype and whether one mask serves the whole batch
     (batch_stride == 0), and -- shape-like, dropped with the sample size -- the mask's elements per sample.
     A guided launch (`guide`: its descriptor) adds that it is one, the operand the guided value replaces (`slot`) and whether that value
-    is stored; its scale is a row value."""
+    is stored; its scale is a row value.  `rescale` (a rescaled guided launch: its descriptor) adds nothing: phi is a row value as well and
+    the factor a buffer of the hook, so the plain and the rescaled guided launch of a step are ONE structure -- a refill may move a slot
+    between guidance_rescale == 0 and != 0."""
     plain = (plan.n_terms, plan.n_group_a, plan.dtype_a, plan.dtype_b, plan.out0_dtype, plan.out1_dtype, plan.acc_f64, plan.noise_mode,
              plan.sample_numel if sample_numel else None, plan.convert_to, plan.convert_from)  # fmt: skip
     if guide is not None:
@@ -240,14 +247,29 @@ class IndexedRows:
     `sample_index_dev[b] + k`.
     `guided` (a capture with guidance): guided launches go through the recorder as well (skr_step_launch_guided_indexed[_per_sample]),
     each row carrying its launch's guidance scale.
+    `rescaled` (with `guided`; `samples`: the captured batch): rescaled guided launches go through it too, each row carrying
+    guidance_rescale in convert_k[1] -- 0.0 for a plain guided launch.  Every emitted guided step is then TWO launches on buffers the hook
+    owns (`factor`, `partials`: allocated in the recording pass, the same in every step of the graph), with the same row offset:
+    skr_guidance_rescale_factor_indexed[_per_sample], then skr_step_launch_guided_rescaled_indexed[_per_sample] -- whether or not the
+    recording pass rescaled, since a row with phi == 0 makes the first return at once and the second the plain guided step.
 
     mode "record": launches run normally and append one row each (their structure is remembered);
     mode "emit"  : launches become indexed launches reading row `base + k` (k = position in the loop) -- used under graph capture;
     mode "refill": launches run normally (on whatever tensors the dry run uses) and overwrite row `slot*length + k` after checking
                    that the structure is the captured one -- how a captured loop is re-targeted to another schedule."""
 
-    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None, guided: bool = False):
+    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None, guided: bool = False, rescaled: bool = False, samples: int | None = None):
+        if rescaled and not guided:
+            raise ValueError("rescaled=True needs guided=True: guidance_rescale is applied to the guided prediction a guided launch forms")
+        if rescaled and (samples is None or samples < 1):
+            raise ValueError("rescaled=True needs samples=: the captured batch, one factor per sample")
+        if rescaled and batch is not None and batch != samples:
+            raise ValueError(f"a per-sample capture of {batch} samples cannot hold factors for {samples}")
         self.device, self.slots, self.batch = device, slots, batch
+        # a capture with rescaled guidance: the factor T[samples] and the partials workspace of every emitted statistics launch
+        self.rescaled, self.samples = rescaled, samples
+        self.factor: torch.Tensor | None = None
+        self.partials: torch.Tensor | None = None
         # a capture with guidance: launch_step_guided goes through this hook (skr_step_launch_guided_indexed[_per_sample]), and a row
         # carries the guidance scale in convert_k[0]; any other hook refuses a guided launch
         self.guided = guided
@@ -261,8 +283,9 @@ class IndexedRows:
         self.slot = 0
 
     @staticmethod
-    def row_from(plan: StepPlanC, scale: float | None = None) -> StepRowC:
-        "the row of a launch; `scale`: a guided one's guidance scale, kept in convert_k[0] (such a plan has no rounded conversion)"
+    def row_from(plan: StepPlanC, scale: float | None = None, phi: float | None = None) -> StepRowC:
+        """the row of a launch; `scale`: a guided one's guidance scale, kept in convert_k[0] (such a plan has no rounded conversion);
+        `phi` (a hook created with `rescaled`): its guidance_rescale, kept in convert_k[1] -- 0.0 for a plain guided launch"""
         if plan.n_terms > ROW_TERMS:
             raise SkrampleHipError(f"a launch with {plan.n_terms} operands does not fit a device-resident row ({ROW_TERMS})")
         row = StepRowC()
@@ -273,6 +296,8 @@ class IndexedRows:
             row.convert_k[k] = plan.convert_k[k]
         if scale is not None:
             row.convert_k[0] = scale
+        if phi is not None:
+            row.convert_k[1] = phi
         return row
 
     def finish_recording(self) -> None:
@@ -331,15 +356,50 @@ class IndexedRows:
             return "guided rows need at least one operand"
         return None
 
+    def _uncovered_rescaled(self, plan: StepPlanC, numel: int) -> str | None:
+        "why the rescaled guided row kernels do not cover this launch of the captured batch (skr_step_launch_guided_rescaled_indexed), or None"
+        if numel % self.samples != 0 or (numel // self.samples) % PER_SAMPLE_CHUNK != 0:
+            return f"rescaled guided rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {numel} elements for {self.samples} samples"
+        if plan.sample_numel > 0 and plan.sample_numel != numel // self.samples:
+            return f"rescaled guided rows take the statistic over the samples the noise is drawn by: {numel // self.samples} elements, not {plan.sample_numel}"
+        return None
+
+    def _emit_rescaled(self, lib, plan: StepPlanC, arr, out0_ptr, guide: "StepGuidanceC", seeds_ptr, numel: int, stream_ptr: int, k: int) -> int:
+        """the two launches of a guided step of a rescaled capture, on the hook's factor and partials and with the same row offset: the
+        statistics row launch over (inputs[slot], cond), then the rescaled row step.  A row with phi == 0 makes the first return before it
+        reads anything and the second the plain guided step."""
+        per = numel // self.samples
+        if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
+            plan = StepPlanC.from_buffer_copy(plan)
+            plan.sample_numel = per
+        if numel != self.samples * plan.sample_numel:
+            raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {self.samples} samples of {plan.sample_numel} the factor holds")
+        rescale = StepRescaleC(self.factor.data_ptr(), 0.0, per, 0)  # (phi is the row's)
+        per_sample = self.sample_index_dev is not None
+        rows, index, uncond = self.rows_dev.data_ptr(), (self.sample_index_dev if per_sample else self.index_dev).data_ptr(), arr[guide.slot]
+        statistic = lib.skr_guidance_rescale_factor_indexed_per_sample if per_sample else lib.skr_guidance_rescale_factor_indexed
+        step = lib.skr_step_launch_guided_rescaled_indexed_per_sample if per_sample else lib.skr_step_launch_guided_rescaled_indexed
+        status = statistic(uncond, guide.cond, plan.dtype_a, numel, per, rows, index, k, self.factor.data_ptr(), None, self.partials.data_ptr(), stream_ptr)
+        if status != 0:
+            return status
+        return step(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), ctypes.byref(rescale), seeds_ptr, numel, rows, index, k, stream_ptr)
+
     def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int, mask: "StepMaskC | None" = None,
-               guide: "StepGuidanceC | None" = None) -> int:
+               guide: "StepGuidanceC | None" = None, rescale: "StepRescaleC | None" = None) -> int:
         """one launch of the loop; `mask` (its descriptor): a masked one (skr_step_launch_masked and its row forms; out1_ptr is None);
-        `guide` (its descriptor): a guided one (skr_step_launch_guided and its row forms; out1_ptr is None), whose scale goes into the row"""
+        `guide` (its descriptor): a guided one (skr_step_launch_guided and its row forms; out1_ptr is None), whose scale goes into the row;
+        `rescale` (with `guide`, under a hook created with `rescaled`): a rescaled guided one, whose phi goes into the row as well"""
         k = self.cursor
         self.cursor += 1
         scale = guide.scale if guide is not None else None
+        phi = None
+        rescaled = guide is not None and getattr(self, "rescaled", False)  # (a recorder put together without the constructor has no such field)
+        if rescaled:
+            phi = rescale.phi if rescale is not None else 0.0  # (a plain guided launch is what the wrapper issues for guidance_rescale == 0)
 
         def run_now() -> int:  # the launch itself, with the plan's own scalars
+            if rescale is not None:
+                return lib.skr_step_launch_guided_rescaled(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), ctypes.byref(rescale), seeds_ptr, numel, stream_ptr)
             if guide is not None:
                 return lib.skr_step_launch_guided(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, stream_ptr)
             if mask is not None:
@@ -359,23 +419,34 @@ class IndexedRows:
                 why = self._uncovered_guided(plan, numel)
                 if why is not None:  # (what skr_step_launch_guided_indexed would answer during the capture)
                     raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
-            row = self.row_from(plan, scale)
-            self.structures.append(plan_structure(plan, mask=mask, guide=guide))
-            self.shapeless.append(plan_structure(plan, sample_numel=False, mask=mask, guide=guide))
+                if rescaled:
+                    why = self._uncovered_rescaled(plan, numel)
+                    if why is not None:  # (what skr_step_launch_guided_rescaled_indexed would answer during the capture)
+                        raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
+                    if self.factor is None:  # allocated here, before a stream captures; every emitted step of the graph uses these two
+                        self.factor = torch.zeros(self.samples, dtype=CODE_DTYPE[plan.dtype_a], device=self.device)
+                        self.partials = torch.zeros(guidance_partials(numel, numel // self.samples), dtype=torch.float64, device=self.device)
+                    elif self.factor.dtype != CODE_DTYPE[plan.dtype_a] or self.partials.numel() != guidance_partials(numel, numel // self.samples):
+                        raise SkrampleHipError(f"launch {k}: the guided steps of one rescaled capture share one factor and one workspace: one dtype and one size")
+            row = self.row_from(plan, scale, phi)
+            self.structures.append(plan_structure(plan, mask=mask, guide=guide, rescale=rescale))
+            self.shapeless.append(plan_structure(plan, sample_numel=False, mask=mask, guide=guide, rescale=rescale))
             self.host.append(row)
             return run_now()
         if k >= self.length:
             raise SkrampleHipError("more launches than the captured loop has")
         if self.mode == "refill":
-            found = plan_structure(plan, sample_numel=False, mask=mask, guide=guide)
+            found = plan_structure(plan, sample_numel=False, mask=mask, guide=guide, rescale=rescale)
             if mask is not None and len(found) == len(self.shapeless[k]) and numel == plan.sample_numel:
                 found = (*found[:-2], self.shapeless[k][-2], found[-1])  # (a dry run on one sample has no batch stride to compare)
             if found != self.shapeless[k]:
                 raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
-            self.host[self.slot * self.length + k] = self.row_from(plan, scale)
+            self.host[self.slot * self.length + k] = self.row_from(plan, scale, phi)
             return run_now()
-        if plan_structure(plan, mask=mask, guide=guide) != self.structures[k]:
+        if plan_structure(plan, mask=mask, guide=guide, rescale=rescale) != self.structures[k]:
             raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
+        if rescaled:
+            return self._emit_rescaled(lib, plan, arr, out0_ptr, guide, seeds_ptr, numel, stream_ptr, k)
         if self.sample_index_dev is not None:
             if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
                 plan = StepPlanC.from_buffer_copy(plan)
@@ -487,6 +558,12 @@ def load() -> ctypes.CDLL:
         lib.skr_guidance_rescale_factor_rolling.restype = ctypes.c_int
         lib.skr_step_launch_guided_rescaled_rolling.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp, vp, i32, vp]
         lib.skr_step_launch_guided_rescaled_rolling.restype = ctypes.c_int
+        for factor_rows in (lib.skr_guidance_rescale_factor_indexed, lib.skr_guidance_rescale_factor_indexed_per_sample):
+            factor_rows.argtypes = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp]
+            factor_rows.restype = ctypes.c_int
+        for rescaled_rows in (lib.skr_step_launch_guided_rescaled_indexed, lib.skr_step_launch_guided_rescaled_indexed_per_sample):
+            rescaled_rows.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp, vp, i32, vp]
+            rescaled_rows.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -666,8 +743,8 @@ def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond:
     check(status, "skr_step_launch_guided")
 
 
-NO_RESCALED_ROWS = ("rescaled guidance (guidance_rescale) has no row form: capture the loop with indexed=False, which freezes guidance_rescale into "
-                    "the graph, or pass guidance_rescale=0.0")
+NO_RESCALED_ROWS = ("rescaled guidance (guidance_rescale) has no row form in a loop captured without it: pass rescaled=True to capture_sampling_loop (guidance_rescale "
+                    "is then a row value), capture the loop with indexed=False, which freezes guidance_rescale into the graph, or pass guidance_rescale=0.0")
 
 
 def launch_guidance_factor(uncond: torch.Tensor, cond: torch.Tensor, scale: float, sample_numel: int, factor: torch.Tensor, stats: "torch.Tensor | None" = None) -> None:
@@ -675,13 +752,18 @@ def launch_guidance_factor(uncond: torch.Tensor, cond: torch.Tensor, scale: floa
     per sample of `sample_numel` elements in storage order, rounded as torch rounds it; `stats` (float64[2 * samples] or None) receives
     the two standard deviations.  The workspace comes from torch's allocator, which is safe under graph capture.
     A `_hip.trace` list receives ("guidance_factor", uncond, cond, scale, sample_numel, factor, stats): no plan leads it, no step program
-    is built from it.  Under the indexed-rows hook it raises: there is no row form of rescaled guidance."""
+    is built from it.  Under an indexed-rows hook created for a rescaled capture (IndexedRows(guided=True, rescaled=True)) it runs as it
+    stands while the hook records or refills, and is NOT issued while the hook emits: the step launch that follows emits the statistics
+    row launch itself, on the hook's buffers (IndexedRows._emit_rescaled).  Under any other hook it raises."""
     lib = load()
-    if getattr(_hooks, "indexed", None) is not None:
+    rows = getattr(_hooks, "indexed", None)
+    if rows is not None and not getattr(rows, "rescaled", False):
         raise SkrampleHipError(NO_RESCALED_ROWS)
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append(("guidance_factor", uncond, cond, scale, sample_numel, factor, stats))
+    if rows is not None and rows.mode == "emit":
+        return
     numel = uncond.numel()
     partials = torch.empty(max(guidance_partials(numel, sample_numel), 1), dtype=torch.float64, device=uncond.device)
     status = lib.skr_guidance_rescale_factor(uncond.data_ptr(), cond.data_ptr(), DTYPE_CODE[uncond.dtype], float(scale), numel, int(sample_numel), factor.data_ptr(),
@@ -694,9 +776,13 @@ def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], o
     """one rescaled guided step launch (skr_step_launch_guided_rescaled): launch_step_guided with the guided value p replaced by
     phi * (p * factor[sample]) + (1 - phi) * p, rounded as torch's four tensor ops round it; `guided_out` (or None) receives that value.
     A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, cond, guided_out, scale, slot, factor, phi, sample_numel) --
-    thirteen entries no step program is built from.  Under the indexed-rows hook it raises: there is no row form of rescaled guidance."""
+    thirteen entries no step program is built from.  Under an indexed-rows hook created for a rescaled capture
+    (IndexedRows(guided=True, rescaled=True): capture_sampling_loop with `rescaled=True`) the launch is recorded, emitted as
+    skr_guidance_rescale_factor_indexed[_per_sample] plus skr_step_launch_guided_rescaled_indexed[_per_sample] -- scale and phi row values,
+    `factor` replaced by the hook's own -- or refilled (IndexedRows.launch).  Under any other hook it raises."""
     lib = load()
-    if getattr(_hooks, "indexed", None) is not None:
+    rows = getattr(_hooks, "indexed", None)
+    if rows is not None and not getattr(rows, "rescaled", False):
         raise SkrampleHipError(NO_RESCALED_ROWS)
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
@@ -704,6 +790,9 @@ def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], o
     desc = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
     rescale = StepRescaleC(factor.data_ptr(), float(phi), int(sample_numel), 0)
     arr, stream = _operand_array(operands), current_stream_ptr(device)
+    if rows is not None:
+        check(rows.launch(lib, plan, arr, _ptr(out), None, _ptr(seeds), numel, stream, guide=desc, rescale=rescale), "skr_step_launch_guided_rescaled")
+        return
     status = lib.skr_step_launch_guided_rescaled(ctypes.byref(plan), arr, _ptr(out), ctypes.byref(desc), ctypes.byref(rescale), _ptr(seeds), numel, stream)
     check(status, "skr_step_launch_guided_rescaled")
 

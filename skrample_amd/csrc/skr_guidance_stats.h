@@ -1,4 +1,5 @@
-// What the statistic of rescaled guidance (skr_guidance_stats.hip) and its rolling form (skr_guidance_stats_rolling.hip) share: the summation
+// What the statistic of rescaled guidance (skr_guidance_stats.hip), its rolling form (skr_guidance_stats_rolling.hip) and its row forms
+// (skr_guidance_stats_rows.hip) share: the summation
 // order documented in include/skrample_hip.h (skr_guidance_rescale_factor) -- a lane's eight elements in index order, the shuffle tree
 // o = 32 .. 1, the four waves as ((w0 + w1) + w2) + w3 -- and the last operations behind the sums.  One body, so that a sample has the
 // same bits through either entry.
@@ -22,6 +23,15 @@ template <typename T, typename M>
 __device__ __forceinline__ M stat_load(const void* base, int64_t e) {
   if constexpr (std::is_same<T, double>::value) return reinterpret_cast<const double*>(base)[e];
   else return load_scalar<T>(base, e);
+}
+
+// the first element of a 16-byte aligned run of T, read as one dword from a uniform address (the pivots of the row and rolling forms)
+template <typename T>
+__device__ __forceinline__ float first_of(const char* at) {
+  const uint32_t w = *reinterpret_cast<const uint32_t*>(at);
+  if constexpr (std::is_same<T, bf16_t>::value) return __uint_as_float(w << 16);
+  else if constexpr (std::is_same<T, f16_t>::value) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
+  else return __uint_as_float(w);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

@@ -25,15 +25,6 @@ __device__ __forceinline__ const skr_step_row* rescaling_row(const RowRef& r, ui
   return (__builtin_bit_cast(uint64_t, row->convert_k[1]) << 1) != 0 ? row : nullptr;  // phi == +-0: the sample does not rescale
 }
 
-// the first element of a 16-byte aligned run of T, read as one dword from a uniform address
-template <typename T>
-__device__ __forceinline__ float first_of(const char* at) {
-  const uint32_t w = *reinterpret_cast<const uint32_t*>(at);
-  if constexpr (std::is_same<T, bf16_t>::value) return __uint_as_float(w << 16);
-  else if constexpr (std::is_same<T, f16_t>::value) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
-  else return __uint_as_float(w);
-}
-
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void rescale_stats_spans_rolling(const void* uncond, const void* cond, int64_t sample_numel, uint32_t spans, const RowRef tab,
                                                                      double* partials) {

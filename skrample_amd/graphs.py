@@ -33,6 +33,13 @@ Classifier-free guidance (`guidance_scale=`): `model(x, t)` returns `(uncond, co
 cond, guidance_scale, t, x)`, whose guidance runs inside the step launch.  A plain capture freezes the scale into the graph; an indexed
 one keeps it in the rows (`skr_step_launch_guided_indexed[_per_sample]`), so `retarget(wrapper, slot, guidance_scale=...)` loads another
 scale beside another schedule, several scales stay resident, and with `per_sample=True` every sample of a replay follows its own.
+
+Rescaled guidance (`guidance_rescale=`, diffusers' `rescale_noise_cfg`): a plain capture freezes phi into the graph.  An indexed capture
+made with `rescaled=True` keeps it in the rows beside the scale (`convert_k[1]`): every guided step of the graph is the statistics row
+launch and the rescaled row step (`skr_guidance_rescale_factor_indexed[_per_sample]`, `skr_step_launch_guided_rescaled_indexed[_per_sample]`)
+on one factor tensor and one workspace the loop owns, `retarget(wrapper, slot, guidance_rescale=...)` loads another phi -- 0.0 included,
+which makes the first launch return at once and the second the plain guided step -- and with `per_sample=True` every sample follows its
+own.  Without `rescaled=True` an indexed capture refuses a non-zero `guidance_rescale`, as before.
 """
 
 from __future__ import annotations
@@ -65,8 +72,10 @@ class CapturedLoop:
 
     def __init__(self, graph: torch.cuda.CUDAGraph, static_in: torch.Tensor, static_out: torch.Tensor, seeds_dev: torch.Tensor | None, rows=None, runner=None,
                  static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None, inpaint: tuple | None = None,
-                 guidance_scale: float | None = None):
+                 guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False):
         self.guidance_scale = guidance_scale  # the scale the loop was captured with, or None: a loop captured without guidance
+        # the phi the loop was captured with, and whether it is a row value (captured with rescaled=True) that retarget may replace
+        self.guidance_rescale, self.rescaled = guidance_rescale, rescaled
         self.inpaint = inpaint  # (mask, original_samples, noise) the captured masked steps read, or None: a loop captured without in-painting
         self.graph, self.static_in, self.static_out, self.seeds_dev = graph, static_in, static_out, seeds_dev
         self.rows, self._runner = rows, runner  # _hip.IndexedRows of an indexed capture; runner(wrapper, x) = the captured loop body
@@ -116,11 +125,13 @@ class CapturedLoop:
         if self.sample_times is not None:
             self.sample_times.copy_(self._assemble_times(self._sample_slots))  # one copy, stream-ordered ahead of the replay
 
-    def retarget(self, wrapper, slot: int = 0, guidance_scale: float | None = None) -> None:
+    def retarget(self, wrapper, slot: int = 0, guidance_scale: float | None = None, guidance_rescale: float | None = None) -> None:
         """Load the step scalars of `wrapper` (same sampler structure and number of steps as the captured one, any schedule /
         shift / begin index / stochasticity) into table slot `slot`: a dry run of its loop on one sample fills the rows, one
         small host-to-device copy publishes them.  The graph itself is untouched.
         A loop captured with `guidance_scale` loads a scale into the slot as well: `guidance_scale`, or the captured one when None.
+        A loop captured with `rescaled=True` loads a phi too: `guidance_rescale`, or the captured one when None; 0.0 turns the rescale
+        off for that slot.  On any other loop a `guidance_rescale` is refused: its phi, if any, is frozen into the graph.
         A loop captured with in-painting takes a wrapper that has `set_inpaint(...)` in force itself (the dry run steps on one-sample
         views of ITS tensors); only its scalars reach the graph, which goes on reading `loop.inpaint`."""
         from . import _hip
@@ -131,13 +142,21 @@ class CapturedLoop:
             raise ValueError(f"slot {slot} outside 0..{self.rows.slots - 1}")
         if guidance_scale is not None and self.guidance_scale is None:
             raise ValueError("this loop was captured without guidance: pass guidance_scale= to capture_sampling_loop")
+        if guidance_rescale is not None and not self.rescaled:
+            raise ValueError("this loop was captured without rescaled=True: its guidance_rescale is not a row value; pass rescaled=True to capture_sampling_loop")
+        if self.guidance_scale is not None:
+            from .sampling import lazy
+
+            scale = guidance_scale if guidance_scale is not None else self.guidance_scale
+            phi = guidance_rescale if guidance_rescale is not None else self.guidance_rescale
+            lazy.check_guidance_numbers(scale, phi)  # (before anything of the slot changes)
         self.rows.begin("refill", slot)
         _hip.indexed = self.rows
         try:
             if self.guidance_scale is None:
                 self._runner(wrapper, self.static_in[:1].clone())
             else:
-                self._runner(wrapper, self.static_in[:1].clone(), guidance_scale if guidance_scale is not None else self.guidance_scale)
+                self._runner(wrapper, self.static_in[:1].clone(), scale, phi)
         finally:
             _hip.indexed = None
         if self.rows.cursor != self.rows.length:
@@ -251,7 +270,7 @@ class CapturedLoops:
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
                           indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False,
-                          guidance_scale: float | None = None, guidance_rescale: float = 0.0) -> CapturedLoop:
+                          guidance_scale: float | None = None, rescaled: bool = False, guidance_rescale: float = 0.0) -> CapturedLoop:
     """Capture `for t in wrapper.timesteps: x = wrapper.step(model(x, t), t, x)` for `steps` steps.
 
     `wrapper` is any scheduler wrapper of skrample_amd.diffusers; `model(x, t)` must be capturable (pure device
@@ -281,25 +300,36 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     guidance is a launch of its own -- is refused during the recording pass, before the stream captures.
 
     `guidance_rescale` (with `guidance_scale`; 0.0: nothing changes): the loop body is `wrapper.step_guided(..., guidance_rescale=...)`.
-    With `indexed=False` the statistics launch and the rescaled step are captured, guidance_rescale frozen into the graph.  There is no
-    row form of rescaled guidance: `indexed=True` (and so `per_sample`) with a non-zero guidance_rescale is refused during the recording
-    pass, before the stream captures.
+    With `indexed=False` the statistics launch and the rescaled step are captured, guidance_rescale frozen into the graph.  A loop
+    captured without `rescaled` has no row form of rescaled guidance: `indexed=True` (and so `per_sample`) with a non-zero
+    guidance_rescale is refused during the recording pass, before the stream captures.
+
+    `rescaled` (a keyword, like its neighbours; needs `indexed=True` and `guidance_scale`; off by default, and then nothing changes): guidance_rescale -- 0.0 allowed --
+    is a row value beside the scale.  Every guided step of the graph is two launches, the statistics row launch and the rescaled row
+    step, on one factor tensor `[batch]` and one workspace the loop owns; `loop.retarget(wrapper, slot, guidance_rescale=...)` loads
+    another phi, zero included, and with `per_sample=True` every sample follows its own.  On top of what a guided indexed capture needs,
+    every sample must be made of whole 2048-element chunks.  Anything else is refused during the recording pass, before the stream
+    captures.
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
     if guidance_rescale != 0.0 and guidance_scale is None:
         raise ValueError("guidance_rescale belongs to a guided loop: pass guidance_scale= as well")
+    if rescaled and not indexed:
+        raise ValueError("rescaled=True needs indexed=True: it makes guidance_rescale a value of the device-resident rows (a plain capture freezes it into the graph)")
+    if rescaled and guidance_scale is None:
+        raise ValueError("rescaled=True belongs to a guided loop: pass guidance_scale= as well")
     from .pytorch import noise as _noise
 
     _noise._private_vectors[0] += 1  # the loop's seed vector is overwritten in place by replays with new seeds: it is this loop's alone
     try:
-        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale)
+        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale, rescaled)
     finally:
         _noise._private_vectors[0] -= 1
 
 
 def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False,
-             guidance_scale: float | None = None, guidance_rescale: float = 0.0) -> CapturedLoop:
+             guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False) -> CapturedLoop:
     dev = example.device
     static_in = example.clone()
     gen = list(seeds) if seeds is not None else None
@@ -319,11 +349,11 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     sample_times = static_times.detach().clone().unsqueeze(1).repeat(1, example.shape[0]).contiguous() if per_sample and device_timesteps else None
     model_times = [sample_times[i] for i in range(sample_times.shape[0])] if sample_times is not None else times
 
-    def step_of(w, x, t, tm, generator, scale):  # the loop body: a guided capture's network returns (uncond, cond)
+    def step_of(w, x, t, tm, generator, scale, rescale=guidance_rescale):  # the loop body: a guided capture's network returns (uncond, cond)
         if scale is None:
             return w.step(model(x, tm), t, x, generator=generator, return_dict=False)[0]
         uncond, cond = model(x, tm)
-        return w.step_guided(uncond, cond, scale, t, x, generator=generator, return_dict=False, guidance_rescale=guidance_rescale)[0]
+        return w.step_guided(uncond, cond, scale, t, x, generator=generator, return_dict=False, guidance_rescale=rescale)[0]
 
     def run(x):
         wrapper.reset_run()  # same schedule, same device seed vector; history and draw counter rewound
@@ -331,7 +361,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
             x = step_of(wrapper, x, t, tm, gen, guidance_scale)
         return x
 
-    def run_other(other, x, scale=None):  # the same loop body on another scheduler instance (re-targeting dry run, one sample); `scale`: its guidance scale
+    def run_other(other, x, scale=None, rescale=guidance_rescale):  # the same loop body on another scheduler instance (re-targeting dry run, one sample) under its own scale and phi
         other.set_timesteps(steps, device=dev) if device_timesteps else other.set_timesteps(steps)
         sub = gen[: x.shape[0]] if gen is not None else None
         ts = other.timesteps
@@ -343,7 +373,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         try:
             for t in ([ts[i] for i in range(ts.numel())] if device_timesteps else ts.tolist()):
                 tm = t.reshape(1).expand(x.shape[0]) if sample_times is not None else t  # (the dry run's samples: `t` of shape [1])
-                x = step_of(other, x, t, tm, sub, scale)
+                x = step_of(other, x, t, tm, sub, scale, rescale)
         finally:
             if held is not None:
                 other._inpaint = held
@@ -363,7 +393,8 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     if indexed:
         from . import _hip
 
-        rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None, guided=guidance_scale is not None)
+        rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None, guided=guidance_scale is not None,
+                                rescaled=rescaled, samples=int(example.shape[0]) if rescaled else None)
         _hip.indexed = rows
         try:
             rows.begin("record")
@@ -386,4 +417,4 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     from .pytorch.noise import forget_seed_vector
 
     forget_seed_vector(seeds_dev)  # the graph reads this very buffer and replays may overwrite it: no other run may share it from now on
-    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale)
+    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale, guidance_rescale, rescaled)

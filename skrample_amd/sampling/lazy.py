@@ -123,6 +123,16 @@ class RoundedConversion:
         return self
 
 
+def check_guidance_numbers(scale, rescale=0.0) -> None:
+    "what a guidance scale and a guidance_rescale must be, wherever they enter (Guidance, CapturedLoop.retarget): one set of messages"
+    if isinstance(scale, bool) or not isinstance(scale, NUMBER):
+        raise SkrampleHipError(f"the guidance scale is a Python number, not {type(scale).__name__}")
+    if isinstance(rescale, bool) or not isinstance(rescale, NUMBER):
+        raise SkrampleHipError(f"guidance_rescale is a Python number, not {type(rescale).__name__}")
+    if not rescale >= 0.0:
+        raise SkrampleHipError(f"guidance_rescale must be >= 0, not {rescale}")
+
+
 class Guidance:
     """The classifier-free-guidance prediction  uncond + scale * (cond - uncond)  as ONE leaf of a step's form: its value is torch's --
     three tensor ops, each rounded in the tensors' dtype, the Python scalar kept in the op-math type -- and `evaluate_guided` computes
@@ -140,12 +150,7 @@ class Guidance:
             raise SkrampleHipError(
                 f"guidance needs uncond and cond of one dtype, shape and device: {uncond.dtype} {tuple(uncond.shape)} {uncond.device} vs {cond.dtype} {tuple(cond.shape)} {cond.device}"
             )
-        if isinstance(scale, bool) or not isinstance(scale, NUMBER):
-            raise SkrampleHipError(f"the guidance scale is a Python number, not {type(scale).__name__}")
-        if isinstance(rescale, bool) or not isinstance(rescale, NUMBER):
-            raise SkrampleHipError(f"guidance_rescale is a Python number, not {type(rescale).__name__}")
-        if not rescale >= 0.0:
-            raise SkrampleHipError(f"guidance_rescale must be >= 0, not {rescale}")
+        check_guidance_numbers(scale, rescale)
         if rescale != 0.0 and (uncond.ndim < 2 or uncond.numel() // max(uncond.shape[0], 1) < 2):
             raise SkrampleHipError(f"rescaled guidance takes the std of every sample: it needs tensors of ndim >= 2 (dim 0 the sample) with at least 2 elements per sample, not {tuple(uncond.shape)}")
         self.uncond, self.cond, self.scale, self.rescale = uncond, cond, float(scale), float(rescale)

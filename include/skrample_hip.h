@@ -899,7 +899,14 @@ int skr_noise_pyramid_nd(void* out, int32_t out_dtype, float* scratch_f32, float
  * d3 a multiple of 4 (every such side up to 126 / 252, then 96 * 2^k, 160 * 2^k ...: 90, 96, 104, 112, 144, 152, 160, 168, 192 ...) as long as one plane fits a CU's LDS (up to 192 x 192).  Other shapes:
  * SKR_ERR_UNSUPPORTED -- use skr_noise_colored_any.
  * Workspaces (caller-provided): spec_c64 = batch*d1*d2*(d3/2+1) complex64, scratch_f32 = batch*d1*d2*d3,
- * partials_f64 = 4*batch*partial_slots doubles with partial_slots >= ceil(d1*d2 / max(1, 4096/d3)). */
+ * partials_f64 = 4*batch*partial_slots doubles with partial_slots >= max(d1, ceil(d1*d2 / max(1, 4096/d3))): the plane routes keep one
+ * white-noise slot per plane of the outer axis (d1 of them; a Mixed unit given fewer is SKR_ERR_UNSUPPORTED, a power-of-two one
+ * SKR_ERR_SHAPE), the route of separate passes one per workgroup of its last-axis pass (at most the second term).  The coloured
+ * statistics and the bookkeeping of the 128 x 128 inverse share the same 4*batch*partial_slots doubles; nothing is written behind them.
+ * That minimum guarantees that the draw is accepted, not its fastest route: a 2- or 4-channel unit over planes too large for the LDS takes
+ * the fused mid-axes kernel only when its tiles of the half spectrum, ceil((d3/2+1) / 4) at most, fit the slots the white noise leaves
+ * free, 2*partial_slots minus the workgroups of the last-axis pass (2 channels over 256 x 256: 33 <= 2*partial_slots - 16, i.e. 25 slots);
+ * with fewer the separate passes run, with the same values to rounding.  The Python side passes max(256, ...) slots. */
 int skr_noise_colored(void* out, int32_t out_dtype, void* spec_c64, float* scratch_f32, double* partials_f64,
                       int64_t partial_slots, const uint64_t* seeds_dev, uint64_t stream_id, int64_t batch,
                       int32_t d1, int32_t d2, int32_t d3, double exponent, int32_t has_energy, double energy,

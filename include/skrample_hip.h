@@ -938,7 +938,9 @@ int skr_philox_u32(uint32_t* out /* [n_blocks*4] device */, uint64_t seed, uint6
 
 /* Colored.colorize_noise (noise.py:337-403) on a caller's white noise: white_f32 ([batch * prod(dims)] fp32, used as
  * the transform workspace and overwritten) is shaped exactly as skr_noise_colored_any shapes its own draws; same
- * workspaces, any dims (hipFFT).  exponent = 0 is the caller's fast path (plain rescale), not handled here. */
+ * workspaces and the same dims: the own any-length transforms, never the plane kernels; hipFFT only when asked for, a shape outside
+ * the own transforms' lengths is SKR_ERR_UNSUPPORTED otherwise, refused before anything is written (white_f32 keeps the caller's
+ * values).  exponent = 0 is the caller's fast path (plain rescale), not handled here. */
 int skr_colorize(void* out, int32_t out_dtype, void* spec_c64, float* white_f32, double* partials_f64, int64_t batch,
                  int32_t rank, const int32_t* dims, double exponent, int32_t has_energy, double energy, void* stream);
 

@@ -14,6 +14,7 @@ import torch
 
 from skr_oracle import noise as ON
 from conftest import note_margin
+from fft_lengths import _own_length, _short_length  # noqa: F401  (the documented length rule, shared with the length sweep)
 from skrample_amd import _hip
 from skrample_amd.common import Step
 from skrample_amd.pytorch import noise as PN
@@ -837,25 +838,6 @@ def test_colored_with_two_axes_on_the_transform_and_the_rest_direct(unit, hipfft
         assert lib.skr_set_tuning(b"fft_rank", 0) == 0 and lib.skr_set_tuning(b"hipfft", -1) == 0
 
 
-def _short_length(d: int) -> bool:
-    "an axis length the tile transforms of skr_fft_own.hip take: anything up to 2048 (Bluestein), and up to 4096 the direct ones -- 2^a (a >= 1) times at most three factors out of 3, 5, 7, 11, 13"
-    if d <= 2048:
-        return True
-    odd = 0
-    for f in (13, 11, 7, 5, 3):
-        while d % f == 0 and odd < 3:
-            d, odd = d // f, odd + 1
-    return d <= 4096 and d & (d - 1) == 0 and (odd == 0 or d >= 2)
-
-
-def _own_length(d: int, last: bool = False) -> bool:
-    "... or, as the LAST axis, an even length 2 A B with A, B such lengths (the half-length transform in four steps)"
-    if _short_length(d):
-        return True
-    h = d // 2
-    return last and d % 2 == 0 and any(h % a == 0 and _short_length(a) and _short_length(h // a) for a in range(2, int(h**0.5) + 1))
-
-
 @pytest.mark.parametrize("unit", [(4, 97, 97), (4, 30, 90), (3, 250, 250), (2, 66, 130), (1, 45, 96), (2, 134, 64), (3, 7, 11, 13), (2, 1025), (1, 3, 2050), (4, 720, 1280), (2, 3, 5), (5, 1300),
                                   (2, 250, 60), (3, 3072), (3, 2560), (2, 90, 18), (1, 720, 30), (2, 3000), (2, 1500), (1, 6, 10), (3, 1080), (3, 3840),
                                   (2, 154, 182), (3, 2002), (2, 28, 44), (1, 4004), (2, 14, 22, 26), (16, 66, 130)])
@@ -863,7 +845,9 @@ def test_awkward_shapes_run_on_the_own_transforms(unit, dev):
     """odd sides, widths that are not multiples of 4, odd parts beyond 63, primes, lengths next to a power of two, a 720 x 1280 plane, one-,
     two- and three-level 2^a 3^b 5^c lengths (30, 60, 90, 250, 720, 3072 ...) and ones with four odd factors (1080, 1500: Bluestein again): every
     axis length up to 2048, and the direct ones up to 4096, run on skr_fft_own.hip -- no hipFFT plan is made, no hipFFT transform
-    runs -- and meet the oracle bar; only a longer axis (2050, 3000) is still served by hipFFT"""
+    runs -- and meet the oracle bar; a longer LAST axis (2050, 3000: even, 2 A B) takes the four-step route there as well, any other
+    axis is refused unless hipFFT is asked for (test_the_vendor_fft_runs_only_when_asked_for).  tests/test_fft_lengths_gpu.py runs
+    every admissible length, one axis at a time."""
     lib = _hip.load()
     seeds = [61, 62]
     before = lib.skr_stat(b"own_fft_execs"), lib.skr_stat(b"hipfft_plans"), lib.skr_stat(b"hipfft_execs")

@@ -837,6 +837,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
 
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
         inpaint = getattr(self, "_inpaint", None)
+        if model_output is sample:  # one tensor in both roles: a view object per role (lazy.distinct), or the form would hold ONE operand
+            model_output, sample = lazy.distinct(model_output, sample)
         # a step autograd records takes the general path: the replayed steps and step programs bind raw pointers (no autograd node)
         recorded = lazy.grad_recorded(model_output, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
         if type(timestep) is float and self._fast_ids is not None and not recorded and inpaint is None:
@@ -861,6 +863,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     # (skr_step_launch_guided_rescaled), which is what history and pred_original_sample read.
     def step_guided(self, model_output_uncond: Tensor, model_output_cond: Tensor, guidance_scale: float, timestep, sample: Tensor, generator=None, return_dict: bool = True,
                     guidance_rescale: float = 0.0):
+        model_output_uncond, model_output_cond, sample = lazy.distinct(model_output_uncond, model_output_cond, sample)
         guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale, guidance_rescale)
         recorded = lazy.grad_recorded(model_output_uncond, model_output_cond, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
         return self._step_general(model_output_uncond, timestep, sample, generator, return_dict, recorded, guidance)
@@ -890,9 +893,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         keep = self.sampler.require_previous  # (a computed property: read once per step)
         aliasing = keep > 0 and self._alias_now(model_output, sample)
         if keep > 0 and not aliasing:
-            sample = sample.clone()
+            sample = lazy.snapshot(sample)
             if not guided_call:  # (a guided prediction is the engine's own tensor)
-                model_output = model_output.clone()
+                model_output = lazy.snapshot(model_output)
         elif aliasing:
             self._alias_check(model_output, sample)
 
@@ -905,7 +908,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             # reference hands it the negated TENSOR (diffusers.py:563-564) -- an exact op, one launch
             from .sampling import native
 
-            if native._eligible(sample, model_output) and model_output.is_contiguous():
+            if native._eligible(sample, model_output):  # (a view is copied by the tape: Tape.leaf)
                 prediction = native._express(model_output, lambda o: -o, model_output)
         noise = None
         if self.sampler.require_noise:
@@ -1194,10 +1197,15 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
 
 
 def _memory_format(t):
-    "what a history record's signature says of a tensor's storage: None contiguous, (channels, plane) dense channels-last, else \"strided\""
-    if not isinstance(t, Tensor) or t.is_contiguous():
+    """what a history record's signature says of a tensor's storage: None contiguous, (channels, plane) dense channels-last, else "strided";
+    "unaligned" for either dense form at an address that is no multiple of 16 -- a replayed step binds the addresses of its history blind,
+    and the launch refuses such a pointer (the general path copies the operand instead)"""
+    if not isinstance(t, Tensor):
         return None
-    return lazy.layout_of(t) or "strided"
+    if t.is_contiguous():
+        return "unaligned" if t.data_ptr() & 15 else None
+    layout = lazy.layout_of(t)
+    return "strided" if layout is None else "unaligned" if t.data_ptr() & 15 else layout
 
 
 class _FastEntry:
@@ -1368,6 +1376,8 @@ class RKWrapperCore(SkrampleWrapperCore):
         return lazy.settle(form, dtype=self.compute_scale)
 
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
+        if model_output is sample:  # (see SkrampleWrapperScheduler.step)
+            model_output, sample = lazy.distinct(model_output, sample)
         value = _host_number(timestep)
         expected = self.all_points[self._index].timestep
         if value is None:  # device timestep: checked through its position in the `timesteps` tensor we handed out (no sync)
@@ -1381,7 +1391,7 @@ class RKWrapperCore(SkrampleWrapperCore):
             assert value == expected, f"Expected timestep {expected} for step {self._index}, got {timestep=}!"
         aliasing = self.order > 1 and self._alias_now(model_output, sample)
         if self.order > 1 and not aliasing:
-            sample, model_output = sample.clone(), model_output.clone()
+            sample, model_output = lazy.snapshot(sample), lazy.snapshot(model_output)
         elif aliasing:
             self._alias_check(model_output, sample)
             try:

@@ -215,11 +215,16 @@ def is_host(device) -> bool:
 
 
 def _from_numpy(x) -> torch.Tensor:
-    hit = _numpy_views.get(id(x))
-    if hit is not None and hit[0] is x:
-        return hit[1]
     import numpy as np
 
+    hit = _numpy_views.get(id(x))
+    if hit is not None and hit[0] is x:
+        # a C-contiguous array is SHARED with its tensor.  A strided one (a slice, a reversed or transposed view) was copied, and the caller
+        # may have refilled it since: its copy stands only while it still holds the array's numbers.  (It cannot simply go unremembered:
+        # a step lifts one array several times, and the same tensor must come back each time for the form to hold ONE operand)
+        held = hit[1].numpy()
+        if np.may_share_memory(held, x) or np.array_equal(held.reshape(-1).view(np.uint8), np.ascontiguousarray(x).reshape(-1).view(np.uint8)):
+            return hit[1]
     t = torch.from_numpy(np.ascontiguousarray(x))
     if t.dtype not in _hip.DTYPE_CODE:
         raise SkrampleHipError(f"unsupported array dtype {x.dtype}; float16/32/64 arrays are handled")
@@ -488,6 +493,26 @@ def shared_layout(tensors, shape) -> "tuple[int, int] | None":
                 return None
             first = strides
     return layout
+
+
+def snapshot(t: torch.Tensor) -> torch.Tensor:
+    """the engine's own copy of a caller's tensor: in the caller's layout when that is contiguous or dense channels-last (a launch takes
+    it as it is), contiguous for every other view -- `clone()` alone would hand the strides of a permuted operand on to the copy, and to
+    whatever is returned of it"""
+    return t.clone() if t.is_contiguous() or layout_of(t) is not None else t.clone(memory_format=torch.contiguous_format)
+
+
+def distinct(*operands) -> tuple:
+    """the operands of one call, with a tensor that the caller passed in more than one role (`model_output is sample`, `uncond is cond`)
+    seen through a view object of its own per role -- no copy.  Forms merge their leaves by identity, so one object in two roles would
+    collapse into one operand with the summed coefficient, whose rounding is not that of the same numbers in two tensors."""
+    seen, out = set(), []
+    for t in operands:
+        if isinstance(t, torch.Tensor) and id(t) in seen:
+            t = t[...]
+        seen.add(id(t))
+        out.append(t)
+    return tuple(out)
 
 
 def _prepare_keeping_layout(t: torch.Tensor) -> torch.Tensor:
@@ -791,7 +816,7 @@ def guide_only(guidance: Guidance) -> torch.Tensor:
     under the same conditions, and torch's lines with rescale_noise_cfg's four otherwise."""
     u, c = guidance.uncond, guidance.cond
     if is_host(guidance.device) or grad_recorded(u, c):
-        return guidance.torch_lines()
+        return _host_result(guidance.torch_lines(), (u, c), guidance.shape)
     in_place = in_place_layout((u, c), guidance.shape) is not None
     prepare = _prepare_keeping_layout if in_place else _prepare_tensor
     u, c = prepare(u), prepare(c)
@@ -903,7 +928,7 @@ def _host_evaluate_masked(f0: "Lin", f1: "Lin", mask: torch.Tensor, out_dtype: t
         return acc
 
     m = mask.to(wide).reshape((1,) * (len(f0.shape) - mask.ndim) + tuple(mask.shape))
-    return (m * total(f0) + (1 - m) * total(f1)).to(out_dtype)
+    return _host_result((m * total(f0) + (1 - m) * total(f1)).to(out_dtype), leaves, f0.shape)
 
 
 # ---- autograd ------------------------------------------------------------------------------------------------------------------------
@@ -1100,7 +1125,16 @@ def _host_evaluate(conv, f0: "Lin", f1, out_dtypes, acc_f64) -> list:
         chain = sum(c for leaf, c in f1.terms.values() if isinstance(leaf, Node))
         acc1 = total(f1, acc0 * chain if chain != 0.0 else None)
         outs.append(acc1.to(out_dtypes[1]))
+    outs = [_host_result(o, leaves, f0.shape) for o in outs]
     return [o.numpy() for o in outs] if as_numpy else outs
+
+
+def _host_result(out: torch.Tensor, leaves, shape) -> torch.Tensor:
+    """a host result in the layout a device launch returns: dense channels-last when every tensor operand shares that layout, contiguous
+    otherwise (torch's own ops hand the strides of a permuted or sliced operand on to their result)"""
+    if leaves and shared_layout(leaves, shape) is not None:
+        return out if layout_of(out) is not None else empty_output(shape, out.dtype, out.device, channels_last=True).copy_(out)
+    return out.contiguous()
 
 
 def cast(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -1151,7 +1185,7 @@ def power_blend(a: torch.Tensor, b: torch.Tensor, wa: float, wb: float, power: f
         raise SkrampleHipError("the signed-power blend is evaluated in float32 or float64")
     if not a.is_cuda and not b.is_cuda:  # host-resident operands
         spow = lambda v, f: v.abs().pow(f) * torch.where(v < 0, -1.0, 1.0).to(v.dtype)  # noqa: E731  (sign(+-0) = +1, as the kernel and the reference)
-        blended = spow(wa * spow(a.to(dtype), power) + wb * spow(b.to(dtype), power), 1 / power)
+        blended = spow(wa * spow(a.to(dtype), power) + wb * spow(b.to(dtype), power), 1 / power).contiguous()  # (the device launch copies views: contiguous, as there)
         return blended.numpy() if as_numpy else blended
     a, b = _prepare_tensor(a), _prepare_tensor(b)
     if grad_recorded(a, b):

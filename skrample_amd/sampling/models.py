@@ -22,6 +22,7 @@ from functools import wraps
 from typing import Callable
 
 from ..common import DeltaPoint, Point
+from .lazy import distinct as lazy_distinct
 from .lazy import lift, settle
 
 
@@ -82,6 +83,7 @@ class DiffusionModel(abc.ABC):
     # ---- value-level API (numbers, lazy forms or HIP tensors) ------------------------------------------
     def to_x(self, sample, output, point: Point):
         "output -> x_hat"
+        sample, output = lazy_distinct(sample, output)
         done = _native().try_expr(lambda s_, o_: _native()._to_x(self, s_, o_, point), sample, output)  # 16-bit tensors: the reference's rounded ops
         if done is not None:
             return done
@@ -92,6 +94,7 @@ class DiffusionModel(abc.ABC):
 
     def from_x(self, sample, x, point: Point):
         "x_hat -> output"
+        sample, x = lazy_distinct(sample, x)
         done = _native().try_expr(lambda s_, x_: _native()._from_x(self, s_, x_, point), sample, x)
         if done is not None:
             return done

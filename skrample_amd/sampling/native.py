@@ -43,6 +43,17 @@ class _Refused(Exception):
     "this step is outside what the tape covers: the caller takes the fused path"
 
 
+def _flat_aligned(t: torch.Tensor) -> torch.Tensor:
+    """what a tape reads: contiguous storage, 16-byte aligned on the device.  A view (a slice, a permutation, channels-last storage, a
+    `chunk` half at an odd address) is copied -- the step keeps the tape's bits, the result is contiguous -- and the caller's tensor is
+    never written"""
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.is_cuda and t.data_ptr() % 16:
+        t = t.clone()
+    return t
+
+
 class Tape:
     "operations of one step over `Val` handles; leaves are device tensors"
 
@@ -51,6 +62,7 @@ class Tape:
         self.ops: list[tuple[int, int, int, float]] = []  # (code, a, b, k); the value an op defines is its position
         self.leaves: list[torch.Tensor] = []
         self._leaf_of: dict[int, Val] = {}
+        self._given: list = []  # the tensors the leaves were made of: `_leaf_of` is keyed by their ids, which must not be recycled while the tape lives
 
     def leaf(self, t) -> "Val":
         if isinstance(t, Val):
@@ -59,13 +71,14 @@ class Tape:
             t = t.realize(self.dtype)
         if isinstance(t, lazy.LazyTensor):
             t = t.materialize()
-        if not isinstance(t, torch.Tensor) or (self.require_device and not t.is_cuda) or t.dtype != self.dtype or tuple(t.shape) != self.shape or t.device != self.device or not t.is_contiguous():
+        if not isinstance(t, torch.Tensor) or (self.require_device and not t.is_cuda) or t.dtype != self.dtype or tuple(t.shape) != self.shape or t.device != self.device:
             raise _Refused
         hit = self._leaf_of.get(id(t))
         if hit is None:
             if len(self.leaves) >= _hip.TAPE_MAX_INPUTS:
                 raise _Refused
-            self.leaves.append(t)
+            self._given.append(t)
+            self.leaves.append(_flat_aligned(t))
             hit = self._leaf_of[id(t)] = self._emit(_hip.TAPE_LOAD, len(self.leaves) - 1, 0, 0.0)
         return hit
 
@@ -411,6 +424,7 @@ def _compile(tape: Tape, results: list):
 
 
 def _launch(c, leaves: list[torch.Tensor], n_outputs: int, plain: bool = False) -> list[torch.Tensor]:
+    leaves = [_flat_aligned(t) for t in leaves]  # (a remembered step binds today's arguments: contiguous by then, not necessarily aligned)
     first = leaves[0]
     make = torch.empty if plain else lazy.empty_output
     outs = [make(first.shape, dtype=first.dtype, device=first.device) for _ in range(n_outputs)]
@@ -736,7 +750,7 @@ def try_expr(fn, *tensors):
     if not tensors or not all(isinstance(t, torch.Tensor) for t in tensors) or not _eligible(tensors[0], tensors[-1]):
         return None
     first = tensors[0]
-    if any(t.dtype != first.dtype or t.shape != first.shape or t.device != first.device or not t.is_contiguous() for t in tensors):
+    if any(t.dtype != first.dtype or t.shape != first.shape or t.device != first.device for t in tensors):
         return None
     try:
         return _express(first, fn, *tensors)
@@ -753,12 +767,12 @@ def _express(like: torch.Tensor, fn, *tensors):
 
 
 def _tensor_expression(like: torch.Tensor):
-    """`run(fn, *operands)`: the expression as ONE recorded launch while every operand is a contiguous tensor of `like`'s dtype / shape / device and the
-    tape takes it; otherwise -- and from then on -- through the operands' own operators, which is the reference's arithmetic op by op"""
+    """`run(fn, *operands)`: the expression as ONE recorded launch while every operand is a tensor of `like`'s dtype / shape / device and the
+    tape takes it (a view is copied by `Tape.leaf`); otherwise -- and from then on -- through the operands' own operators, which is the reference's arithmetic op by op"""
     plain = [False]
 
     def run(fn, *operands):
-        if not plain[0] and all(isinstance(t, torch.Tensor) and t.dtype == like.dtype and t.shape == like.shape and t.device == like.device and t.is_contiguous() for t in operands):
+        if not plain[0] and all(isinstance(t, torch.Tensor) and t.dtype == like.dtype and t.shape == like.shape and t.device == like.device for t in operands):
             try:
                 return _express(like, fn, *operands)
             except _Refused:
@@ -774,7 +788,7 @@ def rk_step(wrapper, model_output: torch.Tensor, sample: torch.Tensor, generator
     conversion, `forward(sample, sumprod(derivatives, row) / fsum(row))` per stage, `backward` for the stages on the clean end -- each as one
     recorded expression (one launch).  Returns (stage input or step result, pred_original_sample), or None when the call is outside this
     mode (the caller then takes the fused path); state (`_derivatives`, `_sample`, `_index`) advances exactly as in the reference."""
-    if wrapper.compute_scale is not None or not _eligible(sample, model_output) or not (sample.is_contiguous() and model_output.is_contiguous()):
+    if wrapper.compute_scale is not None or not _eligible(sample, model_output):
         return None
     held = list(wrapper._derivatives)
     if any(not isinstance(d, torch.Tensor) or d.dtype != sample.dtype for d in held) or (wrapper._sample is not None and not isinstance(wrapper._sample, torch.Tensor)):
@@ -837,7 +851,7 @@ def step_tableau(tableau, sample, model, model_transform, schedule, step, deriva
     """`functional.step_tableau` (reference functional.py:55-108) for a tensor sample of one 16-bit dtype outside a compute scale: every stage input,
     clean-end derivative and weighted result is one recorded expression in the reference's own order (one launch each); a network output that is not a
     tensor of that dtype sends the rest of the step through plain tensor operators -- the reference's own arithmetic, op by op.  None: not this mode."""
-    if not isinstance(sample, torch.Tensor) or not _eligible(sample, sample) or not sample.is_contiguous():
+    if not isinstance(sample, torch.Tensor) or not _eligible(sample, sample):
         return None
     if noise is not None and not (isinstance(noise, torch.Tensor) and noise.dtype == sample.dtype and noise.shape == sample.shape and noise.device == sample.device):
         return None

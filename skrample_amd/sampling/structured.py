@@ -64,6 +64,17 @@ class SKSamples(SampleInput):
     "the step result"
 
 
+def _distinct_roles(packed: SampleInput) -> SampleInput:
+    """the inputs of a fused step with one tensor passed in two roles (`prediction is sample`, the sample given as the noise) seen through
+    a view object per role (lazy.distinct): the form then holds two operands, as it does for two tensors of the same numbers, and
+    rounds as they round.  (The op tape needs none of this: it rounds op by op, whichever leaf an op reads.)"""
+    s, p, n = packed.sample, packed.prediction, packed.noise
+    if p is s or (n is not None and (n is s or n is p)):
+        s, p, n = lazy.distinct(s, p, n)
+        return replace(packed, sample=s, prediction=p, noise=n)
+    return packed
+
+
 def _result_dtype(value) -> torch.dtype | None:
     if isinstance(value, torch.Tensor):
         return value.dtype
@@ -115,6 +126,7 @@ class StatedSampler(StructuredSampler):
         record = native.try_stated(self, packed, model_transform, schedule, previous)
         if record is not None:
             return record
+        packed = _distinct_roles(packed)
         form = self._form(packed, model_transform, schedule, previous)
         blend = lazy.pending_blend()  # in-painting: the step's one launch is the masked launch (lazy.evaluate_masked)
         guided = lazy.pending_guidance()  # classifier-free guidance: the step's one launch is the guided launch (lazy.evaluate_guided)
@@ -350,6 +362,7 @@ class UniPC(UniP):
         record = native.try_unipc(self, packed, model_transform, schedule, previous)  # (see StatedSampler.sample_packed)
         if record is not None:
             return record
+        packed = _distinct_roles(packed)
         result_dtype = _result_dtype(packed.sample)
         if self.derivative_transform:
             conv = models.ModelConvert(model_transform, self.derivative_transform)
@@ -424,6 +437,7 @@ class SPC(traits.DerivativeTransform, StructuredSampler):
     def sample_packed(self, packed, model_transform, schedule, previous=()):
         if abs(self.power - 1) <= 1e-8 and native._eligible(packed.sample, packed.prediction):
             return self._sample_packed_composed(packed, model_transform, schedule, previous)
+        packed = _distinct_roles(packed)
         result_dtype = _result_dtype(packed.sample)
         point_from = _ipoint(schedule, packed.step[0])
         if self.derivative_transform:

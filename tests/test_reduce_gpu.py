@@ -91,6 +91,17 @@ def test_error_mean_edge_values(dtype, dev):
     # non-contiguous operands
     m, k = a.reshape(12, 25).to(dev), b.reshape(12, 25).to(dev)
     assert lazy.error_mean(m.t(), k.t(), 2) == lazy.error_mean(m.t().contiguous(), k.t().contiguous(), 2) == lazy.error_mean(m, k, 2)
+    # operand views (tests/view_cases.py): storage in another axis order, a strided slice and an odd address, each inside a padded base that
+    # stays untouched -- the contiguous clones' mean, bit for bit (the kernel reads the normalised copy in logical order)
+    import view_cases as VC
+
+    for kind in ("permuted_other", "sliced", "offset_small"):
+        for power in (1, 2):
+            va, vb = (VC.KINDS[kind](t.reshape(2, 3, 5, 10).to(dev)) for t in (a, b))
+            watch = VC.Watch(va, vb)
+            assert lazy.error_mean(va, vb, power) == lazy.error_mean(VC.twin(va), VC.twin(vb), power), (kind, power)
+            assert lazy.error_mean(0, vb, power) == lazy.error_mean(0, VC.twin(vb), power), (kind, power)
+            watch.assert_untouched(f"error_mean {kind}")
 
 
 def test_error_mean_refusals(dev):

@@ -1,5 +1,4 @@
-// What the statistic of rescaled guidance (skr_guidance_stats.hip), its rolling form (skr_guidance_stats_rolling.hip) and its row forms
-// (skr_guidance_stats_rows.hip) share: the summation
+// What the statistic of rescaled guidance (skr_guidance_stats.hip) and its row and rolling forms (skr_guidance_stats_rows.hip) share: the summation
 // order documented in include/skrample_hip.h (skr_guidance_rescale_factor) -- a lane's eight elements in index order, the shuffle tree
 // o = 32 .. 1, the four waves as ((w0 + w1) + w2) + w3 -- and the last operations behind the sums.  One body, so that a sample has the
 // same bits through either entry.

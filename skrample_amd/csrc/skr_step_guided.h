@@ -1,12 +1,9 @@
-// What the guided step (skr_step_guided.hip), its row forms (skr_step_guided_rows.hip), the rescaled step (skr_step_guided_rescaled.hip) and
-// its statistic (skr_guidance_stats.hip) share: the guided value, one rounded operation at a time, torch's fp16 tail rule, and the entry
-// checks of a guided launch.
+// What the guided step in all its forms (skr_step_guided.hip) and the statistic of rescaled guidance (skr_guidance_stats.hip,
+// skr_guidance_stats_rows.hip) share: the guided value and its rescaled twin, one rounded operation at a time, and torch's fp16 tail rule.
 #pragma once
 #include "skr_step_common.h"
 
 namespace skr {
-
-constexpr int guided_kmax(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : 16)); }
 
 // an individually rounded add: the twin of sub_ / mul_ (skr_step_common.h), contraction off so that no neighbour fuses with it
 __device__ __forceinline__ float add_(float a, float b) {
@@ -34,8 +31,7 @@ __device__ __forceinline__ float guided_value(float u, float c, float g) {
   return rnd<T>(p);
 }
 
-// diffusers' rescale_noise_cfg of the guided value p with the sample's factor r (skr_step_guided_rescaled.hip and its rolling form): the
-// four torch ops behind the guided value, one rounded operation at a time, each fp32 result pinned in a register of its own (neither
+// diffusers' rescale_noise_cfg of the guided value p with the sample's factor r: the four torch ops behind the guided value, one rounded operation at a time, each fp32 result pinned in a register of its own (neither
 // fused nor paired into packed instructions: see guided_value)
 template <typename T>
 __device__ __forceinline__ float rescaled_value(float p, float r, float phi, float psi) {
@@ -76,32 +72,30 @@ __device__ __forceinline__ float guided_value_f16_tail(float u, float c, float g
   asm("" : "+v"(p));
   return rnd<f16_t>(p);
 }
+// The rescaled value there: the two scalar products are rounded once (p * r is exact in fp32, a + b is a sum of two fp16 values: neither
+// is changed by its second rounding).  Measured against torch on the device: the fused multiply-and-convert of that block is a
+// multiply-ADD with +0 (v_fma_mixlo_f16 k, x, 0), so a product that is exactly zero comes out as +0 whatever its sign -- (-0) + (+0) = +0
+// -- while a product that only underflows in the rounding keeps its sign.  It shows where phi or psi is 0: psi * p = 0 * (negative p) is
+// +0 there and -0 in the whole blocks, and a + b = (-0) + that differs in the sign bit.
+__device__ __forceinline__ float mul_once_f16_add0(float k, float x) {
+  const float m = mul_once_f16(k, x);
+  return (k == 0.f || x == 0.f) && m == 0.f ? 0.f : m;  // (0 * inf is NaN and stays one)
+}
+__device__ __forceinline__ float rescaled_value_f16_tail(float p, float r, float phi, float psi) {
+  float resc = mul_(p, r);
+  asm("" : "+v"(resc));
+  resc = rnd<f16_t>(resc);
+  const float a = mul_once_f16_add0(phi, resc), b = mul_once_f16_add0(psi, p);
+  float q = add_(a, b);
+  asm("" : "+v"(q));
+  return rnd<f16_t>(q);
+}
 // the block of that torch kernel for 16-bit tensors on gfx950 (256 threads of 8 elements): elements from the last multiple of it on are
 // its tail.  The one-trip kernel's chunk has the same size, so a tensor of whole chunks has no tail.
 constexpr int64_t TORCH_TAIL = 2048;
 static_assert(TORCH_TAIL == (int64_t)BLOCK * VEC, "whole chunks must be whole blocks of torch's kernel: the one-trip kernel has no tail path");
 
 __device__ __forceinline__ double guide_d(double u, double c, double g) { return add_(u, mul_(g, sub_(c, u))); }
-
-// the rolling forms (skr_step_guided_rolling.hip, skr_step_guided_rescaled_rolling.hip): an operand other than the slot is present unless
-// its coef0 is exactly zero (either sign): decided on the row's double, in SGPRs
-__device__ __forceinline__ bool guided_row_has(const skr_step_row* row, int j) { return (__builtin_bit_cast(uint64_t, row->coef0[j]) << 1) != 0; }
-
-// What the entry checks of a guided launch leave behind for its launcher.
-struct GuidedLaunch {
-  bool step_out;   // the launch has a step output (out0_dtype is a dtype): false is the guidance-only form
-  bool noise;      // the launch may draw: the plan's zeta0 decides for the kernarg form, noise_mode alone for the row forms (the row's zeta0 is data)
-  bool one_trip;   // the one-trip vector kernel covers it (the row forms have no other)
-  int64_t chunks;  // 2048-element chunks of the launch, and
-  int bps_shift;   // chunks per sample as the kernels take them (sample_of; 0 for a launch that does not draw); both set when one_trip
-  int32_t dtype_b, dtype_g;  // the dtype of group b (group a's when that group is empty) and of the group `slot` lies in
-};
-
-// every check of a guided launch behind its NULL plan / guide tests, in skr_step_launch_guided's order and with its codes (skr_step_guided.hip);
-// `rows`: for a row form, whose plan scalars are ignored.  SKR_OK with numel == 0 means "nothing to do".
-// `rescale` (skr_step_launch_guided_rescaled alone): what it adds is checked where the like of it stands -- `reserved` beside the
-// guide's, the sample size behind that of a launch that draws, factor_dev beside the operands.
-int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
-                   bool rows, GuidedLaunch* launch, const skr_step_rescale* rescale = nullptr);
+__device__ __forceinline__ double rescaled_d(double p, double r, double phi, double psi) { return add_(mul_(phi, mul_(p, r)), mul_(psi, p)); }
 
 }  // namespace skr

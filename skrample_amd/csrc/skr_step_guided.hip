@@ -1,91 +1,52 @@
-// The guided solver step (include/skrample_hip.h, skr_step_launch_guided): classifier-free guidance fused into the step launch.
+// The guided solver step (include/skrample_hip.h, skr_step_launch_guided and its seven siblings): classifier-free guidance, and diffusers'
+// rescale_noise_cfg of it where asked for, fused into the step launch.
 //
-//   p   = rn_T( u + rn_T( g * rn_T(c - u) ) )       u = inputs[slot], c = cond: torch's three tensor ops, one rounded op at a time in
-//                                                   the op-math type of T (fp32; fp64 for fp64 tensors), g converted to it once
-//   out = sum_k c0[k]*v_k + zeta0*N(stream0)        v_slot = p, v_k = in_k otherwise: accumulated exactly as skr_step_launch does
-//   guided_out = p                                  (when asked for: the tensor the unfused loop hands to the step and keeps as history)
+//   p   = rn_T( u + rn_T( g * rn_T(c - u) ) )                u = inputs[slot], c = cond: torch's three tensor ops, one rounded op at a time in
+//                                                            the op-math type of T (fp32; fp64 for fp64 tensors), g converted to it once
+//   p'  = rn_T( rn_T(phi * rn_T(p * r)) + rn_T(psi * p) )    a rescaled launch: r = factor_dev[sample], what the statistics launch wrote
+//                                                            (skr_guidance_stats.hip, skr_guidance_stats_rows.hip); psi = 1 - phi, formed in
+//                                                            double and narrowed once.  p' = p in an unrescaled one
+//   out = sum_k c0[k]*v_k + zeta0*N(stream0)                 v_slot = p', v_k = in_k otherwise: accumulated exactly as skr_step_launch does
+//   guided_out = p'                                          (when asked for: the tensor the unfused loop hands to the step and keeps as history)
 //
-//   * one-trip kernel (guided_kernel_v1<T, K, NOISE>): whole 2048-element chunks, samples made of whole chunks when it draws, operands /
-//     cond / both outputs of one 16- or 32-bit dtype, fp32 arithmetic, <= 16 operands.  Lane ownership, XCD chunk map, loads, stores and
-//     Philox block numbering are those of masked_kernel_v1's kernarg form (skr_step_masked.hip): every operand load is issued first, the
-//     cond vector right behind them, the scalars and the Philox rounds while they are in flight.  `slot` is a kernarg scalar: each
-//     unrolled operand compares its own number with it (a uniform branch), so the register arrays are never indexed at run time.
-//     Whether p is stored is a uniform branch on the pointer, not a template flag: 3 dtypes x 16 operand counts x 2 (noise) = 96 instantiations.
-//   * general kernel (guided_kernel_gen): grid-stride, one element per lane and trip, any size, any dtype combination skr_step_launch
-//     takes, fp32 or fp64 arithmetic, and the guidance-only form (no step output).
-// Both evaluate the same operations in the same order on every element, so they agree bit for bit where both apply.
-// One exception follows torch's own device op: for fp16 the elements past the last whole 2048 of the tensor have  g * d  rounded once
-// (mul_once_f16, skr_step_guided.h).  Only the general kernel meets such elements.
-// The row forms of the one-trip kernel (skr_step_launch_guided_indexed[_per_sample]) are skr_step_guided_rows.hip, the rescaled step
-// (skr_step_launch_guided_rescaled) skr_step_guided_rescaled.hip; the guided value and the entry checks, which they share, are
-// skr_step_guided.h.
-#include "skr_step_guided.h"
-#include "skr_device.h"
+//   * one-trip kernel (guided_kernel_v1<T, K, NOISE, RowForm, RESCALE>): whole 2048-element chunks, samples made of whole chunks when it
+//     draws, rescales or has per-sample rows, operands / cond / both outputs of one 16- or 32-bit dtype, fp32 arithmetic, <= 16 operands.
+//     Lane ownership, XCD chunk map, loads, stores and Philox block numbering are those of masked_kernel_v1 (skr_step_masked.hip).  `slot`
+//     is a kernarg scalar: each unrolled operand compares its own number with it (a uniform branch), so the register arrays are never
+//     indexed at run time.  Whether p' is stored is a uniform branch on the pointer, not a template flag:
+//     3 dtypes x 16 operand counts x 2 (noise) x 4 forms x 2 (rescale) = 768 instantiations, the template in skr_step_guided_kernel.h, the
+//     RESCALE half compiled in skr_step_guided_rescaled.hip.
+//   * general kernel (guided_kernel_gen<Acc, RESCALE>), Kernarg form only: grid-stride, one element per lane and trip, any size, any dtype
+//     combination skr_step_launch takes, fp32 or fp64 arithmetic, ragged and small samples, and the guidance-only form (no step output).
+// Both evaluate the same operations in the same order on every element, so they agree bit for bit where both apply.  One exception follows
+// torch's own device op: for fp16 the elements past the last whole 2048 of the tensor have their tensor-times-number products (g * d,
+// phi * resc, psi * p) rounded once (mul_once_f16, skr_step_guided.h).  Only the general kernel meets such elements.
+//
+// Eight entries, one template.  RowForm (skr_step_common.h) says where a launch's scalars come from, as for the plain and the masked step:
+//   Kernarg     skr_step_launch_guided[_rescaled]                      coef0 / zeta0 / stream0 from the plan, g from guide->scale, phi from rescale->phi,
+//                                                                      narrowed on the host.  The rescale is unconditional.
+//   WholeBatch  skr_step_launch_guided[_rescaled]_indexed              from rows[index[0] + row_offset], read by the kernel behind its loads, so that a
+//   PerSample   skr_step_launch_guided[_rescaled]_indexed_per_sample   captured loop serves any schedule, any guidance scale (convert_k[0]) and any
+//                                                                      guidance_rescale (convert_k[1]); per sample: rows[index[sample] + row_offset]
+//   Rolling     skr_step_launch_guided[_rescaled]_rolling              per-sample rows for the slots of a rolling.RollingBatch, the row fetch IN FRONT
+//                                                                      of the loads (rolling_row), with the three rolling semantics:
+//       inactive sample   a negative index entry (tested before row_offset is added) ends the workgroup before its first vector-memory
+//                         instruction: no operand, cond, seed, factor or row is read, `out` and `guided_out` keep their bytes;
+//       absent operand    an operand other than `slot` whose coef0 is exactly zero (either sign) in the row is neither loaded nor summed
+//                         (history a request in its ramp-up does not have yet).  Its bytes may be NaN or inf, and its pointer is fetched from
+//                         the kernarg inside its branch.  inputs[slot] and cond are always loaded, and p' takes its one fma whatever
+//                         coef0[slot] is.  (The other forms give every operand its fma, zero coefficients included.)
+//       operand order     the present operands are summed in slot order, one fma each, p' in the slot's place, noise last: the bits of the
+//                         narrower Kernarg launch that holds exactly these operands.
+// A row launch is bit for bit the Kernarg launch with the row's values in its plan, guide and rescale.  A row is uniform over the workgroup
+// (the sample id goes through readfirstlane, the index entry and the row are scalar loads), so every decision taken from it is a scalar
+// branch with exec never masked: a NOISE instantiation skips the draw for a row whose zeta0 narrows to zero, and a RESCALE one rescales
+// only where the row's phi is not +-0 -- a real branch, not arithmetic (0 * inf would leak through), with the factor's load inside it:
+// an unrescaled row never touches the factor, which may hold NaN.  A rescaling launch keeps a workgroup inside one sample of the
+// statistic in every form.  The row forms have no grid-stride kernel: what the one-trip kernel does not cover is SKR_ERR_UNSUPPORTED.
+#include "skr_step_guided_kernel.h"
 
 namespace skr {
-
-// Kernarg of the one-trip kernel: what the first instructions need (operand pointers, chunk map) leads, as in MaskedArgs.
-template <int KMAX>
-struct GuidedArgs {
-  const void* in[KMAX];
-  const void* cond;
-  void* out;
-  void* guided;         // nullptr: p is not stored
-  int32_t xmap_lr;      // log2(run length) of the XCD chunk map
-  int32_t bps_shift;    // chunks per sample: log2 when >= 0, minus the count otherwise (see sample_of); read by a launch that draws only
-  const uint64_t* seeds;
-  uint64_t stream0;
-  float zeta0;
-  float scale;          // g in the op-math type
-  int32_t slot;         // the operand that p replaces in the sum
-  float c0[KMAX];
-};
-
-template <typename T, int K, bool NOISE>
-__global__ __launch_bounds__(BLOCK) void guided_kernel_v1(const GuidedArgs<guided_kmax(K)> a) {
-  constexpr bool TILE = sizeof(T) == 4;  // whole chunks are whole tiles: 32-bit tensors take the whole-line layout, as in launch_k1
-  const uint32_t c = chunk_of(blockIdx.x, a.xmap_lr);
-  const int64_t v = (int64_t)c * BLOCK + threadIdx.x;
-  Raw<T> raw[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) raw[j] = load_raw<T, TILE>(a.in[j], v);
-  Raw<T> rc = load_raw<T, TILE>(a.cond, v);
-  __builtin_amdgcn_sched_barrier(0);  // every load is out before the first scalar of the arithmetic is fetched
-  float c0[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) c0[j] = a.c0[j];
-  const float zeta0 = a.zeta0, g = a.scale;
-  const int32_t slot = a.slot;
-  float z[VEC];
-  if constexpr (NOISE) {
-    uint32_t smp, within;
-    sample_of(c, a.bps_shift, smp, within);
-    const uint32_t vs = within * BLOCK + threadIdx.x;  // lane-vector within the sample (sample_numel < 2^31)
-    const uint64_t seed = a.seeds[smp];
-    normal4(seed, a.stream0, (uint64_t)group0<TILE>((int64_t)vs), z);
-    normal4(seed, a.stream0, (uint64_t)group1<TILE>((int64_t)vs), z + 4);
-  }
-  float s[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) s[i] = 0.f;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    float w[VEC];
-    widen<T, float>(raw[j], w);
-    if (j == slot) {  // (uniform: a kernarg scalar against the unrolled operand's number) the guided value takes this operand's place
-      float cf[VEC];
-      widen<T, float>(rc, cf);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) w[i] = guided_value<T>(w[i], cf[i], g);
-      if (a.guided != nullptr) store8<T, float, TILE>(a.guided, v, w);  // (p is a value of T: the store's rounding is exact)
-    }
-    const float w0 = c0[j];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) s[i] = fma_(w0, w[i], s[i]);
-  }
-  if constexpr (NOISE) fma_noise8<float>(zeta0, z, s);
-  store8<T, float, TILE>(a.out, v, s);
-}
 
 // ---- general kernel: per-element accesses, run-time dtypes -----------------------------------------------------------------
 struct GuidedGenArgs {
@@ -93,37 +54,70 @@ struct GuidedGenArgs {
   double c0[SKR_ROW_TERMS];
   const void* cond;
   void* out;      // nullptr: the guidance-only form
-  void* guided;   // nullptr: p is not stored
+  void* guided;   // nullptr: p' is not stored
   const uint64_t* seeds;
   double zeta0, scale;
   uint64_t stream0;
   int64_t numel, sample_numel;
   int32_t n, n_a, dt_a, dt_b, dt_out, dt_g, slot, noise;
 };
+struct GuidedRescaledGenArgs {
+  const void* in[SKR_ROW_TERMS];
+  double c0[SKR_ROW_TERMS];
+  const void* cond;
+  void* out;
+  void* guided;
+  const uint64_t* seeds;
+  const void* factor;
+  double zeta0, scale, phi, psi;
+  uint64_t stream0;
+  int64_t numel, sample_numel, stat_numel;  // the draw's sample and the statistic's (equal when the launch draws)
+  int32_t n, n_a, dt_a, dt_b, dt_out, dt_g, slot, noise;
+};
 
-template <typename Acc>
-__global__ __launch_bounds__(BLOCK) void guided_kernel_gen(const GuidedGenArgs a) {
+// p' of one element in fp32 op-math; TAIL: an fp16 element of torch's partial last block
+template <typename T, bool RESCALE, bool TAIL = false>
+__device__ __forceinline__ float guided_gen_value(float u, float c, float g, float r, float phi, float psi) {
+  if constexpr (TAIL) {
+    const float p = guided_value_f16_tail(u, c, g);
+    if constexpr (RESCALE) return rescaled_value_f16_tail(p, r, phi, psi);
+    else return p;
+  } else {
+    const float p = guided_value<T>(u, c, g);
+    if constexpr (RESCALE) return rescaled_value<T>(p, r, phi, psi);
+    else return p;
+  }
+}
+
+template <typename Acc, bool RESCALE>
+__global__ __launch_bounds__(BLOCK) void guided_kernel_gen(const std::conditional_t<RESCALE, GuidedRescaledGenArgs, GuidedGenArgs> a) {
   constexpr bool F64 = std::is_same<Acc, double>::value;  // (an fp64 tensor takes part in fp64 arithmetic only)
-  const int64_t tail_from = a.numel - a.numel % TORCH_TAIL;  // fp16: torch rounds g * d once from here on (mul_once_f16)
+  const int64_t tail_from = a.numel - a.numel % TORCH_TAIL;  // fp16: torch rounds a tensor-times-number product once from here on (mul_once_f16)
   for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < a.numel; e += (int64_t)gridDim.x * BLOCK) {
-    // the guided value, in the op-math type of the slot's dtype whatever the accumulate type is; then widened exactly
+    [[maybe_unused]] int64_t stat_smp = 0;
+    if constexpr (RESCALE) stat_smp = e / a.stat_numel;
+    // p', in the op-math type of the slot's dtype whatever the accumulate type is; then widened exactly
     Acc p;
     bool wide_p = false;
     if constexpr (F64) wide_p = a.dt_g == SKR_F64;
     if (wide_p) {
       const double* up = reinterpret_cast<const double*>(a.in[a.slot]);
       const double* cp = reinterpret_cast<const double*>(a.cond);
-      p = (Acc)guide_d(up[e], cp[e], a.scale);
+      if constexpr (RESCALE) p = (Acc)rescaled_d(guide_d(up[e], cp[e], a.scale), reinterpret_cast<const double*>(a.factor)[stat_smp], a.phi, a.psi);
+      else p = (Acc)guide_d(up[e], cp[e], a.scale);
     } else {
       const float u = load_elem<float, false>(a.in[a.slot], e, a.dt_g), cv = load_elem<float, false>(a.cond, e, a.dt_g);
+      float r = 0.f, phi = 0.f, psi = 0.f;
+      if constexpr (RESCALE) r = load_elem<float, false>(a.factor, stat_smp, a.dt_g);
       const float g = (float)a.scale;
+      if constexpr (RESCALE) { phi = (float)a.phi; psi = (float)a.psi; }
       float pf;
-      if (a.dt_g == SKR_BF16) pf = guided_value<bf16_t>(u, cv, g);
-      else if (a.dt_g == SKR_F16) pf = e >= tail_from ? guided_value_f16_tail(u, cv, g) : guided_value<f16_t>(u, cv, g);
-      else pf = guided_value<float>(u, cv, g);
+      if (a.dt_g == SKR_BF16) pf = guided_gen_value<bf16_t, RESCALE>(u, cv, g, r, phi, psi);
+      else if (a.dt_g == SKR_F16) pf = e >= tail_from ? guided_gen_value<f16_t, RESCALE, true>(u, cv, g, r, phi, psi) : guided_gen_value<f16_t, RESCALE>(u, cv, g, r, phi, psi);
+      else pf = guided_gen_value<float, RESCALE>(u, cv, g, r, phi, psi);
       p = (Acc)pf;
     }
-    if (a.guided != nullptr) store_any<Acc>(a.guided, e, a.dt_g, p);  // (p is a value of that dtype: exact)
+    if (a.guided != nullptr) store_any<Acc>(a.guided, e, a.dt_g, p);  // (p' is a value of that dtype: exact)
     if (a.out == nullptr) continue;
     Acc s = 0;
     for (int j = 0; j < a.n; ++j) {
@@ -144,29 +138,34 @@ __global__ __launch_bounds__(BLOCK) void guided_kernel_gen(const GuidedGenArgs a
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-// the one-trip launch: dtype x noise x operand count to the instantiation, and its kernarg
-static void launch_guided_v1(const skr_step_plan& p, const void* const* inputs, void* out, const skr_step_guidance& gd, const uint64_t* seeds, bool noise,
-                             int64_t chunks, int bps_shift, hipStream_t s) {
-  with_step_type<false>(p.dtype_a, [&](auto tt) {
-    with_bools([&](auto nz) {
-      with_count<1, SKR_ROW_TERMS>(p.n_terms, [&](auto n) {
-        using T = typename decltype(tt)::type;
-        constexpr int N = decltype(n)::value, KMAX = guided_kmax(N);
-        GuidedArgs<KMAX> a;
-        for (int k = 0; k < KMAX; ++k) { a.in[k] = k < N ? inputs[k] : nullptr; a.c0[k] = k < N ? (float)p.coef0[k] : 0.f; }
-        a.cond = gd.cond; a.out = out; a.guided = gd.guided_out; a.seeds = seeds;
-        a.xmap_lr = xmap_lr_for(chunks); a.bps_shift = bps_shift;
-        a.stream0 = p.stream0; a.zeta0 = (float)p.zeta0; a.scale = (float)gd.scale; a.slot = gd.slot;
-        hipLaunchKernelGGL((guided_kernel_v1<T, N, decltype(nz)::value>), dim3((unsigned)chunks), dim3(BLOCK), 0, s, a);
-      });
-    }, noise);
-  });
+// the general launch (Kernarg form): accumulate type x rescale, and its kernarg
+static void launch_guided_gen(const skr_step_plan& p, const void* const* inputs, void* out, const skr_step_guidance& gd, const skr_step_rescale* rs,
+                              const uint64_t* seeds, const GuidedLaunch& l, int64_t numel, hipStream_t s) {
+  with_bools([&](auto f64, auto re) {
+    constexpr bool RESCALE = decltype(re)::value;
+    std::conditional_t<RESCALE, GuidedRescaledGenArgs, GuidedGenArgs> a;
+    for (int k = 0; k < SKR_ROW_TERMS; ++k) {
+      const bool live = k < p.n_terms;
+      a.in[k] = live ? inputs[k] : nullptr;
+      a.c0[k] = live ? p.coef0[k] : 0.0;
+    }
+    a.cond = gd.cond; a.out = l.step_out ? out : nullptr; a.guided = gd.guided_out; a.seeds = seeds;
+    a.zeta0 = p.zeta0; a.scale = gd.scale; a.stream0 = p.stream0;
+    a.numel = numel; a.sample_numel = l.noise ? p.sample_numel : numel;
+    if constexpr (RESCALE) { a.factor = rs->factor_dev; a.phi = rs->phi; a.psi = 1.0 - rs->phi; a.stat_numel = rs->sample_numel; }
+    a.n = p.n_terms; a.n_a = p.n_group_a; a.dt_a = p.dtype_a; a.dt_b = l.dtype_b; a.dt_out = p.out0_dtype; a.dt_g = l.dtype_g; a.slot = gd.slot;
+    a.noise = l.noise ? 1 : 0;
+    const dim3 grid((unsigned)grid_blocks(numel, BLOCK, 256 * 64));
+    hipLaunchKernelGGL((guided_kernel_gen<std::conditional_t<decltype(f64)::value, double, float>, RESCALE>), grid, dim3(BLOCK), 0, s, a);
+  }, p.acc_f64 != 0, rs != nullptr);
 }
 
-// Every check of a guided launch behind its NULL plan / guide tests: those of skr_step_launch in its order, with what the guidance adds
-// where the like of it stands there.  (Declared in skr_step_guided.h: the row entries ask it too.)
-int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
-                   bool rows, GuidedLaunch* launch, const skr_step_rescale* rescale) {
+// Every check of a guided launch behind its NULL tests: those of skr_step_launch in its order, with what the guidance adds where the like
+// of it stands there.  `rows`: for a row form, whose plan scalars are ignored.  SKR_OK with numel == 0 means "nothing to do".
+// `rescale` (nullptr: an unrescaled entry): what it adds is checked where the like of it stands -- `reserved` beside the guide's, the
+// sample size behind that of a launch that draws, factor_dev beside the operands.
+static int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const void* const* inputs, void* out, const uint64_t* seeds_dev, int64_t numel,
+                          bool rows, GuidedLaunch* launch, const skr_step_rescale* rescale) {
   launch->step_out = launch->noise = launch->one_trip = false;
   const bool step_out = p.out0_dtype != SKR_NONE;
   const bool noise = step_out && p.noise_mode == 1 && (rows || p.zeta0 != 0.0);
@@ -207,43 +206,82 @@ int guided_prepare(const skr_step_plan& p, const skr_step_guidance& gd, const vo
   return SKR_OK;
 }
 
-static int guided_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide, const uint64_t* seeds_dev,
-                              int64_t numel, void* stream) {
-  if (!plan || !guide) return SKR_ERR_NULL;
+// The eight entries (from the table test on: rows != nullptr exactly when has_table(form); `rescaled`: the entry has a rescale argument).
+static int guided_launch_impl(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide, bool rescaled,
+                              const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, RowForm form, const skr_step_row* rows,
+                              const int32_t* index, int32_t row_offset, void* stream) {
+  const bool table = has_table(form);
+  if (!plan || !guide || (rescaled && !rescale) || (table && (!rows || (per_sample_rows(form) && !index)))) return SKR_ERR_NULL;
   const skr_step_plan& p = *plan;
-  const skr_step_guidance& gd = *guide;
   GuidedLaunch l;
-  if (const int rc = guided_prepare(p, gd, inputs, out, seeds_dev, numel, false, &l)) return rc;
+  if (const int rc = guided_prepare(p, *guide, inputs, out, seeds_dev, numel, table, &l, rescale)) return rc;
   if (numel == 0) return SKR_OK;
-  const bool step_out = l.step_out, noise = l.noise;
-  const int32_t db = l.dtype_b, dt_g = l.dtype_g;
-
-  DeviceGuard device_guard(step_out ? out : gd.guided_out);
+  constexpr int64_t CHUNK = (int64_t)BLOCK * VEC;
+  if (table) {
+    if (!l.one_trip || row_offset < 0) return SKR_ERR_UNSUPPORTED;
+    if (per_sample_rows(form) || rescale) {  // a workgroup lies inside one sample, with or without noise, and a rescaled one inside the statistic's
+      if (p.sample_numel <= 0 || numel % p.sample_numel != 0 || (rescale && rescale->sample_numel != p.sample_numel)) return SKR_ERR_SHAPE;
+      if (p.sample_numel % CHUNK != 0 || p.sample_numel >= (1ll << 31)) return SKR_ERR_UNSUPPORTED;
+      l.bps_shift = bps_shift_of(p.sample_numel / CHUNK);
+    }
+  } else if (rescale && l.one_trip) {  // a workgroup inside one sample of the statistic, or the general kernel
+    l.one_trip = rescale->sample_numel % CHUNK == 0 && rescale->sample_numel < (1ll << 31);
+    if (l.one_trip) l.bps_shift = bps_shift_of(rescale->sample_numel / CHUNK);
+  }
+  DeviceGuard device_guard(l.step_out ? out : guide->guided_out);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (l.one_trip) {
-    launch_guided_v1(p, inputs, out, gd, seeds_dev, noise, l.chunks, l.bps_shift, s);
-    return finish_launch();
-  }
-
-  GuidedGenArgs a;
-  for (int k = 0; k < SKR_ROW_TERMS; ++k) {
-    const bool live = k < p.n_terms;
-    a.in[k] = live ? inputs[k] : nullptr;
-    a.c0[k] = live ? p.coef0[k] : 0.0;
-  }
-  a.cond = gd.cond; a.out = step_out ? out : nullptr; a.guided = gd.guided_out; a.seeds = seeds_dev;
-  a.zeta0 = p.zeta0; a.scale = gd.scale; a.stream0 = p.stream0;
-  a.numel = numel; a.sample_numel = noise ? p.sample_numel : numel;
-  a.n = p.n_terms; a.n_a = p.n_group_a; a.dt_a = p.dtype_a; a.dt_b = db; a.dt_out = p.out0_dtype; a.dt_g = dt_g; a.slot = gd.slot;
-  a.noise = noise ? 1 : 0;
-  const dim3 grid((unsigned)grid_blocks(numel, BLOCK, 256 * 64));
-  with_bools([&](auto f64) { hipLaunchKernelGGL((guided_kernel_gen<std::conditional_t<decltype(f64)::value, double, float>>), grid, dim3(BLOCK), 0, s, a); }, p.acc_f64 != 0);
+  if (l.one_trip && rescale) launch_guided_rescaled_v1(p, inputs, out, *guide, rescale, seeds_dev, l, form, RowRef{rows, index, row_offset}, s);
+  else if (l.one_trip) launch_guided_v1<false>(p, inputs, out, *guide, nullptr, seeds_dev, l, form, RowRef{rows, index, row_offset}, s);
+  else launch_guided_gen(p, inputs, out, *guide, rescale, seeds_dev, l, numel, s);
   return finish_launch();
 }
 
 }  // namespace skr
 
+using skr::RowForm;
+
 extern "C" int skr_step_launch_guided(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
                                       const uint64_t* seeds_dev, int64_t numel, void* stream) {
-  return skr::guided_launch_impl(plan, inputs, out, guide, seeds_dev, numel, stream);
+  return skr::guided_launch_impl(plan, inputs, out, guide, false, nullptr, seeds_dev, numel, RowForm::Kernarg, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int skr_step_launch_guided_indexed(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                              const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev, const int32_t* index_dev,
+                                              int32_t row_offset, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, false, nullptr, seeds_dev, numel, RowForm::WholeBatch, rows_dev, index_dev, row_offset, stream);
+}
+
+extern "C" int skr_step_launch_guided_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                                         const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                                         const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, false, nullptr, seeds_dev, numel, RowForm::PerSample, rows_dev, sample_index_dev, row_offset, stream);
+}
+
+extern "C" int skr_step_launch_guided_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                              const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                              const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, false, nullptr, seeds_dev, numel, RowForm::Rolling, rows_dev, sample_index_dev, row_offset, stream);
+}
+
+extern "C" int skr_step_launch_guided_rescaled(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                               const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, true, rescale, seeds_dev, numel, RowForm::Kernarg, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int skr_step_launch_guided_rescaled_indexed(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                                       const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                                       const int32_t* index_dev, int32_t row_offset, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, true, rescale, seeds_dev, numel, RowForm::WholeBatch, rows_dev, index_dev, row_offset, stream);
+}
+
+extern "C" int skr_step_launch_guided_rescaled_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                                                  const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel,
+                                                                  const skr_step_row* rows_dev, const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, true, rescale, seeds_dev, numel, RowForm::PerSample, rows_dev, sample_index_dev, row_offset, stream);
+}
+
+extern "C" int skr_step_launch_guided_rescaled_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                                       const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel,
+                                                       const skr_step_row* rows_dev, const int32_t* sample_index_dev, int32_t row_offset, void* stream) {
+  return skr::guided_launch_impl(plan, inputs, out, guide, true, rescale, seeds_dev, numel, RowForm::Rolling, rows_dev, sample_index_dev, row_offset, stream);
 }

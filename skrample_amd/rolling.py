@@ -19,7 +19,7 @@ share it, and a tick is still one launch (`skr_step_launch_masked_rolling`, csrc
     batch.admit(other, latents, wrapper, steps)      # a plain request: its slot of `batch.mask` is ones
 
 Classifier-free guidance: a batch built with `guided=True` takes the two halves of the network output and forms every request's guided
-prediction inside the tick's one launch (`skr_step_launch_guided_rolling`, csrc/skr_step_guided_rolling.hip), each request under its own
+prediction inside the tick's one launch (`skr_step_launch_guided_rolling`, csrc/skr_step_guided.hip), each request under its own
 scale -- or its own guidance schedule, one scale per step:
 
     batch = RollingBatch(make_wrapper, example, capacity=B, guided=True)
@@ -99,10 +99,10 @@ Rescaled guidance (`guided=True, rescaled=True`): diffusers' `rescale_noise_cfg`
     done = batch.step_guided(uncond, cond)
 
 phi travels in the row's `convert_k[1]` beside the scale in `convert_k[0]` (zero in every other batch's rows).  A tick is two launches on
-the current stream with the same index, rows and row offset: `skr_guidance_rescale_factor_rolling` (csrc/skr_guidance_stats_rolling.hip)
+the current stream with the same index, rows and row offset: `skr_guidance_rescale_factor_rolling` (csrc/skr_guidance_stats_rows.hip)
 writes std(cond) / std(prediction) of every active slot whose phi is not zero into the batch's `factor` tensor, `[capacity]` in the latents'
 dtype, through a partial-sum workspace -- both allocated once, when the batch is built, the same in every phase of `CapturedTicks` --; then
-`skr_step_launch_guided_rescaled_rolling` (csrc/skr_step_guided_rescaled_rolling.hip) steps every active slot, with the rescaled prediction
+`skr_step_launch_guided_rescaled_rolling` (csrc/skr_step_guided.hip) steps every active slot, with the rescaled prediction
 where phi is not zero and with the plain guided one -- its factor unread -- where it is.  Free slots, finished slots and requests that do
 not rescale cost no statistics traffic; the tick has the same two launches whether or not a resident request rescales.  Every request has
 the bits of its lone `step_guided(uncond, cond, g, t, x, guidance_rescale=phi)` run, and a request with phi = 0 throughout those of a

@@ -1,11 +1,11 @@
 """The rescaled guided step kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_guided_rescaled` runs `guided_rescaled_kernel_v1<T, K, NOISE>` (csrc/skr_step_guided_rescaled.hip) where whole chunks of
-one dtype and samples of whole chunks allow it.  It keeps the shape of `guided_kernel_v1`, and that is visible in the instruction stream:
+`skr_step_launch_guided_rescaled` runs `guided_kernel_v1<T, K, NOISE, RowForm::Kernarg, true>` (csrc/skr_step_guided_kernel.h, compiled in csrc/skr_step_guided_rescaled.hip) where whole chunks
+of one dtype and samples of whole chunks allow it.  It keeps the shape of its unrescaled twin (RESCALE false), and that is visible in the instruction stream:
 nothing goes to scratch, operands and cond are 16-byte global loads and both outputs 16-byte global stores, `slot` is a uniform
 comparison (no exec masking), and for an fp32 tensor the seven operations of  phi * (p * r) + psi * p  over  p = u + g * (c - u)  stay
 seven instructions per element -- four multiplies and three additions that a contraction would have fused are all there.  The register
-and occupancy table is printed beside that of the guided_kernel_v1 twins (run with -s) and recorded in profiles/guided_rescale_isa.txt;
+and occupancy table is printed beside that of the unrescaled twins (run with -s) and recorded in profiles/guided_rescale_isa.txt;
 the brackets asserted at the end are what that record shows.  Registers, memory-operation widths and arithmetic counts only."""
 
 import re
@@ -13,19 +13,19 @@ import re
 import pytest
 from isa_cases import HIPCC, compile_asm, kernels_of, waves_per_simd
 
-# guided_rescaled_kernel_v1<T, K, NOISE> and its twin guided_kernel_v1<T, K, NOISE>
-SYMBOL = re.compile(r"guided_rescaled_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")
-TWIN = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")
+# guided_kernel_v1<T, K, NOISE, RowForm::Kernarg, true> and its twin guided_kernel_v1<T, K, NOISE, RowForm::Kernarg, false>
+SYMBOL = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE0ELb1EE")
+TWIN = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE0ELb0EE")
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 VEC = 8  # elements per lane
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    "every guided_rescaled_kernel_v1 instantiation of the one translation unit, compiled once"
+    "every Kernarg, rescaled guided_kernel_v1 instantiation of their translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rescaled.hip", str(tmp_path_factory.mktemp("isa") / "rescaled")))
+    found = kernels_of(compile_asm("skr_step_guided_rescaled.hip", str(tmp_path_factory.mktemp("isa") / "guided_rescaled")))
     return {k: v for k, v in found.items() if SYMBOL.search(k)}
 
 
@@ -83,7 +83,7 @@ def test_register_and_occupancy_table(kernels, twins):
     twin.  Pinned from that record: one instantiation sits a waves-per-SIMD bracket below its twin -- bf16 with noise at 14 operands, 130
     against 128 VGPRs -- and no other, and the twin's brackets hold: 8 waves per SIMD up to 4 operands, at least 5 up to 8, never below 3."""
     names = {v: k for k, v in TYPES.items()}
-    print("\nguided_rescaled_kernel_v1<T, K, NOISE>: VGPRs (waves per SIMD) | guided_kernel_v1 twin")
+    print("\nguided_kernel_v1<T, K, NOISE, Kernarg, true>: VGPRs (waves per SIMD) | guided_kernel_v1<T, K, NOISE, Kernarg, false> twin")
     rows = {}
     for k, (_, vgprs, *_rest) in kernels.items():
         t, n, nz = SYMBOL.search(k).groups()

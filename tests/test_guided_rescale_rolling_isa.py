@@ -1,14 +1,14 @@
 """The rescaled guided rolling kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_guided_rescaled_rolling` runs `guided_rescaled_rolling_kernel_v1<T, K, NOISE>` (csrc/skr_step_guided_rescaled_rolling.hip):
-`guided_rolling_kernel_v1` with one more decision taken from the sample's row -- whether the sample rescales.  Its contract is visible in
+`skr_step_launch_guided_rescaled_rolling` runs `guided_kernel_v1<T, K, NOISE, RowForm::Rolling, true>` (csrc/skr_step_guided_kernel.h, compiled in csrc/skr_step_guided_rescaled.hip): its
+unrescaled twin with one more decision taken from the sample's row -- whether the sample rescales.  Its contract is visible in
 the instruction stream, as that of its twin is (tests/test_guided_rolling_isa.py): a workgroup of an inactive sample ends before its
 first vector-memory instruction; the row's decisions, the `phi` test among them, and the `slot` test of each unrolled operand are scalar
 branches with exec never masked; operands and cond are 16-byte global loads, both outputs 16-byte global stores; nothing spills.  The
-VGPR and occupancy table is printed beside `guided_rolling_kernel_v1<T, K, NOISE>` -- run with -s -- and recorded in
+VGPR and occupancy table is printed beside `guided_kernel_v1<T, K, NOISE, RowForm::Rolling, false>` -- run with -s -- and recorded in
 profiles/guided_rescale_rolling_isa.txt; the brackets asserted at the end are what that record shows.
 
-`skr_guidance_rescale_factor_rolling` runs two kernels (csrc/skr_guidance_stats_rolling.hip).  Both end an inactive or unrescaled
+`skr_guidance_rescale_factor_rolling` runs two kernels (the Rolling form of csrc/skr_guidance_stats_rows.hip).  Both end an inactive or unrescaled
 sample's workgroups before their first vector-memory instruction, neither spills, and every vector load of either is 16 bytes wide (the
 index, the row and the pivots are scalar loads)."""
 
@@ -20,28 +20,27 @@ from isa_cases import HIPCC, ROOT, compile_asm, kernels_of, waves_per_simd
 
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
-SYMBOL = re.compile(r"guided_rescaled_rolling_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")  # guided_rescaled_rolling_kernel_v1<T, K, NOISE>
-TWIN = re.compile(r"guided_rolling_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")  # guided_rolling_kernel_v1<T, K, NOISE>
-STATS = re.compile(r"rescale_stats_(spans|final)_rollingI(\w+?)EEv")
+SYMBOL = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE3ELb1EE")  # guided_kernel_v1<T, K, NOISE, RowForm::Rolling, true>
+TWIN = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE3ELb0EE")  # guided_kernel_v1<T, K, NOISE, RowForm::Rolling, false>
+STATS = re.compile(r"rescale_stats_(spans|final)_rowsI(\w+?)LNS_7RowFormE3EE")  # rescale_stats_{spans,final}_rows<T, RowForm::Rolling>
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 RECORD = os.path.join(ROOT, "profiles", "guided_rescale_rolling_isa.txt")
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    "every kernel of the step's translation unit, compiled once"
+    "every rescaled Rolling instantiation of guided_kernel_v1, selected from their translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rescaled_rolling.hip", str(tmp_path_factory.mktemp("isa") / "guided_rescaled_rolling")))
-    assert all(SYMBOL.search(k) for k in found), sorted(k for k in found if not SYMBOL.search(k))  # the file holds no other kernel
-    return found
+    found = kernels_of(compile_asm("skr_step_guided_rescaled.hip", str(tmp_path_factory.mktemp("isa") / "guided_rescaled")))
+    return {k: v for k, v in found.items() if SYMBOL.search(k)}  # (the census of the whole file: tests/test_guided_isa.py)
 
 
 @pytest.fixture(scope="module")
 def twins(tmp_path_factory):
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rolling.hip", str(tmp_path_factory.mktemp("isa") / "guided_rolling")))
+    found = kernels_of(compile_asm("skr_step_guided.hip", str(tmp_path_factory.mktemp("isa") / "guided")))
     return {TWIN.search(k).groups(): v for k, v in found.items() if TWIN.search(k)}
 
 
@@ -50,9 +49,8 @@ def stats(tmp_path_factory):
     "both stages of the rolling statistics launch, every dtype"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_guidance_stats_rolling.hip", str(tmp_path_factory.mktemp("isa") / "stats_rolling")))
-    assert all(STATS.search(k) for k in found), sorted(k for k in found if not STATS.search(k))
-    return found
+    found = kernels_of(compile_asm("skr_guidance_stats_rows.hip", str(tmp_path_factory.mktemp("isa") / "stats_rows")))
+    return {k: v for k, v in found.items() if STATS.search(k)}  # (the census of the whole file: tests/test_guided_isa.py)
 
 
 def count(lines, *prefixes):
@@ -118,10 +116,10 @@ def recorded_short() -> list:
 
 def test_register_and_occupancy_table_against_the_unrescaled_twins(kernels, twins):
     """printed for DESIGN.md section 4.7 and profiles/guided_rescale_rolling_isa.txt (run with -s).  At least 3 waves per SIMD everywhere,
-    at least 4 up to 8 operands, 8 up to 4 operands; the instantiations that sit a bracket below their guided_rolling_kernel_v1 twin are
+    at least 4 up to 8 operands, 8 up to 4 operands; the instantiations that sit a bracket below their unrescaled rolling twin are
     the ones the record lists by name."""
     names = {v: k for k, v in TYPES.items()}
-    print("\nVGPRs (waves per SIMD): guided_rescaled_rolling_kernel_v1<T, K, NOISE> vs guided_rolling_kernel_v1<T, K, NOISE>")
+    print("\nVGPRs (waves per SIMD): guided_kernel_v1<T, K, NOISE, Rolling, true> vs guided_kernel_v1<T, K, NOISE, Rolling, false>")
     short = []
     for key in sorted((SYMBOL.search(k).groups() for k in kernels), key=lambda g: (g[0], g[2], int(g[1]))):
         symbol = next(k for k in kernels if SYMBOL.search(k).groups() == key)
@@ -144,7 +142,7 @@ def test_register_and_occupancy_table_against_the_unrescaled_twins(kernels, twin
 
 def test_statistics_kernels_exit_early_spill_nothing_and_load_16_bytes(stats):
     have = {STATS.search(k).groups() for k in stats}
-    assert have == {(stage, t) for stage in ("spans", "final") for t in TYPES.values()}, sorted(have)
+    assert have == {(stage, t) for stage in ("spans", "final") for t in TYPES.values()} and len(stats) == 6, sorted(have)
     for k, (lines, _, scratch, private) in stats.items():
         assert exits_before_vector_memory(lines), k
         assert scratch == 0 and private == 0, (k, scratch, private)

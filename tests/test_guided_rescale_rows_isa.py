@@ -1,14 +1,14 @@
 """The rescaled guided row kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_guided_rescaled_indexed[_per_sample]` run `guided_rescaled_rows_kernel_v1<T, K, NOISE, RowForm>`
-(csrc/skr_step_guided_rescaled_rows.hip): `guided_rows_kernel_v1` with one more decision taken from the row -- whether it rescales.  What
+`skr_step_launch_guided_rescaled_indexed[_per_sample]` run `guided_kernel_v1<T, K, NOISE, RowForm, true>` (csrc/skr_step_guided_kernel.h, compiled in csrc/skr_step_guided_rescaled.hip) in its
+WholeBatch and PerSample forms: their unrescaled twins with one more decision taken from the row -- whether it rescales.  What
 the contract promises is visible in the instruction stream, as that of its twin is (tests/test_guided_rows_isa.py): `slot` stays a kernarg
 scalar compared per unrolled operand and the `phi` test is a scalar branch (nothing goes to scratch, exec is never masked); operands and
 cond are 16-byte global loads, both outputs 16-byte global stores; beside them there is at most the factor, one 16-bit element from a
-uniform address.  The VGPR and occupancy table is printed beside `guided_rows_kernel_v1<T, K, NOISE, RowForm>` -- run with -s -- and
+uniform address.  The VGPR and occupancy table is printed beside `guided_kernel_v1<T, K, NOISE, RowForm, false>` -- run with -s -- and
 recorded in profiles/guided_rescale_rows_isa.txt; the brackets asserted at the end are what that record shows.
 
-`skr_guidance_rescale_factor_indexed[_per_sample]` run two kernels (csrc/skr_guidance_stats_rows.hip).  Both end the workgroups of an
+`skr_guidance_rescale_factor_indexed[_per_sample]` run two kernels (the WholeBatch and PerSample forms of csrc/skr_guidance_stats_rows.hip).  Both end the workgroups of an
 unrescaled row before their first vector-memory instruction, neither spills, and every vector load of either is 16 bytes wide (the index,
 the row and the pivots are scalar loads)."""
 
@@ -20,9 +20,9 @@ from isa_cases import HIPCC, ROOT, compile_asm, kernels_of, waves_per_simd
 
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
-SYMBOL = re.compile(r"guided_rescaled_rows_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([12])EE")  # guided_rescaled_rows_kernel_v1<T, K, NOISE, RowForm>
-TWIN = re.compile(r"guided_rows_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([12])EE")  # guided_rows_kernel_v1<T, K, NOISE, RowForm>
-STATS = re.compile(r"rescale_stats_(spans|final)_rowsI(\w+?)Lb([01])EE")
+SYMBOL = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([12])ELb1EE")  # guided_kernel_v1<T, K, NOISE, WholeBatch / PerSample, true>
+TWIN = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([12])ELb0EE")  # guided_kernel_v1<T, K, NOISE, WholeBatch / PerSample, false>
+STATS = re.compile(r"rescale_stats_(spans|final)_rowsI(\w+?)LNS_7RowFormE([12])EE")  # rescale_stats_{spans,final}_rows<T, WholeBatch / PerSample>
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 FORMS = {"1": "whole-batch", "2": "per-sample"}  # RowForm::WholeBatch, RowForm::PerSample
 RECORD = os.path.join(ROOT, "profiles", "guided_rescale_rows_isa.txt")
@@ -30,19 +30,18 @@ RECORD = os.path.join(ROOT, "profiles", "guided_rescale_rows_isa.txt")
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    "every kernel of the step's translation unit, compiled once"
+    "every rescaled WholeBatch and PerSample instantiation of guided_kernel_v1, selected from their translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rescaled_rows.hip", str(tmp_path_factory.mktemp("isa") / "guided_rescaled_rows")))
-    assert all(SYMBOL.search(k) for k in found), sorted(k for k in found if not SYMBOL.search(k))  # the file holds no other kernel
-    return found
+    found = kernels_of(compile_asm("skr_step_guided_rescaled.hip", str(tmp_path_factory.mktemp("isa") / "guided_rescaled")))
+    return {k: v for k, v in found.items() if SYMBOL.search(k)}  # (the census of the whole file: tests/test_guided_isa.py)
 
 
 @pytest.fixture(scope="module")
 def twins(tmp_path_factory):
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rows.hip", str(tmp_path_factory.mktemp("isa") / "guided_rows")))
+    found = kernels_of(compile_asm("skr_step_guided.hip", str(tmp_path_factory.mktemp("isa") / "guided")))
     return {TWIN.search(k).groups(): v for k, v in found.items() if TWIN.search(k)}
 
 
@@ -52,8 +51,7 @@ def stats(tmp_path_factory):
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
     found = kernels_of(compile_asm("skr_guidance_stats_rows.hip", str(tmp_path_factory.mktemp("isa") / "stats_rows")))
-    assert all(STATS.search(k) for k in found), sorted(k for k in found if not STATS.search(k))
-    return found
+    return {k: v for k, v in found.items() if STATS.search(k)}  # (the census of the whole file: tests/test_guided_isa.py)
 
 
 def count(lines, *prefixes):
@@ -125,10 +123,10 @@ def recorded_short() -> list:
 def test_register_and_occupancy_table_against_the_unrescaled_twins(kernels, twins):
     """printed for DESIGN.md section 4.7 and profiles/guided_rescale_rows_isa.txt (run with -s).  At least 3 waves per SIMD everywhere, at
     least 4 up to 8 operands, 8 up to 4 operands -- the twin's own brackets (tests/test_guided_rows_isa.py) -- except 7 for the listed
-    fp32 noise forms at K = 4; the instantiations that sit a bracket below their guided_rows_kernel_v1 twin are the ones the record lists
+    fp32 noise forms at K = 4; the instantiations that sit a bracket below their unrescaled twin are the ones the record lists
     by name."""
     names = {v: k for k, v in TYPES.items()}
-    print("\nVGPRs (waves per SIMD): guided_rescaled_rows_kernel_v1<T, K, NOISE, RowForm> vs guided_rows_kernel_v1<T, K, NOISE, RowForm>")
+    print("\nVGPRs (waves per SIMD): guided_kernel_v1<T, K, NOISE, RowForm, true> vs guided_kernel_v1<T, K, NOISE, RowForm, false>")
     short = []
     for key in sorted((SYMBOL.search(k).groups() for k in kernels), key=lambda g: (g[0], g[3], g[2], int(g[1]))):
         symbol = next(k for k in kernels if SYMBOL.search(k).groups() == key)
@@ -151,7 +149,7 @@ def test_register_and_occupancy_table_against_the_unrescaled_twins(kernels, twin
 
 def test_statistics_kernels_exit_early_spill_nothing_and_load_16_bytes(stats):
     have = {STATS.search(k).groups() for k in stats}
-    assert have == {(stage, t, f) for stage in ("spans", "final") for t in TYPES.values() for f in "01"}, sorted(have)
+    assert have == {(stage, t, f) for stage in ("spans", "final") for t in TYPES.values() for f in FORMS} and len(stats) == 12, sorted(have)
     for k, (lines, _, scratch, private) in stats.items():
         assert exits_before_vector_memory(lines), k
         assert scratch == 0 and private == 0, (k, scratch, private)

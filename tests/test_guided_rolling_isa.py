@@ -1,12 +1,12 @@
 """The guided rolling step kernels in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_guided_rolling` runs `guided_rolling_kernel_v1<T, K, NOISE>` (csrc/skr_step_guided_rolling.hip): the per-sample row form
-of the guided kernel with the statement order of the rolling forms.  Its contract is visible in the instruction stream, as that of the
+`skr_step_launch_guided_rolling` runs `guided_kernel_v1<T, K, NOISE, RowForm::Rolling, false>` (csrc/skr_step_guided.hip): the per-sample
+row form of the guided kernel with the statement order of the rolling forms.  Its contract is visible in the instruction stream, as that of the
 other rolling kernels is (tests/test_rolling_isa.py, tests/test_masked_rolling_isa.py): a workgroup of an inactive sample ends before its
 first vector-memory instruction, every decision taken from the sample's row and the `slot` test of each unrolled operand is a scalar
 branch with exec never masked, operands and cond are 16-byte global loads, both outputs 16-byte global stores, and nothing spills.  The
-VGPR and occupancy table is printed beside the per-sample twins `guided_rows_kernel_v1<T, K, NOISE, RowForm::PerSample>`
-(csrc/skr_step_guided_rows.hip) -- run with -s -- and recorded in profiles/guided_rolling_isa.txt; the brackets asserted at the end are
+VGPR and occupancy table is printed beside the per-sample twins `guided_kernel_v1<T, K, NOISE, RowForm::PerSample, false>` of the same
+file -- run with -s -- and recorded in profiles/guided_rolling_isa.txt; the brackets asserted at the end are
 what that record shows."""
 
 import re
@@ -16,26 +16,25 @@ from isa_cases import HIPCC, compile_asm, kernels_of, waves_per_simd
 
 VMEM = re.compile(r"^(global|flat|buffer|scratch)_(load|store|atomic)")
 BRANCH = ("s_cbranch_scc", "s_cbranch_vcc")
-SYMBOL = re.compile(r"guided_rolling_kernel_v1I(\w+?)Li(\d+)ELb([01])EE")  # guided_rolling_kernel_v1<T, K, NOISE>
-TWIN = re.compile(r"guided_rows_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE2EE")  # guided_rows_kernel_v1<T, K, NOISE, RowForm::PerSample>
+SYMBOL = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE3ELb0EE")  # guided_kernel_v1<T, K, NOISE, RowForm::Rolling, false>
+TWIN = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE2ELb0EE")  # guided_kernel_v1<T, K, NOISE, RowForm::PerSample, false>
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    "every kernel of the new translation unit, compiled once"
+    "every unrescaled Rolling instantiation of guided_kernel_v1, selected from the one translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rolling.hip", str(tmp_path_factory.mktemp("isa") / "guided_rolling")))
-    assert all(SYMBOL.search(k) for k in found), sorted(k for k in found if not SYMBOL.search(k))  # the file holds no other kernel
-    return found
+    found = kernels_of(compile_asm("skr_step_guided.hip", str(tmp_path_factory.mktemp("isa") / "guided")))
+    return {k: v for k, v in found.items() if SYMBOL.search(k)}  # (the census of the whole file: tests/test_guided_isa.py)
 
 
 @pytest.fixture(scope="module")
 def twins(tmp_path_factory):
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rows.hip", str(tmp_path_factory.mktemp("isa") / "guided_rows")))
+    found = kernels_of(compile_asm("skr_step_guided.hip", str(tmp_path_factory.mktemp("isa") / "guided")))
     return {TWIN.search(k).groups(): v for k, v in found.items() if TWIN.search(k)}
 
 
@@ -92,7 +91,7 @@ def test_register_and_occupancy_table_against_the_per_sample_twins(kernels, twin
     per-sample twins' own record (tests/test_guided_rows_isa.py) hold here too -- 8 waves per SIMD up to 4 operands, at least 4 up to 8,
     never below 3 -- and no instantiation has fewer waves per SIMD than its twin."""
     names = {v: k for k, v in TYPES.items()}
-    print("\nVGPRs (waves per SIMD): guided_rolling_kernel_v1<T, K, NOISE> vs guided_rows_kernel_v1<T, K, NOISE, PerSample>")
+    print("\nVGPRs (waves per SIMD): guided_kernel_v1<T, K, NOISE, Rolling, false> vs guided_kernel_v1<T, K, NOISE, PerSample, false>")
     short = []
     for key in sorted((SYMBOL.search(k).groups() for k in kernels), key=lambda g: (g[0], g[2], int(g[1]))):
         symbol = next(k for k in kernels if SYMBOL.search(k).groups() == key)

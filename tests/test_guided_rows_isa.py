@@ -1,7 +1,7 @@
 """The row forms of the guided step kernel in the compiled ISA (no GPU needed: hipcc cross-compiles gfx950).
 
-`skr_step_launch_guided_indexed[_per_sample]` run `guided_rows_kernel_v1<T, K, NOISE, RowForm>` (csrc/skr_step_guided_rows.hip): the
-one-trip guided kernel with its scalars -- coefficients, zeta, Philox stream and the guidance scale -- read from a device-resident row
+`skr_step_launch_guided_indexed[_per_sample]` run `guided_kernel_v1<T, K, NOISE, RowForm, false>` (csrc/skr_step_guided.hip) in its
+WholeBatch and PerSample forms: the one-trip guided kernel with its scalars -- coefficients, zeta, Philox stream and the guidance scale -- read from a device-resident row
 behind the loads.  What the contract promises is visible in the instruction stream: `slot` stays a kernarg scalar compared per unrolled
 operand (nothing goes to scratch, no exec masking), operands are 16-byte global loads and both outputs 16-byte global stores.  The
 register and occupancy table is printed (run with -s) and recorded in profiles/guided_rows_isa.txt; the brackets asserted at the end
@@ -12,8 +12,8 @@ import re
 import pytest
 from isa_cases import HIPCC, compile_asm, kernels_of, waves_per_simd
 
-# guided_rows_kernel_v1<T, K, NOISE, RowForm>
-SYMBOL = re.compile(r"guided_rows_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([12])EE")
+# guided_kernel_v1<T, K, NOISE, RowForm::WholeBatch / PerSample, false>
+SYMBOL = re.compile(r"guided_kernel_v1I(\w+?)Li(\d+)ELb([01])ELNS_7RowFormE([12])ELb0EE")
 TYPES = {"bf16": "NS_6bf16_tE", "fp16": "NS_5f16_tE", "fp32": "f"}
 FORMS = {"1": "whole-batch", "2": "per-sample"}  # RowForm::WholeBatch, RowForm::PerSample
 VEC = 8  # elements per lane
@@ -21,12 +21,11 @@ VEC = 8  # elements per lane
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    "every guided_rows_kernel_v1 instantiation of the one translation unit, compiled once"
+    "every unrescaled WholeBatch and PerSample instantiation of guided_kernel_v1, selected from the one translation unit, compiled once"
     if HIPCC is None:
         pytest.skip("no hipcc on this box")
-    found = kernels_of(compile_asm("skr_step_guided_rows.hip", str(tmp_path_factory.mktemp("isa") / "guided_rows")))
-    assert all(SYMBOL.search(k) for k in found), sorted(k for k in found if not SYMBOL.search(k))  # the file holds no other kernel
-    return found
+    found = kernels_of(compile_asm("skr_step_guided.hip", str(tmp_path_factory.mktemp("isa") / "guided")))
+    return {k: v for k, v in found.items() if SYMBOL.search(k)}  # (the census of the whole file: tests/test_guided_isa.py)
 
 
 def count(lines, *prefixes):
@@ -71,7 +70,7 @@ def test_register_and_occupancy_table(kernels):
     least 4 -- the noisy forms hold the draw across its branch and sit up to 10 VGPRs above the twin there, one bracket below it at
     K = 8 --, and none falls below 3."""
     names = {v: k for k, v in TYPES.items()}
-    print("\nguided_rows_kernel_v1<T, K, NOISE, RowForm>: VGPRs (waves per SIMD)")
+    print("\nguided_kernel_v1<T, K, NOISE, RowForm, false>: VGPRs (waves per SIMD)")
     rows = {}
     for k, (_, vgprs, *_rest) in kernels.items():
         t, n, nz, f = SYMBOL.search(k).groups()

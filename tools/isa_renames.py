@@ -6,6 +6,10 @@
 Demangles the kernel symbols of both trees' assembly, rewrites each old template-id by the rule and prints one line
 `OLD_SYMBOL NEW_SYMBOL` per old kernel the rule applies to; an old kernel whose new name no new symbol has is an error.  Rules:
 
+  guided_forms  the six one-trip guided templates (guided[_rescaled]_kernel_v1<T, K, NOISE>, guided[_rescaled]_rows_kernel_v1<T, K, NOISE,
+                RowForm>, guided[_rescaled]_rolling_kernel_v1<T, K, NOISE>) became guided_kernel_v1<T, K, NOISE, RowForm, RESCALE>, the two
+                general kernels guided_kernel_gen<Acc, RESCALE>, and rescale_stats_{spans,final}_rows<T, PER_SAMPLE> /
+                rescale_stats_{spans,final}_rolling<T> became rescale_stats_{spans,final}_rows<T, RowForm> (790 symbols)
   masked_forms  masked_kernel_v1<T, K, NOISE>, masked_rows_kernel_v1<T, K, NOISE, PER_SAMPLE> and masked_rolling_kernel_v1<T, K, NOISE>
                 became masked_kernel_v1<T, K, NOISE, RowForm> (384 symbols)
   row_form      step_kernel_k1 / _rk1 / _k2 took the row form as a tag around the element type (PerSample<T>, Rolling<T>) and a bool
@@ -29,6 +33,18 @@ def masked_forms(name: str, args: list[str]):
     return None
 
 
+def guided_forms(name: str, args: list[str]):
+    step = re.fullmatch(r"guided_(rescaled_)?(rows_|rolling_)?kernel_(v1|gen)", name)
+    if step and len(args) < (5 if step.group(3) == "v1" else 2):  # (a name of the new tree has its five, or two, arguments already)
+        form = {None: ["(skr::RowForm)0"], "rows_": [], "rolling_": ["(skr::RowForm)3"]}[step.group(2)] if step.group(3) == "v1" else []
+        return "guided_kernel_" + step.group(3), args + form + ["true" if step.group(1) else "false"]
+    stats = re.fullmatch(r"rescale_stats_(spans|final)_(rows|rolling)", name)
+    if stats and not args[-1].startswith("(skr::RowForm)"):
+        form = 3 if stats.group(2) == "rolling" else 1 + (args[1] == "true")
+        return f"rescale_stats_{stats.group(1)}_rows", [args[0], f"(skr::RowForm){form}"]
+    return None
+
+
 TAB_AT = {"step_kernel_k1": 5, "step_kernel_rk1": 4, "step_kernel_k2": 5}
 
 
@@ -42,7 +58,7 @@ def row_form(name: str, args: list[str]):
     return name, args
 
 
-RULES = {"masked_forms": masked_forms, "row_form": row_form}
+RULES = {"guided_forms": guided_forms, "masked_forms": masked_forms, "row_form": row_form}
 
 
 def template_ids(pattern: str) -> dict:

@@ -138,7 +138,8 @@ int skr_step_backward_launch(const skr_step_grad_plan* plan, const void* g0, con
  * the row's kinds.  One captured loop therefore serves any schedule of its length (rewrite the rows: new sigmas, shift,
  * begin index, stochasticity) and several resident schedules (move index_dev), with no re-capture and no host sync.
  * Rows with zeta = 0 skip the draw exactly as a launch without noise does.  Covered: launches the one-trip kernels take
- * (whole 2048-element chunks, <= 16 operands -- the size of a row --, fp32 accumulation); anything else returns SKR_ERR_UNSUPPORTED.
+ * (whole 2048-element chunks, <= 16 operands -- the size of a row --, fp32 accumulation) and, for single-output plans, ragged samples
+ * (below, behind skr_step_launch_rolling); anything else returns SKR_ERR_UNSUPPORTED.
  */
 #define SKR_ROW_TERMS 16
 typedef struct skr_step_row {
@@ -163,8 +164,9 @@ int skr_step_launch_indexed(const skr_step_plan* plan, const void* const* inputs
  * sample's seed and the element's position within the sample, so a sample's result is bit-identical to what
  * skr_step_launch_indexed gives it with that row for the whole batch.
  * Covered: what skr_step_launch_indexed covers, and a workgroup must lie inside one sample: plan->sample_numel must be a positive
- * multiple of 2048 that divides numel, with or without noise (SKR_ERR_SHAPE / SKR_ERR_UNSUPPORTED otherwise).  A NULL
- * sample_index_dev is SKR_ERR_NULL.
+ * multiple of 2048 that divides numel, with or without noise (SKR_ERR_SHAPE / SKR_ERR_UNSUPPORTED otherwise) -- or, for a
+ * single-output plan, a ragged sample size (below, behind skr_step_launch_rolling), whose workgroups are the sample's own as well.
+ * A NULL sample_index_dev is SKR_ERR_NULL.
  * Index validity is the caller's business, as with index_dev: every sample_index_dev[s] + row_offset must name a row of the
  * table.  The kernel neither checks nor clamps an index -- an entry outside the table reads whatever lies there (or faults) --
  * so validate on the host before uploading (skrample_amd.graphs.CapturedLoop does).
@@ -194,6 +196,28 @@ int skr_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs
                             const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
                             const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */, int32_t row_offset,
                             void* stream);
+
+/*
+ * Ragged samples: samples that are NOT whole 2048-element chunks (most non-square SDXL latent buckets: (4,144,112) is 31.5 chunks).
+ * No new entry: skr_step_launch_indexed, skr_step_launch_indexed_per_sample and skr_step_launch_rolling take them for SINGLE-OUTPUT
+ * plans -- out1_dtype == SKR_NONE, no convert_to / convert_from, one 16- or 32-bit dtype for the operands and out0, fp32 accumulation
+ * (acc_f64 == 0), 1 .. SKR_ROW_TERMS operands.  A launch is ragged when
+ *     plan->sample_numel >= 2048,  % 8 == 0,  % 2048 != 0,  < 2^31,   numel == batch * plan->sample_numel,
+ * and batch * ceil(sample_numel / 2048) workgroups fit the grid of the whole-chunk kernels (INT32_MAX).  Every sample then gets
+ * ceil(sample_numel / 2048) workgroups of its own, the last of them partly empty: lanes and 4-element groups behind the sample's
+ * end issue no load and no store (csrc/skr_step_ragged.hip).
+ *   skr_step_launch_indexed_per_sample, skr_step_launch_rolling   every such launch takes the ragged form.
+ *   skr_step_launch_indexed   when the plan draws (noise_mode == 1) or numel is not whole chunks; plan->sample_numel must then be given
+ *                             and divide numel, with or without noise.  A launch the whole-chunk kernels take keeps them; a numel that is
+ *                             not whole chunks with no usable sample_numel stays SKR_ERR_UNSUPPORTED.
+ * Contract: every sample of a ragged launch has, bit for bit, what skr_step_launch writes for that sample alone with its row's values in
+ * the plan -- for the rolling form the plan that holds exactly the sample's present operands, in slot order.  No byte outside
+ * [out0, out0 + numel * sizeof(T)) is written, and an inactive slot's bytes are not written either (its neighbour's partly empty last
+ * chunk ends at the neighbour's last element).  The checks keep their order and their codes: the ragged test stands where the
+ * whole-chunk test stands, and everything else answers as before -- samples below 2048 elements or not a multiple of 8, two-output
+ * plans, rounded conversions, acc_f64 and two dtype groups on samples that are not whole chunks are SKR_ERR_UNSUPPORTED.  The masked,
+ * guided, rescaled, statistics, backward, channels-last and noise entries have no ragged form.
+ */
 
 /*
  * Device-resident positions of a rolling batch: computes, on the device, the sample_index_dev a skr_step_launch_rolling reads and the

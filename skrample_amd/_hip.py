@@ -156,6 +156,23 @@ ROW_TERMS = 16  # include/skrample_hip.h SKR_ROW_TERMS
 PER_SAMPLE_CHUNK = 2048  # elements per workgroup of the one-trip kernels: a sample of a per-sample launch is made of whole ones
 
 
+def ragged_sample(sample_numel: int) -> bool:
+    """a sample the ragged form of the table launches takes (include/skrample_hip.h, "ragged samples"): at least one chunk, a multiple
+    of 8 elements, not whole chunks -- its last workgroup is partly empty"""
+    return PER_SAMPLE_CHUNK <= sample_numel < 2**31 and sample_numel % 8 == 0 and sample_numel % PER_SAMPLE_CHUNK != 0
+
+
+def single_output_plan(plan: "StepPlanC") -> bool:
+    "what a ragged launch must be: one output in the operands' one 16- or 32-bit dtype, no rounded conversion, float32 arithmetic, 1..ROW_TERMS operands"
+    one = plan.dtype_a
+    return (plan.out1_dtype == NONE and plan.out0_dtype == one and one in (BF16, F16, F32) and (plan.n_group_a == plan.n_terms or plan.dtype_b == one)
+            and not plan.convert_to and not plan.convert_from and not plan.acc_f64 and 1 <= plan.n_terms <= ROW_TERMS)  # fmt: skip
+
+
+RAGGED_SINGLE_OUTPUT = ("ragged samples (not whole 2048-element chunks) are served for single-output launches only -- Euler, DPM, Adams and UniP steps in one 16- or "
+                        "32-bit dtype under the default compute scale; the two-output (UniPC, SPC), Runge-Kutta, masked and guided row kernels need whole chunks")
+
+
 class StepRowC(ctypes.Structure):
     "mirror of `skr_step_row`: the scalars of one launch, resident on the device for indexed launches"
 
@@ -252,6 +269,11 @@ class IndexedRows:
     owns (`factor`, `partials`: allocated in the recording pass, the same in every step of the graph), with the same row offset:
     skr_guidance_rescale_factor_indexed[_per_sample], then skr_step_launch_guided_rescaled_indexed[_per_sample] -- whether or not the
     recording pass rescaled, since a row with phi == 0 makes the first return at once and the second the plain guided step.
+
+    Ragged samples (at least one 2048-element chunk, a multiple of 8 elements, not whole chunks): plain single-output launches are
+    recorded and emitted as they stand -- the row entries take the ragged form themselves --; a whole-batch capture needs `samples` for
+    that, to give a launch without noise the sample size it does not carry.  Any other launch on ragged samples is refused while
+    recording, before a stream captures.
 
     mode "record": launches run normally and append one row each (their structure is remembered);
     mode "emit"  : launches become indexed launches reading row `base + k` (k = position in the loop) -- used under graph capture;
@@ -356,6 +378,13 @@ class IndexedRows:
             return "guided rows need at least one operand"
         return None
 
+    def _ragged_whole_batch(self, plan: StepPlanC, numel: int) -> bool:
+        """a plain launch of a whole-batch capture that only the ragged form of skr_step_launch_indexed takes: ragged samples -- the plan's,
+        or the captured batch's (`samples`) for a launch that carries no sample size -- and a draw, or a launch that is not whole chunks"""
+        samples = getattr(self, "samples", None)
+        per = plan.sample_numel if plan.sample_numel > 0 else (numel // samples if samples and numel % samples == 0 else 0)
+        return ragged_sample(per) and numel % per == 0 and (plan.noise_mode == 1 or numel % PER_SAMPLE_CHUNK != 0)
+
     def _uncovered_rescaled(self, plan: StepPlanC, numel: int) -> str | None:
         "why the rescaled guided row kernels do not cover this launch of the captured batch (skr_step_launch_guided_rescaled_indexed), or None"
         if numel % self.samples != 0 or (numel // self.samples) % PER_SAMPLE_CHUNK != 0:
@@ -407,10 +436,17 @@ class IndexedRows:
             return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
 
         if self.mode == "record":
+            plain = mask is None and guide is None
             if self.batch is not None and (numel % self.batch != 0 or (numel // self.batch) % PER_SAMPLE_CHUNK != 0):
                 # (what skr_step_launch_indexed_per_sample would answer during the capture: said here, before a stream is capturing)
-                raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, "
-                                       f"not {numel} elements for {self.batch} samples")
+                if not (plain and numel % self.batch == 0 and ragged_sample(numel // self.batch)):
+                    raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, "
+                                           f"not {numel} elements for {self.batch} samples")
+                if not single_output_plan(plan):
+                    raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {RAGGED_SINGLE_OUTPUT}")
+            if self.batch is None and plain and self._ragged_whole_batch(plan, numel) and not single_output_plan(plan):
+                # (what skr_step_launch_indexed would answer during the capture)
+                raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {RAGGED_SINGLE_OUTPUT}")
             if mask is not None:
                 why = self._uncovered(plan, mask, numel)
                 if why is not None:  # (what skr_step_launch_masked_indexed would answer during the capture)
@@ -462,6 +498,10 @@ class IndexedRows:
             return lib.skr_step_launch_guided_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
         if mask is not None:
             return lib.skr_step_launch_masked_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
+        if plan.sample_numel <= 0 and self._ragged_whole_batch(plan, numel):
+            # (a launch without noise carries no sample size; one that is not whole chunks takes the ragged form, which needs it: the captured batch gives it)
+            plan = StepPlanC.from_buffer_copy(plan)
+            plan.sample_numel = numel // self.samples
         return lib.skr_step_launch_indexed(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
 
 

@@ -561,10 +561,14 @@ static int step_launch_impl(const skr_step_plan* plan, const void* const* inputs
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (has_table(form)) {
     // one row per sample: the batch is numel / sample_numel, and a workgroup (2048 elements) must lie inside one sample
+    // (or, for a single-output plan, ragged samples: at least one chunk each and a multiple of 8 elements -- skr_step_ragged.hip)
+    const bool ragged = skr::ragged_launch(p, numel, form);
     if (per_sample_rows(form) || p.noise_mode == 1) {
-      if (const int rc = samples_ok(p, numel, per_sample_rows(form) ? 2048 : 8)) return rc;
+      const int rc = samples_ok(p, numel, per_sample_rows(form) ? 2048 : 8);
+      if (rc != SKR_OK && !(ragged && rc == SKR_ERR_UNSUPPORTED)) return rc;
     }
     if (p.acc_f64 || p.n_terms > SKR_ROW_TERMS || row_offset < 0) return SKR_ERR_UNSUPPORTED;
+    if (ragged) return skr::launch_ragged(p, inputs, out0, seeds_dev, numel, s, form, rows, index, row_offset);
     return skr::run<float>(p, inputs, out0, out1, seeds_dev, numel, s, form, rows, index, row_offset);
   }
   return p.acc_f64 ? skr::run<double>(p, inputs, out0, out1, seeds_dev, numel, s)

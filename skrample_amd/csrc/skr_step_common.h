@@ -507,4 +507,11 @@ template <typename T> int launch_one_trip_k(const StepArgs<float>& args, bool no
 template <typename T> int launch_one_trip_rk(const StepArgs<float>& args, bool noise, hipStream_t stream, bool& taken);
 template <typename TA> int launch_one_trip_two(const StepArgs<float>& args, bool noise, bool group_b_f32, hipStream_t stream, bool& taken);
 
+// ragged samples (skr_step_ragged.hip): a table launch of a single-output plan whose samples are at least one 2048-element chunk, a
+// multiple of 8 elements and NOT whole chunks, and that no whole-chunk kernel takes -- every per-sample form, and the whole-batch form
+// when it draws or numel is not whole chunks.  launch_ragged launches what ragged_launch admitted.
+bool ragged_launch(const skr_step_plan& p, int64_t numel, RowForm form);
+int launch_ragged(const skr_step_plan& p, const void* const* inputs, void* out0, const uint64_t* seeds, int64_t numel, hipStream_t stream,
+                  RowForm form, const skr_step_row* rows, const int32_t* index, int32_t row_offset);
+
 }  // namespace skr

@@ -282,9 +282,16 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     follows a re-targeted schedule, because the tensor's contents are replaced with the rows.
 
     `per_sample` (needs `indexed=True`; off by default, and then nothing changes): every sample of a replay may follow its own slot,
-    `loop(latents, slot=[...])`; with `device_timesteps` the network receives a 1-D `t` of shape `[batch]`.  Needs latents of whole
-    2048-element chunks per sample.  `slots` may be as large as the batch (one schedule per request): the table is
+    `loop(latents, slot=[...])`; with `device_timesteps` the network receives a 1-D `t` of shape `[batch]`.  Needs samples of at least
+    2048 elements and a multiple of 8 (below).  `slots` may be as large as the batch (one schedule per request): the table is
     `slots * launches per loop * 328 bytes` of device memory -- 256 slots of a 30-launch loop are 2.5 MB.
+
+    Sample sizes of an indexed capture.  Samples of whole 2048-element chunks are served for every sampler the row kernels cover.
+    Ragged samples -- at least 2048 elements, a multiple of 8, not whole chunks: most non-square SDXL latent buckets, (4,144,112) for
+    one -- are served, with or without `per_sample`, for the samplers whose step is one single-output launch (Euler, DPM 1-3, Adams,
+    UniP) in one 16- or 32-bit dtype under the default compute scale, with `Random` noise or none.  UniPC and SPC, the Runge-Kutta
+    wrappers, in-painting, guidance and `compute_scale=float64` on ragged samples are refused during the recording pass, before the
+    stream captures; so are samples below 2048 elements or not a multiple of 8 wherever a row kernel needs a sample size.
 
     A wrapper with `set_inpaint(...)` in force is captured with its masked steps; its three in-paint tensors become static buffers of
     the loop (`loop.inpaint`).  With `indexed=True` the masked row kernel must cover the launches -- samples of whole 2048-element
@@ -394,7 +401,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         from . import _hip
 
         rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None, guided=guidance_scale is not None,
-                                rescaled=rescaled, samples=int(example.shape[0]) if rescaled else None)
+                                rescaled=rescaled, samples=int(example.shape[0]))  # (samples: the factor's size, and the sample size of a ragged launch without noise)
         _hip.indexed = rows
         try:
             rows.begin("record")

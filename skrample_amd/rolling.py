@@ -112,6 +112,13 @@ of a guided batch are unchanged.  `rescaled=True` without `guided=True`, a negat
 the wrong length and a non-zero `guidance_rescale` on a batch built without `rescaled` are refused.  Not covered: changing a resident
 request's phi mid-run (admit it with a schedule), skipping the statistics launch from the host when nobody rescales.
 
+Sample sizes.  A unit (`example.shape[1:]`) of whole 2048-element chunks joins any batch.  A ragged unit -- at least 2048 elements and a
+multiple of 8, not whole chunks: (4,144,112) and most other non-square SDXL latent buckets -- joins a plain batch: not `guided`, no
+`inpaint_mask_shape`, `Random` noise or none, and a sampler whose step is one single-output launch (Euler, DPM 1-3, Adams, UniP).  The
+entry takes the ragged form of the kernel by itself (csrc/skr_step_ragged.hip: a sample's last workgroup is partly empty), and `admit()`,
+`step()`, `advance()`, `capture()` and `CapturedTicks.tick()` need nothing new.  Refused when the batch is built, each naming the reason:
+UniPC and SPC, `guided`, `inpaint_mask_shape` and Offset / Pyramid noise on a ragged unit; units below 2048 elements or not a multiple of 8.
+
 Covered: `SkrampleWrapperScheduler` with Euler, DPM 1-3, Adams 2-4, UniP / UniPC 2-3 and SPC, with or without stochasticity,
 `Random` noise (drawn in the kernel), `Offset` / `Pyramid` noise (drawn per slot, above) or none, bf16 / fp16 / fp32 latents under the default compute scale -- what
 `skr_step_launch_indexed` covers (UniPC on fp32 latents is refused, as by the captured loops); a device-resident position vector
@@ -247,10 +254,15 @@ class RollingBatch:
         self.sample_numel = 1
         for n in self.unit_shape:
             self.sample_numel *= int(n)
-        if self.sample_numel <= 0 or self.sample_numel % PER_SAMPLE_CHUNK != 0:
-            raise ValueError(f"per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {self.sample_numel} elements per sample")
+        # ragged samples (at least one chunk, a multiple of 8 elements, not whole chunks: most non-square SDXL buckets) join a plain batch
+        self.ragged = _hip.ragged_sample(self.sample_numel)
+        if self.sample_numel <= 0 or (self.sample_numel % PER_SAMPLE_CHUNK != 0 and not self.ragged):
+            raise ValueError(f"per-sample rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {self.sample_numel} elements per sample "
+                             f"(ragged samples are served from {PER_SAMPLE_CHUNK} elements on, in multiples of 8)")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
+        if self.ragged:
+            self._refuse_ragged(first)
         if self.guided:
             self._refuse_guided(first)
         self.draws_noise = bool(first.sampler.require_noise)
@@ -261,6 +273,8 @@ class RollingBatch:
         self.keep = int(first.sampler.require_previous)
         self.plan, self.roles = self._widest(self._trace(first, self.keep + 4, seed=0 if self.draws_noise else None))
         self.two_outputs = self.plan.out0_dtype != _hip.NONE and self.plan.out1_dtype != _hip.NONE
+        if self.ragged and not _hip.single_output_plan(self.plan):  # (whatever else the dry run turned up: compute_scale=float64, a rounded conversion)
+            raise SkrampleHipError(f"skr_step_launch_rolling: request outside kernel coverage ({_hip.RAGGED_SINGLE_OUTPUT})")
         if self.plan.n_terms > ROW_TERMS:
             raise SkrampleHipError(f"a launch with {self.plan.n_terms} operands does not fit a device-resident row ({ROW_TERMS})")
         shape = (self.capacity, *self.unit_shape)
@@ -324,6 +338,24 @@ class RollingBatch:
         if refused is not None:
             raise SkrampleHipError(f"{kind.__name__} noise on samples {self.unit_shape}: {refused}")
         return True
+
+    def _refuse_ragged(self, first) -> None:
+        """ragged samples (not whole 2048-element chunks): only the single-output rolling step has a ragged kernel form
+        (csrc/skr_step_ragged.hip); everything else is refused by name before anything is allocated or traced"""
+        from .pytorch import noise as generators
+        from .sampling import structured as sampling
+
+        what = f"ragged samples ({self.sample_numel} elements, not whole {PER_SAMPLE_CHUNK}-element chunks)"
+        if self.guided:
+            raise ValueError(f"guided together with {what}: the guided row kernels need samples of whole chunks")
+        if self.masked:
+            raise ValueError(f"inpaint_mask_shape together with {what}: the masked row kernels need samples of whole chunks")
+        sampler = first.sampler
+        if type(sampler).sample_packed is not sampling.StatedSampler.sample_packed:
+            raise SkrampleHipError(f"{type(sampler).__name__} on {what}: its step is a two-output launch, whose row kernel needs samples of whole chunks; "
+                                   "a rolling batch of ragged samples takes Euler, DPM 1-3, Adams and UniP")  # fmt: skip
+        if bool(sampler.require_noise) and first.noise_type in (generators.Offset, generators.Pyramid):
+            raise ValueError(f"{first.noise_type.__name__} noise on {what}: the rolling draws need samples of whole chunks; a rolling batch of ragged samples draws Random noise or none")
 
     def _refuse_guided(self, first) -> None:
         "a guided batch: what its one launch per tick does not cover, refused by name before anything is allocated or traced"

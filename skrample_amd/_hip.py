@@ -7,6 +7,7 @@ package.  If the library is missing or a launch fails, `SkrampleHipError` is rai
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 import sys
 import threading
@@ -162,11 +163,22 @@ def ragged_sample(sample_numel: int) -> bool:
     return PER_SAMPLE_CHUNK <= sample_numel < 2**31 and sample_numel % 8 == 0 and sample_numel % PER_SAMPLE_CHUNK != 0
 
 
-def single_output_plan(plan: "StepPlanC") -> bool:
-    "what a ragged launch must be: one output in the operands' one 16- or 32-bit dtype, no rounded conversion, float32 arithmetic, 1..ROW_TERMS operands"
+def one_dtype_f32(plan: "StepPlanC", *also: int) -> bool:
+    """THE coverage rule of the masked, guided and ragged row kernels, the one place it is written: the operands of both groups, the first
+    output and `also` (dtype codes: a mask's, a batch's) are one 16- or 32-bit dtype, evaluated in float32"""
     one = plan.dtype_a
-    return (plan.out1_dtype == NONE and plan.out0_dtype == one and one in (BF16, F16, F32) and (plan.n_group_a == plan.n_terms or plan.dtype_b == one)
-            and not plan.convert_to and not plan.convert_from and not plan.acc_f64 and 1 <= plan.n_terms <= ROW_TERMS)  # fmt: skip
+    return (one in (BF16, F16, F32) and plan.out0_dtype == one and (plan.n_group_a == plan.n_terms or plan.dtype_b == one)
+            and all(code == one for code in also) and not plan.acc_f64)  # fmt: skip
+
+
+def one_group_launch(plan: "StepPlanC", *also: int) -> bool:
+    "what a masked or guided rolling batch steps with: one single-output launch of one operand group under the coverage rule"
+    return plan.out1_dtype == NONE and plan.n_group_a == plan.n_terms and one_dtype_f32(plan, *also)
+
+
+def single_output_plan(plan: "StepPlanC") -> bool:
+    "what a ragged launch must be: one output under the coverage rule, no rounded conversion, 1..ROW_TERMS operands"
+    return plan.out1_dtype == NONE and one_dtype_f32(plan) and not plan.convert_to and not plan.convert_from and 1 <= plan.n_terms <= ROW_TERMS
 
 
 RAGGED_SINGLE_OUTPUT = ("ragged samples (not whole 2048-element chunks) are served for single-output launches only -- Euler, DPM, Adams and UniP steps in one 16- or "
@@ -229,6 +241,67 @@ GUIDANCE_SPAN = 2048  # elements per partial sum of skr_guidance_rescale_factor 
 def guidance_partials(numel: int, sample_numel: int) -> int:
     "doubles of workspace skr_guidance_rescale_factor needs (include/skrample_hip.h, SKR_GUIDANCE_PARTIALS)"
     return 4 * (numel // sample_numel) * ((sample_numel + GUIDANCE_SPAN - 1) // GUIDANCE_SPAN)
+
+
+# The launch table.  A launch has a KIND -- what it computes -- and a FORM -- where its scalars and its layout come from; the C entry's name
+# and its argument list follow from the two by ONE rule, which the prototypes (load()), every launcher of the package (launch_call,
+# IndexedRows.launch, rolling.RollingBatch._launch) and the tests read.  A new kind or form is a row here.
+FACTOR = "guidance_factor"  # the statistics launch of rescaled guidance: a kind of its own, with arguments of its own
+STEP_KINDS = {"plain": ("out1",), "masked": ("mask",), "guided": ("guide",), "guided_rescaled": ("guide", "rescale")}  # kind -> what follows out0
+FORMS = ("direct", "channels_last", "indexed", "indexed_per_sample", "rolling")
+_vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+ARGTYPES = {"plan": ctypes.POINTER(StepPlanC), "operands": ctypes.POINTER(_vp), "out0": _vp, "out1": _vp, "mask": ctypes.POINTER(StepMaskC),
+            "guide": ctypes.POINTER(StepGuidanceC), "rescale": ctypes.POINTER(StepRescaleC), "seeds": _vp, "layout": ctypes.POINTER(StepLayoutC), "numel": _i64,
+            "rows": _vp, "index": _vp, "row_offset": _i32, "stream": _vp,
+            "uncond": _vp, "cond": _vp, "dtype": _i32, "scale": ctypes.c_double, "sample_numel": _i64, "factor": _vp, "stats": _vp, "partials": _vp}  # fmt: skip
+
+
+def _entry(kind: str, form: str) -> "tuple[str, tuple[str, ...]] | None":
+    "the rule: (C entry name, argument names in order) of a kind in a form, None for a combination the library does not have"
+    table = ("rows", "index", "row_offset") if form in FORMS[2:] else ()
+    suffix = "" if form == "direct" else "_" + form
+    if kind == FACTOR:  # (the scale is a row value in the table forms)
+        names = ("uncond", "cond", "dtype", *(() if table else ("scale",)), "numel", "sample_numel", *table, "factor", "stats", "partials", "stream")
+        return None if form == "channels_last" else ("skr_guidance_rescale_factor" + suffix, names)
+    if form == "channels_last" and kind not in ("plain", "masked"):
+        return None
+    layout = ("layout",) if form == "channels_last" else ()
+    return ("skr_step_launch" + ("" if kind == "plain" else "_" + kind) + suffix, ("plan", "operands", "out0", *STEP_KINDS[kind], "seeds", *layout, "numel", *table, "stream"))
+
+
+ENTRIES = {key: found for key in ((kind, form) for kind in (*STEP_KINDS, FACTOR) for form in FORMS) if (found := _entry(*key)) is not None}
+BY_REFERENCE = {"plan", "mask", "guide", "rescale", "layout"}  # callers hand over the structure, the entry takes its address
+# per key: (name, the arguments picked from a dict of values in one call, the positions that go by reference)
+_LAID_OUT = {key: (name, operator.itemgetter(*names), tuple(i for i, n in enumerate(names) if n in BY_REFERENCE)) for key, (name, names) in ENTRIES.items()}
+
+
+def _lay_out(kind: str, form: str, values: dict) -> "tuple[str, list]":
+    try:
+        name, pick, references = _LAID_OUT[kind, form]
+    except KeyError:  # a combination the library does not have is an error, never another route
+        raise SkrampleHipError(f"the library has no {form} form of a {kind} launch") from None
+    args = list(pick(values))
+    for i in references:
+        args[i] = ctypes.byref(args[i])
+    return name, args
+
+
+def entry_name(kind: str, form: str) -> str:
+    "the C entry of a kind of launch in a form"
+    if (kind, form) not in ENTRIES:
+        raise SkrampleHipError(f"the library has no {form} form of a {kind} launch")
+    return ENTRIES[kind, form][0]
+
+
+def entry_args(kind: str, form: str, **values) -> list:
+    "the arguments of that entry from values by name (structures go by reference); names the entry does not take are ignored"
+    return _lay_out(kind, form, values)[1]
+
+
+def call_entry(lib, kind: str, form: str, values: dict) -> int:
+    "one call of the entry, looked up in `lib` by name at call time, on the arguments `values` names; returns the status"
+    name, args = _lay_out(kind, form, values)
+    return getattr(lib, name)(*args)
 
 
 def plan_structure(plan: StepPlanC, sample_numel: bool = True, mask: "StepMaskC | None" = None, guide: "StepGuidanceC | None" = None,
@@ -351,8 +424,7 @@ class IndexedRows:
         "why the masked row kernel does not cover this launch (include/skrample_hip.h, skr_step_launch_masked_indexed), or None"
         if plan.acc_f64:
             return "masked rows are evaluated in float32, not under compute_scale=float64"
-        one = plan.dtype_a
-        if (plan.n_group_a != plan.n_terms and plan.dtype_b != one) or plan.out0_dtype != one or mask.dtype != one or one not in (BF16, F16, F32):
+        if not one_dtype_f32(plan, mask.dtype):
             return "masked rows need one 16- or 32-bit dtype for operands, mask and output"
         if plan.sample_numel <= 0 or plan.sample_numel % PER_SAMPLE_CHUNK != 0 or numel % PER_SAMPLE_CHUNK != 0:
             return f"masked rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {plan.sample_numel} elements"
@@ -369,8 +441,7 @@ class IndexedRows:
                     "compute_scale=None and channels-last or strided operands")
         if plan.acc_f64:
             return "guided rows are evaluated in float32, not under compute_scale=float64"
-        one = plan.dtype_a
-        if (plan.n_group_a != plan.n_terms and plan.dtype_b != one) or plan.out0_dtype != one or one not in (BF16, F16, F32):
+        if not one_dtype_f32(plan):
             return "guided rows need one 16- or 32-bit dtype for operands, cond and both outputs"
         if numel % PER_SAMPLE_CHUNK != 0 or (plan.noise_mode == 1 and (plan.sample_numel <= 0 or plan.sample_numel % PER_SAMPLE_CHUNK != 0)):
             return f"guided rows need whole {PER_SAMPLE_CHUNK}-element chunks, not {numel} elements in samples of {plan.sample_numel}"
@@ -393,26 +464,6 @@ class IndexedRows:
             return f"rescaled guided rows take the statistic over the samples the noise is drawn by: {numel // self.samples} elements, not {plan.sample_numel}"
         return None
 
-    def _emit_rescaled(self, lib, plan: StepPlanC, arr, out0_ptr, guide: "StepGuidanceC", seeds_ptr, numel: int, stream_ptr: int, k: int) -> int:
-        """the two launches of a guided step of a rescaled capture, on the hook's factor and partials and with the same row offset: the
-        statistics row launch over (inputs[slot], cond), then the rescaled row step.  A row with phi == 0 makes the first return before it
-        reads anything and the second the plain guided step."""
-        per = numel // self.samples
-        if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
-            plan = StepPlanC.from_buffer_copy(plan)
-            plan.sample_numel = per
-        if numel != self.samples * plan.sample_numel:
-            raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {self.samples} samples of {plan.sample_numel} the factor holds")
-        rescale = StepRescaleC(self.factor.data_ptr(), 0.0, per, 0)  # (phi is the row's)
-        per_sample = self.sample_index_dev is not None
-        rows, index, uncond = self.rows_dev.data_ptr(), (self.sample_index_dev if per_sample else self.index_dev).data_ptr(), arr[guide.slot]
-        statistic = lib.skr_guidance_rescale_factor_indexed_per_sample if per_sample else lib.skr_guidance_rescale_factor_indexed
-        step = lib.skr_step_launch_guided_rescaled_indexed_per_sample if per_sample else lib.skr_step_launch_guided_rescaled_indexed
-        status = statistic(uncond, guide.cond, plan.dtype_a, numel, per, rows, index, k, self.factor.data_ptr(), None, self.partials.data_ptr(), stream_ptr)
-        if status != 0:
-            return status
-        return step(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), ctypes.byref(rescale), seeds_ptr, numel, rows, index, k, stream_ptr)
-
     def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int, mask: "StepMaskC | None" = None,
                guide: "StepGuidanceC | None" = None, rescale: "StepRescaleC | None" = None) -> int:
         """one launch of the loop; `mask` (its descriptor): a masked one (skr_step_launch_masked and its row forms; out1_ptr is None);
@@ -425,16 +476,8 @@ class IndexedRows:
         rescaled = guide is not None and getattr(self, "rescaled", False)  # (a recorder put together without the constructor has no such field)
         if rescaled:
             phi = rescale.phi if rescale is not None else 0.0  # (a plain guided launch is what the wrapper issues for guidance_rescale == 0)
-
-        def run_now() -> int:  # the launch itself, with the plan's own scalars
-            if rescale is not None:
-                return lib.skr_step_launch_guided_rescaled(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), ctypes.byref(rescale), seeds_ptr, numel, stream_ptr)
-            if guide is not None:
-                return lib.skr_step_launch_guided(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, stream_ptr)
-            if mask is not None:
-                return lib.skr_step_launch_masked(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, stream_ptr)
-            return lib.skr_step_launch(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, stream_ptr)
-
+        kind = "guided_rescaled" if rescale is not None else "guided" if guide is not None else "masked" if mask is not None else "plain"
+        values = dict(plan=plan, operands=arr, out0=out0_ptr, out1=out1_ptr, mask=mask, guide=guide, rescale=rescale, seeds=seeds_ptr, numel=numel, stream=stream_ptr)
         if self.mode == "record":
             plain = mask is None and guide is None
             if self.batch is not None and (numel % self.batch != 0 or (numel // self.batch) % PER_SAMPLE_CHUNK != 0):
@@ -468,7 +511,7 @@ class IndexedRows:
             self.structures.append(plan_structure(plan, mask=mask, guide=guide, rescale=rescale))
             self.shapeless.append(plan_structure(plan, sample_numel=False, mask=mask, guide=guide, rescale=rescale))
             self.host.append(row)
-            return run_now()
+            return call_entry(lib, kind, "direct", values)  # the launch itself, with the plan's own scalars
         if k >= self.length:
             raise SkrampleHipError("more launches than the captured loop has")
         if self.mode == "refill":
@@ -478,31 +521,35 @@ class IndexedRows:
             if found != self.shapeless[k]:
                 raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
             self.host[self.slot * self.length + k] = self.row_from(plan, scale, phi)
-            return run_now()
+            return call_entry(lib, kind, "direct", values)  # the launch itself, with the plan's own scalars
         if plan_structure(plan, mask=mask, guide=guide, rescale=rescale) != self.structures[k]:
             raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
-        if rescaled:
-            return self._emit_rescaled(lib, plan, arr, out0_ptr, guide, seeds_ptr, numel, stream_ptr, k)
-        if self.sample_index_dev is not None:
+        # emit: the row form of the launch, reading row `k` behind the loop's slot (or behind every sample's own)
+        per_sample = self.sample_index_dev is not None
+        form = "indexed_per_sample" if per_sample else "indexed"
+        values.update(rows=self.rows_dev.data_ptr(), index=(self.sample_index_dev if per_sample else self.index_dev).data_ptr(), row_offset=k)
+        if rescaled or per_sample:
+            count, holder = (self.samples, "factor") if rescaled else (self.batch, "per-sample index")
             if plan.sample_numel <= 0:  # (a launch without noise carries no sample size: the captured batch gives it)
-                plan = StepPlanC.from_buffer_copy(plan)
-                plan.sample_numel = numel // self.batch
-            if numel != self.batch * plan.sample_numel:
-                raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {self.batch} samples of {plan.sample_numel} the per-sample index holds")
-            if guide is not None:
-                return lib.skr_step_launch_guided_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
-            if mask is not None:
-                return lib.skr_step_launch_masked_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
-            return lib.skr_step_launch_indexed_per_sample(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.sample_index_dev.data_ptr(), k, stream_ptr)
-        if guide is not None:
-            return lib.skr_step_launch_guided_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(guide), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
-        if mask is not None:
-            return lib.skr_step_launch_masked_indexed(ctypes.byref(plan), arr, out0_ptr, ctypes.byref(mask), seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
-        if plan.sample_numel <= 0 and self._ragged_whole_batch(plan, numel):
+                plan = values["plan"] = StepPlanC.from_buffer_copy(plan)
+                plan.sample_numel = numel // count
+            if numel != count * plan.sample_numel:
+                raise SkrampleHipError(f"launch {k} covers {numel} elements, not the {count} samples of {plan.sample_numel} the {holder} holds")
+        elif kind == "plain" and plan.sample_numel <= 0 and self._ragged_whole_batch(plan, numel):
             # (a launch without noise carries no sample size; one that is not whole chunks takes the ragged form, which needs it: the captured batch gives it)
-            plan = StepPlanC.from_buffer_copy(plan)
+            plan = values["plan"] = StepPlanC.from_buffer_copy(plan)
             plan.sample_numel = numel // self.samples
-        return lib.skr_step_launch_indexed(ctypes.byref(plan), arr, out0_ptr, out1_ptr, seeds_ptr, numel, self.rows_dev.data_ptr(), self.index_dev.data_ptr(), k, stream_ptr)
+        if rescaled:
+            # the two launches of a guided step of a rescaled capture, on the hook's factor and partials and with the same row offset: the statistics
+            # row launch over (inputs[slot], cond), then the rescaled row step.  A row with phi == 0 makes the first return before it reads
+            # anything and the second the plain guided step.
+            per = numel // self.samples
+            status = call_entry(lib, FACTOR, form, dict(values, uncond=arr[guide.slot], cond=guide.cond, dtype=plan.dtype_a, sample_numel=per, factor=self.factor.data_ptr(),
+                                                        stats=None, partials=self.partials.data_ptr()))  # fmt: skip
+            if status != 0:
+                return status
+            kind, values["rescale"] = "guided_rescaled", StepRescaleC(self.factor.data_ptr(), 0.0, per, 0)  # (phi is the row's)
+        return call_entry(lib, kind, form, values)
 
 
 # Launch hooks, PER THREAD (a scheduler instance is single-threaded by contract, but several may run in different threads of one
@@ -571,39 +618,9 @@ def load() -> ctypes.CDLL:
         except OSError as exc:  # pragma: no cover - depends on the box
             raise SkrampleHipError(f"cannot load {LIB_PATH}: {exc}") from exc
         vp, i64, u64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32
-        lib.skr_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp]
-        lib.skr_step_launch.restype = ctypes.c_int
-        for table_launch in (lib.skr_step_launch_indexed, lib.skr_step_launch_indexed_per_sample, lib.skr_step_launch_rolling):
-            table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp, i32, vp]
-            table_launch.restype = ctypes.c_int
-        lib.skr_step_launch_channels_last.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, vp, vp, ctypes.POINTER(StepLayoutC), i64, vp]
-        lib.skr_step_launch_channels_last.restype = ctypes.c_int
-        lib.skr_step_launch_masked.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp]
-        lib.skr_step_launch_masked.restype = ctypes.c_int
-        for masked_table_launch in (lib.skr_step_launch_masked_indexed, lib.skr_step_launch_masked_indexed_per_sample, lib.skr_step_launch_masked_rolling):
-            masked_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, i64, vp, vp, i32, vp]
-            masked_table_launch.restype = ctypes.c_int
-        lib.skr_step_launch_masked_channels_last.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepMaskC), vp, ctypes.POINTER(StepLayoutC), i64, vp]
-        lib.skr_step_launch_masked_channels_last.restype = ctypes.c_int
-        lib.skr_step_launch_guided.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp]
-        lib.skr_step_launch_guided.restype = ctypes.c_int
-        for guided_table_launch in (lib.skr_step_launch_guided_indexed, lib.skr_step_launch_guided_indexed_per_sample, lib.skr_step_launch_guided_rolling):
-            guided_table_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), vp, i64, vp, vp, i32, vp]
-            guided_table_launch.restype = ctypes.c_int
-        lib.skr_guidance_rescale_factor.argtypes = [vp, vp, i32, ctypes.c_double, i64, i64, vp, vp, vp, vp]
-        lib.skr_guidance_rescale_factor.restype = ctypes.c_int
-        lib.skr_step_launch_guided_rescaled.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp]
-        lib.skr_step_launch_guided_rescaled.restype = ctypes.c_int
-        lib.skr_guidance_rescale_factor_rolling.argtypes = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp]
-        lib.skr_guidance_rescale_factor_rolling.restype = ctypes.c_int
-        lib.skr_step_launch_guided_rescaled_rolling.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp, vp, i32, vp]
-        lib.skr_step_launch_guided_rescaled_rolling.restype = ctypes.c_int
-        for factor_rows in (lib.skr_guidance_rescale_factor_indexed, lib.skr_guidance_rescale_factor_indexed_per_sample):
-            factor_rows.argtypes = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp]
-            factor_rows.restype = ctypes.c_int
-        for rescaled_rows in (lib.skr_step_launch_guided_rescaled_indexed, lib.skr_step_launch_guided_rescaled_indexed_per_sample):
-            rescaled_rows.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepRescaleC), vp, i64, vp, vp, i32, vp]
-            rescaled_rows.restype = ctypes.c_int
+        for name, names in ENTRIES.values():  # the step launches and the guidance statistics: prototypes from the table's one rule
+            entry = getattr(lib, name)
+            entry.argtypes, entry.restype = [ARGTYPES[n] for n in names], ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -695,11 +712,6 @@ def current_stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-# When a list is installed as `_hip.trace` (per thread, see _HipModule) every launch appends
-# (plan, inputs, out0, out1, seeds, numel): used by the step programs and by bench.py to lift the exact plans the
-# samplers emit and replay them through the C ABI.
-
-
 def _ptr(t):
     "`data_ptr()` of a tensor, None (a NULL argument) for None"
     return t.data_ptr() if t is not None else None
@@ -710,159 +722,117 @@ def _operand_array(tensors):
     return (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
 
 
-def _no_rows_with_layout(layout) -> None:
-    "the indexed-rows hook has no channels-last form: the caller takes the contiguous route while one is installed"
-    if layout is not None and getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError("captured loops with device-resident rows take contiguous operands")
+class StepCall(tuple):
+    """The record of one step launch: what a `_hip.trace` list (per thread, see _HipModule) receives for it.  It IS the six-tuple
+    (plan, inputs, out0, out1, seeds, numel) that the step programs, bench.py and the tools unpack to lift the exact plans the samplers emit,
+    and it says what the launch is by name, never by its length: `kind` (a key of STEP_KINDS), `layout` ((channels, plane) or None: read
+    off the tensors) and -- None where the kind has none -- `mask`, `mask_numel`, `batch_stride` (masked), `cond`, `guided_out`, `scale`,
+    `slot` (guided), `factor`, `phi`, `sample_numel` (guided_rescaled).  A step program is built from a plain one only."""
+
+    kind, layout = "plain", None
+    mask = mask_numel = batch_stride = cond = guided_out = scale = slot = factor = phi = sample_numel = None
+    plan, inputs, out0, out1, seeds, numel = (property(operator.itemgetter(i)) for i in range(6))
+
+    def __new__(cls, plan, inputs, out0, out1, seeds, numel, kind: str = "plain", **named):
+        self = tuple.__new__(cls, (plan, list(inputs), out0, out1, seeds, numel))
+        if named:  # (a plain contiguous launch, the common one, is the class's defaults)
+            self.__dict__.update(named, kind=kind)
+        return self
 
 
-def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, numel: int, device: torch.device, layout: tuple[int, int] | None = None) -> None:
-    """one fused kernel launch on torch's current stream of `device`.  With `layout` = (channels, plane) the operands and outputs all share
-    that dense channels-last layout (skr_step_launch_channels_last); the `_hip.trace` entry is the same: the layout is read off the tensors."""
-    lib = load()
-    _no_rows_with_layout(layout)
-    trace = getattr(_hooks, "trace", None)
-    if trace is not None:
-        trace.append((plan, list(inputs), out0, out1, seeds, numel))
-    arr, stream = _operand_array(inputs), current_stream_ptr(device)
-    if layout is None:
-        check(step_launch_raw(plan, arr, _ptr(out0), _ptr(out1), _ptr(seeds), numel, stream), "skr_step_launch")
-    else:
-        status = lib.skr_step_launch_channels_last(ctypes.byref(plan), arr, _ptr(out0), _ptr(out1), _ptr(seeds), ctypes.byref(StepLayoutC(*layout)), numel, stream)
-        check(status, "skr_step_launch_channels_last")
+class FactorCall:
+    "the record of the statistics launch of rescaled guidance: no tuple and no plan, so nothing unpacks it as a step launch"
 
+    kind, layout = FACTOR, None
 
-def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device,
-                       layout: tuple[int, int] | None = None) -> None:
-    """one masked step launch (skr_step_launch_masked) on torch's current stream of `device`: out = m * (coef0 form + noise) + (1 - m) * (coef1 form).
-    A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, mask) -- a seventh entry no step program is built from.
-    Under the indexed-rows hook (captured loops with device-resident scalars) the launch is recorded, emitted as
-    skr_step_launch_masked_indexed[_per_sample] or refilled, as a plain step launch is (IndexedRows.launch).
-    With `layout` = (channels, plane) the operands and the output all share that dense channels-last layout
-    (skr_step_launch_masked_channels_last); `mask` stays contiguous, in logical order, and the trace entry is the same."""
-    lib = load()
-    _no_rows_with_layout(layout)
-    trace = getattr(_hooks, "trace", None)
-    if trace is not None:
-        trace.append((plan, list(operands), out, None, seeds, numel, mask))
-    arr, stream = _operand_array(operands), current_stream_ptr(device)
-    desc = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
-    if layout is not None:
-        status = lib.skr_step_launch_masked_channels_last(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), _ptr(seeds), ctypes.byref(StepLayoutC(*layout)), numel, stream)
-        check(status, "skr_step_launch_masked_channels_last")
-        return
-    rows = getattr(_hooks, "indexed", None)
-    if rows is not None:
-        status = rows.launch(lib, plan, arr, out.data_ptr(), None, _ptr(seeds), numel, stream, mask=desc)
-    else:
-        status = lib.skr_step_launch_masked(ctypes.byref(plan), arr, out.data_ptr(), ctypes.byref(desc), _ptr(seeds), numel, stream)
-    check(status, "skr_step_launch_masked")
-
-
-def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, scale: float, slot: int, seeds, numel: int, device: torch.device) -> None:
-    """one guided step launch (skr_step_launch_guided) on torch's current stream of `device`: operands[slot] is `uncond`, and the value
-    p = uncond + scale * (cond - uncond), rounded as torch's three tensor ops round it, takes its place in the step's sum; `guided_out`
-    (or None) receives p.  `out` None with a plan whose out0_dtype is NONE is the guidance-only form.
-    A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, cond, guided_out, scale, slot) -- ten entries no step program
-    is built from.  Under an indexed-rows hook created for a guided capture (IndexedRows(guided=True): capture_sampling_loop with
-    `guidance_scale`) the launch is recorded, emitted as skr_step_launch_guided_indexed[_per_sample] -- the scale a row value -- or
-    refilled, as a plain step launch is (IndexedRows.launch).  Under any other hook it raises: that loop was captured without guidance."""
-    lib = load()
-    rows = getattr(_hooks, "indexed", None)
-    if rows is not None and not getattr(rows, "guided", False):
-        raise SkrampleHipError("guided steps are not part of captured loops unless the loop is captured for them: pass guidance_scale= to capture_sampling_loop")
-    trace = getattr(_hooks, "trace", None)
-    if trace is not None:
-        trace.append((plan, list(operands), out, None, seeds, numel, cond, guided_out, scale, slot))
-    desc = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
-    arr, stream = _operand_array(operands), current_stream_ptr(device)
-    if rows is not None:
-        status = rows.launch(lib, plan, arr, _ptr(out), None, _ptr(seeds), numel, stream, guide=desc)
-    else:
-        status = lib.skr_step_launch_guided(ctypes.byref(plan), arr, _ptr(out), ctypes.byref(desc), _ptr(seeds), numel, stream)
-    check(status, "skr_step_launch_guided")
+    def __init__(self, uncond, cond, scale, sample_numel, factor, stats):
+        self.uncond, self.cond, self.scale, self.sample_numel, self.factor, self.stats = uncond, cond, scale, sample_numel, factor, stats
 
 
 NO_RESCALED_ROWS = ("rescaled guidance (guidance_rescale) has no row form in a loop captured without it: pass rescaled=True to capture_sampling_loop (guidance_rescale "
                     "is then a row value), capture the loop with indexed=False, which freezes guidance_rescale into the graph, or pass guidance_rescale=0.0")
 
 
-def launch_guidance_factor(uncond: torch.Tensor, cond: torch.Tensor, scale: float, sample_numel: int, factor: torch.Tensor, stats: "torch.Tensor | None" = None) -> None:
-    """the statistics launch of rescaled guidance (skr_guidance_rescale_factor) on torch's current stream: factor[s] = std(cond_s) / std(p_s)
-    per sample of `sample_numel` elements in storage order, rounded as torch rounds it; `stats` (float64[2 * samples] or None) receives
-    the two standard deviations.  The workspace comes from torch's allocator, which is safe under graph capture.
-    A `_hip.trace` list receives ("guidance_factor", uncond, cond, scale, sample_numel, factor, stats): no plan leads it, no step program
-    is built from it.  Under an indexed-rows hook created for a rescaled capture (IndexedRows(guided=True, rescaled=True)) it runs as it
-    stands while the hook records or refills, and is NOT issued while the hook emits: the step launch that follows emits the statistics
-    row launch itself, on the hook's buffers (IndexedRows._emit_rescaled).  Under any other hook it raises."""
+def launch_call(call: "StepCall | FactorCall", device: torch.device) -> None:
+    """THE launcher of the eager entry points: one launch on torch's current stream of `device`, from its record.  Refuses what the installed
+    indexed-rows hook was not created for, appends the record to a `_hip.trace` list, builds the descriptors, hands the launch to the hook
+    (IndexedRows.launch: recorded, emitted in its row form or refilled) or calls the direct / channels-last entry of the table, and checks
+    the status under that entry's name."""
     lib = load()
+    kind, layout = call.kind, call.layout
     rows = getattr(_hooks, "indexed", None)
-    if rows is not None and not getattr(rows, "rescaled", False):
-        raise SkrampleHipError(NO_RESCALED_ROWS)
+    if rows is not None:
+        if layout is not None:  # (the hook has no channels-last form: the caller takes the contiguous route while one is installed)
+            raise SkrampleHipError("captured loops with device-resident rows take contiguous operands")
+        if kind == "guided" and not getattr(rows, "guided", False):
+            raise SkrampleHipError("guided steps are not part of captured loops unless the loop is captured for them: pass guidance_scale= to capture_sampling_loop")
+        if kind in ("guided_rescaled", FACTOR) and not getattr(rows, "rescaled", False):
+            raise SkrampleHipError(NO_RESCALED_ROWS)
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
-        trace.append(("guidance_factor", uncond, cond, scale, sample_numel, factor, stats))
-    if rows is not None and rows.mode == "emit":
-        return
-    numel = uncond.numel()
-    partials = torch.empty(max(guidance_partials(numel, sample_numel), 1), dtype=torch.float64, device=uncond.device)
-    status = lib.skr_guidance_rescale_factor(uncond.data_ptr(), cond.data_ptr(), DTYPE_CODE[uncond.dtype], float(scale), numel, int(sample_numel), factor.data_ptr(),
-                                             _ptr(stats), partials.data_ptr(), current_stream_ptr(uncond.device))
-    check(status, "skr_guidance_rescale_factor")
+        trace.append(call)
+    form = "direct" if layout is None else "channels_last"
+    name = entry_name(kind, form)
+    if kind == FACTOR:
+        if rows is not None and rows.mode == "emit":  # (the step launch that follows emits the statistics row launch itself, on the hook's buffers)
+            return
+        numel = call.uncond.numel()  # (the workspace comes from torch's allocator, which is safe under graph capture)
+        partials = torch.empty(max(guidance_partials(numel, call.sample_numel), 1), dtype=torch.float64, device=device)
+        values = dict(uncond=call.uncond.data_ptr(), cond=call.cond.data_ptr(), dtype=DTYPE_CODE[call.uncond.dtype], scale=float(call.scale), numel=numel, sample_numel=int(call.sample_numel),
+                      factor=call.factor.data_ptr(), stats=_ptr(call.stats), partials=partials.data_ptr(), stream=current_stream_ptr(device))  # fmt: skip
+        return check(call_entry(lib, kind, form, values), name)
+    plan, inputs, out0, out1, seeds, numel = call
+    mask = StepMaskC(call.mask.data_ptr(), DTYPE_CODE[call.mask.dtype], 0, call.mask_numel, call.batch_stride) if call.mask is not None else None
+    guide = StepGuidanceC(call.cond.data_ptr(), _ptr(call.guided_out), float(call.scale), int(call.slot), 0) if call.cond is not None else None
+    rescale = StepRescaleC(call.factor.data_ptr(), float(call.phi), int(call.sample_numel), 0) if call.factor is not None else None
+    arr, stream = _operand_array(inputs), current_stream_ptr(device)
+    if rows is not None:
+        status = rows.launch(lib, plan, arr, _ptr(out0), _ptr(out1), _ptr(seeds), numel, stream, mask=mask, guide=guide, rescale=rescale)
+    else:
+        values = dict(plan=plan, operands=arr, out0=_ptr(out0), out1=_ptr(out1), mask=mask, guide=guide, rescale=rescale, seeds=_ptr(seeds),
+                      layout=StepLayoutC(*layout) if layout is not None else None, numel=numel, stream=stream)  # fmt: skip
+        status = call_entry(lib, kind, form, values)
+    check(status, name)
+
+
+def launch_step(plan: StepPlanC, inputs: list[torch.Tensor], out0, out1, seeds, numel: int, device: torch.device, layout: tuple[int, int] | None = None) -> None:
+    """one fused kernel launch (skr_step_launch).  With `layout` = (channels, plane) the operands and outputs all share that dense
+    channels-last layout (skr_step_launch_channels_last)."""
+    launch_call(StepCall(plan, inputs, out0, out1, seeds, numel, **({} if layout is None else {"layout": layout})), device)
+
+
+def launch_step_masked(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, mask: torch.Tensor, mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device,
+                       layout: tuple[int, int] | None = None) -> None:
+    """one masked step launch (skr_step_launch_masked): out = m * (coef0 form + noise) + (1 - m) * (coef1 form).  Under the indexed-rows
+    hook it is recorded, emitted as skr_step_launch_masked_indexed[_per_sample] or refilled, as a plain step launch is.  With `layout` the
+    operands and the output share that channels-last layout (skr_step_launch_masked_channels_last); `mask` stays contiguous, in logical order."""
+    launch_call(StepCall(plan, operands, out, None, seeds, numel, "masked", mask=mask, mask_numel=mask_numel, batch_stride=batch_stride, layout=layout), device)
+
+
+def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, scale: float, slot: int, seeds, numel: int, device: torch.device) -> None:
+    """one guided step launch (skr_step_launch_guided): operands[slot] is `uncond`, and the value p = uncond + scale * (cond - uncond),
+    rounded as torch's three tensor ops round it, takes its place in the step's sum; `guided_out` (or None) receives p.  `out` None with a
+    plan whose out0_dtype is NONE is the guidance-only form.  Under an indexed-rows hook created for a guided capture
+    (IndexedRows(guided=True): capture_sampling_loop with `guidance_scale`) the launch is recorded, emitted as
+    skr_step_launch_guided_indexed[_per_sample] -- the scale a row value -- or refilled.  Under any other hook it raises: that loop was
+    captured without guidance."""
+    launch_call(StepCall(plan, operands, out, None, seeds, numel, "guided", cond=cond, guided_out=guided_out, scale=scale, slot=slot), device)
+
+
+def launch_guidance_factor(uncond: torch.Tensor, cond: torch.Tensor, scale: float, sample_numel: int, factor: torch.Tensor, stats: "torch.Tensor | None" = None) -> None:
+    """the statistics launch of rescaled guidance (skr_guidance_rescale_factor): factor[s] = std(cond_s) / std(p_s) per sample of `sample_numel`
+    elements in storage order, rounded as torch rounds it; `stats` (float64[2 * samples] or None) receives the two standard deviations.
+    Under an indexed-rows hook created for a rescaled capture (IndexedRows(guided=True, rescaled=True)) it runs as it stands while the hook
+    records or refills, and is NOT issued while the hook emits.  Under any other hook it raises."""
+    launch_call(FactorCall(uncond, cond, scale, sample_numel, factor, stats), uncond.device)
 
 
 def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, scale: float, slot: int, factor: torch.Tensor, phi: float,
                                 sample_numel: int, seeds, numel: int, device: torch.device) -> None:
     """one rescaled guided step launch (skr_step_launch_guided_rescaled): launch_step_guided with the guided value p replaced by
     phi * (p * factor[sample]) + (1 - phi) * p, rounded as torch's four tensor ops round it; `guided_out` (or None) receives that value.
-    A `_hip.trace` list receives (plan, operands, out, None, seeds, numel, cond, guided_out, scale, slot, factor, phi, sample_numel) --
-    thirteen entries no step program is built from.  Under an indexed-rows hook created for a rescaled capture
-    (IndexedRows(guided=True, rescaled=True): capture_sampling_loop with `rescaled=True`) the launch is recorded, emitted as
-    skr_guidance_rescale_factor_indexed[_per_sample] plus skr_step_launch_guided_rescaled_indexed[_per_sample] -- scale and phi row values,
-    `factor` replaced by the hook's own -- or refilled (IndexedRows.launch).  Under any other hook it raises."""
-    lib = load()
-    rows = getattr(_hooks, "indexed", None)
-    if rows is not None and not getattr(rows, "rescaled", False):
-        raise SkrampleHipError(NO_RESCALED_ROWS)
-    trace = getattr(_hooks, "trace", None)
-    if trace is not None:
-        trace.append((plan, list(operands), out, None, seeds, numel, cond, guided_out, scale, slot, factor, phi, sample_numel))
-    desc = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
-    rescale = StepRescaleC(factor.data_ptr(), float(phi), int(sample_numel), 0)
-    arr, stream = _operand_array(operands), current_stream_ptr(device)
-    if rows is not None:
-        check(rows.launch(lib, plan, arr, _ptr(out), None, _ptr(seeds), numel, stream, guide=desc, rescale=rescale), "skr_step_launch_guided_rescaled")
-        return
-    status = lib.skr_step_launch_guided_rescaled(ctypes.byref(plan), arr, _ptr(out), ctypes.byref(desc), ctypes.byref(rescale), _ptr(seeds), numel, stream)
-    check(status, "skr_step_launch_guided_rescaled")
-
-
-def launch_step_masked_rolling_raw(plan: StepPlanC, arr, out_ptr, mask: StepMaskC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:
-    """one masked rolling step launch (skr_step_launch_masked_rolling) from raw pointers; returns the status code.  `arr`: the operand
-    pointer array, `mask`: its descriptor; the caller owns every check of the index (rolling.RollingBatch)."""
-    return load().skr_step_launch_masked_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(mask), seeds_ptr, numel, rows_ptr, sample_index_ptr, row_offset, stream_ptr)
-
-
-def launch_step_guided_rolling_raw(plan: StepPlanC, arr, out_ptr, guide: StepGuidanceC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr, row_offset: int, stream_ptr) -> int:
-    """one guided rolling step launch (skr_step_launch_guided_rolling) from raw pointers; returns the status code.  `arr`: the operand
-    pointer array, `guide`: its descriptor (cond, guided_out or NULL, slot; the scale is each sample's row value); the caller owns every
-    check of the index (rolling.RollingBatch)."""
-    return load().skr_step_launch_guided_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), seeds_ptr, numel, rows_ptr, sample_index_ptr, row_offset, stream_ptr)
-
-
-def launch_guidance_factor_rolling_raw(uncond_ptr, cond_ptr, dtype_code: int, numel: int, sample_numel: int, rows_ptr, sample_index_ptr, row_offset: int, factor_ptr, stats_ptr,
-                                       partials_ptr, stream_ptr) -> int:
-    """the statistics launch of a rescaled guided rolling batch (skr_guidance_rescale_factor_rolling) from raw pointers; returns the status
-    code.  Scale and phi are each sample's row values (convert_k[0], convert_k[1]); inactive samples and samples whose phi is zero are
-    skipped, their factor left alone.  `stats_ptr` may be None; the caller owns the partials workspace and every check of the index."""
-    return load().skr_guidance_rescale_factor_rolling(uncond_ptr, cond_ptr, dtype_code, numel, sample_numel, rows_ptr, sample_index_ptr, row_offset, factor_ptr, stats_ptr,
-                                                      partials_ptr, stream_ptr)
-
-
-def launch_step_guided_rescaled_rolling_raw(plan: StepPlanC, arr, out_ptr, guide: StepGuidanceC, rescale: StepRescaleC, seeds_ptr, numel: int, rows_ptr, sample_index_ptr,
-                                            row_offset: int, stream_ptr) -> int:
-    """one rescaled guided rolling step launch (skr_step_launch_guided_rescaled_rolling) from raw pointers; returns the status code.
-    `guide` as in launch_step_guided_rolling_raw; `rescale`: the factor tensor the statistics launch wrote and the sample size (its phi is
-    ignored: each sample's is its row's convert_k[1]); the caller owns every check of the index (rolling.RollingBatch)."""
-    return load().skr_step_launch_guided_rescaled_rolling(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), ctypes.byref(rescale), seeds_ptr, numel, rows_ptr,
-                                                          sample_index_ptr, row_offset, stream_ptr)
+    Under an indexed-rows hook created for a rescaled capture (capture_sampling_loop with `rescaled=True`) the launch is recorded, emitted
+    as skr_guidance_rescale_factor_indexed[_per_sample] plus skr_step_launch_guided_rescaled_indexed[_per_sample] -- scale and phi row
+    values, `factor` replaced by the hook's own -- or refilled (IndexedRows.launch).  Under any other hook it raises."""
+    launch_call(StepCall(plan, operands, out, None, seeds, numel, "guided_rescaled", cond=cond, guided_out=guided_out, scale=scale, slot=slot, factor=factor, phi=phi,
+                         sample_numel=sample_numel), device)  # fmt: skip

@@ -315,6 +315,7 @@ class RollingBatch:
             self.position_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
             self.length_dev = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
             self.times_dev = torch.zeros(self.capacity * self.max_steps, dtype=torch.float32, device=self.device)
+        self._fixed = self._fixed_arguments()
 
     def _init_noise(self, first) -> bool:
         "a wrapper whose sampler draws: False for `Random` (drawn in the step kernel), True for a generator the batch draws per slot, or the refusal"
@@ -400,11 +401,10 @@ class RollingBatch:
     def _trace(self, wrapper, steps: int, seed: int | None) -> list[tuple[StepPlanC, list[Role], float]]:
         """Dry run of `wrapper` for `steps` steps on one sample: (plan, operand roles, timestep) of every step's single launch.
         Coefficients depend on the schedule and the step alone, never on tensor contents, so the model outputs are zeros.
-        A wrapper with `set_inpaint` in force (a masked batch's in-painting request) must issue masked launches -- the seven-entry
-        trace tuple of `_hip.launch_step_masked` -- and one without it plain ones.  A guided batch steps the wrapper with
-        `step_guided(uncond, cond, 1.0, ...)` and must see the ten-entry tuple of `_hip.launch_step_guided`: `uncond` is the operand of
-        role ("o",) -- the launch's `slot` --, `cond` and `guided_out` are not operands, and the history operands are the wrapper's
-        stored guided predictions, role ("po", k)."""
+        A wrapper with `set_inpaint` in force (a masked batch's in-painting request) must issue masked launches -- a `_hip.StepCall`
+        of kind "masked" -- and one without it plain ones.  A guided batch steps the wrapper with `step_guided(uncond, cond, 1.0, ...)`
+        and must see one of kind "guided": `uncond` is the operand of role ("o",) -- the call's `slot` --, `cond` and `guided_out` are
+        not operands, and the history operands are the wrapper's stored guided predictions, role ("po", k)."""
         inpaint = getattr(wrapper, "_inpaint", None)
         if inpaint is not None and not self.masked:
             raise SkrampleHipError("this wrapper has set_inpaint in force and the batch was built without inpaint_mask_shape")
@@ -441,11 +441,12 @@ class RollingBatch:
                 _hip.trace = held
             if len(launches) != 1:
                 raise SkrampleHipError(f"a step of this wrapper is {len(launches)} launches, not one fused launch: it cannot join a rolling batch")
-            if self.guided and len(launches[0]) != 10:
+            call = launches[0]
+            if self.guided and call.kind != "guided":
                 raise SkrampleHipError("a guided step of this wrapper is not one fused guided launch: it cannot join a guided rolling batch")
-            if (len(launches[0]) == 7) != (inpaint is not None):
+            if (call.kind == "masked") != (inpaint is not None):
                 raise SkrampleHipError("a step of this wrapper is not the masked launch its in-painting asks for" if inpaint is not None else "a step of this wrapper is a masked launch although no in-painting is set")
-            plan, inputs = StepPlanC.from_buffer_copy(launches[0][0]), launches[0][1]
+            plan, inputs = StepPlanC.from_buffer_copy(call.plan), call.inputs
             known[x.data_ptr()], known[out.data_ptr()] = ("x",), ("o",)
             if inpaint is not None:
                 known[inpaint[1].data_ptr()], known[inpaint[2].data_ptr()] = ("orig",), ("znoise",)
@@ -454,40 +455,49 @@ class RollingBatch:
             roles = [known.get(tensor.data_ptr()) for tensor in inputs]
             if any(r is None for r in roles):
                 raise SkrampleHipError("a step of this wrapper reads a temporary tensor (a cast, a copy, realised noise): it cannot join a rolling batch")
-            if self.guided and (launches[0][1][launches[0][9]] is not out or roles.count(("o",)) != 1):
+            if self.guided and (inputs[call.slot] is not out or roles.count(("o",)) != 1):
                 raise SkrampleHipError("the guided launch of this wrapper does not replace its `uncond` operand: it cannot join a guided rolling batch")
             found.append((plan, roles, float(t)))
             x = new
         torch.cuda.synchronize(self.device)
         return found
 
-    def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None, cond: torch.Tensor | None = None, guided_out: torch.Tensor | None = None) -> None:
-        if self.guided:  # (one output; `cond` and `guided_out` -- None: not stored -- are launch arguments, the scale each slot's row value)
-            guide = StepGuidanceC(cond.data_ptr(), guided_out.data_ptr() if guided_out is not None else None, 0.0, self.slot, 0)
-            if self.rescaled:  # (the statistics launch, then the step launch: same stream, same index, same rows, same row_offset)
-                rows, index, stream = self.rows_dev.data_ptr(), self.index_dev.data_ptr(), _hip.current_stream_ptr(self.device)
-                status = _hip.launch_guidance_factor_rolling_raw(arr[self.slot], cond.data_ptr(), _hip.DTYPE_CODE[self.dtype], self.numel, self.sample_numel, rows, index, 0,
-                                                                 self.factor.data_ptr(), None, self._partials.data_ptr(), stream)  # fmt: skip
-                _hip.check(status, "skr_guidance_rescale_factor_rolling")
-                status = _hip.launch_step_guided_rescaled_rolling_raw(self.plan, arr, out0.data_ptr(), guide, self._rescale_desc, self.seeds_dev.data_ptr() if self.draws_noise else None,
-                                                                      self.numel, rows, index, 0, stream)  # fmt: skip
-                _hip.check(status, "skr_step_launch_guided_rescaled_rolling")
-                return
-            status = _hip.launch_step_guided_rolling_raw(self.plan, arr, out0.data_ptr(), guide, self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel,
-                                                         self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0, _hip.current_stream_ptr(self.device))  # fmt: skip
-            _hip.check(status, "skr_step_launch_guided_rolling")
-            return
+    def _fixed_arguments(self) -> list:
+        """Per batch, once: [(C entry name, its arguments laid out by the launch table, name -> position of those a tick fills in)] of the
+        tick's launches -- the statistics launch of a rescaled batch, then the step launch.  Everything else in them is the batch's own --
+        plan, descriptors, and the addresses of rows_dev, index_dev, seeds_dev, factor and _partials, which are allocated in __init__ and
+        never reassigned."""
+        kind = "guided_rescaled" if self.rescaled else "guided" if self.guided else "masked" if self.masked else "plain"
+        # structured noise is an operand, drawn by a launch of its own: no seeds (masked and guided batches refuse structured noise when built)
+        seeds = self.seeds_dev.data_ptr() if self.draws_noise and not self.structured else None
+        values = dict(plan=self.plan, seeds=seeds, numel=self.numel, rows=self.rows_dev.data_ptr(), index=self.index_dev.data_ptr(), row_offset=0,
+                      operands=None, out0=None, out1=None, stream=None, uncond=None, cond=None, guide=StepGuidanceC())  # fmt: skip
         if self.masked:  # (one output: a masked step is one single-output launch)
-            status = _hip.launch_step_masked_rolling_raw(self.plan, arr, out0.data_ptr(), self._mask_desc, self.seeds_dev.data_ptr() if self.draws_noise else None, self.numel,
-                                                         self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0, _hip.current_stream_ptr(self.device))  # fmt: skip
-            _hip.check(status, "skr_step_launch_masked_rolling")
-            return
-        lib = _hip.load()
-        status = lib.skr_step_launch_rolling(ctypes.byref(self.plan), arr, out0.data_ptr() if out0 is not None else None, out1.data_ptr() if out1 is not None else None,
-                                             self.seeds_dev.data_ptr() if self.draws_noise and not self.structured else None, self.numel, self.rows_dev.data_ptr(),
-                                             self.index_dev.data_ptr(), 0,
-                                             _hip.current_stream_ptr(self.device))  # fmt: skip
-        _hip.check(status, "skr_step_launch_rolling")
+            values["mask"] = self._mask_desc
+        if self.rescaled:  # (the statistics launch reads the same index, rows and row_offset, and writes the factor the step's descriptor names)
+            values.update(rescale=self._rescale_desc, dtype=_hip.DTYPE_CODE[self.dtype], sample_numel=self.sample_numel, factor=self.factor.data_ptr(), stats=None,
+                          partials=self._partials.data_ptr())  # fmt: skip
+        launches = []
+        for each in (_hip.FACTOR, kind) if self.rescaled else (kind,):
+            name, names = _hip.ENTRIES[each, "rolling"]
+            launches.append((name, _hip.entry_args(each, "rolling", **values), {n: i for i, n in enumerate(names)}))
+        return launches
+
+    def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None, cond: torch.Tensor | None = None, guided_out: torch.Tensor | None = None) -> None:
+        """the tick's step launch through the rolling form of the launch table (_hip.ENTRIES); a rescaled batch: behind the statistics
+        launch, on the same stream.  Only what changes from tick to tick is filled in."""
+        lib, stream = _hip.load(), _hip.current_stream_ptr(self.device)
+        given = {"operands": arr, "out0": _hip._ptr(out0), "out1": _hip._ptr(out1), "stream": stream}
+        if self.guided:  # (one output; `cond` and `guided_out` -- None: not stored -- are launch arguments, the scale each slot's row value)
+            given["guide"] = ctypes.byref(StepGuidanceC(cond.data_ptr(), _hip._ptr(guided_out), 0.0, self.slot, 0))
+            if self.rescaled:  # (what the statistics launch reads)
+                given["uncond"], given["cond"] = arr[self.slot], cond.data_ptr()
+        for name, fixed, at in self._fixed:
+            args = list(fixed)
+            for what, value in given.items():
+                if what in at:
+                    args[at[what]] = value
+            _hip.check(getattr(lib, name)(*args), name)
 
     def _draw(self, out: torch.Tensor) -> None:
         "a structured-noise batch: ONE launch of the generator's rolling entry draws, into `out`, every slot the index on the device names"
@@ -533,12 +543,11 @@ class RollingBatch:
             wide.noise_mode = 1
         if self.dtype == torch.float32 and wide.out0_dtype != _hip.NONE and wide.out1_dtype != _hip.NONE:
             raise SkrampleHipError("skr_step_launch_rolling: request outside kernel coverage (the two-output table kernels take 16-bit operands)")
-        if self.masked and (wide.out0_dtype == _hip.NONE or wide.out1_dtype != _hip.NONE or wide.acc_f64 or wide.n_group_a != wide.n_terms
-                            or wide.dtype_a != wide.out0_dtype or wide.dtype_a != _hip.DTYPE_CODE[self.dtype]):  # fmt: skip
+        # (the batch's dtype is a 16- or 32-bit one: _init_inpaint and _refuse_guided have seen to it)
+        if self.masked and not _hip.one_group_launch(wide, _hip.DTYPE_CODE[self.dtype]):
             raise SkrampleHipError("skr_step_launch_masked_rolling: request outside kernel coverage (one single-output launch of one 16- or 32-bit dtype, evaluated in float32)")
         if self.guided:
-            if (wide.out0_dtype == _hip.NONE or wide.out1_dtype != _hip.NONE or wide.acc_f64 or wide.n_group_a != wide.n_terms or wide.convert_to or wide.convert_from
-                    or wide.dtype_a != wide.out0_dtype or wide.dtype_a != _hip.DTYPE_CODE[self.dtype]):  # fmt: skip
+            if not _hip.one_group_launch(wide, _hip.DTYPE_CODE[self.dtype]) or wide.convert_to or wide.convert_from:
                 raise SkrampleHipError("skr_step_launch_guided_rolling: request outside kernel coverage (one single-output launch of one 16- or 32-bit dtype, evaluated in float32)")
             if roles.count(("o",)) != 1:
                 raise SkrampleHipError("the guided launch structure has no single `uncond` operand for the guided value to replace")
@@ -552,11 +561,11 @@ class RollingBatch:
         for step, (plan, roles, _) in enumerate(traced):
             if (plan.dtype_a, plan.acc_f64, plan.convert_to, plan.convert_from) != (self.plan.dtype_a, self.plan.acc_f64, self.plan.convert_to, self.plan.convert_from):
                 raise SkrampleHipError("a step of this request differs in dtype or conversion from the batch's launch structure")
-            if self.masked and (plan.out0_dtype != self.plan.out0_dtype or plan.out1_dtype != _hip.NONE or plan.n_group_a != plan.n_terms):
+            if self.masked and not _hip.one_group_launch(plan):  # (dtype and arithmetic are the batch's by the check above)
                 raise SkrampleHipError("a step of this request is not one single-output launch of the masked batch's dtype")
             row = place_row(self.roles, plan, roles, self.two_outputs)
             if self.guided:
-                if plan.out0_dtype != self.plan.out0_dtype or plan.out1_dtype != _hip.NONE or plan.n_group_a != plan.n_terms or list(roles).count(("o",)) != 1:
+                if not _hip.one_group_launch(plan) or list(roles).count(("o",)) != 1:
                     raise SkrampleHipError("a step of this request is not one single-output guided launch of the batch's dtype with one `uncond` operand")
                 if row.coef0[self.slot] != plan.coef0[list(roles).index(("o",))]:  # (place_row put `uncond` where the batch's launches replace it)
                     raise SkrampleHipError(f"the `uncond` operand of this step is not at the batch's slot {self.slot}")
@@ -589,16 +598,22 @@ class RollingBatch:
         owned = self._x[:-1] + list(self._state) + [self._blank] + (list(self._n) if self.structured else []) + list(self._g)
         return owned + ([] if self.alias_history else list(self._outputs))
 
-    def index_vector(self) -> list[int]:
-        "host: the row every slot reads this tick, -1 for a free or finished slot (validated: nothing outside a slot's own run)"
-        out = []
+    def _running(self) -> list[tuple[int, _Request]]:
+        "host: (slot, request) of every active slot, validated -- nothing outside a slot's own run; THE scan every tick starts with"
+        live, finished, max_steps = [], self._finished, self.max_steps
         for b, req in enumerate(self._requests):
-            if req is None or b in self._finished:
-                out.append(-1)
+            if req is None or b in finished:
                 continue
-            if not 0 <= req.position < len(req.rows) <= self.max_steps:
+            if not 0 <= req.position < len(req.rows) <= max_steps:
                 raise ValueError(f"slot {b} is at position {req.position} of a run of {len(req.rows)} steps")
-            out.append(b * self.max_steps + req.position)
+            live.append((b, req))
+        return live
+
+    def index_vector(self, live: list | None = None) -> list[int]:
+        "host: the row every slot reads this tick, -1 for a free or finished slot (validated: nothing outside a slot's own run)"
+        out, max_steps = [-1] * self.capacity, self.max_steps
+        for b, req in self._running() if live is None else live:
+            out[b] = b * max_steps + req.position
         return out
 
     def admit(self, slot: int, latents: torch.Tensor, wrapper, steps: int, seed: int | None = None, inpaint: Sequence[torch.Tensor] | None = None,
@@ -735,91 +750,86 @@ class RollingBatch:
             if ptr == model_output.data_ptr():
                 raise SkrampleHipError(ALIAS_HELP.format(what="its buffer now holds this tick's model output"))
 
-    def _bind(self, role: Role, model_output: torch.Tensor) -> torch.Tensor:
-        kind = role[0]
+    def _bind(self, role: Role, model_output: torch.Tensor, p: int = 0, outputs: Sequence[torch.Tensor] | None = None) -> torch.Tensor:
+        """THE rule that turns a role into a tensor, for the eager tick (p = 0) and for phase p of CapturedTicks alike.  Every ring is read
+        as it stands BEFORE the tick's rotation (_ticked), oldest first, p rotations on: the tick reads its latents from _x[P - 1 + p]
+        and writes its results into entry p of every ring -- new latents, new state, this tick's draw, this tick's guided prediction --
+        and the entry of -k ticks ago lies k places before either.  `outputs` (CapturedTicks): the graphs' static outputs, the
+        model-output ring there; None: the caller's last model outputs, or `_blank` for one no tick has produced yet."""
+        kind, P = role[0], len(self._x)
         if kind == "x":
-            return self._x[-1]
+            return self._x[(P - 1 + p) % P]
         if kind == "o":
             return model_output
         if kind == "none":
             return self._blank
-        if kind in ("orig", "znoise") and self.masked:
+        if kind in ("orig", "znoise") and self.masked:  # the batch's own in-paint tensors: the same in every phase
             return self.original if kind == "orig" else self.noise
-        if kind in ("n", "pn") and self.structured:  # (bound after this tick's rotation: [-1] is the tensor this tick draws into)
-            return self._n[-1] if kind == "n" else self._n[(role[1] - 1) % len(self._n)]
+        if kind in ("n", "pn") and self.structured:
+            return self._n[(p + (role[1] if kind == "pn" else 0)) % len(self._n)]
         if len(role) < 2:
             raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
         k = role[1]
         if kind == "pi":
-            return self._x[k - 1]
+            return self._x[(P - 1 + p + k) % P]
         if kind == "px":
-            return self._state[k]
-        if kind == "po" and self.guided:  # (bound after this tick's rotation: [-1] is the tensor this tick's launch stores into)
-            return self._g[k - 1]
+            return self._state[(p + k) % P]
+        if kind == "po" and self.guided:  # the batch's own guided prediction of -k ticks ago
+            return self._g[(p + k) % P]
+        if kind == "po" and outputs is not None:  # the static output of the graph replayed -k ticks ago
+            return outputs[(p + k) % P]
         if kind == "po":
             return self._outputs[k] if -k <= len(self._outputs) else self._blank
         raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
+
+    def _operands(self, model_output: torch.Tensor, p: int = 0, outputs: Sequence[torch.Tensor] | None = None) -> tuple:
+        "(operand pointer array, out0, out1) of the step launch of the eager tick, or of phase p: entry p of the rings takes the results"
+        bind = self._bind
+        arr = (ctypes.c_void_p * max(len(self.roles), 1))(*[bind(role, model_output, p, outputs).data_ptr() for role in self.roles])
+        new_x = self._x[p]  # the oldest entries take this tick's results: no operand of the structure reaches that far back
+        if self.two_outputs:
+            return arr, self._state[p], new_x
+        return (arr, new_x, None) if self.plan.out0_dtype != _hip.NONE else (arr, None, new_x)
+
+    def _tick_begins(self, what: str, **tensors: torch.Tensor) -> list:
+        "the refusals shared by step() and step_guided(), in their order; returns this tick's active (slot, request) pairs"
+        if self._captured is not None:
+            raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
+        live = self._running()
+        if not live:
+            raise ValueError(f"no active slot: admit() a request before {what}()")
+        if self.device_positions and not self._advanced:
+            raise ValueError(f"device-resident positions: advance() publishes this tick's index and timesteps; call it before the network and {what}()")
+        for name, t in tensors.items():
+            if tuple(t.shape) != tuple(self._x[-1].shape) or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} of a tick is a contiguous {tuple(self._x[-1].shape)} {self.dtype} tensor on {self.device}")
+        return live
+
+    def _publish(self, live: list) -> None:
+        "host-published positions: one small stream-ordered copy of this tick's index, ahead of every launch of the tick"
+        if not self.device_positions:
+            self.index_dev.copy_(torch.tensor(self.index_vector(live), dtype=torch.int32))
 
     def step(self, model_output: torch.Tensor) -> list[int]:
         "advance every active slot by one step of its own run with ONE launch; returns the slots that finished with this tick"
         if self.guided:
             raise ValueError("this batch was built with guided=True: a tick is step_guided(uncond, cond), the guided prediction is formed inside its launch")
-        if self._captured is not None:
-            raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
-        index = self.index_vector()
-        if all(i < 0 for i in index):
-            raise ValueError("no active slot: admit() a request before step()")
-        if self.device_positions and not self._advanced:
-            raise ValueError("device-resident positions: advance() publishes this tick's index and timesteps; call it before the network and step()")
-        if tuple(model_output.shape) != tuple(self._x[-1].shape) or model_output.dtype != self.dtype or model_output.device != self.device or not model_output.is_contiguous():
-            raise ValueError(f"the model output of a tick is a contiguous {tuple(self._x[-1].shape)} {self.dtype} tensor on {self.device}")
+        live = self._tick_begins("step", **{"the model output": model_output})
         if self.alias_history:
             self._guard(model_output)
         elif self.keep:
             model_output = model_output.clone()
+        self._publish(live)
         if self.structured:
-            self._n.append(self._n.pop(0))  # the oldest draw's tensor takes this tick's
-        operands = [self._bind(role, model_output) for role in self.roles]
-        if not self.device_positions:
-            self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
-        if self.structured:
-            self._draw(self._n[-1])  # behind the index, ahead of the step launch that reads it
-        arr = (ctypes.c_void_p * max(len(operands), 1))(*[t.data_ptr() for t in operands])
-        # the oldest ring entries take this tick's results: no operand of the structure reaches that far back
-        new_x = self._x.pop(0)
-        new_state = self._state.pop(0) if self.two_outputs else None
-        if self.two_outputs:
-            self._launch(arr, new_state, new_x)
-            self._state.append(new_state)
-        elif self.plan.out0_dtype != _hip.NONE:
-            self._launch(arr, new_x, None)
-        else:
-            self._launch(arr, None, new_x)
-        self._x.append(new_x)
+            self._draw(self._n[0])  # behind the index, ahead of the step launch that reads it: the oldest draw's tensor takes this tick's
+        self._launch(*self._operands(model_output))
         if self.keep:
             self._outputs.append(model_output)
             del self._outputs[: max(len(self._outputs) - self.keep, 0)]
             if self.alias_history:
                 self._stamps.append((model_output, model_output.data_ptr(), model_output._version))
                 del self._stamps[: max(len(self._stamps) - self.keep, 0)]
-        self.ticks += 1
-        self._advanced = False
-        done = []
-        for b, i in enumerate(index):
-            if i < 0:
-                continue
-            req = self._requests[b]
-            req.position += 1
-            if req.position == len(req.rows):
-                done.append(b)
-                self._finished.add(b)
-                self._results[b] = new_x[b].clone()
-            elif not self.device_positions:
-                self._times_host[b] = req.times[req.position]
-        # (the slices of free slots are not touched, by the kernel or here: they hold what an older tick left there)
-        if not self.device_positions:
-            self.timesteps.copy_(self._times_host)
-        return done
+        return self._ticked(live)
 
     def step_guided(self, uncond: torch.Tensor, cond: torch.Tensor) -> list[int]:
         """A tick of a guided batch: ONE skr_step_launch_guided_rolling forms every active slot's guided prediction
@@ -829,43 +839,31 @@ class RollingBatch:
         both halves: cond - uncond is exactly 0 and the guided prediction is uncond (for finite values), whatever its scale."""
         if not self.guided:
             raise ValueError("step_guided() needs a batch built with guided=True: this one steps with step(model_output)")
-        if self._captured is not None:
-            raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
-        index = self.index_vector()
-        if all(i < 0 for i in index):
-            raise ValueError("no active slot: admit() a request before step_guided()")
-        if self.device_positions and not self._advanced:
-            raise ValueError("device-resident positions: advance() publishes this tick's index and timesteps; call it before the network and step_guided()")
-        for name, t in (("uncond", uncond), ("cond", cond)):
-            if tuple(t.shape) != tuple(self._x[-1].shape) or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"{name} of a tick is a contiguous {tuple(self._x[-1].shape)} {self.dtype} tensor on {self.device}")
-        if self._g:
-            self._g.append(self._g.pop(0))  # the oldest guided prediction's tensor takes this tick's: no operand of the structure reaches that far back
-        operands = [self._bind(role, uncond) for role in self.roles]
-        if not self.device_positions:
-            self.index_dev.copy_(torch.tensor(index, dtype=torch.int32))  # one small stream-ordered copy, ahead of the launch
-        arr = (ctypes.c_void_p * max(len(operands), 1))(*[t.data_ptr() for t in operands])
-        new_x = self._x.pop(0)
-        self._launch(arr, new_x, None, cond, self._g[-1] if self._g else None)
-        self._x.append(new_x)
-        return self._ticked(index, new_x)
+        live = self._tick_begins("step_guided", uncond=uncond, cond=cond)
+        self._publish(live)
+        self._launch(*self._operands(uncond), cond, self._g[0] if self._g else None)  # (the oldest guided prediction's tensor takes this tick's)
+        return self._ticked(live)
 
-    def _ticked(self, index: list, new_x: torch.Tensor) -> list[int]:
-        "the host bookkeeping behind a guided tick's launch: positions, finished slots, the next timesteps"
+    def _ticked(self, live: list) -> list[int]:
+        """THE host bookkeeping behind a tick's launches, for step(), step_guided() and CapturedTicks.tick(): every ring rotates -- the oldest
+        entry, which took this tick's result, becomes the newest, so that `latents` is where admit() must write --, then positions, finished
+        slots, the result clones and the next timesteps"""
+        for ring in (self._x, self._state, self._n if self.structured else (), self._g):
+            if ring:
+                ring.append(ring.pop(0))
+        new_x = self._x[-1]
         self.ticks += 1
         self._advanced = False
-        done = []
-        for b, i in enumerate(index):
-            if i < 0:
-                continue
-            req = self._requests[b]
+        done, on_host = [], not self.device_positions
+        for b, req in live:
             req.position += 1
             if req.position == len(req.rows):
                 done.append(b)
                 self._finished.add(b)
                 self._results[b] = new_x[b].clone()
-            elif not self.device_positions:
+            elif on_host:
                 self._times_host[b] = req.times[req.position]
+        # (the slices of free slots are not touched, by the kernel or here: they hold what an older tick left there)
         if not self.device_positions:
             self.timesteps.copy_(self._times_host)
         return done
@@ -880,7 +878,7 @@ class RollingBatch:
             raise ValueError("this batch's ticks are captured: the rings' phase belongs to CapturedTicks.tick()")
         if self._advanced:
             raise ValueError("advance() ran for this tick already: step() comes next")
-        if all(i < 0 for i in self.index_vector()):
+        if not self._running():
             raise ValueError("no active slot: admit() a request before advance()")
         self._advance()
         self._advanced = True
@@ -949,87 +947,26 @@ class CapturedTicks:
         self.replays = [0] * P
 
     def _bind_phases(self) -> None:
-        "the operand arrays and outputs of every phase's step launch, and the tensor its draw goes to, from the rings as they stand and the graphs' outputs"
-        batch, P = self.batch, self.phases
-        x_ring, state_ring = list(batch._x), list(batch._state)
-        latents = [x_ring[(P - 1 + p) % P] for p in range(P)]
-        # a structured-noise batch: the tick of phase p draws into n_ring[p mod its length] -- one tensor, or a ring of P (the eager rotation of step())
-        n_ring = list(batch._n) if batch.structured else []
-        self._draws = [n_ring[p % len(n_ring)] for p in range(P)] if batch.structured else None
-        # a guided batch: the tick of phase p stores its guided prediction into g_ring[p] (the eager rotation of step_guided()); Euler stores none
-        g_ring = list(batch._g) if batch.guided else []
-        self._guides = [(self.conds[p], g_ring[p] if g_ring else None) for p in range(P)] if batch.guided else None
-        self._launches = []  # per phase: (operand pointers, out0, out1, the tensor that holds the tick's new latents)
-        for p in range(P):
-            ptrs = []
-            for role in batch.roles:
-                kind = role[0]
-                if kind == "x":
-                    t = latents[p]
-                elif kind == "o":
-                    t = self.outputs[p]
-                elif kind == "none":
-                    t = batch._blank
-                elif kind in ("orig", "znoise") and batch.masked:  # the batch's own in-paint tensors: the same in every phase
-                    t = batch.original if kind == "orig" else batch.noise
-                elif kind in ("n", "pn") and batch.structured:  # phase p draws into n_ring[p]; the draw of -k ticks ago is k places before it
-                    t = n_ring[(p + (role[1] if kind == "pn" else 0)) % len(n_ring)]
-                elif kind == "pi":  # the latents of -k ticks ago
-                    t = x_ring[(P - 1 + p + role[1]) % P]
-                elif kind == "px":
-                    t = state_ring[(p + role[1]) % P]
-                elif kind == "po" and batch.guided:  # the batch's own guided prediction of -k ticks ago: k places before this phase's
-                    t = g_ring[(p + role[1]) % P]
-                elif kind == "po":  # the static output of the graph replayed -k ticks ago
-                    t = self.outputs[(p + role[1]) % P]
-                else:
-                    raise SkrampleHipError(f"operand role {role} is not one a rolling batch binds (noise tensors of a batch built without structured noise, or an unknown role)")
-                ptrs.append(t.data_ptr())
-            arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
-            new_x = x_ring[p]
-            if batch.two_outputs:
-                self._launches.append((arr, state_ring[p], new_x, new_x))
-            elif batch.plan.out0_dtype != _hip.NONE:
-                self._launches.append((arr, new_x, None, new_x))
-            else:
-                self._launches.append((arr, None, new_x, new_x))
+        """the step launch of every phase -- (operand pointers, out0, out1) --, the tensor its draw goes to and its guided arguments, from the
+        rings as they stand and the graphs' outputs: RollingBatch._bind, the eager tick's rule, p rotations on"""
+        batch, phases = self.batch, range(self.phases)
+        self._launches = [batch._operands(self.outputs[p], p, self.outputs) for p in phases]
+        # a structured-noise batch: the tick of phase p draws into entry p of the noise ring -- one tensor, or a ring of P
+        self._draws = [batch._bind(("n",), None, p) for p in phases] if batch.structured else None
+        # a guided batch: the tick of phase p stores its guided prediction into entry p of that ring; Euler stores none
+        self._guides = [(self.conds[p], batch._g[p] if batch._g else None) for p in phases] if batch.guided else None
 
     def tick(self) -> list[int]:
         "one graph replay (advance + network), the draw of a structured-noise batch, and ONE step launch; returns the slots that finished with this tick"
         batch = self.batch
-        live = []
-        for b, req in enumerate(batch._requests):
-            if req is None or b in batch._finished:
-                continue
-            if not 0 <= req.position < len(req.rows) <= batch.max_steps:  # (as index_vector(): before anything is enqueued)
-                raise ValueError(f"slot {b} is at position {req.position} of a run of {len(req.rows)} steps")
-            live.append((b, req))
+        live = batch._running()  # (validated before anything is enqueued)
         if not live:
             raise ValueError("no active slot: admit() a request before tick()")
         phase = self.ticks % self.phases
-        arr, out0, out1, new_x = self._launches[phase]
         self.graphs[phase].replay()
         if self._draws is not None:  # eager like the step launch, between the advance (in the graph) and the step that reads the draw
             batch._draw(self._draws[phase])
-            batch._n.append(batch._n.pop(0))
-        if self._guides is not None:
-            batch._launch(arr, out0, out1, *self._guides[phase])
-            if batch._g:
-                batch._g.append(batch._g.pop(0))
-        else:
-            batch._launch(arr, out0, out1)
-        # the batch's rings follow, so that `latents` is where admit() must write
-        batch._x.append(batch._x.pop(0))
-        if batch.two_outputs:
-            batch._state.append(batch._state.pop(0))
+        batch._launch(*self._launches[phase], *(self._guides[phase] if self._guides is not None else ()))
         self.replays[phase] += 1
         self.ticks += 1
-        batch.ticks += 1
-        done = []
-        for b, req in live:
-            req.position += 1
-            if req.position == len(req.rows):
-                done.append(b)
-                batch._finished.add(b)
-                batch._results[b] = new_x[b].clone()
-        return done
+        return batch._ticked(live)  # the batch's rings follow the phase

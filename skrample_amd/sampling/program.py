@@ -172,7 +172,7 @@ class StepProgram:
             arr[i] = ops[i].data_ptr()
         lib = _hip.load()
         if _hip.trace is not None:
-            _hip.trace.append((plan, ops, out0, out1, None, self.numel))
+            _hip.trace.append(_hip.StepCall(plan, ops, out0, out1, None, self.numel, layout=self.layout))
         if self.layout is not None:
             desc = _hip.StepLayoutC(*self.layout)
             status = lib.skr_step_launch_channels_last(ctypes.byref(plan), arr, out0.data_ptr(), out1.data_ptr() if out1 is not None else None, seeds_ptr,

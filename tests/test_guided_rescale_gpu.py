@@ -340,9 +340,9 @@ def twins(sampler, dev, launches, phi_at=lambda i: PHI, prepare=lambda w: None, 
             finally:
                 _hip.trace = None
             if launches is not None and phi != 0.0:
-                assert [e[0] == "guidance_factor" for e in trace] == [True] + [False] * launches and len(trace[1]) == 13, (i, [len(e) for e in trace])
+                assert [e.kind == "guidance_factor" for e in trace] == [True] + [False] * launches and trace[1].kind == "guided_rescaled", (i, [e.kind for e in trace])
             elif launches is not None:
-                assert len(trace) == launches and all(len(e) != 13 and e[0] != "guidance_factor" for e in trace), (i, [len(e) for e in trace])
+                assert len(trace) == launches and all(e.kind not in ("guided_rescaled", "guidance_factor") for e in trace), (i, [e.kind for e in trace])
         xb, pb = plain.step(lines(uncond, cond, SCALE, phi or 0.0), t, xb, generator=gens[1], return_dict=False)
         assert xa.dtype == torch.bfloat16 and same_bits(xa, xb) and xa.stride() == xb.stride(), i
         assert same_bits(pa, pb), i
@@ -387,11 +387,11 @@ def test_guidance_rescale_zero_is_the_call_without_the_keyword(dev):
         _hip.trace = []
         try:
             out = w.step_guided(outs[0][0], outs[0][1], SCALE, w.timesteps.tolist()[0], x, return_dict=False, **kw)
-            results.append((out, [(len(e), e[5], e[8], e[9]) for e in _hip.trace]))
+            results.append((out, [(e.kind, e[5], e.scale, e.slot) for e in _hip.trace]))
         finally:
             _hip.trace = None
     (ra, ta), (rb, tb) = results
-    assert ta == tb and len(ta) == 1 and ta[0][0] == 10  # one launch_step_guided tuple
+    assert ta == tb and len(ta) == 1 and ta[0][0] == "guided"  # one launch_step_guided record
     assert same_bits(ra[0], rb[0]) and same_bits(ra[1], rb[1])
 
 

@@ -41,7 +41,7 @@ def test_header_declares_both_entries_and_the_binding_lists_them():
         assert name in _hip.EXPORTS
     assert re.search(r"#define\s+SKR_ABI_VERSION\s+15\b", header) and _hip.ABI_VERSION == 15  # purely additive
     assert ctypes.sizeof(_hip.StepRowC) == 328 and _hip.StepRowC.convert_k.offset == 296  # the row keeps its layout
-    assert callable(_hip.launch_guidance_factor_rolling_raw) and callable(_hip.launch_step_guided_rescaled_rolling_raw)
+    assert _hip.entry_name(_hip.FACTOR, "rolling") == STATS and _hip.entry_name("guided_rescaled", "rolling") == STEP
 
 
 def test_header_is_still_plain_c_and_the_row_keeps_its_size(tmp_path):
@@ -233,7 +233,7 @@ def stub_plan(roles, scale):
 
 
 class StubBatch(RollingBatch):
-    "the dry run gives an Adams-3-like ramp-up (2, 3, 4, 4, ... operands); the two raw launches are recorded by the tests, not made"
+    "the dry run gives an Adams-3-like ramp-up (2, 3, 4, 4, ... operands); the two launches are recorded by the tests, not made"
 
     history = HISTORY
 
@@ -264,10 +264,16 @@ def rescaled_batch(capacity=4, cls=StubBatch, make=wrapper, **options):
 
 @pytest.fixture
 def launches(monkeypatch):
-    "the raw launches of _hip replaced by recorders: (name, arguments) in issue order"
+    "the library replaced by a recorder: (C entry name, arguments -- a descriptor passed by reference as the descriptor) in issue order"
     calls = []
-    for name in ("launch_guidance_factor_rolling_raw", "launch_step_guided_rescaled_rolling_raw", "launch_step_guided_rolling_raw"):
-        monkeypatch.setattr(_hip, name, lambda *args, _name=name: calls.append((_name, args)) or 0)
+
+    class Lib:
+        def __getattr__(self, name):
+            if not name.startswith(("skr_step_launch", "skr_guidance_rescale_factor")):
+                raise AttributeError(name)
+            return lambda *args: calls.append((name, tuple(getattr(a, "_obj", a) for a in args))) or 0
+
+    monkeypatch.setattr(_hip, "load", lambda: Lib())
     monkeypatch.setattr(_hip, "current_stream_ptr", lambda device: 77)
     return calls
 
@@ -346,7 +352,7 @@ def test_a_tick_is_the_statistics_launch_then_the_step_launch_on_the_same_index_
         done = batch.step_guided(u, c)
         assert done == ([0, 2] if tick == 2 else [])
         (first, stats), (second, step) = launches[2 * tick :]
-        assert (first, second) == ("launch_guidance_factor_rolling_raw", "launch_step_guided_rescaled_rolling_raw")
+        assert (first, second) == ("skr_guidance_rescale_factor_rolling", "skr_step_launch_guided_rescaled_rolling")
         uncond_ptr, cond_ptr, code, numel, sample_numel, rows, index, offset, factor, stats_ptr, partials, stream = stats
         assert (uncond_ptr, cond_ptr, code, numel, sample_numel) == (u.data_ptr(), c.data_ptr(), _hip.BF16, batch.numel, batch.sample_numel)
         assert (factor, stats_ptr, partials, stream) == (batch.factor.data_ptr(), None, batch._partials.data_ptr(), 77)
@@ -366,13 +372,13 @@ def test_euler_passes_no_guided_out_and_a_guided_batch_keeps_its_one_launch(laun
     batch.admit(0, torch.zeros(UNIT, dtype=torch.bfloat16), euler(), 2, guidance_scale=1.5, guidance_rescale=1.0)
     u, c = torch.zeros(2, *UNIT, dtype=torch.bfloat16), torch.zeros(2, *UNIT, dtype=torch.bfloat16)
     batch.step_guided(u, c)
-    assert [name for name, _ in launches] == ["launch_guidance_factor_rolling_raw", "launch_step_guided_rescaled_rolling_raw"]
+    assert [name for name, _ in launches] == ["skr_guidance_rescale_factor_rolling", "skr_step_launch_guided_rescaled_rolling"]
     assert launches[1][1][3].guided_out is None
     del launches[:]
     guided = EulerStub(euler, torch.zeros(2, *UNIT, dtype=torch.bfloat16), capacity=2, guided=True)
     guided.admit(0, torch.zeros(UNIT, dtype=torch.bfloat16), euler(), 2, guidance_scale=1.5)
     guided.step_guided(u, c)
-    assert [name for name, _ in launches] == ["launch_step_guided_rolling_raw"]
+    assert [name for name, _ in launches] == ["skr_step_launch_guided_rolling"]
 
 
 def test_the_constructor_refusals_of_a_guided_batch_are_unchanged():

@@ -38,7 +38,7 @@ def test_header_declares_the_entry_and_the_binding_lists_it():
     assert re.search(r"#define\s+SKR_ABI_VERSION\s+15\b", header) and _hip.ABI_VERSION == 15  # purely additive
     assert ctypes.sizeof(_hip.StepRowC) == 328 and _hip.StepRowC.convert_k.offset == 296  # the row keeps its layout
     assert ctypes.sizeof(_hip.StepGuidanceC) == 32
-    assert callable(_hip.launch_step_guided_rolling_raw)
+    assert _hip.entry_name("guided", "rolling") == NAME and _hip.entry_name("guided", "indexed_per_sample") == TWIN
 
 
 def test_header_is_still_plain_c_and_the_row_keeps_its_size(tmp_path):

@@ -293,8 +293,8 @@ def test_inpainting_steps_run_in_place_on_channels_last_latents(name, dev):
     for i, ((a, entries), (b, _)) in enumerate(zip(got, want)):
         assert a.dtype == b.dtype and torch.equal(a, b), (name, i)
         assert is_cl(a) and b.is_contiguous(), (name, i)
-        assert len(entries) == 1 and len(entries[0]) == 7, (name, i, len(entries))  # exactly one launch, the masked one
-        plan, operands, out, _, _, _, used_mask = entries[0]
+        assert len(entries) == 1 and entries[0].kind == "masked", (name, i, len(entries))  # exactly one launch, the masked one
+        (plan, operands, out, _, _, _), used_mask = entries[0], entries[0].mask
         for t in operands:  # the caller's tensors, or what an earlier step of this loop wrote: no copy has been made
             assert t.data_ptr() in known and lazy.layout_of(t) == (4, 1024), (name, i)
         assert used_mask.data_ptr() == w._inpaint[0].data_ptr() and used_mask.is_contiguous(), (name, i)  # the wrapper's own, in logical order
@@ -312,7 +312,7 @@ def test_unipc_makes_two_launches_per_step_both_in_place(dev):
     known = {t.data_ptr() for t in (x0_cl, orig_cl, nz_cl, *outs_cl)}
     for i, ((a, entries), (b, _)) in enumerate(zip(got, want)):
         assert torch.equal(a, b) and is_cl(a) and b.is_contiguous(), i
-        assert [len(e) for e in entries] == [6, 7], (i, [len(e) for e in entries])  # the step launch, then the identity-form blend
+        assert [e.kind for e in entries] == ["plain", "masked"], (i, [e.kind for e in entries])  # the step launch, then the identity-form blend
         for entry in entries:
             for t in entry[1]:
                 assert t.data_ptr() in known and lazy.layout_of(t) == (4, 1024), i

@@ -42,25 +42,18 @@ PER_GRAPH = 20  # ticks of a kernels-alone graph
 def kernels_alone(batch, guided: bool, uncond, cond, repeats: int, ticks: int):
     """forms ka / kb: every slot on a steady-state row of its run (position 8 of 16: no operand absent), the tick's device work captured
     PER_GRAPH times over in one graph; returns (event us, wall us) per tick of every repeat"""
-    import ctypes
-
     import torch
 
     dev = batch.device
     batch.index_dev.copy_(torch.tensor([b * batch.max_steps + 8 for b in range(batch.capacity)], dtype=torch.int32))
-    out = batch._x[0]
-    if batch._g:
-        batch._g.append(batch._g.pop(0))
 
-    def work():
+    def work():  # (the eager tick's own binding, the rings left where they stand)
         for _ in range(PER_GRAPH):
             prediction = uncond if guided else uncond + SCALE * (cond - uncond)
-            operands = [batch._bind(role, prediction) for role in batch.roles]
-            arr = (ctypes.c_void_p * len(operands))(*[t.data_ptr() for t in operands])
             if guided:
-                batch._launch(arr, out, None, cond, batch._g[-1] if batch._g else None)
+                batch._launch(*batch._operands(prediction), cond, batch._g[0] if batch._g else None)
             else:
-                batch._launch(arr, out, None)
+                batch._launch(*batch._operands(prediction))
 
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))

@@ -81,8 +81,6 @@ def replayed(work, dev, repeats: int, ticks: int):
 
 
 def child(form: str, sampler: str, repeats: int, ticks: int) -> None:
-    import ctypes
-
     import torch
 
     import skrample_amd.diffusers as PD
@@ -110,9 +108,6 @@ def child(form: str, sampler: str, repeats: int, ticks: int) -> None:
     if alone:
         # every resident slot on a steady-state row of its run (position 8 of 16: no operand absent)
         batch.index_dev.copy_(torch.tensor([b * batch.max_steps + 8 if b in resident else -1 for b in range(CAPACITY)], dtype=torch.int32))
-        out = batch._x[0]
-        if batch._g:
-            batch._g.append(batch._g.pop(0))
         lib = _hip.load()
 
         def work():
@@ -123,17 +118,15 @@ def child(form: str, sampler: str, repeats: int, ticks: int) -> None:
                                                              batch._partials.data_ptr(), stream)  # fmt: skip
                     _hip.check(status, "skr_guidance_rescale_factor")
                 elif form[0] == "s":
-                    status = _hip.launch_guidance_factor_rolling_raw(uncond.data_ptr(), cond.data_ptr(), _hip.BF16, batch.numel, batch.sample_numel, batch.rows_dev.data_ptr(),
+                    status = lib.skr_guidance_rescale_factor_rolling(uncond.data_ptr(), cond.data_ptr(), _hip.BF16, batch.numel, batch.sample_numel, batch.rows_dev.data_ptr(),
                                                                      batch.index_dev.data_ptr(), 0, batch.factor.data_ptr(), None, batch._partials.data_ptr(), stream)  # fmt: skip
                     _hip.check(status, "skr_guidance_rescale_factor_rolling")
                 else:
                     prediction = uncond if rescaled else torch_lines(uncond, cond)
-                    operands = [batch._bind(role, prediction) for role in batch.roles]
-                    arr = (ctypes.c_void_p * len(operands))(*[t.data_ptr() for t in operands])
-                    if rescaled:
-                        batch._launch(arr, out, None, cond, batch._g[-1] if batch._g else None)
+                    if rescaled:  # (the eager tick's own binding, the rings left where they stand)
+                        batch._launch(*batch._operands(prediction), cond, batch._g[0] if batch._g else None)
                     else:
-                        batch._launch(arr, out, None)
+                        batch._launch(*batch._operands(prediction))
 
         result["event_us"] = replayed(work, dev, repeats, ticks)
         print("RESULT " + json.dumps(result), flush=True)

@@ -959,6 +959,12 @@ int skr_error_mean(const void* a_or_null, const void* b, int32_t dtype, int64_t 
 /* raw generator outputs, for parity tests of the RNG itself */
 int skr_philox_u32(uint32_t* out /* [n_blocks*4] device */, uint64_t seed, uint64_t stream_id,
                    uint64_t first_block, int64_t n_blocks, void* stream);
+/* The Philox-to-normal transform on caller-provided words, one block of four words per thread.  parts = 0:
+ * out[4i..4i+3] = the four normals the generators and step kernels make of words[4i..4i+3].  parts = 1: the factors of
+ * the first pair, out[4i..] = (r(x), cos(y), sin(y), r(x) * cos(y)) with r = sqrt(-2 ln u), the angle 2 pi u and
+ * u = fl32(x) * 2^-32 + 2^-33; words z and w are ignored.  Any other parts is SKR_ERR_UNSUPPORTED. */
+int skr_normal_u32(float* out /* [n_blocks*4] device */, const uint32_t* words /* [n_blocks*4] device */,
+                   int64_t n_blocks, int32_t parts, void* stream);
 
 /* Colored.colorize_noise (noise.py:337-403) on a caller's white noise: white_f32 ([batch * prod(dims)] fp32, used as
  * the transform workspace and overwritten) is shaped exactly as skr_noise_colored_any shapes its own draws; same

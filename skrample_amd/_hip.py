@@ -74,6 +74,7 @@ EXPORTS = (
     "skr_power_blend",
     "skr_power_blend_backward",
     "skr_philox_u32",
+    "skr_normal_u32",
     "skr_abi_version",
     "skr_strerror",
     "skr_last_hip_error",
@@ -667,6 +668,8 @@ def load() -> ctypes.CDLL:
         lib.skr_error_mean.restype = ctypes.c_int
         lib.skr_philox_u32.argtypes = [vp, u64, u64, u64, i64, vp]
         lib.skr_philox_u32.restype = ctypes.c_int
+        lib.skr_normal_u32.argtypes = [vp, vp, i64, i32, vp]
+        lib.skr_normal_u32.restype = ctypes.c_int
         lib.skr_power_blend.argtypes = [vp, i32, vp, i32, vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i64, vp]
         lib.skr_power_blend.restype = ctypes.c_int
         lib.skr_power_blend_backward.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i64, vp]

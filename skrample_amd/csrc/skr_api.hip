@@ -218,3 +218,36 @@ extern "C" int skr_philox_u32(uint32_t* out, uint64_t seed, uint64_t stream_id, 
   hipLaunchKernelGGL(philox_dump_kernel, dim3(blocks), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), out, seed, stream_id, first_block, n_blocks);
   return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
 }
+
+// parts = 0: the four normals of each block of four words; parts = 1: the factors (r, cos, sin, r * cos) of its first pair
+template <int PARTS>
+__global__ void normal_dump_kernel(float* out, const uint32_t* words, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const skr::u32x4 w{words[4 * i + 0], words[4 * i + 1], words[4 * i + 2], words[4 * i + 3]};
+  float z[4];
+  if constexpr (PARTS == 0) {
+    skr::normals_of(w, z);
+  } else {
+    skr::polar(w.x, w.y, z[0], z[1], z[2]);
+    z[3] = z[0] * z[1];
+  }
+  out[4 * i + 0] = z[0];
+  out[4 * i + 1] = z[1];
+  out[4 * i + 2] = z[2];
+  out[4 * i + 3] = z[3];
+}
+
+extern "C" int skr_normal_u32(float* out, const uint32_t* words, int64_t n_blocks, int32_t parts, void* stream) {
+  skr::DeviceGuard device_guard(out);
+  if (!out || !words) return SKR_ERR_NULL;
+  if (n_blocks < 0) return SKR_ERR_SHAPE;
+  if (parts != 0 && parts != 1) return SKR_ERR_UNSUPPORTED;
+  if (n_blocks == 0) return SKR_OK;
+  const int threads = 256;
+  const unsigned blocks = (unsigned)((n_blocks + threads - 1) / threads);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (parts == 0) hipLaunchKernelGGL(normal_dump_kernel<0>, dim3(blocks), dim3(threads), 0, s, out, words, n_blocks);
+  else hipLaunchKernelGGL(normal_dump_kernel<1>, dim3(blocks), dim3(threads), 0, s, out, words, n_blocks);
+  return hipGetLastError() == hipSuccess ? SKR_OK : SKR_ERR_LAUNCH;
+}

@@ -52,6 +52,9 @@ def test_argument_validation_without_gpu():
     assert lib.skr_noise_random(None, _hip.F32, None, 0, 0, 16, None) == 0
     assert lib.skr_noise_random(None, _hip.F32, None, 0, 2, 16, None) == 1
     assert lib.skr_philox_u32(None, 0, 0, 0, 4, None) == 1
+    assert lib.skr_normal_u32(None, None, 4, 0, None) == 1 and lib.skr_normal_u32(ctypes.c_void_p(addr), None, 4, 1, None) == 1
+    assert lib.skr_normal_u32(ctypes.c_void_p(addr), ctypes.c_void_p(addr), 4, 2, None) == 7  # SKR_ERR_UNSUPPORTED: parts is 0 or 1
+    assert lib.skr_normal_u32(ctypes.c_void_p(addr), ctypes.c_void_p(addr), -1, 2, None) == 5  # shape before parts, as skr_philox_u32 orders them
 
 
 def _imports(path: str) -> set[str]:

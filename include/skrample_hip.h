@@ -636,6 +636,41 @@ int skr_step_launch_guided_rescaled(const skr_step_plan* plan, const void* const
                                     const skr_step_rescale* rescale, const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * Guided in-painting: classifier-free guidance, the solver step and the keep-region blend in ONE launch -- what a guided step under a
+ * mask otherwise takes two for (the guidance-only form of skr_step_launch_guided[_rescaled], which writes the prediction p to HBM, and
+ * skr_step_launch_masked, which reads it straight back).  `guide`, `rescale` and `mask` are the structures of those launches, unchanged;
+ * rescale == NULL: the guidance is not rescaled.  Per element e, with T the one dtype of the launch and u = inputs[slot][e]:
+ *
+ *     p      = the guided value of skr_step_launch_guided (torch's bits: three separate op-math operations, each fp32 result rounded
+ *              to T), then, when rescale != NULL, rn_T(rn_T(phi_M * rn_T(p * r)) + rn_T(psi_M * p)) with r = factor_dev[s(e)] and
+ *              psi = 1 - phi, exactly as skr_step_launch_guided_rescaled forms it
+ *     s      = sum_k coef0[k] * v_k + zeta0 * N(seed[s(e)], stream0, e)     v_slot = p, v_k = inputs[k][e] otherwise; from zero, in
+ *              slot order, one fma each, the noise term last (skipped when zeta0 == 0)
+ *     kn     = sum over k with coef1[k] != 0 of coef1[k] * inputs[k][e]     one fma each, in slot order
+ *     out[e] = rn_T( fma(m, s, (1 - m) * kn) )                              m = the mask value, as in skr_step_launch_masked
+ *     guided_out[e] = p                                                     (when guided_out is given)
+ *
+ * `out` has, bit for bit, what skr_step_launch_masked writes for the same plan when inputs[slot] is a tensor holding p, and guided_out
+ * the bits of the guidance-only launch, rescaled or not.  The known form never contains the prediction: coef1[slot] != 0 is
+ * SKR_ERR_UNSUPPORTED.
+ * Covered: exactly what a one-trip kernel takes -- whole 2048-element chunks, samples made of whole chunks (plan->sample_numel a
+ * multiple of 2048 below 2^31 that divides numel; rescale->sample_numel equal to it), one 16- or 32-bit dtype for operands, cond, mask
+ * and both outputs, fp32 arithmetic (acc_f64 == 0), 1..SKR_ROW_TERMS operands, mask_numel % 8 == 0, out0_dtype set (there is no
+ * guidance-only form).  There is no grid-stride kernel and there are no row forms: everything else -- "one_trip" 0 and fp32 tensors
+ * with "tile" 0 included -- is SKR_ERR_UNSUPPORTED with nothing written, and the caller takes the two launches instead.  numel is
+ * always whole chunks, so the fp16 exception of skr_step_launch_guided (the partial last block of torch's kernel) cannot arise here.
+ * Checked before the launch, without dereferencing device memory: a NULL plan, guide or mask SKR_ERR_NULL; then the checks of
+ * skr_step_launch_guided[_rescaled] in its order and with its codes (out0_dtype SKR_NONE with a guided_out: SKR_ERR_UNSUPPORTED; a
+ * rescale->sample_numel other than plan->sample_numel: SKR_ERR_SHAPE); then the checks of skr_step_launch_masked (the mask's shape
+ * against the sample SKR_ERR_SHAPE, a mask dtype that is no 16- or 32-bit dtype SKR_ERR_DTYPE, a NULL or misaligned mask->mask
+ * SKR_ERR_NULL / SKR_ERR_ALIGN); then the coverage above.  numel == 0 that passes the shape checks is SKR_OK with nothing launched.
+ * Allocates nothing, never synchronises: capturable.
+ */
+int skr_guided_masked_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                  const skr_step_rescale* rescale /* NULL: none */, const skr_step_mask* mask, const uint64_t* seeds_dev,
+                                  int64_t numel, void* stream);
+
+/*
  * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,
  * rows_dev[sample_index_dev[s] + row_offset] -- convert_k[0] the guidance scale (as in skr_step_launch_guided_rolling), convert_k[1]
  * phi = guidance_rescale (skr_step_launch_guided_rolling does not read it).  convert_k[2..3], coef1, chain, zeta1 and stream1 are not

@@ -49,6 +49,7 @@ EXPORTS = (
     "skr_guidance_rescale_factor_indexed_per_sample",
     "skr_step_launch_guided_rescaled_indexed",
     "skr_step_launch_guided_rescaled_indexed_per_sample",
+    "skr_guided_masked_step_launch",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -622,6 +623,9 @@ def load() -> ctypes.CDLL:
         for name, names in ENTRIES.values():  # the step launches and the guidance statistics: prototypes from the table's one rule
             entry = getattr(lib, name)
             entry.argtypes, entry.restype = [ARGTYPES[n] for n in names], ctypes.c_int
+        # (guided in-painting: one entry, no forms, so no row of the table)
+        lib.skr_guided_masked_step_launch.argtypes = [ARGTYPES[n] for n in ("plan", "operands", "out0", "guide", "rescale", "mask", "seeds", "numel", "stream")]
+        lib.skr_guided_masked_step_launch.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -728,7 +732,8 @@ def _operand_array(tensors):
 class StepCall(tuple):
     """The record of one step launch: what a `_hip.trace` list (per thread, see _HipModule) receives for it.  It IS the six-tuple
     (plan, inputs, out0, out1, seeds, numel) that the step programs, bench.py and the tools unpack to lift the exact plans the samplers emit,
-    and it says what the launch is by name, never by its length: `kind` (a key of STEP_KINDS), `layout` ((channels, plane) or None: read
+    and it says what the launch is by name, never by its length: `kind` (a key of STEP_KINDS, or "guided_masked", the one launch outside
+    the table: launch_guided_masked_step, which carries the masked AND the guided names), `layout` ((channels, plane) or None: read
     off the tensors) and -- None where the kind has none -- `mask`, `mask_numel`, `batch_stride` (masked), `cond`, `guided_out`, `scale`,
     `slot` (guided), `factor`, `phi`, `sample_numel` (guided_rescaled).  A step program is built from a plain one only."""
 
@@ -820,6 +825,33 @@ def launch_step_guided(plan: StepPlanC, operands: list[torch.Tensor], out, cond:
     skr_step_launch_guided_indexed[_per_sample] -- the scale a row value -- or refilled.  Under any other hook it raises: that loop was
     captured without guidance."""
     launch_call(StepCall(plan, operands, out, None, seeds, numel, "guided", cond=cond, guided_out=guided_out, scale=scale, slot=slot), device)
+
+
+GUIDED_MASKED = "skr_guided_masked_step_launch"
+
+
+def launch_guided_masked_step(plan: StepPlanC, operands: list[torch.Tensor], out: torch.Tensor, cond: torch.Tensor, guided_out, scale: float, slot: int, mask: torch.Tensor,
+                              mask_numel: int, batch_stride: int, seeds, numel: int, device: torch.device, factor: "torch.Tensor | None" = None, phi: float = 0.0) -> None:
+    """one guided masked step launch (skr_guided_masked_step_launch): guidance, step and keep-region blend in one -- launch_step_guided's
+    guided value p (with `factor`, what launch_guidance_factor wrote: launch_step_guided_rescaled's, with `phi`) in operands[slot]'s place
+    in the step form, `out` = m * (coef0 form + noise) + (1 - m) * (coef1 form) as launch_step_masked blends it, `guided_out` (or None)
+    receives p.  The entry covers what its one-trip kernel takes and nothing else; the caller decides beforehand (lazy.evaluate_guided_masked)
+    and takes the two launches otherwise.  It has no row form: under an indexed-rows hook it raises, so captured loops keep their route."""
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError("a guided masked step has no row form: captured loops take the guidance-only launch and the masked step")
+    lib = load()
+    rescaled = factor is not None
+    call = StepCall(plan, operands, out, None, seeds, numel, "guided_masked", cond=cond, guided_out=guided_out, scale=scale, slot=slot, mask=mask, mask_numel=mask_numel,
+                    batch_stride=batch_stride, **({"factor": factor, "phi": phi, "sample_numel": plan.sample_numel} if rescaled else {}))  # fmt: skip
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append(call)
+    guide = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), float(scale), int(slot), 0)
+    rescale = ctypes.byref(StepRescaleC(factor.data_ptr(), float(phi), int(plan.sample_numel), 0)) if rescaled else None
+    descriptor = StepMaskC(mask.data_ptr(), DTYPE_CODE[mask.dtype], 0, mask_numel, batch_stride)
+    status = lib.skr_guided_masked_step_launch(ctypes.byref(plan), _operand_array(operands), out.data_ptr(), ctypes.byref(guide), rescale, ctypes.byref(descriptor),
+                                               _ptr(seeds), numel, current_stream_ptr(device))  # fmt: skip
+    check(status, GUIDED_MASKED)
 
 
 def launch_guidance_factor(uncond: torch.Tensor, cond: torch.Tensor, scale: float, sample_numel: int, factor: torch.Tensor, stats: "torch.Tensor | None" = None) -> None:

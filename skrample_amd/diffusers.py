@@ -681,6 +681,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         self._run_seq = False  # every call of this run so far took the next schedule index
         self._fast_hits = 0  # steps served by _fast_step (diagnostics / tests)
         self._inpaint = None  # (mask, original_samples, noise) while in-painting is set (set_inpaint)
+        self._inpaint_fuse = False  # set_inpaint(fuse_guidance=True): a guided step settles guidance and blend in one launch
 
     @classmethod
     def from_diffusers_config(
@@ -807,10 +808,16 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     # Channels-last latents: when sample, model output, history, `original_samples` and `noise` all share one dense channels-last layout
     # the masked launch runs on them as they are (skr_step_launch_masked_channels_last): no copy, a channels-last prev_sample with the
     # bits of the contiguous run.  The mask is kept contiguous, in logical order.  A mixed layout takes the copying path as before.
-    def set_inpaint(self, mask: Tensor, original_samples: Tensor, noise: Tensor) -> None:
+    # Guided in-painting: with set_inpaint(..., fuse_guidance=True) a step_guided() call whose sampler settles one form through
+    # StatedSampler.sample_packed (Euler, DPM, Adams, UniP) runs guidance, step and blend in ONE launch (lazy.evaluate_guided_masked /
+    # skr_guided_masked_step_launch; two with guidance_rescale, the statistics launch in front) where the default takes the guidance-only
+    # launch and then the masked step.  The bits are the default route's.  What that launch does not cover -- UniPC, SPC,
+    # compute_scale=None, channels-last or strided operands, ragged samples -- keeps the default route.
+    def set_inpaint(self, mask: Tensor, original_samples: Tensor, noise: Tensor, fuse_guidance: bool = False) -> None:
         """blend every following step(): mask == 1 is generated, mask == 0 keeps `original_samples`, re-noised with `noise` to the
         level of the step's target (after the last step: `original_samples` itself).  `mask` broadcasts over leading axes of the
-        latents -- (B,1,H,W), (1,1,H,W), (B,C,H,W) or (H,W) -- and is cast once to the latents' dtype (bool / uint8 accepted)."""
+        latents -- (B,1,H,W), (1,1,H,W), (B,C,H,W) or (H,W) -- and is cast once to the latents' dtype (bool / uint8 accepted).
+        `fuse_guidance`: step_guided() calls under this mask take one launch for guidance, step and blend where they can (same bits)."""
         for name, t in (("mask", mask), ("original_samples", original_samples), ("noise", noise)):
             if not isinstance(t, Tensor):
                 raise lazy.SkrampleHipError(f"set_inpaint: {name} must be a torch tensor, not {type(t).__name__}")
@@ -820,20 +827,23 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         lazy.mask_layout(mask.shape, original_samples.shape)  # (refused here, not at the first step)
         mask = mask.to(device=original_samples.device, dtype=original_samples.dtype).contiguous()
         self._inpaint = (mask, original_samples, noise)
+        self._inpaint_fuse = bool(fuse_guidance)
 
     def clear_inpaint(self) -> None:
         "steps are plain steps again (and take the replayed fast path where they did)"
         self._inpaint = None
+        self._inpaint_fuse = False
 
-    def _inpaint_blend(self, idx: int, steps: int):
-        "the pending blend of the step at schedule index `idx`: the kept region at the noise level of index idx + 1 (Point.add_noise's algebra, host fp64)"
+    def _inpaint_blend(self, idx: int, steps: int, fuse_guidance: bool = False):
+        """the pending blend of the step at schedule index `idx`: the kept region at the noise level of index idx + 1 (Point.add_noise's algebra, host fp64);
+        `fuse_guidance`: marked to be settled together with the step's pending guidance"""
         mask, original, noise = self._inpaint
         if idx + 1 < steps:
             point = Point(*self.schedule_np[idx + 1])
             known = Lin.leaf(original) * float(point.alpha) + Lin.leaf(noise) * float(point.sigma)
         else:
             known = Lin.leaf(original) * 1.0
-        return lazy.MaskedBlend(known, mask)
+        return lazy.MaskedBlend(known, mask, fuse_guidance)
 
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
         inpaint = getattr(self, "_inpaint", None)
@@ -853,7 +863,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     # before step() reads it.  step_guided() takes the two halves and the scale instead: for the samplers whose step is one
     # single-output launch (Euler, DPM, Adams, UniP) the three ops run inside that launch (lazy.evaluate_guided /
     # skr_step_launch_guided), which also stores the guided prediction that history, pred_original_sample and callbacks read.
-    # Everything else -- the two-output samplers (UniPC, SPC), a step under set_inpaint, compute_scale=None, channels-last or strided
+    # Everything else -- the two-output samplers (UniPC, SPC), a step under set_inpaint (unless it was set with fuse_guidance=True: see there), compute_scale=None, channels-last or strided
     # operands -- forms the prediction in one guidance-only launch and steps as ever; host-resident operands and operands that autograd
     # records form it with torch's own three lines.  Either way prev_sample and pred_original_sample have the bits of
     # step(uncond + guidance_scale * (cond - uncond), ...) on a wrapper in the same state, and calls of both kinds may be mixed in a run.
@@ -876,8 +886,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         inpaint = getattr(self, "_inpaint", None)
         guided_call = guidance is not None
         if guided_call:
-            # one launch: a sampler that settles one form through StatedSampler.sample_packed, over contiguous device tensors
-            fused = (type(self.sampler).sample_packed is sampling.StatedSampler.sample_packed and inpaint is None and self.compute_scale is not None
+            # one launch: a sampler that settles one form through StatedSampler.sample_packed, over contiguous device tensors; under a mask
+            # only where set_inpaint asked for it (the pending blend then takes the guidance up: lazy.MaskedBlend.settle_guided)
+            fused = (type(self.sampler).sample_packed is sampling.StatedSampler.sample_packed and (inpaint is None or getattr(self, "_inpaint_fuse", False)) and self.compute_scale is not None
                           and not recorded and isinstance(sample, Tensor) and sample.is_cuda and sample.is_contiguous()
                           and model_output.is_contiguous() and guidance.cond.is_contiguous())  # fmt: skip
             if not fused:
@@ -933,7 +944,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         )  # fmt: skip
         record = None
         prog = self._programs.get(key) if not recorded and inpaint is None and not guided_call else False  # (a masked or guided step: no program, no tracing)
-        blend = self._inpaint_blend(idx, len(table)) if inpaint is not None else None
+        blend = self._inpaint_blend(idx, len(table), guidance is not None) if inpaint is not None else None
         guide = lazy.GuidedStep(guidance) if guidance is not None else None
         if prog is not None and prog is not False:
             record = prog.run(roles, step, prediction, sample.device)

@@ -785,10 +785,12 @@ _pending_blend: contextvars.ContextVar = contextvars.ContextVar("skr_pending_ble
 
 
 class MaskedBlend:
-    "context manager: `with MaskedBlend(known, mask): sampler.sample_packed(...)`; taken up at most once"
+    """context manager: `with MaskedBlend(known, mask): sampler.sample_packed(...)`; taken up at most once.  `fuse_guidance`: a guidance
+    pending beside it (GuidedStep) is settled with it, in one launch (settle_guided / evaluate_guided_masked); without the mark the
+    blend is settled alone, as ever."""
 
-    def __init__(self, known: Lin, mask: torch.Tensor):
-        self.known, self.mask, self.used = known, mask, False
+    def __init__(self, known: Lin, mask: torch.Tensor, fuse_guidance: bool = False):
+        self.known, self.mask, self.used, self.fuse_guidance = known, mask, False, fuse_guidance
 
     def __enter__(self):
         self.token = _pending_blend.set(self)
@@ -800,6 +802,12 @@ class MaskedBlend:
     def settle(self, form: Lin, dtype: torch.dtype | None) -> torch.Tensor:
         self.used = True
         return evaluate_masked(form, self.known, self.mask, dtype)
+
+    def settle_guided(self, form: Lin, pending: "GuidedStep", dtype: torch.dtype | None) -> torch.Tensor:
+        "the blend and the pending guidance together: both are used, and `pending` keeps the stored prediction"
+        self.used = pending.used = True
+        final, pending.guided = evaluate_guided_masked(form, pending.guidance, self.known, self.mask, dtype)
+        return final
 
 
 def pending_blend() -> "MaskedBlend | None":
@@ -906,6 +914,65 @@ class GuidedStep:
 def pending_guidance() -> "GuidedStep | None":
     pending = _pending_guidance.get()
     return pending if pending is not None and not pending.used else None
+
+
+# ---- guided in-painting: guidance, step and keep-region blend in one launch -------------------------------------------------------------
+def evaluate_guided_masked(form: Lin, guidance: Guidance, known: Lin, mask: torch.Tensor, dtype: torch.dtype | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(final, guided): mask * form + (1 - mask) * known, where `form` holds `guidance.node()` wherever the prediction stands, and the
+    guided prediction itself, in ONE launch (skr_guided_masked_step_launch).  `form` (with `uncond` in the node's place) and `known` are
+    lowered into one merged operand list exactly as evaluate_masked lowers them, and the node's position is the launch's `slot`, as in
+    evaluate_guided: `final` has the bits of evaluate_masked over the form with the tensor `guided` in the node's place, and `guided` the
+    bits of torch's lines.  A rescaled guidance has the statistics launch in front (skr_guidance_rescale_factor).
+    The entry has one one-trip kernel and nothing behind it, so whether it covers the step is decided here, from shapes and dtypes,
+    before anything is launched.  Everything else takes `guide_only(guidance)` and then evaluate_masked() on the substituted form -- the
+    route of a guided step under a mask without this function, with the same bits: an installed `_hip.indexed` hook (the entry has no row
+    form, so captured loops keep their route), host-resident or grad-recorded operands,
+    non-contiguous (channels-last included) or misaligned operands, operands or a mask of another dtype than the guidance's, fp64 and
+    float64 accumulation, samples that are not whole 2048-element chunks, a mask whose elements per sample are no multiple of 8, a
+    Philox leaf that would be realised to a tensor, `uncond` as an operand of either form in its own right, a zero node coefficient, and
+    more than 16 leaves."""
+    f, f1 = lift(form), lift(known)
+    if not isinstance(f, Lin) or not isinstance(f1, Lin) or not isinstance(guidance, Guidance) or not isinstance(mask, torch.Tensor):
+        raise SkrampleHipError("evaluate_guided_masked() takes a tensor form, a Guidance, the known form and a mask tensor")
+    f, f1 = f.expanded(keep=guidance), f1.expanded()
+    if any(isinstance(leaf, Node) and leaf.form is not guidance for form_ in (f, f1) for leaf, _ in form_.terms.values()):
+        raise SkrampleHipError("a guided masked launch has one step output: its forms cannot refer to another stored form")
+    if f.shape != guidance.shape or f1.shape != f.shape:
+        raise SkrampleHipError(f"shape mismatch between the step form {f.shape}, the known form {f1.shape} and the guidance operands {guidance.shape}")
+    shape, device, one = f.shape, guidance.device, guidance.dtype
+    out_dtype = dtype if dtype is not None else one
+    u, c = guidance.uncond, guidance.cond
+    live = [(leaf, k) for form_ in (f, f1) for leaf, k in form_.terms.values() if k != 0.0]
+    leaves = [leaf for leaf, _ in live if isinstance(leaf, torch.Tensor)]
+    draws = [leaf for leaf, k in f.terms.values() if k != 0.0 and isinstance(leaf, PhiloxNoise)]
+    numel = math.prod(shape)
+    sample = numel // shape[0] if shape and shape[0] else 0
+    tensors = (*leaves, u, c, mask)
+    covered = (
+        _hip.indexed is None  # (no row form: a captured loop keeps the two launches)
+        and f.device != NUMPY and f1.device != NUMPY and all(t.is_cuda and t.device == device for t in tensors) and not grad_recorded(*tensors)
+        and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors)
+        and one in (torch.bfloat16, torch.float16, torch.float32) and out_dtype == one and all(t.dtype == one for t in tensors) and _compute_dtype.get() != torch.float64
+        and 0 < sample < 2**31 and sample % _hip.PER_SAMPLE_CHUNK == 0 and numel // _hip.PER_SAMPLE_CHUNK < 2**31
+        and mask_layout(mask.shape, shape)[0] % 8 == 0
+        # at most one draw, fused into the launch; a Philox leaf of the known form, a second one or an unfusable one would become an fp32 operand
+        and len(draws) <= 1 and all(nz.fusable() and nz.shape == shape for nz in draws) and not any(isinstance(leaf, PhiloxNoise) for leaf, _ in f1.terms.values())
+        and id(u) not in f.terms and id(u) not in f1.terms
+        and any(isinstance(leaf, Node) and k != 0.0 for leaf, k in f.terms.values())
+        and len(live) <= _hip.ROW_TERMS
+    )  # fmt: skip
+    if covered:
+        plan, operands, seeds = _lower(None, f.substitute(guidance, u), f1, 0.0, [out_dtype], None, fuse1=False, max_terms=_hip.ROW_TERMS)
+        slot = next((k for k, t in enumerate(operands) if t is u), None)
+        plan.sample_numel = sample
+        if slot is not None and plan.coef1[slot] == 0.0 and _hip.one_group_launch(plan, _hip.DTYPE_CODE[mask.dtype]):
+            mask_numel, batch_stride = mask_layout(mask.shape, shape)
+            final, guided = empty_output(shape, out_dtype, device), empty_output(shape, one, device)
+            factor = guidance.device_factor(u, c) if guidance.rescale != 0.0 else None  # the statistics launch, the same on either route
+            _hip.launch_guided_masked_step(plan, operands, final, c, guided, guidance.scale, slot, mask, mask_numel, batch_stride, seeds, numel, device, factor, guidance.rescale)
+            return final, guided
+    guided = guide_only(guidance)
+    return evaluate_masked(f.substitute(guidance, guided), f1, mask, dtype), guided
 
 
 def _host_evaluate_masked(f0: "Lin", f1: "Lin", mask: torch.Tensor, out_dtype: torch.dtype, acc_f64) -> torch.Tensor:

@@ -130,7 +130,9 @@ class StatedSampler(StructuredSampler):
         form = self._form(packed, model_transform, schedule, previous)
         blend = lazy.pending_blend()  # in-painting: the step's one launch is the masked launch (lazy.evaluate_masked)
         guided = lazy.pending_guidance()  # classifier-free guidance: the step's one launch is the guided launch (lazy.evaluate_guided)
-        if blend is not None and isinstance(form, Lin):
+        if blend is not None and guided is not None and blend.fuse_guidance and isinstance(form, Lin):
+            final = blend.settle_guided(form, guided, _result_dtype(packed.sample))  # guided in-painting: both in one launch (lazy.evaluate_guided_masked)
+        elif blend is not None and isinstance(form, Lin):
             final = blend.settle(form, _result_dtype(packed.sample))
         elif guided is not None and isinstance(form, Lin):
             final = guided.settle(form, _result_dtype(packed.sample))

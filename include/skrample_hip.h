@@ -671,6 +671,87 @@ int skr_guided_masked_step_launch(const skr_step_plan* plan, const void* const* 
                                   int64_t numel, void* stream);
 
 /*
+ * Dynamic thresholding (Imagen; diffusers' `thresholding`, `dynamic_thresholding_ratio`, `sample_max_value`): the data prediction is
+ * clipped to a per-sample quantile of its magnitudes and divided by it before the step reads it.  A whole-sample order statistic has
+ * to finish before the elementwise part starts, so the fused form is two launches: the statistic below (4 tensor reads), then
+ * skr_thresholded_step_launch with its per-sample scale (the guided step's traffic).
+ *
+ * Definition.  For a launch of numel elements in samples of sample_numel contiguous elements, T the one tensor dtype (bf16, fp16 or
+ * fp32), x = the sample, o = the network output, a_M and b_M the model's to_x weights at the step's point, narrowed to fp32 once:
+ *
+ *     x0[e]  = rn32( rn32(a_M * x[e]) + rn32(b_M * o[e]) )      three separate fp32 operations, nothing contracted
+ *     A      = |x0| of the sample, ascending;  n = sample_numel
+ *     r      = ratio * (n - 1)   in double;   k = floor(r);   w = r - k
+ *     q      = rn32( A[k] + w * (A[min(k+1, n-1)] - A[k]) )     evaluated in double, rounded once
+ *     s      = NaN if the sample holds a NaN, else min(max(q, 1), sample_max_value)      (fp32)
+ *     p[e]   = rn_T( min(max(x0[e], -s), s) / s )               IEEE fp32 division
+ *     out[e] = skr_step_launch's sum with p in the place of inputs[slot]  (slot order, one fma each, noise last, one rounding)
+ *
+ * A[k] and A[k+1] are exact order statistics -- a radix select over the 31 magnitude bits (a non-negative fp32 orders as its bit
+ * pattern), not a sketch and not an estimate -- so a sample has the same s bits alone and inside any batch, at any alignment, whatever
+ * the grid.  0 < ratio <= 1; at ratio == 1, w == 0 and q is the maximum.  q is three IEEE double operations as written: where w == 0
+ * or A[k] == A[k+1] is finite, q is A[k] itself; an infinite A[k+1] gives inf for w > 0 and NaN for w == 0 or an infinite A[k], as
+ * torch's lerp does.  The clamps and the clip are made of comparisons: a NaN q gives a NaN s, a NaN x0 stays NaN, and a NaN s makes
+ * every p of its sample NaN.  sample_max_value <= 1 makes s identically 1 -- a plain clip: the host then skips the
+ * statistic and passes a NULL scale_dev.  torch forms the rank in fp32; this definition forms it in double (profiles/thresholding.txt
+ * has the difference in s).
+ *
+ * skr_threshold_scale writes s per sample to scale_dev.  Four kernels on `stream`: one that clears the histograms inside the workspace;
+ * a histogram pass (workgroups of 256 lanes over runs of 2048-element spans of one sample, whole 16-byte aligned spans by 16-byte
+ * non-temporal loads, others element by element; the top 11 magnitude bits counted into one LDS sub-histogram per wave, the lanes of
+ * a wave that share a bin combined into one LDS atomic, the non-empty bins flushed to the sample's 8 KiB histogram; NaNs counted on
+ * the side); a candidate pass (every workgroup finds the bins of rank k and k + 1 in the finished histogram, re-reads its spans and
+ * appends the magnitudes in those bins to the sample's list through a wave-aggregated cursor); and a finish (one workgroup per
+ * sample: two further 10-bit LDS histogram passes over the list select both ranks, then q and s).
+ * workspace_dev: SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes, 16-byte aligned, overwritten: per sample a 2048-bin histogram,
+ * a NaN count and a cursor, and sample_numel candidate slots (a sample whose elements are all equal has every element a candidate).
+ * Checked before any launch, without dereferencing device memory: a NULL sample, output, scale_dev or workspace_dev SKR_ERR_NULL;
+ * numel < 0, sample_numel < 1 or sample_numel not dividing numel SKR_ERR_SHAPE;  numel == 0 SKR_OK with nothing launched;  sample,
+ * output or workspace_dev not 16-byte aligned, scale_dev not 4-byte aligned SKR_ERR_ALIGN;  a dtype other than bf16, fp16 or fp32
+ * SKR_ERR_DTYPE;  ratio outside (0, 1] or not finite, sample_numel >= 2^31 or more than INT32_MAX workgroups SKR_ERR_UNSUPPORTED.
+ * Allocates nothing, never synchronises: capturable.
+ */
+#define SKR_THRESHOLD_WORKSPACE(numel, sample_numel) (((numel) / (sample_numel)) * 8208 + 4 * (numel))
+
+int skr_threshold_scale(const void* sample, const void* output, int32_t dtype, double a, double b, double ratio, double sample_max_value,
+                        int64_t numel, int64_t sample_numel, float* scale_dev /* [numel / sample_numel] */,
+                        void* workspace_dev /* SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes */, void* stream);
+
+/*
+ * skr_thresholded_step_launch: the step with p, as defined above, in the place of inputs[slot] -- a sibling of skr_step_launch_guided
+ * under its plan contract: no second output; chain, zeta1 and convert_* zero; at most SKR_ROW_TERMS operands; coef1 is ignored.
+ * inputs[slot] is the network output, inputs[xslot] the sample, which keeps its own coefficient in the sum.  T is the dtype of the
+ * group `slot` lies in.  `out` has, bit for bit, what skr_step_launch writes for the same plan over the operand list whose entry
+ * `slot` is a tensor holding p; x0_out is that tensor (what history and pred_original_sample read).
+ * Thresholding-only form: out0_dtype == SKR_NONE with out == NULL and n_terms == 2 stores p alone; x0_out is then required, and
+ * nothing is drawn.  It serves the two-output samplers, whose step then runs as ever over p.
+ * Launches of whole 2048-element chunks whose thr->sample_numel is a multiple of 2048 below 2^31, with one 16- or 32-bit dtype, take a
+ * one-trip vector kernel -- a workgroup then lies inside one sample and s is one uniform load --; everything else (ragged sizes,
+ * small samples, two dtype groups) a grid-stride per-element kernel.  The two agree bit for bit ("one_trip" 0 forces the second).
+ * Checked before the launch, without dereferencing device memory, in this order (skr_step_launch_guided's, xslot beside slot):
+ *   a NULL plan or thr SKR_ERR_NULL;  a launch that draws without seeds SKR_ERR_NULL;  n_terms outside 0..SKR_ROW_TERMS or n_group_a
+ *   outside 0..n_terms SKR_ERR_TERMS;  slot or xslot outside 0..n_terms-1, or slot == xslot SKR_ERR_TERMS;  numel < 0 SKR_ERR_SHAPE;
+ *   no output at all SKR_ERR_NULL;  a noise_mode other than 0 / 1, a second output, chain, zeta1, convert_*, a non-zero `reserved`,
+ *   acc_f64, or out0_dtype SKR_NONE outside the thresholding-only form SKR_ERR_UNSUPPORTED;  the sample size of a launch that draws
+ *   SKR_ERR_SHAPE / SKR_ERR_UNSUPPORTED as in skr_step_launch;  thr->sample_numel < 1 or not dividing numel, or a drawing plan whose
+ *   sample_numel differs SKR_ERR_SHAPE;  numel == 0 SKR_OK with nothing launched;  a NULL inputs, operand or out SKR_ERR_NULL;  a
+ *   misaligned operand, out or x0_out (16 bytes) or scale_dev (4 bytes) SKR_ERR_ALIGN;  an fp64 tensor SKR_ERR_UNSUPPORTED;  any other
+ *   dtype combination skr_step_launch does not take SKR_ERR_DTYPE.
+ * Allocates nothing, never synchronises: capturable.
+ */
+typedef struct skr_step_threshold {
+  const float* scale_dev;   /* what skr_threshold_scale wrote; NULL: s = 1 for every sample */
+  void* x0_out;             /* device, dtype T; NULL: p is not stored */
+  double a, b;              /* to_x weights */
+  int64_t sample_numel;     /* elements per sample of the statistic */
+  int32_t slot, xslot;      /* inputs[slot] is the network output and p takes its place; inputs[xslot] is the sample */
+  int64_t reserved;         /* 0 */
+} skr_step_threshold;
+
+int skr_thresholded_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_threshold* thr,
+                                const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
  * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,
  * rows_dev[sample_index_dev[s] + row_offset] -- convert_k[0] the guidance scale (as in skr_step_launch_guided_rolling), convert_k[1]
  * phi = guidance_rescale (skr_step_launch_guided_rolling does not read it).  convert_k[2..3], coef1, chain, zeta1 and stream1 are not

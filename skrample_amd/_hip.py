@@ -50,6 +50,8 @@ EXPORTS = (
     "skr_step_launch_guided_rescaled_indexed",
     "skr_step_launch_guided_rescaled_indexed_per_sample",
     "skr_guided_masked_step_launch",
+    "skr_threshold_scale",
+    "skr_thresholded_step_launch",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -235,6 +237,26 @@ class StepRescaleC(ctypes.Structure):
         ("sample_numel", ctypes.c_int64),
         ("reserved", ctypes.c_int64),
     ]
+
+
+class StepThresholdC(ctypes.Structure):
+    "mirror of `skr_step_threshold`: the per-sample scale of the statistics launch, the to_x weights and the two operands a thresholded step launch reads"
+
+    _fields_ = [
+        ("scale_dev", ctypes.c_void_p),
+        ("x0_out", ctypes.c_void_p),
+        ("a", ctypes.c_double),
+        ("b", ctypes.c_double),
+        ("sample_numel", ctypes.c_int64),
+        ("slot", ctypes.c_int32),
+        ("xslot", ctypes.c_int32),
+        ("reserved", ctypes.c_int64),
+    ]
+
+
+def threshold_workspace(numel: int, sample_numel: int) -> int:
+    "bytes of workspace skr_threshold_scale needs (include/skrample_hip.h, SKR_THRESHOLD_WORKSPACE)"
+    return (numel // sample_numel) * 8208 + 4 * numel
 
 
 GUIDANCE_SPAN = 2048  # elements per partial sum of skr_guidance_rescale_factor (SKR_GUIDANCE_PARTIALS)
@@ -626,6 +648,12 @@ def load() -> ctypes.CDLL:
         # (guided in-painting: one entry, no forms, so no row of the table)
         lib.skr_guided_masked_step_launch.argtypes = [ARGTYPES[n] for n in ("plan", "operands", "out0", "guide", "rescale", "mask", "seeds", "numel", "stream")]
         lib.skr_guided_masked_step_launch.restype = ctypes.c_int
+        # (dynamic thresholding: two entries, no forms, so no rows of the table)
+        f64 = ctypes.c_double
+        lib.skr_threshold_scale.argtypes = [vp, vp, i32, f64, f64, f64, f64, i64, i64, vp, vp, vp]
+        lib.skr_threshold_scale.restype = ctypes.c_int
+        lib.skr_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepThresholdC), vp, i64, vp]
+        lib.skr_thresholded_step_launch.restype = ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -871,3 +899,32 @@ def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], o
     values, `factor` replaced by the hook's own -- or refilled (IndexedRows.launch).  Under any other hook it raises."""
     launch_call(StepCall(plan, operands, out, None, seeds, numel, "guided_rescaled", cond=cond, guided_out=guided_out, scale=scale, slot=slot, factor=factor, phi=phi,
                          sample_numel=sample_numel), device)  # fmt: skip
+
+
+THRESHOLD_NO_ROWS = "dynamic thresholding (set_thresholding) has no row form: capture_sampling_loop and RollingBatch do not take a thresholding wrapper"
+
+
+def launch_threshold_scale(sample: torch.Tensor, output: torch.Tensor, a: float, b: float, ratio: float, sample_max_value: float, sample_numel: int, scale: torch.Tensor) -> None:
+    """the statistics launch of dynamic thresholding (skr_threshold_scale): scale[s] = min(max(q_s, 1), sample_max_value) with q_s the `ratio`
+    quantile of |a * sample + b * output| over sample s of `sample_numel` elements -- an exact radix select; `scale` is float32[samples].
+    It has no row form: under an indexed-rows hook it raises."""
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError(THRESHOLD_NO_ROWS)
+    numel, device = sample.numel(), sample.device
+    workspace = torch.empty(threshold_workspace(numel, sample_numel), dtype=torch.uint8, device=device)  # (torch's allocator: 16-byte aligned, safe under capture)
+    status = load().skr_threshold_scale(sample.data_ptr(), output.data_ptr(), DTYPE_CODE[sample.dtype], float(a), float(b), float(ratio), float(sample_max_value), numel,
+                                        int(sample_numel), scale.data_ptr(), workspace.data_ptr(), current_stream_ptr(device))  # fmt: skip
+    check(status, "skr_threshold_scale")
+
+
+def launch_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor], out, x0_out, scale: "torch.Tensor | None", a: float, b: float, sample_numel: int, slot: int, xslot: int,
+                            seeds, numel: int, device: torch.device) -> None:
+    """one thresholded step launch (skr_thresholded_step_launch): operands[slot] is the network output, operands[xslot] the sample, and
+    p = clamp(a * sample + b * output, -s, s) / s with s = scale[sample index] (1 when `scale` is None) takes the output's place in the step's
+    sum; `x0_out` (or None) receives p.  `out` None with a plan whose out0_dtype is NONE and two operands is the thresholding-only form.
+    It has no row form: under an indexed-rows hook it raises."""
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError(THRESHOLD_NO_ROWS)
+    thr = StepThresholdC(_ptr(scale), _ptr(x0_out), float(a), float(b), int(sample_numel), int(slot), int(xslot), 0)
+    status = load().skr_thresholded_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(thr), _ptr(seeds), numel, current_stream_ptr(device))
+    check(status, "skr_thresholded_step_launch")

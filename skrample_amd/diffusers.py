@@ -640,6 +640,9 @@ class SkrampleWrapperCore(abc.ABC):
         return attr_dict(prev_sample=prev, pred_original_sample=pred) if return_dict else (prev, pred)
 
 
+_DATA_MODEL = DataModel()  # the model transform of a step under set_thresholding: its prediction is the thresholded x0
+
+
 @dataclasses.dataclass
 class SkrampleWrapperScheduler(SkrampleWrapperCore):
     sampler: StructuredSampler
@@ -682,6 +685,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         self._fast_hits = 0  # steps served by _fast_step (diagnostics / tests)
         self._inpaint = None  # (mask, original_samples, noise) while in-painting is set (set_inpaint)
         self._inpaint_fuse = False  # set_inpaint(fuse_guidance=True): a guided step settles guidance and blend in one launch
+        self._thresholding = None  # (ratio, sample_max_value) of the current run (set_thresholding, taken up by set_timesteps)
+        self._thresholding_next = None
 
     @classmethod
     def from_diffusers_config(
@@ -752,6 +757,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         if steps is None:
             return
         self._steps = steps
+        self._thresholding = getattr(self, "_thresholding_next", None)
         if self.allow_dynamic:
             self.schedule = _apply_dynamic(self.schedule, steps, mu)
         self._previous = []
@@ -818,6 +824,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         level of the step's target (after the last step: `original_samples` itself).  `mask` broadcasts over leading axes of the
         latents -- (B,1,H,W), (1,1,H,W), (B,C,H,W) or (H,W) -- and is cast once to the latents' dtype (bool / uint8 accepted).
         `fuse_guidance`: step_guided() calls under this mask take one launch for guidance, step and blend where they can (same bits)."""
+        if getattr(self, "_thresholding_next", None) is not None or getattr(self, "_thresholding", None) is not None:
+            raise lazy.SkrampleHipError("set_inpaint: in-painting beside dynamic thresholding (set_thresholding) is not covered; clear one of them")
         for name, t in (("mask", mask), ("original_samples", original_samples), ("noise", noise)):
             if not isinstance(t, Tensor):
                 raise lazy.SkrampleHipError(f"set_inpaint: {name} must be a torch tensor, not {type(t).__name__}")
@@ -845,8 +853,57 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             known = Lin.leaf(original) * 1.0
         return lazy.MaskedBlend(known, mask, fuse_guidance)
 
+    # ---- dynamic thresholding (diffusers' `thresholding`; not in the reference) ----------------------------------------------------------
+    # Imagen-style dynamic thresholding, as diffusers' multistep schedulers apply it: the network output is converted to the data
+    # prediction x0 (this wrapper's model, the weights to_x uses), x0 is clipped to the per-sample `ratio` quantile s of |x0| (clamped to
+    # [1, sample_max_value]) and divided by s, and the sampler steps over that prediction p under DataModel.  On device tensors the
+    # quantile is one statistics launch (skr_threshold_scale, an exact radix select) and Euler, DPM, Adams and UniP form x0, clip and step
+    # in ONE launch (lazy.evaluate_thresholded / skr_thresholded_step_launch), which also stores p for history and pred_original_sample;
+    # UniPC and SPC take the thresholding-only launch and then their step over p.  Host-resident operands evaluate the same definition
+    # with torch ops.  A thresholding step builds no step program and learns no replayed entry.
+    def set_thresholding(self, ratio: float | None = 0.995, sample_max_value: float = 1.0) -> None:
+        """dynamic thresholding for the runs that follow: takes effect from the next set_timesteps().  `ratio` None clears it.
+        `sample_max_value` <= 1 is a plain clip to [-1, 1] (no quantile is taken)."""
+        table_len = len(self._timestep_table()) if getattr(self, "_steps", None) else 0
+        if 0 < self._calls and self._index + self._calls < table_len:
+            raise lazy.SkrampleHipError("set_thresholding: thresholding cannot change in the middle of a run; it takes effect from the next set_timesteps()")
+        if ratio is None:
+            self._thresholding_next = None
+            return
+        for name, v in (("ratio", ratio), ("sample_max_value", sample_max_value)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise lazy.SkrampleHipError(f"set_thresholding: {name} is a finite Python number, not {v!r}")
+        if not 0.0 < ratio <= 1.0:
+            raise lazy.SkrampleHipError(f"set_thresholding: ratio must lie in (0, 1], not {ratio}")
+        if not sample_max_value > 0.0:
+            raise lazy.SkrampleHipError(f"set_thresholding: sample_max_value must be positive, not {sample_max_value}")
+        if getattr(self, "_inpaint", None) is not None:
+            raise lazy.SkrampleHipError("set_thresholding: dynamic thresholding beside in-painting (set_inpaint) is not covered; clear one of them")
+        self._thresholding_next = (float(ratio), float(sample_max_value))
+
+    def _step_thresholded(self, model_output: Tensor, timestep, sample: Tensor, generator, return_dict: bool):
+        "step() under set_thresholding: the Threshold leaf at this step's point, then the general path with DataModel as the model transform"
+        ratio, max_value = self._thresholding
+        if getattr(self, "_inpaint", None) is not None:
+            raise lazy.SkrampleHipError("dynamic thresholding beside in-painting (set_inpaint) is not covered; clear one of them")
+        if self.compute_scale is None:
+            raise lazy.SkrampleHipError("dynamic thresholding needs a compute scale: compute_scale=None steps in the tensors' own rounded arithmetic, which has no thresholding form")
+        if not isinstance(model_output, Tensor) or not isinstance(sample, Tensor):
+            raise lazy.SkrampleHipError(f"dynamic thresholding takes torch tensors, not {type(model_output).__name__} and {type(sample).__name__}")
+        if model_output is sample:
+            model_output, sample = lazy.distinct(model_output, sample)
+        if lazy.grad_recorded(model_output, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous)):
+            raise lazy.SkrampleHipError("dynamic thresholding has no backward: operands that autograd records are refused")
+        table = self._timestep_table()
+        idx = self._lookup(table, timestep, self._index + self._calls)
+        a, b = self.model.x_weights(sampling._ipoint(self.schedule, Step.from_int(idx, len(table)).time_from))
+        thr = lazy.Threshold(model_output, sample, a, -b if self.invert_prediction else b, ratio, max_value)
+        return self._step_general(model_output, timestep, sample, generator, return_dict, False, thr)
+
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
         inpaint = getattr(self, "_inpaint", None)
+        if getattr(self, "_thresholding", None) is not None:
+            return self._step_thresholded(model_output, timestep, sample, generator, return_dict)
         if model_output is sample:  # one tensor in both roles: a view object per role (lazy.distinct), or the form would hold ONE operand
             model_output, sample = lazy.distinct(model_output, sample)
         # a step autograd records takes the general path: the replayed steps and step programs bind raw pointers (no autograd node)
@@ -875,6 +932,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
                     guidance_rescale: float = 0.0):
         model_output_uncond, model_output_cond, sample = lazy.distinct(model_output_uncond, model_output_cond, sample)
         guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale, guidance_rescale)
+        if getattr(self, "_thresholding", None) is not None:  # the guidance-only launch, then the thresholding route over its prediction
+            return self._step_thresholded(lazy.guide_only(guidance), timestep, sample, generator, return_dict)
         recorded = lazy.grad_recorded(model_output_uncond, model_output_cond, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
         return self._step_general(model_output_uncond, timestep, sample, generator, return_dict, recorded, guidance)
 
@@ -885,6 +944,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         step program and learns no replayed entry."""
         inpaint = getattr(self, "_inpaint", None)
         guided_call = guidance is not None
+        thresholded = isinstance(guidance, lazy.Threshold)  # (its operands are output and sample; the sampler then steps under DataModel, nothing left to invert)
+        invert = self.invert_prediction and not thresholded
         if guided_call:
             # one launch: a sampler that settles one form through StatedSampler.sample_packed, over contiguous device tensors; under a mask
             # only where set_inpaint asked for it (the pending blend then takes the guidance up: lazy.MaskedBlend.settle_guided)
@@ -892,7 +953,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
                           and not recorded and isinstance(sample, Tensor) and sample.is_cuda and sample.is_contiguous()
                           and model_output.is_contiguous() and guidance.cond.is_contiguous())  # fmt: skip
             if not fused:
-                guidance, model_output = None, lazy.guide_only(guidance)
+                guidance, model_output = None, (lazy.threshold_only(guidance) if thresholded else lazy.guide_only(guidance))
         table = self._timestep_table()
         idx = self._lookup(table, timestep, self._index + self._calls)
         if self._calls == 0:
@@ -907,14 +968,16 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             sample = lazy.snapshot(sample)
             if not guided_call:  # (a guided prediction is the engine's own tensor)
                 model_output = lazy.snapshot(model_output)
+            if thresholded and guidance is not None:  # the leaf reads the sample the form holds: one operand, not two
+                guidance.cond = guidance.sample = sample
         elif aliasing:
             self._alias_check(model_output, sample)
 
         if guidance is not None:  # the guided prediction as a leaf of the sampler's form; under invert_prediction just a sign
-            prediction = LazyTensor(-guidance.node() if self.invert_prediction else guidance.node(), model_output.dtype)
+            prediction = LazyTensor(-guidance.node() if invert else guidance.node(), model_output.dtype)
         else:
-            prediction = LazyTensor(-Lin.leaf(model_output), model_output.dtype) if self.invert_prediction else model_output
-        if self.invert_prediction and self.compute_scale is None and isinstance(model_output, Tensor) and isinstance(sample, Tensor):
+            prediction = LazyTensor(-Lin.leaf(model_output), model_output.dtype) if invert else model_output
+        if invert and self.compute_scale is None and isinstance(model_output, Tensor) and isinstance(sample, Tensor):
             # no compute scale: the sampler runs the reference's rounded tensor ops on what it is handed (sampling/native.py), and the
             # reference hands it the negated TENSOR (diffusers.py:563-564) -- an exact op, one launch
             from .sampling import native
@@ -945,7 +1008,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         record = None
         prog = self._programs.get(key) if not recorded and inpaint is None and not guided_call else False  # (a masked or guided step: no program, no tracing)
         blend = self._inpaint_blend(idx, len(table), guidance is not None) if inpaint is not None else None
-        guide = lazy.GuidedStep(guidance) if guidance is not None else None
+        guide = (lazy.ThresholdedStep if thresholded else lazy.GuidedStep)(guidance) if guidance is not None else None
         if prog is not None and prog is not False:
             record = prog.run(roles, step, prediction, sample.device)
             if record is not None and self._run_seq and (self._index, idx) not in self._fast:
@@ -960,7 +1023,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
                 with lazy.compute_scale(self.compute_scale), (blend if one_launch else contextlib.nullcontext()), (guide if guide is not None else contextlib.nullcontext()):
                     record = self.sampler.sample_packed(
                         SampleInput(sample=sample, prediction=prediction, step=step, noise=noise),
-                        model_transform=self.model,
+                        model_transform=_DATA_MODEL if thresholded else self.model,
                         schedule=self.schedule,
                         previous=self._previous,
                     )
@@ -968,8 +1031,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
                         record = dataclasses.replace(record, final=blend.settle(lift(record.final), getattr(record.final, "dtype", None)))
                 if guide is not None:
                     # the record that goes into history holds the stored tensor, as the unfused run's does (negated lazily under invert_prediction)
-                    model_output = guide.guided if guide.used else lazy.guide_only(guidance)
-                    record = dataclasses.replace(record, prediction=LazyTensor(-Lin.leaf(model_output), model_output.dtype) if self.invert_prediction else model_output)
+                    model_output = guide.guided if guide.used else (lazy.threshold_only(guidance) if thresholded else lazy.guide_only(guidance))
+                    record = dataclasses.replace(record, prediction=LazyTensor(-Lin.leaf(model_output), model_output.dtype) if invert else model_output)
                 if tracing:
                     built = program.StepProgram.build(_hip.trace[0], roles, record, prediction) if len(_hip.trace) == 1 else None
                     self._programs[key] = built if built is not None else False

@@ -320,6 +320,10 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
+    if getattr(wrapper, "_thresholding_next", None) is not None or getattr(wrapper, "_thresholding", None) is not None:
+        from . import _hip
+
+        raise _hip.SkrampleHipError(_hip.THRESHOLD_NO_ROWS)  # (a quantile per step: two launches whose first has no row form)
     if guidance_rescale != 0.0 and guidance_scale is None:
         raise ValueError("guidance_rescale belongs to a guided loop: pass guidance_scale= as well")
     if rescaled and not indexed:

@@ -261,6 +261,8 @@ class RollingBatch:
                              f"(ragged samples are served from {PER_SAMPLE_CHUNK} elements on, in multiples of 8)")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
+        if getattr(first, "_thresholding_next", None) is not None or getattr(first, "_thresholding", None) is not None:
+            raise SkrampleHipError(_hip.THRESHOLD_NO_ROWS)  # (before anything is allocated)
         if self.ragged:
             self._refuse_ragged(first)
         if self.guided:

@@ -323,6 +323,8 @@ class Lin:
                     raise SkrampleHipError("a rounded conversion can only be consumed by the launch that stores it")
                 if isinstance(leaf.form, Guidance):
                     raise SkrampleHipError("a guided prediction is not a linear form: it is settled by evaluate_guided()")
+                if isinstance(leaf.form, Threshold):
+                    raise SkrampleHipError("a thresholded prediction is not a linear form: it is settled by evaluate_thresholded()")
                 acc = acc._plus(leaf.form.expanded(keep)._scaled(c), 1.0)
             else:
                 acc = acc._plus(Lin({i: (leaf, c)}, self.shape, self.device), 1.0)
@@ -914,6 +916,130 @@ class GuidedStep:
 def pending_guidance() -> "GuidedStep | None":
     pending = _pending_guidance.get()
     return pending if pending is not None and not pending.used else None
+
+
+# ---- dynamic thresholding: the clipped, normalised data prediction in front of a step, inside its launch --------------------------------
+class Threshold:
+    """The dynamically thresholded data prediction  p = clamp(x0, -s, s) / s,  x0 = a * sample + b * output,  s = the per-sample `ratio`
+    quantile of |x0| clamped to [1, max_value]  (include/skrample_hip.h, skr_threshold_scale) as ONE leaf of a step's form, as `Guidance`
+    is: `evaluate_thresholded` computes it inside the launch that consumes it (skr_thresholded_step_launch), with one statistics launch
+    in front when max_value > 1.  `uncond` / `cond` name the output and the sample where a wrapper asks a pending prediction for its
+    operands without caring which kind it is."""
+
+    def __init__(self, output: torch.Tensor, sample: torch.Tensor, a: float, b: float, ratio: float, max_value: float):
+        if not isinstance(output, torch.Tensor) or not isinstance(sample, torch.Tensor):
+            raise SkrampleHipError(f"thresholding takes two torch tensors, not {type(output).__name__} and {type(sample).__name__}")
+        _check_tensor(output), _check_tensor(sample)
+        if output.dtype != sample.dtype or output.shape != sample.shape or output.device != sample.device:
+            raise SkrampleHipError(
+                f"thresholding needs output and sample of one dtype, shape and device: {output.dtype} {tuple(output.shape)} {output.device} vs {sample.dtype} {tuple(sample.shape)} {sample.device}"
+            )
+        if output.dtype == torch.float64:
+            raise SkrampleHipError("thresholding takes bf16, fp16 or fp32 tensors, not fp64")
+        if grad_recorded(output, sample):
+            raise SkrampleHipError("thresholding has no backward: its operands must not be recorded by autograd")
+        if output.ndim < 2 or output.numel() == 0:
+            raise SkrampleHipError(f"thresholding takes a quantile of every sample: it needs non-empty tensors of ndim >= 2 (dim 0 the sample), not {tuple(output.shape)}")
+        self.uncond = self.output = output
+        self.cond = self.sample = sample
+        self.a, self.b, self.ratio, self.max_value = float(a), float(b), float(ratio), float(max_value)
+        self.shape, self.device, self.dtype = tuple(output.shape), output.device, output.dtype
+
+    def node(self) -> "Lin":
+        n = Node(self)
+        return Lin({id(n): (n, 1.0)}, self.shape, self.device)
+
+    def expanded(self, keep=None):
+        return self
+
+    def host_value(self) -> torch.Tensor:
+        "the definition in torch ops, a sort for the order statistics (host-resident operands)"
+        n = math.prod(self.shape[1:])
+        x0 = self.sample.float() * self.a + self.output.float() * self.b  # (a Python number meets an fp32 tensor as an fp32 scalar: three rounded fp32 ops)
+        s = torch.ones(self.shape[0], dtype=torch.float32)
+        if self.max_value > 1.0:
+            mags = x0.abs().reshape(self.shape[0], n).double().sort(dim=1).values
+            r = self.ratio * (n - 1)
+            k = math.floor(r)
+            lo, hi, w = mags[:, k], mags[:, min(k + 1, n - 1)], r - k
+            s = (lo + w * (hi - lo)).float().clamp(min=1.0).clamp(max=torch.tensor(self.max_value, dtype=torch.float32).item())  # (torch's clamp keeps a NaN)
+        s = torch.where(x0.reshape(self.shape[0], n).isnan().any(dim=1), torch.full_like(s, math.nan), s).reshape((-1,) + (1,) * (len(self.shape) - 1))
+        clipped = torch.where(x0 < -s, -s.expand_as(x0), x0)
+        clipped = torch.where(clipped > s, s.expand_as(x0), clipped)
+        return (clipped / s).to(self.dtype)
+
+    def device_scale(self, o: torch.Tensor, x: torch.Tensor) -> "torch.Tensor | None":
+        "the statistics launch over contiguous 16-byte aligned device operands: float32[samples], or None where s is identically 1"
+        if self.max_value <= 1.0:
+            return None
+        scale = torch.empty(self.shape[0], dtype=torch.float32, device=self.device)
+        _hip.launch_threshold_scale(x, o, self.a, self.b, self.ratio, self.max_value, o.numel() // self.shape[0], scale)
+        return scale
+
+
+def threshold_only(thr: Threshold) -> torch.Tensor:
+    "the thresholded prediction as a tensor of its own: the statistics launch and the thresholding-only launch on the HIP device, torch's ops on the host"
+    if is_host(thr.device):
+        return thr.host_value().contiguous()
+    o, x = _prepare_tensor(thr.output), _prepare_tensor(thr.sample)
+    out = empty_output(thr.shape, thr.dtype, thr.device)
+    plan = _hip.StepPlanC()
+    plan.n_terms = plan.n_group_a = 2
+    plan.dtype_a = plan.dtype_b = _hip.DTYPE_CODE[thr.dtype]
+    plan.out0_dtype = plan.out1_dtype = _hip.NONE
+    numel = math.prod(thr.shape)
+    _hip.launch_step_thresholded(plan, [o, x], None, out, thr.device_scale(o, x), thr.a, thr.b, numel // thr.shape[0], 0, 1, None, numel, thr.device)
+    return out
+
+
+def evaluate_thresholded(form: Lin, thr: Threshold, dtype: torch.dtype | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(final, p): `form`, which holds `thr.node()` wherever the prediction stands, and the thresholded prediction itself, in ONE step
+    launch (skr_thresholded_step_launch) behind the statistics launch.  The node is lowered as the operand `output` at its natural
+    position -- the launch's `slot` --, the sample's position is `xslot`, so `final` has the bits of evaluate() over the form with the
+    tensor `p` in the node's place.  What the one launch does not cover -- the sample is no operand of the form (a last step whose
+    sample coefficient is zero), the output is one in its own right, strided operands, more than 16 operands, a wide accumulator --
+    takes `threshold_only` and then evaluate().  Host-resident operands evaluate the definition with torch and then the host executor."""
+    f = lift(form)
+    if not isinstance(f, Lin) or not isinstance(thr, Threshold):
+        raise SkrampleHipError("evaluate_thresholded() takes a tensor form and a Threshold")
+    f = f.expanded(keep=thr)
+    if any(isinstance(leaf, Node) and leaf.form is not thr for leaf, _ in f.terms.values()):
+        raise SkrampleHipError("a thresholded launch has one step output: its form cannot refer to another stored form")
+    if f.shape != thr.shape:
+        raise SkrampleHipError(f"shape mismatch between the step form {f.shape} and the thresholding operands {thr.shape}")
+    leaves = [leaf for leaf, _ in f.terms.values() if isinstance(leaf, torch.Tensor)]
+    host = [is_host(t.device) for t in (*leaves, thr.output)] + ([True] if f.device == NUMPY else [])
+    if any(host) and not all(host):
+        raise SkrampleHipError("operands of one step must all live on the HIP device or all on the host")
+    if grad_recorded(*leaves):
+        raise SkrampleHipError("thresholding has no backward: its operands must not be recorded by autograd")
+    if any(t.dtype == torch.float64 for t in leaves) or dtype == torch.float64:
+        raise SkrampleHipError("thresholding takes bf16, fp16 or fp32 tensors, not fp64")
+    out_dtype = dtype if dtype is not None else thr.dtype
+    o, x = thr.output, thr.sample
+    fused = not any(host) and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (*leaves, o, x))
+    fused = fused and id(o) not in f.terms and any(isinstance(leaf, Node) and k != 0.0 for leaf, k in f.terms.values())
+    if fused:
+        plan, operands, seeds = _lower(None, f.substitute(thr, o), None, 0.0, [out_dtype], None)
+        slot = next((k for k, t in enumerate(operands) if t is o), None)
+        xslot = next((k for k, t in enumerate(operands) if t is x), None)
+        if slot is not None and xslot is not None and len(operands) <= _hip.ROW_TERMS and not plan.acc_f64:
+            final = empty_output(f.shape, out_dtype, thr.device)
+            p = empty_output(f.shape, thr.dtype, thr.device)
+            numel = math.prod(f.shape)
+            _hip.launch_step_thresholded(plan, operands, final, p, thr.device_scale(o, x), thr.a, thr.b, numel // f.shape[0], slot, xslot, seeds, numel, thr.device)
+            return final, p
+    p = threshold_only(thr)
+    return evaluate([f.substitute(thr, p)], [out_dtype])[0], p
+
+
+class ThresholdedStep(GuidedStep):
+    "context manager: `with ThresholdedStep(thr): sampler.sample_packed(...)`; a sampler takes it up where it takes a pending guidance up"
+
+    def settle(self, form: Lin, dtype: torch.dtype | None) -> torch.Tensor:
+        self.used = True
+        final, self.guided = evaluate_thresholded(form, self.guidance, dtype)
+        return final
 
 
 # ---- guided in-painting: guidance, step and keep-region blend in one launch -------------------------------------------------------------

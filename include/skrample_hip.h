@@ -876,6 +876,81 @@ int skr_step_launch_guided_rescaled_indexed_per_sample(const skr_step_plan* plan
                                                        int32_t row_offset, void* stream);
 
 /*
+ * Dynamic thresholding in captured loops: the two launches of dynamic thresholding with everything a schedule or a thresholding
+ * setting changes taken from the row that skr_step_launch_indexed[_per_sample] reads --
+ *     indexed      rows_dev[(index_dev ? index_dev[0] : 0) + row_offset]
+ *     per sample   rows_dev[sample_index_dev[s] + row_offset]            for the workgroups of sample s
+ * A thresholded plan has convert_to == convert_from == 0, so the row's convert_k are free, as they are for guidance:
+ *     convert_k[0]  a, the to_x weight of the sample          convert_k[2]  ratio
+ *     convert_k[1]  b, the to_x weight of the network output  convert_k[3]  sample_max_value
+ * coef0, zeta0 and stream0 are read as skr_step_launch_indexed reads them; coef1, chain, zeta1 and stream1 are not read.  A captured
+ * loop then serves any schedule and any (ratio, sample_max_value) without a re-capture.  A step is the statistics launch, then the step
+ * launch, with the same index, rows and row_offset.  There is no inactive-sample semantic: every index names a row.  No entry has a
+ * grid-stride form: bf16, fp16 or fp32, sample_numel a positive multiple of 2048 that divides numel and is below 2^31, one dtype, at
+ * most SKR_ROW_TERMS operands.
+ *
+ * Bits.  For every sample, bit for bit what the direct entries give that sample alone with the row's four values and the row's
+ * coefficients, zeta and stream: scale_dev[s];  out and x0_out;  and the sample's part of the workspace that the finish reads -- its
+ * histogram, its NaN count, its cursor and its candidates (as a set with multiplicities: the list's order is free in either entry).
+ * Rank.  The device forms r = ratio * (n - 1), k = floor(r), k1 = min(k + 1, n - 1) and w = r - k in double: one multiplication, one
+ * floor, one subtraction, nothing contracted -- the IEEE operations skr_threshold_scale makes on the host, which is why the bits agree.
+ * a, b, the maximum, coef0 and zeta0 are narrowed to fp32 once on the device, round to nearest even: the host's (float) cast.
+ * Plain-clip row.  A row whose convert_k[3] <= 1 -- where the eager path skips the statistic and passes a NULL scale_dev.  Every
+ * workgroup of the statistics launch that reads the row, in all four kernels, returns before its first vector-memory instruction (in
+ * the indexed form every workgroup of the launch): scale_dev[s] and the sample's part of the workspace keep their bytes.  The step kernel
+ * takes s = 1 by a branch uniform over the workgroup and does NOT read scale_dev[s], which may be uninitialised or NaN.  In a per-sample
+ * launch a plain-clip sample costs no statistics traffic beside neighbours that select.
+ * Row validity is the caller's business, as index validity is (skrample_amd.graphs.CapturedLoop validates ratio in (0, 1] and a positive
+ * finite maximum on the host before a row is written).  No row value makes a kernel store outside its buffers: the histogram and
+ * candidate passes address the workspace by sample and by the 11 top bits of a magnitude; a rank past the total finds no bin and
+ * leaves zero (find_rank), and k is clamped to n - 1 on the device; the candidate store is bounded by sample_numel whatever the
+ * histogram holds; the finish reads at most sample_numel candidates and writes scale_dev[s] alone.  A NaN ratio gives k = 0; a NaN
+ * maximum selects and is kept by the clamp's comparisons.  Such rows give meaningless scales, nothing else.
+ *
+ * skr_threshold_scale_indexed[_per_sample]: skr_threshold_scale without a, b, ratio and sample_max_value.  The workspace is
+ * SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes in skr_threshold_scale's layout; the clearing is one workgroup per sample, so that
+ * a plain-clip sample's part is not touched.  Checked before any launch, without dereferencing device memory, in this order: a NULL
+ * sample, output, scale_dev, workspace_dev or rows_dev -- or a NULL sample_index_dev in the per-sample entry; index_dev may be NULL --
+ * SKR_ERR_NULL;  numel < 0, sample_numel < 1 or sample_numel not dividing numel SKR_ERR_SHAPE;  numel == 0 SKR_OK with nothing launched;
+ * sample, output or workspace_dev not 16-byte aligned, scale_dev not 4-byte aligned SKR_ERR_ALIGN;  a dtype other than bf16, fp16 or
+ * fp32 SKR_ERR_DTYPE;  sample_numel % 2048 != 0, a negative row_offset, sample_numel >= 2^31 or more than INT32_MAX workgroups
+ * SKR_ERR_UNSUPPORTED.  Allocates nothing, never synchronises: capturable.
+ */
+int skr_threshold_scale_indexed(const void* sample, const void* output, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                const skr_step_row* rows_dev, const int32_t* index_dev /* device int32, may be NULL */, int32_t row_offset,
+                                float* scale_dev /* [numel / sample_numel] */,
+                                void* workspace_dev /* SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes */, void* stream);
+
+int skr_threshold_scale_indexed_per_sample(const void* sample, const void* output, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                           const skr_step_row* rows_dev,
+                                           const int32_t* sample_index_dev /* device int32[numel / sample_numel] */, int32_t row_offset,
+                                           float* scale_dev /* [numel / sample_numel] */,
+                                           void* workspace_dev /* SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes */, void* stream);
+
+/*
+ * skr_thresholded_step_launch_indexed[_per_sample]: skr_thresholded_step_launch's one-trip kernel with the row's values.  thr->a and
+ * thr->b are ignored (row values), and so are the plan's coef0, chain, zeta and stream values; plan->noise_mode == 1 means "a row may
+ * draw": a row whose zeta0 narrows to zero skips the draw, as in skr_step_launch_indexed.  The thresholding-only form (out0_dtype ==
+ * SKR_NONE, out == NULL, two operands) is taken too, so that the two-output samplers capture: their own step then runs through
+ * skr_step_launch_indexed over the stored p.  The row's scalars arrive by scalar loads behind the operand loads.
+ * Checks, their order and their codes are skr_thresholded_step_launch's, with on top of them, where the rescaled row entries put
+ * theirs: a NULL rows_dev -- or sample_index_dev in the per-sample entry -- SKR_ERR_NULL (beside the NULL plan);  a NULL
+ * thr->scale_dev SKR_ERR_NULL (beside the NULL operands: a row may select);  and, behind the dtype checks, SKR_ERR_UNSUPPORTED for a
+ * negative row_offset and for every launch the one-trip kernel does not take (numel or thr->sample_numel not whole 2048-element chunks,
+ * thr->sample_numel >= 2^31, two dtype groups, fewer than two operands, "one_trip" 0).  A non-zero plan->chain or zeta1 is not refused:
+ * the plan's scalars are not read.
+ */
+int skr_thresholded_step_launch_indexed(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_threshold* thr,
+                                        const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                        const int32_t* index_dev /* device int32, may be NULL */, int32_t row_offset, void* stream);
+
+int skr_thresholded_step_launch_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out,
+                                                   const skr_step_threshold* thr, const uint64_t* seeds_dev, int64_t numel,
+                                                   const skr_step_row* rows_dev,
+                                                   const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                                   int32_t row_offset, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

@@ -52,6 +52,10 @@ EXPORTS = (
     "skr_guided_masked_step_launch",
     "skr_threshold_scale",
     "skr_thresholded_step_launch",
+    "skr_threshold_scale_indexed",
+    "skr_threshold_scale_indexed_per_sample",
+    "skr_thresholded_step_launch_indexed",
+    "skr_thresholded_step_launch_indexed_per_sample",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -359,6 +363,11 @@ class IndexedRows:
     `batch` (a per-sample capture): the emitted launches are skr_step_launch_indexed_per_sample launches, and `sample_index_dev`
     -- int32[batch], beside `index_dev` -- holds every sample's `slot * length`; sample b of the captured batch reads row
     `sample_index_dev[b] + k`.
+    `thresholded` (`samples`: the captured batch): thresholded step launches go through the recorder (launch_thresholded), each row carrying
+    the to_x weights, the ratio and the maximum in convert_k[0..3].  Every emitted thresholded step is TWO launches on buffers the hook owns
+    (`scale`, `workspace`), with the same row offset: skr_threshold_scale_indexed[_per_sample], then
+    skr_thresholded_step_launch_indexed[_per_sample] -- whether or not the recording pass took a quantile, since a row whose maximum is
+    <= 1 makes the first return at once and the second the plain clip.
     `guided` (a capture with guidance): guided launches go through the recorder as well (skr_step_launch_guided_indexed[_per_sample]),
     each row carrying its launch's guidance scale.
     `rescaled` (with `guided`; `samples`: the captured batch): rescaled guided launches go through it too, each row carrying
@@ -377,7 +386,16 @@ class IndexedRows:
     mode "refill": launches run normally (on whatever tensors the dry run uses) and overwrite row `slot*length + k` after checking
                    that the structure is the captured one -- how a captured loop is re-targeted to another schedule."""
 
-    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None, guided: bool = False, rescaled: bool = False, samples: int | None = None):
+    def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None, guided: bool = False, rescaled: bool = False, samples: int | None = None,
+                 thresholded: bool = False):
+        if thresholded and (samples is None or samples < 1):
+            raise ValueError("thresholded=True needs samples=: the captured batch, one scale per sample")
+        if thresholded and batch is not None and batch != samples:
+            raise ValueError(f"a per-sample capture of {batch} samples cannot hold scales for {samples}")
+        # a capture with dynamic thresholding: the scale float32[samples] and the workspace of every emitted statistics launch
+        self.thresholded = thresholded
+        self.scale: torch.Tensor | None = None
+        self.workspace: torch.Tensor | None = None
         if rescaled and not guided:
             raise ValueError("rescaled=True needs guided=True: guidance_rescale is applied to the guided prediction a guided launch forms")
         if rescaled and (samples is None or samples < 1):
@@ -487,6 +505,73 @@ class IndexedRows:
         if plan.sample_numel > 0 and plan.sample_numel != numel // self.samples:
             return f"rescaled guided rows take the statistic over the samples the noise is drawn by: {numel // self.samples} elements, not {plan.sample_numel}"
         return None
+
+    def _uncovered_thresholded(self, plan: StepPlanC, thr: "StepThresholdC", numel: int) -> str | None:
+        "why the thresholded row kernels do not cover this launch of the captured batch (skr_thresholded_step_launch_indexed), or None"
+        if plan.acc_f64:
+            return "thresholded rows are evaluated in float32, not under compute_scale=float64"
+        one = plan.dtype_a
+        if one not in (BF16, F16, F32) or (plan.n_group_a != plan.n_terms and plan.dtype_b != one) or plan.out0_dtype not in (one, NONE):
+            return "thresholded rows need one 16- or 32-bit dtype for operands, prediction and output"
+        if numel % self.samples != 0 or (numel // self.samples) % PER_SAMPLE_CHUNK != 0:
+            return f"thresholded rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {numel} elements for {self.samples} samples (ragged samples have no thresholded row form)"
+        if thr.sample_numel != numel // self.samples:
+            return f"thresholded rows take the quantile over the samples of the captured batch: {numel // self.samples} elements, not {thr.sample_numel}"
+        if not 2 <= plan.n_terms <= ROW_TERMS:
+            return f"thresholded rows take 2 to {ROW_TERMS} operands, not {plan.n_terms}"
+        return None
+
+    def launch_thresholded(self, lib, plan: StepPlanC, arr, out_ptr, thr: "StepThresholdC", ratio: float, max_value: float, seeds_ptr, numel: int, stream_ptr: int) -> int:
+        """one thresholded step launch of the loop (skr_thresholded_step_launch and its row forms): recorded or refilled with the to_x weights,
+        the ratio and the maximum in the row's convert_k[0..3], emitted as the statistics row launch and the row step on the hook's buffers"""
+        k = self.cursor
+        self.cursor += 1
+        if not (0.0 < ratio <= 1.0) or not (0.0 < max_value < float("inf")):  # (before a row is written: the kernels trust their rows)
+            raise SkrampleHipError(f"launch {k}: a thresholded row needs a ratio in (0, 1] and a positive finite maximum, not {ratio} and {max_value}")
+
+        def structure(shaped: bool) -> tuple:
+            return (*plan_structure(plan, sample_numel=shaped), "thresholded", thr.slot, thr.xslot, bool(thr.x0_out), thr.sample_numel if shaped else None)
+
+        def direct() -> int:  # the launch itself, with the plan's own scalars and the caller's scale
+            return lib.skr_thresholded_step_launch(ctypes.byref(plan), arr, out_ptr, ctypes.byref(thr), seeds_ptr, numel, stream_ptr)
+
+        row = self.row_from(plan)
+        row.convert_k[0], row.convert_k[1], row.convert_k[2], row.convert_k[3] = thr.a, thr.b, ratio, max_value
+        if self.mode == "record":
+            why = self._uncovered_thresholded(plan, thr, numel)
+            if why is not None:  # (what skr_thresholded_step_launch_indexed would answer during the capture: said here, before a stream is capturing)
+                raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
+            size = threshold_workspace(numel, thr.sample_numel)
+            if self.scale is None:  # allocated here, before a stream captures; every emitted step of the graph uses these two
+                self.scale = torch.zeros(self.samples, dtype=torch.float32, device=self.device)
+                self.workspace = torch.zeros(size, dtype=torch.uint8, device=self.device)
+                self.threshold_dtype = plan.dtype_a
+            elif self.threshold_dtype != plan.dtype_a or self.workspace.numel() != size:
+                raise SkrampleHipError(f"launch {k}: the thresholded steps of one capture share one scale and one workspace: one dtype and one size")
+            self.structures.append(structure(True))
+            self.shapeless.append(structure(False))
+            self.host.append(row)
+            return direct()
+        if k >= self.length:
+            raise SkrampleHipError("more launches than the captured loop has")
+        if self.mode == "refill":
+            if structure(False) != self.shapeless[k]:
+                raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
+            self.host[self.slot * self.length + k] = row
+            return direct()
+        if structure(True) != self.structures[k]:
+            raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
+        # emit: the statistics row launch over (sample, output), then the row step, on the hook's scale and workspace and with the same row
+        # offset.  A row whose maximum is <= 1 makes the first return before it reads anything and the second the plain clip.
+        per_sample = self.sample_index_dev is not None
+        suffix = "_indexed_per_sample" if per_sample else "_indexed"
+        table = (self.rows_dev.data_ptr(), (self.sample_index_dev if per_sample else self.index_dev).data_ptr(), k)
+        status = getattr(lib, "skr_threshold_scale" + suffix)(arr[thr.xslot], arr[thr.slot], plan.dtype_a, numel, thr.sample_numel, *table, self.scale.data_ptr(),
+                                                              self.workspace.data_ptr(), stream_ptr)  # fmt: skip
+        if status != 0:
+            return status
+        held = StepThresholdC(self.scale.data_ptr(), thr.x0_out, 0.0, 0.0, thr.sample_numel, thr.slot, thr.xslot, 0)  # (a and b are the row's)
+        return getattr(lib, "skr_thresholded_step_launch" + suffix)(ctypes.byref(plan), arr, out_ptr, ctypes.byref(held), seeds_ptr, numel, *table, stream_ptr)
 
     def launch(self, lib, plan: StepPlanC, arr, out0_ptr, out1_ptr, seeds_ptr, numel: int, stream_ptr: int, mask: "StepMaskC | None" = None,
                guide: "StepGuidanceC | None" = None, rescale: "StepRescaleC | None" = None) -> int:
@@ -654,6 +739,11 @@ def load() -> ctypes.CDLL:
         lib.skr_threshold_scale.restype = ctypes.c_int
         lib.skr_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepThresholdC), vp, i64, vp]
         lib.skr_thresholded_step_launch.restype = ctypes.c_int
+        for suffix in ("_indexed", "_indexed_per_sample"):  # (their row forms: the direct arguments without the row values, the table where the rescaled row entries have it)
+            entry = getattr(lib, "skr_threshold_scale" + suffix)
+            entry.argtypes, entry.restype = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp], ctypes.c_int
+            entry = getattr(lib, "skr_thresholded_step_launch" + suffix)
+            entry.argtypes, entry.restype = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepThresholdC), vp, i64, vp, vp, i32, vp], ctypes.c_int
         lib.skr_rolling_advance.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
         lib.skr_rolling_advance.restype = ctypes.c_int
         lib.skr_step_backward_launch.argtypes = [ctypes.POINTER(StepGradPlanC), vp, vp, ctypes.POINTER(vp), i64, vp]
@@ -901,15 +991,27 @@ def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], o
                          sample_numel=sample_numel), device)  # fmt: skip
 
 
-THRESHOLD_NO_ROWS = "dynamic thresholding (set_thresholding) has no row form: capture_sampling_loop and RollingBatch do not take a thresholding wrapper"
+THRESHOLD_NO_ROWS = ("dynamic thresholding (set_thresholding) has no row form in a loop captured without it: pass thresholded=True to capture_sampling_loop (the to_x weights, "
+                     "the ratio and the maximum are then row values); RollingBatch does not take a thresholding wrapper")
+
+
+def _threshold_hook() -> "IndexedRows | None":
+    "the installed indexed-rows hook, which must have been created for dynamic thresholding (capture_sampling_loop with `thresholded=True`)"
+    rows = getattr(_hooks, "indexed", None)
+    if rows is not None and not getattr(rows, "thresholded", False):
+        raise SkrampleHipError(THRESHOLD_NO_ROWS)
+    return rows
 
 
 def launch_threshold_scale(sample: torch.Tensor, output: torch.Tensor, a: float, b: float, ratio: float, sample_max_value: float, sample_numel: int, scale: torch.Tensor) -> None:
     """the statistics launch of dynamic thresholding (skr_threshold_scale): scale[s] = min(max(q_s, 1), sample_max_value) with q_s the `ratio`
     quantile of |a * sample + b * output| over sample s of `sample_numel` elements -- an exact radix select; `scale` is float32[samples].
-    It has no row form: under an indexed-rows hook it raises."""
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError(THRESHOLD_NO_ROWS)
+    Under an indexed-rows hook created for a thresholded capture (IndexedRows(thresholded=True)) it runs as it stands while the hook records
+    or refills, and is NOT issued while the hook emits: the step launch that follows emits the statistics row launch itself, on the hook's
+    buffers.  Under any other hook it raises."""
+    rows = _threshold_hook()
+    if rows is not None and rows.mode == "emit":
+        return
     numel, device = sample.numel(), sample.device
     workspace = torch.empty(threshold_workspace(numel, sample_numel), dtype=torch.uint8, device=device)  # (torch's allocator: 16-byte aligned, safe under capture)
     status = load().skr_threshold_scale(sample.data_ptr(), output.data_ptr(), DTYPE_CODE[sample.dtype], float(a), float(b), float(ratio), float(sample_max_value), numel,
@@ -918,13 +1020,19 @@ def launch_threshold_scale(sample: torch.Tensor, output: torch.Tensor, a: float,
 
 
 def launch_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor], out, x0_out, scale: "torch.Tensor | None", a: float, b: float, sample_numel: int, slot: int, xslot: int,
-                            seeds, numel: int, device: torch.device) -> None:
+                            seeds, numel: int, device: torch.device, ratio: "float | None" = None, max_value: "float | None" = None) -> None:
     """one thresholded step launch (skr_thresholded_step_launch): operands[slot] is the network output, operands[xslot] the sample, and
     p = clamp(a * sample + b * output, -s, s) / s with s = scale[sample index] (1 when `scale` is None) takes the output's place in the step's
     sum; `x0_out` (or None) receives p.  `out` None with a plan whose out0_dtype is NONE and two operands is the thresholding-only form.
-    It has no row form: under an indexed-rows hook it raises."""
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError(THRESHOLD_NO_ROWS)
+    Under an indexed-rows hook created for a thresholded capture the launch is recorded, emitted as skr_threshold_scale_indexed[_per_sample]
+    plus skr_thresholded_step_launch_indexed[_per_sample] -- a, b, `ratio` and `max_value` (both required there) row values, `scale`
+    replaced by the hook's own -- or refilled (IndexedRows.launch_thresholded).  Under any other hook it raises."""
+    rows = _threshold_hook()
     thr = StepThresholdC(_ptr(scale), _ptr(x0_out), float(a), float(b), int(sample_numel), int(slot), int(xslot), 0)
-    status = load().skr_thresholded_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(thr), _ptr(seeds), numel, current_stream_ptr(device))
+    if rows is not None:
+        if ratio is None or max_value is None:
+            raise SkrampleHipError("a thresholded launch of a captured loop carries its ratio and its maximum: they are row values")
+        status = rows.launch_thresholded(load(), plan, _operand_array(operands), _ptr(out), thr, float(ratio), float(max_value), _ptr(seeds), numel, current_stream_ptr(device))
+    else:
+        status = load().skr_thresholded_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(thr), _ptr(seeds), numel, current_stream_ptr(device))
     check(status, "skr_thresholded_step_launch")

@@ -715,6 +715,10 @@ int launch_one_trip_two(const StepArgs<float>& args, bool noise, bool group_b_f3
   if (noise && na + nb <= 7 && g_tune.two_out != 2 && !table) return SKR_OK;
   int bps_shift = 0;
   if (!one_trip_ok(args.numel, args.sample_numel, noise, args.form, &bps_shift)) return SKR_OK;
+  // 3 + 1 is no count of the list: UniPC over a DATA prediction (a thresholded step: the stored p stands for the output and for x0 alike)
+  // emits it from its second step on.  It is instantiated for the table forms alone, which have no other kernel to go to (unpaced,
+  // write-through); a direct launch keeps the general kernel it has always taken.
+  if (table && na == 3 && nb == 1) { taken = true; return launch_k2_as<TA, 3, 1, false>(args, noise, bps_shift, stream); }
   return launch_k2_of<TA>(TwoOutCounts{}, na, nb, args, noise, bps_shift, stream, taken);
 }
 template int launch_one_trip_two<bf16_t>(const StepArgs<float>&, bool, bool, hipStream_t, bool&);

@@ -40,6 +40,15 @@ launch and the rescaled row step (`skr_guidance_rescale_factor_indexed[_per_samp
 on one factor tensor and one workspace the loop owns, `retarget(wrapper, slot, guidance_rescale=...)` loads another phi -- 0.0 included,
 which makes the first launch return at once and the second the plain guided step -- and with `per_sample=True` every sample follows its
 own.  Without `rescaled=True` an indexed capture refuses a non-zero `guidance_rescale`, as before.
+
+Dynamic thresholding (`wrapper.set_thresholding(ratio, sample_max_value)`) is captured on request, `thresholded=True`.  A plain capture
+records the eager launches -- the radix-select statistic and the thresholded step -- and freezes the to_x weights, the ratio and the maximum
+into the graph.  An indexed capture keeps all four in the rows (`convert_k[0..3]`): every thresholded step of the graph is the statistics
+row launch and the row step (`skr_threshold_scale_indexed[_per_sample]`, `skr_thresholded_step_launch_indexed[_per_sample]`) on one scale
+tensor and one workspace the loop owns, `retarget(wrapper, slot)` loads the new wrapper's schedule AND its thresholding setting -- a
+maximum <= 1 included, the plain clip, which makes the first launch return at once -- and with `per_sample=True` every sample follows its
+own.  UniPC and SPC take the thresholding-only row launch and then their step through the plain row launches.  Without the keyword a
+thresholding wrapper is refused, as before.
 """
 
 from __future__ import annotations
@@ -72,7 +81,8 @@ class CapturedLoop:
 
     def __init__(self, graph: torch.cuda.CUDAGraph, static_in: torch.Tensor, static_out: torch.Tensor, seeds_dev: torch.Tensor | None, rows=None, runner=None,
                  static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None, inpaint: tuple | None = None,
-                 guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False):
+                 guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False, thresholded: bool = False):
+        self.thresholded = thresholded  # captured with thresholded=True: retarget takes thresholding wrappers, and only those
         self.guidance_scale = guidance_scale  # the scale the loop was captured with, or None: a loop captured without guidance
         # the phi the loop was captured with, and whether it is a row value (captured with rescaled=True) that retarget may replace
         self.guidance_rescale, self.rescaled = guidance_rescale, rescaled
@@ -133,11 +143,16 @@ class CapturedLoop:
         A loop captured with `rescaled=True` loads a phi too: `guidance_rescale`, or the captured one when None; 0.0 turns the rescale
         off for that slot.  On any other loop a `guidance_rescale` is refused: its phi, if any, is frozen into the graph.
         A loop captured with in-painting takes a wrapper that has `set_inpaint(...)` in force itself (the dry run steps on one-sample
-        views of ITS tensors); only its scalars reach the graph, which goes on reading `loop.inpaint`."""
+        views of ITS tensors); only its scalars reach the graph, which goes on reading `loop.inpaint`.
+        A loop captured with `thresholded=True` takes a wrapper with `set_thresholding(...)` in force and loads its ratio and its
+        sample_max_value beside its schedule; both may differ from the captured ones, and a maximum <= 1 is the plain-clip row."""
         from . import _hip
 
         if self.rows is None:
             raise ValueError("capture the loop with indexed=True to re-target it")
+        if self.thresholded and getattr(wrapper, "_thresholding_next", None) is None:
+            raise ValueError("this loop was captured with thresholded=True: retarget takes a wrapper with set_thresholding(ratio, sample_max_value) in force "
+                             "(a sample_max_value <= 1 is the plain clip)")
         if not 0 <= slot < self.rows.slots:
             raise ValueError(f"slot {slot} outside 0..{self.rows.slots - 1}")
         if guidance_scale is not None and self.guidance_scale is None:
@@ -270,7 +285,7 @@ class CapturedLoops:
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
                           indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False,
-                          guidance_scale: float | None = None, rescaled: bool = False, guidance_rescale: float = 0.0) -> CapturedLoop:
+                          guidance_scale: float | None = None, rescaled: bool = False, thresholded: bool = False, guidance_rescale: float = 0.0) -> CapturedLoop:
     """Capture `for t in wrapper.timesteps: x = wrapper.step(model(x, t), t, x)` for `steps` steps.
 
     `wrapper` is any scheduler wrapper of skrample_amd.diffusers; `model(x, t)` must be capturable (pure device
@@ -317,13 +332,26 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     another phi, zero included, and with `per_sample=True` every sample follows its own.  On top of what a guided indexed capture needs,
     every sample must be made of whole 2048-element chunks.  Anything else is refused during the recording pass, before the stream
     captures.
+
+    `thresholded` (a keyword, like `rescaled`; off by default, and then a wrapper with `set_thresholding` in force is refused, as before):
+    the wrapper's dynamic thresholding is captured.  With `indexed=False` the statistic and the thresholded step are recorded as the eager
+    step issues them, everything frozen into the graph; every sampler and `step_guided` are served.  With `indexed=True` the to_x weights,
+    the ratio and the maximum are row values (`loop.retarget(wrapper, slot)` loads another wrapper's; per sample with `per_sample=True`):
+    every thresholded step is the statistics row launch and the row step on one scale tensor `[batch]` and one workspace the loop owns.
+    The row kernels must cover the launches: contiguous latents in samples of whole 2048-element chunks, one 16- or 32-bit dtype, a
+    compute scale other than None / float64, no autograd.  `step_guided` under thresholding is refused in an indexed capture (its
+    guidance-only launch has no row form); `set_inpaint` beside thresholding is refused by the wrapper itself.  A wrapper without
+    thresholding is a ValueError.
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
-    if getattr(wrapper, "_thresholding_next", None) is not None or getattr(wrapper, "_thresholding", None) is not None:
+    thresholding = getattr(wrapper, "_thresholding_next", None) is not None
+    if not thresholded and (thresholding or getattr(wrapper, "_thresholding", None) is not None):
         from . import _hip
 
-        raise _hip.SkrampleHipError(_hip.THRESHOLD_NO_ROWS)  # (a quantile per step: two launches whose first has no row form)
+        raise _hip.SkrampleHipError(_hip.THRESHOLD_NO_ROWS)  # (a quantile per step: two launches, captured on request only)
+    if thresholded and not thresholding:
+        raise ValueError("thresholded=True captures a wrapper's dynamic thresholding: call wrapper.set_thresholding(ratio, sample_max_value) first")
     if guidance_rescale != 0.0 and guidance_scale is None:
         raise ValueError("guidance_rescale belongs to a guided loop: pass guidance_scale= as well")
     if rescaled and not indexed:
@@ -334,13 +362,13 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
 
     _noise._private_vectors[0] += 1  # the loop's seed vector is overwritten in place by replays with new seeds: it is this loop's alone
     try:
-        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale, rescaled)
+        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale, rescaled, thresholded)
     finally:
         _noise._private_vectors[0] -= 1
 
 
 def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False,
-             guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False) -> CapturedLoop:
+             guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False, thresholded: bool = False) -> CapturedLoop:
     dev = example.device
     static_in = example.clone()
     gen = list(seeds) if seeds is not None else None
@@ -405,7 +433,7 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
         from . import _hip
 
         rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None, guided=guidance_scale is not None,
-                                rescaled=rescaled, samples=int(example.shape[0]))  # (samples: the factor's size, and the sample size of a ragged launch without noise)
+                                rescaled=rescaled, samples=int(example.shape[0]), thresholded=thresholded)  # (samples: the factor's and the scale's size, and the sample size of a ragged launch without noise)
         _hip.indexed = rows
         try:
             rows.begin("record")
@@ -428,4 +456,4 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     from .pytorch.noise import forget_seed_vector
 
     forget_seed_vector(seeds_dev)  # the graph reads this very buffer and replays may overwrite it: no other run may share it from now on
-    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale, guidance_rescale, rescaled)
+    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale, guidance_rescale, rescaled, thresholded)

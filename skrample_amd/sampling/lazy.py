@@ -988,7 +988,8 @@ def threshold_only(thr: Threshold) -> torch.Tensor:
     plan.dtype_a = plan.dtype_b = _hip.DTYPE_CODE[thr.dtype]
     plan.out0_dtype = plan.out1_dtype = _hip.NONE
     numel = math.prod(thr.shape)
-    _hip.launch_step_thresholded(plan, [o, x], None, out, thr.device_scale(o, x), thr.a, thr.b, numel // thr.shape[0], 0, 1, None, numel, thr.device)
+    _hip.launch_step_thresholded(plan, [o, x], None, out, thr.device_scale(o, x), thr.a, thr.b, numel // thr.shape[0], 0, 1, None, numel, thr.device,
+                                 ratio=thr.ratio, max_value=thr.max_value)
     return out
 
 
@@ -1027,7 +1028,8 @@ def evaluate_thresholded(form: Lin, thr: Threshold, dtype: torch.dtype | None = 
             final = empty_output(f.shape, out_dtype, thr.device)
             p = empty_output(f.shape, thr.dtype, thr.device)
             numel = math.prod(f.shape)
-            _hip.launch_step_thresholded(plan, operands, final, p, thr.device_scale(o, x), thr.a, thr.b, numel // f.shape[0], slot, xslot, seeds, numel, thr.device)
+            _hip.launch_step_thresholded(plan, operands, final, p, thr.device_scale(o, x), thr.a, thr.b, numel // f.shape[0], slot, xslot, seeds, numel, thr.device,
+                                         ratio=thr.ratio, max_value=thr.max_value)
             return final, p
     p = threshold_only(thr)
     return evaluate([f.substitute(thr, p)], [out_dtype])[0], p

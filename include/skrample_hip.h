@@ -951,6 +951,42 @@ int skr_thresholded_step_launch_indexed_per_sample(const skr_step_plan* plan, co
                                                    int32_t row_offset, void* stream);
 
 /*
+ * Dynamic thresholding in rolling batches: the two launches for the slots of a rolling batch (skr_step_launch_rolling), with the
+ * arguments of the per-sample entries above.  Slot b reads rows_dev[sample_index_dev[b] + row_offset]; a NEGATIVE entry, tested before
+ * row_offset is added, marks an inactive slot.  The row's values, the rank, the plain-clip row and the bits of an active slot are those
+ * of the per-sample entries: a slot's scale_dev[b], out and x0_out are what the direct entries give that sample alone, whatever the
+ * capacity, the grid or the neighbours (the statistic is integer counting).
+ *
+ * skr_threshold_scale_rolling.  In all four kernels a workgroup loads its slot's index entry, tests the sign and ends: before any
+ * vector-memory instruction and, in the histogram pass, before the LDS clearing.  An inactive slot keeps every byte of scale_dev[b] and
+ * of its part of the workspace (histogram, counters, candidates); so does a plain-clip slot.  The grid is a function of numel and
+ * sample_numel alone.  The rolling form pays one scalar round trip (the index entry) in front of the histogram pass's clearing, where
+ * the per-sample form runs both of its round trips under it.  Checks, order and codes: skr_threshold_scale_indexed_per_sample's.
+ *
+ * skr_thresholded_step_launch_rolling.  The row is fetched in FRONT of the loads.  An inactive slot's workgroups end before their first
+ * vector-memory instruction: its slices of out and x0_out keep their bytes.  inputs[thr->slot] and inputs[thr->xslot] are read for
+ * every active slot.  p is summed with the row's coefficient at slot; the sample is summed unless both of its coefficients are exactly
+ * zero (a step whose form does not hold it: an Inf or NaN sample element then reaches out only through p, as in the two launches the
+ * eager path makes for such a step).  Any other operand is present unless both of its coefficients are exactly
+ * zero (either sign); an absent operand is neither loaded nor summed -- its pointer must still be a valid 16-byte aligned address --,
+ * and present operands are summed from zero in slot order: a request in its multistep ramp-up has the bits of the narrower
+ * skr_thresholded_step_launch that holds exactly its operands.  All of 2 .. SKR_ROW_TERMS operands are instantiated; 16-bit launches of
+ * more than 12 keep 12 loads in flight; 32-bit launches load their last operand (4 operands) or last two (5 and more) behind the first
+ * sums, which keeps every instantiation at or above the occupancy of its per-sample twin.  There is no thresholding-only form: out0_dtype == SKR_NONE is SKR_ERR_UNSUPPORTED (beside
+ * the one-trip test).  Every other check, its place and its code are skr_thresholded_step_launch_indexed_per_sample's.
+ */
+int skr_threshold_scale_rolling(const void* sample, const void* output, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                const skr_step_row* rows_dev,
+                                const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */, int32_t row_offset,
+                                float* scale_dev /* [numel / sample_numel] */,
+                                void* workspace_dev /* SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes */, void* stream);
+
+int skr_thresholded_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_threshold* thr,
+                                        const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                        const int32_t* sample_index_dev /* device int32[numel / sample_numel], < 0: inactive */,
+                                        int32_t row_offset, void* stream);
+
+/*
  * A solver step replayed one rounded tensor operation at a time -- the reference's arithmetic when its samplers are called on tensors
  * directly (StructuredSampler.sample, skrample/sampling/structured.py:70-86 with :167-497 and models.py:53-224; no scheduler wrapper,
  * or a wrapper with compute_scale=None): every `*`, `+`, `-`, `/` is a torch op of its own in the TENSOR dtype -- operands widened to the

@@ -56,6 +56,8 @@ EXPORTS = (
     "skr_threshold_scale_indexed_per_sample",
     "skr_thresholded_step_launch_indexed",
     "skr_thresholded_step_launch_indexed_per_sample",
+    "skr_threshold_scale_rolling",
+    "skr_thresholded_step_launch_rolling",
     "skr_rolling_advance",
     "skr_step_backward_launch",
     "skr_step_masked_backward_launch",
@@ -739,7 +741,7 @@ def load() -> ctypes.CDLL:
         lib.skr_threshold_scale.restype = ctypes.c_int
         lib.skr_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepThresholdC), vp, i64, vp]
         lib.skr_thresholded_step_launch.restype = ctypes.c_int
-        for suffix in ("_indexed", "_indexed_per_sample"):  # (their row forms: the direct arguments without the row values, the table where the rescaled row entries have it)
+        for suffix in ("_indexed", "_indexed_per_sample", "_rolling"):  # (their row forms: the direct arguments without the row values, the table where the rescaled row entries have it)
             entry = getattr(lib, "skr_threshold_scale" + suffix)
             entry.argtypes, entry.restype = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp], ctypes.c_int
             entry = getattr(lib, "skr_thresholded_step_launch" + suffix)
@@ -853,10 +855,13 @@ class StepCall(tuple):
     and it says what the launch is by name, never by its length: `kind` (a key of STEP_KINDS, or "guided_masked", the one launch outside
     the table: launch_guided_masked_step, which carries the masked AND the guided names), `layout` ((channels, plane) or None: read
     off the tensors) and -- None where the kind has none -- `mask`, `mask_numel`, `batch_stride` (masked), `cond`, `guided_out`, `scale`,
-    `slot` (guided), `factor`, `phi`, `sample_numel` (guided_rescaled).  A step program is built from a plain one only."""
+    `slot` (guided), `factor`, `phi`, `sample_numel` (guided_rescaled).  A step program is built from a plain one only.
+    Kind "thresholded" (launch_step_thresholded, outside the table as well): `x0_out`, `scale` (the per-sample scale tensor or None), `a`, `b`,
+    `ratio`, `max_value`, `sample_numel`, `slot`, `xslot`; `out0` None is the thresholding-only form."""
 
     kind, layout = "plain", None
     mask = mask_numel = batch_stride = cond = guided_out = scale = slot = factor = phi = sample_numel = None
+    x0_out = a = b = ratio = max_value = xslot = None
     plan, inputs, out0, out1, seeds, numel = (property(operator.itemgetter(i)) for i in range(6))
 
     def __new__(cls, plan, inputs, out0, out1, seeds, numel, kind: str = "plain", **named):
@@ -993,6 +998,20 @@ def launch_step_guided_rescaled(plan: StepPlanC, operands: list[torch.Tensor], o
 
 THRESHOLD_NO_ROWS = ("dynamic thresholding (set_thresholding) has no row form in a loop captured without it: pass thresholded=True to capture_sampling_loop (the to_x weights, "
                      "the ratio and the maximum are then row values); RollingBatch does not take a thresholding wrapper")
+THRESHOLD_ROLLING = ("skr_threshold_scale_rolling", "skr_thresholded_step_launch_rolling")  # a thresholded rolling tick: the statistic, then the step
+
+
+def launch_threshold_scale_rolling(lib, sample: int, output: int, dtype: int, numel: int, sample_numel: int, rows: int, index: int, row_offset: int, scale: int, workspace: int,
+                                   stream: int) -> None:
+    """the statistics launch of a thresholded rolling tick (skr_threshold_scale_rolling), on addresses: every active slot whose row selects
+    gets its scale, free slots, finished slots and plain-clip slots keep every byte of `scale` and `workspace`"""
+    check(lib.skr_threshold_scale_rolling(sample, output, dtype, numel, sample_numel, rows, index, row_offset, scale, workspace, stream), THRESHOLD_ROLLING[0])
+
+
+def launch_step_thresholded_rolling(lib, plan: StepPlanC, arr, out: int, thr: "StepThresholdC", seeds: "int | None", numel: int, rows: int, index: int, row_offset: int,
+                                    stream: int) -> None:
+    "the step launch of a thresholded rolling tick (skr_thresholded_step_launch_rolling), behind the statistics launch, with the same index, rows and row offset"
+    check(lib.skr_thresholded_step_launch_rolling(ctypes.byref(plan), arr, out, ctypes.byref(thr), seeds, numel, rows, index, row_offset, stream), THRESHOLD_ROLLING[1])
 
 
 def _threshold_hook() -> "IndexedRows | None":
@@ -1028,6 +1047,10 @@ def launch_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor], out, 
     plus skr_thresholded_step_launch_indexed[_per_sample] -- a, b, `ratio` and `max_value` (both required there) row values, `scale`
     replaced by the hook's own -- or refilled (IndexedRows.launch_thresholded).  Under any other hook it raises."""
     rows = _threshold_hook()
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:  # (what a dry run reads a request's rows off: rolling.RollingBatch._trace)
+        trace.append(StepCall(plan, operands, out, None, seeds, numel, "thresholded", x0_out=x0_out, scale=scale, a=float(a), b=float(b), ratio=ratio, max_value=max_value,
+                              sample_numel=int(sample_numel), slot=int(slot), xslot=int(xslot)))  # fmt: skip
     thr = StepThresholdC(_ptr(scale), _ptr(x0_out), float(a), float(b), int(sample_numel), int(slot), int(xslot), 0)
     if rows is not None:
         if ratio is None or max_value is None:

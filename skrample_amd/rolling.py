@@ -112,6 +112,28 @@ of a guided batch are unchanged.  `rescaled=True` without `guided=True`, a negat
 the wrong length and a non-zero `guidance_rescale` on a batch built without `rescaled` are refused.  Not covered: changing a resident
 request's phi mid-run (admit it with a schedule), skipping the statistics launch from the host when nobody rescales.
 
+Dynamic thresholding (`thresholded=True`): requests whose wrappers have `set_thresholding(ratio, sample_max_value)` in force, each with
+its own setting -- a maximum <= 1 is the plain clip:
+
+    batch = RollingBatch(make_wrapper, example, capacity=B, thresholded=True)      # make_wrapper() has set_thresholding too
+    batch.admit(slot, latents, wrapper, steps, seed=None)                           # the wrapper's own (ratio, sample_max_value)
+    done = batch.step(model(batch.latents, batch.timesteps))
+
+A tick is two launches on the current stream with the same index, rows and row offset: `skr_threshold_scale_rolling`
+(csrc/skr_threshold_rows.hip) writes the exact per-sample quantile scale of every active slot whose row selects into the batch's `scale`
+tensor, float32[capacity], through a workspace sized for the capacity; then `skr_thresholded_step_launch_rolling`
+(csrc/skr_step_thresholded_rows.hip) forms x0, clips, divides and steps every active slot.  The to_x weights, the ratio and the maximum of
+every step travel in the row's `convert_k[0..3]`, as in captured loops.  The wrapper is traced under DataModel, as its eager thresholded
+step runs; a step whose form does not hold the sample (a last step onto sigma = 0: eagerly the thresholding-only launch plus a plain step)
+is one row with the prediction at the network output's place and a zero at the sample's.  The history operands ("po", k) are the
+THRESHOLDED predictions of earlier ticks: the batch owns a ring `_p` of them, as long as the latents ring, used as the guided ring is --
+nothing of the caller is held, no alias guard, no snapshot; Euler keeps none.  Free slots, finished slots and plain-clip requests cost no
+statistics traffic.  `advance()`, `device_positions=True` and `capture(model)` work as on a guided batch (`CapturedTicks.tick()`: one replay
+plus the two eager launches).  Without the keyword a thresholding wrapper is refused, at construction and at `admit()`; with it a wrapper
+without thresholding is refused at `admit()`.  Refused when the batch is built, each with its reason, before anything is allocated: UniPC
+and SPC (two launches over a stored prediction), `guided`, `inpaint_mask_shape`, Offset / Pyramid noise, `compute_scale=None`, fp64,
+ragged samples and the Runge-Kutta wrappers.
+
 Sample sizes.  A unit (`example.shape[1:]`) of whole 2048-element chunks joins any batch.  A ragged unit -- at least 2048 elements and a
 multiple of 8, not whole chunks: (4,144,112) and most other non-square SDXL latent buckets -- joins a plain batch: not `guided`, no
 `inpaint_mask_shape`, `Random` noise or none, and a sampler whose step is one single-output launch (Euler, DPM 1-3, Adams, UniP).  The
@@ -140,7 +162,7 @@ from typing import Callable, Sequence
 import torch
 
 from . import _hip
-from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepGuidanceC, StepMaskC, StepPlanC, StepRescaleC, StepRowC, upload_rows
+from ._hip import PER_SAMPLE_CHUNK, ROW_TERMS, SkrampleHipError, StepGuidanceC, StepMaskC, StepPlanC, StepRescaleC, StepRowC, StepThresholdC, upload_rows
 from .sampling import lazy
 
 Role = tuple  # ("x",) ("o",) ("pi", k) ("po", k) ("px", k), k < 0: see sampling/program.py; ("orig",) ("znoise",): a masked batch's original / re-noising tensor;
@@ -232,15 +254,18 @@ class RollingBatch:
     the device (`advance()` before each `step()`, or `capture()`); the host publishes nothing per tick.  `guided`: True makes a tick
     `step_guided(uncond, cond)`, one `skr_step_launch_guided_rolling` with every request's own guidance scale (module docstring).
     `rescaled` (with `guided`): True makes that tick two launches -- `skr_guidance_rescale_factor_rolling`, then
-    `skr_step_launch_guided_rescaled_rolling` -- with every request's own `guidance_rescale` beside its scale (module docstring)."""
+    `skr_step_launch_guided_rescaled_rolling` -- with every request's own `guidance_rescale` beside its scale (module docstring).
+    `thresholded`: True batches wrappers with `set_thresholding` in force, each under its own (ratio, sample_max_value): a tick is
+    `skr_threshold_scale_rolling`, then `skr_thresholded_step_launch_rolling` (module docstring)."""
 
     def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True,
-                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False, rescaled: bool = False):  # fmt: skip
+                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False, rescaled: bool = False, thresholded: bool = False):  # fmt: skip
         if capacity < 1:
             raise ValueError("a rolling batch has at least one slot")
         self.masked = inpaint_mask_shape is not None
         self.guided = bool(guided)
         self.rescaled = bool(rescaled)
+        self.thresholded = bool(thresholded)
         if self.rescaled and not self.guided:
             raise ValueError("rescaled=True needs guided=True: guidance_rescale is applied to the guided prediction a guided batch forms")
         if self.guided and self.masked:
@@ -261,7 +286,9 @@ class RollingBatch:
                              f"(ragged samples are served from {PER_SAMPLE_CHUNK} elements on, in multiples of 8)")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
-        if getattr(first, "_thresholding_next", None) is not None or getattr(first, "_thresholding", None) is not None:
+        if self.thresholded:
+            self._refuse_thresholded(first)
+        elif getattr(first, "_thresholding_next", None) is not None or getattr(first, "_thresholding", None) is not None:
             raise SkrampleHipError(_hip.THRESHOLD_NO_ROWS)  # (before anything is allocated)
         if self.ragged:
             self._refuse_ragged(first)
@@ -293,6 +320,13 @@ class RollingBatch:
         # a guided batch: the guided predictions of the last ticks, oldest first, as long as the latents ring (so that the phases of
         # CapturedTicks close); [-1] is the tensor this tick's launch stores into, ("po", k) the one of -k ticks ago.  Euler keeps none.
         self._g = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1)] if self.guided and self.keep else []
+        # a thresholded batch: the thresholded predictions of the last ticks, a ring used as _g is -- [-1] is the tensor this tick's launch stores
+        # into (x0_out), ("po", k) the one of -k ticks ago; Euler keeps none --, every slot's scale and the statistic's workspace for `capacity`
+        # samples (SKR_THRESHOLD_WORKSPACE): allocated once, the same in every phase of CapturedTicks
+        self._p = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(depth + 1)] if self.thresholded and self.keep else []
+        if self.thresholded:
+            self.scale = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+            self._threshold_ws = torch.zeros(_hip.threshold_workspace(self.numel, self.sample_numel), dtype=torch.uint8, device=self.device)
         if self.rescaled:
             # a rescaled batch: every slot's factor std(cond) / std(p) and the partial sums behind it, written by the tick's statistics
             # launch and read by its step launch; allocated once, the same in every phase of CapturedTicks
@@ -378,6 +412,33 @@ class RollingBatch:
         if self.dtype not in (torch.bfloat16, torch.float16, torch.float32):
             raise SkrampleHipError(f"guided rows need one 16- or 32-bit dtype for operands, cond and both outputs, not {self.dtype}")
 
+    def _refuse_thresholded(self, first) -> None:
+        "a thresholded batch: what its two launches per tick do not cover, refused by name before anything is allocated or traced"
+        from . import diffusers
+        from .pytorch import noise as generators
+        from .sampling import structured as sampling
+
+        if self.guided:
+            raise ValueError("thresholded together with guided: the guidance-only launch has no rolling form (step_guided under thresholding is not covered in batches)")
+        if self.masked:
+            raise ValueError("thresholded together with inpaint_mask_shape: in-painting beside dynamic thresholding is not covered")
+        if self.ragged:
+            raise ValueError(f"thresholded together with ragged samples ({self.sample_numel} elements, not whole {PER_SAMPLE_CHUNK}-element chunks): the thresholded row kernels need samples of whole chunks")
+        if isinstance(first, diffusers.RKWrapperCore):
+            raise SkrampleHipError(f"{type(first).__name__} cannot join a thresholded rolling batch: the Runge-Kutta wrappers have no dynamic thresholding")
+        if getattr(first, "_thresholding_next", None) is None:
+            raise ValueError("thresholded=True batches wrappers with dynamic thresholding: make_wrapper() must return one with set_thresholding(ratio, sample_max_value) in force")
+        sampler = first.sampler
+        if type(sampler).sample_packed is not sampling.StatedSampler.sample_packed:
+            raise SkrampleHipError(f"a thresholded step of {type(sampler).__name__} is two launches over a stored prediction (the thresholding-only launch, then its two-output step): "
+                                   "a thresholded rolling batch takes Euler, DPM 1-3, Adams 2-4 and UniP 2-3")  # fmt: skip
+        if first.compute_scale is None:
+            raise SkrampleHipError("dynamic thresholding needs a compute scale: compute_scale=None has no thresholding form")
+        if bool(sampler.require_noise) and first.noise_type in (generators.Offset, generators.Pyramid):
+            raise ValueError(f"thresholded together with {first.noise_type.__name__} noise: a thresholded rolling batch draws Random noise or none")
+        if self.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise SkrampleHipError(f"thresholding takes bf16, fp16 or fp32 tensors, not fp64 ({self.dtype})")
+
     def _init_inpaint(self, mask_shape: tuple, first) -> None:
         """A masked batch: the three whole-batch in-paint tensors (every slot's mask starts as ones: generate everything), the mask
         descriptor of every tick's launch -- one mask per slot, always -- and in-painting set on the wrapper whose dry run gives the
@@ -441,6 +502,16 @@ class RollingBatch:
                 launches = _hip.trace
             finally:
                 _hip.trace = held
+            settled = None
+            if self.thresholded:
+                if len(launches) == 2 and launches[0].kind == "thresholded" and launches[0].out0 is None and launches[1].kind == "plain":
+                    # a step whose form does not hold the sample (a last step onto sigma = 0): the eager wrapper takes the thresholding-only
+                    # launch and steps over the stored p.  In the batch it is one row like any other: p at the network output's place, a
+                    # zero at the sample's, which the kernel reads for x0 and sums to nothing
+                    settled, launches = launches[0], launches[1:]
+                    known[settled.x0_out.data_ptr()] = ("o",)
+                elif len(launches) != 1 or launches[0].kind != "thresholded" or launches[0].out0 is None:
+                    raise SkrampleHipError("a thresholded step of this wrapper is not one thresholded step launch: it cannot join a thresholded rolling batch")
             if len(launches) != 1:
                 raise SkrampleHipError(f"a step of this wrapper is {len(launches)} launches, not one fused launch: it cannot join a rolling batch")
             call = launches[0]
@@ -449,6 +520,11 @@ class RollingBatch:
             if (call.kind == "masked") != (inpaint is not None):
                 raise SkrampleHipError("a step of this wrapper is not the masked launch its in-painting asks for" if inpaint is not None else "a step of this wrapper is a masked launch although no in-painting is set")
             plan, inputs = StepPlanC.from_buffer_copy(call.plan), call.inputs
+            if self.thresholded:  # the step's (a, b, ratio, maximum) travel in the traced plan where the row keeps them (such a plan has no rounded conversion)
+                given = settled if settled is not None else call
+                if plan.convert_to or plan.convert_from or given.ratio is None or given.max_value is None:
+                    raise SkrampleHipError("a thresholded step of this wrapper carries a rounded conversion or no thresholding setting: it cannot join a thresholded rolling batch")
+                plan.convert_k[0], plan.convert_k[1], plan.convert_k[2], plan.convert_k[3] = given.a, given.b, given.ratio, given.max_value
             known[x.data_ptr()], known[out.data_ptr()] = ("x",), ("o",)
             if inpaint is not None:
                 known[inpaint[1].data_ptr()], known[inpaint[2].data_ptr()] = ("orig",), ("znoise",)
@@ -469,6 +545,8 @@ class RollingBatch:
         tick's launches -- the statistics launch of a rescaled batch, then the step launch.  Everything else in them is the batch's own --
         plan, descriptors, and the addresses of rows_dev, index_dev, seeds_dev, factor and _partials, which are allocated in __init__ and
         never reassigned."""
+        if self.thresholded:  # (two entries outside the launch table: _launch_thresholded)
+            return []
         kind = "guided_rescaled" if self.rescaled else "guided" if self.guided else "masked" if self.masked else "plain"
         # structured noise is an operand, drawn by a launch of its own: no seeds (masked and guided batches refuse structured noise when built)
         seeds = self.seeds_dev.data_ptr() if self.draws_noise and not self.structured else None
@@ -500,6 +578,18 @@ class RollingBatch:
                 if what in at:
                     args[at[what]] = value
             _hip.check(getattr(lib, name)(*args), name)
+
+    def _launch_thresholded(self, arr, out: torch.Tensor, x0_out: torch.Tensor | None) -> None:
+        """the two launches of a thresholded tick, on the current stream with the same index, rows and row offset: the statistic over this
+        tick's latents and model output (skr_threshold_scale_rolling) writes `scale` for every active slot whose row selects, then the step
+        (skr_thresholded_step_launch_rolling) clips, divides and steps every active slot and stores its prediction into `x0_out`"""
+        lib, stream = _hip.load(), _hip.current_stream_ptr(self.device)
+        table = (self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0)
+        _hip.launch_threshold_scale_rolling(lib, arr[self.xslot], arr[self.slot], _hip.DTYPE_CODE[self.dtype], self.numel, self.sample_numel, *table, self.scale.data_ptr(),
+                                            self._threshold_ws.data_ptr(), stream)  # fmt: skip
+        thr = StepThresholdC(self.scale.data_ptr(), _hip._ptr(x0_out), 0.0, 0.0, self.sample_numel, self.slot, self.xslot, 0)  # (a and b are the rows')
+        seeds = self.seeds_dev.data_ptr() if self.draws_noise else None
+        _hip.launch_step_thresholded_rolling(lib, self.plan, arr, out.data_ptr(), thr, seeds, self.numel, *table, stream)
 
     def _draw(self, out: torch.Tensor) -> None:
         "a structured-noise batch: ONE launch of the generator's rolling entry draws, into `out`, every slot the index on the device names"
@@ -554,6 +644,14 @@ class RollingBatch:
             if roles.count(("o",)) != 1:
                 raise SkrampleHipError("the guided launch structure has no single `uncond` operand for the guided value to replace")
             self.slot = roles.index(("o",))
+        if self.thresholded:
+            if not _hip.one_group_launch(wide, _hip.DTYPE_CODE[self.dtype]) or wide.convert_to or wide.convert_from or wide.n_terms < 2:
+                raise SkrampleHipError("skr_thresholded_step_launch_rolling: request outside kernel coverage (one single-output launch of one 16- or 32-bit dtype, evaluated in float32)")
+            if roles.count(("o",)) != 1 or roles.count(("x",)) != 1:
+                raise SkrampleHipError("the thresholded launch structure needs one network output and one sample operand: x0 is formed from the two")
+            self.slot, self.xslot = roles.index(("o",)), roles.index(("x",))
+            for k in range(4):  # (a row's values, never the structure's)
+                wide.convert_k[k] = 0.0
         return wide, list(roles)
 
     def _rows_of(self, traced, scales: Sequence[float] | None = None, rescales: Sequence[float] | None = None) -> list[StepRowC]:
@@ -574,6 +672,16 @@ class RollingBatch:
                 row.convert_k[0] = float(scales[step])
                 if self.rescaled and rescales is not None:
                     row.convert_k[1] = float(rescales[step])
+            if self.thresholded:  # convert_k[0..3] = a, b, ratio, maximum of the step, as IndexedRows.launch_thresholded keeps them for captured loops
+                if not _hip.one_group_launch(plan) or list(roles).count(("o",)) != 1 or list(roles).count(("x",)) > 1:
+                    raise SkrampleHipError("a step of this request is not one single-output thresholded launch of the batch's dtype over one network output and one sample")
+                if row.coef0[self.slot] != plan.coef0[list(roles).index(("o",))]:  # (place_row put the network output where the batch's launches replace it)
+                    raise SkrampleHipError(f"the network output of this step is not at the batch's slot {self.slot}")
+                ratio, max_value = plan.convert_k[2], plan.convert_k[3]
+                if not (0.0 < ratio <= 1.0) or not (0.0 < max_value < float("inf")):  # (before a row is written: the kernels trust their rows)
+                    raise SkrampleHipError(f"step {step}: a thresholded row needs a ratio in (0, 1] and a positive finite maximum, not {ratio} and {max_value}")
+                for k in range(4):
+                    row.convert_k[k] = plan.convert_k[k]
             rows.append(row)
         return rows
 
@@ -597,7 +705,7 @@ class RollingBatch:
 
     def ring_tensors(self) -> list[torch.Tensor]:
         "every whole-batch tensor a history operand may be bound to: the batch's own latents and states, snapshots of model outputs"
-        owned = self._x[:-1] + list(self._state) + [self._blank] + (list(self._n) if self.structured else []) + list(self._g)
+        owned = self._x[:-1] + list(self._state) + [self._blank] + (list(self._n) if self.structured else []) + list(self._g) + list(self._p)
         return owned + ([] if self.alias_history else list(self._outputs))
 
     def _running(self) -> list[tuple[int, _Request]]:
@@ -638,6 +746,12 @@ class RollingBatch:
             raise ValueError(f"a request runs 1..{self.max_steps} steps (max_steps), not {steps}")
         if sampler_structure(wrapper) != self.structure:
             raise ValueError(f"this wrapper's sampler structure {sampler_structure(wrapper)} is not the batch's {self.structure}")
+        thresholding = getattr(wrapper, "_thresholding_next", None)
+        if self.thresholded and thresholding is None:
+            raise ValueError("this batch was built with thresholded=True: admit() takes a wrapper with set_thresholding(ratio, sample_max_value) in force "
+                             "(every request brings its own setting; a maximum <= 1 is the plain clip)")
+        if not self.thresholded and thresholding is not None:
+            raise SkrampleHipError(_hip.THRESHOLD_NO_ROWS)
         scales = None
         if self.guided:
             if guidance_scale is None:
@@ -778,6 +892,8 @@ class RollingBatch:
             return self._state[(p + k) % P]
         if kind == "po" and self.guided:  # the batch's own guided prediction of -k ticks ago
             return self._g[(p + k) % P]
+        if kind == "po" and self.thresholded:  # the batch's own thresholded prediction of -k ticks ago
+            return self._p[(p + k) % P]
         if kind == "po" and outputs is not None:  # the static output of the graph replayed -k ticks ago
             return outputs[(p + k) % P]
         if kind == "po":
@@ -817,6 +933,13 @@ class RollingBatch:
         if self.guided:
             raise ValueError("this batch was built with guided=True: a tick is step_guided(uncond, cond), the guided prediction is formed inside its launch")
         live = self._tick_begins("step", **{"the model output": model_output})
+        if self.thresholded:
+            # the statistic, then the step; history operands read the batch's own ring of thresholded predictions, so nothing of the caller
+            # is held -- no alias guard, no snapshot -- and the model output may be overwritten once step() has returned
+            self._publish(live)
+            arr, out, _ = self._operands(model_output)
+            self._launch_thresholded(arr, out, self._p[0] if self._p else None)  # (the oldest prediction's tensor takes this tick's)
+            return self._ticked(live)
         if self.alias_history:
             self._guard(model_output)
         elif self.keep:
@@ -850,7 +973,7 @@ class RollingBatch:
         """THE host bookkeeping behind a tick's launches, for step(), step_guided() and CapturedTicks.tick(): every ring rotates -- the oldest
         entry, which took this tick's result, becomes the newest, so that `latents` is where admit() must write --, then positions, finished
         slots, the result clones and the next timesteps"""
-        for ring in (self._x, self._state, self._n if self.structured else (), self._g):
+        for ring in (self._x, self._state, self._n if self.structured else (), self._g, self._p):
             if ring:
                 ring.append(ring.pop(0))
         new_x = self._x[-1]
@@ -957,6 +1080,8 @@ class CapturedTicks:
         self._draws = [batch._bind(("n",), None, p) for p in phases] if batch.structured else None
         # a guided batch: the tick of phase p stores its guided prediction into entry p of that ring; Euler stores none
         self._guides = [(self.conds[p], batch._g[p] if batch._g else None) for p in phases] if batch.guided else None
+        # a thresholded batch: the tick of phase p stores its thresholded prediction into entry p of that ring; Euler stores none
+        self._predictions = [batch._p[p] if batch._p else None for p in phases] if batch.thresholded else None
 
     def tick(self) -> list[int]:
         "one graph replay (advance + network), the draw of a structured-noise batch, and ONE step launch; returns the slots that finished with this tick"
@@ -968,7 +1093,11 @@ class CapturedTicks:
         self.graphs[phase].replay()
         if self._draws is not None:  # eager like the step launch, between the advance (in the graph) and the step that reads the draw
             batch._draw(self._draws[phase])
-        batch._launch(*self._launches[phase], *(self._guides[phase] if self._guides is not None else ()))
+        if self._predictions is not None:  # the statistic and the step, both eager: both read this replay's model output
+            arr, out, _ = self._launches[phase]
+            batch._launch_thresholded(arr, out, self._predictions[phase])
+        else:
+            batch._launch(*self._launches[phase], *(self._guides[phase] if self._guides is not None else ()))
         self.replays[phase] += 1
         self.ticks += 1
         return batch._ticked(live)  # the batch's rings follow the phase

@@ -752,6 +752,46 @@ int skr_thresholded_step_launch(const skr_step_plan* plan, const void* const* in
                                 const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * Guided dynamic thresholding: the two launches above with classifier-free guidance formed inside them, so that a guided thresholded
+ * step has no guidance-only launch and no intermediate tensor.  Nothing new is defined: two definitions are composed.  Per element e of
+ * a launch of one tensor dtype T (bf16, fp16 or fp32), u = uncond[e], c = cond[e], x = sample[e]:
+ *
+ *     pg  = rn_T( u + rn_T( g_M * rn_T(c - u) ) )        the guided value of skr_step_launch_guided: three separate fp32 operations,
+ *                                                        torch's fp16 exception included (the elements from the last multiple of 2048
+ *                                                        below numel on, by their index in the WHOLE launch, round g_M * d once)
+ *     x0  = rn32( rn32(a_M * x) + rn32(b_M * pg) )       as above, pg in the place of the network output
+ *     s, p, out                                          as above
+ *
+ * Bit contract, against the two-launch route: scale_dev has the bits skr_threshold_scale writes when its `output` is the tensor the
+ * guidance-only form of skr_step_launch_guided stores; out and x0_out have the bits skr_thresholded_step_launch writes over that tensor.
+ *
+ * skr_guided_threshold_scale: skr_threshold_scale's four kernels, workspace layout and size, the histogram and the candidate pass
+ * reading sample, uncond and cond (whole 16-byte aligned spans by 16-byte non-temporal loads, all three issued before the first use;
+ * any other span element by element, in the same lane ownership).  A launch with numel % 2048 == 0 has no fp16 tail and makes no
+ * per-element test for it; any other launch tests every element, a whole aligned span included (it can straddle the tail).
+ * Checks, their order and their codes are skr_threshold_scale's; `cond` is checked wherever `output` is (NULL, 16-byte alignment).
+ * Allocates nothing, never synchronises: capturable.
+ *
+ * skr_guided_thresholded_step_launch: inputs[thr->slot] is uncond and p takes its place in the sum; inputs[thr->xslot] is the sample;
+ * guide->cond is cond and guide->scale is g.  The thresholding-only form (out0_dtype == SKR_NONE, out == NULL, n_terms == 2) stores p
+ * alone through x0_out.  Launches of whole 2048-element chunks whose thr->sample_numel is a multiple of 2048 below 2^31, with one 16-
+ * or 32-bit dtype and 2..SKR_ROW_TERMS operands, take a one-trip vector kernel, the thresholding-only form included; everything else a
+ * grid-stride per-element kernel with the fp16 exception by element index.  The two agree bit for bit ("one_trip" 0 forces the second).
+ * Checked before the launch, without dereferencing device memory, in the order and with the codes of skr_thresholded_step_launch, with
+ * on top of them: a NULL guide SKR_ERR_NULL (beside the NULL plan and thr);  guide->slot != thr->slot SKR_ERR_TERMS (beside the slot
+ * checks);  a non-zero guide->reserved (beside thr->reserved) or a non-NULL guide->guided_out -- the guided prediction is never
+ * stored -- SKR_ERR_UNSUPPORTED;  a NULL guide->cond SKR_ERR_NULL and a misaligned one SKR_ERR_ALIGN (beside the operands).
+ * Neither entry has a row form.  Allocates nothing, never synchronises: capturable.
+ */
+int skr_guided_threshold_scale(const void* sample, const void* uncond, const void* cond, int32_t dtype, double guidance_scale,
+                               double a, double b, double ratio, double sample_max_value, int64_t numel, int64_t sample_numel,
+                               float* scale_dev /* [numel / sample_numel] */,
+                               void* workspace_dev /* SKR_THRESHOLD_WORKSPACE(numel, sample_numel) bytes */, void* stream);
+
+int skr_guided_thresholded_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                       const skr_step_threshold* thr, const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
  * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,
  * rows_dev[sample_index_dev[s] + row_offset] -- convert_k[0] the guidance scale (as in skr_step_launch_guided_rolling), convert_k[1]
  * phi = guidance_rescale (skr_step_launch_guided_rolling does not read it).  convert_k[2..3], coef1, chain, zeta1 and stream1 are not

@@ -52,6 +52,8 @@ EXPORTS = (
     "skr_guided_masked_step_launch",
     "skr_threshold_scale",
     "skr_thresholded_step_launch",
+    "skr_guided_threshold_scale",
+    "skr_guided_thresholded_step_launch",
     "skr_threshold_scale_indexed",
     "skr_threshold_scale_indexed_per_sample",
     "skr_thresholded_step_launch_indexed",
@@ -741,6 +743,11 @@ def load() -> ctypes.CDLL:
         lib.skr_threshold_scale.restype = ctypes.c_int
         lib.skr_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepThresholdC), vp, i64, vp]
         lib.skr_thresholded_step_launch.restype = ctypes.c_int
+        # (their guided forms: uncond and cond in the place of the output, the guidance descriptor beside the threshold's)
+        lib.skr_guided_threshold_scale.argtypes = [vp, vp, vp, i32, f64, f64, f64, f64, f64, i64, i64, vp, vp, vp]
+        lib.skr_guided_threshold_scale.restype = ctypes.c_int
+        lib.skr_guided_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepThresholdC), vp, i64, vp]
+        lib.skr_guided_thresholded_step_launch.restype = ctypes.c_int
         for suffix in ("_indexed", "_indexed_per_sample", "_rolling"):  # (their row forms: the direct arguments without the row values, the table where the rescaled row entries have it)
             entry = getattr(lib, "skr_threshold_scale" + suffix)
             entry.argtypes, entry.restype = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp], ctypes.c_int
@@ -1059,3 +1066,39 @@ def launch_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor], out, 
     else:
         status = load().skr_thresholded_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(thr), _ptr(seeds), numel, current_stream_ptr(device))
     check(status, "skr_thresholded_step_launch")
+
+
+GUIDED_THRESHOLD_NO_HOOK = ("a guided thresholded launch has no row form and is not traced: under an indexed-rows hook or a dry run the caller takes the guidance-only launch "
+                            "and the thresholded launches (lazy.Threshold.fused_guidance)")
+
+
+def _no_hook(what: str) -> None:
+    if not hooks_clear():
+        raise SkrampleHipError(f"{what}: {GUIDED_THRESHOLD_NO_HOOK}")
+
+
+def launch_guided_threshold_scale(sample: torch.Tensor, uncond: torch.Tensor, cond: torch.Tensor, guidance_scale: float, a: float, b: float, ratio: float, sample_max_value: float,
+                                  sample_numel: int, scale: torch.Tensor) -> None:
+    """the statistics launch of guided dynamic thresholding (skr_guided_threshold_scale): launch_threshold_scale over the guided prediction
+    uncond + guidance_scale * (cond - uncond), formed in registers with torch's bits; `scale` is float32[samples].  It has no row form:
+    called under an indexed-rows hook or while a dry run collects, it raises."""
+    _no_hook("skr_guided_threshold_scale")
+    numel, device = sample.numel(), sample.device
+    workspace = torch.empty(threshold_workspace(numel, sample_numel), dtype=torch.uint8, device=device)  # (torch's allocator: 16-byte aligned, safe under capture)
+    status = load().skr_guided_threshold_scale(sample.data_ptr(), uncond.data_ptr(), cond.data_ptr(), DTYPE_CODE[sample.dtype], float(guidance_scale), float(a), float(b),
+                                               float(ratio), float(sample_max_value), numel, int(sample_numel), scale.data_ptr(), workspace.data_ptr(),
+                                               current_stream_ptr(device))  # fmt: skip
+    check(status, "skr_guided_threshold_scale")
+
+
+def launch_guided_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor], out, x0_out, cond: torch.Tensor, guidance_scale: float, scale: "torch.Tensor | None", a: float,
+                                   b: float, sample_numel: int, slot: int, xslot: int, seeds, numel: int, device: torch.device) -> None:
+    """one guided thresholded step launch (skr_guided_thresholded_step_launch): launch_step_thresholded with operands[slot] = uncond and the
+    guided prediction formed inside the launch from it and `cond`; `x0_out` (or None) receives p, the guided prediction is never stored.
+    It has no row form: called under an indexed-rows hook or while a dry run collects, it raises."""
+    _no_hook("skr_guided_thresholded_step_launch")
+    guide = StepGuidanceC(cond.data_ptr(), None, float(guidance_scale), int(slot), 0)
+    thr = StepThresholdC(_ptr(scale), _ptr(x0_out), float(a), float(b), int(sample_numel), int(slot), int(xslot), 0)
+    status = load().skr_guided_thresholded_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(guide), ctypes.byref(thr), _ptr(seeds), numel,
+                                                       current_stream_ptr(device))  # fmt: skip
+    check(status, "skr_guided_thresholded_step_launch")

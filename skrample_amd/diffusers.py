@@ -758,6 +758,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             return
         self._steps = steps
         self._thresholding = getattr(self, "_thresholding_next", None)
+        self._thresholding_fuse = self._thresholding is not None and getattr(self, "_thresholding_fuse_next", False)
         if self.allow_dynamic:
             self.schedule = _apply_dynamic(self.schedule, steps, mu)
         self._previous = []
@@ -861,14 +862,19 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     # in ONE launch (lazy.evaluate_thresholded / skr_thresholded_step_launch), which also stores p for history and pred_original_sample;
     # UniPC and SPC take the thresholding-only launch and then their step over p.  Host-resident operands evaluate the same definition
     # with torch ops.  A thresholding step builds no step program and learns no replayed entry.
-    def set_thresholding(self, ratio: float | None = 0.995, sample_max_value: float = 1.0) -> None:
+    # step_guided() under it forms the guided prediction in one guidance-only launch first; with set_thresholding(..., fuse_guidance=True)
+    # the statistic and the step form it in registers from the two halves instead (skr_guided_threshold_scale,
+    # skr_guided_thresholded_step_launch): no guidance-only launch, no intermediate tensor, the same bits.
+    def set_thresholding(self, ratio: float | None = 0.995, sample_max_value: float = 1.0, fuse_guidance: bool = False) -> None:
         """dynamic thresholding for the runs that follow: takes effect from the next set_timesteps().  `ratio` None clears it.
-        `sample_max_value` <= 1 is a plain clip to [-1, 1] (no quantile is taken)."""
+        `sample_max_value` <= 1 is a plain clip to [-1, 1] (no quantile is taken).
+        `fuse_guidance`: step_guided() calls under it form the guidance inside the statistics launch and the step launch where they can
+        (unrescaled guidance, a contiguous aligned cond, no capture hook; same bits), as set_inpaint's keyword does for the blend."""
         table_len = len(self._timestep_table()) if getattr(self, "_steps", None) else 0
         if 0 < self._calls and self._index + self._calls < table_len:
             raise lazy.SkrampleHipError("set_thresholding: thresholding cannot change in the middle of a run; it takes effect from the next set_timesteps()")
         if ratio is None:
-            self._thresholding_next = None
+            self._thresholding_next, self._thresholding_fuse_next = None, False
             return
         for name, v in (("ratio", ratio), ("sample_max_value", sample_max_value)):
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
@@ -879,10 +885,11 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             raise lazy.SkrampleHipError(f"set_thresholding: sample_max_value must be positive, not {sample_max_value}")
         if getattr(self, "_inpaint", None) is not None:
             raise lazy.SkrampleHipError("set_thresholding: dynamic thresholding beside in-painting (set_inpaint) is not covered; clear one of them")
-        self._thresholding_next = (float(ratio), float(sample_max_value))
+        self._thresholding_next, self._thresholding_fuse_next = (float(ratio), float(sample_max_value)), bool(fuse_guidance)
 
-    def _step_thresholded(self, model_output: Tensor, timestep, sample: Tensor, generator, return_dict: bool):
-        "step() under set_thresholding: the Threshold leaf at this step's point, then the general path with DataModel as the model transform"
+    def _step_thresholded(self, model_output: Tensor, timestep, sample: Tensor, generator, return_dict: bool, guidance=None):
+        """step() under set_thresholding: the Threshold leaf at this step's point, then the general path with DataModel as the model transform.
+        `guidance` (step_guided under fuse_guidance: `model_output` is its uncond half): the leaf carries it"""
         ratio, max_value = self._thresholding
         if getattr(self, "_inpaint", None) is not None:
             raise lazy.SkrampleHipError("dynamic thresholding beside in-painting (set_inpaint) is not covered; clear one of them")
@@ -897,7 +904,7 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         table = self._timestep_table()
         idx = self._lookup(table, timestep, self._index + self._calls)
         a, b = self.model.x_weights(sampling._ipoint(self.schedule, Step.from_int(idx, len(table)).time_from))
-        thr = lazy.Threshold(model_output, sample, a, -b if self.invert_prediction else b, ratio, max_value)
+        thr = lazy.Threshold(model_output, sample, a, -b if self.invert_prediction else b, ratio, max_value, guidance)
         return self._step_general(model_output, timestep, sample, generator, return_dict, False, thr)
 
     def step(self, model_output: Tensor, timestep, sample: Tensor, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None, return_dict: bool = True):
@@ -932,7 +939,10 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
                     guidance_rescale: float = 0.0):
         model_output_uncond, model_output_cond, sample = lazy.distinct(model_output_uncond, model_output_cond, sample)
         guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale, guidance_rescale)
-        if getattr(self, "_thresholding", None) is not None:  # the guidance-only launch, then the thresholding route over its prediction
+        if getattr(self, "_thresholding", None) is not None:
+            if getattr(self, "_thresholding_fuse", False):  # the guidance rides on the Threshold leaf, which forms it inside its launches where it can
+                return self._step_thresholded(model_output_uncond, timestep, sample, generator, return_dict, guidance)
+            # the guidance-only launch, then the thresholding route over its prediction
             return self._step_thresholded(lazy.guide_only(guidance), timestep, sample, generator, return_dict)
         recorded = lazy.grad_recorded(model_output_uncond, model_output_cond, sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous))
         return self._step_general(model_output_uncond, timestep, sample, generator, return_dict, recorded, guidance)

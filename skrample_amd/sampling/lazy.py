@@ -924,9 +924,13 @@ class Threshold:
     quantile of |x0| clamped to [1, max_value]  (include/skrample_hip.h, skr_threshold_scale) as ONE leaf of a step's form, as `Guidance`
     is: `evaluate_thresholded` computes it inside the launch that consumes it (skr_thresholded_step_launch), with one statistics launch
     in front when max_value > 1.  `uncond` / `cond` name the output and the sample where a wrapper asks a pending prediction for its
-    operands without caring which kind it is."""
+    operands without caring which kind it is.
+    `guidance` (a `Guidance` whose uncond half is `output`): the network output is the guided prediction of its two halves, formed
+    inside the statistics launch and the step launch (skr_guided_threshold_scale, skr_guided_thresholded_step_launch) where
+    `fused_guidance` holds, and by `guide_only` in front of the launches above otherwise (`settle_guidance`).  The real cond half lives
+    in `guidance.cond`: `cond` here stays the sample's alias."""
 
-    def __init__(self, output: torch.Tensor, sample: torch.Tensor, a: float, b: float, ratio: float, max_value: float):
+    def __init__(self, output: torch.Tensor, sample: torch.Tensor, a: float, b: float, ratio: float, max_value: float, guidance: "Guidance | None" = None):
         if not isinstance(output, torch.Tensor) or not isinstance(sample, torch.Tensor):
             raise SkrampleHipError(f"thresholding takes two torch tensors, not {type(output).__name__} and {type(sample).__name__}")
         _check_tensor(output), _check_tensor(sample)
@@ -936,7 +940,9 @@ class Threshold:
             )
         if output.dtype == torch.float64:
             raise SkrampleHipError("thresholding takes bf16, fp16 or fp32 tensors, not fp64")
-        if grad_recorded(output, sample):
+        if guidance is not None and (not isinstance(guidance, Guidance) or guidance.uncond is not output):
+            raise SkrampleHipError("a guided Threshold takes a Guidance whose uncond half is its output")
+        if grad_recorded(output, sample) or (guidance is not None and grad_recorded(guidance.cond)):
             raise SkrampleHipError("thresholding has no backward: its operands must not be recorded by autograd")
         if output.ndim < 2 or output.numel() == 0:
             raise SkrampleHipError(f"thresholding takes a quantile of every sample: it needs non-empty tensors of ndim >= 2 (dim 0 the sample), not {tuple(output.shape)}")
@@ -944,6 +950,7 @@ class Threshold:
         self.cond = self.sample = sample
         self.a, self.b, self.ratio, self.max_value = float(a), float(b), float(ratio), float(max_value)
         self.shape, self.device, self.dtype = tuple(output.shape), output.device, output.dtype
+        self.guidance = guidance
 
     def node(self) -> "Lin":
         n = Node(self)
@@ -952,10 +959,23 @@ class Threshold:
     def expanded(self, keep=None):
         return self
 
+    def fused_guidance(self) -> bool:
+        """the carried guidance can be formed inside the two launches: unrescaled, cond a contiguous 16-byte aligned device tensor (dtype,
+        shape and device are the output's: Guidance checked them), and no hook installed -- neither guided entry has a row form"""
+        g = self.guidance
+        return (g is not None and g.rescale == 0.0 and _hip.hooks_clear() and not is_host(self.device) and g.cond.is_contiguous() and g.cond.data_ptr() % 16 == 0)  # fmt: skip
+
+    def settle_guidance(self) -> None:
+        "the default route: the guided prediction as a tensor of its own (guide_only), which is the output from here on"
+        if self.guidance is not None:
+            self.uncond = self.output = guide_only(self.guidance)
+            self.guidance = None
+
     def host_value(self) -> torch.Tensor:
-        "the definition in torch ops, a sort for the order statistics (host-resident operands)"
+        "the definition in torch ops, a sort for the order statistics (host-resident operands); a carried guidance is torch's lines first"
         n = math.prod(self.shape[1:])
-        x0 = self.sample.float() * self.a + self.output.float() * self.b  # (a Python number meets an fp32 tensor as an fp32 scalar: three rounded fp32 ops)
+        output = self.guidance.torch_lines() if self.guidance is not None else self.output
+        x0 = self.sample.float() * self.a + output.float() * self.b  # (a Python number meets an fp32 tensor as an fp32 scalar: three rounded fp32 ops)
         s = torch.ones(self.shape[0], dtype=torch.float32)
         if self.max_value > 1.0:
             mags = x0.abs().reshape(self.shape[0], n).double().sort(dim=1).values
@@ -969,10 +989,14 @@ class Threshold:
         return (clipped / s).to(self.dtype)
 
     def device_scale(self, o: torch.Tensor, x: torch.Tensor) -> "torch.Tensor | None":
-        "the statistics launch over contiguous 16-byte aligned device operands: float32[samples], or None where s is identically 1"
+        """the statistics launch over contiguous 16-byte aligned device operands: float32[samples], or None where s is identically 1; with a
+        guidance carried (the caller has settled one that cannot be fused) `o` is uncond and the guided entry runs"""
         if self.max_value <= 1.0:
             return None
         scale = torch.empty(self.shape[0], dtype=torch.float32, device=self.device)
+        if self.guidance is not None:
+            _hip.launch_guided_threshold_scale(x, o, self.guidance.cond, self.guidance.scale, self.a, self.b, self.ratio, self.max_value, o.numel() // self.shape[0], scale)
+            return scale
         _hip.launch_threshold_scale(x, o, self.a, self.b, self.ratio, self.max_value, o.numel() // self.shape[0], scale)
         return scale
 
@@ -981,6 +1005,8 @@ def threshold_only(thr: Threshold) -> torch.Tensor:
     "the thresholded prediction as a tensor of its own: the statistics launch and the thresholding-only launch on the HIP device, torch's ops on the host"
     if is_host(thr.device):
         return thr.host_value().contiguous()
+    if not thr.fused_guidance():
+        thr.settle_guidance()
     o, x = _prepare_tensor(thr.output), _prepare_tensor(thr.sample)
     out = empty_output(thr.shape, thr.dtype, thr.device)
     plan = _hip.StepPlanC()
@@ -988,6 +1014,10 @@ def threshold_only(thr: Threshold) -> torch.Tensor:
     plan.dtype_a = plan.dtype_b = _hip.DTYPE_CODE[thr.dtype]
     plan.out0_dtype = plan.out1_dtype = _hip.NONE
     numel = math.prod(thr.shape)
+    if thr.guidance is not None:  # the guided statistic and the guided thresholding-only launch
+        _hip.launch_guided_step_thresholded(plan, [o, x], None, out, thr.guidance.cond, thr.guidance.scale, thr.device_scale(o, x), thr.a, thr.b, numel // thr.shape[0], 0, 1,
+                                            None, numel, thr.device)
+        return out
     _hip.launch_step_thresholded(plan, [o, x], None, out, thr.device_scale(o, x), thr.a, thr.b, numel // thr.shape[0], 0, 1, None, numel, thr.device,
                                  ratio=thr.ratio, max_value=thr.max_value)
     return out
@@ -1017,6 +1047,8 @@ def evaluate_thresholded(form: Lin, thr: Threshold, dtype: torch.dtype | None = 
     if any(t.dtype == torch.float64 for t in leaves) or dtype == torch.float64:
         raise SkrampleHipError("thresholding takes bf16, fp16 or fp32 tensors, not fp64")
     out_dtype = dtype if dtype is not None else thr.dtype
+    if not any(host) and not thr.fused_guidance():  # a carried guidance the launches cannot form: guide_only first, then as ever
+        thr.settle_guidance()
     o, x = thr.output, thr.sample
     fused = not any(host) and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (*leaves, o, x))
     fused = fused and id(o) not in f.terms and any(isinstance(leaf, Node) and k != 0.0 for leaf, k in f.terms.values())
@@ -1028,6 +1060,10 @@ def evaluate_thresholded(form: Lin, thr: Threshold, dtype: torch.dtype | None = 
             final = empty_output(f.shape, out_dtype, thr.device)
             p = empty_output(f.shape, thr.dtype, thr.device)
             numel = math.prod(f.shape)
+            if thr.guidance is not None:  # uncond stands at `slot`: the guided statistic, then guidance, thresholding and step in one launch
+                _hip.launch_guided_step_thresholded(plan, operands, final, p, thr.guidance.cond, thr.guidance.scale, thr.device_scale(o, x), thr.a, thr.b, numel // f.shape[0],
+                                                    slot, xslot, seeds, numel, thr.device)
+                return final, p
             _hip.launch_step_thresholded(plan, operands, final, p, thr.device_scale(o, x), thr.a, thr.b, numel // f.shape[0], slot, xslot, seeds, numel, thr.device,
                                          ratio=thr.ratio, max_value=thr.max_value)
             return final, p

@@ -792,6 +792,79 @@ int skr_guided_thresholded_step_launch(const skr_step_plan* plan, const void* co
                                        const skr_step_threshold* thr, const uint64_t* seeds_dev, int64_t numel, void* stream);
 
 /*
+ * Adaptive projected guidance (APG; Sadat, Hilliges and Weber, "Eliminating Oversaturation and Artifacts of High Guidance Scales in
+ * Diffusion Models", 2024): the guidance difference, optionally a running average of it, is clamped to a per-sample norm, split into the
+ * part parallel to cond and the rest, and the parallel part is weighted by eta before the guided sum.  Three whole-sample dot products
+ * have to finish before the elementwise part starts, so the fused form is two launches, as rescaled guidance is: the statistic below,
+ * then skr_projected_guided_step_launch with its two per-sample coefficients.
+ *
+ * Definition.  Per sample s of sample_numel contiguous elements, T the tensors' dtype (bf16, fp16 or fp32), u, c, m elements of uncond,
+ * cond and the momentum buffer; g = guidance_scale, r = norm_threshold, beta = momentum.  Every operation is a separate IEEE fp32
+ * operation unless marked double, nothing is contracted, rn_T is the rounding of the store (the identity for fp32), and a double
+ * argument is narrowed to fp32 once where it meets tensor values:
+ *
+ *     d      = rn_T( (c - u) + (beta_f32 * m) )      with momentum (beta != 0);   d = rn_T(c - u) without
+ *     m_new  = d                                     stored in place whenever momentum_buf is given: the buffer is the running average
+ *     Sdd = sum d*d,  Sdc = sum d*c,  Scc = sum c*c  over the sample, in DOUBLE, in the fixed order below
+ *     norm   = sqrt(Sdd);   scale = (r > 0 && norm > r) ? r / norm : 1.0                  (double)
+ *     alpha  = Sdc / max(sqrt(Scc), 1e-12)^2                                              (double)
+ *     A_s    = (g - 1) * scale;   B_s = 1 - A_s * (1 - eta) * alpha                       (double, each narrowed to fp32 once on store)
+ *     p      = rn_T( (B_s * c) + (A_s * d) )
+ *
+ * p is the paper's cond + (g - 1) * (d_orth + eta * d_par) over the clamped difference, collected into two per-sample coefficients;
+ * eta = 1, r = 0 and beta = 0 give A = g - 1, B = 1: plain classifier-free guidance.
+ *
+ * skr_projected_guidance_coef writes coef_dev[2 s] = A_s, coef_dev[2 s + 1] = B_s and, when stats_dev is given, stats_dev[3 s .. 3 s + 2] =
+ * Sdd, Sdc, Scc.  Order of summation: that of skr_guidance_rescale_factor -- one workgroup of 256 lanes per 2048-element span of a
+ * sample; lane t owns the span's elements 8 t .. 8 t + 7 and adds them in that order to three running doubles that start at zero, each
+ * product formed in double by the fma that adds it (fma(d, d, Sdd), fma(d, c, Sdc), fma(c, c, Scc)); the shuffle tree o = 32 .. 1; the
+ * four waves as ((w0 + w1) + w2) + w3; three doubles per span at partials_dev[4 * (s * spans + j) .. + 2]; stage 2, one wave per sample,
+ * sums the spans in index order from zero.  No atomics: the order depends on sample_numel and the dtype alone, so a sample has the same
+ * coefficient bits alone and inside any batch.  A span that is 16-byte aligned and whole is read with 16-byte non-temporal loads, any
+ * other element by element: same lanes, same order, same bits; the lane that read m stores m_new.
+ * partials_dev: SKR_PROJECTED_PARTIALS(numel, sample_numel) doubles of device workspace, 8-byte aligned, overwritten.
+ * Checked before the launch, without dereferencing device memory, in the order and with the codes of skr_guidance_rescale_factor: a NULL
+ * uncond, cond, coef_dev or partials_dev, or momentum != 0 with a NULL momentum_buf, SKR_ERR_NULL;  numel < 0, sample_numel < 2 or
+ * numel % sample_numel != 0 SKR_ERR_SHAPE;  numel == 0 SKR_OK with nothing launched;  uncond, cond or momentum_buf not 16-byte aligned, or
+ * coef_dev not 4-byte aligned, SKR_ERR_ALIGN;  a dtype other than bf16, fp16 or fp32 SKR_ERR_DTYPE;  more than INT32_MAX spans in all
+ * SKR_ERR_UNSUPPORTED.  Allocates nothing, never synchronises: capturable.
+ *
+ * skr_projected_guided_step_launch: skr_step_launch_guided with p, as defined above, in the place of inputs[slot].  guide->scale is
+ * ignored: the coefficients carry it.  d is proj->diff[e] -- the momentum buffer after the statistic -- when diff is given, and
+ * rn_T(c - u) with u = inputs[slot][e] otherwise; with diff, inputs[slot] is checked like every operand and never read.  `out` has, bit
+ * for bit, what skr_step_launch writes for the same plan over the operand list whose entry `slot` is a tensor holding p; guided_out is
+ * that tensor (what history and pred_original_sample read).  The guidance-only form (out0_dtype == SKR_NONE, out == NULL, n_terms == 1)
+ * stores p alone.
+ * Launches of whole 2048-element chunks whose proj->sample_numel is a multiple of 2048 below 2^31, with one 16- or 32-bit dtype,
+ * 1..SKR_ROW_TERMS operands and a step output take a one-trip vector kernel -- a workgroup then lies inside one sample and A_s, B_s are
+ * two uniform loads behind the operand loads; with diff it loads cond and diff and never uncond, a compile-time split --; everything
+ * else (ragged sizes, small samples, two dtype groups, the guidance-only form) a grid-stride per-element kernel.  The two agree bit for
+ * bit ("one_trip" 0 forces the second).
+ * Checked before the launch, without dereferencing device memory, in the order and with the codes of skr_step_launch_guided, with what
+ * skr_step_launch_guided_rescaled adds for its structure: a NULL proj beside the NULL plan or guide SKR_ERR_NULL;  a non-zero
+ * proj->reserved, or acc_f64, beside the guide's `reserved` SKR_ERR_UNSUPPORTED;  behind the sample size of a launch that draws:
+ * proj->sample_numel < 2 or not dividing numel SKR_ERR_SHAPE, then a drawing plan whose sample_numel differs SKR_ERR_SHAPE;  a NULL
+ * coef_dev beside the NULL operands SKR_ERR_NULL;  a misaligned diff (16 bytes) or coef_dev (4 bytes) beside the others SKR_ERR_ALIGN;
+ * an fp64 tensor SKR_ERR_DTYPE.  Neither entry has a row form.  Allocates nothing, never synchronises: capturable.
+ */
+#define SKR_PROJECTED_PARTIALS(numel, sample_numel) (4 * ((numel) / (sample_numel)) * (((sample_numel) + 2047) / 2048))
+
+int skr_projected_guidance_coef(const void* uncond, const void* cond, void* momentum_buf /* T[numel], in / out; may be NULL */, int32_t dtype,
+                                double guidance_scale, double eta, double norm_threshold, double momentum, int64_t numel, int64_t sample_numel,
+                                float* coef_dev /* [2 * samples]: A_s, B_s */, double* stats_dev /* [3 * samples]: Sdd, Sdc, Scc; may be NULL */,
+                                double* partials_dev /* [SKR_PROJECTED_PARTIALS(numel, sample_numel)] */, void* stream);
+
+typedef struct skr_step_projection {
+  const float* coef_dev;   /* device float[2 * numel / sample_numel]: what skr_projected_guidance_coef wrote */
+  const void* diff;        /* device, 16-byte aligned, dtype T: the momentum buffer after the statistic; NULL: d = rn_T(c - u) in registers */
+  int64_t sample_numel;    /* elements per sample of the statistic */
+  int64_t reserved;        /* 0 */
+} skr_step_projection;
+
+int skr_projected_guided_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                     const skr_step_projection* proj, const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
  * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,
  * rows_dev[sample_index_dev[s] + row_offset] -- convert_k[0] the guidance scale (as in skr_step_launch_guided_rolling), convert_k[1]
  * phi = guidance_rescale (skr_step_launch_guided_rolling does not read it).  convert_k[2..3], coef1, chain, zeta1 and stream1 are not

@@ -54,6 +54,8 @@ EXPORTS = (
     "skr_thresholded_step_launch",
     "skr_guided_threshold_scale",
     "skr_guided_thresholded_step_launch",
+    "skr_projected_guidance_coef",
+    "skr_projected_guided_step_launch",
     "skr_threshold_scale_indexed",
     "skr_threshold_scale_indexed_per_sample",
     "skr_thresholded_step_launch_indexed",
@@ -258,6 +260,17 @@ class StepThresholdC(ctypes.Structure):
         ("sample_numel", ctypes.c_int64),
         ("slot", ctypes.c_int32),
         ("xslot", ctypes.c_int32),
+        ("reserved", ctypes.c_int64),
+    ]
+
+
+class StepProjectionC(ctypes.Structure):
+    "mirror of `skr_step_projection`: the per-sample coefficients of the statistics launch, the stored difference (or NULL) and the statistic's sample size"
+
+    _fields_ = [
+        ("coef_dev", ctypes.c_void_p),
+        ("diff", ctypes.c_void_p),
+        ("sample_numel", ctypes.c_int64),
         ("reserved", ctypes.c_int64),
     ]
 
@@ -748,6 +761,11 @@ def load() -> ctypes.CDLL:
         lib.skr_guided_threshold_scale.restype = ctypes.c_int
         lib.skr_guided_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepThresholdC), vp, i64, vp]
         lib.skr_guided_thresholded_step_launch.restype = ctypes.c_int
+        # (adaptive projected guidance: the statistic and the step, no forms)
+        lib.skr_projected_guidance_coef.argtypes = [vp, vp, vp, i32, f64, f64, f64, f64, i64, i64, vp, vp, vp, vp]
+        lib.skr_projected_guidance_coef.restype = ctypes.c_int
+        lib.skr_projected_guided_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepProjectionC), vp, i64, vp]
+        lib.skr_projected_guided_step_launch.restype = ctypes.c_int
         for suffix in ("_indexed", "_indexed_per_sample", "_rolling"):  # (their row forms: the direct arguments without the row values, the table where the rescaled row entries have it)
             entry = getattr(lib, "skr_threshold_scale" + suffix)
             entry.argtypes, entry.restype = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp], ctypes.c_int
@@ -1102,3 +1120,45 @@ def launch_guided_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor]
     status = load().skr_guided_thresholded_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(guide), ctypes.byref(thr), _ptr(seeds), numel,
                                                        current_stream_ptr(device))  # fmt: skip
     check(status, "skr_guided_thresholded_step_launch")
+
+
+PROJECTED_NO_HOOK = ("adaptive projected guidance (set_projected_guidance) has no row form: captured loops (capture_sampling_loop) and rolling batches (RollingBatch) "
+                     "do not take a wrapper under it")
+
+
+def projected_partials(numel: int, sample_numel: int) -> int:
+    "doubles of workspace skr_projected_guidance_coef needs (include/skrample_hip.h, SKR_PROJECTED_PARTIALS)"
+    return 4 * (numel // sample_numel) * ((sample_numel + GUIDANCE_SPAN - 1) // GUIDANCE_SPAN)
+
+
+def launch_projected_coef(uncond: torch.Tensor, cond: torch.Tensor, momentum_buf: "torch.Tensor | None", guidance_scale: float, eta: float, norm_threshold: float, momentum: float,
+                          sample_numel: int, coef: torch.Tensor, partials: torch.Tensor, stats: "torch.Tensor | None" = None) -> None:
+    """the statistics launch of adaptive projected guidance (skr_projected_guidance_coef): coef[2 s], coef[2 s + 1] = the two per-sample
+    coefficients of the projected prediction over sample s of `sample_numel` elements; `momentum_buf` (or None) is the running average of the
+    difference, read when `momentum` != 0 and overwritten in place with the new difference.  `coef` is float32[2 * samples], `partials`
+    float64[projected_partials(...)]: both the caller's, nothing is allocated here.  It has no row form: under an indexed-rows hook it raises."""
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError(f"skr_projected_guidance_coef: {PROJECTED_NO_HOOK}")
+    numel, device = uncond.numel(), uncond.device
+    status = load().skr_projected_guidance_coef(uncond.data_ptr(), cond.data_ptr(), _ptr(momentum_buf), DTYPE_CODE[uncond.dtype], float(guidance_scale), float(eta),
+                                                float(norm_threshold), float(momentum), numel, int(sample_numel), coef.data_ptr(), _ptr(stats), partials.data_ptr(),
+                                                current_stream_ptr(device))  # fmt: skip
+    check(status, "skr_projected_guidance_coef")
+
+
+def launch_projected_guided_step(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, slot: int, coef: torch.Tensor, diff: "torch.Tensor | None",
+                                 sample_numel: int, seeds, numel: int, device: torch.device) -> None:
+    """one projected guided step launch (skr_projected_guided_step_launch): launch_step_guided with the guided value replaced by
+    coef[2 s + 1] * cond + coef[2 s] * d, d the stored difference `diff` (the momentum buffer after launch_projected_coef) or, with None,
+    cond - operands[slot] formed in registers; `guided_out` (or None) receives it.  `out` None with a plan whose out0_dtype is NONE is the
+    guidance-only form.  The record goes to a `_hip.trace` list as kind "guided_projected"; it has no row form: under an indexed-rows hook it raises."""
+    if getattr(_hooks, "indexed", None) is not None:
+        raise SkrampleHipError(f"skr_projected_guided_step_launch: {PROJECTED_NO_HOOK}")
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append(StepCall(plan, operands, out, None, seeds, numel, "guided_projected", cond=cond, guided_out=guided_out, slot=int(slot), factor=coef, sample_numel=int(sample_numel)))
+    guide = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), 0.0, int(slot), 0)
+    proj = StepProjectionC(coef.data_ptr(), _ptr(diff), int(sample_numel), 0)
+    status = load().skr_projected_guided_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(guide), ctypes.byref(proj), _ptr(seeds), numel,
+                                                     current_stream_ptr(device))  # fmt: skip
+    check(status, "skr_projected_guided_step_launch")

@@ -759,6 +759,9 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         self._steps = steps
         self._thresholding = getattr(self, "_thresholding_next", None)
         self._thresholding_fuse = self._thresholding is not None and getattr(self, "_thresholding_fuse_next", False)
+        self._projection = getattr(self, "_projection_next", None)
+        if self._projection is not None:
+            self._projection.reset()  # a new run: the running average starts from zero, in the buffer it has
         if self.allow_dynamic:
             self.schedule = _apply_dynamic(self.schedule, steps, mu)
         self._previous = []
@@ -827,6 +830,8 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
         `fuse_guidance`: step_guided() calls under this mask take one launch for guidance, step and blend where they can (same bits)."""
         if getattr(self, "_thresholding_next", None) is not None or getattr(self, "_thresholding", None) is not None:
             raise lazy.SkrampleHipError("set_inpaint: in-painting beside dynamic thresholding (set_thresholding) is not covered; clear one of them")
+        if getattr(self, "_projection_next", None) is not None or getattr(self, "_projection", None) is not None:
+            raise lazy.SkrampleHipError("set_inpaint: in-painting beside projected guidance (set_projected_guidance) is not covered; clear one of them")
         for name, t in (("mask", mask), ("original_samples", original_samples), ("noise", noise)):
             if not isinstance(t, Tensor):
                 raise lazy.SkrampleHipError(f"set_inpaint: {name} must be a torch tensor, not {type(t).__name__}")
@@ -885,7 +890,35 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
             raise lazy.SkrampleHipError(f"set_thresholding: sample_max_value must be positive, not {sample_max_value}")
         if getattr(self, "_inpaint", None) is not None:
             raise lazy.SkrampleHipError("set_thresholding: dynamic thresholding beside in-painting (set_inpaint) is not covered; clear one of them")
+        if getattr(self, "_projection_next", None) is not None:
+            raise lazy.SkrampleHipError("set_thresholding: dynamic thresholding beside projected guidance (set_projected_guidance) is not covered; clear one of them")
         self._thresholding_next, self._thresholding_fuse_next = (float(ratio), float(sample_max_value)), bool(fuse_guidance)
+
+    # ---- adaptive projected guidance (APG; not in the reference) --------------------------------------------------------------------------
+    # Sadat, Hilliges and Weber (2024): the guidance difference cond - uncond, optionally a running average of it, is clamped to a
+    # per-sample norm and split into the part parallel to cond and the rest; the parallel part is weighted by eta.  In a pipeline that is
+    # some twenty tensor passes between the network and step(), several of them in float64.  Under set_projected_guidance() step_guided()
+    # runs it as two launches: the statistic (skr_projected_guidance_coef: three dot products per sample in double, the running average
+    # updated in place, two coefficients per sample) and the step with the projected prediction formed in registers
+    # (skr_projected_guided_step_launch) for Euler, DPM, Adams and UniP; UniPC, SPC and compute_scale=None take the guidance-only form
+    # of that launch and then their step over the stored prediction.  prev_sample and pred_original_sample are what step() gives over
+    # that prediction.  Host-resident operands evaluate the same definition with torch ops (lazy.Projection.host_value).
+    def set_projected_guidance(self, eta: float | None = 0.0, norm_threshold: float = 0.0, momentum: float = 0.0) -> None:
+        """adaptive projected guidance for the step_guided() calls of the runs that follow: takes effect from the next set_timesteps(), which
+        also zeroes the running average.  `eta` None clears it.  `eta` weights the part of the difference parallel to cond (1 keeps it:
+        plain guidance), `norm_threshold` > 0 clamps the difference's per-sample norm, `momentum` (the paper's is negative) keeps a running
+        average of the difference across the steps of a run.  The buffers are allocated once per latent shape and reused by every step."""
+        table_len = len(self._timestep_table()) if getattr(self, "_steps", None) else 0
+        if 0 < self._calls and self._index + self._calls < table_len:
+            raise lazy.SkrampleHipError("set_projected_guidance: projected guidance cannot change in the middle of a run; it takes effect from the next set_timesteps()")
+        if eta is None:
+            self._projection_next = None
+            return
+        if getattr(self, "_inpaint", None) is not None:
+            raise lazy.SkrampleHipError("set_projected_guidance: projected guidance beside in-painting (set_inpaint) is not covered; clear one of them")
+        if getattr(self, "_thresholding_next", None) is not None:
+            raise lazy.SkrampleHipError("set_projected_guidance: projected guidance beside dynamic thresholding (set_thresholding) is not covered; clear one of them")
+        self._projection_next = lazy.Projection(eta, norm_threshold, momentum)
 
     def _step_thresholded(self, model_output: Tensor, timestep, sample: Tensor, generator, return_dict: bool, guidance=None):
         """step() under set_thresholding: the Threshold leaf at this step's point, then the general path with DataModel as the model transform.
@@ -938,7 +971,13 @@ class SkrampleWrapperScheduler(SkrampleWrapperCore):
     def step_guided(self, model_output_uncond: Tensor, model_output_cond: Tensor, guidance_scale: float, timestep, sample: Tensor, generator=None, return_dict: bool = True,
                     guidance_rescale: float = 0.0):
         model_output_uncond, model_output_cond, sample = lazy.distinct(model_output_uncond, model_output_cond, sample)
-        guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale, guidance_rescale)
+        projection = getattr(self, "_projection", None)
+        if projection is not None:
+            if getattr(self, "_inpaint", None) is not None or getattr(self, "_thresholding", None) is not None:
+                raise lazy.SkrampleHipError("projected guidance beside in-painting (set_inpaint) or dynamic thresholding (set_thresholding) is not covered; clear one of them")
+            if lazy.grad_recorded(sample, *self._raw_outputs, *self._raw_samples, *(rec.sample for rec in self._previous)):
+                raise lazy.SkrampleHipError("projected guidance has no backward: operands that autograd records are refused")
+        guidance = lazy.Guidance(model_output_uncond, model_output_cond, guidance_scale, guidance_rescale, projection)
         if getattr(self, "_thresholding", None) is not None:
             if getattr(self, "_thresholding_fuse", False):  # the guidance rides on the Threshold leaf, which forms it inside its launches where it can
                 return self._step_thresholded(model_output_uncond, timestep, sample, generator, return_dict, guidance)

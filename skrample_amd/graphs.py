@@ -345,6 +345,10 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
+    if getattr(wrapper, "_projection_next", None) is not None or getattr(wrapper, "_projection", None) is not None:
+        from . import _hip
+
+        raise _hip.SkrampleHipError(_hip.PROJECTED_NO_HOOK)  # (three dot products per step: two launches without a row form)
     thresholding = getattr(wrapper, "_thresholding_next", None) is not None
     if not thresholded and (thresholding or getattr(wrapper, "_thresholding", None) is not None):
         from . import _hip

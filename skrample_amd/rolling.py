@@ -286,6 +286,8 @@ class RollingBatch:
                              f"(ragged samples are served from {PER_SAMPLE_CHUNK} elements on, in multiples of 8)")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
+        if getattr(first, "_projection_next", None) is not None or getattr(first, "_projection", None) is not None:
+            raise SkrampleHipError(_hip.PROJECTED_NO_HOOK)  # (before anything is allocated)
         if self.thresholded:
             self._refuse_thresholded(first)
         elif getattr(first, "_thresholding_next", None) is not None or getattr(first, "_thresholding", None) is not None:

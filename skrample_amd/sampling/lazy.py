@@ -133,6 +133,72 @@ def check_guidance_numbers(scale, rescale=0.0) -> None:
         raise SkrampleHipError(f"guidance_rescale must be >= 0, not {rescale}")
 
 
+class Projection:
+    """Adaptive projected guidance (include/skrample_hip.h, skr_projected_guidance_coef) carried beside a `Guidance`: the parallel weight,
+    the norm threshold, the momentum, and the buffers that outlive a step -- the running average of the difference (`momentum_buf`:
+    the operands' shape and dtype, None without momentum), the per-sample coefficients and the statistic's partial sums.  A wrapper
+    keeps one per run (SkrampleWrapperScheduler.set_projected_guidance); buffers that are missing or of another shape are allocated
+    where they are first needed, and never again for that shape."""
+
+    def __init__(self, eta: float, norm_threshold: float = 0.0, momentum: float = 0.0):
+        for name, v in (("eta", eta), ("norm_threshold", norm_threshold), ("momentum", momentum)):
+            if isinstance(v, bool) or not isinstance(v, NUMBER) or not math.isfinite(v):
+                raise SkrampleHipError(f"projected guidance: {name} is a finite Python number, not {v!r}")
+        if norm_threshold < 0.0:
+            raise SkrampleHipError(f"projected guidance: norm_threshold must be >= 0 (0 switches the clamp off), not {norm_threshold}")
+        self.eta, self.norm_threshold, self.momentum = float(eta), float(norm_threshold), float(momentum)
+        self.momentum_buf = self.coef = self.partials = None
+
+    def buffers(self, like: torch.Tensor) -> None:
+        "the three buffers for operands like `like` (dim 0 the sample): kept while shape, dtype and device stay"
+        m = self.momentum_buf
+        if self.momentum != 0.0 and (m is None or m.shape != like.shape or m.dtype != like.dtype or m.device != like.device):
+            self.momentum_buf = torch.zeros(like.shape, dtype=like.dtype, device=like.device)
+        if is_host(like.device):
+            return
+        samples, numel = like.shape[0], like.numel()
+        if self.coef is None or self.coef.numel() != 2 * samples or self.coef.device != like.device:
+            self.coef = torch.empty(2 * samples, dtype=torch.float32, device=like.device)
+        need = max(_hip.projected_partials(numel, numel // samples), 1)
+        if self.partials is None or self.partials.numel() != need or self.partials.device != like.device:
+            self.partials = torch.empty(need, dtype=torch.float64, device=like.device)
+
+    def reset(self) -> None:
+        "a new run: the running average starts from zero"
+        if self.momentum_buf is not None:
+            self.momentum_buf.zero_()
+
+    def host_value(self, u: torch.Tensor, c: torch.Tensor, scale: float) -> torch.Tensor:
+        "the definition in torch ops with the same roundings (host-resident operands); the running average is updated in place"
+        self.buffers(u)
+        dtype, samples = u.dtype, u.shape[0]
+        cf = c.float()
+        d = cf - u.float()
+        if self.momentum != 0.0:
+            d = d + self.momentum_buf.float() * self.momentum  # (a Python number meets an fp32 tensor as an fp32 scalar)
+            self.momentum_buf.copy_(d.to(dtype))
+        df = d.to(dtype).float()
+        dd, cd = df.double().reshape(samples, -1), cf.double().reshape(samples, -1)
+        sdd, sdc, scc = (dd * dd).sum(1), (dd * cd).sum(1), (cd * cd).sum(1)
+        norm, r = sdd.sqrt(), self.norm_threshold
+        clamp = torch.where(norm > r, r / norm, torch.ones_like(norm)) if r > 0.0 else torch.ones_like(norm)
+        root = scc.sqrt().clamp_min(1e-12)
+        a = (scale - 1.0) * clamp
+        b = 1.0 - a * (1.0 - self.eta) * (sdc / (root * root))
+        per_sample = (samples,) + (1,) * (u.ndim - 1)
+        return (b.float().reshape(per_sample) * cf + a.float().reshape(per_sample) * df).to(dtype)
+
+    def device_coef(self, guidance: "Guidance", u: torch.Tensor, c: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor | None]":
+        """(coef, diff) over contiguous 16-byte aligned device operands: the statistics launch, ONCE per guidance -- it advances the running
+        average --, whichever launch reads them afterwards"""
+        if guidance._coef_done is None:
+            self.buffers(u)
+            diff = self.momentum_buf if self.momentum != 0.0 else None
+            _hip.launch_projected_coef(u, c, diff, guidance.scale, self.eta, self.norm_threshold, self.momentum, u.numel() // u.shape[0], self.coef, self.partials)
+            guidance._coef_done = (self.coef, diff)
+        return guidance._coef_done
+
+
 class Guidance:
     """The classifier-free-guidance prediction  uncond + scale * (cond - uncond)  as ONE leaf of a step's form: its value is torch's --
     three tensor ops, each rounded in the tensors' dtype, the Python scalar kept in the op-math type -- and `evaluate_guided` computes
@@ -142,9 +208,19 @@ class Guidance:
     `torch_lines` -- with dim 0 the sample; on the HIP device the two per-sample stds are one statistics launch (`factor`,
     skr_guidance_rescale_factor) and the elementwise part runs inside the consuming launch (skr_step_launch_guided_rescaled)."""
 
-    def __init__(self, uncond: torch.Tensor, cond: torch.Tensor, scale: float, rescale: float = 0.0):
+    def __init__(self, uncond: torch.Tensor, cond: torch.Tensor, scale: float, rescale: float = 0.0, projection: "Projection | None" = None):
         if not isinstance(uncond, torch.Tensor) or not isinstance(cond, torch.Tensor):
             raise SkrampleHipError(f"guidance takes two torch tensors, not {type(uncond).__name__} and {type(cond).__name__}")
+        if projection is not None:  # `projection` (adaptive projected guidance): the prediction is Projection's, formed from the same two halves
+            if rescale != 0.0:
+                raise SkrampleHipError("projected guidance beside guidance_rescale is not covered: pass guidance_rescale=0.0 or clear set_projected_guidance")
+            if uncond.dtype == torch.float64:
+                raise SkrampleHipError("projected guidance takes bf16, fp16 or fp32 tensors, not fp64")
+            if grad_recorded(uncond, cond):
+                raise SkrampleHipError("projected guidance has no backward: its operands must not be recorded by autograd")
+            if uncond.ndim < 2 or uncond.numel() // max(uncond.shape[0], 1) < 2:
+                raise SkrampleHipError(f"projected guidance takes dot products over every sample: it needs tensors of ndim >= 2 (dim 0 the sample) with at least 2 elements per sample, not {tuple(uncond.shape)}")
+        self.projection, self._coef_done = projection, None
         _check_tensor(uncond), _check_tensor(cond)
         if uncond.dtype != cond.dtype or uncond.shape != cond.shape or uncond.device != cond.device:
             raise SkrampleHipError(
@@ -165,6 +241,8 @@ class Guidance:
 
     def torch_lines(self) -> torch.Tensor:
         "the pipeline's three lines -- and, rescaled, the four of rescale_noise_cfg -- by torch itself (host-resident operands; operands that autograd records)"
+        if self.projection is not None:  # (host-resident operands only: Guidance refused recorded ones)
+            return self.projection.host_value(self.uncond, self.cond, self.scale)
         d = self.cond - self.uncond
         m = self.scale * d
         p = self.uncond + m
@@ -827,7 +905,8 @@ def guide_only(guidance: Guidance) -> torch.Tensor:
     u, c = guidance.uncond, guidance.cond
     if is_host(guidance.device) or grad_recorded(u, c):
         return _host_result(guidance.torch_lines(), (u, c), guidance.shape)
-    in_place = in_place_layout((u, c), guidance.shape) is not None
+    projection = guidance.projection
+    in_place = projection is None and in_place_layout((u, c), guidance.shape) is not None  # (a projected guidance copies channels-last operands: its sums run in logical order)
     prepare = _prepare_keeping_layout if in_place else _prepare_tensor
     u, c = prepare(u), prepare(c)
     out = empty_output(guidance.shape, guidance.dtype, guidance.device, channels_last=in_place)
@@ -838,7 +917,11 @@ def guide_only(guidance: Guidance) -> torch.Tensor:
     plan.acc_f64 = 1 if guidance.dtype == torch.float64 else 0
     plan.coef0[0] = 1.0
     numel = math.prod(guidance.shape)
-    if guidance.rescale != 0.0:  # the statistic over the same storage order, then the rescaled guidance-only launch
+    if projection is not None:  # the statistic, then the guidance-only form of the projected step
+        plan.acc_f64 = 0
+        coef, diff = projection.device_coef(guidance, u, c)
+        _hip.launch_projected_guided_step(plan, [u], None, c, out, 0, coef, diff, numel // guidance.shape[0], None, numel, guidance.device)
+    elif guidance.rescale != 0.0:  # the statistic over the same storage order, then the rescaled guidance-only launch
         _hip.launch_step_guided_rescaled(plan, [u], None, c, out, guidance.scale, 0, guidance.device_factor(u, c), guidance.rescale, numel // guidance.shape[0], None, numel, guidance.device)
     else:
         _hip.launch_step_guided(plan, [u], None, c, out, guidance.scale, 0, None, numel, guidance.device)
@@ -875,11 +958,14 @@ def evaluate_guided(form: Lin, guidance: Guidance, dtype: torch.dtype | None = N
     if fused:
         plan, operands, seeds = _lower(None, f.substitute(guidance, u), None, 0.0, [out_dtype], acc_f64)
         slot = next((k for k, t in enumerate(operands) if t is u), None)
-        if slot is not None and len(operands) <= _hip.ROW_TERMS:
+        if slot is not None and len(operands) <= _hip.ROW_TERMS and (guidance.projection is None or not plan.acc_f64):
             final = empty_output(f.shape, out_dtype, guidance.device)
             guided = empty_output(f.shape, guidance.dtype, guidance.device)
             numel = math.prod(f.shape)
-            if guidance.rescale != 0.0:  # the statistics launch, then the step with its per-sample factor
+            if guidance.projection is not None:  # the statistics launch, then the step with its two per-sample coefficients
+                coef, diff = guidance.projection.device_coef(guidance, u, c)
+                _hip.launch_projected_guided_step(plan, operands, final, c, guided, slot, coef, diff, numel // f.shape[0], seeds, numel, guidance.device)
+            elif guidance.rescale != 0.0:  # the statistics launch, then the step with its per-sample factor
                 _hip.launch_step_guided_rescaled(plan, operands, final, c, guided, guidance.scale, slot, guidance.device_factor(u, c), guidance.rescale, numel // f.shape[0],
                                                  seeds, numel, guidance.device)
             else:
@@ -942,6 +1028,8 @@ class Threshold:
             raise SkrampleHipError("thresholding takes bf16, fp16 or fp32 tensors, not fp64")
         if guidance is not None and (not isinstance(guidance, Guidance) or guidance.uncond is not output):
             raise SkrampleHipError("a guided Threshold takes a Guidance whose uncond half is its output")
+        if guidance is not None and guidance.projection is not None:
+            raise SkrampleHipError("projected guidance beside dynamic thresholding is not covered: the guided thresholded launches have no projected form")
         if grad_recorded(output, sample) or (guidance is not None and grad_recorded(guidance.cond)):
             raise SkrampleHipError("thresholding has no backward: its operands must not be recorded by autograd")
         if output.ndim < 2 or output.numel() == 0:
@@ -1098,6 +1186,8 @@ def evaluate_guided_masked(form: Lin, guidance: Guidance, known: Lin, mask: torc
     f, f1 = lift(form), lift(known)
     if not isinstance(f, Lin) or not isinstance(f1, Lin) or not isinstance(guidance, Guidance) or not isinstance(mask, torch.Tensor):
         raise SkrampleHipError("evaluate_guided_masked() takes a tensor form, a Guidance, the known form and a mask tensor")
+    if guidance.projection is not None:
+        raise SkrampleHipError("projected guidance beside in-painting is not covered: the guided masked launch has no projected form")
     f, f1 = f.expanded(keep=guidance), f1.expanded()
     if any(isinstance(leaf, Node) and leaf.form is not guidance for form_ in (f, f1) for leaf, _ in form_.terms.values()):
         raise SkrampleHipError("a guided masked launch has one step output: its forms cannot refer to another stored form")

@@ -845,7 +845,7 @@ int skr_guided_thresholded_step_launch(const skr_step_plan* plan, const void* co
  * proj->reserved, or acc_f64, beside the guide's `reserved` SKR_ERR_UNSUPPORTED;  behind the sample size of a launch that draws:
  * proj->sample_numel < 2 or not dividing numel SKR_ERR_SHAPE, then a drawing plan whose sample_numel differs SKR_ERR_SHAPE;  a NULL
  * coef_dev beside the NULL operands SKR_ERR_NULL;  a misaligned diff (16 bytes) or coef_dev (4 bytes) beside the others SKR_ERR_ALIGN;
- * an fp64 tensor SKR_ERR_DTYPE.  Neither entry has a row form.  Allocates nothing, never synchronises: capturable.
+ * an fp64 tensor SKR_ERR_DTYPE.  Allocates nothing, never synchronises: capturable.  The row forms of both follow the two entries.
  */
 #define SKR_PROJECTED_PARTIALS(numel, sample_numel) (4 * ((numel) / (sample_numel)) * (((sample_numel) + 2047) / 2048))
 
@@ -863,6 +863,61 @@ typedef struct skr_step_projection {
 
 int skr_projected_guided_step_launch(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
                                      const skr_step_projection* proj, const uint64_t* seeds_dev, int64_t numel, void* stream);
+
+/*
+ * Projected guidance in captured loops: the two launches above with the four scalars of a setting taken from a row, so that one captured
+ * loop serves any schedule, any guidance scale and any (eta, norm_threshold, momentum) without re-capture.  A projected plan has
+ * convert_to == convert_from == 0, so a projected row carries
+ *     convert_k[0] = g (guidance scale)   convert_k[1] = eta   convert_k[2] = r (norm_threshold)   convert_k[3] = beta (momentum)
+ * and the row is the one every indexed entry reads: rows_dev[(index_dev ? index_dev[0] : 0) + row_offset] in the indexed entries,
+ * rows_dev[sample_index_dev[s] + row_offset] for the workgroups of sample s in the per-sample entries.  Index validity is the caller's
+ * business, as in skr_step_launch_indexed_per_sample.  coef1, chain, zeta1 and stream1 are not read.  A step of a loop is the statistics
+ * launch, then the step launch, with the same rows, index and row_offset, on one momentum buffer the loop owns.
+ *
+ * Contract.  For every sample s, the buffer's elements of s, coef_dev[2 s .. 2 s + 1], out and guided_out have, bit for bit, what
+ * skr_projected_guidance_coef followed by skr_projected_guided_step_launch write for that sample ALONE, called with the row's g, eta, r
+ * and beta, the row's coef0 / zeta0 / stream0 in the plan, and momentum_buf / diff given exactly when beta != 0 (either sign of zero is
+ * zero).
+ *
+ * skr_projected_guidance_coef_indexed[_per_sample]: momentum_buf is REQUIRED.  A workgroup takes a uniform branch on its row's beta: a
+ * zero-momentum row neither reads the buffer nor stores to it -- the sample's bytes stay as they are --, a momentum row reads m, forms
+ * d = rn_T((c - u) + beta_f32 * m), beta narrowed once on the device (round to nearest even), and stores it over m.  Summation order,
+ * partials layout and coefficient arithmetic are the direct entry's.  Covered: bf16, fp16, fp32; sample_numel a positive multiple of 2048
+ * that divides numel (there is no element-by-element path).  Checked in the order and with the codes of
+ * skr_guidance_rescale_factor_indexed[_per_sample]: a NULL uncond, cond, momentum_buf, coef_dev, partials_dev or rows_dev, or a NULL
+ * sample_index_dev in the per-sample entry, SKR_ERR_NULL;  numel < 0, sample_numel < 2 or numel % sample_numel != 0 SKR_ERR_SHAPE;
+ * numel == 0 SKR_OK;  uncond, cond or momentum_buf not 16-byte aligned, or coef_dev not 4-byte aligned, SKR_ERR_ALIGN;  a dtype that is
+ * no tensor dtype SKR_ERR_DTYPE;  fp64, a sample that is not whole 2048-element spans, a negative row_offset or more than INT32_MAX spans
+ * SKR_ERR_UNSUPPORTED.
+ *
+ * skr_projected_guided_step_launch_indexed[_per_sample]: `plan` fixes the structure only; coef0[0 .. n_terms), zeta0 and stream0 are the
+ * row's (a row whose zeta0 narrows to zero skips the draw), guide->scale is ignored, and proj->diff -- the loop's buffer -- is REQUIRED
+ * beside inputs[slot] = uncond.  A workgroup of a momentum row loads the difference and never uncond; a workgroup of a zero-momentum row
+ * loads uncond, never the buffer, and forms d = rn_T(c - u) in registers.  Covered: whole 2048-element chunks, proj->sample_numel a
+ * multiple of 2048 below 2^31 that divides numel, one 16- or 32-bit dtype, 1..SKR_ROW_TERMS operands and a step output; there is no
+ * grid-stride kernel and no guidance-only form.  Checked in the order and with the codes of skr_projected_guided_step_launch, with what
+ * skr_thresholded_step_launch_indexed adds for rows: a NULL rows_dev, or sample_index_dev in the per-sample entry, beside the NULL plan;
+ * the plan's chain and zeta1 are ignored like its other scalars;  a plan without a step output SKR_ERR_UNSUPPORTED where the direct
+ * entry tests the guidance-only form;  a NULL proj->diff beside the NULL coef_dev SKR_ERR_NULL;  after the dtype checks anything the
+ * one-trip kernel does not cover, or a negative row_offset, SKR_ERR_UNSUPPORTED.
+ * All four allocate nothing and never synchronise: capturable.
+ */
+int skr_projected_guidance_coef_indexed(const void* uncond, const void* cond, void* momentum_buf /* T[numel], in / out */, int32_t dtype, int64_t numel,
+                                        int64_t sample_numel, const skr_step_row* rows_dev, const int32_t* index_dev /* may be NULL */, int32_t row_offset,
+                                        float* coef_dev /* [2 * samples] */, double* stats_dev /* [3 * samples]; may be NULL */,
+                                        double* partials_dev /* [SKR_PROJECTED_PARTIALS(numel, sample_numel)] */, void* stream);
+
+int skr_projected_guidance_coef_indexed_per_sample(const void* uncond, const void* cond, void* momentum_buf, int32_t dtype, int64_t numel, int64_t sample_numel,
+                                                   const skr_step_row* rows_dev, const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                                   int32_t row_offset, float* coef_dev, double* stats_dev, double* partials_dev, void* stream);
+
+int skr_projected_guided_step_launch_indexed(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                             const skr_step_projection* proj, const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                             const int32_t* index_dev /* may be NULL */, int32_t row_offset, void* stream);
+
+int skr_projected_guided_step_launch_indexed_per_sample(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                                        const skr_step_projection* proj, const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                                        const int32_t* sample_index_dev, int32_t row_offset, void* stream);
 
 /*
  * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,

@@ -56,6 +56,10 @@ EXPORTS = (
     "skr_guided_thresholded_step_launch",
     "skr_projected_guidance_coef",
     "skr_projected_guided_step_launch",
+    "skr_projected_guidance_coef_indexed",
+    "skr_projected_guidance_coef_indexed_per_sample",
+    "skr_projected_guided_step_launch_indexed",
+    "skr_projected_guided_step_launch_indexed_per_sample",
     "skr_threshold_scale_indexed",
     "skr_threshold_scale_indexed_per_sample",
     "skr_thresholded_step_launch_indexed",
@@ -387,6 +391,11 @@ class IndexedRows:
     <= 1 makes the first return at once and the second the plain clip.
     `guided` (a capture with guidance): guided launches go through the recorder as well (skr_step_launch_guided_indexed[_per_sample]),
     each row carrying its launch's guidance scale.
+    `projected` (with `guided`; `samples`: the captured batch): projected guided step launches go through the recorder (launch_projected),
+    each row carrying the guidance scale, eta, the norm threshold and the momentum in convert_k[0..3].  Every emitted projected step is TWO
+    launches on buffers the hook owns (`momentum_buf`, `coef`, `projected_partials`), with the same row offset:
+    skr_projected_guidance_coef_indexed[_per_sample], then skr_projected_guided_step_launch_indexed[_per_sample].  The running average is
+    the hook's alone: recording and refilling run the eager pair on the wrapper's own buffers.
     `rescaled` (with `guided`; `samples`: the captured batch): rescaled guided launches go through it too, each row carrying
     guidance_rescale in convert_k[1] -- 0.0 for a plain guided launch.  Every emitted guided step is then TWO launches on buffers the hook
     owns (`factor`, `partials`: allocated in the recording pass, the same in every step of the graph), with the same row offset:
@@ -404,7 +413,18 @@ class IndexedRows:
                    that the structure is the captured one -- how a captured loop is re-targeted to another schedule."""
 
     def __init__(self, device: torch.device, slots: int = 4, batch: int | None = None, guided: bool = False, rescaled: bool = False, samples: int | None = None,
-                 thresholded: bool = False):
+                 thresholded: bool = False, projected: bool = False):
+        if projected and (not guided or rescaled or thresholded):
+            raise ValueError("projected=True needs guided=True and neither rescaled nor thresholded: a row's convert_k holds one feature's scalars")
+        if projected and (samples is None or samples < 1):
+            raise ValueError("projected=True needs samples=: the captured batch, two coefficients per sample")
+        if projected and batch is not None and batch != samples:
+            raise ValueError(f"a per-sample capture of {batch} samples cannot hold coefficients for {samples}")
+        # a capture with projected guidance: the running average (shaped like the latents), coef float32[2 * samples] and the partials of every emitted statistics launch
+        self.projected = projected
+        self.momentum_buf: torch.Tensor | None = None
+        self.coef: torch.Tensor | None = None
+        self.projected_partials: torch.Tensor | None = None
         if thresholded and (samples is None or samples < 1):
             raise ValueError("thresholded=True needs samples=: the captured batch, one scale per sample")
         if thresholded and batch is not None and batch != samples:
@@ -537,6 +557,75 @@ class IndexedRows:
         if not 2 <= plan.n_terms <= ROW_TERMS:
             return f"thresholded rows take 2 to {ROW_TERMS} operands, not {plan.n_terms}"
         return None
+
+    def _uncovered_projected(self, plan: StepPlanC, proj: "StepProjectionC", numel: int) -> str | None:
+        "why the projected row kernels do not cover this launch of the captured batch (skr_projected_guided_step_launch_indexed), or None"
+        if plan.out0_dtype == NONE:
+            return ("the guidance-only launch of projected guidance has no row form: it serves the two-output samplers (UniPC, SPC), compute_scale=None / float64 "
+                    "and channels-last or strided operands")
+        if plan.acc_f64:
+            return "projected rows are evaluated in float32, not under compute_scale=float64"
+        if not one_dtype_f32(plan):
+            return "projected rows need one 16- or 32-bit dtype for operands, cond and both outputs"
+        if numel % self.samples != 0 or (numel // self.samples) % PER_SAMPLE_CHUNK != 0:
+            return f"projected rows need samples of whole {PER_SAMPLE_CHUNK}-element chunks, not {numel} elements for {self.samples} samples (ragged samples have no projected row form)"
+        if proj.sample_numel != numel // self.samples:
+            return f"projected rows take the dot products over the samples of the captured batch: {numel // self.samples} elements, not {proj.sample_numel}"
+        if not 1 <= plan.n_terms <= ROW_TERMS:
+            return f"projected rows take 1 to {ROW_TERMS} operands, not {plan.n_terms}"
+        return None
+
+    def launch_projected(self, lib, plan: StepPlanC, arr, out_ptr, guide: "StepGuidanceC", proj: "StepProjectionC", setting: tuple, seeds_ptr, numel: int, stream_ptr: int) -> int:
+        """one projected guided step launch of the loop (skr_projected_guided_step_launch and its row forms): recorded or refilled with
+        `setting` -- (guidance scale, eta, norm_threshold, momentum) -- in the row's convert_k[0..3], emitted as the statistics row launch and
+        the row step on the hook's buffers"""
+        k = self.cursor
+        self.cursor += 1
+
+        def structure(shaped: bool) -> tuple:
+            return (*plan_structure(plan, sample_numel=shaped), "projected", guide.slot, bool(guide.guided_out), proj.sample_numel if shaped else None)
+
+        def direct() -> int:  # the launch itself, with the plan's own scalars, on the coefficients and the difference the caller's statistics launch left
+            return lib.skr_projected_guided_step_launch(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), ctypes.byref(proj), seeds_ptr, numel, stream_ptr)
+
+        row = self.row_from(plan)
+        row.convert_k[0], row.convert_k[1], row.convert_k[2], row.convert_k[3] = setting
+        if self.mode == "record":
+            why = self._uncovered_projected(plan, proj, numel)
+            if why is not None:  # (what skr_projected_guided_step_launch_indexed would answer during the capture: said here, before a stream is capturing)
+                raise SkrampleHipError(f"launch {k}: {lib.skr_strerror(SKR_ERR_UNSUPPORTED).decode()}: {why}")
+            dtype, need = CODE_DTYPE[plan.dtype_a], projected_partials(numel, proj.sample_numel)
+            if self.momentum_buf is None:  # allocated here, before a stream captures; every emitted step of the graph uses these three
+                self.momentum_buf = torch.zeros(numel, dtype=dtype, device=self.device)
+                self.coef = torch.zeros(2 * self.samples, dtype=torch.float32, device=self.device)
+                self.projected_partials = torch.zeros(need, dtype=torch.float64, device=self.device)
+            elif self.momentum_buf.dtype != dtype or self.momentum_buf.numel() != numel:
+                raise SkrampleHipError(f"launch {k}: the projected steps of one capture share one running average and one workspace: one dtype and one size")
+            self.structures.append(structure(True))
+            self.shapeless.append(structure(False))
+            self.host.append(row)
+            return direct()
+        if k >= self.length:
+            raise SkrampleHipError("more launches than the captured loop has")
+        if self.mode == "refill":
+            if structure(False) != self.shapeless[k]:
+                raise SkrampleHipError(f"launch {k} of the new schedule has a different structure than the captured loop: re-capture")
+            self.host[self.slot * self.length + k] = row
+            return direct()
+        if structure(True) != self.structures[k]:
+            raise SkrampleHipError(f"launch {k} differs in structure between the recording pass and the capture")
+        # emit: the statistics row launch over (inputs[slot], cond), then the row step, on the hook's buffers and with the same row offset.  A
+        # zero-momentum row leaves the running average alone in the first and reads uncond in the second.
+        per_sample = self.sample_index_dev is not None
+        suffix = "_indexed_per_sample" if per_sample else "_indexed"
+        table = (self.rows_dev.data_ptr(), (self.sample_index_dev if per_sample else self.index_dev).data_ptr(), k)
+        status = getattr(lib, "skr_projected_guidance_coef" + suffix)(arr[guide.slot], guide.cond, self.momentum_buf.data_ptr(), plan.dtype_a, numel, proj.sample_numel, *table,
+                                                                      self.coef.data_ptr(), None, self.projected_partials.data_ptr(), stream_ptr)  # fmt: skip
+        if status != 0:
+            return status
+        held = StepProjectionC(self.coef.data_ptr(), self.momentum_buf.data_ptr(), proj.sample_numel, 0)
+        return getattr(lib, "skr_projected_guided_step_launch" + suffix)(ctypes.byref(plan), arr, out_ptr, ctypes.byref(guide), ctypes.byref(held), seeds_ptr, numel, *table,
+                                                                         stream_ptr)  # fmt: skip
 
     def launch_thresholded(self, lib, plan: StepPlanC, arr, out_ptr, thr: "StepThresholdC", ratio: float, max_value: float, seeds_ptr, numel: int, stream_ptr: int) -> int:
         """one thresholded step launch of the loop (skr_thresholded_step_launch and its row forms): recorded or refilled with the to_x weights,
@@ -761,11 +850,17 @@ def load() -> ctypes.CDLL:
         lib.skr_guided_threshold_scale.restype = ctypes.c_int
         lib.skr_guided_thresholded_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepThresholdC), vp, i64, vp]
         lib.skr_guided_thresholded_step_launch.restype = ctypes.c_int
-        # (adaptive projected guidance: the statistic and the step, no forms)
+        # (adaptive projected guidance: the statistic and the step, outside the table like thresholding's)
         lib.skr_projected_guidance_coef.argtypes = [vp, vp, vp, i32, f64, f64, f64, f64, i64, i64, vp, vp, vp, vp]
         lib.skr_projected_guidance_coef.restype = ctypes.c_int
         lib.skr_projected_guided_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepProjectionC), vp, i64, vp]
         lib.skr_projected_guided_step_launch.restype = ctypes.c_int
+        for suffix in ("_indexed", "_indexed_per_sample"):  # (their row forms: the four doubles and the plan's scalars are row values, the table where the thresholded row entries have it)
+            entry = getattr(lib, "skr_projected_guidance_coef" + suffix)
+            entry.argtypes, entry.restype = [vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp], ctypes.c_int
+            entry = getattr(lib, "skr_projected_guided_step_launch" + suffix)
+            entry.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepProjectionC), vp, i64, vp, vp, i32, vp]
+            entry.restype = ctypes.c_int
         for suffix in ("_indexed", "_indexed_per_sample", "_rolling"):  # (their row forms: the direct arguments without the row values, the table where the rescaled row entries have it)
             entry = getattr(lib, "skr_threshold_scale" + suffix)
             entry.argtypes, entry.restype = [vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp], ctypes.c_int
@@ -1122,8 +1217,16 @@ def launch_guided_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor]
     check(status, "skr_guided_thresholded_step_launch")
 
 
-PROJECTED_NO_HOOK = ("adaptive projected guidance (set_projected_guidance) has no row form: captured loops (capture_sampling_loop) and rolling batches (RollingBatch) "
-                     "do not take a wrapper under it")
+PROJECTED_NO_HOOK = ("adaptive projected guidance (set_projected_guidance) has no row form in a loop captured without it: pass projected=True to capture_sampling_loop (the "
+                     "guidance scale, eta, the norm threshold and the momentum are then row values); RollingBatch does not take a wrapper under it")
+
+
+def _projected_hook() -> "IndexedRows | None":
+    "the installed indexed-rows hook, which must have been created for projected guidance (capture_sampling_loop with `projected=True`)"
+    rows = getattr(_hooks, "indexed", None)
+    if rows is not None and not getattr(rows, "projected", False):
+        raise SkrampleHipError(PROJECTED_NO_HOOK)
+    return rows
 
 
 def projected_partials(numel: int, sample_numel: int) -> int:
@@ -1136,9 +1239,13 @@ def launch_projected_coef(uncond: torch.Tensor, cond: torch.Tensor, momentum_buf
     """the statistics launch of adaptive projected guidance (skr_projected_guidance_coef): coef[2 s], coef[2 s + 1] = the two per-sample
     coefficients of the projected prediction over sample s of `sample_numel` elements; `momentum_buf` (or None) is the running average of the
     difference, read when `momentum` != 0 and overwritten in place with the new difference.  `coef` is float32[2 * samples], `partials`
-    float64[projected_partials(...)]: both the caller's, nothing is allocated here.  It has no row form: under an indexed-rows hook it raises."""
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError(f"skr_projected_guidance_coef: {PROJECTED_NO_HOOK}")
+    float64[projected_partials(...)]: both the caller's, nothing is allocated here.
+    Under an indexed-rows hook created for a projected capture (IndexedRows(projected=True)) it runs as it stands while the hook records or
+    refills, and is NOT issued while the hook emits: the step launch that follows emits the statistics row launch itself, on the hook's
+    buffers.  Under any other hook it raises."""
+    rows = _projected_hook()
+    if rows is not None and rows.mode == "emit":
+        return
     numel, device = uncond.numel(), uncond.device
     status = load().skr_projected_guidance_coef(uncond.data_ptr(), cond.data_ptr(), _ptr(momentum_buf), DTYPE_CODE[uncond.dtype], float(guidance_scale), float(eta),
                                                 float(norm_threshold), float(momentum), numel, int(sample_numel), coef.data_ptr(), _ptr(stats), partials.data_ptr(),
@@ -1147,18 +1254,26 @@ def launch_projected_coef(uncond: torch.Tensor, cond: torch.Tensor, momentum_buf
 
 
 def launch_projected_guided_step(plan: StepPlanC, operands: list[torch.Tensor], out, cond: torch.Tensor, guided_out, slot: int, coef: torch.Tensor, diff: "torch.Tensor | None",
-                                 sample_numel: int, seeds, numel: int, device: torch.device) -> None:
+                                 sample_numel: int, seeds, numel: int, device: torch.device, setting: "tuple | None" = None) -> None:
     """one projected guided step launch (skr_projected_guided_step_launch): launch_step_guided with the guided value replaced by
     coef[2 s + 1] * cond + coef[2 s] * d, d the stored difference `diff` (the momentum buffer after launch_projected_coef) or, with None,
     cond - operands[slot] formed in registers; `guided_out` (or None) receives it.  `out` None with a plan whose out0_dtype is NONE is the
-    guidance-only form.  The record goes to a `_hip.trace` list as kind "guided_projected"; it has no row form: under an indexed-rows hook it raises."""
-    if getattr(_hooks, "indexed", None) is not None:
-        raise SkrampleHipError(f"skr_projected_guided_step_launch: {PROJECTED_NO_HOOK}")
+    guidance-only form.  The record goes to a `_hip.trace` list as kind "guided_projected".
+    Under an indexed-rows hook created for a projected capture the launch is recorded, emitted as skr_projected_guidance_coef_indexed[_per_sample]
+    plus skr_projected_guided_step_launch_indexed[_per_sample] -- `setting`, (guidance scale, eta, norm_threshold, momentum), required there,
+    row values; `coef` and `diff` replaced by the hook's own -- or refilled (IndexedRows.launch_projected).  Under any other hook it raises."""
+    rows = _projected_hook()
     trace = getattr(_hooks, "trace", None)
     if trace is not None:
         trace.append(StepCall(plan, operands, out, None, seeds, numel, "guided_projected", cond=cond, guided_out=guided_out, slot=int(slot), factor=coef, sample_numel=int(sample_numel)))
     guide = StepGuidanceC(cond.data_ptr(), _ptr(guided_out), 0.0, int(slot), 0)
     proj = StepProjectionC(coef.data_ptr(), _ptr(diff), int(sample_numel), 0)
-    status = load().skr_projected_guided_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(guide), ctypes.byref(proj), _ptr(seeds), numel,
-                                                     current_stream_ptr(device))  # fmt: skip
+    if rows is not None:
+        if setting is None:
+            raise SkrampleHipError("a projected launch of a captured loop carries its guidance scale, eta, norm threshold and momentum: they are row values")
+        status = rows.launch_projected(load(), plan, _operand_array(operands), _ptr(out), guide, proj, tuple(float(v) for v in setting), _ptr(seeds), numel,
+                                       current_stream_ptr(device))  # fmt: skip
+    else:
+        status = load().skr_projected_guided_step_launch(ctypes.byref(plan), _operand_array(operands), _ptr(out), ctypes.byref(guide), ctypes.byref(proj), _ptr(seeds), numel,
+                                                         current_stream_ptr(device))  # fmt: skip
     check(status, "skr_projected_guided_step_launch")

@@ -11,7 +11,6 @@
 //   stage 2 (projected_final): one wave per sample; lanes 0..2 each sum one quantity over the sample's spans in index order, lane 0
 //     finishes in double and narrows each coefficient once.
 // MODE: 0 no buffer (d = rn_T(c - u), nothing stored); 1 a buffer without momentum (the same d, stored); 2 momentum (m read, d stored).
-#include "skr_guidance_stats.h"
 #include "skr_projected.h"
 #include "skr_device.h"
 
@@ -64,45 +63,15 @@ __global__ __launch_bounds__(BLOCK) void projected_spans(const void* uncond, con
     }
   }
 
-  double sdd = 0.0, sdc = 0.0, scc = 0.0;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    if (whole || at + i < len) {
-      const double dd = (double)d[i], cc = (double)c[i];
-      sdd = fma_(dd, dd, sdd);
-      sdc = fma_(dd, cc, sdc);
-      scc = fma_(cc, cc, scc);
-    }
-  }
-  __shared__ double red[3][4];
-  sdd = wave_sum(sdd), sdc = wave_sum(sdc), scc = wave_sum(scc);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = sdd; red[1][wave] = sdc; red[2][wave] = scc; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const double* r = red[threadIdx.x];
-    partials[(int64_t)blockIdx.x * 4 + threadIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
-  }
+  projected_span_sums(d, c, whole, at, len, partials + (int64_t)blockIdx.x * 4);
 }
 
 __global__ __launch_bounds__(64) void projected_final(const double* partials, uint32_t spans, double g, double eta, double r, float* coef, double* stats) {
   const int64_t smp = blockIdx.x;
-  double acc = 0.0;
-  if (threadIdx.x < 3) {
-    const double* p = partials + smp * spans * 4 + threadIdx.x;
-    for (uint32_t j = 0; j < spans; ++j) acc += p[(int64_t)j * 4];
-  }
-  const double sdd = __shfl(acc, 0), sdc = __shfl(acc, 1), scc = __shfl(acc, 2);
+  double sdd, sdc, scc;
+  projected_sample_sums(partials, smp, spans, sdd, sdc, scc);
   if (threadIdx.x != 0) return;
-  if (stats != nullptr) { stats[3 * smp] = sdd; stats[3 * smp + 1] = sdc; stats[3 * smp + 2] = scc; }
-  const double norm = __dsqrt_rn(sdd);
-  const double scale = (r > 0.0 && norm > r) ? div_(r, norm) : 1.0;
-  const double root = __dsqrt_rn(scc), den = root > 1e-12 ? root : 1e-12;
-  const double alpha = div_(sdc, mul_(den, den));
-  const double A = mul_(sub_(g, 1.0), scale);
-  const double B = sub_(1.0, mul_(mul_(A, sub_(1.0, eta)), alpha));
-  coef[2 * smp] = (float)A;
-  coef[2 * smp + 1] = (float)B;
+  projected_finish(sdd, sdc, scc, g, eta, r, smp, coef, stats);
 }
 
 }  // namespace skr

@@ -49,6 +49,14 @@ tensor and one workspace the loop owns, `retarget(wrapper, slot)` loads the new 
 maximum <= 1 included, the plain clip, which makes the first launch return at once -- and with `per_sample=True` every sample follows its
 own.  UniPC and SPC take the thresholding-only row launch and then their step through the plain row launches.  Without the keyword a
 thresholding wrapper is refused, as before.
+
+Adaptive projected guidance (`wrapper.set_projected_guidance(eta, norm_threshold, momentum)`) is captured on request as well,
+`projected=True` beside `guidance_scale=`.  A plain capture records the eager pair -- the statistic and the projected step -- and freezes
+the four scalars into the graph.  An indexed capture keeps them in the rows (`convert_k[0..3]`: scale, eta, norm threshold, momentum): every
+step of the graph is the statistics row launch and the row step (`skr_projected_guidance_coef_indexed[_per_sample]`,
+`skr_projected_guided_step_launch_indexed[_per_sample]`) on one running average, one coefficient tensor and one workspace the loop owns,
+`retarget(wrapper, slot, guidance_scale=...)` loads another setting, and with `per_sample=True` every sample follows its own.  The graph's
+first node clears the running average, so every replay is a new run.  Without the keyword a wrapper under it is refused, as before.
 """
 
 from __future__ import annotations
@@ -81,8 +89,9 @@ class CapturedLoop:
 
     def __init__(self, graph: torch.cuda.CUDAGraph, static_in: torch.Tensor, static_out: torch.Tensor, seeds_dev: torch.Tensor | None, rows=None, runner=None,
                  static_times: torch.Tensor | None = None, sample_times: torch.Tensor | None = None, inpaint: tuple | None = None,
-                 guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False, thresholded: bool = False):
+                 guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False, thresholded: bool = False, projected: bool = False):
         self.thresholded = thresholded  # captured with thresholded=True: retarget takes thresholding wrappers, and only those
+        self.projected = projected  # captured with projected=True: retarget takes wrappers under set_projected_guidance, and only those
         self.guidance_scale = guidance_scale  # the scale the loop was captured with, or None: a loop captured without guidance
         # the phi the loop was captured with, and whether it is a row value (captured with rescaled=True) that retarget may replace
         self.guidance_rescale, self.rescaled = guidance_rescale, rescaled
@@ -145,7 +154,10 @@ class CapturedLoop:
         A loop captured with in-painting takes a wrapper that has `set_inpaint(...)` in force itself (the dry run steps on one-sample
         views of ITS tensors); only its scalars reach the graph, which goes on reading `loop.inpaint`.
         A loop captured with `thresholded=True` takes a wrapper with `set_thresholding(...)` in force and loads its ratio and its
-        sample_max_value beside its schedule; both may differ from the captured ones, and a maximum <= 1 is the plain-clip row."""
+        sample_max_value beside its schedule; both may differ from the captured ones, and a maximum <= 1 is the plain-clip row.
+        A loop captured with `projected=True` takes a wrapper with `set_projected_guidance(...)` in force and loads its eta, its
+        norm_threshold and its momentum beside the scale and the schedule; the dry run advances the new wrapper's own running average,
+        never the loop's."""
         from . import _hip
 
         if self.rows is None:
@@ -153,6 +165,8 @@ class CapturedLoop:
         if self.thresholded and getattr(wrapper, "_thresholding_next", None) is None:
             raise ValueError("this loop was captured with thresholded=True: retarget takes a wrapper with set_thresholding(ratio, sample_max_value) in force "
                              "(a sample_max_value <= 1 is the plain clip)")
+        if self.projected and getattr(wrapper, "_projection_next", None) is None:
+            raise ValueError("this loop was captured with projected=True: retarget takes a wrapper with set_projected_guidance(eta, norm_threshold, momentum) in force")
         if not 0 <= slot < self.rows.slots:
             raise ValueError(f"slot {slot} outside 0..{self.rows.slots - 1}")
         if guidance_scale is not None and self.guidance_scale is None:
@@ -285,7 +299,8 @@ class CapturedLoops:
 
 def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], example: torch.Tensor, steps: int, seeds: Sequence[int] | None = None, warmup: int = 2,
                           indexed: bool = False, slots: int = 4, device_timesteps: bool | None = None, per_sample: bool = False,
-                          guidance_scale: float | None = None, rescaled: bool = False, thresholded: bool = False, guidance_rescale: float = 0.0) -> CapturedLoop:
+                          guidance_scale: float | None = None, rescaled: bool = False, thresholded: bool = False, projected: bool = False,
+                          guidance_rescale: float = 0.0) -> CapturedLoop:
     """Capture `for t in wrapper.timesteps: x = wrapper.step(model(x, t), t, x)` for `steps` steps.
 
     `wrapper` is any scheduler wrapper of skrample_amd.diffusers; `model(x, t)` must be capturable (pure device
@@ -342,13 +357,35 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
     compute scale other than None / float64, no autograd.  `step_guided` under thresholding is refused in an indexed capture (its
     guidance-only launch has no row form); `set_inpaint` beside thresholding is refused by the wrapper itself.  A wrapper without
     thresholding is a ValueError.
+
+    `projected` (a keyword, like `thresholded`; needs `guidance_scale`; off by default, and then a wrapper with `set_projected_guidance`
+    in force is refused, as before): the wrapper's adaptive projected guidance is captured.  With `indexed=False` the statistic and the
+    projected step are recorded as the eager `step_guided` issues them, the scale, eta, the norm threshold and the momentum frozen into the
+    graph; every sampler the eager route serves is served.  With `indexed=True` the four are row values (`loop.retarget(wrapper, slot,
+    guidance_scale=...)` loads another wrapper's setting and another scale; per sample with `per_sample=True`): every step is the
+    statistics row launch and the row step on one running average, one coefficient tensor `[2 * batch]` and one workspace the loop owns.
+    The row kernels must cover the launches: a sampler whose step is one single-output launch (Euler, DPM 1-3, Adams, UniP), contiguous
+    latents in samples of whole 2048-element chunks, one 16- or 32-bit dtype; UniPC, SPC, `compute_scale=None` / `float64` and ragged
+    samples are refused during the recording pass, before the stream captures.  Either way the graph's first node clears the running
+    average, as a new eager run does.  It stands beside neither `rescaled`, `thresholded`, a non-zero `guidance_rescale` nor in-painting;
+    a wrapper without projected guidance is a ValueError.
     """
     if per_sample and not indexed:
         raise ValueError("per_sample=True needs indexed=True: only device-resident rows can differ by sample")
-    if getattr(wrapper, "_projection_next", None) is not None or getattr(wrapper, "_projection", None) is not None:
+    projecting = getattr(wrapper, "_projection_next", None) is not None
+    if not projected and (projecting or getattr(wrapper, "_projection", None) is not None):
         from . import _hip
 
-        raise _hip.SkrampleHipError(_hip.PROJECTED_NO_HOOK)  # (three dot products per step: two launches without a row form)
+        raise _hip.SkrampleHipError(_hip.PROJECTED_NO_HOOK)  # (three dot products per step: two launches, captured on request only)
+    if projected:
+        if guidance_scale is None:
+            raise ValueError("projected=True belongs to a guided loop: pass guidance_scale= as well")
+        if rescaled or thresholded or guidance_rescale != 0.0:
+            raise ValueError("projected=True stands beside neither rescaled, thresholded nor a non-zero guidance_rescale: a row's convert_k holds one feature's scalars")
+        if not projecting:
+            raise ValueError("projected=True captures a wrapper's projected guidance: call wrapper.set_projected_guidance(eta, norm_threshold, momentum) first")
+        if getattr(wrapper, "_inpaint", None) is not None:
+            raise ValueError("projected=True beside in-painting (set_inpaint) is not covered; clear one of them")
     thresholding = getattr(wrapper, "_thresholding_next", None) is not None
     if not thresholded and (thresholding or getattr(wrapper, "_thresholding", None) is not None):
         from . import _hip
@@ -366,14 +403,15 @@ def capture_sampling_loop(wrapper, model: Callable[[torch.Tensor, torch.Tensor],
 
     _noise._private_vectors[0] += 1  # the loop's seed vector is overwritten in place by replays with new seeds: it is this loop's alone
     try:
-        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale, rescaled, thresholded)
+        return _capture(wrapper, model, example, steps, seeds, warmup, indexed, slots, device_timesteps, per_sample, guidance_scale, guidance_rescale, rescaled, thresholded, projected)
     finally:
         _noise._private_vectors[0] -= 1
 
 
 def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: int, indexed: bool, slots: int, device_timesteps, per_sample: bool = False,
-             guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False, thresholded: bool = False) -> CapturedLoop:
+             guidance_scale: float | None = None, guidance_rescale: float = 0.0, rescaled: bool = False, thresholded: bool = False, projected: bool = False) -> CapturedLoop:
     dev = example.device
+    rows = None
     static_in = example.clone()
     gen = list(seeds) if seeds is not None else None
     if device_timesteps is None:
@@ -400,6 +438,11 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
 
     def run(x):
         wrapper.reset_run()  # same schedule, same device seed vector; history and draw counter rewound
+        if projected:  # a new run: the running average starts from zero -- the hook's while it emits, the wrapper's own otherwise.  A fill
+            # kernel, never a memset node: under capture it is the graph's first node
+            held = rows.momentum_buf if rows is not None and rows.mode == "emit" else wrapper._projection.momentum_buf
+            if held is not None:
+                held.fill_(0)
         for t, tm in zip(times, model_times):
             x = step_of(wrapper, x, t, tm, gen, guidance_scale)
         return x
@@ -432,12 +475,11 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     if hasattr(wrapper, "noise_quiesced"):
         wrapper.noise_quiesced()  # the warm-up may have drawn noise ahead on the wrapper's side stream; the device is idle now
 
-    rows = None
     if indexed:
         from . import _hip
 
         rows = _hip.IndexedRows(dev, slots=slots, batch=int(example.shape[0]) if per_sample else None, guided=guidance_scale is not None,
-                                rescaled=rescaled, samples=int(example.shape[0]), thresholded=thresholded)  # (samples: the factor's and the scale's size, and the sample size of a ragged launch without noise)
+                                rescaled=rescaled, samples=int(example.shape[0]), thresholded=thresholded, projected=projected)  # (samples: the factor's and the scale's size, and the sample size of a ragged launch without noise)
         _hip.indexed = rows
         try:
             rows.begin("record")
@@ -460,4 +502,4 @@ def _capture(wrapper, model, example: torch.Tensor, steps: int, seeds, warmup: i
     from .pytorch.noise import forget_seed_vector
 
     forget_seed_vector(seeds_dev)  # the graph reads this very buffer and replays may overwrite it: no other run may share it from now on
-    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale, guidance_rescale, rescaled, thresholded)
+    return CapturedLoop(graph, static_in, static_out, seeds_dev, rows, run_other, static_times, sample_times, getattr(wrapper, "_inpaint", None), guidance_scale, guidance_rescale, rescaled, thresholded, projected)

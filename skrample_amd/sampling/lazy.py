@@ -198,6 +198,10 @@ class Projection:
             guidance._coef_done = (self.coef, diff)
         return guidance._coef_done
 
+    def setting(self, guidance: "Guidance") -> tuple:
+        "(guidance scale, eta, norm_threshold, momentum): what a projected row carries (_hip.IndexedRows.launch_projected)"
+        return (guidance.scale, self.eta, self.norm_threshold, self.momentum)
+
 
 class Guidance:
     """The classifier-free-guidance prediction  uncond + scale * (cond - uncond)  as ONE leaf of a step's form: its value is torch's --
@@ -920,7 +924,7 @@ def guide_only(guidance: Guidance) -> torch.Tensor:
     if projection is not None:  # the statistic, then the guidance-only form of the projected step
         plan.acc_f64 = 0
         coef, diff = projection.device_coef(guidance, u, c)
-        _hip.launch_projected_guided_step(plan, [u], None, c, out, 0, coef, diff, numel // guidance.shape[0], None, numel, guidance.device)
+        _hip.launch_projected_guided_step(plan, [u], None, c, out, 0, coef, diff, numel // guidance.shape[0], None, numel, guidance.device, projection.setting(guidance))
     elif guidance.rescale != 0.0:  # the statistic over the same storage order, then the rescaled guidance-only launch
         _hip.launch_step_guided_rescaled(plan, [u], None, c, out, guidance.scale, 0, guidance.device_factor(u, c), guidance.rescale, numel // guidance.shape[0], None, numel, guidance.device)
     else:
@@ -964,7 +968,8 @@ def evaluate_guided(form: Lin, guidance: Guidance, dtype: torch.dtype | None = N
             numel = math.prod(f.shape)
             if guidance.projection is not None:  # the statistics launch, then the step with its two per-sample coefficients
                 coef, diff = guidance.projection.device_coef(guidance, u, c)
-                _hip.launch_projected_guided_step(plan, operands, final, c, guided, slot, coef, diff, numel // f.shape[0], seeds, numel, guidance.device)
+                _hip.launch_projected_guided_step(plan, operands, final, c, guided, slot, coef, diff, numel // f.shape[0], seeds, numel, guidance.device,
+                                                  guidance.projection.setting(guidance))
             elif guidance.rescale != 0.0:  # the statistics launch, then the step with its per-sample factor
                 _hip.launch_step_guided_rescaled(plan, operands, final, c, guided, guidance.scale, slot, guidance.device_factor(u, c), guidance.rescale, numel // f.shape[0],
                                                  seeds, numel, guidance.device)

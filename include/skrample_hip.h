@@ -920,6 +920,48 @@ int skr_projected_guided_step_launch_indexed_per_sample(const skr_step_plan* pla
                                                         const int32_t* sample_index_dev, int32_t row_offset, void* stream);
 
 /*
+ * Projected guidance in a rolling batch (rolling.RollingBatch(..., guided=True, projected=True)): the two per-sample launches above for
+ * the slots of a batch whose requests arrive and leave one by one.  The row of slot s is rows_dev[sample_index_dev[s] + row_offset]; a
+ * NEGATIVE index entry, tested before row_offset is added, marks an inactive slot.  A projected rolling row is the captured-loop projected
+ * row -- coef0[K], zeta0, stream0, convert_k[0..3] = g, eta, r, beta -- with one more field:
+ *     stream1 != 0   the row on which this request's running average STARTS (its first step).  No single-output launch reads stream1
+ *                    otherwise; chain and zeta1 stay what the traced plan holds and are not read.
+ * A slot's slice of the momentum buffer is the slot's state, and the slot is reused by the next request, whose average must start from
+ * zero.  Nothing is zeroed at admission: on a starting row the statistic does not load m, takes it as +0.0f and still carries out the
+ * three rounded operations d = rn_T((c - u) + beta_f32 * (+0)), so that the slice's stale bytes -- NaN patterns included -- reach no
+ * output bit and a difference of -0 is stored as the +0 the lone run stores from its zeroed buffer.
+ *
+ * Contract.  For every ACTIVE slot s, the buffer's elements of s, coef_dev[2 s .. 2 s + 1], stats_dev[3 s .. 3 s + 2], out and guided_out
+ * have, bit for bit, what skr_projected_guidance_coef followed by skr_projected_guided_step_launch write for that sample ALONE with the
+ * row's values, momentum_buf / diff given exactly when beta != 0 (a zeroed buffer on a starting row), and the plan holding exactly the
+ * operands whose coef0 is not zero (and the one at guide->slot).  For every INACTIVE slot no byte of the momentum buffer, coef_dev,
+ * stats_dev, partials_dev, out or guided_out is read or written.
+ *
+ * skr_projected_guidance_coef_rolling.  Stage 1, one workgroup per 2048-element span: the index entry is one scalar load; a negative one
+ * ends the workgroup before any vector-memory instruction and before the LDS reduction.  Three workgroup-uniform cases follow by the
+ * row's beta and stream1: a zero-momentum row (beta == +-0) neither reads nor writes the buffer; a momentum row that does not start loads
+ * m and stores d over it; a momentum row that starts stores d without loading m.  Stage 2, one wave per slot: an inactive slot returns
+ * before reading partials.  Sums, their order, the partials layout (SKR_PROJECTED_PARTIALS at capacity) and the coefficient arithmetic are
+ * the direct entry's.  Arguments, checks and codes are those of skr_projected_guidance_coef_indexed_per_sample.
+ *
+ * skr_projected_guided_step_launch_rolling.  The row stands in FRONT of the loads: coef0[0 .. K) is known before any operand load, and an
+ * operand whose coef0 is zero (either sign) is neither loaded nor summed -- an absent ramp-up term, whose history ring may hold another
+ * request's bytes.  The operand at guide->slot is always loaded, from proj->diff on a momentum row (the statistic has just stored d there,
+ * on a starting row too) and from inputs[slot] on a zero-momentum row: one of the two, chosen before the load.  cond is always loaded.  A
+ * row whose zeta0 narrows to zero skips the draw; the seed is seeds_dev[s], the block numbers are local to the sample.  Covered: what
+ * skr_projected_guided_step_launch_indexed_per_sample covers; arguments, checks and codes are that entry's.
+ * Both allocate nothing and never synchronise: capturable.
+ */
+int skr_projected_guidance_coef_rolling(const void* uncond, const void* cond, void* momentum_buf /* T[numel], in / out */, int32_t dtype, int64_t numel,
+                                        int64_t sample_numel, const skr_step_row* rows_dev, const int32_t* sample_index_dev /* device int32[numel / sample_numel] */,
+                                        int32_t row_offset, float* coef_dev /* [2 * slots] */, double* stats_dev /* [3 * slots]; may be NULL */,
+                                        double* partials_dev /* [SKR_PROJECTED_PARTIALS(numel, sample_numel)] */, void* stream);
+
+int skr_projected_guided_step_launch_rolling(const skr_step_plan* plan, const void* const* inputs, void* out, const skr_step_guidance* guide,
+                                             const skr_step_projection* proj, const uint64_t* seeds_dev, int64_t numel, const skr_step_row* rows_dev,
+                                             const int32_t* sample_index_dev, int32_t row_offset, void* stream);
+
+/*
  * Rescaled guidance in a rolling batch: the two launches above with every per-request scalar taken from the sample's row,
  * rows_dev[sample_index_dev[s] + row_offset] -- convert_k[0] the guidance scale (as in skr_step_launch_guided_rolling), convert_k[1]
  * phi = guidance_rescale (skr_step_launch_guided_rolling does not read it).  convert_k[2..3], coef1, chain, zeta1 and stream1 are not

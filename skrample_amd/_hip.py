@@ -60,6 +60,8 @@ EXPORTS = (
     "skr_projected_guidance_coef_indexed_per_sample",
     "skr_projected_guided_step_launch_indexed",
     "skr_projected_guided_step_launch_indexed_per_sample",
+    "skr_projected_guidance_coef_rolling",
+    "skr_projected_guided_step_launch_rolling",
     "skr_threshold_scale_indexed",
     "skr_threshold_scale_indexed_per_sample",
     "skr_thresholded_step_launch_indexed",
@@ -855,7 +857,7 @@ def load() -> ctypes.CDLL:
         lib.skr_projected_guidance_coef.restype = ctypes.c_int
         lib.skr_projected_guided_step_launch.argtypes = [ctypes.POINTER(StepPlanC), ctypes.POINTER(vp), vp, ctypes.POINTER(StepGuidanceC), ctypes.POINTER(StepProjectionC), vp, i64, vp]
         lib.skr_projected_guided_step_launch.restype = ctypes.c_int
-        for suffix in ("_indexed", "_indexed_per_sample"):  # (their row forms: the four doubles and the plan's scalars are row values, the table where the thresholded row entries have it)
+        for suffix in ("_indexed", "_indexed_per_sample", "_rolling"):  # (their row forms: the four doubles and the plan's scalars are row values, the table where the thresholded row entries have it)
             entry = getattr(lib, "skr_projected_guidance_coef" + suffix)
             entry.argtypes, entry.restype = [vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp], ctypes.c_int
             entry = getattr(lib, "skr_projected_guided_step_launch" + suffix)
@@ -1217,8 +1219,31 @@ def launch_guided_step_thresholded(plan: StepPlanC, operands: list[torch.Tensor]
     check(status, "skr_guided_thresholded_step_launch")
 
 
-PROJECTED_NO_HOOK = ("adaptive projected guidance (set_projected_guidance) has no row form in a loop captured without it: pass projected=True to capture_sampling_loop (the "
-                     "guidance scale, eta, the norm threshold and the momentum are then row values); RollingBatch does not take a wrapper under it")
+PROJECTED_NO_HOOK = ("adaptive projected guidance (set_projected_guidance) has no row form in a loop captured or a batch built without it: pass projected=True to "
+                     "capture_sampling_loop, or guided=True, projected=True to RollingBatch (the guidance scale, eta, the norm threshold and the momentum are then row values)")
+PROJECTED_ROLLING = ("skr_projected_guidance_coef_rolling", "skr_projected_guided_step_launch_rolling")  # a projected rolling tick: the statistic, then the step
+
+
+def launch_projected_coef_rolling(lib, uncond: int, cond: int, momentum_buf: int, dtype: int, numel: int, sample_numel: int, rows: int, index: int, row_offset: int, coef: int,
+                                  partials: int, stream: int) -> None:
+    """the statistics launch of a projected rolling tick (skr_projected_guidance_coef_rolling), on addresses: every active slot gets its two
+    coefficients and, on a momentum row, its slice of `momentum_buf` advanced (started without being read where the row's stream1 says
+    so); free and finished slots keep every byte.  Recorded into an installed `_hip.trace` list as (entry name, arguments)."""
+    args = (uncond, cond, momentum_buf, dtype, numel, sample_numel, rows, index, row_offset, coef, None, partials, stream)
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((PROJECTED_ROLLING[0], args))
+    check(lib.skr_projected_guidance_coef_rolling(*args), PROJECTED_ROLLING[0])
+
+
+def launch_projected_step_rolling(lib, plan: StepPlanC, arr, out: int, guide: "StepGuidanceC", proj: "StepProjectionC", seeds: "int | None", numel: int, rows: int, index: int,
+                                  row_offset: int, stream: int) -> None:
+    "the step launch of a projected rolling tick (skr_projected_guided_step_launch_rolling), behind the statistics launch, with the same index, rows and row offset"
+    trace = getattr(_hooks, "trace", None)
+    if trace is not None:
+        trace.append((PROJECTED_ROLLING[1], (plan, arr, out, guide, proj, seeds, numel, rows, index, row_offset, stream)))
+    check(lib.skr_projected_guided_step_launch_rolling(ctypes.byref(plan), arr, out, ctypes.byref(guide), ctypes.byref(proj), seeds, numel, rows, index, row_offset, stream),
+          PROJECTED_ROLLING[1])
 
 
 def _projected_hook() -> "IndexedRows | None":

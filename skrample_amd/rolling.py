@@ -134,6 +134,31 @@ without thresholding is refused at `admit()`.  Refused when the batch is built, 
 and SPC (two launches over a stored prediction), `guided`, `inpaint_mask_shape`, Offset / Pyramid noise, `compute_scale=None`, fp64,
 ragged samples and the Runge-Kutta wrappers.
 
+Adaptive projected guidance (`guided=True, projected=True`): requests whose wrappers have `set_projected_guidance(eta, norm_threshold,
+momentum)` in force, each with its own setting, its own guidance scale or schedule and its own running average of the guidance difference:
+
+    batch = RollingBatch(make_wrapper, example, capacity=B, guided=True, projected=True)   # make_wrapper() has set_projected_guidance too
+    batch.admit(slot, latents, wrapper, steps, seed=None, guidance_scale=7.5)               # the wrapper's own (eta, norm_threshold, momentum)
+    done = batch.step_guided(uncond, cond)
+
+The row of a request's step carries g, eta, r and beta in `convert_k[0..3]`, as in captured loops, and one more field: `stream1 = 1` on the
+request's FIRST row when beta is not zero (no single-output launch reads `stream1` otherwise).  The running average is per-request state
+that lives in the slot -- the slot's slice of `momentum_buf`, `[capacity, *unit_shape]` in the latents' dtype -- and the slot is reused by
+the next request, whose average must start from zero.  Nothing is zeroed at `admit()` (an admission between ticks costs no device work
+beyond its row upload): on a row with `stream1 != 0` the statistic takes the average as +0.0 WITHOUT loading the slice, carries out the same
+three rounded operations and stores the new difference, so whatever the previous occupant left there, NaN patterns included, reaches no
+output bit.  A tick is two launches on the current stream with the same index, rows and row offset: `skr_projected_guidance_coef_rolling`
+(csrc/skr_projected_rolling.hip) advances every active momentum slot's average and writes every active slot's two coefficients into `coef`,
+float32[2 capacity], through partial sums sized for the capacity; then `skr_projected_guided_step_launch_rolling`
+(csrc/skr_step_projected_rolling.hip) forms every active slot's projected prediction -- from the stored difference on a momentum row, from
+`uncond` on a zero-momentum row --, steps with it and stores it into the ring of guided predictions.  Free and finished slots touch no
+memory.  Every request has the bits of its lone eager `step_guided` run under its own `set_projected_guidance`.  Ring upkeep, `guided_out`
+(NULL for Euler), "nothing of the caller is held", `advance()`, `device_positions=True` and `capture(model)` (`CapturedTicks.tick()`: one
+replay plus the two eager launches) are a guided batch's.  Without the keyword a wrapper under projected guidance is refused, at
+construction and at `admit()`; with it a wrapper without is refused at `admit()`.  Refused when the batch is built, each by name, before
+anything is allocated: `projected` without `guided`; beside `rescaled`, `thresholded` or `inpaint_mask_shape`; ragged samples; UniPC and
+SPC; `compute_scale=None`; fp64; Offset / Pyramid noise.  Not covered: changing a resident request's setting mid-run.
+
 Sample sizes.  A unit (`example.shape[1:]`) of whole 2048-element chunks joins any batch.  A ragged unit -- at least 2048 elements and a
 multiple of 8, not whole chunks: (4,144,112) and most other non-square SDXL latent buckets -- joins a plain batch: not `guided`, no
 `inpaint_mask_shape`, `Random` noise or none, and a sampler whose step is one single-output launch (Euler, DPM 1-3, Adams, UniP).  The
@@ -256,16 +281,26 @@ class RollingBatch:
     `rescaled` (with `guided`): True makes that tick two launches -- `skr_guidance_rescale_factor_rolling`, then
     `skr_step_launch_guided_rescaled_rolling` -- with every request's own `guidance_rescale` beside its scale (module docstring).
     `thresholded`: True batches wrappers with `set_thresholding` in force, each under its own (ratio, sample_max_value): a tick is
-    `skr_threshold_scale_rolling`, then `skr_thresholded_step_launch_rolling` (module docstring)."""
+    `skr_threshold_scale_rolling`, then `skr_thresholded_step_launch_rolling` (module docstring).
+    `projected` (with `guided`): True batches wrappers with `set_projected_guidance` in force, each under its own (eta, norm_threshold,
+    momentum) and its own running average, kept in its slot: a tick is `skr_projected_guidance_coef_rolling`, then
+    `skr_projected_guided_step_launch_rolling` (module docstring)."""
 
     def __init__(self, make_wrapper: Callable[[], object], example: torch.Tensor, capacity: int, max_steps: int = 128, alias_history: bool = True,
-                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False, rescaled: bool = False, thresholded: bool = False):  # fmt: skip
+                 device_positions: bool = False, inpaint_mask_shape: Sequence[int] | None = None, guided: bool = False, rescaled: bool = False, thresholded: bool = False,
+                 projected: bool = False):  # fmt: skip
         if capacity < 1:
             raise ValueError("a rolling batch has at least one slot")
         self.masked = inpaint_mask_shape is not None
         self.guided = bool(guided)
         self.rescaled = bool(rescaled)
         self.thresholded = bool(thresholded)
+        self.projected = bool(projected)
+        if self.projected and not self.guided:
+            raise ValueError("projected=True needs guided=True: projected guidance replaces the guided prediction a guided batch forms from step_guided(uncond, cond)")
+        if self.projected and (self.rescaled or self.thresholded or self.masked):
+            beside = "rescaled" if self.rescaled else "thresholded" if self.thresholded else "inpaint_mask_shape"
+            raise ValueError(f"projected together with {beside}: a row's convert_k holds one feature's scalars (projected guidance beside rescale, thresholding or in-painting is not covered)")
         if self.rescaled and not self.guided:
             raise ValueError("rescaled=True needs guided=True: guidance_rescale is applied to the guided prediction a guided batch forms")
         if self.guided and self.masked:
@@ -286,7 +321,9 @@ class RollingBatch:
                              f"(ragged samples are served from {PER_SAMPLE_CHUNK} elements on, in multiples of 8)")
         self.numel = self.capacity * self.sample_numel
         first = make_wrapper()
-        if getattr(first, "_projection_next", None) is not None or getattr(first, "_projection", None) is not None:
+        if self.projected:
+            self._refuse_projected(first)
+        elif getattr(first, "_projection_next", None) is not None or getattr(first, "_projection", None) is not None:
             raise SkrampleHipError(_hip.PROJECTED_NO_HOOK)  # (before anything is allocated)
         if self.thresholded:
             self._refuse_thresholded(first)
@@ -329,6 +366,13 @@ class RollingBatch:
         if self.thresholded:
             self.scale = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
             self._threshold_ws = torch.zeros(_hip.threshold_workspace(self.numel, self.sample_numel), dtype=torch.uint8, device=self.device)
+        if self.projected:
+            # a projected batch: every slot's running average of the guidance difference (the slot's slice is the request's state: a request's
+            # first momentum row starts it without reading it, so nothing here is zeroed per admission), every slot's two coefficients and the
+            # statistic's partial sums for `capacity` samples; allocated once, the same in every phase of CapturedTicks
+            self.momentum_buf = torch.zeros(shape, dtype=self.dtype, device=self.device)
+            self.coef = torch.zeros(2 * self.capacity, dtype=torch.float32, device=self.device)
+            self._projected_partials = torch.zeros(max(_hip.projected_partials(self.numel, self.sample_numel), 1), dtype=torch.float64, device=self.device)
         if self.rescaled:
             # a rescaled batch: every slot's factor std(cond) / std(p) and the partial sums behind it, written by the tick's statistics
             # launch and read by its step launch; allocated once, the same in every phase of CapturedTicks
@@ -413,6 +457,26 @@ class RollingBatch:
             raise ValueError(f"guided together with {first.noise_type.__name__} noise: a guided rolling batch draws Random noise or none (structured noise is not covered)")
         if self.dtype not in (torch.bfloat16, torch.float16, torch.float32):
             raise SkrampleHipError(f"guided rows need one 16- or 32-bit dtype for operands, cond and both outputs, not {self.dtype}")
+
+    def _refuse_projected(self, first) -> None:
+        "a projected batch: what its two launches per tick do not cover, refused by name before anything is allocated or traced"
+        from .pytorch import noise as generators
+        from .sampling import structured as sampling
+
+        if self.ragged:
+            raise ValueError(f"projected together with ragged samples ({self.sample_numel} elements, not whole {PER_SAMPLE_CHUNK}-element chunks): the projected row kernels need samples of whole chunks")
+        if getattr(first, "_projection_next", None) is None:
+            raise ValueError("projected=True batches wrappers with projected guidance: make_wrapper() must return one with set_projected_guidance(eta, norm_threshold, momentum) in force")
+        sampler = first.sampler
+        if type(sampler).sample_packed is not sampling.StatedSampler.sample_packed:
+            raise SkrampleHipError(f"a projected step of {type(sampler).__name__} is the guidance-only launch and then its two-output step, and the guidance-only launch has no "
+                                   "row form: a projected rolling batch takes Euler, DPM 1-3, Adams 2-4 and UniP 2-3")  # fmt: skip
+        if first.compute_scale is None:
+            raise SkrampleHipError("a projected step under compute_scale=None takes the guidance-only launch, which has no row form: a projected rolling batch needs a compute scale")
+        if self.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise SkrampleHipError(f"projected rows take bf16, fp16 or fp32 tensors, not fp64 ({self.dtype})")
+        if bool(sampler.require_noise) and first.noise_type in (generators.Offset, generators.Pyramid):
+            raise ValueError(f"projected together with {first.noise_type.__name__} noise: a projected rolling batch draws Random noise or none (structured noise is not covered)")
 
     def _refuse_thresholded(self, first) -> None:
         "a thresholded batch: what its two launches per tick do not cover, refused by name before anything is allocated or traced"
@@ -517,7 +581,9 @@ class RollingBatch:
             if len(launches) != 1:
                 raise SkrampleHipError(f"a step of this wrapper is {len(launches)} launches, not one fused launch: it cannot join a rolling batch")
             call = launches[0]
-            if self.guided and call.kind != "guided":
+            if self.projected and call.kind != "guided_projected":
+                raise SkrampleHipError("a projected step of this wrapper is not one projected guided step launch: it cannot join a projected rolling batch")
+            if self.guided and not self.projected and call.kind != "guided":
                 raise SkrampleHipError("a guided step of this wrapper is not one fused guided launch: it cannot join a guided rolling batch")
             if (call.kind == "masked") != (inpaint is not None):
                 raise SkrampleHipError("a step of this wrapper is not the masked launch its in-painting asks for" if inpaint is not None else "a step of this wrapper is a masked launch although no in-painting is set")
@@ -547,7 +613,7 @@ class RollingBatch:
         tick's launches -- the statistics launch of a rescaled batch, then the step launch.  Everything else in them is the batch's own --
         plan, descriptors, and the addresses of rows_dev, index_dev, seeds_dev, factor and _partials, which are allocated in __init__ and
         never reassigned."""
-        if self.thresholded:  # (two entries outside the launch table: _launch_thresholded)
+        if self.thresholded or self.projected:  # (two entries outside the launch table: _launch_thresholded, _launch_projected)
             return []
         kind = "guided_rescaled" if self.rescaled else "guided" if self.guided else "masked" if self.masked else "plain"
         # structured noise is an operand, drawn by a launch of its own: no seeds (masked and guided batches refuse structured noise when built)
@@ -568,6 +634,8 @@ class RollingBatch:
     def _launch(self, arr, out0: torch.Tensor | None, out1: torch.Tensor | None, cond: torch.Tensor | None = None, guided_out: torch.Tensor | None = None) -> None:
         """the tick's step launch through the rolling form of the launch table (_hip.ENTRIES); a rescaled batch: behind the statistics
         launch, on the same stream.  Only what changes from tick to tick is filled in."""
+        if self.projected:
+            return self._launch_projected(arr, out0, cond, guided_out)
         lib, stream = _hip.load(), _hip.current_stream_ptr(self.device)
         given = {"operands": arr, "out0": _hip._ptr(out0), "out1": _hip._ptr(out1), "stream": stream}
         if self.guided:  # (one output; `cond` and `guided_out` -- None: not stored -- are launch arguments, the scale each slot's row value)
@@ -592,6 +660,20 @@ class RollingBatch:
         thr = StepThresholdC(self.scale.data_ptr(), _hip._ptr(x0_out), 0.0, 0.0, self.sample_numel, self.slot, self.xslot, 0)  # (a and b are the rows')
         seeds = self.seeds_dev.data_ptr() if self.draws_noise else None
         _hip.launch_step_thresholded_rolling(lib, self.plan, arr, out.data_ptr(), thr, seeds, self.numel, *table, stream)
+
+    def _launch_projected(self, arr, out: torch.Tensor, cond: torch.Tensor, guided_out: torch.Tensor | None) -> None:
+        """the two launches of a projected tick, on the current stream with the same index, rows and row offset: the statistic over this
+        tick's uncond and cond (skr_projected_guidance_coef_rolling) advances every active momentum slot's running average in
+        `momentum_buf` -- starting it, unread, on a request's first row -- and writes `coef`; then the step
+        (skr_projected_guided_step_launch_rolling) forms every active slot's projected prediction, steps with it and stores it into `guided_out`"""
+        lib, stream = _hip.load(), _hip.current_stream_ptr(self.device)
+        table = (self.rows_dev.data_ptr(), self.index_dev.data_ptr(), 0)
+        _hip.launch_projected_coef_rolling(lib, arr[self.slot], cond.data_ptr(), self.momentum_buf.data_ptr(), _hip.DTYPE_CODE[self.dtype], self.numel, self.sample_numel, *table,
+                                           self.coef.data_ptr(), self._projected_partials.data_ptr(), stream)  # fmt: skip
+        guide = StepGuidanceC(cond.data_ptr(), _hip._ptr(guided_out), 0.0, self.slot, 0)  # (the scale is the rows')
+        proj = _hip.StepProjectionC(self.coef.data_ptr(), self.momentum_buf.data_ptr(), self.sample_numel, 0)
+        seeds = self.seeds_dev.data_ptr() if self.draws_noise else None
+        _hip.launch_projected_step_rolling(lib, self.plan, arr, out.data_ptr(), guide, proj, seeds, self.numel, *table, stream)
 
     def _draw(self, out: torch.Tensor) -> None:
         "a structured-noise batch: ONE launch of the generator's rolling entry draws, into `out`, every slot the index on the device names"
@@ -656,9 +738,11 @@ class RollingBatch:
                 wide.convert_k[k] = 0.0
         return wide, list(roles)
 
-    def _rows_of(self, traced, scales: Sequence[float] | None = None, rescales: Sequence[float] | None = None) -> list[StepRowC]:
+    def _rows_of(self, traced, scales: Sequence[float] | None = None, rescales: Sequence[float] | None = None, setting: tuple | None = None) -> list[StepRowC]:
         """`scales` (a guided batch): the guidance scale of every step, carried in the row's convert_k[0] (a guided plan has no rounded
-        conversion); `rescales` (a rescaled batch): guidance_rescale of every step, in convert_k[1] -- zero in every other batch's rows"""
+        conversion); `rescales` (a rescaled batch): guidance_rescale of every step, in convert_k[1] -- zero in every other batch's rows;
+        `setting` (a projected batch): the request's (eta, norm_threshold, momentum), in convert_k[1..3] of every row, and `stream1 = 1`
+        on the first row of a request with momentum"""
         rows = []
         for step, (plan, roles, _) in enumerate(traced):
             if (plan.dtype_a, plan.acc_f64, plan.convert_to, plan.convert_from) != (self.plan.dtype_a, self.plan.acc_f64, self.plan.convert_to, self.plan.convert_from):
@@ -674,6 +758,10 @@ class RollingBatch:
                 row.convert_k[0] = float(scales[step])
                 if self.rescaled and rescales is not None:
                     row.convert_k[1] = float(rescales[step])
+                if self.projected:  # convert_k[1..3] = eta, r, beta of the request; stream1 marks the row its running average starts on
+                    eta, threshold, momentum = setting
+                    row.convert_k[1], row.convert_k[2], row.convert_k[3] = eta, threshold, momentum
+                    row.stream1 = 1 if step == 0 and momentum != 0.0 else 0
             if self.thresholded:  # convert_k[0..3] = a, b, ratio, maximum of the step, as IndexedRows.launch_thresholded keeps them for captured loops
                 if not _hip.one_group_launch(plan) or list(roles).count(("o",)) != 1 or list(roles).count(("x",)) > 1:
                     raise SkrampleHipError("a step of this request is not one single-output thresholded launch of the batch's dtype over one network output and one sample")
@@ -754,6 +842,13 @@ class RollingBatch:
                              "(every request brings its own setting; a maximum <= 1 is the plain clip)")
         if not self.thresholded and thresholding is not None:
             raise SkrampleHipError(_hip.THRESHOLD_NO_ROWS)
+        projection = getattr(wrapper, "_projection_next", None)
+        if self.projected and projection is None:
+            raise ValueError("this batch was built with projected=True: admit() takes a wrapper with set_projected_guidance(eta, norm_threshold, momentum) in force "
+                             "(every request brings its own setting; eta=1 without clamp or momentum is plain guidance)")
+        if not self.projected and (projection is not None or getattr(wrapper, "_projection", None) is not None):
+            raise SkrampleHipError(_hip.PROJECTED_NO_HOOK)
+        setting = (projection.eta, projection.norm_threshold, projection.momentum) if self.projected else None
         scales = None
         if self.guided:
             if guidance_scale is None:
@@ -809,7 +904,7 @@ class RollingBatch:
         traced = self._trace(wrapper, steps, seed if noisy else None)
         if len(traced) != steps:
             raise SkrampleHipError(f"the schedule issued {len(traced)} launches for {steps} steps")
-        request = _Request(self._rows_of(traced, scales, rescales) if self.guided else self._rows_of(traced), [t for _, _, t in traced])
+        request = _Request(self._rows_of(traced, scales, rescales, setting) if self.guided else self._rows_of(traced), [t for _, _, t in traced])
         upload_rows(self.rows_dev, slot * self.max_steps, request.rows)
         self._x[-1][slot].copy_(latents.reshape(self.unit_shape))
         if noisy:

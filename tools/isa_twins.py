@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""VGPRs, scratch and waves per SIMD of every thresholded_rolling_kernel_v1 beside its PerSample twin (no GPU needed).
+"""VGPRs, scratch and waves per SIMD of every *_rolling_kernel_v1 beside its PerSample twin (no GPU needed).
 
     python tools/isa_twins.py WORK/new/skr_step_thresholded_rows.hip.s
+    python tools/isa_twins.py WORK/new/skr_step_projected_rolling.hip.s WORK/new/skr_step_projected_rows.hip.s
 
-The argument is the device assembly that `tools/isa_compare.py OLD NEW --files skr_step_thresholded_rows.hip --work WORK` keeps.  The
-figures are the compiler's own; an instantiation below its twin's occupancy is marked."""
+The arguments are the device assembly that `tools/isa_compare.py OLD NEW --files ... --work WORK` keeps: one file where the rolling kernel
+and its twin share a translation unit, the rolling kernel's and the twin's where they do not.  The figures are the compiler's own; an
+instantiation below its twin's occupancy is marked."""
 
 import re
 import sys
@@ -15,12 +17,12 @@ DTYPE = {"NS_5f16_tE": "fp16", "NS_6bf16_tE": "bf16", "f": "fp32"}
 
 def main() -> int:
     rolling, twin = {}, {}
-    for m in KERNEL.finditer(open(sys.argv[1]).read()):
+    for m in KERNEL.finditer("\n".join(open(path).read() for path in sys.argv[1:])):
         k = re.search(r"kernel_v1I(NS_5f16_tE|NS_6bf16_tE|f)Li(\d+)ELb(\d)", m.group(1))
         if k is None:
             continue
         key = (DTYPE[k.group(1)], int(k.group(2)), int(k.group(3)))
-        if "thresholded_rolling" in m.group(1):
+        if "_rolling_kernel" in m.group(1):
             rolling[key] = m.groups()[1:]
         elif "RowFormE2" in m.group(1):  # RowForm::PerSample
             twin[key] = m.groups()[1:]
